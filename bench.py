@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: differentiable 2D P1 Poisson solves/sec (fwd + adjoint).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json metric / SURVEY 8(d) C4): FEMesh.rectangle(1024, 1024), 256 samples
 per GPU, one scalar kappa_b ~ U(0.5, 2.0) per sample (seed 4096 + rank), f == 1,
@@ -14,13 +14,16 @@ from the environment; a plain `python bench.py --gpus N` starts the N rank proce
 before this process touches the GPU) and relays rank 0's JSON line.  The batch is sharded (weak scaling:
 256 per GPU) through `diffhe.distributed.ShardedBatchSolve`; the headline's only collective is the fused loss
 all-reduce (per-sample kappa needs no gradient reduction).  `variants.shared_kappa_allreduce` -- reported at
-EVERY N -- is the same workload with ONE per-element kappa field shared by the batch: its 16.8 MB gradient
-really crosses the reduce-scatter + all-gather of BASELINE config 4's "RCCL grad all-reduce".
+EVERY N under `--full` -- is the same workload with ONE per-element kappa field shared by the batch: its 16.8 MB
+gradient really crosses the reduce-scatter + all-gather of BASELINE config 4's "RCCL grad all-reduce".
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` for the
-dominant kernel (+ the step-level figure), `cpu_baseline` (CPU restatements of the reference path timed on
-the host cores, rank 0, N = 1), parity against the oracle, and `variants`: the other BASELINE configs
-(2: 1D 10^4 x 1024, 3: 512^2 x 256, 5: kappa recovery by Adam) and the secondary forms of the headline workload.
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step) and
+the solver's own record of the timed steps.  A plain run does only that: set-up, warm-up, the timed steps, the
+outputs of the last one if `--dump-outputs DIR` is given, the line.  With `--full` the same line also carries
+`roofline` for the dominant kernel (+ the step-level figure), `cpu_baseline` (CPU restatements of the reference
+path timed on the host cores, rank 0, N = 1), parity against the oracle, and `variants`: the other BASELINE configs
+(2: 1D 10^4 x 1024, 3: 512^2 x 256, 5: kappa recovery by Adam) and the secondary forms of the headline workload;
+without `--full` those entries are null.
 """
 import argparse
 import json
@@ -37,6 +40,8 @@ sys.path.insert(0, os.path.join(ROOT, "difffe-physics-lab_amd"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 PMC_PROFILE = "r04_pmc_traffic.json"   # profiles/: rocprofv3 --pmc passes over this command, reduced by tools/pmc_reduce.py
+DUMP_LIMIT_BYTES = 48 << 20            # --dump-outputs: all files together
+DUMP_SEED = 0                          # --dump-outputs: the sample of an array above its share is drawn with this seed
 
 
 def parse(argv=None):
@@ -66,7 +71,20 @@ def parse(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: exercise launch, rendezvous, barriers and the max-over-ranks timing only "
                          "(value is null); used by the CPU tests of the multi-rank launch path")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: in-solver kernel timing and "
+                         "`roofline`, `cpu_baseline` and `parity_vs_oracle`, `variants` (other configurations, precisions "
+                         "and layouts).  --no-cpu-baseline, --no-variants, --only-variant, --kernel-reps and "
+                         "--variant-reps shape this part; without --full none of it runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned -- loss, dL/dkappa, nodal values "
+                         "u, each in the caller's layout -- as DIR/<name>.npy (float64); an array above its share of "
+                         f"{DUMP_LIMIT_BYTES >> 20} MB is a fixed, seeded sample along its longest axis, whose indices "
+                         "go to DIR/<name>_index.npy.  With N > 1: rank 0's shard")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1 (it writes the outputs of the last timed step)")
+    return args
 
 
 def _free_port():
@@ -292,13 +310,14 @@ def main():
     import gc
     gc.collect()
     gc.freeze()
-    # main kernels timed with HIP events INSIDE the solver loop, over the timed region only;
+    # --full: main kernels timed with HIP events INSIDE the solver loop, over the timed region only;
     # algorithmic bytes of every launch of the timed steps from the library's own accounting
     prof_ms, prof_n = ctypes.c_double(0.0), ctypes.c_longlong(0)
     acc_bytes, acc_launches = ctypes.c_double(0.0), ctypes.c_longlong(0)
-    if rank == 0:
+    if rank == 0 and args.full:
         L.diffhe_lattice_pcg_profile(1, None, None)
-    L.diffhe_traffic_account(1, None, None)
+    if args.full:
+        L.diffhe_traffic_account(1, None, None)
     seg0 = torch.cuda.memory_stats(dev).get("segment.all.allocated", 0)
     marks = []
     t0 = time.perf_counter()
@@ -311,9 +330,10 @@ def main():
     step_ms = [1e3 * (b - a) for a, b in zip([t0] + marks[:-1], marks)]
     sync_all()
     elapsed = time.perf_counter() - t0
-    L.diffhe_traffic_account(1, ctypes.byref(acc_bytes), ctypes.byref(acc_launches))
-    kprof = read_kprof(L, ctypes) if rank == 0 else []
-    if rank == 0:
+    if args.full:
+        L.diffhe_traffic_account(1, ctypes.byref(acc_bytes), ctypes.byref(acc_launches))
+    kprof = read_kprof(L, ctypes) if rank == 0 and args.full else []
+    if rank == 0 and args.full:
         L.diffhe_lattice_pcg_profile(0, ctypes.byref(prof_ms), ctypes.byref(prof_n))
     rank_ms = [1e3 * own_elapsed / max(args.steps, 1)]
     if world > 1:
@@ -330,9 +350,13 @@ def main():
     lattice = solver.last_info.path == "lattice-mgpcg"
     head_info = solver.last_info
     u_main, kgrad_main = u, (kappa.grad.detach().clone() if kappa.grad is not None else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np, torch, {"loss": loss.detach().reshape(1), "dloss_dkappa": kgrad_main,
+                                                    "u": u_main.detach()})
 
     # ------------------------------------------------------------------------------------------------------------
-    # secondary measurements, same run.  Every entry: `variant_reps` repetitions after one warm call, MEDIAN reported.
+    # --full: secondary measurements, same run.  Every entry: `variant_reps` repetitions after one warm call, MEDIAN
+    # reported.
     # ------------------------------------------------------------------------------------------------------------
     def timed(fn, reps=None):
         fn()
@@ -354,7 +378,7 @@ def main():
         return statistics.median(ts), ts
 
     variants = {}
-    want = (lambda name: (not args.no_variants and args.only_variant in (None, name)))
+    want = (lambda name: (args.full and not args.no_variants and args.only_variant in (None, name)))
 
     # (A) at EVERY N: one per-element kappa field SHARED by the batch -- the (m,) gradient crosses the RCCL
     #     reduce-scatter + all-gather (BASELINE config 4: "with RCCL grad all-reduce")
@@ -445,7 +469,8 @@ def main():
                 torch.cuda.empty_cache()
 
     if rank == 0:
-        roof = roofline(args, torch, L, _hip, solver, plan, kappa, n, B, N, dev, prof_ms.value, prof_n.value, kprof)
+        roof = (roofline(args, torch, L, _hip, solver, plan, kappa, n, B, N, dev, prof_ms.value, prof_n.value, kprof)
+                if args.full else None)
         if roof is not None:
             bps = acc_bytes.value / max(args.steps, 1)
             roof["step"] = {"bytes_per_step": bps, "launches_per_step": acc_launches.value / max(args.steps, 1),
@@ -454,9 +479,9 @@ def main():
                             "definition": "algorithmic bytes of EVERY launch of the timed steps (library accounting, "
                                           "DESIGN.md section 4; the loss's own torch kernels excluded) / step time"}
         cpu = parity = None
-        if not args.no_cpu_baseline and world == 1 and args.kappa != "shared-field":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.kappa != "shared-field":
             cpu, parity = cpu_baseline_and_parity(args, np, torch, mesh, kappa, kgrad_main, u_main, B, N, node)
-        elif world == 1 and args.kappa == "sample" and N & (N - 1) == 0:
+        elif args.full and world == 1 and args.kappa == "sample" and N & (N - 1) == 0:
             parity = {"vs_exact_solution": exact_dst_parity(np, torch, mesh, kappa, kgrad_main, u_main, B, N, node)}
         it = timed_iters
         fp32 = bool(solver.mg.get("fp32")) and lattice
@@ -511,8 +536,8 @@ def main():
                                     "rounded diagonal moves the exact solution by ~cond * eps: "
                                     + (f"measured distance to the refined oracle in this run u {parity['u_rel_err']:.1e}, "
                                        f"dL/dkappa {parity['dkappa_rel_err']:.1e}" if parity and "u_rel_err" in parity
-                                       else "3e-11 in u / 8e-11 in dL/dkappa at 1024^2, see parity_vs_oracle of a run with "
-                                            "the CPU baseline")
+                                       else "3e-11 in u / 8e-11 in dL/dkappa at 1024^2, see parity_vs_oracle of a --full "
+                                            "run with the CPU baseline")
                                     + "); every sample is solved by its own PCG, no u(1)/kappa shortcut.  The general "
                                     "case -- a per-element field per sample, one matrix per sample -- is "
                                     "variants.kappa_element_field") if args.kappa == "sample" else
@@ -534,7 +559,8 @@ def main():
                               f"fp32; ALL vectors stored fp64: {v64} solves/s/GPU; per-element kappa field per sample "
                               f"(general case, one matrix per sample): {vel} solves/s/GPU") if single and variants else None,
             "roofline": roof, "cpu_baseline": cpu, "parity_vs_oracle": parity, "variants": variants or None,
-            "peak_hbm_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2),
+            "peak_hbm_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2), "full": bool(args.full),
+            "outputs_dumped_to": args.dump_outputs,
         }
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -543,6 +569,30 @@ def main():
             import shutil
             shutil.rmtree(os.environ["DIFFHE_PLAN_CACHE"], ignore_errors=True)
         dist.destroy_process_group()
+
+
+def dump_outputs(dirname, np, torch, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64, in the layout the caller received it, DUMP_LIMIT_BYTES
+    in all.  Smallest first, each array may take an equal part of what is left; one larger than that is cut to a sample
+    of whole slices along its longest axis -- indices drawn with DUMP_SEED, sorted, written to DIR/<name>_index.npy and
+    counted in its part -- so the same arguments give the same sample in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    items = sorted(((k, v) for k, v in arrays.items() if v is not None), key=lambda kv: kv[1].numel())
+    left = DUMP_LIMIT_BYTES - 1024 * 2 * len(items)          # the .npy headers
+    for i, (name, t) in enumerate(items):
+        t = t.detach().to(torch.float64)
+        share = left // (len(items) - i)
+        if 8 * t.numel() > share:
+            axis = max(range(t.dim()), key=lambda d: t.shape[d])
+            keep = max(1, share // (8 * (t.numel() // t.shape[axis] + 1)))     # + 1: the index of the slice
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.shape[axis], size=keep, replace=False))
+            t = t.index_select(axis, torch.from_numpy(idx).to(t.device))
+            np.save(os.path.join(dirname, f"{name}_index.npy"), idx.astype(np.float64))
+            left -= 8 * idx.size
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        left -= a.nbytes
+    assert left >= 0, left
 
 
 def read_kprof(L, ctypes):

@@ -456,3 +456,26 @@ def test_rank_affinity_slices_follow_the_gpu_numa_nodes():
     assert bench.rank_cpu_slice({0, 1}, 8, 5) == [0, 1]                     # fewer cores than ranks: no pinning
     assert isinstance(bench.gpu_numa_nodes(), list)
     assert bench._parse_cpulist("0-3,8,10-11\n") == {0, 1, 2, 3, 8, 10, 11}
+
+
+def test_bench_dump_outputs_stays_in_budget_and_samples_reproducibly(tmp_path):
+    """`bench.py --dump-outputs`: small arrays whole, a headline-sized u cut to a seeded sample of whole rows whose
+    indices are written next to it, everything float64 and inside the budget; the same arrays give the same files."""
+    sys.path.insert(0, ROOT)
+    import bench
+    gen = torch.Generator().manual_seed(0)
+    u = torch.randn(300_000, 64, generator=gen, dtype=torch.float64)      # 154 MB: above any share of the budget
+    g = torch.randn(64, generator=gen, dtype=torch.float64)
+    arrays = {"loss": torch.tensor([2.5], dtype=torch.float64), "dloss_dkappa": g, "u": u}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), np, torch, arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["dloss_dkappa.npy", "loss.npy", "u.npy", "u_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "dloss_dkappa.npy"), g.numpy())
+    idx = np.load(tmp_path / "a" / "u_index.npy").astype(np.int64)
+    assert len(idx) > 1000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "u.npy"), u.numpy()[idx])

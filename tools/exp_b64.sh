@@ -1,7 +1,7 @@
 #!/bin/bash
 # config-5 shape (512^2 x 64 per GPU): where a step goes, new (one-sample fused) vs old (single passes) kernels
 cd $GRAFT_REPO_ROOT
-A="--mesh 512 --batch 64 --steps 20 --warmup 3 --no-cpu-baseline --no-variants"
+A="--full --mesh 512 --batch 64 --steps 20 --warmup 3 --no-cpu-baseline --no-variants"
 for s2 in 1 0; do
   export DIFFHE_STRIP2=$s2
   python bench.py $A > gpurun_out/r4f_s$s2.json 2> gpurun_out/r4f_s$s2.err || { tail -5 gpurun_out/r4f_s$s2.err; exit 1; }

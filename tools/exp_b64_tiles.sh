@@ -2,7 +2,7 @@
 # 512^2 x 64 (config 5 shard shape): tile heights of the fused passes against the resident-block count
 #   bash tools/exp_b64_tiles.sh "pre:post" "pre:post" ...     (0 = default)
 cd $GRAFT_REPO_ROOT
-A="--mesh 512 --batch 64 --steps 20 --warmup 3 --no-cpu-baseline --no-variants"
+A="--full --mesh 512 --batch 64 --steps 20 --warmup 3 --no-cpu-baseline --no-variants"
 for pp in "$@"; do
   pre=${pp%%:*}; post=${pp##*:}
   unset DIFFHE_FUSED_TR_PRE DIFFHE_FUSED_TR_POST

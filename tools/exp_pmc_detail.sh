@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/${1:-r4g_pmc}; mkdir -p $out
-P="--steps 1 --warmup 1 --no-cpu-baseline --no-variants --kernel-reps 2"
+P="--full --steps 1 --warmup 1 --no-cpu-baseline --no-variants --kernel-reps 2"
 i=0
 for grp in \
   "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_INSTS_VALU GRBM_GUI_ACTIVE" \

@@ -2,7 +2,7 @@
 # quick look: headline step + in-solver kernel times (+ optional per-element-field variant): bash tools/exp_quick.sh tag [elem]
 cd $GRAFT_REPO_ROOT
 tag=${1:-q}
-A="--steps 5 --warmup 2 --no-cpu-baseline"
+A="--full --steps 5 --warmup 2 --no-cpu-baseline"
 if [ "$2" == "elem" ]; then V="--only-variant kappa_element_field"; else V="--no-variants"; fi
 python bench.py $A $V > gpurun_out/${tag}.json 2> gpurun_out/${tag}.err || { tail -5 gpurun_out/${tag}.err; exit 1; }
 python - <<PY

@@ -4,9 +4,9 @@
 out=${1:-gpurun_out/prof}; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-A="--steps 3 --warmup 1 --no-cpu-baseline --no-variants"
+A="--full --steps 3 --warmup 1 --no-cpu-baseline --no-variants"
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/trace -- python3 $R/bench.py $A > $R/$out/bench_under_rocprof.json 2> $R/$out/trace.err || exit 1
-P="--steps 1 --warmup 1 --no-cpu-baseline --no-variants --kernel-reps 2"
+P="--full --steps 1 --warmup 1 --no-cpu-baseline --no-variants --kernel-reps 2"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/$out/fetch -- python3 $R/bench.py $P > $R/$out/bench_fetch.json 2> $R/$out/fetch.err || exit 1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/$out/write -- python3 $R/bench.py $P > $R/$out/bench_write.json 2> $R/$out/write.err || exit 1
 cd $R

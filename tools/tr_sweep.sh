@@ -3,7 +3,7 @@
 out=${1:-gpurun_out/trsweep}; mkdir -p $out
 run() {  # label, env...
   label=$1; shift
-  env "$@" timeout -k 10 120 python bench.py --no-variants --no-cpu-baseline --steps 8 --warmup 2 --kernel-reps 1 > $out/$label.json 2> $out/$label.err || { echo "$label FAILED"; return 1; }
+  env "$@" timeout -k 10 120 python bench.py --full --no-variants --no-cpu-baseline --steps 8 --warmup 2 --kernel-reps 1 > $out/$label.json 2> $out/$label.err || { echo "$label FAILED"; return 1; }
   python - $out/$label.json $label <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
