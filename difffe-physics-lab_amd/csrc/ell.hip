@@ -1,4 +1,4 @@
-// General P1 path (any 1D/2D mesh): element integrals, assembly into a batch-shared ELL
+// General P1 path (any 1D/2D mesh, P1 tetrahedra in 3D): element integrals, assembly into a batch-shared ELL
 // pattern, Dirichlet elimination, batched Jacobi-PCG, gradient contraction, layout changes.
 //
 // Data layout: node-major, batch-innermost (n, Bp): entry (i, b) at i*Bp + b.  A wave's 64
@@ -32,6 +32,42 @@ __device__ inline void tri_integrals(double xi, double yi, double xj, double yj,
   *area_out = keep ? area : 0.0;
 }
 
+// P1 tetrahedron [v0, v1, v2, v3] (ours: the reference stops at 2D, solver.py:67).  Edge vectors a, b, c from v0; the
+// cofactor vectors g_1 = b x c, g_2 = c x a, g_3 = a x b, g_0 = -(g_1 + g_2 + g_3) are 6 V grad phi_p, det = a . g_1 =
+// +-6 V, so k0[pq] = (g_p . g_q) / (36 V) with 36 V = 6 |det|.  Every operation is rounded on its own (no contraction): a
+// product that cancels exactly (hx hy - hy hx on an axis-aligned box) stays an exact zero, which is what lets the plan
+// drop structurally zero couplings (diffhe/plan.py: build_ell_pattern) -- and what reference_order_integrals restates
+// on the host bit for bit.  Degenerate: |det| <= 1e-12 l^3, l the longest of a, b, c (relative to the element's size,
+// unlike the triangles' absolute 1e-15); such a tetrahedron contributes nothing, *vol_out = 0.
+__device__ inline void tet_integrals(const double* __restrict__ coords, int n, int v0, int v1, int v2, int v3, double* k0,
+                                     double* vol_out) {
+#pragma clang fp contract(off)
+  const double* X = coords;
+  const double* Y = coords + n;
+  const double* Z = coords + 2 * (i64)n;
+  const double x0 = X[v0], y0 = Y[v0], z0 = Z[v0];
+  const double ax = X[v1] - x0, ay = Y[v1] - y0, az = Z[v1] - z0;
+  const double bx = X[v2] - x0, by = Y[v2] - y0, bz = Z[v2] - z0;
+  const double cx = X[v3] - x0, cy = Y[v3] - y0, cz = Z[v3] - z0;
+  double g[4][3];
+  g[1][0] = by * cz - bz * cy; g[1][1] = bz * cx - bx * cz; g[1][2] = bx * cy - by * cx;
+  g[2][0] = cy * az - cz * ay; g[2][1] = cz * ax - cx * az; g[2][2] = cx * ay - cy * ax;
+  g[3][0] = ay * bz - az * by; g[3][1] = az * bx - ax * bz; g[3][2] = ax * by - ay * bx;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) g[0][d] = -((g[1][d] + g[2][d]) + g[3][d]);
+  const double det = ax * g[1][0] + ay * g[1][1] + az * g[1][2];
+  const double la = ax * ax + ay * ay + az * az, lb = bx * bx + by * by + bz * bz, lc = cx * cx + cy * cy + cz * cz;
+  const double l2 = fmax(fmax(la, lb), lc);
+  const bool keep = fabs(det) > 1e-12 * (l2 * sqrt(l2));
+  const double den = keep ? 6.0 * fabs(det) : 1.0;
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      k0[p * 4 + q] = keep ? (g[p][0] * g[q][0] + g[p][1] * g[q][1] + g[p][2] * g[q][2]) / den : 0.0;
+  *vol_out = keep ? fabs(det) / 6.0 : 0.0;
+}
+
 __global__ __launch_bounds__(256) void element_integrals_kernel(const double* __restrict__ coords,
                                                                  const int* __restrict__ elems, int dim, int n, int m,
                                                                  double* __restrict__ k0, double* __restrict__ m0) {
@@ -42,6 +78,15 @@ __global__ __launch_bounds__(256) void element_integrals_kernel(const double* __
       const double k = 1.0 / h;
       k0[e] = k; k0[(i64)m + e] = -k; k0[2 * (i64)m + e] = -k; k0[3 * (i64)m + e] = k;
       m0[e] = 0.5 * h; m0[(i64)m + e] = 0.0; m0[2 * (i64)m + e] = 0.0; m0[3 * (i64)m + e] = 0.5 * h;
+    } else if (dim == 3) {
+      double loc[16], vol;
+      tet_integrals(coords, n, elems[e], elems[(i64)m + e], elems[2 * (i64)m + e], elems[3 * (i64)m + e], loc, &vol);
+#pragma unroll
+      for (int pq = 0; pq < 16; ++pq) {
+        k0[(i64)pq * m + e] = loc[pq];
+        // F_p += V/4 * (f_0+f_1+f_2+f_3)/4: the 2D rule above lifted to tetrahedra (no reference rule to copy)
+        m0[(i64)pq * m + e] = vol / 16.0;
+      }
     } else {
       const int i = elems[e], j = elems[(i64)m + e], k = elems[2 * (i64)m + e];
       double loc[9], area;
@@ -253,13 +298,16 @@ __global__ __launch_bounds__(256) void lattice_assemble_strip_kernel(const doubl
 // ---------------------------------------------------------------------------------------
 constexpr int kElemTile = 64;
 
+// NPE: the largest element the instance handles (3: intervals and triangles; 4: tetrahedra, whose pruned stiffness
+// pattern has no slot for a structurally zero coupling: slot_of < 0, skipped)
+template <int NPE>
 __global__ __launch_bounds__(256) void assemble_atomic_kernel(const double* __restrict__ coords,
                                                                const int* __restrict__ elems, int dim,
                                                                const double* __restrict__ kappa, i64 kse, i64 ksb,
                                                                const int* __restrict__ slot_of,
                                                                double* __restrict__ vals, int n, int m, int Bp) {
-  __shared__ double k0s[9][kElemTile];
-  __shared__ int rows[3][kElemTile];
+  __shared__ double k0s[NPE * NPE][kElemTile];
+  __shared__ int rows[NPE][kElemTile];
   const int npe = dim + 1, nloc = npe * npe;
   const int LB = Bp < kWave ? Bp : kWave;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -275,6 +323,16 @@ __global__ __launch_bounds__(256) void assemble_atomic_kernel(const double* __re
         const double k = 1.0 / (coords[j] - coords[i]);
         k0s[0][t] = k; k0s[1][t] = -k; k0s[2][t] = -k; k0s[3][t] = k;
         rows[0][t] = i; rows[1][t] = j;
+      } else if (NPE == 4 && dim == 3) {
+        double loc[16], vol;
+        int v[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) v[p] = elems[(i64)p * m + e];
+        tet_integrals(coords, n, v[0], v[1], v[2], v[3], loc, &vol);
+#pragma unroll
+        for (int pq = 0; pq < 16; ++pq) k0s[pq % (NPE * NPE)][t] = loc[pq];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) rows[p % NPE][t] = v[p];
       } else {
         const int i = elems[e], j = elems[(i64)m + e], k = elems[2 * (i64)m + e];
         double loc[9], area;
@@ -292,6 +350,7 @@ __global__ __launch_bounds__(256) void assemble_atomic_kernel(const double* __re
       const double kap = kappa ? kappa[e * kse + (i64)b * ksb] : 1.0;
       for (int pq = 0; pq < nloc; ++pq) {
         const int slot = slot_of[(i64)pq * m + e];
+        if (NPE == 4 && slot < 0) continue;
         const int row = rows[pq / npe][el];
         unsafeAtomicAdd(&vals[((i64)slot * n + row) * Bp + b], kap * k0s[pq][el]);
       }
@@ -1440,7 +1499,7 @@ static int sync_xcd_switch(hipStream_t st) {
 // =========================================================================================
 extern "C" int diffhe_p1_element_integrals(const double* coords, const int* elems, int dim, int n, int m,
                                            double* k0, double* m0, void* stream) {
-  if (!coords || !elems || !k0 || !m0 || (dim != 1 && dim != 2) || n < 1 || m < 1) return DIFFHE_E_BADARG;
+  if (!coords || !elems || !k0 || !m0 || dim < 1 || dim > 3 || n < 1 || m < 1) return DIFFHE_E_BADARG;
   int blocks = (m + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(element_integrals_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, coords, elems, dim, n,
@@ -1506,13 +1565,17 @@ extern "C" int diffhe_ell_assemble_atomic(const double* coords, const int* elems
                                           long long kappa_se, long long kappa_sb, const int* slot_of, double* vals,
                                           int n, int m, int W, int Bp, void* stream) {
   (void)W;
-  if (!coords || !elems || !slot_of || !vals || (dim != 1 && dim != 2) || n < 1 || m < 1) return DIFFHE_E_BADARG;
+  if (!coords || !elems || !slot_of || !vals || dim < 1 || dim > 3 || n < 1 || m < 1) return DIFFHE_E_BADARG;
   if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
   int gx = (m + kElemTile - 1) / kElemTile;
   if (gx > 4096) gx = 4096;
   dim3 grid(gx, (Bp + 63) / 64);
-  hipLaunchKernelGGL(assemble_atomic_kernel, grid, dim3(256), 0, (hipStream_t)stream, coords, elems, dim, kappa,
-                     kappa_se, kappa_sb, slot_of, vals, n, m, Bp);
+  if (dim == 3)
+    hipLaunchKernelGGL(assemble_atomic_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, coords, elems, dim, kappa,
+                       kappa_se, kappa_sb, slot_of, vals, n, m, Bp);
+  else
+    hipLaunchKernelGGL(assemble_atomic_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, coords, elems, dim, kappa,
+                       kappa_se, kappa_sb, slot_of, vals, n, m, Bp);
   return diffhe::check_launch();
 }
 
@@ -1759,7 +1822,7 @@ extern "C" int diffhe_grad_kappa_blocks(int m, int Bp) { return (int)diffhe::nod
 extern "C" int diffhe_p1_grad_kappa(const int* elems, const double* k0, const double* lam, const double* u,
                                     const double* g, int npe, int m, int Bp, double* dk_e, double* dk_part,
                                     double* dk_sum, void* stream) {
-  if (!elems || !k0 || !lam || !u || !dk_part || !dk_sum || (npe != 2 && npe != 3 && npe != 6) || m < 1) return DIFFHE_E_BADARG;
+  if (!elems || !k0 || !lam || !u || !dk_part || !dk_sum || (npe != 2 && npe != 3 && npe != 4 && npe != 6) || m < 1) return DIFFHE_E_BADARG;
   if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
   const dim3 grid = diffhe::node_grid(m, Bp);
   diffhe::account(8.0 * Bp * (2.0 * m * (npe == 3 ? 0.5 : 1.0) + (dk_e ? m : 0)));  // lambda and u once per node, dk per element
@@ -1772,7 +1835,7 @@ extern "C" int diffhe_p1_grad_kappa(const int* elems, const double* k0, const do
 
 extern "C" int diffhe_p1_grad_kappa_shared(const int* elems, const double* k0, const double* lam, const double* u,
                                            const double* g, int npe, int m, int B, int Bp, double* dk, void* stream) {
-  if (!elems || !k0 || !lam || !u || !dk || (npe != 2 && npe != 3 && npe != 6) || m < 1 || B < 1 || B > Bp) return DIFFHE_E_BADARG;
+  if (!elems || !k0 || !lam || !u || !dk || (npe != 2 && npe != 3 && npe != 4 && npe != 6) || m < 1 || B < 1 || B > Bp) return DIFFHE_E_BADARG;
   if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
   long long blocks = ((long long)m + 3) / 4;
   if (blocks > 16384) blocks = 16384;

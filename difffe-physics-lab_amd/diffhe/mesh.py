@@ -95,6 +95,37 @@ class FEMesh:
         bc_ = dict.fromkeys(np.nonzero(on_edge)[0].tolist(), bc_value)
         return cls(nodes=torch.from_numpy(coords), elements=torch.from_numpy(tris), dirichlet_nodes=bc_)
 
+    @classmethod
+    def box(cls, nx: int = 4, ny: int = 4, nz: int = 4, x_range: Tuple[float, float] = (0.0, 1.0),
+            y_range: Tuple[float, float] = (0.0, 1.0), z_range: Tuple[float, float] = (0.0, 1.0),
+            bc_value: float = 0.0) -> "FEMesh":
+        """P1 TETRAHEDRA on a uniform nx x ny x nz grid of boxes -- ours: the reference stops at 2D (solver.py:67); solve
+        with `diffhe.tet3d.DifferentiableFESolver3D`.  Node id = (k (ny+1) + j)(nx+1) + i, x fastest (like `rectangle`'s
+        row (nx+1) + col).  Cube (i, j, k), taken in the same order (cube id (k ny + j) nx + i), is split into the 6 Kuhn
+        tetrahedra 6 cube + s: tetrahedron s is the path from corner (i, j, k) to (i+1, j+1, k+1) that steps along the
+        axes in the order of the s-th permutation of (x, y, z) in lexicographic order -- xyz, xzy, yxz, yzx, zxy, zyx --
+        and lists its four vertices along that path.  All cubes share the direction of their main diagonal, so the mesh
+        is conforming.  Dirichlet `bc_value` on every node of the six faces (found with `np.isclose`)."""
+        xs = np.linspace(x_range[0], x_range[1], nx + 1)
+        ys = np.linspace(y_range[0], y_range[1], ny + 1)
+        zs = np.linspace(z_range[0], z_range[1], nz + 1)
+        gz, gy, gx = np.meshgrid(zs, ys, xs, indexing="ij")
+        coords = np.stack([gx.ravel(), gy.ravel(), gz.ravel()], axis=1)
+        k, rest = np.divmod(np.arange(nx * ny * nz, dtype=np.int64), nx * ny)
+        j, i = np.divmod(rest, nx)
+        corner = (k * (ny + 1) + j) * (nx + 1) + i
+        step = np.array([1, nx + 1, (nx + 1) * (ny + 1)], dtype=np.int64)       # node-id step along x, y, z
+        tets = np.empty((6 * nx * ny * nz, 4), dtype=np.int64)
+        for s, perm in enumerate(((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))):
+            v1 = corner + step[perm[0]]
+            v2 = v1 + step[perm[1]]
+            tets[s::6] = np.stack([corner, v1, v2, v2 + step[perm[2]]], axis=1)
+        on_face = (np.isclose(coords[:, 0], x_range[0]) | np.isclose(coords[:, 0], x_range[1])
+                   | np.isclose(coords[:, 1], y_range[0]) | np.isclose(coords[:, 1], y_range[1])
+                   | np.isclose(coords[:, 2], z_range[0]) | np.isclose(coords[:, 2], z_range[1]))
+        bc = dict.fromkeys(np.nonzero(on_face)[0].tolist(), bc_value)
+        return cls(nodes=torch.from_numpy(coords), elements=torch.from_numpy(tets), dirichlet_nodes=bc)
+
     # -- convenience ---------------------------------------------------------------
     def free_nodes(self) -> List[int]:
         """Ascending ids of the unconstrained nodes (reference mesh.py:127-129)."""

@@ -108,12 +108,16 @@ def chain_segments(n: int, is_bc: np.ndarray) -> np.ndarray:
     return np.asarray(segs, dtype=np.int32)
 
 
-def build_ell_pattern(elements: np.ndarray, n: int):
+def build_ell_pattern(elements: np.ndarray, n: int, zero: Optional[np.ndarray] = None):
     """ELL pattern + gather lists from the connectivity.
 
-    Returns dict(W, cols (W,n) i32, ent_ptr (W*n+1) i32, contrib i32, slot_of (npe*npe, m) i32).
+    Returns dict(W, cols (W,n) i32, ent_ptr (W*n+1) i32, contrib i32, slot_of (npe*npe, m) i32, pruned).
     Entry (row i, slot k) is stored at k*n + i; slot 0 is the diagonal; unused slots
     point at the row itself and carry no contribution.
+    zero (npe*npe, m) bool or None: contributions that are EXACT zeros for every kappa (tnum == 0.0).  An off-diagonal
+    entry all of whose contributions are such zeros is left out of the pattern (its slot_of is -1; `pruned` counts the
+    entries dropped) -- on FEMesh.box the Kuhn tetrahedra couple each node to 14 neighbours of which 6 carry exact
+    zeros (W 15 -> 7).
     """
     m, npe = elements.shape
     _check_gather_code_range(m)
@@ -122,6 +126,16 @@ def build_ell_pattern(elements: np.ndarray, n: int):
     pq = np.tile(np.arange(nloc, dtype=np.int64), m)
     rows = elements[e_idx, pq // npe].astype(np.int64)
     cols = elements[e_idx, pq % npe].astype(np.int64)
+    keep_c, pruned = None, 0
+    if zero is not None:
+        nonzero = ~np.ascontiguousarray(zero.T).reshape(-1)                # (e, pq) order, like e_idx / pq
+        uniq, inv0 = np.unique(rows * n + cols, return_inverse=True)
+        live = np.bincount(inv0.reshape(-1), weights=nonzero, minlength=len(uniq)) > 0
+        live |= uniq // n == uniq % n                                      # diagonals stay
+        pruned = int((~live).sum())
+        if pruned:
+            keep_c = live[inv0.reshape(-1)]
+            e_idx, pq, rows, cols = e_idx[keep_c], pq[keep_c], rows[keep_c], cols[keep_c]
     # every row owns a diagonal entry even if no element touches the node
     rows_all = np.concatenate([np.arange(n, dtype=np.int64), rows])
     cols_all = np.concatenate([np.arange(n, dtype=np.int64), cols])
@@ -151,11 +165,16 @@ def build_ell_pattern(elements: np.ndarray, n: int):
     counts = np.bincount(contrib_entry, minlength=W * n)
     ent_ptr = np.zeros(W * n + 1, dtype=np.int64)
     np.cumsum(counts, out=ent_ptr[1:])
-    slot_of = (contrib_entry // n).reshape(m, nloc).T.copy().astype(np.int32)
+    if keep_c is None:
+        slot_of = (contrib_entry // n).reshape(m, nloc).T.copy().astype(np.int32)
+    else:
+        slot_all = np.full(m * nloc, -1, dtype=np.int64)
+        slot_all[keep_c] = contrib_entry // n
+        slot_of = slot_all.reshape(m, nloc).T.copy().astype(np.int32)
     if ent_ptr[-1] >= 2 ** 31:
         raise ValueError("mesh too large for int32 gather lists")
     return dict(W=W, cols=ell_cols.reshape(W, n), ent_ptr=ent_ptr.astype(np.int32), contrib=contrib,
-                slot_of=slot_of)
+                slot_of=slot_of, pruned=pruned)
 
 
 def _check_gather_code_range(m: int) -> None:
@@ -163,6 +182,19 @@ def _check_gather_code_range(m: int) -> None:
     (a 4096 x 4096 lattice).  Beyond that the cast would wrap silently and the kernel would read out of bounds."""
     if m >= 2 ** 25:
         raise ValueError(f"mesh too large for int32 gather lists: {m} elements >= 2**25")
+
+
+def boundary_faces(tets: np.ndarray) -> np.ndarray:
+    """(k, 3) sorted vertex triples that occur in exactly one tetrahedron of `tets` (m, 4): the boundary faces."""
+    f = np.concatenate([tets[:, [1, 2, 3]], tets[:, [0, 2, 3]], tets[:, [0, 1, 3]], tets[:, [0, 1, 2]]]).astype(np.int64)
+    f.sort(axis=1)
+    n = int(f.max()) + 1 if len(f) else 1
+    if n < 2 ** 21:                                  # one int64 key per face: a flat sort, not a row-wise one
+        key, cnt = np.unique((f[:, 0] * n + f[:, 1]) * n + f[:, 2], return_counts=True)
+        key = key[cnt == 1]
+        return np.stack([key // (n * n), key // n % n, key % n], axis=1)
+    uniq, cnt = np.unique(f, axis=0, return_counts=True)
+    return uniq[cnt == 1]
 
 
 def detect_lattice(elements: np.ndarray, n: int):
@@ -281,13 +313,22 @@ def reference_order_integrals(coords: np.ndarray, elems: np.ndarray):
     """Numerators and denominators of the element stiffness entries in the reference's operation order, computed
     with numpy (every operation rounded on its own, like torch's): 2D t[pq] = b_p b_q + c_p c_q, den = 4.0 area
     (solver.py:119-139; skipped elements contribute 0); 1D t = +-1, den = h (solver.py:86-92).  coords (dim, n),
-    elems (npe, m) as uploaded to the device.  Returns (tnum (npe*npe, m), den (m))."""
+    elems (npe, m) as uploaded to the device.  Returns (tnum (npe*npe, m), den (m)).
+    3D (P1 tetrahedra, ours -- the reference has no 3D operator): t[pq] = g_p . g_q with the cofactor vectors
+    g_1 = b x c, g_2 = c x a, g_3 = a x b, g_0 = -((g_1 + g_2) + g_3) of the edge vectors a, b, c from vertex 0, the dot
+    product summed x + y + z left to right; den = 6 |det| = 36 V, det = a . g_1; degenerate (|det| <= 1e-12 l^3, l the
+    longest of a, b, c) -> t = 0, den = 1.  The same operations in the same order as tet_integrals (csrc/ell.hip)."""
     dim = coords.shape[0]
     e = elems.astype(np.int64)
     if dim == 1:
         h = coords[0, e[1]] - coords[0, e[0]]
         m = e.shape[1]
         return np.stack([np.ones(m), -np.ones(m), -np.ones(m), np.ones(m)]), h
+    if dim == 3:
+        g, det, keep = _tet_cofactors(coords, e)
+        t = (g[:, None, 0] * g[None, :, 0] + g[:, None, 1] * g[None, :, 1] + g[:, None, 2] * g[None, :, 2]).reshape(16, -1)
+        t[:, ~keep] = 0.0
+        return t, np.where(keep, 6.0 * np.abs(det), 1.0)
     xi, yi = coords[0, e[0]], coords[1, e[0]]
     xj, yj = coords[0, e[1]], coords[1, e[1]]
     xk, yk = coords[0, e[2]], coords[1, e[2]]
@@ -298,6 +339,24 @@ def reference_order_integrals(coords: np.ndarray, elems: np.ndarray):
     t = (b[:, None, :] * b[None, :, :] + c[:, None, :] * c[None, :, :]).reshape(9, -1)
     t[:, ~keep] = 0.0
     return t, np.where(keep, 4.0 * area, 1.0)
+
+
+def _tet_cofactors(coords: np.ndarray, e: np.ndarray):
+    """(g (4, 3, m), det (m), keep (m)) of P1 tetrahedra: coords (3, n), e (4, m).  g_p = 6 V grad phi_p (see
+    reference_order_integrals), det = +-6 V, keep = not degenerate."""
+    X, Y, Z = coords[0], coords[1], coords[2]
+    x0, y0, z0 = X[e[0]], Y[e[0]], Z[e[0]]
+    ax, ay, az = X[e[1]] - x0, Y[e[1]] - y0, Z[e[1]] - z0
+    bx, by, bz = X[e[2]] - x0, Y[e[2]] - y0, Z[e[2]] - z0
+    cx, cy, cz = X[e[3]] - x0, Y[e[3]] - y0, Z[e[3]] - z0
+    g1 = np.stack([by * cz - bz * cy, bz * cx - bx * cz, bx * cy - by * cx])
+    g2 = np.stack([cy * az - cz * ay, cz * ax - cx * az, cx * ay - cy * ax])
+    g3 = np.stack([ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx])
+    g0 = -((g1 + g2) + g3)
+    det = ax * g1[0] + ay * g1[1] + az * g1[2]
+    l2 = np.maximum(np.maximum(ax * ax + ay * ay + az * az, bx * bx + by * by + bz * bz), cx * cx + cy * cy + cz * cz)
+    keep = np.abs(det) > 1e-12 * (l2 * np.sqrt(l2))
+    return np.stack([g0, g1, g2, g3]), det, keep
 
 
 def p2_element_integrals(nodes: np.ndarray, elements: np.ndarray):
@@ -331,6 +390,9 @@ def _lumped_mass(nodes: np.ndarray, elements: np.ndarray) -> np.ndarray:
     n = nodes.shape[0]
     if nodes.shape[1] == 1:
         size = np.abs(nodes[elements[:, 1], 0] - nodes[elements[:, 0], 0])
+    elif nodes.shape[1] == 3:
+        _, det, keep = _tet_cofactors(np.ascontiguousarray(nodes.T), elements.T.astype(np.int64))
+        size = np.where(keep, np.abs(det) / 6.0, 0.0)              # volume; degenerate tetrahedra carry no mass
     else:
         a, b, c = (nodes[elements[:, k]] for k in range(3))
         size = 0.5 * np.abs((b[:, 0] - a[:, 0]) * (c[:, 1] - a[:, 1]) - (c[:, 0] - a[:, 0]) * (b[:, 1] - a[:, 1]))
@@ -433,9 +495,9 @@ class SolvePlan:
         self.dim = mesh.dim
         self.n = mesh.n_nodes
         self.m = mesh.n_elements
-        self.npe = int(mesh.elements.shape[1])                        # 2 (1D), 3 (P1 triangles) or 6 (P2 triangles)
-        if self.dim not in (1, 2):
-            raise NotImplementedError("Only 1D and 2D supported")  # reference solver.py:67
+        self.npe = int(mesh.elements.shape[1])      # 2 (1D), 3 (P1 triangles), 6 (P2 triangles) or 4 (P1 tetrahedra)
+        if self.dim not in (1, 2, 3):
+            raise NotImplementedError("Only 1D, 2D and 3D (P1 tetrahedra) supported")
         nodes = mesh.nodes.detach().to("cpu", torch.float64).numpy()
         elements = mesh.elements.detach().to("cpu", torch.int64).numpy()
         if self.npe != self.dim + 1 and not (self.dim == 2 and self.npe == 6):
@@ -602,12 +664,21 @@ class SolvePlan:
         L = _hip.lib()
         device = self.device
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
-        pat = build_ell_pattern(self._elements, self.n)
+        tn = dn = None
+        if not self.is_p2:
+            tn, dn = reference_order_integrals(np.ascontiguousarray(self._nodes_host.T), self._elements.T)
+        # tetrahedra: couplings whose every contribution is an exact zero (t = g_p . g_q == 0.0: the cofactor arithmetic
+        # keeps them exact on axis-aligned boxes) are left out of the STIFFNESS pattern -- zero for every finite kappa, so
+        # the solution, the Dirichlet lift and the gradients are unchanged, and the sweeps gather 7 instead of 15 columns
+        # per node on FEMesh.box.  DIFFHE_TET_PRUNE=0 keeps the full pattern (the A/B switch of tools/box3d_bench.py).
+        prune = self.dim == 3 and os.environ.get("DIFFHE_TET_PRUNE", "1") != "0"
+        pat = build_ell_pattern(self._elements, self.n, zero=(tn == 0.0) if prune else None)
         self.W = pat["W"]
         self.cols = dev(pat["cols"])
         self.ent_ptr = dev(pat["ent_ptr"])
         self.contrib = dev(pat["contrib"])
         self.slot_of = dev(pat["slot_of"])
+        self.pruned_entries = pat["pruned"]
         stream = _stream(device)
         nloc = self.npe * self.npe
         if self.is_p2:      # quadratic triangles (ours): batch-shared integrals from the host, plain kappa * k0 assembly
@@ -620,19 +691,27 @@ class SolvePlan:
             _hip.check(L.diffhe_p1_element_integrals(_hip.ptr(self.coords), _hip.ptr(self.elems), self.dim, self.n,
                                                      self.m, _hip.ptr(self.k0), _hip.ptr(self.m0), stream),
                        "diffhe_p1_element_integrals")
-            tn, dn = reference_order_integrals(self.coords.cpu().numpy(), self.elems.cpu().numpy())
             self.tnum, self.den = dev(tn), dev(dn)       # reference-order assembly
-        # load matrix M (batch-shared ELL values): F = M f, df = M^T lambda
-        self.Mvals = torch.empty((self.W, self.n), dtype=torch.float64, device=device)
-        _hip.check(L.diffhe_ell_assemble_rows(_hip.ptr(self.m0), None, 0, 0, _hip.ptr(self.ent_ptr),
-                                              _hip.ptr(self.contrib), _hip.ptr(self.cols), None, None, None,
-                                              _hip.ptr(self.Mvals), None, self.n, self.m, self.W, 1, stream),
+        # load matrix M (batch-shared ELL values): F = M f, df = M^T lambda.  Its own pattern where the stiffness pattern
+        # was pruned: m0 = V/16 couples every pair of a tetrahedron's vertices.  M is applied twice per fwd + adjoint step
+        # (F = M f, dL/df = M lambda), the stiffness in every sweep of every iteration: the full pattern is kept where it is
+        # cheap, and the (W, n) index array it costs is plan memory only.
+        self.MW, self.Mcols = self.W, self.cols
+        m_ent_ptr, m_contrib = self.ent_ptr, self.contrib
+        if self.pruned_entries:
+            mpat = build_ell_pattern(self._elements, self.n)
+            self.MW, self.Mcols = mpat["W"], dev(mpat["cols"])
+            m_ent_ptr, m_contrib = dev(mpat["ent_ptr"]), dev(mpat["contrib"])
+        self.Mvals = torch.empty((self.MW, self.n), dtype=torch.float64, device=device)
+        _hip.check(L.diffhe_ell_assemble_rows(_hip.ptr(self.m0), None, 0, 0, _hip.ptr(m_ent_ptr),
+                                              _hip.ptr(m_contrib), _hip.ptr(self.Mcols), None, None, None,
+                                              _hip.ptr(self.Mvals), None, self.n, self.m, self.MW, 1, stream),
                    "diffhe_ell_assemble_rows(M)")
         self._ell_ready = True
 
     def closed_boundary_general(self) -> bool:
         """Every node of the mesh boundary is a Dirichlet node (general meshes, P1: a boundary edge belongs to exactly one
-        triangle; 1D: a boundary node to exactly one element).  The regime in which one scalar kappa per sample may stay
+        triangle; 3D: a boundary face to exactly one tetrahedron; 1D: a boundary node to exactly one element).  The regime in which one scalar kappa per sample may stay
         FACTORED, K_b = kappa_b K_1 (closed lattices have `closed_boundary`): with Neumann parts the system is
         ill-conditioned enough for the last-bit difference to the reference's rounded matrix to show.  Cached."""
         cached = self.__dict__.get("_closed_general")
@@ -645,6 +724,8 @@ class SolvePlan:
             if self.dim == 1:
                 deg = np.bincount(el.reshape(-1), minlength=self.n)
                 bnodes = np.nonzero(deg == 1)[0]
+            elif self.dim == 3:
+                bnodes = np.unique(boundary_faces(el))
             else:
                 e = np.concatenate([el[:, [0, 1]], el[:, [1, 2]], el[:, [2, 0]]])
                 e.sort(axis=1)

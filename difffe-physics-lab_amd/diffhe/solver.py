@@ -206,8 +206,8 @@ class _Engine:
                                                           _hip.ptr(F), Bp, _stream(p.device)),
                        "diffhe_lattice_apply_shared")
             return F
-        _hip.check(self.L.diffhe_ell_spmv_shared(_hip.ptr(p.Mvals), _hip.ptr(p.cols), _hip.ptr(f_nm), _hip.ptr(lift),
-                                                 Bv, _hip.ptr(lift_scale), _hip.ptr(p.is_bc), _hip.ptr(F), p.n, p.W,
+        _hip.check(self.L.diffhe_ell_spmv_shared(_hip.ptr(p.Mvals), _hip.ptr(p.Mcols), _hip.ptr(f_nm), _hip.ptr(lift),
+                                                 Bv, _hip.ptr(lift_scale), _hip.ptr(p.is_bc), _hip.ptr(F), p.n, p.MW,
                                                  Bp, _stream(p.device)), "diffhe_ell_spmv_shared")
         return F
 
@@ -220,8 +220,8 @@ class _Engine:
                                                           1, None, None, _hip.ptr(y), Bp, _stream(p.device)),
                        "diffhe_lattice_apply_shared")
             return y
-        _hip.check(self.L.diffhe_ell_spmv_shared(_hip.ptr(p.Mvals), _hip.ptr(p.cols), _hip.ptr(x_nm), None, 1, None,
-                                                 None, _hip.ptr(y), p.n, p.W, Bp, _stream(p.device)),
+        _hip.check(self.L.diffhe_ell_spmv_shared(_hip.ptr(p.Mvals), _hip.ptr(p.Mcols), _hip.ptr(x_nm), None, 1, None,
+                                                 None, _hip.ptr(y), p.n, p.MW, Bp, _stream(p.device)),
                    "diffhe_ell_spmv_shared")
         return y
 
@@ -1071,7 +1071,7 @@ def _fe_setup_context(ctx, inputs, output):
 def _element_forms(plan: SolvePlan):
     """Unit-kappa element stiffness and load matrices (m, npe, npe) and the (m, npe) connectivity, as torch tensors
     built from the plan's coordinates -- the differentiable restatement of reference solver.py:86-96 (1D) and :125-145
-    (2D P1) used by the second-order path only."""
+    (2D P1), and of the P1 tetrahedra of csrc/ell.hip (3D), used by the second-order path only."""
     cached = plan.__dict__.get("_element_forms")
     if cached is not None:
         return cached
@@ -1083,6 +1083,18 @@ def _element_forms(plan: SolvePlan):
         h = (X[0][el[:, 1]] - X[0][el[:, 0]]).abs()
         k0 = torch.tensor([[1.0, -1.0], [-1.0, 1.0]], dtype=torch.float64, device=h.device)[None] / h[:, None, None]
         m0 = torch.eye(2, dtype=torch.float64, device=h.device)[None] * (0.5 * h)[:, None, None]
+    elif plan.dim == 3:
+        P = X.t()[el]                                                # (m, 4, 3)
+        a, b, c = P[:, 1] - P[:, 0], P[:, 2] - P[:, 0], P[:, 3] - P[:, 0]
+        g1, g2, g3 = torch.cross(b, c, dim=1), torch.cross(c, a, dim=1), torch.cross(a, b, dim=1)
+        G = torch.stack([-(g1 + g2 + g3), g1, g2, g3], 1)            # (m, 4, 3): 6 V grad phi_p
+        det = (a * g1).sum(1)
+        l2 = torch.maximum(torch.maximum((a * a).sum(1), (b * b).sum(1)), (c * c).sum(1))
+        keep = det.abs() > 1e-12 * (l2 * l2.sqrt())                  # degenerate tetrahedra: nothing, as in ell.hip
+        safe = torch.where(keep, det.abs(), torch.ones_like(det))
+        zero = torch.zeros((), dtype=torch.float64, device=det.device)
+        k0 = torch.where(keep[:, None, None], G @ G.transpose(1, 2) / (6.0 * safe)[:, None, None], zero)
+        m0 = torch.where(keep[:, None, None], (safe / 96.0)[:, None, None].expand(-1, 4, 4), zero).contiguous()
     else:
         x, y = X[0][el], X[1][el]                                    # (m, 3)
         b = torch.stack([y[:, 1] - y[:, 2], y[:, 2] - y[:, 0], y[:, 0] - y[:, 1]], 1)
@@ -1180,6 +1192,8 @@ class DifferentiableFESolver(nn.Module):
         path); `method="ell"` forces the general ELL path on lattice meshes; `mg` overrides
         the multigrid parameters (nu, n_coarse, omega) of the lattice path.
     """
+
+    _dims = (1, 2)        # mesh dimensions forward() accepts: the reference's (diffhe.tet3d adds 3)
 
     def __init__(self, mesh: FEMesh, kappa: float = 1.0, *, device=None, tol: Optional[float] = None,
                  max_iter: int = 20000, check_every: int = 25, assembly: str = "gather", method: str = "auto",
@@ -1294,7 +1308,7 @@ class DifferentiableFESolver(nn.Module):
                 mesh0 = FEMesh(nodes=self.mesh.nodes, elements=self.mesh.elements,
                                dirichlet_nodes={k: 0.0 for k in self.mesh.dirichlet_nodes})
                 self.mesh.__dict__["_diffhe_zero_twin"] = mesh0
-            twin = DifferentiableFESolver(mesh0, self._kappa, device=self._device)
+            twin = type(self)(mesh0, self._kappa, device=self._device)
             self.__dict__["_twin"] = twin
         for name in ("tol", "_tol_user", "max_iter", "check_every", "assembly", "method", "chain", "warm_start",
                      "reaction", "operator", "_mg_user", "_amg_user"):
@@ -1310,7 +1324,7 @@ class DifferentiableFESolver(nn.Module):
         layout (ours): "sample" = the shapes above; "node" = f, load and u are (n, B), the batch INNERMOST -- the layout
         the kernels work in, so a caller that keeps its batch that way (an optimisation loop over kappa, say) pays no
         transposing pass in or out (3 x 16 B per node and sample of a fwd + adjoint step); 2D meshes, same results."""
-        if self.mesh.dim not in (1, 2):
+        if self.mesh.dim not in self._dims:
             raise NotImplementedError("Only 1D and 2D supported")       # reference solver.py:67
         if layout not in ("sample", "node"):
             raise ValueError(f"Unknown layout: {layout!r}")

@@ -98,15 +98,16 @@ int diffhe_chain1d_adjoint(const double* x, const double* kappa, long long kappa
                            double* stage, void* stream);
 
 /* ------------------------------------------------------------------------------
- * General P1 path (any 1D/2D mesh): per-element integrals, deterministic gather
+ * General P1 path (any 1D/2D mesh, P1 tetrahedra in 3D): per-element integrals, deterministic gather
  * assembly into a batch-shared ELL pattern, Dirichlet elimination, batched PCG.
  * ---------------------------------------------------------------------------- */
 
-/* Element integrals, batch-invariant (solver.py:84-88 1D; solver.py:119-139 2D).
+/* Element integrals, batch-invariant (solver.py:84-88 1D; solver.py:119-139 2D; dim = 3: P1 tetrahedra, ours).
  *   coords (dim, n) SoA; elems (npe, m) SoA int32, npe = dim + 1
- *   k0 (npe*npe, m): unit-kappa local stiffness, entry p*npe+q
- *   m0 (npe*npe, m): local load map (1D: diag h/2; 2D: area/9 everywhere)
- *   degenerate triangles (area < 1e-15, solver.py:120-121) get zeros. */
+ *   k0 (npe*npe, m): unit-kappa local stiffness, entry p*npe+q (3D: g_p . g_q / (36 V), g_p = 6 V grad phi_p)
+ *   m0 (npe*npe, m): local load map (1D: diag h/2; 2D: area/9 everywhere; 3D: V/16 everywhere)
+ *   degenerate triangles (area < 1e-15, solver.py:120-121) and tetrahedra (6 V <= 1e-12 l^3, l the longest edge
+ *   from the first vertex) get zeros. */
 int diffhe_p1_element_integrals(const double* coords, const int* elems, int dim, int n, int m,
                                 double* k0, double* m0, void* stream);
 
@@ -155,7 +156,8 @@ int diffhe_ell_assemble_rows_ref(const double* tnum, const double* den, const do
 /* Element-parallel assembly with fp64 global atomics (the literal scatter-add of
  * solver.py:89-92 / :137-140): element integrals are computed from coords and
  * staged in LDS, then scattered for all Bp samples.  `vals` must be zeroed by the
- * caller; `slot_of` (npe*npe, m) gives the ELL slot of entry (p,q) of element e.
+ * caller; `slot_of` (npe*npe, m) gives the ELL slot of entry (p,q) of element e (dim 3: -1 = the entry was
+ * pruned from the pattern as a structural zero, skipped).
  * No Dirichlet handling (use diffhe_ell_apply_dirichlet). */
 int diffhe_ell_assemble_atomic(const double* coords, const int* elems, int dim, const double* kappa,
                                long long kappa_se, long long kappa_sb, const int* slot_of, double* vals, int n,
