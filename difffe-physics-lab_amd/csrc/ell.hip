@@ -472,8 +472,6 @@ __device__ __forceinline__ double ell_row(double acc, const TM* __restrict__ val
                   : ell_row_uniform<SUB, SHARED, 8, false>(acc, vals, cols, x, i, n, W, Bp, b);
   return ell_row_chunks<SUB, 8>(acc, vals, cols, x, i, n, W, Bp, Bv, b);
 }
-__device__ int g_xcd_ranges = 1;   // DIFFHE_ELL_XCD=0 (read once per process, sync_xcd_switch): the plain grid-stride walk
-__device__ __forceinline__ bool xcd_ranges() { return g_xcd_ranges != 0; }
 // for (i over this lane's nodes) BODY -- with batches of >= 64 through wave-uniform indices (see ell_row_uniform), and
 // with the nodes dealt to the XCDs in CONTIGUOUS ranges: workgroups go round-robin to the 8 XCDs (block b -> XCD b % 8),
 // each with its own L2, and a row's neighbours sit close to it in any sensible numbering.  With the plain grid-stride
@@ -486,7 +484,7 @@ __device__ __forceinline__ void wave_node_range(int n, int& first, int& hi, int&
   first = (int)blockIdx.x * 4 + wave_u;
   hi = n;
   step = (int)gridDim.x * 4;
-  if ((gridDim.x & 7) == 0 && xcd_ranges()) {
+  if ((gridDim.x & 7) == 0) {   // else the plain grid-stride walk
     const int chunk = (n + 7) >> 3, lo = ((int)blockIdx.x & 7) * chunk;
     hi = lo + chunk < n ? lo + chunk : n;
     first = lo + ((int)blockIdx.x >> 3) * 4 + wave_u;
@@ -1479,21 +1477,6 @@ inline int cg_blocks(int n, int Bp) { return (int)node_grid(n, Bp).x; }
 
 }  // namespace
 
-// DIFFHE_ELL_XCD=0 switches the XCD-contiguous node ranges off (A/B); copied to the device once per process
-static int sync_xcd_switch(hipStream_t st) {
-  static int done = 0;
-  if (done) return DIFFHE_OK;
-  const int on = getenv("DIFFHE_ELL_XCD") ? atoi(getenv("DIFFHE_ELL_XCD")) : 1;
-  if (!on) {
-    const int rc = diffhe::check(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_xcd_ranges), &on, sizeof(int), 0, hipMemcpyHostToDevice, st));
-    if (rc) return rc;
-    const int rc2 = diffhe::check(hipStreamSynchronize(st));
-    if (rc2) return rc2;
-  }
-  done = 1;
-  return DIFFHE_OK;
-}
-
 // =========================================================================================
 // C ABI
 // =========================================================================================
@@ -1534,7 +1517,7 @@ extern "C" int diffhe_lattice_assemble_rows(const double* local, int local_compa
   const int strip_on = getenv("DIFFHE_ASM_STRIP") ? atoi(getenv("DIFFHE_ASM_STRIP")) : 1;
   if (strip_on && kappa && kappa_se && Bv >= kWave && Bv % kWave == 0 && nx >= 128 && ny >= 64) {
     // per-sample kappa fields on a strip-sized level: every kappa_e loaded once per wave and quad row
-    const int TR = getenv("DIFFHE_ASM_TR") ? atoi(getenv("DIFFHE_ASM_TR")) : 8;
+    constexpr int TR = 8;   // lattice rows per tile
     const int ncb = (nx + 1 + 4 * kAsmCols - 1) / (4 * kAsmCols), nrc = (ny + 1 + TR - 1) / TR;
     hipLaunchKernelGGL(lattice_assemble_strip_kernel, dim3(ncb * nrc, Bv / kWave), dim3(256), 0, (hipStream_t)stream, local,
                        (i64)(local_compact ? 2 : m), (i64)(local_compact ? 1 : -1), kappa, (i64)kappa_se, (i64)kappa_sb,
@@ -1605,7 +1588,7 @@ extern "C" int diffhe_ell_spmv_shared(const double* vals, const int* cols, const
   do {                                                                                                                    \
     const double* pa__ = (pa_);                                                                                           \
     const double* pb__ = (pb_);                                                                                           \
-    if (two_stage && nblk >= 256) {                                                                                       \
+    if (nblk >= 256) {                                                                                                    \
       hipLaunchKernelGGL(cg_slice_kernel, dim3(sgrid.x, kEllSlices, pb__ ? 2 : 1), dim3(256), 0, st, pa__, pb__, nblk, Bp,  \
                          slices);                                                                                         \
       hipLaunchKernelGGL(cg_scalar_kernel, sgrid, dim3(256), 0, st, (int)(phase_), (const double*)slices,                 \
@@ -1630,7 +1613,6 @@ extern "C" int diffhe_ell_cg_solve(const double* vals, const int* cols, const do
   if (Bv != 1 && Bv != Bp) return DIFFHE_E_BADARG;
   if (check_every < 1) check_every = 1;
   hipStream_t st = (hipStream_t)stream;
-  if (int rcx = sync_xcd_switch(st)) return rcx;
   const dim3 grid = diffhe::node_grid(n, Bp);
   const int nblk = grid.x;
   const long long NB = (long long)n * Bp;
@@ -1654,7 +1636,6 @@ extern "C" int diffhe_ell_cg_solve(const double* vals, const int* cols, const do
   S.Bv = Bv;
   const dim3 sgrid((Bp + 63) / 64);
   double* const slices = sc + 16LL * Bp;   // 2 x kEllSlices rows
-  static const int two_stage = getenv("DIFFHE_ELL_SCALAR2") ? atoi(getenv("DIFFHE_ELL_SCALAR2")) : 1;
 
   hipLaunchKernelGGL(cg_init_kernel, grid, dim3(256), 0, st, vals, b, x, r, z, p, partA, partB, n, Bp, Bv);
   ELL_SCALAR(PH_INIT, (const double*)partA, (const double*)partB);
@@ -1727,7 +1708,6 @@ extern "C" int diffhe_ell_amg_pcg_solve(const diffhe_amg_level* levels, int n_le
   H.n_coarse = n_coarse; H.gamma = gamma; H.scale = scale;
   H.w0 = 0.56; H.w1 = 1.39;  // Chebyshev weights for the interval [0.5, 2] of D^-1 A
   hipStream_t st = (hipStream_t)stream;
-  if (int rcx = sync_xcd_switch(st)) return rcx;
   const diffhe_amg_level& L0 = H.lev[0];
   const int n = L0.n, W = L0.W;
   const dim3 grid = diffhe::node_grid(n, Bp);
@@ -1754,7 +1734,6 @@ extern "C" int diffhe_ell_amg_pcg_solve(const diffhe_amg_level* levels, int n_le
   S.Bv = Bv;
   const dim3 sgrid((Bp + 63) / 64);
   double* const slices = sc + 16LL * Bp;   // 2 x kEllSlices rows
-  static const int two_stage = getenv("DIFFHE_ELL_SCALAR2") ? atoi(getenv("DIFFHE_ELL_SCALAR2")) : 1;
   rc = diffhe::check(hipMemsetAsync((void*)S.maxdiag, 0, sizeof(double) * Bv, st));
   if (rc) return rc;
   if (S.xx) {

@@ -971,22 +971,15 @@ template <> struct VLane<v4f> {
 };
 
 // A vector stream of the fused kernels: buffer-resource addressing (raw_buffer_load, 32-bit per-lane offset + uniform
-// SGPR row offset) or, with -DDIFFHE_FLAT_LD=1, global loads off a wave-uniform 64-bit base (SGPR pair, the row offset
-// added by the scalar unit) + the 32-bit per-lane offset (the form strip_body uses).  A/B switch of round 4: the PMC
-// counters show the texture-addresser FIFOs full 28-35 % of the time in the buffer-load kernels and never in strip_body's.
-#ifndef DIFFHE_FLAT_LD
-#define DIFFHE_FLAT_LD 0
-#endif
+// SGPR row offset).  Global loads off a wave-uniform 64-bit base (the form strip_body uses) spilled and ran slower
+// (DESIGN.md section 6, round 4), although the PMC counters show the texture-addresser FIFOs full 28-35 % of the time in
+// the buffer-load kernels and never in strip_body's.
 struct Src {
   rsrc_t r;
-  const char* p;
 };
-__device__ __forceinline__ Src make_src(const void* p) { return Src{make_rsrc(p), (const char*)p}; }
+__device__ __forceinline__ Src make_src(const void* p) { return Src{make_rsrc(p)}; }
 template <typename VT>
-__device__ __forceinline__ VT ldsrc(const Src& s, unsigned voff, unsigned soff) {
-  if constexpr (DIFFHE_FLAT_LD != 0) return *(const VT*)((s.p + (size_t)soff) + (size_t)voff);
-  else return VLane<VT>::ld(s.r, voff, soff);
-}
+__device__ __forceinline__ VT ldsrc(const Src& s, unsigned voff, unsigned soff) { return VLane<VT>::ld(s.r, voff, soff); }
 
 // Where the matrix coefficients of the fused passes come from.
 //   SHARED: batch-shared fp32 copies + reciprocal diagonal, wave-uniform scalar loads (values are plain floats);
@@ -1768,6 +1761,11 @@ constexpr int strip_cols() { return sizeof(TV) == 4 ? 4 : kStripCols; }
 constexpr int kRestrictCols = 2;  // coarse columns per wave of the fused residual + restriction (5 fine columns; 3, 4, 6: slower)
 constexpr int kPupdCols = 4;  // narrower strips for the 3-stream fused CG kernel: fewer VGPRs, more waves
 constexpr int kPartBlocks = 2048;  // capacity (in blocks) of every partial-sum buffer
+// blocks (of 4 waves) a strip-kernel launch aims at; the tile height follows from it
+constexpr int kStripBlocks = 6144;
+// small levels: one wave marching down a strip is latency-bound; the simple kernels win below ~200^2
+// 128: the 129^2 level of a 1024^2 hierarchy takes the strip / fused kernels too (-0.7 ms per step; 64: slower again)
+constexpr int kStripMinW = 128;
 
 struct StripGeom {
   bool use;
@@ -1776,16 +1774,12 @@ struct StripGeom {
 
 inline StripGeom strip_geom(const Level& L, int Bp, int rw = kStripCols, int spl = 1, int nw = 4) {
   StripGeom g{false, 0, 0, 0};
-  // small levels: one wave marching down a strip is latency-bound; the simple kernels win below ~200^2
-  // 128: the 129^2 level of a 1024^2 hierarchy takes the strip / fused kernels too (-0.7 ms per step; 64: slower again)
-  static const int minw = getenv("DIFFHE_STRIP_MINW") ? atoi(getenv("DIFFHE_STRIP_MINW")) : 128;
-  if (Bp < kWave || L.W < minw || L.ny + 1 < 64) return g;
+  if (Bp < kWave || L.W < kStripMinW || L.ny + 1 < 64) return g;
   g.use = true;
   g.ncb = (L.W + nw * rw - 1) / (nw * rw);   // nw = waves (strips) per block
   const int gy = Bp / (kWave * spl);   // spl = samples per lane (2: dia_strip2_kernel)
   if (gy < 1) { g.use = false; return g; }   // fewer samples than one wave of that form holds
-  static const int target4 = getenv("DIFFHE_STRIP_BLOCKS") ? atoi(getenv("DIFFHE_STRIP_BLOCKS")) : 6144;
-  const int target = target4 * 4 / nw;       // the same number of WAVES (and tile height) whatever the block width
+  const int target = kStripBlocks * 4 / nw;   // the same number of WAVES (and tile height) whatever the block width
   int nrc = (target + g.ncb * gy - 1) / (g.ncb * gy);
   const int nyp = L.ny + 1;
   if (nrc > nyp / 8) nrc = nyp / 8;
@@ -1815,30 +1809,36 @@ void launch_strip(const Level& L, int Bv, const double* scale, const TV* xin, co
     if (Bv != 1) bpn += m16 ? 4.0 + 2.0 * (L.nd - 1) : L.nd * (m32 ? 4.0 : 8.0);
     diffhe::account(bpn * (double)L.n * Bp);
   }
-  // development knob: DIFFHE_S1_LDS=<bytes> of dynamic LDS per block caps the blocks resident per CU (160 KB / bytes)
-  const unsigned dyn_lds = getenv("DIFFHE_S1_LDS") ? (unsigned)atoi(getenv("DIFFHE_S1_LDS")) : 0u;
 #define STRIP(ND_, SH_, TM_)                                                                                       \
-  hipLaunchKernelGGL((dia_strip_kernel<TV, TA, TM_, MODE, FUSE, ND_, SH_, XFROMB, RW, MINW>), grid, dim3(256), dyn_lds, st, L,   \
+  hipLaunchKernelGGL((dia_strip_kernel<TV, TA, TM_, MODE, FUSE, ND_, SH_, XFROMB, RW, MINW>), grid, dim3(256), 0, st, L,   \
                      scale, xin, bvec, out, omega, omega_in, ex, part, Bp, g.ncb, g.TR)
 #define STRIP_SHIFT(ND_)                                                                                           \
   hipLaunchKernelGGL((dia_strip_shift_kernel<TV, TA, MODE, FUSE, ND_, XFROMB, RW, MINW>), grid, dim3(256), 0, st, L, scale, \
                      xin, bvec, out, omega, omega_in, ex, part, Bp, g.ncb, g.TR)
+  // fp32 / fp16 coefficient copies only in a cycle with fp32 vectors (m32): other instantiations could never launch
+#define STRIP_ND(ND_)                                                                                              \
+  do {                                                                                                             \
+    if (Bv == 1) STRIP(ND_, true, double);                                                                         \
+    else if constexpr (sizeof(TV) == 4) {                                                                          \
+      if (m16) STRIP(ND_, false, h16m); else if (m32) STRIP(ND_, false, float); else STRIP(ND_, false, double);   \
+    } else STRIP(ND_, false, double);                                                                              \
+  } while (0)
   if (Bv == 1 && L.shift) {
     if (L.nd == 3) STRIP_SHIFT(3); else STRIP_SHIFT(4);
   } else if (L.nd == 3) {
-    if (Bv == 1) STRIP(3, true, double); else if (m16) STRIP(3, false, h16m); else if (m32) STRIP(3, false, float); else STRIP(3, false, double);
+    STRIP_ND(3);
   } else {
-    if (Bv == 1) STRIP(4, true, double); else if (m16) STRIP(4, false, h16m); else if (m32) STRIP(4, false, float); else STRIP(4, false, double);
+    STRIP_ND(4);
   }
+#undef STRIP_ND
 #undef STRIP
 #undef STRIP_SHIFT
 }
 
 // fp32 V-cycle, batch-shared matrix with fp32 coefficient copies and reciprocal diagonal, batch a multiple of 128,
-// no diagonal shift: the two-samples-per-lane kernels apply (DIFFHE_STRIP2=0 switches them off: A/B runs)
+// no diagonal shift: the two-samples-per-lane kernels apply
 inline bool shared32_ok(const Level& L, int Bv, int Bp) {   // the fp32 copies of a batch-shared matrix are there, whole waves
-  static const int on = getenv("DIFFHE_STRIP2") ? atoi(getenv("DIFFHE_STRIP2")) : 1;
-  return on && Bv == 1 && L.v32 && L.rd32 && L.mk32 && !L.shift && Bp % kWave == 0;
+  return Bv == 1 && L.v32 && L.rd32 && L.mk32 && !L.shift && Bp % kWave == 0;
 }
 inline bool strip2_ok(const Level& L, int Bv, int Bp) { return shared32_ok(L, Bv, Bp) && Bp % (2 * kWave) == 0; }
 // the kernels address their tile (`rows` fine rows + the window's two halo rows) with 32-bit byte offsets
@@ -1864,57 +1864,25 @@ void launch_strip2(const Level& L, const double* scale, const float* xin, const 
   diffhe::account(bpn * (double)L.n * Bp);
   // 40 000 B of dynamic LDS per block cap the residency at 4 blocks (16 waves) per CU: measured best for these kernels
   // (sweep over 3 .. 7 blocks per CU on one box, gpurun_out/r3d: first two sweeps 0.506 / prolongation 0.803 / restriction
-  // 0.582 ms at 4 against 0.514-0.523 / 0.815-0.818 / 0.589-0.590 unrestricted); DIFFHE_S2_LDS=<bytes> overrides
-  static const unsigned dyn_lds = getenv("DIFFHE_S2_LDS") ? (unsigned)atoi(getenv("DIFFHE_S2_LDS")) : 40000u;
-#define STRIP2(ND_, DOT_, BST_)                                                                                            \
-  hipLaunchKernelGGL((dia_strip2_kernel<MODE, FUSE, ND_, XFROMB, RW, DOT_, BST_>), grid, dim3(256), dyn_lds, st, L, scale, xin, \
+  // 0.582 ms at 4 against 0.514-0.523 / 0.815-0.818 / 0.589-0.590 unrestricted)
+  constexpr unsigned dyn_lds = 40000u;
+#define STRIP2(ND_, DOT_)                                                                                                  \
+  hipLaunchKernelGGL((dia_strip2_kernel<MODE, FUSE, ND_, XFROMB, RW, DOT_, false>), grid, dim3(256), dyn_lds, st, L, scale, xin, \
                      bvec, out, (float)omega, (float)omega_in, ex, part, Bp, g.ncb, g.TR)
-#define STRIP2B(ND_, DOT_) STRIP2(ND_, DOT_, false)
   if (MODE == M_JACOBI && part) {   // the sweep that leaves the partials of rhs . x (the CG's r.z)
-    if (L.nd == 3) STRIP2B(3, (MODE == M_JACOBI)); else STRIP2B(4, (MODE == M_JACOBI));
+    if (L.nd == 3) STRIP2(3, MODE == M_JACOBI); else STRIP2(4, MODE == M_JACOBI);
   } else {
-    if (L.nd == 3) STRIP2B(3, false); else STRIP2B(4, false);
+    if (L.nd == 3) STRIP2(3, false); else STRIP2(4, false);
   }
-#undef STRIP2B
 #undef STRIP2
 }
 
-// Fused two-stage passes (fused_pre_kernel / fused_post_kernel): DIFFHE_FUSED=0 keeps the four single-stage passes,
-// DIFFHE_FUSED_SPL=1 runs them with one sample per lane
-inline int fused_mode() {
-  static const int on = getenv("DIFFHE_FUSED") ? atoi(getenv("DIFFHE_FUSED")) : 1;
-  static const int spl = getenv("DIFFHE_FUSED_SPL") ? atoi(getenv("DIFFHE_FUSED_SPL")) : 2;
-  return on ? (spl == 1 ? 1 : 2) : 0;
-}
-inline unsigned fused_lds() {
-  // dynamic LDS per block = a cap on the blocks resident per CU; the fused passes (118-125 VGPRs: 4 waves per SIMD
-  // anyway) run best without one (gpurun_out/r3w: 93.9 ms per step at 0, 94.4 at 40 000, 103.8 at 54 000)
-  static const unsigned v = getenv("DIFFHE_FUSED_LDS") ? (unsigned)atoi(getenv("DIFFHE_FUSED_LDS")) : 0u;
-  return v;
-}
-
-// fused passes apply to: a batch-shared matrix with its fp32 copy, reciprocal diagonal and mask (strip2_ok), or a
+// Fused two-stage passes (fused_pre_kernel / fused_post_kernel), two samples per lane where the batch allows (fill_hier).
+// They run without dynamic LDS: a cap on the blocks resident per CU only slowed them (118-125 VGPRs: 4 waves per SIMD
+// anyway; run r3w: 93.9 ms per step uncapped, 94.4 at 40 000 B per block, 103.8 at 54 000).
+// They apply to: a batch-shared matrix with its fp32 copy, reciprocal diagonal and mask (strip2_ok), or a
 // per-sample matrix with the compact copies (fp32 diagonal + scaled fp16 off-diagonals) and the mask, no per-sample scale
 // returns a bit mask: 1 = the PRE pass may be fused, 2 = the POST pass
-// development knob: "a:b:c" = one integer per multigrid level (0 / missing = keep the default)
-// DIFFHE_RUPD: 0 = store A p and read it back in pcg_update_kernel; 1 = recompute it in the residual update (F_RUPD);
-// 2 / 4 = the same with other launch shapes (development)
-inline int rupd_env() {
-  static const int v = getenv("DIFFHE_RUPD") ? atoi(getenv("DIFFHE_RUPD")) : 1;
-  return v;
-}
-
-inline int env_level_int(const char* name, int level) {
-  const char* e = getenv(name);
-  if (!e) return 0;
-  for (int l = 0; l < level; ++l) {
-    e = strchr(e, ':');
-    if (!e) return 0;
-    ++e;
-  }
-  return atoi(e);
-}
-
 inline int fused_ok(const Level& L, int Bv, int Bp, const double* scale) {
   // batch-shared matrix: two samples per lane for multiples of 128, else ONE per lane (batches of 64 or 192 per GPU --
   // BASELINE config 5's shard: same fused passes, fp32 arithmetic, 4-byte accesses)
@@ -1923,9 +1891,8 @@ inline int fused_ok(const Level& L, int Bv, int Bp, const double* scale) {
   // 174 / 206 VGPRs, 2 waves per SIMD, no spills).  Without the cache the PRE pass needed 256 VGPRs and measured slower
   // than its two single passes (forward solve 153 ms against 140), and the POST pass re-read every coefficient row four
   // times (PMC 4.5 passes of traffic for 2.6 algorithmic); 1024^2 x 256 step: 245 (POST only, uncached) -> 236 (POST
-  // cached) -> 219 ms (both, cached; gpurun_out/r5b, r5d).  DIFFHE_FUSED_PS: bit 0 = PRE, bit 1 = POST.
-  static const int per_sample = getenv("DIFFHE_FUSED_PS") ? atoi(getenv("DIFFHE_FUSED_PS")) : 3;
-  return (Bv == Bp && Bp % (2 * kWave) == 0 && L.v32 && L.o16 && L.mk32 && !L.shift && !scale) ? per_sample : 0;
+  // cached) -> 219 ms (both, cached; runs r5b, r5d).
+  return (Bv == Bp && Bp % (2 * kWave) == 0 && L.v32 && L.o16 && L.mk32 && !L.shift && !scale) ? 3 : 0;
 }
 
 void launch_fused_pre(const Level& L, const Level& C, int Bv, const double* scale, const float* rhs, float* x2, float* crhs,
@@ -1935,16 +1902,12 @@ void launch_fused_pre(const Level& L, const Level& C, int Bv, const double* scal
   diffhe::account((9.0 + (Bv == 1 ? 0.0 : 4.0 + 2.0 * (L.nd - 1))) * (double)L.n * Bp);
   const dim3 grid(g.ncb * g.nrc, Bp / (spl * kWave));
 #define FPRE(VT_, ND_, SH_)                                                                                               \
-  hipLaunchKernelGGL((fused_pre_kernel<VT_, ND_, CW, SH_>), grid, dim3(256), fused_lds(), st, L, scale, rhs, x2, crhs,     \
+  hipLaunchKernelGGL((fused_pre_kernel<VT_, ND_, CW, SH_>), grid, dim3(256), 0, st, L, scale, rhs, x2, crhs,              \
                      (float)w0, (float)w1, C.W, C.bc, Bp, g.ncb, g.TR)
   // per-sample coefficients: 206 VGPRs = 2 waves per SIMD; capped at 168 (3 waves) it spills and loses (launch_fused_post)
-  static const int ps_mw = getenv("DIFFHE_FUSED_PS_MW") ? atoi(getenv("DIFFHE_FUSED_PS_MW")) : 2;
-  if (Bv != 1 && L.nd == 3 && (ps_mw & 1))
-    hipLaunchKernelGGL((fused_pre_kernel<v2f, 3, CW, false, 4, 3>), grid, dim3(256), fused_lds(), st, L, scale, rhs, x2, crhs,
-                       (float)w0, (float)w1, C.W, C.bc, Bp, g.ncb, g.TR);
-  else if (Bv != 1) { if (L.nd == 3) FPRE(v2f, 3, false); else FPRE(v2f, 4, false); }
+  if (Bv != 1) { if (L.nd == 3) FPRE(v2f, 3, false); else FPRE(v2f, 4, false); }
   else if (spl == 4 && L.nd == 3)
-    hipLaunchKernelGGL((fused_pre_kernel<v4f, 3, CW, true, 4, 2>), grid, dim3(256), fused_lds(), st, L, scale, rhs, x2, crhs,
+    hipLaunchKernelGGL((fused_pre_kernel<v4f, 3, CW, true, 4, 2>), grid, dim3(256), 0, st, L, scale, rhs, x2, crhs,
                        (float)w0, (float)w1, C.W, C.bc, Bp, g.ncb, g.TR);
   else if (spl >= 2) { if (L.nd == 3) FPRE(v2f, 3, true); else FPRE(v2f, 4, true); }
   else { if (L.nd == 3) FPRE(float, 3, true); else FPRE(float, 4, true); }
@@ -1958,7 +1921,7 @@ void launch_fused_post(const Level& L, const Level& C, int Bv, const double* sca
   diffhe::account(((xin ? 13.0 : 9.0) + (Bv == 1 ? 0.0 : 4.0 + 2.0 * (L.nd - 1))) * (double)L.n * Bp);
   const dim3 grid(g.ncb * g.nrc, Bp / (spl * kWave));
 #define FPOST(VT_, ND_, DOT_, SH_, XZ_)                                                                                      \
-  hipLaunchKernelGGL((fused_post_kernel<VT_, ND_, 4, DOT_, SH_, XZ_>), grid, dim3(256), fused_lds(), st, L, scale, xin, rhs, ec, \
+  hipLaunchKernelGGL((fused_post_kernel<VT_, ND_, 4, DOT_, SH_, XZ_>), grid, dim3(256), 0, st, L, scale, xin, rhs, ec,         \
                      z, (float)wA, (float)wB, C.W, part, Bp, g.ncb, g.TR)
 #define FPOSTD(VT_, ND_, SH_)                                                                                              \
   do {                                                                                                                     \
@@ -1968,11 +1931,10 @@ void launch_fused_post(const Level& L, const Level& C, int Bv, const double* sca
   } while (0)
   // per-sample coefficients: the POST pass needs 173 VGPRs uncapped (176 allocated: 2 waves per SIMD); capped at 168 it runs
   // 3 waves per SIMD without spills: 218.1 -> 213.5 ms per 1024^2 x 256 step of the per-element-field workload; the PRE pass
-  // (206 VGPRs) spills under the same cap: 248.9 ms (gpurun_out/r4e).  DIFFHE_FUSED_PS_MW: bit 0 = PRE, bit 1 = POST capped
-  static const int ps_mw = getenv("DIFFHE_FUSED_PS_MW") ? atoi(getenv("DIFFHE_FUSED_PS_MW")) : 2;
-  if (Bv != 1 && L.nd == 3 && (ps_mw & 2)) {
+  // (206 VGPRs) spills under the same cap: 248.9 ms (run r4e)
+  if (Bv != 1 && L.nd == 3) {
 #define FPOSTM(DOT_, XZ_)                                                                                                  \
-  hipLaunchKernelGGL((fused_post_kernel<v2f, 3, 4, DOT_, false, XZ_, 4, 3>), grid, dim3(256), fused_lds(), st, L, scale, xin, \
+  hipLaunchKernelGGL((fused_post_kernel<v2f, 3, 4, DOT_, false, XZ_, 4, 3>), grid, dim3(256), 0, st, L, scale, xin,         \
                      rhs, ec, z, (float)wA, (float)wB, C.W, part, Bp, g.ncb, g.TR)
     if (!xin) FPOSTM(false, true); else if (part) FPOSTM(true, false); else FPOSTM(false, false);
 #undef FPOSTM
@@ -2145,8 +2107,7 @@ __global__ __launch_bounds__(256) void mg_restrict2_kernel(Level F, Level C, con
 }
 
 inline bool transfers2_ok(const Level& F, const Level& C, int Bp, size_t esz) {
-  static const int on = getenv("DIFFHE_TRANSFER2") ? atoi(getenv("DIFFHE_TRANSFER2")) : 1;
-  return on && esz == 4 && F.nx == 2 * C.nx && F.ny == 2 * C.ny && Bp % (2 * kWave) == 0;
+  return esz == 4 && F.nx == 2 * C.nx && F.ny == 2 * C.ny && Bp % (2 * kWave) == 0;
 }
 inline dim3 transfer2_grid(int n, int Bp) { return dim3((unsigned)(((i64)n + 3) / 4 < 4096 ? ((i64)n + 3) / 4 : 4096), Bp / (2 * kWave)); }
 
@@ -2232,7 +2193,7 @@ __global__ __launch_bounds__(256) void pcg_update_kernel(const double* __restric
                                                           const double* __restrict__ alpha, double* __restrict__ x,
                                                           double* __restrict__ r, float* __restrict__ r32,
                                                           const double* __restrict__ rs, double* __restrict__ part,
-                                                          int n, int Bp, int unroll = 0) {
+                                                          int n, int Bp) {
   __shared__ double lds[4 * kWave];
   const NodeMap nm = node_map(Bp);
   const double a = alpha[nm.b];
@@ -2241,7 +2202,7 @@ __global__ __launch_bounds__(256) void pcg_update_kernel(const double* __restric
   int i = nm.node0;
   // four nodes per trip (the loads of all four in flight together; one node per trip left a wave with two loads
   // outstanding: 4.8 TB/s); same nodes, same order of the partial sum
-  if (unroll && !x)
+  if (!x)
     for (; (i64)i + 3LL * nm.stride < n; i += 4 * nm.stride) {
       double rv[4], av[4];
 #pragma unroll
@@ -2286,14 +2247,13 @@ __global__ __launch_bounds__(256) void mg_add_kernel(const TV* __restrict__ x, T
 template <typename TV>
 __global__ __launch_bounds__(256) void pcg_setx_kernel(const TV* __restrict__ x0, const double* __restrict__ rs,
                                                         double* __restrict__ x, double* __restrict__ part, int n,
-                                                        int Bp, int add = 0, const TV* __restrict__ e0 = nullptr,
-                                                        int unroll = 0) {
+                                                        int Bp, int add = 0, const TV* __restrict__ e0 = nullptr) {
   __shared__ double lds[4 * kWave];
   const NodeMap nm = node_map(Bp);
   const double inv = rs ? 1.0 / rs[nm.b] : 1.0;  // the start was computed from the scaled right-hand side
   double s = 0.0;
   int i = nm.node0;
-  if (unroll && !add)   // four nodes per trip (see pcg_update_kernel)
+  if (!add)   // four nodes per trip (see pcg_update_kernel)
     for (; (i64)i + 3LL * nm.stride < n; i += 4 * nm.stride) {
       TV xv[4], ev[4];
 #pragma unroll
@@ -2384,7 +2344,7 @@ template <typename TP>
 __global__ __launch_bounds__(256) void pcg_finish_kernel(const double* __restrict__ alpha, const TP* __restrict__ p,
                                                           long long slot_stride, int j0, int count, int n_slots,
                                                           const TP* __restrict__ z, const double* __restrict__ rs,
-                                                          double* __restrict__ x, int n, int Bp, int unroll = 0) {
+                                                          double* __restrict__ x, int n, int Bp) {
   // x += sum_{j = j0 .. j0 + count - 1} alpha_j p_j (+ z / rs): direction j lives in slot j % n_slots of `p`, its
   // step lengths in row j % n_slots of `alpha` (0 for samples that had stopped)
   const NodeMap nm = node_map(Bp);
@@ -2393,26 +2353,26 @@ __global__ __launch_bounds__(256) void pcg_finish_kernel(const double* __restric
 #pragma unroll
   for (int k = 0; k < kRingSlots; ++k) a[k] = k < count ? alpha[(long long)((j0 + k) % n_slots) * Bp + nm.b] : 0.0;
   int i = nm.node0;
-  if (unroll)   // two nodes per trip: twice the loads in flight per wave (same operations per node)
-    for (; (i64)i + nm.stride < n; i += 2 * nm.stride) {
-      const i64 o0 = (i64)i * Bp + nm.b, o1 = (i64)(i + nm.stride) * Bp + nm.b;
-      double v0 = x[o0], v1 = x[o1];
-      TP z0 = z ? z[o0] : (TP)0, z1 = z ? z[o1] : (TP)0;
-      TP p0[kRingSlots], p1[kRingSlots];
+  // two nodes per trip: twice the loads in flight per wave (same operations per node)
+  for (; (i64)i + nm.stride < n; i += 2 * nm.stride) {
+    const i64 o0 = (i64)i * Bp + nm.b, o1 = (i64)(i + nm.stride) * Bp + nm.b;
+    double v0 = x[o0], v1 = x[o1];
+    TP z0 = z ? z[o0] : (TP)0, z1 = z ? z[o1] : (TP)0;
+    TP p0[kRingSlots], p1[kRingSlots];
 #pragma unroll
-      for (int k = 0; k < kRingSlots; ++k)
-        if (k < count) {
-          const long long so = (long long)((j0 + k) % n_slots) * slot_stride;
-          p0[k] = p[so + o0];
-          p1[k] = p[so + o1];
-        }
-      if (z) { v0 += zi * (double)z0; v1 += zi * (double)z1; }
+    for (int k = 0; k < kRingSlots; ++k)
+      if (k < count) {
+        const long long so = (long long)((j0 + k) % n_slots) * slot_stride;
+        p0[k] = p[so + o0];
+        p1[k] = p[so + o1];
+      }
+    if (z) { v0 += zi * (double)z0; v1 += zi * (double)z1; }
 #pragma unroll
-      for (int k = 0; k < kRingSlots; ++k)
-        if (k < count) { v0 += a[k] * (double)p0[k]; v1 += a[k] * (double)p1[k]; }
-      x[o0] = v0;
-      x[o1] = v1;
-    }
+    for (int k = 0; k < kRingSlots; ++k)
+      if (k < count) { v0 += a[k] * (double)p0[k]; v1 += a[k] * (double)p1[k]; }
+    x[o0] = v0;
+    x[o1] = v1;
+  }
   for (; i < n; i += nm.stride) {
     const i64 o = (i64)i * Bp + nm.b;
     double v = x[o];
@@ -2667,19 +2627,12 @@ int op_jacobi(const Hier& H, int l, const TV* rhs, const TV* xin, TV* xout, doub
               hipStream_t st) {
   const Level& L = H.lev[l];
   // the plain sweep runs at the HBM rate of its real traffic either way (0.69 ms one sample per lane, 0.70-0.72 two):
-  // it keeps the one-sample kernel; DIFFHE_S2_SWEEP=1 switches it over too
-  static const int sweep2 = getenv("DIFFHE_S2_SWEEP") ? atoi(getenv("DIFFHE_S2_SWEEP")) : 0;
-  StripGeom g;
-  const bool two = sweep2 ? strip2_pick<TV>(L, H.Bv, H.Bp, strip_cols<TV>(), &g)
-                          : (g = strip_geom(L, H.Bp, strip_cols<TV>()), false);
+  // it keeps the one-sample kernel
+  const StripGeom g = strip_geom(L, H.Bp, strip_cols<TV>());
   if (g.use && xin) {
     if (l == 0) kp_begin(KP_SWEEP, st);
-    if (two)
-      launch_strip2<M_JACOBI, false, F_NONE, 4>(L, H.scale, (const float*)xin, (const float*)rhs, (float*)xout, omega, 0.0,
-                                                part, H.Bp, g, st);
-    else
-      launch_strip<TV, M_JACOBI, false, F_NONE, TV, strip_cols<TV>()>(L, H.Bv, H.scale, xin, rhs, xout, omega, 0.0, part,
-                                                                     H.Bp, g, st);
+    launch_strip<TV, M_JACOBI, false, F_NONE, TV, strip_cols<TV>()>(L, H.Bv, H.scale, xin, rhs, xout, omega, 0.0, part,
+                                                                   H.Bp, g, st);
     if (l == 0) kp_end(KP_SWEEP, st);
     return g.ncb * g.nrc;
   }
@@ -2898,16 +2851,11 @@ TV* coarse_solve(const Hier& H, int l, const TV* rhs, double* part, int* nblocks
   const Level& L = H.lev[l];
   if (L.inv && H.Bv == 1 && L.n <= kPartBlocks) {  // dense inverse of the shared level matrix: one launch
     diffhe::account(2.0 * sizeof(TV) * (double)L.n * H.Bp);
-    static const int use_mfma = getenv("DIFFHE_DENSE_MFMA") ? atoi(getenv("DIFFHE_DENSE_MFMA")) : 1;
-    if (use_mfma && H.dense_mfma && sizeof(TV) == 4 && H.Bp >= kWave && !part) {
+    if (H.dense_mfma && sizeof(TV) == 4 && H.Bp >= kWave && !part) {
       // 8 waves per 32 x 32 tile split the sum over j: 1089 nodes x 256 samples = 280 blocks, a chain of 17 dependent
       // 4-step groups per wave (4 waves: 28 us, the scalar fp64-accumulating kernel: 51 us)
-      if (use_mfma == 4)
-        hipLaunchKernelGGL(mg_dense_mfma_kernel<4>, dim3((L.n + 31) / 32, H.Bp / 32), dim3(256), 0, st, L.n, (const float*)L.inv,
-                           H.scale, (const float*)rhs, (float*)H.xa[l], H.Bp);
-      else
-        hipLaunchKernelGGL(mg_dense_mfma_kernel<8>, dim3((L.n + 31) / 32, H.Bp / 32), dim3(512), 0, st, L.n, (const float*)L.inv,
-                           H.scale, (const float*)rhs, (float*)H.xa[l], H.Bp);
+      hipLaunchKernelGGL(mg_dense_mfma_kernel<8>, dim3((L.n + 31) / 32, H.Bp / 32), dim3(512), 0, st, L.n, (const float*)L.inv,
+                         H.scale, (const float*)rhs, (float*)H.xa[l], H.Bp);
       if (nblocks) *nblocks = 0;
     } else if (H.Bp >= kWave) {
       constexpr int RPB = 4;
@@ -2977,7 +2925,7 @@ void resid_restrict(const Hier& H, int l, const TV* x, const TV* rhs_l, hipStrea
   g.ncb = (C.W + 4 * CW - 1) / (4 * CW);
   for (int pass = 0; pass < 2; ++pass) {
     const int gy = H.Bp / (two ? 2 * kWave : kWave);
-    int nrc = (6144 + g.ncb * gy - 1) / (g.ncb * gy);
+    int nrc = (kStripBlocks + g.ncb * gy - 1) / (g.ncb * gy);
     if (nrc > (C.ny + 1) / 4) nrc = (C.ny + 1) / 4;
     if (nrc < 1) nrc = 1;
     g.TR = (C.ny + 1 + nrc - 1) / nrc;  // coarse rows per tile
@@ -3003,11 +2951,10 @@ void resid_restrict(const Hier& H, int l, const TV* x, const TV* rhs_l, hipStrea
 // The PRE pass of a 3-diagonal batch-shared level takes FOUR samples per lane where the batch has whole waves of 256:
 // half the vector-memory instructions per byte at half the waves (219 VGPRs, 2 waves per SIMD).  Measured on the
 // 1024^2 x 256 bench, same box (gpurun_out/r4k): PRE 0.707 -> 0.659 ms; the POST pass (240 VGPRs) 0.998 -> 1.042 ms:
-// it keeps two.  DIFFHE_FUSED_PRE4=0 switches the four-sample form off.
+// it keeps two.
 inline int fused_spl(const Hier& H, const Level& L, bool pre) {
   const int spl = H.Bv == 1 ? H.fuse : 2;
-  static const int pre4 = getenv("DIFFHE_FUSED_PRE4") ? atoi(getenv("DIFFHE_FUSED_PRE4")) : 1;
-  if (pre && pre4 && H.pre4 && H.Bv == 1 && spl == 2 && H.Bp % (4 * kWave) == 0 && L.nd == 3) return 4;
+  if (pre && H.pre4 && H.Bv == 1 && spl == 2 && H.Bp % (4 * kWave) == 0 && L.nd == 3) return 4;
   return spl;
 }
 
@@ -3029,7 +2976,7 @@ int fused_level(const Hier& H, int l, StripGeom* gpre, StripGeom* gpost) {
   // ~6144 blocks whatever the samples per lane: the four-sample form gets tiles of half the height (6 instead of 11 coarse
   // rows at 1024^2 x 256).  Measured (gpurun_out/r4l, same box): 6 rows 0.660 ms, 11 rows 0.681, 16 rows 0.778 -- the
   // number of independent marches matters more than the halo rows
-  int nrc = (6144 * 4 / nw + g.ncb * gy - 1) / (g.ncb * gy);
+  int nrc = (kStripBlocks * 4 / nw + g.ncb * gy - 1) / (g.ncb * gy);
   // Levels of <= 300 columns cannot fill the GPU with 4-coarse-row tiles: shorter tiles (2 coarse rows going down, ~5 fine
   // rows going up) double the independent marches; -1.4 ms per 1024^2 step, neutral on the 513^2 level (gpurun_out/r5j, r5k)
   const bool small = L.W <= 300;
@@ -3037,7 +2984,6 @@ int fused_level(const Hier& H, int l, StripGeom* gpre, StripGeom* gpost) {
   if (nrc > cap) nrc = cap;
   if (nrc < 1) nrc = 1;
   g.TR = (C.ny + 1 + nrc - 1) / nrc;  // coarse rows per tile
-  if (const int tr = env_level_int("DIFFHE_FUSED_TR_PRE", l)) g.TR = tr;
   g.nrc = (C.ny + 1 + g.TR - 1) / g.TR;
   *gpre = g;
   *gpost = strip_geom(L, H.Bp, 4, spl, nw);
@@ -3047,12 +2993,6 @@ int fused_level(const Hier& H, int l, StripGeom* gpre, StripGeom* gpost) {
     while (gpost->ncb * ((nyp + tr - 1) / tr) > kPartBlocks) ++tr;
     gpost->TR = tr;
     gpost->nrc = (nyp + tr - 1) / tr;
-  }
-  if (const int tr = env_level_int("DIFFHE_FUSED_TR_POST", l)) {
-    if (gpost->ncb * ((L.ny + 1 + tr - 1) / tr) <= kPartBlocks) {
-      gpost->TR = tr;
-      gpost->nrc = (L.ny + 1 + tr - 1) / tr;
-    }
   }
   const bool fits = strip2_tile_fits(L, H.Bp, 2 * g.TR + 6) && strip2_tile_fits(L, H.Bp, gpost->TR + 5);
   return fits ? fmask : 0;
@@ -3081,7 +3021,6 @@ TV* vcycle(const Hier& H, const TV* rhs0, double* rz_part, int* rz_blocks, hipSt
       break;
     }
     const int sweeps = H.nu;
-    const bool only = false;
     TV* a = (TV*)H.xa[l];
     TV* b2 = (TV*)H.xb[l];
     fused[l] = false;
@@ -3114,20 +3053,15 @@ TV* vcycle(const Hier& H, const TV* rhs0, double* rz_part, int* rz_blocks, hipSt
     int done;
     if (sweeps >= 2) {
       TV* resu;
-      const int nb = op_jacobi_first2<TV>(H, l, rhs[l], a, b2, H.omega[0], H.omega[1 % H.nu],
-                                          (only && sweeps == 2) ? rz_part : nullptr, &resu, st);
-      if (only && sweeps == 2 && rz_blocks) *rz_blocks = nb;
+      op_jacobi_first2<TV>(H, l, rhs[l], a, b2, H.omega[0], H.omega[1 % H.nu], nullptr, &resu, st);
       if (resu != a) { TV* t = a; a = b2; b2 = t; }
       done = 2;
     } else {
-      const int nb = op_jacobi<TV>(H, l, rhs[l], nullptr, a, H.omega[0], (only && sweeps == 1) ? rz_part : nullptr, st);
-      if (only && sweeps == 1 && rz_blocks) *rz_blocks = nb;
+      op_jacobi<TV>(H, l, rhs[l], nullptr, a, H.omega[0], nullptr, st);
       done = 1;
     }
     for (int s = done; s < sweeps; ++s) {
-      const int nb = op_jacobi<TV>(H, l, rhs[l], a, b2, H.omega[s % H.nu],
-                                   (only && s == sweeps - 1) ? rz_part : nullptr, st);
-      if (only && s == sweeps - 1 && rz_blocks) *rz_blocks = nb;
+      op_jacobi<TV>(H, l, rhs[l], a, b2, H.omega[s % H.nu], nullptr, st);
       TV* t = a; a = b2; b2 = t;
     }
     cur[l] = a;
@@ -3211,17 +3145,16 @@ TV* fmg_start(const Hier& H, const TV* b0, hipStream_t st, const TV** pending = 
   }
   const TV* coarse = (const TV*)H.xF[last];      // the iterate of level l + 1
   if (pending) *pending = nullptr;
-  // 2: the initial-guess form of the cycle below the fine level only.  On the fine level it stores the full ITERATE in
+  // The initial-guess form of the cycle runs below the fine level only.  On the fine level it stores the full ITERATE in
   // fp32 between its passes where the correction form stores a correction ~1e-3 of it: rounding noise of 6e-8 |u|, rough,
   // ~3e-5 of the solution's energy -- measured one PCG iteration more (6 + 6 against 5 + 5 at 1024^2; gpurun_out/r4m)
-  static const int guess_form = getenv("DIFFHE_FMG_GUESS") ? atoi(getenv("DIFFHE_FMG_GUESS")) : 2;
   for (int l = last - 1; l >= 0; --l) {
     const Level& L = H.lev[l];
     const int cycles = (l == 0) ? 1 : H.fmg_coarse_cycles;  // extra cycles on the cheap coarse levels
     StripGeom g1, g2;
     TV* x = (TV*)H.xF[l];
     int c0 = 0;
-    if (guess_form && (l > 0 || guess_form == 1) && (fused_level<TV>(H, l, &g1, &g2) & 2)) {
+    if (l > 0 && (fused_level<TV>(H, l, &g1, &g2) & 2)) {
       // levels with the fused passes: ONE cycle from the prolonged guess -- no prolongation, residual or addition pass
       TV* it = vcycle<TV>(H, bl[l], nullptr, nullptr, st, l, coarse);
       if (cycles == 1) {
@@ -3301,9 +3234,8 @@ static int fill_hier(Hier& H, const diffhe_mg_level* levels, int n_levels, int B
   H.nl = n_levels; H.Bv = Bv; H.Bp = Bp; H.scale = scale; H.nu = nu; H.n_coarse = n_coarse;
   H.coarse_lmax = 2.0;
   H.fmg_coarse_cycles = 1;
-  H.fuse = fused_mode();
+  H.fuse = Bp % (2 * kWave) == 0 ? 2 : 1;   // one sample per lane where the batch is no multiple of 128
   H.pre4 = 1;
-  if (H.fuse == 2 && Bp % (2 * kWave) != 0) H.fuse = 1;   // one sample per lane where the batch is no multiple of 128
   H.dense_mfma = 1;
   for (int k = 0; k < 8; ++k) H.omega[k] = omegas[k < nu ? k : nu - 1];
   return DIFFHE_OK;
@@ -3421,12 +3353,9 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   }
   const dim3 sgrid((Bp + 63) / 64);
   double* const slices = sc + 32LL * Bp;          // kScalarSlices rows: first stage of long partial lists
-  static const int two_stage = getenv("DIFFHE_SCALAR2") ? atoi(getenv("DIFFHE_SCALAR2")) : 1;
-  // several nodes per trip in the grid-stride vector kernels (A/B: DIFFHE_VEC_UNROLL=0)
-  static const int vec_unroll = getenv("DIFFHE_VEC_UNROLL") ? atoi(getenv("DIFFHE_VEC_UNROLL")) : 1;
 #define SCALAR(phase, part, nb_)                                                                                           \
   do {                                                                                                                     \
-    if (two_stage && (int)(nb_) >= 256) {                                                                                  \
+    if ((int)(nb_) >= 256) {                                                                                               \
       hipLaunchKernelGGL(pcg_slice_kernel, dim3(sgrid.x, kScalarSlices), dim3(256), 0, st, (const double*)(part), (int)(nb_), \
                          Bp, slices);                                                                                      \
       hipLaunchKernelGGL(pcg_scalar_kernel, sgrid, dim3(1024), 0, st, (int)(phase), (const double*)slices, kScalarSlices, Bp, \
@@ -3475,14 +3404,10 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   //   [p = z + beta p ; x += alpha_prev p_old ; Ap = A p ; p.Ap]  ->  alpha  ->  [r -= alpha Ap ; r.r]
   //   -> convergence flags  ->  z = V(r) (last sweep leaves r.z)  ->  beta
   // Unfused fallback (small meshes / batches): separate p-update, apply and x/r update kernels.
-  // development knob: strip width / occupancy of the fused CG step (gpurun_out/r2l/variants.txt)
-  static const int pupd_variant = getenv("DIFFHE_PUPD_VARIANT") ? atoi(getenv("DIFFHE_PUPD_VARIANT")) : 0;
   const StripGeom g0 = strip_geom(L0, Bp, kPupdCols);
   const bool fused = g0.use;
   // batch-shared matrix, fp32-stored directions: A p is never stored -- the residual update recomputes it from p (F_RUPD)
-  const int rupd_mode = rupd_env();
-  const bool rupd = fused && f32 && Bv == 1 && rupd_mode != 0;
-  const StripGeom g8 = strip_geom(L0, Bp, 8);
+  const bool rupd = fused && f32 && Bv == 1;
   // cgstep2_kernel: two samples per lane for batches that are multiples of 128, else one
   // (four samples per lane -- what pays in the fused PRE pass -- measured here too: 0.699 -> 0.711 ms at 4 waves per SIMD
   // instead of 8, gpurun_out/r4n; not kept)
@@ -3497,10 +3422,10 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
     const double bytes = 16.0 + (f32 ? 4.0 : 8.0) * (count + (with_z ? 1 : 0));
     if (f32)
       LAUNCH(bytes, pcg_finish_kernel<float>, n, (const double*)alpha_ring, (const float*)(const void*)p, slot_stride,
-             flushed, count, n_slots, with_z ? (const float*)z : (const float*)nullptr, (const double*)S.rs, x, n, Bp, vec_unroll);
+             flushed, count, n_slots, with_z ? (const float*)z : (const float*)nullptr, (const double*)S.rs, x, n, Bp);
     else
       LAUNCH(bytes, pcg_finish_kernel<double>, n, (const double*)alpha_ring, (const double*)p, slot_stride, flushed, count,
-             n_slots, with_z ? (const double*)z : (const double*)nullptr, (const double*)nullptr, x, n, Bp, vec_unroll);
+             n_slots, with_z ? (const double*)z : (const double*)nullptr, (const double*)nullptr, x, n, Bp);
     flushed = it;
   };
   auto precondition = [&](int first) {
@@ -3520,17 +3445,16 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
       ex.p_out = ring + (size_t)(it % n_slots) * slot_stride * esz;
       ex.x = nullptr;            // deferred (flush_directions)
       ex.alpha = nullptr; ex.beta = S.beta; ex.first = first;
-#define NXV(RW_, MINW_)                                                                                               \
-  launch_strip<double, M_APPLY, false, F_PUPD_NX, float, RW_, MINW_>(L0, Bv, scale, (const double*)nullptr,                \
-                                                                      (const double*)nullptr, rupd ? (double*)nullptr : Ap, \
-                                                                      0.0, 0.0, partA, Bp, g0, st, ex)
-      static const int cg2 = getenv("DIFFHE_CG2") ? atoi(getenv("DIFFHE_CG2")) : 1;
+#define NXV(MINW_)                                                                                                    \
+  launch_strip<double, M_APPLY, false, F_PUPD_NX, float, kPupdCols, MINW_>(L0, Bv, scale, (const double*)nullptr,          \
+                                                                         (const double*)nullptr, rupd ? (double*)nullptr : Ap, \
+                                                                         0.0, 0.0, partA, Bp, g0, st, ex)
       // flag bit 8: the caller vouches for a lattice closed by Dirichlet data (lambda_min of the scaled operator bounded
       // away from 0).  With large Neumann parts the search directions are dominated by near-null modes, for which the
       // fp32 stencil cancels to noise: measured 13 / 11 instead of 12 / 9 iterations to 1e-14 there (gpurun_out/r6g)
       // (the host also asks for near-square cells and a hierarchy that reaches the dense coarsest level: on a 382 x 259
       // lattice, which coarsens once, 36 iterations to 1e-14 became 38 -- tools/stress.py seed 6301 case 39)
-      if (f32 && rupd && cg2 && (precond_fp32 & 256) && g2.use && shared32_ok(L0, Bv, Bp) &&
+      if (f32 && rupd && (precond_fp32 & 256) && g2.use && shared32_ok(L0, Bv, Bp) &&
           strip2_tile_fits(L0, Bp, g2.TR + 3)) {
         // fp32 stencil for p.Ap (cgstep2_kernel; packed, two samples per lane, where the batch allows): the step length only
         const dim3 grid(g2.ncb * g2.nrc, Bp / (cspl * kWave));
@@ -3555,9 +3479,7 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
         // The same cap on the V-cycle's strip kernels (already 6-7 waves) made them slower: -2...-6 % end to end.
         // per-sample matrices (coefficients in VGPRs): 4 waves per SIMD, 245.2 ms per step of the per-element-field variant
         // against 249.5 at 7 (gpurun_out/r4w)
-        static const int pupd_ps = getenv("DIFFHE_PUPD_PS") ? atoi(getenv("DIFFHE_PUPD_PS")) : 4;
-        const int pv = Bv != 1 ? pupd_ps : pupd_variant;
-        if (pv == 5 || pv == 1) NXV(4, 1); else if (pv == 4) NXV(4, 4); else if (pv == 6) NXV(4, 6); else NXV(4, 7);
+        if (Bv != 1) NXV(4); else NXV(7);
       }
 #undef NXV
       else
@@ -3605,13 +3527,13 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
       const float* x0 = fmg_start<float>(H, (const float*)r32, st, &e0);
       if (!x0) return DIFFHE_E_LAUNCH;
       LAUNCH((warm ? 20.0 : 12.0) + (e0 ? 4.0 : 0.0), pcg_setx_kernel<float>, n, x0, (const double*)S.rs, x,
-             use_floor ? partA : (double*)nullptr, n, Bp, warm ? 1 : 0, e0, vec_unroll);
+             use_floor ? partA : (double*)nullptr, n, Bp, warm ? 1 : 0, e0);
     } else {
       const double* e0 = nullptr;
       const double* x0 = fmg_start<double>(H, warm ? (const double*)r : b, st, &e0);
       if (!x0) return DIFFHE_E_LAUNCH;
       LAUNCH((warm ? 24.0 : 16.0) + (e0 ? 8.0 : 0.0), pcg_setx_kernel<double>, n, x0, (const double*)nullptr, x,
-             use_floor ? partA : (double*)nullptr, n, Bp, warm ? 1 : 0, e0, vec_unroll);
+             use_floor ? partA : (double*)nullptr, n, Bp, warm ? 1 : 0, e0);
     }
     if (use_floor) SCALAR(S_FLOOR, partA, nblk);
     residual_pass(true);
@@ -3634,19 +3556,16 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
       ex.r32 = r32;
       ex.rscale = S.rs;
       ex.alpha = S.alpha;
-#define RUV(RW_, MINW_, G_)                                                                                            \
-  launch_strip<double, M_APPLY, false, F_RUPD, float, RW_, MINW_>(L0, Bv, scale, (const double*)nullptr,                   \
-                                                                   (const double*)nullptr, (double*)nullptr, 0.0, 0.0,   \
-                                                                   partA, Bp, G_, st, ex)
       // 5 waves per SIMD: 1.30 ms at 1024^2 x 256 (compiler's own choice 1.30, 7 waves 2.31 with spills; gpurun_out/r4q)
-      if (rupd_mode == 2) RUV(kPupdCols, 1, g0); else if (rupd_mode == 4) RUV(8, 1, g8); else RUV(kPupdCols, 5, g0);
-#undef RUV
+      launch_strip<double, M_APPLY, false, F_RUPD, float, kPupdCols, 5>(L0, Bv, scale, (const double*)nullptr,
+                                                                         (const double*)nullptr, (double*)nullptr, 0.0, 0.0,
+                                                                         partA, Bp, g0, st, ex);
     } else {
       LAUNCH(24.0 + (r32 ? 4.0 : 0.0) + (fused ? 0.0 : 24.0), pcg_update_kernel, n, (const double*)p, (const double*)Ap, (const double*)S.alpha, fused ? (double*)nullptr : x,
-             r, r32, (const double*)S.rs, partA, n, Bp, vec_unroll);
+             r, r32, (const double*)S.rs, partA, n, Bp);
     }
     kp_end(KP_UPDATE, st);
-    SCALAR(S_CONV, partA, rupd ? (rupd_mode == 4 ? g8.ncb * g8.nrc : g0.ncb * g0.nrc) : nblk);
+    SCALAR(S_CONV, partA, rupd ? g0.ncb * g0.nrc : nblk);
     ++it;
     // z = V(r) and r.z: the new search direction's ingredients AND the energy-norm error estimate of the iterate;
     // the samples still active are counted in the scalar phase behind it (S_BETA)
@@ -3673,11 +3592,13 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   return DIFFHE_OK;
 }
 
-extern "C" int diffhe_lattice_recompute_ap(void) { return rupd_env() != 0; }
+// kept in the ABI for bench.py: the fp32 CG recomputes A p in the residual update (F_RUPD); the fused passes take two
+// samples per lane
+extern "C" int diffhe_lattice_recompute_ap(void) { return 1; }
 
 extern "C" int diffhe_lattice_blocks(int n, int Bp) { (void)n; (void)Bp; return kPartBlocks; }
 
-extern "C" int diffhe_lattice_fused_passes(void) { return fused_mode(); }
+extern "C" int diffhe_lattice_fused_passes(void) { return 2; }
 
 extern "C" int diffhe_lattice_apply(const diffhe_mg_level* level, int Bv, const double* scale, const double* x,
                                     double* y, double* part, int Bp, void* stream) {
@@ -3880,7 +3801,7 @@ extern "C" int diffhe_lattice_grad_kappa(int nx, int ny, const double* k0, int k
   if (Bp < kWave) return DIFFHE_E_TOOBIG;              // small batches: diffhe_p1_grad_kappa
   const int ncb = (nx + 4 * kGradCols - 1) / (4 * kGradCols);
   const int gy = Bp / kWave;
-  int nrc = (6144 + ncb * gy - 1) / (ncb * gy);
+  int nrc = (kStripBlocks + ncb * gy - 1) / (ncb * gy);
   if (nrc > ny / 8) nrc = ny / 8;
   if (nrc < 1) nrc = 1;
   const int TR = (ny + nrc - 1) / nrc;

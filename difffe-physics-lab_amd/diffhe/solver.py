@@ -306,21 +306,15 @@ class _Engine:
     def _lattice_rows(self, lev, which, kl, kse, ksb, g, v, lf, Bv, st):
         """kappa * k0 gathered into the symmetric diagonals of a lattice level (+ the Dirichlet lift).  The lattice form of
         the gather (contribution lists written into the kernel, each kappa_e read once per node) gives bitwise the values
-        of the list-driven kernel (tests/test_robustness.py); DIFFHE_LATTICE_ASSEMBLE=0 keeps the latter."""
+        of the list-driven kernel (tests/test_robustness.py)."""
         L = self.L
         local = lev.k0 if which == "k0" else lev.k0ref()
-        if os.environ.get("DIFFHE_LATTICE_ASSEMBLE", "1") != "0":
-            # congruent triangles (bit for bit): one (9, 2) table instead of the (9, m) array -- same values
-            small = lev.compact(which) if os.environ.get("DIFFHE_COMPACT_K0", "1") != "0" else None
-            _hip.check(L.diffhe_lattice_assemble_rows(_hip.ptr(small if small is not None else local),
-                                                      1 if small is not None else 0, _hip.ptr(kl), kse, ksb,
-                                                      _hip.ptr(lev.is_bc), _hip.ptr(g), _hip.ptr(v), _hip.ptr(lf), lev.nx,
-                                                      lev.ny, lev.nd, Bv, st), "diffhe_lattice_assemble_rows")
-        else:
-            _hip.check(L.diffhe_ell_assemble_rows(_hip.ptr(local), _hip.ptr(kl), kse, ksb, _hip.ptr(lev.ent_ptr),
-                                                  _hip.ptr(lev.contrib), _hip.ptr(lev.cols), _hip.ptr(lev.store_slot),
-                                                  _hip.ptr(lev.is_bc), _hip.ptr(g), _hip.ptr(v), _hip.ptr(lf), lev.n, lev.m,
-                                                  7, Bv, st), "diffhe_ell_assemble_rows(lattice)")
+        # congruent triangles (bit for bit): one (9, 2) table instead of the (9, m) array -- same values
+        small = lev.compact(which)
+        _hip.check(L.diffhe_lattice_assemble_rows(_hip.ptr(small if small is not None else local),
+                                                  1 if small is not None else 0, _hip.ptr(kl), kse, ksb,
+                                                  _hip.ptr(lev.is_bc), _hip.ptr(g), _hip.ptr(v), _hip.ptr(lf), lev.nx,
+                                                  lev.ny, lev.nd, Bv, st), "diffhe_lattice_assemble_rows")
 
     def pack_cycle_coeffs(self, vals, Bv):
         """Per-sample matrices, fp32-stored V-cycle: (fp32 diagonals, fp16 off-diagonals, per-sample scales) per level --
@@ -443,14 +437,14 @@ class _Engine:
                     arr[i].agg_weights, arr[i].p_cols = lv["agg_weights"].data_ptr(), lv["p_cols"].data_ptr()
                     arr[i].p_vals, arr[i].p_width = lv["p_vals"].data_ptr(), int(lv["p_cols"].shape[0])
         last = chain[-1]
-        if dense_coarse and Bv == 1 and len(chain) > 1 and last["n"] <= 128 and os.environ.get("DIFFHE_AMG_DENSE", "1") != "0":
+        if dense_coarse and Bv == 1 and len(chain) > 1 and last["n"] <= 128:
             nc = last["n"]
             dense = torch.zeros((nc, nc), dtype=torch.float64, device=p.device)
             rows = torch.arange(nc, device=p.device).repeat(last["W"])
             dense.index_put_((rows, last["cols"].reshape(-1).long()), last["vals"].reshape(-1), accumulate=True)
-            inv = torch.linalg.inv(dense)
+            inv, info = torch.linalg.inv_ex(dense)  # a singular last level keeps its Jacobi sweeps
             inv = 0.5 * (inv + inv.t())            # symmetric to the last bit: the cycle stays a symmetric preconditioner
-            if bool(torch.isfinite(inv).all()):
+            if int(info) == 0 and bool(torch.isfinite(inv).all()):
                 last["dense_inv"] = inv.contiguous()
                 arr[len(chain) - 1].dense_inv = last["dense_inv"].data_ptr()
         return arr, chain      # keep `chain` alive: it owns the coarse value tensors
@@ -494,7 +488,7 @@ class _Engine:
             # lattice mesh, per-element gradient of every sample: strip pass (each nodal value read once per wave)
             lev = p.levels[0]
             dk_e = torch.empty((p.m, Bp), dtype=torch.float64, device=p.device)
-            small = lev.compact("k0") if os.environ.get("DIFFHE_COMPACT_K0", "1") != "0" else None
+            small = lev.compact("k0")
             _hip.check(L.diffhe_lattice_grad_kappa(lev.nx, lev.ny, _hip.ptr(small if small is not None else lev.k0),
                                                    1 if small is not None else 0, _hip.ptr(lam), _hip.ptr(x), _hip.ptr(p.g),
                                                    _hip.ptr(dk_e), Bp, _stream(p.device)), "diffhe_lattice_grad_kappa")

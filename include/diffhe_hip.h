@@ -339,16 +339,17 @@ int diffhe_lattice_kernel_profile(int id, double* total_ms, long long* launches)
  * `part`, diffhe_lattice_blocks(n, Bp) * Bp doubles) and one damped-Jacobi sweep
  * xout = xin + omega (rhs - A xin)/D  (xin NULL = 0). */
 int diffhe_lattice_blocks(int n, int Bp);
-/* 0: the fp32 V-cycle of a batch-shared matrix runs four single-stage strip passes per level; 1 / 2: the fused
- * two-stage passes (pre-smoothing + residual + restriction; prolongation + post-smoothing) with that many samples per
- * lane (environment DIFFHE_FUSED / DIFFHE_FUSED_SPL; flag bit 6 of diffhe_lattice_pcg_solve switches them off per call).
- * With them, kernel-profile id 2 times the fused PRE pass (9 B per node and sample), id 4 the fused POST pass (13 B),
- * ids 3 and 5 see no launches. */
+/* 2: the fp32 V-cycle of a batch-shared matrix runs the fused two-stage passes (pre-smoothing + residual + restriction;
+ * prolongation + post-smoothing) with two samples per lane (one where the batch is no multiple of 128); flag bit 6 of
+ * diffhe_lattice_pcg_solve switches them off per call (four single-stage strip passes per level).  Always 2 since the
+ * development switches were retired.  With them, kernel-profile id 2 times the fused PRE pass (9 B per node and
+ * sample), id 4 the fused POST pass (13 B), ids 3 and 5 see no launches. */
 int diffhe_lattice_fused_passes(void);
 /* 1: with a batch-shared matrix and fp32-stored search directions the PCG never stores A p -- the fused CG step keeps it
  * in registers for p.Ap (12 B per node and sample: z, p_old read, p written) and the residual update recomputes it from
- * the stored p (24 B: p, r read; r and its fp32 copy written; kernel-profile id 1).  0 (environment DIFFHE_RUPD=0): A p
- * is written by the CG step (20 B) and read back by pcg_update_kernel (28 B). */
+ * the stored p (24 B: p, r read; r and its fp32 copy written; kernel-profile id 1).  Always 1 since the development
+ * switches were retired; fp64 directions, per-sample matrices and the unfused loop still write A p (20 B) and read it
+ * back in pcg_update_kernel (28 B). */
 int diffhe_lattice_recompute_ap(void);
 int diffhe_lattice_apply(const diffhe_mg_level* level, int Bv, const double* scale, const double* x, double* y,
                          double* part, int Bp, void* stream);
