@@ -6,14 +6,16 @@ itself runs in hand-written HIP kernels (libdiffhe_hip.so, include/diffhe_hip.h)
 Extras that have no reference counterpart live in submodules only
 (`diffhe.distributed`: batch sharding over ranks; `diffhe.heat`: time stepping of the heat equation, the
 reference's roadmap item; `diffhe.tet3d`: `DifferentiableFESolver3D`, solves on 3D tetrahedral meshes such as
-`FEMesh.box`; `diffhe._hip`: the ctypes binding).
+`FEMesh.box`; `diffhe.shape`: `ShapeDifferentiableFESolver`, gradients with respect to the node coordinates, also
+exported here; `diffhe._hip`: the ctypes binding).
 """
-from . import loss as _loss, mesh as _mesh, neural as _neural, solver as _solver
+from . import loss as _loss, mesh as _mesh, neural as _neural, shape as _shape, solver as _solver
 
 FEMesh = _mesh.FEMesh
 DifferentiableFESolver = _solver.DifferentiableFESolver
 PhysicsLoss = _loss.PhysicsLoss
 NeuralPDE = _neural.NeuralPDE
+ShapeDifferentiableFESolver = _shape.ShapeDifferentiableFESolver
 
-__all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE")
+__all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

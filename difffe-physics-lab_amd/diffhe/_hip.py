@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DIFFHE_HIP_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libdiffhe_hip.so"))
 
 _P, _I, _L, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_double
-ABI_VERSION = 7     # DIFFHE_ABI_VERSION of include/diffhe_hip.h this binding was written against
+ABI_VERSION = 8     # DIFFHE_ABI_VERSION of include/diffhe_hip.h this binding was written against
 
 
 class MgLevel(C.Structure):
@@ -77,6 +77,8 @@ SIGNATURES = {
     "diffhe_grad_kappa_blocks": (_I, [_I, _I]),
     "diffhe_p1_grad_kappa": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "diffhe_p1_grad_kappa_shared": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "diffhe_p1_shape_grad": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _D, _P, _P, _P,
+                                  _P, _P]),
     "diffhe_to_node_major": (_I, [_P, _L, _P, _P, _I, _I, _I, _P]),
     "diffhe_to_sample_major": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),
 }

@@ -653,6 +653,22 @@ class SolvePlan:
             self._lumped_mass = torch.from_numpy(_lumped_mass(self._nodes_host, self._elements)).to(self.device)
         return self._lumped_mass
 
+    def shape_incidence(self):
+        """(inc_ptr (n+1), inc) int32 on the device: per node, the codes e * npe + p of the (element, local vertex) pairs
+        that touch it, in element order -- the fixed summation order of the node gradient (diffhe_p1_shape_grad).
+        Connectivity only; built once per plan."""
+        cached = self.__dict__.get("_shape_inc")
+        if cached is None:
+            flat = self._elements.reshape(-1)
+            if len(flat) >= 2 ** 31:
+                raise ValueError("mesh too large for int32 incidence lists")
+            order = np.argsort(flat, kind="stable").astype(np.int32)    # grouped by node, element order inside
+            ptr = np.zeros(self.n + 1, dtype=np.int64)
+            np.cumsum(np.bincount(flat, minlength=self.n), out=ptr[1:])
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
+            cached = self.__dict__["_shape_inc"] = (dev(ptr.astype(np.int32)), dev(order))
+        return cached
+
     def ensure_ell(self):
         """ELL pattern, gather lists, element integrals and the ELL load matrix of the general path."""
         with self._build_lock:

@@ -1,0 +1,192 @@
+"""Solves differentiable with respect to the mesh node coordinates (ours: shape / mesh optimisation).
+
+`ShapeDifferentiableFESolver` is `DifferentiableFESolver3D` (1D, 2D and 3D P1 meshes; same constructor, options, kappa
+layouts and `layout=`) that also returns dL/dX when `mesh.nodes.requires_grad` is set -- a leaf, or a tensor computed
+from parameters (a mesh deformation driven by a network, say).  Then `forward` runs the custom op `diffhe::fe_solve_shape`,
+which takes the nodes as an input; its backward runs ONE adjoint solve for the kappa / f / load / node gradients together
+and contracts the adjoint lambda and u once more per element (`diffhe_p1_shape_grad`, csrc/shape.hip):
+
+    dL/dX = -lambda^T (dK/dX) u + lambda^T (dF/dX) - c lambda^T (dM_L/dX) u
+
+with the load map and lumped mass the solve uses (F_p = A_e / (d+1) * mean f in 2D and 3D, the reference's trapezoid
+h/2 f_i in 1D).  Any explicit dependence the caller's graph carries (an f computed from X) adds through autograd as usual.
+Without nodes requiring grad `forward` is exactly the base class.
+
+Convention: this is the full P1 shape derivative.  In 1D it equals the reference's autograd to `mesh.nodes`, where
+h_e = x_j - x_i is not detached.  In 2D it is NOT the reference's partial derivative through `area` alone (the reference
+detaches b and c, solver.py:125-134, as `DifferentiableFESolver` keeps doing by reading detached coordinates).
+
+The batch shares one mesh, so dL/dX sums over the samples.  Not covered: P2 meshes (NotImplementedError), second order
+through X (a backward with create_graph=True while the nodes need grad raises NotImplementedError), node gradients
+through `diffhe.heat.HeatEquation`.  A moved mesh builds a new solve plan, as any change of `mesh.nodes` does.
+
+Layouts handed to the kernel: the 2D / 3D / general paths keep u and lambda node-major (n, Bp); the 1D chain keeps its
+sample-major (B, n) arrays and the kernel takes strides (sn, sb) -- no transposing copy on either path.
+"""
+from __future__ import annotations
+
+import weakref
+from typing import Tuple
+
+import torch
+
+from . import _hip
+from . import solver as _solver
+from .plan import _stream
+from .solver import K_ELEM, K_SAMPLE, K_SCALAR, _SOLVERS, _STATES, _TOKENS, _StateGuard
+from .tet3d import DifferentiableFESolver3D
+
+__all__ = ("ShapeDifferentiableFESolver",)
+
+
+def _check_nodes(mesh, nodes: torch.Tensor, version: int) -> None:
+    """The nodes handed to the op must be the mesh's own tensor at the version `forward` saw: the solve plan is built
+    from (and keyed on) exactly that tensor."""
+    ref = mesh.nodes
+    same = nodes is ref or (nodes.device == ref.device and nodes.data_ptr() == ref.data_ptr()
+                            and tuple(nodes.shape) == tuple(ref.shape) and nodes.stride() == ref.stride())
+    if not same:
+        raise ValueError("diffhe: the nodes given to fe_solve_shape are not mesh.nodes of the solver")
+    if nodes._version != version or ref._version != version:
+        raise ValueError(f"diffhe: mesh.nodes was modified in place (version {nodes._version}, expected {version}); "
+                         "the solve plan would not match the coordinates")
+
+
+def _shape_inputs(state, kappa: torch.Tensor, f: torch.Tensor, node_major: bool) -> None:
+    """Kappa and f as the node-gradient kernel reads them (device views of the op's inputs, strides instead of copies)."""
+    plan, mode, B, m = state.plan, state.mode, state.B, state.plan.m
+    k = kappa.detach().to(plan.device, torch.float64)
+    if mode == K_SCALAR:
+        state.shape_kappa = (k.reshape(1).contiguous(), 0, 0)
+    elif mode == K_SAMPLE:
+        state.shape_kappa = (k.reshape(B).contiguous(), 0, 1)
+    elif mode == K_ELEM:
+        state.shape_kappa = (k.reshape(m).contiguous(), 1, 0)
+    elif state.kappa_em:                                             # (m, B), layout='node'
+        state.shape_kappa = (k.contiguous(), B, 1)
+    else:                                                            # (B, m)
+        state.shape_kappa = (k.reshape(B, m).contiguous(), 1, m)
+    fd = f.detach().to(plan.device, torch.float64)
+    if fd.dim() == 1:
+        state.shape_f = (fd.contiguous(), 1, 0)                      # one forcing for the batch
+    else:
+        fv = fd.t() if node_major else fd                            # (B, n) view
+        state.shape_f = (fv, fv.stride(1), fv.stride(0))
+
+
+def _node_grad(state) -> torch.Tensor:
+    """(n, dim) fp64 dL/dX from the saved solve and the adjoint that `_solve_backward` kept (state.adjoint)."""
+    plan = state.plan
+    L = _hip.lib()
+    n, m, dim, B = plan.n, plan.m, plan.dim, state.B
+    inc_ptr, inc = plan.shape_incidence()
+    if state.path.startswith("chain1d"):
+        u = state.saved[3]                                           # (B, n), Dirichlet values included
+        lam = torch.where(plan.is_bc.bool(), torch.zeros((), dtype=torch.float64, device=plan.device),
+                          state.adjoint / plan.lumped_mass())        # lambda = df / lumped mass, as grad_load
+        lam = lam.contiguous()
+        sn, sb, g = 1, n, None
+    else:
+        _vals, u, Bp, _Bv, _scale = state.saved                      # (n, Bp) eliminated-system solution
+        lam = state.adjoint
+        sn, sb, g = Bp, 1, plan.g
+    kdev, kse, ksb = state.shape_kappa
+    fdev, fsn, fsb = state.shape_f
+    work = torch.empty((m, (dim + 1) * dim), dtype=torch.float64, device=plan.device)
+    grad = torch.empty((n, dim), dtype=torch.float64, device=plan.device)
+    _hip.check(L.diffhe_p1_shape_grad(_hip.ptr(plan.coords), _hip.ptr(plan.elems), dim, n, m, B, _hip.ptr(u),
+                                      _hip.ptr(g), _hip.ptr(lam), sn, sb, _hip.ptr(kdev), kse, ksb, _hip.ptr(fdev),
+                                      fsn, fsb, float(state.reaction), _hip.ptr(inc_ptr), _hip.ptr(inc),
+                                      _hip.ptr(work), _hip.ptr(grad), _stream(plan.device)), "diffhe_p1_shape_grad")
+    return grad
+
+
+@torch.library.custom_op("diffhe::fe_solve_shape", mutates_args=())
+def fe_solve_shape(kappa: torch.Tensor, f: torch.Tensor, load: torch.Tensor, nodes: torch.Tensor, nodes_version: int,
+                   handle: int, save: bool, node_major: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`diffhe::fe_solve` with the node coordinates as an input: (u, token).  `nodes` must be the solver's mesh.nodes at
+    version `nodes_version` (the tensor the plan is built from)."""
+    solver = _SOLVERS[handle]
+    _check_nodes(solver.mesh, nodes, nodes_version)
+    u, state = _solver._solve_forward(solver, kappa, f, load, node_major)
+    token = 0
+    if save:
+        _shape_inputs(state, kappa, f, node_major)
+        token = next(_TOKENS)
+        _STATES[token] = state
+    return u, torch.tensor(token, dtype=torch.int64)
+
+
+@fe_solve_shape.register_fake
+def _fe_solve_shape_fake(kappa, f, load, nodes, nodes_version, handle, save, node_major=False):
+    return _solver._fe_solve_fake(kappa, f, load, handle, save, node_major)
+
+
+@torch.library.custom_op("diffhe::fe_solve_shape_backward", mutates_args=())
+def fe_solve_shape_backward(gbar: torch.Tensor, token: torch.Tensor, need_k: bool, need_f: bool, need_load: bool,
+                            need_x: bool, kappa_like: torch.Tensor, f_like: torch.Tensor, load_like: torch.Tensor,
+                            nodes_like: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dL/dkappa, dL/df, dL/dload, dL/dX) of the forward call named by `token` from ONE adjoint solve; unused gradients
+    come back empty."""
+    state = _STATES.get(int(token))
+    if state is None:
+        raise RuntimeError("diffhe: adjoint state of this solve is gone (its autograd graph was freed)")
+    state.keep_adjoint = need_x
+    gk, gf, gl = _solver._solve_backward(state, gbar, need_k, need_f, need_load)
+    gx = _node_grad(state).to(nodes_like.device, nodes_like.dtype) if need_x else nodes_like.new_empty(0)
+    state.adjoint = None
+    return (gk if gk is not None else kappa_like.new_empty(0), gf if gf is not None else f_like.new_empty(0),
+            gl.to(load_like.dtype) if gl is not None else load_like.new_empty(0), gx)
+
+
+@fe_solve_shape_backward.register_fake
+def _fe_solve_shape_backward_fake(gbar, token, need_k, need_f, need_load, need_x, kappa_like, f_like, load_like,
+                                  nodes_like):
+    return (torch.empty_like(kappa_like) if need_k else kappa_like.new_empty(0),
+            torch.empty_like(f_like) if need_f else f_like.new_empty(0),
+            torch.empty_like(load_like) if need_load else load_like.new_empty(0),
+            torch.empty_like(nodes_like) if need_x else nodes_like.new_empty(0))
+
+
+def _shape_setup_context(ctx, inputs, output):
+    kappa, f, load, nodes, _version, handle, _save, node_major = inputs
+    real = not isinstance(output[1], torch._subclasses.FakeTensor)
+    sentinel = (torch.empty(0),) if real else ()     # frees the adjoint state with the saved tensors (see solver.py)
+    ctx.save_for_backward(output[1], kappa, f, load, nodes, *((output[0],) if node_major else ()), *sentinel)
+    ctx.handle, ctx.node_major = handle, bool(node_major)
+    if real:
+        weakref.finalize(sentinel[0], _STATES.pop, int(output[1]), None)
+        ctx.state_guard = _StateGuard(int(output[1]))
+
+
+def _shape_backward(ctx, grad_u, _grad_token):
+    if torch.is_grad_enabled():
+        raise NotImplementedError("diffhe: second-order derivatives through the node coordinates are not implemented "
+                                  "(backward with create_graph=True while mesh.nodes requires grad)")
+    token, kappa, f, load, nodes = ctx.saved_tensors[:5]
+    need_k, need_f, need_load, need_x = ctx.needs_input_grad[:4]
+    gk, gf, gl, gx = torch.ops.diffhe.fe_solve_shape_backward(grad_u, token, need_k, need_f, need_load, need_x, kappa,
+                                                              f, load, nodes)
+    return ((gk if need_k else None), (gf if need_f else None), (gl if need_load else None), (gx if need_x else None),
+            None, None, None, None)
+
+
+torch.library.register_autograd("diffhe::fe_solve_shape", _shape_backward, setup_context=_shape_setup_context)
+
+
+class ShapeDifferentiableFESolver(DifferentiableFESolver3D):
+    """`DifferentiableFESolver3D` that also differentiates with respect to `mesh.nodes` (see the module docstring)."""
+
+    _dims = (1, 2, 3)
+
+    def _solve_op(self, f64: torch.Tensor, load64: torch.Tensor, node_major: bool) -> torch.Tensor:
+        nodes = self.mesh.nodes
+        if not (nodes.requires_grad and torch.is_grad_enabled()):
+            return super()._solve_op(f64, load64, node_major)
+        if self.mesh.elements.shape[1] != self.mesh.dim + 1:
+            raise NotImplementedError("diffhe: node gradients are implemented for P1 elements only "
+                                      "(this mesh has P2 elements and mesh.nodes requires grad)")
+        _SOLVERS[id(self)] = self
+        u, _token = torch.ops.diffhe.fe_solve_shape(self._kappa, f64, load64, nodes, nodes._version, id(self), True,
+                                                    node_major)
+        return u

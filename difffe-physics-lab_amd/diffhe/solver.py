@@ -892,6 +892,8 @@ def _solve_backward(ctx, gbar, need_k, need_f, need_load=False):
                    "diffhe_chain1d_adjoint")
         dk_sample = part.sum(dim=1)                      # (B,) tiny host-side glue
         dk_elem = dk_e
+        if getattr(ctx, "keep_adjoint", False):          # diffhe.shape: lambda on the free nodes is df / lumped mass
+            ctx.adjoint = df
         if need_load:
             grad_load = df / plan.lumped_mass()
         need_f = need_f_user
@@ -927,6 +929,8 @@ def _solve_backward(ctx, gbar, need_k, need_f, need_load=False):
             if getattr(ctx, "ell_inv_kappa", None) is not None:
                 rhs = rhs * ctx.ell_inv_kappa
             lam, its, bad, relres = eng.cg(vals, rhs, Bp, Bv)
+        if getattr(ctx, "keep_adjoint", False):          # diffhe.shape: the node gradient contracts the same lambda
+            ctx.adjoint = lam
         info.adj_iterations = its
         info.adj_max_relres = float(relres[:B].max())
         info.not_converged += bad
@@ -1329,11 +1333,8 @@ class DifferentiableFESolver(nn.Module):
             if self.mesh.dim == 1:     # the 1D scan works sample-major: transposing views in and out
                 return self.forward(f.t(), None if load is None else load.t()).t()
             f64 = f.to(torch.float64)
-            _SOLVERS[id(self)] = self
             load64 = f64.new_empty(0) if load is None else load.to(torch.float64)
-            save = torch.is_grad_enabled() and (self._kappa.requires_grad or f64.requires_grad or load64.requires_grad)
-            u, _token = torch.ops.diffhe.fe_solve(self._kappa, f64, load64, id(self), save, True)
-            return u
+            return self._solve_op(f64, load64, True)
         f64 = f.to(torch.float64)
         if f64.dim() == 2 and f64.shape == (n, 1):
             f64 = f64.reshape(n)                                          # (n,1) works in the reference too
@@ -1341,7 +1342,6 @@ class DifferentiableFESolver(nn.Module):
             raise ValueError(f"f must be (n,) or (B,n) with n={n}, got {tuple(f.shape)}")
         elif f64.dim() == 1 and f64.shape[0] != n:
             raise ValueError(f"f must have {n} nodal values, got {f64.shape[0]}")
-        _SOLVERS[id(self)] = self
         if load is None:
             load64 = f64.new_empty(0)
         else:
@@ -1350,8 +1350,13 @@ class DifferentiableFESolver(nn.Module):
                 raise ValueError(f"load must be (n,) or (B,n) with n={n}, got {tuple(load.shape)}")
             if load64.dim() == 2 and f64.dim() == 1:
                 f64 = f64.reshape(1, n).expand(load64.shape[0], n)
+        return self._solve_op(f64, load64, False)
+
+    def _solve_op(self, f64: torch.Tensor, load64: torch.Tensor, node_major: bool) -> torch.Tensor:
+        """u = the diffhe::fe_solve op on checked float64 inputs (load64 empty: no extra load)."""
+        _SOLVERS[id(self)] = self
         save = torch.is_grad_enabled() and (self._kappa.requires_grad or f64.requires_grad or load64.requires_grad)
-        u, _token = torch.ops.diffhe.fe_solve(self._kappa, f64, load64, id(self), save, False)
+        u, _token = torch.ops.diffhe.fe_solve(self._kappa, f64, load64, id(self), save, node_major)
         return u
 
     # reference-private names kept as aliases (SURVEY 8(b)); both run the HIP path

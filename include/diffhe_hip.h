@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DIFFHE_ABI_VERSION 7
+#define DIFFHE_ABI_VERSION 8
 
 #define DIFFHE_OK 0
 #define DIFFHE_E_BADARG (-1)
@@ -421,6 +421,21 @@ int diffhe_p1_grad_kappa(const int* elems, const double* k0, const double* lam, 
  * gradient is never materialised.  ABI v6. */
 int diffhe_p1_grad_kappa_shared(const int* elems, const double* k0, const double* lam, const double* u, const double* g,
                                 int npe, int m, int B, int Bp, double* dk, void* stream);
+
+/* Shape derivative dL/dX of a P1 solve (1D segments, triangles, tetrahedra; ABI v8):
+ *   grad[i, k] = sum over the elements e at node i of A_e [ (q_e - tr T_e) I + T_e + T_e^T ] grad phi_i,
+ *   T_e = sum_{b<B} kappa[e*kse + b*ksb] grad u_eb (x) grad lambda_eb,   q_e = sum_{b<B} (load_eb - c lambda_eb . u_eb / (d+1)),
+ *   load_eb = (sum_p lambda_pb)(sum_p f_pb) / (d+1)^2 in 2D / 3D, sum_p lambda_pb f_pb / 2 in 1D (the load maps of the
+ *   solve), with A_e the element's length / area / volume; degenerate elements (the assembly's thresholds) add nothing.
+ * coords (dim, n), elems (dim+1, m) as the element kernels take them.  u and lam (the adjoint, 0 on Dirichlet nodes) share
+ * the strides: entry (i, b) at i*sn + b*sb -- (n, Bp) node-major: sn = Bp, sb = 1; the 1D chain's (B, n): sn = 1, sb = n;
+ * g (n) is added to u (the eliminated-system solution) and may be NULL.  f (i, b) at i*fsn + b*fsb (fsb = 0: one forcing
+ * for the batch), may be NULL.  inc_ptr (n+1) / inc: per node, the codes e*(dim+1) + p of its (element, local vertex)
+ * pairs in a fixed order; work (m, (dim+1)*dim) doubles; grad (n, dim).  No atomics: bitwise reproducible. */
+int diffhe_p1_shape_grad(const double* coords, const int* elems, int dim, int n, int m, int B, const double* u,
+                         const double* g, const double* lam, long long sn, long long sb, const double* kappa,
+                         long long kse, long long ksb, const double* f, long long fsn, long long fsb, double c,
+                         const int* inc_ptr, const int* inc, double* work, double* grad, void* stream);
 
 /* Layout changes between the API's (B, n) and the solver's (n, Bp).
  * to_node_major: dst[i*Bp + b] = src[b*ld + i] (b < B), 0 for padding samples and
