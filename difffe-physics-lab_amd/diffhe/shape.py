@@ -25,7 +25,6 @@ sample-major (B, n) arrays and the kernel takes strides (sn, sb) -- no transposi
 """
 from __future__ import annotations
 
-import weakref
 from typing import Tuple
 
 import torch
@@ -33,7 +32,7 @@ import torch
 from . import _hip
 from . import solver as _solver
 from .plan import _stream
-from .solver import K_ELEM, K_SAMPLE, K_SCALAR, _SOLVERS, _STATES, _TOKENS, _StateGuard
+from .solver import _SOLVERS, _STATES, _TOKENS, _kappa_strided, _save_for_adjoint, _state_of
 from .tet3d import DifferentiableFESolver3D
 
 __all__ = ("ShapeDifferentiableFESolver",)
@@ -54,18 +53,8 @@ def _check_nodes(mesh, nodes: torch.Tensor, version: int) -> None:
 
 def _shape_inputs(state, kappa: torch.Tensor, f: torch.Tensor, node_major: bool) -> None:
     """Kappa and f as the node-gradient kernel reads them (device views of the op's inputs, strides instead of copies)."""
-    plan, mode, B, m = state.plan, state.mode, state.B, state.plan.m
-    k = kappa.detach().to(plan.device, torch.float64)
-    if mode == K_SCALAR:
-        state.shape_kappa = (k.reshape(1).contiguous(), 0, 0)
-    elif mode == K_SAMPLE:
-        state.shape_kappa = (k.reshape(B).contiguous(), 0, 1)
-    elif mode == K_ELEM:
-        state.shape_kappa = (k.reshape(m).contiguous(), 1, 0)
-    elif state.kappa_em:                                             # (m, B), layout='node'
-        state.shape_kappa = (k.contiguous(), B, 1)
-    else:                                                            # (B, m)
-        state.shape_kappa = (k.reshape(B, m).contiguous(), 1, m)
+    call, plan = state.call, state.plan
+    state.shape_kappa = _kappa_strided(kappa, call.mode, call.kappa_em, call.B, plan.m, plan.device)
     fd = f.detach().to(plan.device, torch.float64)
     if fd.dim() == 1:
         state.shape_f = (fd.contiguous(), 1, 0)                      # one forcing for the batch
@@ -74,29 +63,20 @@ def _shape_inputs(state, kappa: torch.Tensor, f: torch.Tensor, node_major: bool)
         state.shape_f = (fv, fv.stride(1), fv.stride(0))
 
 
-def _node_grad(state) -> torch.Tensor:
-    """(n, dim) fp64 dL/dX from the saved solve and the adjoint that `_solve_backward` kept (state.adjoint)."""
+def _node_grad(state, lam: torch.Tensor) -> torch.Tensor:
+    """(n, dim) fp64 dL/dX from the saved solve and its adjoint `lam` (as `_solve_backward` returns it)."""
     plan = state.plan
     L = _hip.lib()
-    n, m, dim, B = plan.n, plan.m, plan.dim, state.B
+    n, m, dim, B = plan.n, plan.m, plan.dim, state.call.B
     inc_ptr, inc = plan.shape_incidence()
-    if state.path.startswith("chain1d"):
-        u = state.saved[3]                                           # (B, n), Dirichlet values included
-        lam = torch.where(plan.is_bc.bool(), torch.zeros((), dtype=torch.float64, device=plan.device),
-                          state.adjoint / plan.lumped_mass())        # lambda = df / lumped mass, as grad_load
-        lam = lam.contiguous()
-        sn, sb, g = 1, n, None
-    else:
-        _vals, u, Bp, _Bv, _scale = state.saved                      # (n, Bp) eliminated-system solution
-        lam = state.adjoint
-        sn, sb, g = Bp, 1, plan.g
+    u, lam, sn, sb, g = state.shape_fields(lam)
     kdev, kse, ksb = state.shape_kappa
     fdev, fsn, fsb = state.shape_f
     work = torch.empty((m, (dim + 1) * dim), dtype=torch.float64, device=plan.device)
     grad = torch.empty((n, dim), dtype=torch.float64, device=plan.device)
     _hip.check(L.diffhe_p1_shape_grad(_hip.ptr(plan.coords), _hip.ptr(plan.elems), dim, n, m, B, _hip.ptr(u),
                                       _hip.ptr(g), _hip.ptr(lam), sn, sb, _hip.ptr(kdev), kse, ksb, _hip.ptr(fdev),
-                                      fsn, fsb, float(state.reaction), _hip.ptr(inc_ptr), _hip.ptr(inc),
+                                      fsn, fsb, float(state.call.reaction), _hip.ptr(inc_ptr), _hip.ptr(inc),
                                       _hip.ptr(work), _hip.ptr(grad), _stream(plan.device)), "diffhe_p1_shape_grad")
     return grad
 
@@ -109,10 +89,9 @@ def fe_solve_shape(kappa: torch.Tensor, f: torch.Tensor, load: torch.Tensor, nod
     solver = _SOLVERS[handle]
     _check_nodes(solver.mesh, nodes, nodes_version)
     u, state = _solver._solve_forward(solver, kappa, f, load, node_major)
-    token = 0
+    token = next(_TOKENS) if save else 0
     if save:
         _shape_inputs(state, kappa, f, node_major)
-        token = next(_TOKENS)
         _STATES[token] = state
     return u, torch.tensor(token, dtype=torch.int64)
 
@@ -128,13 +107,9 @@ def fe_solve_shape_backward(gbar: torch.Tensor, token: torch.Tensor, need_k: boo
                             nodes_like: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """(dL/dkappa, dL/df, dL/dload, dL/dX) of the forward call named by `token` from ONE adjoint solve; unused gradients
     come back empty."""
-    state = _STATES.get(int(token))
-    if state is None:
-        raise RuntimeError("diffhe: adjoint state of this solve is gone (its autograd graph was freed)")
-    state.keep_adjoint = need_x
-    gk, gf, gl = _solver._solve_backward(state, gbar, need_k, need_f, need_load)
-    gx = _node_grad(state).to(nodes_like.device, nodes_like.dtype) if need_x else nodes_like.new_empty(0)
-    state.adjoint = None
+    state = _state_of(token)
+    gk, gf, gl, lam = _solver._solve_backward(state, gbar, need_k, need_f, need_load)
+    gx = _node_grad(state, lam).to(nodes_like.device, nodes_like.dtype) if need_x else nodes_like.new_empty(0)
     return (gk if gk is not None else kappa_like.new_empty(0), gf if gf is not None else f_like.new_empty(0),
             gl.to(load_like.dtype) if gl is not None else load_like.new_empty(0), gx)
 
@@ -150,13 +125,7 @@ def _fe_solve_shape_backward_fake(gbar, token, need_k, need_f, need_load, need_x
 
 def _shape_setup_context(ctx, inputs, output):
     kappa, f, load, nodes, _version, handle, _save, node_major = inputs
-    real = not isinstance(output[1], torch._subclasses.FakeTensor)
-    sentinel = (torch.empty(0),) if real else ()     # frees the adjoint state with the saved tensors (see solver.py)
-    ctx.save_for_backward(output[1], kappa, f, load, nodes, *((output[0],) if node_major else ()), *sentinel)
-    ctx.handle, ctx.node_major = handle, bool(node_major)
-    if real:
-        weakref.finalize(sentinel[0], _STATES.pop, int(output[1]), None)
-        ctx.state_guard = _StateGuard(int(output[1]))
+    _save_for_adjoint(ctx, (kappa, f, load, nodes), output, handle, node_major)
 
 
 def _shape_backward(ctx, grad_u, _grad_token):

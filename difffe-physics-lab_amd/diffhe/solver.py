@@ -18,10 +18,9 @@ from __future__ import annotations
 import ctypes
 import itertools
 import os
-import types
 import warnings
 import weakref
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -114,24 +113,10 @@ class _Engine:
                                                  _stream(p.device)), "diffhe_to_sample_major")
         return dst
 
-    def field_node_major(self, k, B, Bp, em):
-        """(m, Bp) per-sample kappa fields (padding samples = 1) from the API's (B, m) -- one transposing pass -- or from
-        an element-major (m, B) tensor (layout='node'): used as it is when B needs no padding."""
-        p = self.p
-        if em:
-            if Bp == B and k.is_contiguous():
-                return k
-            kp = torch.ones((p.m, Bp), dtype=torch.float64, device=p.device)
-            kp[:, :B] = k
-            return kp
-        kp = self.to_node_major(k.reshape(B, p.m).contiguous(), B, Bp, p.m)
-        if Bp > B:
-            kp[:, B:] = 1.0
-        return kp
-
-    # -- general path ---------------------------------------------------------------------
     def kappa_device(self, kappa, mode, B, Bp, em=False):
-        """-> (tensor, stride_e, stride_b, Bv) in the layout the kernels index."""
+        """-> (tensor, stride_e, stride_b, Bv) in the layout the kernels index.  Per-sample fields are (m, Bp), padding
+        samples = 1: from the API's (B, m) by one transposing pass, or from an element-major (m, B) tensor
+        (layout='node'), used as it is when B needs no padding."""
         p = self.p
         k = kappa.detach().to(p.device, torch.float64)
         if mode == K_SCALAR:
@@ -142,7 +127,16 @@ class _Engine:
             kp = torch.ones(Bp, dtype=torch.float64, device=p.device)
             kp[:B] = k.reshape(B)
             return kp, 0, 1, Bp
-        return self.field_node_major(k, B, Bp, em), Bp, 1, Bp
+        if em and Bp == B and k.is_contiguous():
+            return k, Bp, 1, Bp
+        if em:
+            kp = torch.ones((p.m, Bp), dtype=torch.float64, device=p.device)
+            kp[:, :B] = k
+        else:
+            kp = self.to_node_major(k.reshape(B, p.m).contiguous(), B, Bp, p.m)
+            if Bp > B:
+                kp[:, B:] = 1.0
+        return kp, Bp, 1, Bp
 
     def assemble(self, kdev, kse, ksb, Bv):
         p, L = self.p, self.L
@@ -195,35 +189,23 @@ class _Engine:
             is_bc = lev.is_bc if lattice else p.is_bc
             v[0] += (c * torch.where(is_bc.bool(), torch.zeros_like(mass), mass)).unsqueeze(1)
 
-    def load_vector(self, f_nm, lift, Bv, Bp, lift_scale=None, lattice=False):
-        """F = M f - lift_scale * lift on the free rows, 0 on Dirichlet rows."""
+    def load_vector(self, f_nm, lift, Bv, Bp, lift_scale=None, lattice=False, free_rows=True):
+        """F = M f - lift_scale * lift on the free rows, 0 on Dirichlet rows; free_rows=False: M f on every row (with
+        lift None: dL/df = M^T lambda, M symmetric)."""
         p = self.p
         F = torch.empty((p.n, Bp), dtype=torch.float64, device=p.device)
+        is_bc = _hip.ptr(p.is_bc) if free_rows else None
         if lattice:   # load matrix stored as symmetric diagonals of level 0: no ELL pattern needed
             lev = p.levels[0]
             _hip.check(self.L.diffhe_lattice_apply_shared(lev.nx, lev.ny, 4, _hip.ptr(lev.Mvals), _hip.ptr(f_nm),
-                                                          _hip.ptr(lift), Bv, _hip.ptr(lift_scale), _hip.ptr(p.is_bc),
+                                                          _hip.ptr(lift), Bv, _hip.ptr(lift_scale), is_bc,
                                                           _hip.ptr(F), Bp, _stream(p.device)),
                        "diffhe_lattice_apply_shared")
             return F
         _hip.check(self.L.diffhe_ell_spmv_shared(_hip.ptr(p.Mvals), _hip.ptr(p.Mcols), _hip.ptr(f_nm), _hip.ptr(lift),
-                                                 Bv, _hip.ptr(lift_scale), _hip.ptr(p.is_bc), _hip.ptr(F), p.n, p.MW,
+                                                 Bv, _hip.ptr(lift_scale), is_bc, _hip.ptr(F), p.n, p.MW,
                                                  Bp, _stream(p.device)), "diffhe_ell_spmv_shared")
         return F
-
-    def apply_M(self, x_nm, Bp, lattice=False):
-        p = self.p
-        y = torch.empty((p.n, Bp), dtype=torch.float64, device=p.device)
-        if lattice:
-            lev = p.levels[0]
-            _hip.check(self.L.diffhe_lattice_apply_shared(lev.nx, lev.ny, 4, _hip.ptr(lev.Mvals), _hip.ptr(x_nm), None,
-                                                          1, None, None, _hip.ptr(y), Bp, _stream(p.device)),
-                       "diffhe_lattice_apply_shared")
-            return y
-        _hip.check(self.L.diffhe_ell_spmv_shared(_hip.ptr(p.Mvals), _hip.ptr(p.Mcols), _hip.ptr(x_nm), None, 1, None,
-                                                 None, _hip.ptr(y), p.n, p.MW, Bp, _stream(p.device)),
-                   "diffhe_ell_spmv_shared")
-        return y
 
     def cg(self, vals, rhs, Bp, Bv):
         p, L = self.p, self.L
@@ -249,26 +231,17 @@ class _Engine:
         that in the last bit of every entry, which ill-conditioned systems amplify by their condition number."""
         p, L = self.p, self.L
         st = _stream(p.device)
-        k = kappa.detach().to(p.device, torch.float64)
         scale = None
-        if mode == K_SCALAR and factor:       # K = kappa K_1: the same factored form, one scale for every sample
+        if factor and mode in (K_SCALAR, K_SAMPLE):     # no kappa in the matrices: one scale per sample (or for all)
+            k = kappa.detach().to(p.device, torch.float64)
             kl, kse, ksb, Bv = None, 0, 0, 1
-            scale = k.reshape(1).expand(Bp).contiguous()
-        elif mode == K_SCALAR:
-            kl, kse, ksb, Bv = k.reshape(1).contiguous(), 0, 0, 1
-        elif mode == K_SAMPLE and factor:
-            kl, kse, ksb, Bv = None, 0, 0, 1
-            scale = torch.ones(Bp, dtype=torch.float64, device=p.device)
-            scale[:B] = k.reshape(B)
-        elif mode == K_SAMPLE:
-            kl = torch.ones(Bp, dtype=torch.float64, device=p.device)
-            kl[:B] = k.reshape(B)
-            kse, ksb, Bv = 0, 1, Bp
-        elif mode == K_ELEM:
-            kl, kse, ksb, Bv = k.reshape(p.m, 1).contiguous(), 1, 0, 1
+            if mode == K_SCALAR:
+                scale = k.reshape(1).expand(Bp).contiguous()
+            else:
+                scale = torch.ones(Bp, dtype=torch.float64, device=p.device)
+                scale[:B] = k.reshape(B)
         else:
-            kl = self.field_node_major(k, B, Bp, em)
-            kse, ksb, Bv = Bp, 1, Bp
+            kl, kse, ksb, Bv = self.kappa_device(kappa, mode, B, Bp, em)
         vals, lift = [], None
         for li, lev in enumerate(p.levels[:n_levels] if n_levels else p.levels):
             if li > 0 and mode in (K_ELEM, K_SAMPLE_ELEM):   # coarse kappa = mean of the 4 children
@@ -287,7 +260,7 @@ class _Engine:
                 # cond * eps effect in u, like the factored form) instead of twelve IEEE fp64 divisions per node and
                 # sample (10.3 -> 3 ms at 1024^2 x 256).  NOT on lattices with Neumann parts (cond ~ 1e7 there: a last-bit
                 # difference of the entries shows as 4e-10 in u, which is why per-sample scalars are left unfactored on
-                # them, `closed_` in _solve_forward) -- they, per-sample SCALARS that are not factored, and
+                # them, `closed_` in _LatticeSolve.forward) -- they, per-sample SCALARS that are not factored, and
                 # operator="assembled" keep the bit-identical order below
                 self._lattice_rows(lev, "k0ref", kl, kse, ksb, p.g, v, lf, Bv, st)
             elif li == 0 and kl is not None:   # the operator the solution is defined by: reference operation order
@@ -352,10 +325,10 @@ class _Engine:
         return d32, o16, scales
 
     def lattice_levels(self, vals, vals32=None, dense=None, shift=None, rdiag32=None, off16=None):
-        off16, oscales = off16 if off16 is not None else (None, None)
         """Level descriptors for the C ABI.  dense = (level index, inverse tensor): the hierarchy is cut at that
         level, whose solve becomes one dense product (diffhe_mg_level.dense_inv).  shift = per-level (n,) diagonal
         shifts of a factored operator (diffhe_mg_level.shift)."""
+        off16, oscales = off16 if off16 is not None else (None, None)
         nl = len(vals) if dense is None else dense[0] + 1
         arr = (_hip.MgLevel * nl)()
         for i, (lev, v) in enumerate(zip(self.p.levels[:nl], vals[:nl])):
@@ -554,302 +527,465 @@ def _rule_counts(rule: torch.Tensor, B: int) -> dict:
     return {"cap": c[0], "residual": c[1], "energy": c[2]}
 
 
-def _solve_forward(solver, kappa, f, load=None, node_major=False):
-    """u = (K(kappa) + c M_L)^{-1} (F(f) + load) with Dirichlet elimination (c = solver.reaction, 0 for the reference's
-    problem).  Returns (u, state); `state` carries what the explicit adjoint needs (assembled operators, the
-    eliminated solution, layout facts).
-    node_major (2D paths): f, load and u are (n, B) -- the solver's own layout -- instead of the API's (B, n): no
-    layout change on the way in or out (with B a valid padded batch and zero Dirichlet data, u IS the solver's
-    iterate, no copy at all)."""
-    ctx = types.SimpleNamespace()
-    reaction = float(solver.reaction)
-    if load is not None and load.numel() == 0:
-        load = None
-    plan: SolvePlan = solver._plan()
-    eng = _Engine(plan, solver.tol, solver.max_iter, solver.check_every, solver.assembly)
-    eng.ref_order = solver.operator == "assembled"
-    out_device = f.device
-    batched = f.dim() == 2
-    m, n = plan.m, plan.n
-    if node_major and (plan.is_chain or not batched):
-        raise ValueError("layout='node' takes (n, B) tensors on 2D meshes")
-    if node_major:
-        f = f.t()                       # a (B, n) VIEW for the shape logic below; the data stays (n, B)
-        load = load.t() if load is not None else None
-    ctx.node_major = node_major
-    B_f = f.shape[0] if batched else None
-    # layout='node': per-sample kappa fields may come element-major, (m, B), like f and u -- no transposing pass for
-    # kappa or its gradient either (a square (m, m) tensor is read that way)
+
+def _kappa_layout(kappa: torch.Tensor, m: int, B_f: Optional[int], node_major: bool):
+    """-> (mode, B, kappa_em) of one call; B_f is f's batch, None for one unbatched forcing.  layout='node': per-sample
+    kappa fields may come element-major, (m, B), like f and u -- no transposing pass for kappa or its gradient either
+    (a square (m, m) tensor is read that way)."""
     kappa_em = bool(node_major and kappa.dim() == 2 and tuple(kappa.shape) == (m, B_f))
-    ctx.kappa_em = kappa_em
     mode, B_k = (K_SAMPLE_ELEM, B_f) if kappa_em else _kappa_mode(kappa, m, B_f)
     B = B_f if B_f is not None else (B_k if B_k is not None else 1)
     if B_k is not None and B_k != B:
         raise ValueError(f"kappa batch {B_k} does not match f batch {B}")
-    # lattice fast path unless more than 2 % of the nodes are interior Dirichlet nodes (measured: 5 % on 256^2 needs
-    # 99 geometric-multigrid iterations and misses the parity tolerance; the aggregation path takes 33 and meets it)
-    lattice = plan.is_lattice and solver.method == "auto" and plan.n_bc_interior <= 0.02 * plan.n
-    # Options of THIS call: the user's settings stay as given (a solver object serves scalar and per-element kappa
-    # alike; nothing chosen for one call sticks to the next).
-    mg, amg, tol = dict(solver.mg), dict(solver.amg), solver._tol_user
+    return mode, B, kappa_em
+
+
+def _kappa_strided(kappa: torch.Tensor, mode: int, kappa_em: bool, B: int, m: int, device):
+    """-> (kappa on the device, stride per element, stride per sample): kappa as the 1D scan and the node-gradient
+    kernel read it, in the caller's layout."""
+    k = kappa.detach().to(device, torch.float64)
+    if mode == K_SCALAR:
+        return k.reshape(1).contiguous(), 0, 0
+    if mode == K_SAMPLE:
+        return k.reshape(B).contiguous(), 0, 1
+    if mode == K_ELEM:
+        return k.reshape(m).contiguous(), 1, 0
+    if kappa_em:                                                     # (m, B), layout='node'
+        return k.contiguous(), B, 1
+    return k.reshape(B, m).contiguous(), 1, m                        # (B, m)
+
+
+def _kappa_grad(mode: int, shape, per_sample=None, per_elem=None) -> torch.Tensor:
+    """dL/dkappa in the shape of the caller's kappa, from the per-sample sums over the elements (B,) or from the
+    per-element gradient: (B, m) -- (m, B) for an element-major kappa -- or (m,) already summed over the batch."""
+    if mode == K_SCALAR:
+        g = (per_sample if per_sample is not None else per_elem).sum()
+    elif mode == K_SAMPLE:
+        g = per_sample if per_sample is not None else per_elem.sum(1)
+    elif mode == K_ELEM:
+        g = per_elem if per_elem.dim() == 1 else per_elem.sum(0)
+    else:
+        g = per_elem
+    return g.reshape(shape)
+
+
+@dataclass
+class _Call:
+    """The inputs of one solve, normalised once.  The adjoint state keeps `facts()`: none of the input tensors."""
+    B: int
+    mode: int                       # kappa layout, K_*
+    kappa_em: bool                  # per-sample kappa fields given element-major, (m, B)
+    batched: bool                   # f came with a batch dimension
+    node_major: bool                # f, load and u are (n, B)
+    out_device: torch.device
+    kappa_shape: torch.Size
+    kappa_device: torch.device
+    load_batched: bool
+    reaction: float
+    kappa: Optional[torch.Tensor] = None
+    f_dev: Optional[torch.Tensor] = None       # (B, n) or (n,); layout='node': a (B, n) view of (n, B) data
+    load_dev: Optional[torch.Tensor] = None    # (B, n) or None
+
+    @classmethod
+    def of(cls, solver, plan: SolvePlan, kappa, f, load, node_major) -> "_Call":
+        if load is not None and load.numel() == 0:
+            load = None
+        batched, n, out_device = f.dim() == 2, plan.n, f.device
+        if node_major and (plan.is_chain or not batched):
+            raise ValueError("layout='node' takes (n, B) tensors on 2D meshes")
+        if node_major:
+            f = f.t()                       # a (B, n) VIEW for the shape logic below; the data stays (n, B)
+            load = load.t() if load is not None else None
+        mode, B, kappa_em = _kappa_layout(kappa, plan.m, f.shape[0] if batched else None, node_major)
+        f_dev = f.detach().to(plan.device, torch.float64)
+        f_dev = f_dev if node_major else f_dev.contiguous()      # node-major: a transposed view of contiguous (n, B) data
+        load_dev = None
+        if load is not None:      # extra nodal load, added to the assembled F on the free rows
+            load_dev = load.detach().to(plan.device, torch.float64)
+            load_dev = (load_dev.reshape(1, n).expand(B, n) if load_dev.dim() == 1 else load_dev).contiguous()   # (B, n)
+            if load_dev.shape != (B, n):
+                raise ValueError(f"load must be (n,) or (B,n) with B={B}, n={n}, got {tuple(load.shape)}")
+        return cls(B, mode, kappa_em, batched, node_major, out_device, kappa.shape, kappa.device,
+                   load is not None and load.dim() == 2, float(solver.reaction), kappa, f_dev, load_dev)
+
+    def facts(self) -> "_Call":
+        return replace(self, kappa=None, f_dev=None, load_dev=None)
+
+
+def _call_options(*, chain: bool, lattice: bool, closed_boundary: bool, n: int, mode: int, tol_user: Optional[float],
+                  mg_user, mg: dict, amg: dict) -> Tuple[float, dict, dict]:
+    """(tol, mg, amg) of ONE call, DESIGN section 4 "Stopping rule": `chain` (a 1D chain mesh, whichever path it takes),
+    `lattice` (route taken), `closed_boundary` (every lattice edge node Dirichlet), `n` nodes, kappa `mode`, the user's
+    `tol_user` (None: automatic) and `mg_user` keys.  `mg` / `amg` are copied: nothing sticks to the next call."""
+    mg, amg, tol = dict(mg), dict(amg), tol_user
     if mode in (K_ELEM, K_SAMPLE_ELEM):
-        # Per-element gradients difference the nodal fields, so they amplify the ROUGH part of the solver error by
-        # ~ the mesh resolution; that part keeps converging with the recurrence residual after the true residual
-        # norm has stalled, so per-element kappa runs to 1e-14 without the attainable-accuracy floor (measured:
-        # dL/dkappa_e against the oracle 2.2e-10 -> 1.4e-11 on a 288 x 296 mesh for two more iterations).
-        if "floor" not in solver._mg_user:
+        # per-element gradients amplify the rough part of the solver error, which keeps converging after the true
+        # residual has stalled: no attainable-accuracy floor (288 x 296: dL/dkappa_e 2.2e-10 -> 1.4e-11)
+        if "floor" not in mg_user:
             mg["floor"] = 0
         amg.setdefault("floor", 0)     # honoured as given when the caller put a "floor" key into solver.amg
+    closed = lattice and closed_boundary
     if tol is None:
-        # Default stop (relative residual).  Fully Dirichlet-bounded lattices with one kappa per sample are well
-        # conditioned for their size and multigrid keeps error ~ residual: 1e-12 (validated against the oracle
-        # in every bench run).  Per-element fields (their per-element gradients amplify solver error), partly
-        # Neumann boundaries and the general path get one or two more decades.
-        closed = lattice and plan.closed_boundary
+        # relative residual: 1e-12 on closed lattices with one kappa per sample (multigrid keeps error ~ residual);
+        # one or two more decades for per-element fields, Neumann parts, the general path and systems below 10^5 nodes
         simple = mode in (K_SCALAR, K_SAMPLE)
-        # small systems (< 10^5 nodes) get one more decade whatever their kind: there an iteration costs next to
-        # nothing, and odd shapes (7 x 61 cells of aspect 50, say) converge slowly enough for the error to sit well
-        # above the residual
-        tol = 1e-12 if (plan.is_chain or (closed and simple and plan.n >= 100_000)) else \
+        tol = 1e-12 if (chain or (closed and simple and n >= 100_000)) else \
             (1e-13 if (closed or not lattice) and simple else 1e-14)
-    # The energy norm controls nodal values only where the boundary is (almost) all Dirichlet (Friedrichs: no
-    # near-null mode).  With large Neumann parts the nearly constant mode carries next to no energy per unit of
-    # amplitude, and the estimate fell 40x below the nodal error (330 x 125 lattice, Dirichlet data on one edge and
-    # one interior node: 4e-10 in u at an estimate of 1e-11) -- such meshes stop on the residual alone, as before.
-    closed_lattice = lattice and plan.closed_boundary
-    if not closed_lattice and "tol_energy" not in solver._mg_user:
+    # the energy norm controls nodal values only on closed lattices (with Neumann parts the near-constant mode carries
+    # no energy: the estimate fell 40x below the nodal error): elsewhere the residual decides alone
+    if not closed and "tol_energy" not in mg_user:
         mg["tol_energy"] = 0.0
-    # an explicit `tol` is a request on the RESIDUAL: the energy-norm stop (which ends a solve at relative residuals
-    # up to ~3e-7) steps aside unless the caller asked for it too
-    if solver._tol_user is not None and "tol_energy" not in solver._mg_user:
+    # an explicit `tol` is a request on the RESIDUAL: the energy-norm stop steps aside unless asked for too
+    if tol_user is not None and "tol_energy" not in mg_user:
         mg["tol_energy"] = 0.0
-    if "tol_energy" not in solver._mg_user and mg.get("tol_energy"):
-        # The energy-norm stop is calibrated on NODAL error (the estimate sits 3-10x above it).  Per-element
-        # gradients are pointwise products of the gradients of u and lambda: their max-norm error ran 20-60x
-        # above the estimate on rough data (288 x 296 and 202 x 70 lattices, log-normal fields, random forcing), so
-        # per-element kappa asks for two more decades.  Small systems get one more whatever their kind, like `tol`.
+    if "tol_energy" not in mg_user and mg.get("tol_energy"):
+        # calibrated on nodal error; per-element gradients (products of grad u and grad lambda) ran 20-60x above the
+        # estimate: two more decades for them, one more for small systems, like `tol`
         if mode in (K_ELEM, K_SAMPLE_ELEM):
             mg["tol_energy"] *= 1e-2
-        if plan.n < 100_000:
+        if n < 100_000:
             mg["tol_energy"] *= 0.1
-    solver.tol = eng.tol = tol          # `solver.tol` reports the tolerance of the last call
-    ctx.mg, ctx.amg = mg, amg
-    f_dev = f.detach().to(plan.device, torch.float64)
-    f_dev = f_dev if node_major else f_dev.contiguous()      # node-major: a transposed view of contiguous (n, B) data
-    info = SolveInfo()
-    ctx.solver, ctx.plan, ctx.eng = solver, plan, eng
-    ctx.mode, ctx.B, ctx.batched_f, ctx.out_device = mode, B, batched, out_device
-    ctx.kappa_shape, ctx.kappa_device = kappa.shape, kappa.device
-    ctx.kappa_value = kappa.detach().to(plan.device, torch.float64).reshape(-1)[0] if mode == K_SCALAR else None
+    return tol, mg, amg
 
-    load_dev = None
-    if load is not None:      # extra nodal load, added to the assembled F on the free rows
-        load_dev = load.detach().to(plan.device, torch.float64)
-        load_dev = (load_dev.reshape(1, n).expand(B, n) if load_dev.dim() == 1 else load_dev).contiguous()   # (B, n)
-        if load_dev.shape != (B, n):
-            raise ValueError(f"load must be (n,) or (B,n) with B={B}, n={n}, got {tuple(load.shape)}")
-    ctx.load_batched = load is not None and load.dim() == 2
-    ctx.reaction = reaction
-    if plan.n_bc == 0 and reaction == 0.0:
-        # no Dirichlet node and no reaction term: K is singular (constants are in its null space).  The reference
-        # solves it anyway and returns garbage of size 1e15 (solver.py:174, no check); here the 1D scan returns NaN
-        # and the iterative paths stop at the iteration cap -- either way it is said out loud
-        warnings.warn("diffhe: the system is singular (pure Neumann problem: no Dirichlet node, no reaction term); "
-                      "the returned values are not a solution", RuntimeWarning)
+
+def _select_path(plan: SolvePlan, solver, reaction: float) -> type:
+    """The path class of one call."""
     # the scan solver inverts a pure path-graph Laplacian: with a reaction term the chain takes the general path
     if reaction and plan.is_p2:
         raise NotImplementedError("reaction term with P2 elements: the lumped P2 mass vanishes at the vertices")
-    use_chain = plan.is_chain and reaction == 0.0
-    if use_chain and load_dev is not None:
-        # the 1D load map of solver.py:95-96 is diagonal (h/2 from each side): an extra load is a change of forcing
-        f_dev = (f_dev if batched else f_dev.reshape(1, n).expand(B, n)) + load_dev / plan.lumped_mass()
-        batched_dev = True
-    else:
-        batched_dev = batched
-    if use_chain:
-        L = eng.L
-        kdev = kappa.detach().to(plan.device, torch.float64).contiguous()
-        ksb, kse = {K_SCALAR: (0, 0), K_SAMPLE: (1, 0), K_ELEM: (0, 1), K_SAMPLE_ELEM: (m, 1)}[mode]
-        u = torch.empty((B, n), dtype=torch.float64, device=plan.device)
+    if plan.is_chain and reaction == 0.0:
+        return _ChainSolve
+    # lattice fast path unless more than 2 % of the nodes are interior Dirichlet nodes (5 % on 256^2: 99 geometric-
+    # multigrid iterations, parity missed; the aggregation path takes 33)
+    if plan.is_lattice and solver.method == "auto" and plan.n_bc_interior <= 0.02 * plan.n:
+        return _LatticeSolve
+    return _EllSolve
+
+
+class _PathSolve:
+    """One call's solve on one path: forward() keeps what adjoint() needs as named fields -- no input tensor, right-hand
+    side or assembly temporary -- and this object is the adjoint state the custom ops hold until the end of backward.
+    adjoint(g, need_k, need_f, need_load) -> (lambda in the path's layout, per-sample dL/dkappa sums, per-element
+    dL/dkappa as `_kappa_grad` takes them, dL/df and dL/dload per sample in the caller's layout)."""
+    shape_kappa = shape_f = None    # set by diffhe.shape: kappa and f as the node-gradient kernel reads them
+
+    def __init__(self, solver, plan: SolvePlan, call: _Call, tol: float, mg: dict, amg: dict):
+        self.solver, self.plan, self.call, self.mg, self.amg = solver, plan, call.facts(), mg, amg
+        self.eng = _Engine(plan, tol, solver.max_iter, solver.check_every, solver.assembly)
+        self.eng.ref_order = solver.operator == "assembled"
+
+
+class _ChainSolve(_PathSolve):
+    """1D chain: one scan per sample ("chain1d-scan-ref" in the reference's operation order, "chain1d-scan")."""
+
+    def forward(self, call: _Call, info: SolveInfo) -> torch.Tensor:
+        plan, L, B, n = self.plan, self.eng.L, call.B, self.plan.n
+        f_dev, batched = call.f_dev, call.batched
+        if call.load_dev is not None:
+            # the 1D load map of solver.py:95-96 is diagonal (h/2 from each side): an extra load is a change of forcing
+            f_dev = (f_dev if batched else f_dev.reshape(1, n).expand(B, n)) + call.load_dev / plan.lumped_mass()
+            batched = True
+        self.kdev, self.kse, self.ksb = _kappa_strided(call.kappa, call.mode, False, B, plan.m, plan.device)
+        self.u = torch.empty((B, n), dtype=torch.float64, device=plan.device)      # Dirichlet values included
         # reference-order mode (default): the system the reference assembled in fp64 (rounded diagonal), see chain1d.hip
-        cflags = _hip.CHAIN_REFERENCE_ORDER if solver.chain == "reference" else 0
-        info.path = "chain1d-scan-ref" if cflags else "chain1d-scan"
-        ns = L.diffhe_chain1d_stage_doubles(n, B, plan.max_seg_len, cflags)   # 0: every segment fits the registers
+        self.chain_flags = _hip.CHAIN_REFERENCE_ORDER if self.solver.chain == "reference" else 0
+        info.path = "chain1d-scan-ref" if self.chain_flags else "chain1d-scan"
+        ns = L.diffhe_chain1d_stage_doubles(n, B, plan.max_seg_len, self.chain_flags)   # 0: every segment in registers
         stage = torch.empty(ns, dtype=torch.float64, device=plan.device) if ns > 0 else None
-        _hip.check(L.diffhe_chain1d_solve(_hip.ptr(plan.x), _hip.ptr(kdev), ksb, kse, _hip.ptr(f_dev),
-                                          n if batched_dev else 0, _hip.ptr(plan.seg), plan.n_seg, _hip.ptr(plan.g),
-                                          _hip.ptr(u), n, n, B, plan.max_seg_len, cflags, _hip.ptr(stage),
+        _hip.check(L.diffhe_chain1d_solve(_hip.ptr(plan.x), _hip.ptr(self.kdev), self.ksb, self.kse, _hip.ptr(f_dev),
+                                          n if batched else 0, _hip.ptr(plan.seg), plan.n_seg, _hip.ptr(plan.g),
+                                          _hip.ptr(self.u), n, n, B, plan.max_seg_len, self.chain_flags, _hip.ptr(stage),
                                           _stream(plan.device)), "diffhe_chain1d_solve")
-        ctx.chain_flags = cflags
-        ctx.saved = (kdev, ksb, kse, u)
-    elif lattice:
+        return self.u
+
+    def adjoint(self, g: torch.Tensor, need_k: bool, need_f: bool, need_load: bool):
+        """One fused pass: df = M^T lambda (the adjoint of the scan), dL/dkappa per element and its per-sample sums."""
+        plan, L, B, m, n = self.plan, self.eng.L, self.call.B, self.plan.m, self.plan.n
+        df = torch.empty((B, n), dtype=torch.float64, device=plan.device)
+        want_e = self.call.mode in (K_ELEM, K_SAMPLE_ELEM)
+        dk_e = torch.empty((B, m), dtype=torch.float64, device=plan.device) if want_e else None
+        part = torch.empty((B, plan.n_seg), dtype=torch.float64, device=plan.device)
+        ns = L.diffhe_chain1d_stage_doubles(n, B, plan.max_seg_len, self.chain_flags)
+        stage = torch.empty(ns, dtype=torch.float64, device=plan.device) if ns > 0 else None
+        _hip.check(L.diffhe_chain1d_adjoint(_hip.ptr(plan.x), _hip.ptr(self.kdev), self.ksb, self.kse, _hip.ptr(g), n,
+                                            _hip.ptr(self.u), n, _hip.ptr(plan.seg), plan.n_seg, _hip.ptr(df), n,
+                                            _hip.ptr(dk_e), m, _hip.ptr(part), n, B, plan.max_seg_len,
+                                            self.chain_flags, _hip.ptr(stage), _stream(plan.device)),
+                   "diffhe_chain1d_adjoint")
+        dk_sample = part.sum(dim=1)                      # (B,) tiny host-side glue
+        # the chain's extra load went in as forcing: dL/dload = df / lumped mass
+        return df, dk_sample, dk_e, df, df / plan.lumped_mass() if need_load else None
+
+    def shape_fields(self, lam):
+        """(u, lambda, node stride, sample stride, Dirichlet data) for the node-gradient kernel: (B, n) arrays."""
+        plan = self.plan
+        lam = torch.where(plan.is_bc.bool(), torch.zeros((), dtype=torch.float64, device=plan.device),
+                          lam / plan.lumped_mass())  # lambda = df / lumped mass, as grad_load
+        return self.u, lam.contiguous(), 1, plan.n, None
+
+
+class _NodeMajorSolve(_PathSolve):
+    """The lattice and general paths: the kernels work on (n, Bp) arrays, `x` is the eliminated-system solution."""
+    lattice = False     # the load matrix is stored as lattice diagonals (True) or as ELL rows
+
+    def _rhs(self, call: _Call, lift, Bv, lift_scale=None) -> torch.Tensor:
+        """F = M f - lift_scale * lift (+ load) on the free rows, 0 on Dirichlet rows: (n, Bp)."""
+        eng, plan, B, Bp = self.eng, self.plan, call.B, self.Bp
+        if not call.node_major:
+            f_nm = eng.to_node_major(call.f_dev, B, Bp, plan.n)          # API layout: one transposing pass
+        elif Bp == B and call.f_dev.t().is_contiguous():
+            f_nm = call.f_dev.t()                                        # (n, B) data: used as it is
+        else:
+            f_nm = torch.zeros((plan.n, Bp), dtype=torch.float64, device=plan.device)   # ... or padded
+            f_nm[:, :B] = call.f_dev.t()
+        rhs = eng.load_vector(f_nm, lift, Bv, Bp, lift_scale, lattice=self.lattice)
+        if call.load_dev is not None:
+            rhs += eng.to_node_major(call.load_dev, B, Bp, plan.n, zero_mask=plan.is_bc)
+        return rhs
+
+    def _adjoint_rhs(self, g: torch.Tensor) -> torch.Tensor:
+        plan, B, Bp = self.plan, self.call.B, self.Bp
+        if not self.call.node_major:
+            return self.eng.to_node_major(g, B, Bp, plan.n, zero_mask=plan.is_bc)
+        # the adjoint right-hand side must vanish on Dirichlet rows (lambda_bc = 0): a cotangent that already does
+        # (L = sum u^2 with zero Dirichlet data) is used as it is
+        dirty = plan.n_bc > 0 and bool((g[plan.bc_index()] != 0).any())
+        if Bp == B and g.is_contiguous() and not dirty:
+            return g
+        rhs = torch.zeros((plan.n, Bp), dtype=torch.float64, device=plan.device)
+        rhs[:, :B] = g
+        if dirty:
+            rhs[plan.bc_index()] = 0.0
+        return rhs
+
+    def adjoint(self, g: torch.Tensor, need_k: bool, need_f: bool, need_load: bool):
+        """lambda = A^-1 g on the free rows with the forward's operators and preconditioner, then the gradient pieces."""
+        eng, call, B, Bp, n = self.eng, self.call, self.call.B, self.Bp, self.plan.n
+        info = self.solver.last_info
+        lam, its, bad, relres = self._adjoint_solve(self._adjoint_rhs(g), info)
+        info.adj_iterations = its
+        info.adj_max_relres = float(relres[:B].max())
+        info.not_converged += bad
+        dk_sample, dk_elem = self._grad_kappa(lam) if need_k else (None, None)
+        df = dload = None
+        if need_f:
+            df = eng.load_vector(lam, None, 1, Bp, lattice=self.lattice, free_rows=False)
+            df = df[:, :B] if call.node_major else eng.to_sample_major(df, B, Bp, n)
+        if need_load:
+            dload = lam[:, :B].clone() if call.node_major else eng.to_sample_major(lam, B, Bp, n)
+        return lam, dk_sample, dk_elem, df, dload
+
+    def _grad_kappa(self, lam):
+        """-> (per-sample sums, per-element gradient) of dL/dkappa = -lambda^T k0 u, as `_kappa_grad` takes them."""
+        eng, call, B, Bp = self.eng, self.call, self.call.B, self.Bp
+        if call.mode == K_ELEM:
+            return None, eng.grad_kappa_shared(lam, self.x, B, Bp)       # (m,): summed over the batch in the kernel
+        dk_nm, dk_sum = eng.grad_kappa(lam, self.x, Bp, call.mode == K_SAMPLE_ELEM)
+        if call.mode != K_SAMPLE_ELEM:
+            return dk_sum[:B], None
+        # (B, m) like the API's kappa, or left element-major (m, B) when kappa came that way
+        if call.kappa_em:
+            return None, dk_nm if Bp == B else dk_nm[:, :B]
+        return None, eng.to_sample_major(dk_nm, B, Bp, self.plan.m)
+
+    def shape_fields(self, lam):
+        """(u, lambda, node stride, sample stride, Dirichlet data) for the node-gradient kernel: (n, Bp) arrays."""
+        return self.x, lam, self.Bp, 1, self.plan.g
+
+
+class _LatticeSolve(_NodeMajorSolve):
+    """2D lattice: geometric-multigrid PCG ("lattice-mgpcg"), or one dense product on small meshes ("lattice-direct")."""
+    lattice = True
+
+    def forward(self, call: _Call, info: SolveInfo) -> torch.Tensor:
+        solver, plan, eng, B, mode, reaction = self.solver, self.plan, self.eng, call.B, call.mode, call.reaction
         info.path = "lattice-mgpcg"
-        Bp = padded_batch(B)
-        # per-sample scalar kappa stays factored on closed lattices only: with large Neumann parts the system is
-        # ill-conditioned enough (cond ~ 1e7 in the randomised sweep) for the last-bit difference between
-        # kappa_b (K_1 x) and (sum_e kappa_b k0_e) x to show as 4e-10 in u
+        Bp = self.Bp = padded_batch(B)
+        self.kappa_value = call.kappa.detach().to(plan.device, torch.float64).reshape(-1)[0] if mode == K_SCALAR else None
+        # scalar kappa per sample stays factored on closed lattices only (with Neumann parts, cond ~ 1e7, the last-bit
+        # difference between kappa_b (K_1 x) and (sum_e kappa_b k0_e) x shows as 4e-10 in u)
         closed_ = plan.closed_boundary and solver.operator != "assembled"
-        # factored operator (one plan-constant unit matrix per level, scalar kappa per sample or for all): the levels
-        # from ~33^2 nodes down are replaced by ONE dense product with the cached inverse of that level's matrix (they
-        # cost ~45 launch-bound launches per cycle); a mesh that small as a whole -- the reference's own 2D sizes -- is
-        # solved DIRECTLY by that product (level index 0: no iteration at all)
-        # a reaction term c M_L does not scale with kappa: K_b + c M_L is assembled per sample (or once, scalar kappa)
-        factored = closed_ and mode in (K_SCALAR, K_SAMPLE)
-        kappa_free_unit = factored           # the stored matrix is the unit-kappa K_1 of the mesh: plan-constant
-        # a reaction term c M_L does not scale with kappa: a factored operator carries it as a batch-shared diagonal
-        # SHIFT, A_b = kappa_b K_1 + diag(c m) (coefficients stay scalar loads; no cached dense inverse then: it would
-        # depend on c / kappa_b); per-sample matrices get it added to their diagonals
-        didx = plan.dense_level() if (factored and mg.get("dense_coarse", 1) and reaction == 0.0) else None
-        n_levels = None if didx is None else didx + 1
-        # (cutting the hierarchy of per-sample matrices at 9^2 / 17^2 / 33^2 -- 11 to 30 fewer launches per cycle, the last
-        # level on its Chebyshev iteration -- was measured: 9 + 9 -> 10 + 10 iterations, 208.6 -> 224.0 ... 226.9 ms; r4ab)
-        vals, Bv, scale, lift, lift_scale = eng.lattice_assemble(kappa, mode, B, Bp, factor=closed_,
-                                                                 n_levels=n_levels, em=kappa_em)
-        shift = None
-        if reaction and factored:
-            shift = eng.reaction_shifts(reaction, len(vals))
-        elif reaction:
+        self.factored = factored = closed_ and mode in (K_SCALAR, K_SAMPLE)
+        # a factored operator (plan-constant unit matrices) replaces the levels from ~33^2 nodes down by ONE dense
+        # product with a cached inverse -- the whole solve on meshes that small; not with a reaction term, which a
+        # factored operator carries as a batch-shared diagonal SHIFT and per-sample matrices on their diagonals
+        didx = plan.dense_level() if (factored and self.mg.get("dense_coarse", 1) and reaction == 0.0) else None
+        vals, Bv, scale, lift, lift_scale = eng.lattice_assemble(call.kappa, mode, B, Bp, factor=closed_,
+                                                                 n_levels=None if didx is None else didx + 1,
+                                                                 em=call.kappa_em)
+        self.shift = eng.reaction_shifts(reaction, len(vals)) if reaction and factored else None
+        if reaction and not factored:
             eng.add_reaction(vals, reaction, lattice=True)
-        f_nm = _as_node_major(eng, f_dev, B, Bp, n, node_major)
-        rhs = eng.load_vector(f_nm, lift, Bv, Bp, lift_scale, lattice=True)
-        if load_dev is not None:
-            rhs += eng.to_node_major(load_dev, B, Bp, n, zero_mask=plan.is_bc)
-        # fp32-stored V-cycle: per-sample matrices are read from an fp32 copy of the coefficients; a batch-SHARED
-        # matrix gets an fp32 copy and the reciprocal of its main diagonal (a few MB), which switch the strip levels
-        # to the two-samples-per-lane kernels (packed fp32 arithmetic; batches that are multiples of 128, no shift)
-        vals32 = rdiag32 = off16 = None
-        if mg.get("fp32") and Bv != 1 and mg.get("h16", 1) and Bp > 1:
-            d32_, o16_, osc_ = eng.pack_cycle_coeffs(vals, Bv)   # fp32 diagonal + fp16 off-diagonals (row sums kept)
-            if d32_ is not None:
-                vals32, off16 = d32_, (o16_, osc_)
-        if mg.get("fp32") and Bv != 1 and vals32 is None:
-            vals32 = [v.float() for v in vals]
-        elif mg.get("fp32") and Bv == 1 and mg.get("strip2", 1) and Bp % 64 == 0 and shift is None:
-            vals32, rdiag32 = plan.shared_fp32(vals, cacheable=factored and kappa_free_unit)
-        info.coeff_storage = ("fp64" if not mg.get("fp32") else
-                              ("fp16-rowsum" if off16 is not None else "fp32") if Bv != 1 else "shared-fp32")
-        dense = None
+        rhs = self._rhs(call, lift, Bv, lift_scale)
+        self.vals32, self.rdiag32, self.off16 = self._cycle_coeffs(vals, Bv)
+        info.coeff_storage = ("fp64" if not self.mg.get("fp32") else
+                              ("fp16-rowsum" if self.off16 is not None else "fp32") if Bv != 1 else "shared-fp32")
+        self.direct, self.dense = didx == 0, None
         if didx is not None:
-            if didx == 0:
+            if self.direct:
                 info.path = "lattice-direct"
-                mg = ctx.mg = dict(mg, fp32=0)        # the direct product runs in fp64
-            dense = plan.dense_coarse(didx, vals, bool(mg.get("fp32")))
-        wkey = (Bp, mode, reaction)
-        x, its, bad, relres = eng.lattice_pcg(vals, Bv, scale, rhs, Bp, mg, vals32, dense,
-                                              x0=plan.warm_get(("u",) + wkey) if solver.warm_start else None, shift=shift,
-                                              rdiag32=rdiag32, off16=off16)
-        ctx.shift, ctx.wkey, ctx.rdiag32, ctx.off16 = shift, wkey, rdiag32, off16
+                self.mg = dict(self.mg, fp32=0)        # the direct product runs in fp64
+            self.dense = plan.dense_coarse(didx, vals, bool(self.mg.get("fp32")))
+        self.wkey = (Bp, mode, reaction)
+        x, its, bad, relres = eng.lattice_pcg(vals, Bv, scale, rhs, Bp, self.mg, self.vals32, self.dense,
+                                              x0=plan.warm_get(("u",) + self.wkey) if solver.warm_start else None,
+                                              shift=self.shift, rdiag32=self.rdiag32, off16=self.off16)
         if solver.warm_start and not bad:
-            # never written by the solver again (the next solve starts from a copy) -- but with layout='node' and no padding
-            # the caller's u IS this tensor, and an in-place edit under no_grad would silently move the next warm start:
-            # keep a private copy then (ADVICE r3)
-            shares = node_major and Bp == B and not plan.has_dirichlet_data
-            plan.warm_put(("u",) + wkey, x.clone() if shares else x)
-        info.stop_rules = _rule_counts(eng.last_rule, B) if info.path != "lattice-direct" else {}
+            # the next solve starts from a copy; but with layout='node' and no padding the caller's u IS x: keep a
+            # private copy then, an in-place edit of u must not move the next warm start
+            shares = call.node_major and Bp == B and not plan.has_dirichlet_data
+            plan.warm_put(("u",) + self.wkey, x.clone() if shares else x)
+        info.stop_rules = _rule_counts(eng.last_rule, B) if not self.direct else {}
         info.flags = eng.last_flags
         info.precision = _precision_text(eng.last_flags, info.coeff_storage, Bv, Bp, int(eng.L.diffhe_lattice_fused_passes()),
                                          bool(eng.L.diffhe_lattice_recompute_ap()))
-        info.tol_energy = float(mg.get("tol_energy", 0.0) or 0.0)
-        ctx.dense = dense
-        ctx.factored = factored
+        info.tol_energy = float(self.mg.get("tol_energy", 0.0) or 0.0)
         info.factored = bool(factored)
         info.iterations, info.not_converged = its, bad
         info.max_relres = float(relres[:B].max())
         info.err_est = float(eng.last_est[:B].max())
-        u = _from_node_major(eng, x, B, Bp, n, node_major)
-        ctx.saved = (vals, x, Bp, Bv, scale)
-        ctx.vals32 = vals32
-        ctx.lift = lift if Bv == 1 else None
-    else:
+        self.vals, self.x, self.Bv, self.scale = vals, x, Bv, scale
+        self.lift = lift if Bv == 1 else None
+        return _from_node_major(eng, x, B, Bp, plan.n, call.node_major)
+
+    def _cycle_coeffs(self, vals, Bv):
+        """fp32-stored V-cycle -> (vals32, rdiag32, off16): fp32 copies of per-sample matrices; a batch-SHARED matrix
+        also gets the reciprocal of its main diagonal, for the two-samples-per-lane strip kernels."""
+        mg, Bp = self.mg, self.Bp
+        vals32 = rdiag32 = off16 = None
+        if mg.get("fp32") and Bv != 1 and mg.get("h16", 1) and Bp > 1:
+            d32_, o16_, osc_ = self.eng.pack_cycle_coeffs(vals, Bv)   # fp32 diagonal + fp16 off-diagonals (row sums kept)
+            if d32_ is not None:
+                vals32, off16 = d32_, (o16_, osc_)
+        if mg.get("fp32") and Bv != 1 and vals32 is None:
+            vals32 = [v.float() for v in vals]
+        elif mg.get("fp32") and Bv == 1 and mg.get("strip2", 1) and Bp % 64 == 0 and self.shift is None:
+            # a factored operator is the unit-kappa K_1 of the mesh: plan-constant, its copies are cached
+            vals32, rdiag32 = self.plan.shared_fp32(vals, cacheable=self.factored)
+        return vals32, rdiag32, off16
+
+    def _adjoint_solve(self, rhs, info):
+        plan, eng, B = self.plan, self.eng, self.call.B
+        ws = self.solver.warm_start is True
+        lam, its, bad, relres = eng.lattice_pcg(self.vals, self.Bv, self.scale, rhs, self.Bp, self.mg, self.vals32,
+                                                self.dense, x0=plan.warm_get(("lambda",) + self.wkey) if ws else None,
+                                                shift=self.shift, rdiag32=self.rdiag32, off16=self.off16)
+        if ws and not bad:
+            plan.warm_put(("lambda",) + self.wkey, lam)
+        info.adj_stop_rules = _rule_counts(eng.last_rule, B) if not self.direct else {}
+        info.adj_err_est = float(eng.last_est[:B].max())
+        return lam, its, bad, relres
+
+    def _grad_kappa(self, lam):
+        """Scalar kappa per sample or for all with ONE stored matrix: dL/dkappa_b in one strip pass, above the strip
+        kernels' threshold.  The bilinear form must see K alone: factored operators keep the reaction term apart
+        (`shift`), assembled ones carry it in `vals`."""
+        call = self.call
+        if call.mode in (K_SCALAR, K_SAMPLE) and self.Bv == 1 and (self.factored or not call.reaction):
+            dk_sum = self.eng.grad_kappa_factored(self.vals, self.lift, lam, self.x, self.Bp)
+            if dk_sum is not None:
+                scaled = call.mode == K_SCALAR and not self.factored       # vals carry kappa: K = kappa K_1
+                return (dk_sum / self.kappa_value if scaled else dk_sum)[:call.B], None
+        return super()._grad_kappa(lam)
+
+
+class _EllSolve(_NodeMajorSolve):
+    """General meshes: ELL operator, aggregation-multigrid PCG ("ell-amgpcg") or Jacobi PCG ("ell-pcg")."""
+
+    def forward(self, call: _Call, info: SolveInfo) -> torch.Tensor:
+        solver, plan, eng, B, mode = self.solver, self.plan, self.eng, call.B, call.mode
         plan.ensure_ell()
-        Bp = padded_batch(B)
-        # One scalar kappa per sample on a general mesh whose boundary is closed by Dirichlet data (round 4): kept FACTORED
-        # like on closed lattices, K_b = kappa_b K_1 -- ONE unit matrix for the batch (Bv = 1: the ELL kernels read it as
-        # wave-uniform broadcasts instead of 8 W bytes per node and sample) and the system K_1 x = F_b / kappa_b, whose
-        # solution, residual ratio and adjoint are those of the original one; the aggregation hierarchy and its Galerkin
-        # operators are then plan-constant and built once.  Not with a reaction term (kappa_b K_1 + c M is no multiple of
-        # one matrix), not for operator="assembled", not with Neumann parts (cond * eps, as on lattices).
-        ell_factored = (mode in (K_SCALAR, K_SAMPLE) and reaction == 0.0 and solver.operator != "assembled" and not plan.is_p2
-                        and solver.method != "ell-jacobi" and plan.closed_boundary_general())
-        ctx.ell_inv_kappa = None
-        if ell_factored and "fp32" not in solver._amg_user:
-            # the fp32-stored cycle is off by default because high-contrast kappa FIELDS break it; the factored operator
-            # is the unit-kappa matrix of the mesh -- no coefficient contrast at all: 2.33 -> 2.08 ms per iteration, same 39
-            # iterations (jittered 512^2 x 64, gpurun_out/r4v)
-            amg["fp32"] = 1
-        if ell_factored:
-            one = torch.ones(1, dtype=torch.float64, device=plan.device)
-            vals, lift = eng.assemble(one, 0, 0, 1)
+        Bp = self.Bp = padded_batch(B)
+        # scalar kappa per sample on a boundary closed by Dirichlet data: FACTORED like on closed lattices, ONE unit
+        # matrix K_1 for the batch and K_1 x = F_b / kappa_b, its aggregation hierarchy plan-constant.  Not with a
+        # reaction term, operator="assembled" or Neumann parts (DESIGN section 4, "General meshes")
+        factored = (mode in (K_SCALAR, K_SAMPLE) and call.reaction == 0.0 and solver.operator != "assembled"
+                    and not plan.is_p2 and solver.method != "ell-jacobi" and plan.closed_boundary_general())
+        self.inv_kappa = None
+        if factored:
+            vals, lift = eng.assemble(torch.ones(1, dtype=torch.float64, device=plan.device), 0, 0, 1)
             Bv = 1
             kpad = torch.ones(Bp, dtype=torch.float64, device=plan.device)
-            kpad[:B] = kappa.detach().to(plan.device, torch.float64).reshape(-1)      # (B,), or one scalar for all
-            ctx.ell_inv_kappa = 1.0 / kpad
-            f_nm = _as_node_major(eng, f_dev, B, Bp, n, node_major)
-            rhs = eng.load_vector(f_nm, lift, 1, Bp, kpad)          # F_b = M f_b - kappa_b lift_1
-            if load_dev is not None:
-                rhs += eng.to_node_major(load_dev, B, Bp, n, zero_mask=plan.is_bc)
-            rhs *= ctx.ell_inv_kappa                                 # ... / kappa_b: K_1 x = F_b / kappa_b
+            kpad[:B] = call.kappa.detach().to(plan.device, torch.float64).reshape(-1)      # (B,), or one scalar for all
+            self.inv_kappa = 1.0 / kpad
+            rhs = self._rhs(call, lift, 1, kpad)                   # F_b = M f_b - kappa_b lift_1
+            rhs *= self.inv_kappa                                  # ... / kappa_b: K_1 x = F_b / kappa_b
         else:
-            kdev, kse, ksb, Bv = eng.kappa_device(kappa, mode, B, Bp, em=kappa_em)
+            kdev, kse, ksb, Bv = eng.kappa_device(call.kappa, mode, B, Bp, em=call.kappa_em)
             vals, lift = eng.assemble(kdev, kse, ksb, Bv)
-            if reaction:
-                eng.add_reaction([vals], reaction, lattice=False)
-            f_nm = _as_node_major(eng, f_dev, B, Bp, n, node_major)
-            rhs = eng.load_vector(f_nm, lift, Bv, Bp)
-            if load_dev is not None:
-                rhs += eng.to_node_major(load_dev, B, Bp, n, zero_mask=plan.is_bc)
-        ctx.amg_hier = None
-        if solver.method != "ell-jacobi":
-            smoothed = bool(amg.get("smoothed", 1))
-            amg_levels = plan.ensure_amg(smoothed=smoothed)
-            if amg.get("scale") is None:
-                amg["scale"] = 1.3 if amg.get("smoothed", 1) else 1.8
-            if amg.get("gamma") is None:      # None = automatic (the default); an explicit 1 or 2 is honoured
-                amg["gamma"] = 1
-                big = smoothed and plan.n * Bp >= 12_000_000
-                # W-cycle where the FINE level dominates the cycle (>= 12 M node-samples): the second visit of the
-                # coarser levels costs latency-bound launches on a few thousand nodes, the fine-level sweeps are the
-                # bill -- 39 -> 24 iterations, 38.3 -> 35.0 ms at jittered 512^2 x 64, 143.6 -> 118.9 ms at 512^2 x 256,
-                # per-sample matrices 102.7 -> 94.8; below that size the V-cycle wins (256^2 x 64: 11.1 against 14.4 ms;
-                # 128^2 x 64: 5.9 against 9.3; gpurun_out/r4be, r4bf)
-                if big:
-                    amg["gamma"] = 2
-            if amg_levels and ell_factored:          # plan-constant hierarchy of the unit operator: built once
-                ctx.amg_hier = plan.unit_amg((smoothed, bool(amg.get("fp32", 0))),
-                                             lambda: eng.amg_setup(vals, 1, bool(amg.get("fp32", 0)), amg_levels, dense_coarse=True))
-            elif amg_levels:                         # at least one coarse level: aggregation-AMG PCG
-                ctx.amg_hier = eng.amg_setup(vals, Bv, bool(amg.get("fp32", 0)), amg_levels)
-        if ctx.amg_hier is not None:
+            if call.reaction:
+                eng.add_reaction([vals], call.reaction, lattice=False)
+            rhs = self._rhs(call, lift, Bv)
+        self.amg_hier = self._amg_hierarchy(vals, Bv, factored) if solver.method != "ell-jacobi" else None
+        if self.amg_hier is not None:
             info.path = "ell-amgpcg"
-            x, its, bad, relres = eng.amg_pcg(ctx.amg_hier, rhs, Bp, Bv, amg)
+            x, its, bad, relres = eng.amg_pcg(self.amg_hier, rhs, Bp, Bv, self.amg)
         else:
             info.path = "ell-pcg"
             x, its, bad, relres = eng.cg(vals, rhs, Bp, Bv)
         info.iterations, info.not_converged = its, bad
         info.max_relres = float(relres[:B].max())
-        info.factored = bool(ell_factored)
-        u = _from_node_major(eng, x, B, Bp, n, node_major)
-        ctx.saved = (vals, x, Bp, Bv, None)
+        info.factored = bool(factored)
+        self.vals, self.x, self.Bv = vals, x, Bv
+        return _from_node_major(eng, x, B, Bp, plan.n, call.node_major)
+
+    def _amg_hierarchy(self, vals, Bv, factored):
+        """The aggregation-multigrid hierarchy of this call (None: no coarse level, Jacobi PCG), after the automatic
+        `amg` options of the general path."""
+        solver, plan, eng, amg = self.solver, self.plan, self.eng, self.amg
+        if factored and "fp32" not in solver._amg_user:
+            # the fp32-stored cycle, off for kappa FIELDS (contrast breaks it), suits the contrast-free unit operator
+            amg["fp32"] = 1
+        smoothed = bool(amg.get("smoothed", 1))
+        amg_levels = plan.ensure_amg(smoothed=smoothed)
+        if amg.get("scale") is None:
+            amg["scale"] = 1.3 if amg.get("smoothed", 1) else 1.8
+        if amg.get("gamma") is None:      # None = automatic (the default); an explicit 1 or 2 is honoured
+            # W-cycle where the fine level dominates the cycle (>= 12 M node-samples), V-cycle below (DESIGN section 4)
+            amg["gamma"] = 2 if smoothed and plan.n * self.Bp >= 12_000_000 else 1
+        fp32 = bool(amg.get("fp32", 0))
+        if amg_levels and factored:          # plan-constant hierarchy of the unit operator: built once
+            return plan.unit_amg((smoothed, fp32), lambda: eng.amg_setup(vals, 1, fp32, amg_levels, dense_coarse=True))
+        if amg_levels:                       # at least one coarse level: aggregation-AMG PCG
+            return eng.amg_setup(vals, Bv, fp32, amg_levels)
+        return None
+
+    def _adjoint_solve(self, rhs, info):
+        """The forward's preconditioner and saved (per-sample) coarse operators; factored: lambda_b = K_1^-1 (g_b / kappa_b)."""
+        eng = self.eng
+        if self.inv_kappa is not None:
+            rhs = rhs * self.inv_kappa
+        if self.amg_hier is not None:
+            return eng.amg_pcg(self.amg_hier, rhs, self.Bp, self.Bv, self.amg)
+        return eng.cg(self.vals, rhs, self.Bp, self.Bv)
+
+
+def _solve_forward(solver, kappa, f, load=None, node_major=False):
+    """u = (K(kappa) + c M_L)^{-1} (F(f) + load) with Dirichlet elimination (c = solver.reaction, 0 for the reference's
+    problem).  Returns (u, state): the path object that keeps what the explicit adjoint needs.  node_major (2D paths):
+    f, load and u are (n, B), the solver's own layout: no layout change (with B a valid padded batch and zero Dirichlet
+    data, u IS the solver's iterate)."""
+    plan: SolvePlan = solver._plan()
+    call = _Call.of(solver, plan, kappa, f, load, node_major)
+    path = _select_path(plan, solver, call.reaction)
+    tol, mg, amg = _call_options(chain=plan.is_chain, lattice=path is _LatticeSolve, closed_boundary=plan.closed_boundary,
+                                 n=plan.n, mode=call.mode, tol_user=solver._tol_user, mg_user=solver._mg_user,
+                                 mg=solver.mg, amg=solver.amg)
+    solver.tol = tol          # `solver.tol` reports the tolerance of the last call
+    if plan.n_bc == 0 and call.reaction == 0.0:
+        # K is singular (constants in its null space): the reference returns garbage of size 1e15 (solver.py:174),
+        # the 1D scan NaN, the iterative paths stop at the iteration cap -- either way it is said out loud
+        warnings.warn("diffhe: the system is singular (pure Neumann problem: no Dirichlet node, no reaction term); "
+                      "the returned values are not a solution", RuntimeWarning)
+    state = path(solver, plan, call, tol, mg, amg)
+    info = SolveInfo()
+    u = state.forward(call, info)
     solver.last_info = info
-    ctx.path = info.path
     if info.not_converged:
-        warnings.warn(f"diffhe: {info.not_converged} of {B} systems did not reach tol={solver.tol:g} "
+        warnings.warn(f"diffhe: {info.not_converged} of {call.B} systems did not reach tol={solver.tol:g} "
                       f"(max relative residual {info.max_relres:.2e}, path {info.path})", RuntimeWarning)
-    out = u if batched or B > 1 or node_major else u[0]
-    return out.to(out_device), ctx
-
-
-def _as_node_major(eng, f_dev, B, Bp, n, node_major):
-    """The (n, Bp) forcing the kernels read.  API layout: one transposing pass.  Node-major input ((B, n) view of
-    contiguous (n, B) data): used as it is when B needs no padding, else copied into the padded buffer."""
-    if not node_major:
-        return eng.to_node_major(f_dev, B, Bp, n)
-    f_nb = f_dev.t()
-    if Bp == B and f_nb.is_contiguous():
-        return f_nb
-    out = torch.zeros((n, Bp), dtype=torch.float64, device=f_dev.device)
-    out[:, :B] = f_nb
-    return out
+    out = u if call.batched or call.B > 1 or node_major else u[0]
+    return out.to(call.out_device), state
 
 
 def _from_node_major(eng, x, B, Bp, n, node_major):
@@ -861,123 +997,23 @@ def _from_node_major(eng, x, B, Bp, n, node_major):
     return xo + p.g.unsqueeze(1) if p.has_dirichlet_data else xo   # zero Dirichlet data: u IS x, nothing is copied
 
 
-def _solve_backward(ctx, gbar, need_k, need_f, need_load=False):
+def _solve_backward(state: _PathSolve, gbar, need_k, need_f, need_load=False):
     """Explicit adjoint: lambda = K_free^{-1} gbar_free with the saved operators,
-    dL/dkappa = -lambda^T k0 u, dL/df = M^T lambda, dL/dload = lambda.
-    Returns (grad_kappa | None, grad_f | None, grad_load | None)."""
-    plan, eng, mode, B = ctx.plan, ctx.eng, ctx.mode, ctx.B
-    m, n = plan.m, plan.n
-    node_major = getattr(ctx, "node_major", False)
-    if node_major:
-        g_dev = gbar.detach().to(plan.device, torch.float64).reshape(n, B)
-    else:
-        g_dev = gbar.detach().to(plan.device, torch.float64).reshape(B, n).contiguous()
-    info = ctx.solver.last_info
-    grad_load = None
-    dk_shared = None
-    if ctx.path.startswith("chain1d"):
-        need_f_user, need_f = need_f, need_f or need_load    # the chain's extra load went in as forcing
-        kdev, ksb, kse, u = ctx.saved
-        L = eng.L
-        df = torch.empty((B, n), dtype=torch.float64, device=plan.device)
-        want_e = mode in (K_ELEM, K_SAMPLE_ELEM)
-        dk_e = torch.empty((B, m), dtype=torch.float64, device=plan.device) if want_e else None
-        part = torch.empty((B, plan.n_seg), dtype=torch.float64, device=plan.device)
-        ns = L.diffhe_chain1d_stage_doubles(n, B, plan.max_seg_len, ctx.chain_flags)
-        stage = torch.empty(ns, dtype=torch.float64, device=plan.device) if ns > 0 else None
-        _hip.check(L.diffhe_chain1d_adjoint(_hip.ptr(plan.x), _hip.ptr(kdev), ksb, kse, _hip.ptr(g_dev), n,
-                                            _hip.ptr(u), n, _hip.ptr(plan.seg), plan.n_seg, _hip.ptr(df), n,
-                                            _hip.ptr(dk_e), m, _hip.ptr(part), n, B, plan.max_seg_len,
-                                            ctx.chain_flags, _hip.ptr(stage), _stream(plan.device)),
-                   "diffhe_chain1d_adjoint")
-        dk_sample = part.sum(dim=1)                      # (B,) tiny host-side glue
-        dk_elem = dk_e
-        if getattr(ctx, "keep_adjoint", False):          # diffhe.shape: lambda on the free nodes is df / lumped mass
-            ctx.adjoint = df
-        if need_load:
-            grad_load = df / plan.lumped_mass()
-        need_f = need_f_user
-    else:
-        vals, x, Bp, Bv, scale = ctx.saved
-        if node_major:
-            # the adjoint right-hand side must vanish on Dirichlet rows (lambda_bc = 0): a cotangent that already does
-            # (L = sum u^2 with zero Dirichlet data) is used as it is
-            dirty = plan.n_bc > 0 and bool((g_dev[plan.bc_index()] != 0).any())
-            if Bp == B and g_dev.is_contiguous() and not dirty:
-                rhs = g_dev
-            else:
-                rhs = torch.zeros((n, Bp), dtype=torch.float64, device=plan.device)
-                rhs[:, :B] = g_dev
-                if dirty:
-                    rhs[plan.bc_index()] = 0.0
-        else:
-            rhs = eng.to_node_major(g_dev, B, Bp, n, zero_mask=plan.is_bc)
-        if ctx.path in ("lattice-mgpcg", "lattice-direct"):
-            ws = ctx.solver.warm_start is True
-            lam, its, bad, relres = eng.lattice_pcg(vals, Bv, scale, rhs, Bp, ctx.mg, ctx.vals32, ctx.dense,
-                                                    x0=plan.warm_get(("lambda",) + ctx.wkey) if ws else None,
-                                                    shift=ctx.shift, rdiag32=ctx.rdiag32, off16=ctx.off16)
-            if ws and not bad:
-                plan.warm_put(("lambda",) + ctx.wkey, lam)
-            info.adj_stop_rules = _rule_counts(eng.last_rule, B) if ctx.path != "lattice-direct" else {}
-            info.adj_err_est = float(eng.last_est[:B].max())
-        elif ctx.path == "ell-amgpcg":    # same preconditioner (and the saved per-sample coarse operators) as forward
-            if getattr(ctx, "ell_inv_kappa", None) is not None:   # factored: lambda_b = K_1^-1 (gbar_b / kappa_b)
-                rhs = rhs * ctx.ell_inv_kappa
-            lam, its, bad, relres = eng.amg_pcg(ctx.amg_hier, rhs, Bp, Bv, ctx.amg)
-        else:
-            if getattr(ctx, "ell_inv_kappa", None) is not None:
-                rhs = rhs * ctx.ell_inv_kappa
-            lam, its, bad, relres = eng.cg(vals, rhs, Bp, Bv)
-        if getattr(ctx, "keep_adjoint", False):          # diffhe.shape: the node gradient contracts the same lambda
-            ctx.adjoint = lam
-        info.adj_iterations = its
-        info.adj_max_relres = float(relres[:B].max())
-        info.not_converged += bad
-        want_e = mode in (K_ELEM, K_SAMPLE_ELEM)
-        dk_nm = dk_sum = None
-        if need_k and ctx.path in ("lattice-mgpcg", "lattice-direct") and mode in (K_SCALAR, K_SAMPLE) and Bv == 1 \
-                and (ctx.factored or not ctx.reaction):   # the bilinear form must see K alone: factored operators keep
-            # the reaction term apart (ctx.shift), assembled ones carry it in `vals`
-            dk_sum = eng.grad_kappa_factored(vals, ctx.lift, lam, x, Bp)   # shared matrix: one strip pass
-            if dk_sum is not None and mode == K_SCALAR and not ctx.factored:
-                dk_sum = dk_sum / ctx.kappa_value                           # vals carry kappa: K = kappa K_1
-        if need_k and mode == K_ELEM:
-            dk_shared = eng.grad_kappa_shared(lam, x, B, Bp)       # (m,): summed over the batch in the kernel
-        elif need_k and dk_sum is None:
-            dk_nm, dk_sum = eng.grad_kappa(lam, x, Bp, want_e)
-        dk_sample = dk_sum[:B] if need_k and dk_sum is not None else None
-        dk_elem = None
-        if need_k and mode == K_SAMPLE_ELEM:
-            # (B, m) like the API's kappa, or left element-major (m, B) when kappa came that way
-            dk_elem = (dk_nm if Bp == B else dk_nm[:, :B]) if ctx.kappa_em else eng.to_sample_major(dk_nm, B, Bp, m)
-        df = None
-        if need_f:
-            df = eng.apply_M(lam, Bp, lattice=ctx.path.startswith("lattice-"))
-            df = df[:, :B] if node_major else eng.to_sample_major(df, B, Bp, n)
-        if need_load:
-            grad_load = lam[:, :B].clone() if node_major else eng.to_sample_major(lam, B, Bp, n)
-
-    grad_k = None
+    dL/dkappa = -lambda^T k0 u, dL/df = M^T lambda, dL/dload = lambda -- the path's adjoint, then the gradients shaped,
+    summed over the batch where the input had none, and placed like the inputs.
+    Returns (grad_kappa | None, grad_f | None, grad_load | None, lambda in the path's layout, for state.shape_fields)."""
+    call, plan = state.call, state.plan
+    g = gbar.detach().to(plan.device, torch.float64)
+    g = g.reshape(plan.n, call.B) if call.node_major else g.reshape(call.B, plan.n).contiguous()
+    lam, dk_sample, dk_elem, df, dload = state.adjoint(g, need_k, need_f, need_load)
+    grad_k = grad_f = grad_load = None
     if need_k:
-        if mode == K_SCALAR:
-            grad_k = dk_sample.sum().reshape(ctx.kappa_shape)
-        elif mode == K_SAMPLE:
-            grad_k = dk_sample.reshape(ctx.kappa_shape)
-        elif mode == K_ELEM:
-            grad_k = (dk_shared if dk_shared is not None else dk_elem.sum(dim=0)).reshape(ctx.kappa_shape)
-        else:
-            grad_k = dk_elem.reshape(ctx.kappa_shape)
-        grad_k = grad_k.to(ctx.kappa_device)
-    grad_f = None
+        grad_k = _kappa_grad(call.mode, call.kappa_shape, dk_sample, dk_elem).to(call.kappa_device)
     if need_f:
-        grad_f = df if ctx.batched_f else df.sum(dim=0)
-        grad_f = grad_f.to(ctx.out_device)
-    if grad_load is not None:
-        grad_load = (grad_load if ctx.load_batched else grad_load.sum(dim=1 if node_major else 0)).to(ctx.out_device)
-    return grad_k, grad_f, grad_load
-
-
+        grad_f = (df if call.batched else df.sum(dim=0)).to(call.out_device)
+    if need_load:
+        grad_load = (dload if call.load_batched else dload.sum(dim=1 if call.node_major else 0)).to(call.out_device)
+    return grad_k, grad_f, grad_load, lam
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1001,17 +1037,37 @@ class _StateGuard:
         _STATES.pop(self.token, None)
 
 
+def _state_of(token: torch.Tensor):
+    state = _STATES.get(int(token))
+    if state is None:
+        raise RuntimeError("diffhe: adjoint state of this solve is gone (its autograd graph was freed)")
+    return state
+
+
+def _save_for_adjoint(ctx, inputs, output, handle, node_major):
+    """setup_context of the solve ops: save (token, *inputs) and u when node-major (it may BE the saved iterate: autograd
+    then refuses a backward after an in-place edit), and tie the adjoint state to them."""
+    real = not isinstance(output[1], torch._subclasses.FakeTensor)
+    # A sentinel among the saved tensors dies with them at the end of a backward that does not retain the graph and
+    # takes the adjoint state along, BEFORE the caller lets go of u: a state that overlaps the next step's forward
+    # solve costs new device allocations (DESIGN section 4, "Lifetime of the adjoint state").
+    sentinel = (torch.empty(0),) if real else ()
+    ctx.save_for_backward(output[1], *inputs, *((output[0],) if node_major else ()), *sentinel)
+    ctx.handle, ctx.node_major = handle, bool(node_major)
+    if real:
+        weakref.finalize(sentinel[0], _STATES.pop, int(output[1]), None)
+        ctx.state_guard = _StateGuard(int(output[1]))       # and in any case together with the graph
+
+
 @torch.library.custom_op("diffhe::fe_solve", mutates_args=())
 def fe_solve(kappa: torch.Tensor, f: torch.Tensor, load: torch.Tensor, handle: int,
              save: bool, node_major: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """(u, token) = solve with the solver registered under `handle`; `token` names the saved
     adjoint state (0 when `save` is false).  `load`: extra nodal load vector, empty for none.
     node_major: f, load and u are (n, B) instead of (B, n)."""
-    solver = _SOLVERS[handle]
-    u, state = _solve_forward(solver, kappa, f, load, node_major)
-    token = 0
+    u, state = _solve_forward(_SOLVERS[handle], kappa, f, load, node_major)
+    token = next(_TOKENS) if save else 0
     if save:
-        token = next(_TOKENS)
         _STATES[token] = state     # freed with the autograd graph of this solve (_StateGuard): no cap on pending solves
     return u, torch.tensor(token, dtype=torch.int64)
 
@@ -1022,9 +1078,7 @@ def _fe_solve_fake(kappa, f, load, handle, save, node_major=False):
     n, m = solver.mesh.n_nodes, solver.mesh.n_elements
     if node_major:
         return f.new_empty(tuple(f.shape), dtype=torch.float64), torch.empty((), dtype=torch.int64)
-    B_f = f.shape[0] if f.dim() == 2 else None
-    _, B_k = _kappa_mode(kappa, m, B_f)
-    B = B_f if B_f is not None else (B_k if B_k is not None else 1)
+    _, B, _ = _kappa_layout(kappa, m, f.shape[0] if f.dim() == 2 else None, False)
     shape = (B, n) if (f.dim() == 2 or B > 1) else (n,)
     return f.new_empty(shape, dtype=torch.float64), torch.empty((), dtype=torch.int64)
 
@@ -1034,10 +1088,7 @@ def fe_solve_backward(gbar: torch.Tensor, token: torch.Tensor, need_k: bool, nee
                       kappa_like: torch.Tensor, f_like: torch.Tensor,
                       load_like: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(dL/dkappa, dL/df, dL/dload) for the forward call named by `token`; unused gradients come back empty."""
-    state = _STATES.get(int(token))
-    if state is None:
-        raise RuntimeError("diffhe: adjoint state of this solve is gone (its autograd graph was freed)")
-    gk, gf, gl = _solve_backward(state, gbar, need_k, need_f, need_load)
+    gk, gf, gl = _solve_backward(_state_of(token), gbar, need_k, need_f, need_load)[:3]
     return (gk if gk is not None else kappa_like.new_empty(0), gf if gf is not None else f_like.new_empty(0),
             gl.to(load_like.dtype) if gl is not None else load_like.new_empty(0))
 
@@ -1050,20 +1101,9 @@ def _fe_solve_backward_fake(gbar, token, need_k, need_f, need_load, kappa_like, 
 
 
 def _fe_setup_context(ctx, inputs, output):
-    kappa, f, load, _, _, node_major = inputs
-    # node-major: u may BE the solver's saved iterate -- saving it lets autograd refuse a backward after an in-place edit
-    real = not isinstance(output[1], torch._subclasses.FakeTensor)
-    # A sentinel among the saved tensors: autograd drops its saved tensors at the end of a backward pass that does not
-    # retain the graph, the sentinel dies with them and takes the adjoint state (per-sample operators, iterates: tens of
-    # GB at the bench size) along -- BEFORE the caller lets go of u / the loss.  A state that lived until then overlaps
-    # the next step's forward solve and the caching allocator has to find a second set of blocks for it: measured as
-    # new device allocations (hipMalloc, 70-700 ms each) in otherwise steady 93 ms steps.
-    sentinel = (torch.empty(0),) if real else ()
-    ctx.save_for_backward(output[1], kappa, f, load, *((output[0],) if node_major else ()), *sentinel)
-    ctx.handle, ctx.node_major = inputs[3], bool(node_major)
-    if real:
-        weakref.finalize(sentinel[0], _STATES.pop, int(output[1]), None)
-        ctx.state_guard = _StateGuard(int(output[1]))       # and in any case together with the graph
+    kappa, f, load, handle, _, node_major = inputs
+    _save_for_adjoint(ctx, (kappa, f, load), output, handle, node_major)
+
 
 
 def _element_forms(plan: SolvePlan):
@@ -1142,18 +1182,9 @@ def _second_order_backward(ctx, grad_u):
     B = lam_b.shape[0]
     gk = gf = gl = None
     if need_k:
-        B_f = B if (f.dim() == 2) else None
-        kappa_em = bool(node_major and kappa.dim() == 2 and tuple(kappa.shape) == (m, B))
-        mode, _ = (K_SAMPLE_ELEM, B) if kappa_em else _kappa_mode(kappa, m, B_f)
+        mode, _, kappa_em = _kappa_layout(kappa, m, B if f.dim() == 2 else None, node_major)
         s_be = -torch.einsum("bep,epq,beq->be", lam_b[:, el], k0, u_b[:, el])      # (B, m)
-        if mode == K_SCALAR:
-            gk = s_be.sum().reshape(kappa.shape)
-        elif mode == K_SAMPLE:
-            gk = s_be.sum(1).reshape(kappa.shape)
-        elif mode == K_ELEM:
-            gk = s_be.sum(0).reshape(kappa.shape)
-        else:
-            gk = (s_be.t() if kappa_em else s_be).reshape(kappa.shape)
+        gk = _kappa_grad(mode, kappa.shape, per_elem=s_be.t() if kappa_em else s_be)
     if need_f:
         y = torch.einsum("epq,beq->bep", m0, lam_b[:, el])                          # M^T lambda, M symmetric per element
         gf_b = torch.zeros_like(lam_b).index_add_(1, el.reshape(-1), y.reshape(B, -1))

@@ -3,6 +3,7 @@ plan/pattern construction against the oracle, API quirks of the boundary
 (SURVEY 8(b)).  No HIP kernel runs here."""
 import hashlib
 import os
+import types
 
 import numpy as np
 import pytest
@@ -11,7 +12,8 @@ import torch
 from diffhe import FEMesh, DifferentiableFESolver, PhysicsLoss, NeuralPDE
 from diffhe.plan import (build_ell_pattern, build_dia_pattern, detect_lattice, lattice_elements, chain_segments,
                          padded_batch, _bc_arrays)
-from diffhe.solver import _kappa_mode, K_SCALAR, K_SAMPLE, K_ELEM, K_SAMPLE_ELEM
+from diffhe.solver import (_kappa_mode, _kappa_layout, _call_options, _select_path, _ChainSolve, _LatticeSolve, _EllSolve,
+                           K_SCALAR, K_SAMPLE, K_ELEM, K_SAMPLE_ELEM)
 from oracle import p1_oracle as orc
 from _util import golden, golden_json
 
@@ -172,6 +174,74 @@ def test_kappa_modes():
     with pytest.raises(ValueError):
         _kappa_mode(torch.ones(5, 3), m, 5)
 
+
+
+def test_kappa_layout():
+    """One classification for the forward, the fake op and the second-order backward: (mode, B, element-major)."""
+    m = 32
+    assert _kappa_layout(torch.tensor(1.0), m, None, False) == (K_SCALAR, 1, False)
+    assert _kappa_layout(torch.ones(5), m, None, False) == (K_SAMPLE, 5, False)          # B from kappa
+    assert _kappa_layout(torch.ones(m), m, 5, False) == (K_ELEM, 5, False)
+    assert _kappa_layout(torch.ones(5, m), m, 5, True) == (K_SAMPLE_ELEM, 5, False)
+    assert _kappa_layout(torch.ones(m, 5), m, 5, True) == (K_SAMPLE_ELEM, 5, True)       # (m, B), layout='node'
+    with pytest.raises(ValueError):
+        _kappa_layout(torch.ones(m, 5), m, 5, False)
+    with pytest.raises(ValueError, match="does not match"):
+        _kappa_layout(torch.ones(4), m, 5, False)
+
+
+def _opts(mode, *, chain=False, lattice=True, closed=True, n=1_000_000, **kw):
+    s = DifferentiableFESolver(FEMesh.rectangle(2, 2), 1.0, **kw)
+    tol, mg, amg = _call_options(chain=chain, lattice=lattice, closed_boundary=closed, n=n, mode=mode,
+                                 tol_user=s._tol_user, mg_user=s._mg_user, mg=s.mg, amg=s.amg)
+    assert s.mg == DifferentiableFESolver(FEMesh.rectangle(2, 2), 1.0, **kw).mg      # the solver's dicts are not edited
+    return tol, mg["tol_energy"], mg["floor"], amg.get("floor")
+
+
+def test_call_options_table():
+    """The per-call tolerances of DESIGN section 4, "Stopping rule": (tol, tol_energy, mg floor, amg floor)."""
+    S, E, SE = K_SAMPLE, K_ELEM, K_SAMPLE_ELEM
+    # 1D chain (on the scan or, with a reaction term, on the general path)
+    assert _opts(K_SCALAR, chain=True, lattice=False, closed=False, n=101) == (1e-12, 0.0, 1, None)
+    assert _opts(E, chain=True, lattice=False, closed=False, n=101) == (1e-12, 0.0, 0, 0)
+    # closed lattice, n >= 1e5 and n < 1e5, scalar and per-element kappa
+    assert _opts(K_SCALAR) == (1e-12, 1e-11, 1, None)
+    assert _opts(S, n=100_000) == (1e-12, 1e-11, 1, None)
+    assert _opts(SE) == (1e-14, 1e-11 * 1e-2, 0, 0)
+    assert _opts(S, n=99_999) == (1e-13, 1e-11 * 0.1, 1, None)
+    assert _opts(E, n=99_999) == (1e-14, 1e-11 * 1e-2 * 0.1, 0, 0)
+    # lattice with a Neumann part: residual rule alone
+    assert _opts(S, closed=False) == (1e-14, 0.0, 1, None)
+    assert _opts(SE, closed=False, n=5000) == (1e-14, 0.0, 0, 0)
+    # general path
+    assert _opts(K_SCALAR, lattice=False) == (1e-13, 0.0, 1, None)
+    assert _opts(S, lattice=False, closed=False) == (1e-13, 0.0, 1, None)
+    assert _opts(E, lattice=False) == (1e-14, 0.0, 0, 0)
+    # an explicit tol is a residual request: the energy stop steps aside unless asked for too (then as given)
+    assert _opts(S, tol=1e-9) == (1e-9, 0.0, 1, None)
+    assert _opts(S, tol=1e-9, mg=dict(tol_energy=3e-11)) == (1e-9, 3e-11, 1, None)
+    assert _opts(SE, n=5000, mg=dict(tol_energy=3e-11)) == (1e-14, 3e-11, 0, 0)
+    assert _opts(S, closed=False, mg=dict(tol_energy=3e-11)) == (1e-14, 3e-11, 1, None)
+    # a user floor is honoured with per-element kappa
+    assert _opts(E, mg=dict(floor=1), amg=dict(floor=1)) == (1e-14, 1e-11 * 1e-2, 1, 1)
+    assert _opts(E, lattice=False, mg=dict(floor=0)) == (1e-14, 0.0, 0, 0)
+
+
+def test_select_path_rules():
+    solver = types.SimpleNamespace(method="auto")
+
+    def plan(**kw):
+        base = dict(is_chain=False, is_lattice=False, is_p2=False, n=10_000, n_bc_interior=0)
+        return types.SimpleNamespace(**{**base, **kw})
+
+    assert _select_path(plan(is_chain=True), solver, 0.0) is _ChainSolve
+    assert _select_path(plan(is_chain=True), solver, 0.5) is _EllSolve          # the scan has no reaction term
+    assert _select_path(plan(is_lattice=True, n_bc_interior=200), solver, 0.0) is _LatticeSolve   # 2 % interior
+    assert _select_path(plan(is_lattice=True, n_bc_interior=201), solver, 0.5) is _EllSolve
+    assert _select_path(plan(is_lattice=True), types.SimpleNamespace(method="ell"), 0.0) is _EllSolve
+    assert _select_path(plan(), solver, 0.0) is _EllSolve
+    with pytest.raises(NotImplementedError):
+        _select_path(plan(is_p2=True), solver, 0.5)
 
 def test_solver_boundary_quirks():
     """kappa wrapping, Parameter registration, errors."""
