@@ -79,6 +79,11 @@ SIGNATURES = {
     "diffhe_p1_grad_kappa_shared": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "diffhe_p1_shape_grad": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _D, _P, _P, _P,
                                   _P, _P]),
+    "diffhe_bc_lift": (_I, [_P, _I, _I, _P, _P, _L, _L, _P, _P, _L, _L, _P, _P, _P, _I, _P, _L, _L, _I, _P]),
+    "diffhe_bc_grad": (_I, [_P, _I, _I, _P, _P, _L, _L, _P, _P, _P, _P, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L,
+                            _L, _P, _I, _P]),
+    "diffhe_bc_scatter": (_I, [_P, _I, _P, _L, _L, _P, _L, _L, _I, _P]),
+    "diffhe_bc_grad_kappa": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _P]),
     "diffhe_to_node_major": (_I, [_P, _L, _P, _P, _I, _I, _I, _P]),
     "diffhe_to_sample_major": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),
 }

@@ -18,6 +18,11 @@ theta = 1/2 (Crank-Nicolson, second order) is written in its incremental form
 
 (w = (u_k + u_{k+1}) / 2; Dirichlet rows of w hold g, so u_{k+1} = g there when u_k does) -- again one solve per
 step, with reaction = 2 / dt, and no product K u_k to form.
+
+Time-dependent Dirichlet data (ours): `step(u, f, g)` / `forward(u0, n_steps, f, g)` take the values g at t_{k+1} in the
+order of `mesh.dirichlet_index()`, (n_D,) or (B, n_D), through the solver's `dirichlet=` (diffhe.dirichlet): the
+Dirichlet rows of w hold g (backward Euler) or (u_k[D] + g) / 2 (Crank-Nicolson, so that u_{k+1} = 2 w - u_k = g), and
+`backward()` carries gradients to every step's g through the same discrete adjoint.  g = None keeps the mesh's values.
 """
 from __future__ import annotations
 
@@ -53,6 +58,7 @@ class HeatEquation(nn.Module):
         solver_options.setdefault("warm_start", "forward")
         self.solver = DifferentiableFESolver(mesh, kappa, reaction=1.0 / (self.theta * self.dt), **solver_options)
         self._mass = None
+        self._didx = None
 
     @property
     def kappa(self) -> torch.Tensor:
@@ -64,22 +70,41 @@ class HeatEquation(nn.Module):
             self._mass = get_plan(self.mesh, _resolve_device(self.solver._device)).lumped_mass()
         return self._mass
 
-    def step(self, u: torch.Tensor, f: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _dirichlet_index(self, device) -> torch.Tensor:
+        if self._didx is None or self._didx.device != torch.device(device):
+            self._didx = self.mesh.dirichlet_index().to(device)
+        return self._didx
+
+    def step(self, u: torch.Tensor, f: Optional[torch.Tensor] = None, g: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One time step: u (n,) or (B,n) at t_k -> u at t_k + dt.  f: nodal forcing (n,) or (B,n) at the new time
-        level (backward Euler) / at the midpoint (Crank-Nicolson); None = 0."""
+        level (backward Euler) / at the midpoint (Crank-Nicolson); None = 0.  g: Dirichlet values at t_k + dt, (n_D,) or
+        (B, n_D) in the order of `mesh.dirichlet_index()`; None = the mesh's."""
         m = self.lumped_mass().to(u.device)
         if f is None:
             f = torch.zeros(self.mesh.n_nodes, dtype=torch.float64, device=u.device)
         load = m * u * self.solver.reaction         # M_L u_k / (theta dt); rows of Dirichlet nodes are ignored
-        w = self.solver(f, load=load)
+        if g is None:
+            w = self.solver(f, load=load)
+        else:
+            g = g.to(device=u.device, dtype=torch.float64)
+            gw = g if self.theta == 1.0 else 0.5 * (u.index_select(-1, self._dirichlet_index(u.device)) + g)
+            w = self.solver(f, load=load, dirichlet=gw)
         return w if self.theta == 1.0 else 2.0 * w - u
 
-    def forward(self, u0: torch.Tensor, n_steps: int, f=None, return_all: bool = False) -> torch.Tensor:
+    def forward(self, u0: torch.Tensor, n_steps: int, f=None, g=None, return_all: bool = False) -> torch.Tensor:
         """March `n_steps` steps from u0.  f: None, a tensor (constant in time) or a callable t -> tensor evaluated at
-        t_{k+1} (backward Euler) / t_k + dt/2 (Crank-Nicolson).  Returns u(T), or the stacked (n_steps + 1, ...) history."""
+        t_{k+1} (backward Euler) / t_k + dt/2 (Crank-Nicolson).  g: None (the mesh's Dirichlet values), a tensor
+        (constant in time) or a callable t -> (n_D,) / (B, n_D) tensor evaluated at t_{k+1}; the initial state takes
+        g(0).  Returns u(T), or the stacked (n_steps + 1, ...) history."""
         u = u0.to(torch.float64)
         bc = self.mesh.dirichlet_nodes
-        if bc:     # the initial state takes the Dirichlet values, like every later one
+        if g is not None:
+            g0 = (g(0.0) if callable(g) else g).to(device=u.device, dtype=torch.float64)
+            if u.dim() == 1 and g0.dim() == 2:
+                u = u.expand(g0.shape[0], -1)
+            idx = self._dirichlet_index(u.device)
+            u = u.index_copy(-1, idx, g0.expand(u.shape[:-1] + (len(idx),)))
+        elif bc:     # the initial state takes the Dirichlet values, like every later one
             idx = torch.as_tensor(list(bc.keys()), dtype=torch.long, device=u.device)
             val = torch.as_tensor(list(bc.values()), dtype=torch.float64, device=u.device)
             u = u.index_copy(-1, idx, val.expand(u.shape[:-1] + val.shape) if u.dim() == 2 else val)
@@ -87,7 +112,8 @@ class HeatEquation(nn.Module):
         for k in range(n_steps):
             t = (k + self.theta) * self.dt
             fk = f(t) if callable(f) else f
-            u = self.step(u, fk)
+            gk = g((k + 1) * self.dt) if callable(g) else g
+            u = self.step(u, fk, gk)
             if return_all:
                 hist.append(u)
         return torch.stack(hist) if return_all else u

@@ -134,6 +134,16 @@ class FEMesh:
             keep[np.fromiter(self.dirichlet_nodes.keys(), dtype=np.int64, count=len(self.dirichlet_nodes))] = False
         return np.nonzero(keep)[0].tolist()
 
+    def dirichlet_index(self) -> torch.Tensor:
+        """LongTensor of the Dirichlet node ids in ascending order: the order of the values `dirichlet=` takes."""
+        return torch.as_tensor(sorted(self.dirichlet_nodes.keys()), dtype=torch.long).reshape(-1)
+
+    def dirichlet_values(self) -> torch.Tensor:
+        """The values of `dirichlet_nodes` in the order of `dirichlet_index()`, fp64: `solver(f, dirichlet=
+        mesh.dirichlet_values())` solves what `solver(f)` does."""
+        bc = self.dirichlet_nodes
+        return torch.tensor([float(bc[k]) for k in sorted(bc.keys())], dtype=torch.float64).reshape(-1)
+
     def h(self) -> float:
         """Smallest element length, 1D only (reference mesh.py:131-136)."""
         if self.dim == 1:

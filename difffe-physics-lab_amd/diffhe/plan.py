@@ -669,6 +669,65 @@ class SolvePlan:
             cached = self.__dict__["_shape_inc"] = (dev(ptr.astype(np.int32)), dev(order))
         return cached
 
+    def zero_g(self) -> torch.Tensor:
+        """(n,) zeros: the Dirichlet data every kernel reads when the values come per call (`dirichlet=`)."""
+        z = self.__dict__.get("_zero_g")
+        if z is None:
+            z = self.__dict__["_zero_g"] = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+        return z
+
+    def element_stiffness(self) -> torch.Tensor:
+        """(npe*npe, m) unit-kappa element stiffness, entry p*npe + q: the table the solve's path holds (`k0` of the
+        general path, of lattice level 0, or h_e-scaled +-1 for the chain's scan, which keeps no table)."""
+        if self._ell_ready:
+            return self.k0
+        if self.is_lattice:
+            return self.levels[0].k0
+        k0 = self.__dict__.get("_chain_k0")
+        if k0 is None:
+            inv_h = 1.0 / (self.x[1:] - self.x[:-1])
+            k0 = self.__dict__["_chain_k0"] = torch.stack([inv_h, -inv_h, -inv_h, inv_h]).contiguous()
+        return k0
+
+    def dirichlet_band(self) -> dict:
+        """The boundary band of per-call Dirichlet data (csrc/bc.hip), int32 on the device, built once per plan from the
+        connectivity and the SET of Dirichlet nodes:
+          d_idx (n_D) ascending Dirichlet node ids; d_slot (n) slot of a node in d_idx, -1 on free nodes;
+          rows / row_ptr / row_inc: the free nodes with a Dirichlet neighbour and, per row, the codes e * npe + p of its
+            (element, local node) pairs in the elements that touch a Dirichlet node (element order);
+          d_ptr / d_inc: the same pairs of every Dirichlet node; band_elems: the elements that touch one."""
+        cached = self.__dict__.get("_dirichlet_band")
+        if cached is not None:
+            return cached
+        el = self._elements
+        m, npe = el.shape
+        if m * npe >= 2 ** 31:
+            raise ValueError("mesh too large for int32 incidence lists")
+        is_bc = self.is_bc.cpu().numpy().astype(bool)
+        d_idx = np.nonzero(is_bc)[0]
+        d_slot = np.full(self.n, -1, dtype=np.int64)
+        d_slot[d_idx] = np.arange(len(d_idx))
+        touch = is_bc[el].any(axis=1)                                    # elements with a Dirichlet node
+        codes = np.nonzero(np.repeat(touch, npe))[0]                     # e * npe + p, element order
+        nodes = el.reshape(-1)[codes]
+        order = np.argsort(nodes, kind="stable")
+        codes, nodes = codes[order], nodes[order]
+
+        def csr(want_bc, rows):
+            keep = is_bc[nodes] == want_bc
+            nd = nodes[keep]
+            return np.searchsorted(nd, np.append(rows, self.n)), codes[keep]
+
+        rows = np.unique(nodes[~is_bc[nodes]])
+        row_ptr, row_inc = csr(False, rows)
+        d_ptr, d_inc = csr(True, d_idx)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)  # noqa: E731
+        cached = self.__dict__["_dirichlet_band"] = dict(
+            n_d=len(d_idx), d_idx=dev(d_idx), d_slot=dev(d_slot), rows=dev(rows), n_rows=len(rows),
+            row_ptr=dev(row_ptr), row_inc=dev(row_inc), d_ptr=dev(d_ptr), d_inc=dev(d_inc),
+            band_elems=dev(np.nonzero(touch)[0]), n_be=int(touch.sum()))
+        return cached
+
     def ensure_ell(self):
         """ELL pattern, gather lists, element integrals and the ELL load matrix of the general path."""
         with self._build_lock:

@@ -148,6 +148,12 @@ class ShapeDifferentiableFESolver(DifferentiableFESolver3D):
 
     _dims = (1, 2, 3)
 
+    def _solve_bc_op(self, f64: torch.Tensor, load64: torch.Tensor, g64: torch.Tensor, node_major: bool) -> torch.Tensor:
+        if self.mesh.nodes.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("diffhe: dirichlet= together with node gradients is not implemented "
+                                      "(mesh.nodes requires grad)")
+        return super()._solve_bc_op(f64, load64, g64, node_major)
+
     def _solve_op(self, f64: torch.Tensor, load64: torch.Tensor, node_major: bool) -> torch.Tensor:
         nodes = self.mesh.nodes
         if not (nodes.requires_grad and torch.is_grad_enabled()):

@@ -94,6 +94,7 @@ class _Engine:
         self.p = plan
         self.tol, self.max_iter, self.check_every, self.assembly = tol, max_iter, check_every, assembly
         self.ref_order = False      # per-sample lattice matrices in the reference's exact operation order (operator="assembled")
+        self.g = plan.g             # the (n,) Dirichlet data the kernels read: the plan's, or zeros when it comes per call
         self.L = _hip.lib()
 
     # -- layout helpers -----------------------------------------------------------------
@@ -147,7 +148,7 @@ class _Engine:
             # quadratic triangles (ours; no reference operator to be bit-identical with): kappa * k0, gathered
             _hip.check(L.diffhe_ell_assemble_rows(_hip.ptr(p.k0), _hip.ptr(kdev), kse, ksb, _hip.ptr(p.ent_ptr),
                                                   _hip.ptr(p.contrib), _hip.ptr(p.cols), None, _hip.ptr(p.is_bc),
-                                                  _hip.ptr(p.g), _hip.ptr(vals), _hip.ptr(lift), p.n, p.m, p.W, Bv, st),
+                                                  _hip.ptr(self.g), _hip.ptr(vals), _hip.ptr(lift), p.n, p.m, p.W, Bv, st),
                        "diffhe_ell_assemble_rows(P2)")
         elif self.assembly == "atomic" and Bv > 1:
             vals.zero_()
@@ -155,7 +156,7 @@ class _Engine:
                                                     ksb, _hip.ptr(p.slot_of), _hip.ptr(vals), p.n, p.m, p.W, Bv, st),
                        "diffhe_ell_assemble_atomic")
             lift.zero_()  # apply_dirichlet returns F - lift: feed F = 0, negate
-            _hip.check(L.diffhe_ell_apply_dirichlet(_hip.ptr(p.cols), _hip.ptr(p.is_bc), _hip.ptr(p.g),
+            _hip.check(L.diffhe_ell_apply_dirichlet(_hip.ptr(p.cols), _hip.ptr(p.is_bc), _hip.ptr(self.g),
                                                     _hip.ptr(vals), _hip.ptr(lift), p.n, p.W, Bv, st),
                        "diffhe_ell_apply_dirichlet")
             lift.neg_()
@@ -163,7 +164,7 @@ class _Engine:
             # reference operation order: values bit-identical to the reference's K (include/diffhe_hip.h)
             _hip.check(L.diffhe_ell_assemble_rows_ref(_hip.ptr(p.tnum), _hip.ptr(p.den), _hip.ptr(kdev), kse, ksb,
                                                       _hip.ptr(p.ent_ptr), _hip.ptr(p.contrib), _hip.ptr(p.cols), None,
-                                                      _hip.ptr(p.is_bc), _hip.ptr(p.g), _hip.ptr(vals), _hip.ptr(lift),
+                                                      _hip.ptr(p.is_bc), _hip.ptr(self.g), _hip.ptr(vals), _hip.ptr(lift),
                                                       p.n, p.m, p.W, Bv, st), "diffhe_ell_assemble_rows_ref")
         return vals, lift
 
@@ -262,15 +263,15 @@ class _Engine:
                 # difference of the entries shows as 4e-10 in u, which is why per-sample scalars are left unfactored on
                 # them, `closed_` in _LatticeSolve.forward) -- they, per-sample SCALARS that are not factored, and
                 # operator="assembled" keep the bit-identical order below
-                self._lattice_rows(lev, "k0ref", kl, kse, ksb, p.g, v, lf, Bv, st)
+                self._lattice_rows(lev, "k0ref", kl, kse, ksb, self.g, v, lf, Bv, st)
             elif li == 0 and kl is not None:   # the operator the solution is defined by: reference operation order
                 _hip.check(L.diffhe_ell_assemble_rows_ref(_hip.ptr(lev.tnum), _hip.ptr(lev.den), _hip.ptr(kl), kse, ksb,
                                                           _hip.ptr(lev.ent_ptr), _hip.ptr(lev.contrib),
                                                           _hip.ptr(lev.cols), _hip.ptr(lev.store_slot),
-                                                          _hip.ptr(lev.is_bc), _hip.ptr(p.g), _hip.ptr(v), _hip.ptr(lf),
+                                                          _hip.ptr(lev.is_bc), _hip.ptr(self.g), _hip.ptr(v), _hip.ptr(lf),
                                                           lev.n, lev.m, 7, Bv, st), "diffhe_ell_assemble_rows_ref(lattice)")
             else:
-                self._lattice_rows(lev, "k0", kl, kse, ksb, p.g if li == 0 else lev.zero_g(), v, lf, Bv, st)
+                self._lattice_rows(lev, "k0", kl, kse, ksb, self.g if li == 0 else lev.zero_g(), v, lf, Bv, st)
             vals.append(v)
             if li == 0:
                 lift = lf
@@ -463,7 +464,7 @@ class _Engine:
             dk_e = torch.empty((p.m, Bp), dtype=torch.float64, device=p.device)
             small = lev.compact("k0")
             _hip.check(L.diffhe_lattice_grad_kappa(lev.nx, lev.ny, _hip.ptr(small if small is not None else lev.k0),
-                                                   1 if small is not None else 0, _hip.ptr(lam), _hip.ptr(x), _hip.ptr(p.g),
+                                                   1 if small is not None else 0, _hip.ptr(lam), _hip.ptr(x), _hip.ptr(self.g),
                                                    _hip.ptr(dk_e), Bp, _stream(p.device)), "diffhe_lattice_grad_kappa")
             return dk_e, None
         nblk = L.diffhe_grad_kappa_blocks(p.m, Bp)
@@ -471,7 +472,7 @@ class _Engine:
         part = torch.empty((nblk, Bp), dtype=torch.float64, device=p.device)
         dk_sum = torch.empty(Bp, dtype=torch.float64, device=p.device)
         k0 = p.k0 if p._ell_ready else p.levels[0].k0      # lattice meshes keep k0 on level 0
-        _hip.check(L.diffhe_p1_grad_kappa(_hip.ptr(p.elems), _hip.ptr(k0), _hip.ptr(lam), _hip.ptr(x), _hip.ptr(p.g),
+        _hip.check(L.diffhe_p1_grad_kappa(_hip.ptr(p.elems), _hip.ptr(k0), _hip.ptr(lam), _hip.ptr(x), _hip.ptr(self.g),
                                           p.npe, p.m, Bp, _hip.ptr(dk_e), _hip.ptr(part), _hip.ptr(dk_sum),
                                           _stream(p.device)), "diffhe_p1_grad_kappa")
         return dk_e, dk_sum
@@ -483,9 +484,47 @@ class _Engine:
         dk = torch.empty(p.m, dtype=torch.float64, device=p.device)
         k0 = p.k0 if p._ell_ready else p.levels[0].k0
         _hip.check(L.diffhe_p1_grad_kappa_shared(_hip.ptr(p.elems), _hip.ptr(k0), _hip.ptr(lam), _hip.ptr(x),
-                                                 _hip.ptr(p.g), p.npe, p.m, B, Bp, _hip.ptr(dk), _stream(p.device)),
+                                                 _hip.ptr(self.g), p.npe, p.m, B, Bp, _hip.ptr(dk), _stream(p.device)),
                    "diffhe_p1_grad_kappa_shared")
         return dk
+
+    # -- per-call Dirichlet data (csrc/bc.hip): boundary band only ------------------------------------------
+    def bc_lift(self, kappa_s, G, rhs, rsn, rsb, B):
+        """rhs_b -= K_b[F, D] G_b on the free rows with a Dirichlet neighbour; rhs (i, b) at i*rsn + b*rsb."""
+        p, band = self.p, self.p.dirichlet_band()
+        (kdev, kse, ksb), (gdev, gsj, gsb) = kappa_s, G
+        _hip.check(self.L.diffhe_bc_lift(_hip.ptr(p.elems), p.npe, p.m, _hip.ptr(p.element_stiffness()), _hip.ptr(kdev),
+                                         kse, ksb, _hip.ptr(band["d_slot"]), _hip.ptr(gdev), gsj, gsb,
+                                         _hip.ptr(band["rows"]), _hip.ptr(band["row_ptr"]), _hip.ptr(band["row_inc"]),
+                                         band["n_rows"], _hip.ptr(rhs), rsn, rsb, B, _stream(p.device)), "diffhe_bc_lift")
+
+    def bc_scatter(self, G, u, usn, usb, B):
+        """u_b[j] = G_b[j] on the Dirichlet rows; u (i, b) at i*usn + b*usb."""
+        p, band = self.p, self.p.dirichlet_band()
+        gdev, gsj, gsb = G
+        _hip.check(self.L.diffhe_bc_scatter(_hip.ptr(band["d_idx"]), band["n_d"], _hip.ptr(gdev), gsj, gsb, _hip.ptr(u),
+                                            usn, usb, B, _stream(p.device)), "diffhe_bc_scatter")
+
+    def bc_grad(self, kappa_s, lam, lsn, lsb, gbar, gsn, gsb, out, osj, osb, G=None, dots=None, B=1):
+        """out_b[j] = gbar_b[j] - (K_b lam_b)_j on the Dirichlet nodes (dL/dG_b); dots (n_D, B): G_b[j] (K_1 lam_b)_j."""
+        p, band = self.p, self.p.dirichlet_band()
+        kdev, kse, ksb = kappa_s
+        gdev, Gsj, Gsb = G if G is not None else (None, 0, 0)
+        _hip.check(self.L.diffhe_bc_grad(_hip.ptr(p.elems), p.npe, p.m, _hip.ptr(p.element_stiffness()), _hip.ptr(kdev),
+                                         kse, ksb, _hip.ptr(band["d_slot"]), _hip.ptr(band["d_idx"]),
+                                         _hip.ptr(band["d_ptr"]), _hip.ptr(band["d_inc"]), band["n_d"], _hip.ptr(lam),
+                                         lsn, lsb, _hip.ptr(gbar), gsn, gsb, _hip.ptr(out), osj, osb, _hip.ptr(gdev),
+                                         Gsj, Gsb, _hip.ptr(dots), B, _stream(p.device)), "diffhe_bc_grad")
+
+    def bc_grad_kappa(self, lam, lsn, lsb, G, dk, dse, dsb, shared, B):
+        """dk (e, b) at e*dse + b*dsb -= lam_b^T k0_e G_b on the elements that touch a Dirichlet node (shared: dk (e) at
+        e*dse, minus the sum over the batch)."""
+        p, band = self.p, self.p.dirichlet_band()
+        gdev, gsj, gsb = G
+        _hip.check(self.L.diffhe_bc_grad_kappa(_hip.ptr(p.elems), p.npe, p.m, _hip.ptr(p.element_stiffness()),
+                                               _hip.ptr(band["d_slot"]), _hip.ptr(band["band_elems"]), band["n_be"],
+                                               _hip.ptr(lam), lsn, lsb, _hip.ptr(gdev), gsj, gsb, _hip.ptr(dk), dse, dsb,
+                                               int(shared), B, _stream(p.device)), "diffhe_bc_grad_kappa")
 
 
 def _precision_text(flags: int, coeff_storage: str, Bv: int, Bp: int, fused_lib: int, recompute_ap: bool) -> str:
@@ -585,9 +624,12 @@ class _Call:
     kappa: Optional[torch.Tensor] = None
     f_dev: Optional[torch.Tensor] = None       # (B, n) or (n,); layout='node': a (B, n) view of (n, B) data
     load_dev: Optional[torch.Tensor] = None    # (B, n) or None
+    # per-call Dirichlet data (`dirichlet=`): (device values, stride per Dirichlet node, stride per sample), G_b[j] at
+    # j * sj + b * sb (sb = 0: one G for the batch); None: the mesh's.  Boundary-sized: the adjoint state keeps it
+    bc: Optional[tuple] = None
 
     @classmethod
-    def of(cls, solver, plan: SolvePlan, kappa, f, load, node_major) -> "_Call":
+    def of(cls, solver, plan: SolvePlan, kappa, f, load, node_major, dirichlet=None) -> "_Call":
         if load is not None and load.numel() == 0:
             load = None
         batched, n, out_device = f.dim() == 2, plan.n, f.device
@@ -605,8 +647,18 @@ class _Call:
             load_dev = (load_dev.reshape(1, n).expand(B, n) if load_dev.dim() == 1 else load_dev).contiguous()   # (B, n)
             if load_dev.shape != (B, n):
                 raise ValueError(f"load must be (n,) or (B,n) with B={B}, n={n}, got {tuple(load.shape)}")
+        bc = None
+        if dirichlet is not None:
+            gd = dirichlet.detach().to(plan.device, torch.float64)
+            if gd.dim() == 1 and gd.shape[0] == plan.n_bc:
+                bc = (gd.contiguous(), 1, 0)
+            elif gd.dim() == 2 and tuple(gd.shape) == ((plan.n_bc, B) if node_major else (B, plan.n_bc)):
+                bc = (gd, gd.stride(0), gd.stride(1)) if node_major else (gd, gd.stride(1), gd.stride(0))
+            else:
+                raise ValueError(f"dirichlet must be ({plan.n_bc},) or "
+                                 f"{(plan.n_bc, B) if node_major else (B, plan.n_bc)}, got {tuple(dirichlet.shape)}")
         return cls(B, mode, kappa_em, batched, node_major, out_device, kappa.shape, kappa.device,
-                   load is not None and load.dim() == 2, float(solver.reaction), kappa, f_dev, load_dev)
+                   load is not None and load.dim() == 2, float(solver.reaction), kappa, f_dev, load_dev, bc)
 
     def facts(self) -> "_Call":
         return replace(self, kappa=None, f_dev=None, load_dev=None)
@@ -673,6 +725,8 @@ class _PathSolve:
         self.solver, self.plan, self.call, self.mg, self.amg = solver, plan, call.facts(), mg, amg
         self.eng = _Engine(plan, tol, solver.max_iter, solver.check_every, solver.assembly)
         self.eng.ref_order = solver.operator == "assembled"
+        if call.bc is not None:     # per-call Dirichlet data: the path solves with homogeneous data, csrc/bc.hip adds G
+            self.eng.g = plan.zero_g()
 
 
 class _ChainSolve(_PathSolve):
@@ -681,11 +735,18 @@ class _ChainSolve(_PathSolve):
     def forward(self, call: _Call, info: SolveInfo) -> torch.Tensor:
         plan, L, B, n = self.plan, self.eng.L, call.B, self.plan.n
         f_dev, batched = call.f_dev, call.batched
-        if call.load_dev is not None:
-            # the 1D load map of solver.py:95-96 is diagonal (h/2 from each side): an extra load is a change of forcing
-            f_dev = (f_dev if batched else f_dev.reshape(1, n).expand(B, n)) + call.load_dev / plan.lumped_mass()
-            batched = True
         self.kdev, self.kse, self.ksb = _kappa_strided(call.kappa, call.mode, False, B, plan.m, plan.device)
+        load_dev = call.load_dev
+        if call.bc is not None:
+            # per-call Dirichlet data: the lift -K_b[F, D] G_b enters as an extra load, the scan sees homogeneous data
+            self.bc_kappa = (self.kdev, self.kse, self.ksb)
+            lift = torch.zeros((B, n), dtype=torch.float64, device=plan.device)
+            self.eng.bc_lift(self.bc_kappa, call.bc, lift, 1, n, B)
+            load_dev = lift if load_dev is None else load_dev + lift
+        if load_dev is not None:
+            # the 1D load map of solver.py:95-96 is diagonal (h/2 from each side): an extra load is a change of forcing
+            f_dev = (f_dev if batched else f_dev.reshape(1, n).expand(B, n)) + load_dev / plan.lumped_mass()
+            batched = True
         self.u = torch.empty((B, n), dtype=torch.float64, device=plan.device)      # Dirichlet values included
         # reference-order mode (default): the system the reference assembled in fp64 (rounded diagonal), see chain1d.hip
         self.chain_flags = _hip.CHAIN_REFERENCE_ORDER if self.solver.chain == "reference" else 0
@@ -693,9 +754,11 @@ class _ChainSolve(_PathSolve):
         ns = L.diffhe_chain1d_stage_doubles(n, B, plan.max_seg_len, self.chain_flags)   # 0: every segment in registers
         stage = torch.empty(ns, dtype=torch.float64, device=plan.device) if ns > 0 else None
         _hip.check(L.diffhe_chain1d_solve(_hip.ptr(plan.x), _hip.ptr(self.kdev), self.ksb, self.kse, _hip.ptr(f_dev),
-                                          n if batched else 0, _hip.ptr(plan.seg), plan.n_seg, _hip.ptr(plan.g),
+                                          n if batched else 0, _hip.ptr(plan.seg), plan.n_seg, _hip.ptr(self.eng.g),
                                           _hip.ptr(self.u), n, n, B, plan.max_seg_len, self.chain_flags, _hip.ptr(stage),
                                           _stream(plan.device)), "diffhe_chain1d_solve")
+        if call.bc is not None:     # u keeps G in its Dirichlet rows: the adjoint's dL/dkappa reads u as it is
+            self.eng.bc_scatter(call.bc, self.u, 1, n, B)
         return self.u
 
     def adjoint(self, g: torch.Tensor, need_k: bool, need_f: bool, need_load: bool):
@@ -741,6 +804,9 @@ class _NodeMajorSolve(_PathSolve):
         rhs = eng.load_vector(f_nm, lift, Bv, Bp, lift_scale, lattice=self.lattice)
         if call.load_dev is not None:
             rhs += eng.to_node_major(call.load_dev, B, Bp, plan.n, zero_mask=plan.is_bc)
+        if call.bc is not None:     # per-call Dirichlet data: - K_b[F, D] G_b on the boundary band
+            self.bc_kappa = _kappa_strided(call.kappa, call.mode, call.kappa_em, B, plan.m, plan.device)
+            eng.bc_lift(self.bc_kappa, call.bc, rhs, Bp, 1, B)
         return rhs
 
     def _adjoint_rhs(self, g: torch.Tensor) -> torch.Tensor:
@@ -790,7 +856,7 @@ class _NodeMajorSolve(_PathSolve):
 
     def shape_fields(self, lam):
         """(u, lambda, node stride, sample stride, Dirichlet data) for the node-gradient kernel: (n, Bp) arrays."""
-        return self.x, lam, self.Bp, 1, self.plan.g
+        return self.x, lam, self.Bp, 1, self.eng.g
 
 
 class _LatticeSolve(_NodeMajorSolve):
@@ -833,7 +899,7 @@ class _LatticeSolve(_NodeMajorSolve):
         if solver.warm_start and not bad:
             # the next solve starts from a copy; but with layout='node' and no padding the caller's u IS x: keep a
             # private copy then, an in-place edit of u must not move the next warm start
-            shares = call.node_major and Bp == B and not plan.has_dirichlet_data
+            shares = call.node_major and Bp == B and not plan.has_dirichlet_data and call.bc is None
             plan.warm_put(("u",) + self.wkey, x.clone() if shares else x)
         info.stop_rules = _rule_counts(eng.last_rule, B) if not self.direct else {}
         info.flags = eng.last_flags
@@ -846,7 +912,7 @@ class _LatticeSolve(_NodeMajorSolve):
         info.err_est = float(eng.last_est[:B].max())
         self.vals, self.x, self.Bv, self.scale = vals, x, Bv, scale
         self.lift = lift if Bv == 1 else None
-        return _from_node_major(eng, x, B, Bp, plan.n, call.node_major)
+        return _from_node_major(eng, x, B, Bp, plan.n, call.node_major, call.bc)
 
     def _cycle_coeffs(self, vals, Bv):
         """fp32-stored V-cycle -> (vals32, rdiag32, off16): fp32 copies of per-sample matrices; a batch-SHARED matrix
@@ -927,7 +993,7 @@ class _EllSolve(_NodeMajorSolve):
         info.max_relres = float(relres[:B].max())
         info.factored = bool(factored)
         self.vals, self.x, self.Bv = vals, x, Bv
-        return _from_node_major(eng, x, B, Bp, plan.n, call.node_major)
+        return _from_node_major(eng, x, B, Bp, plan.n, call.node_major, call.bc)
 
     def _amg_hierarchy(self, vals, Bv, factored):
         """The aggregation-multigrid hierarchy of this call (None: no coarse level, Jacobi PCG), after the automatic
@@ -960,13 +1026,13 @@ class _EllSolve(_NodeMajorSolve):
         return eng.cg(self.vals, rhs, self.Bp, self.Bv)
 
 
-def _solve_forward(solver, kappa, f, load=None, node_major=False):
+def _solve_forward(solver, kappa, f, load=None, node_major=False, dirichlet=None):
     """u = (K(kappa) + c M_L)^{-1} (F(f) + load) with Dirichlet elimination (c = solver.reaction, 0 for the reference's
     problem).  Returns (u, state): the path object that keeps what the explicit adjoint needs.  node_major (2D paths):
     f, load and u are (n, B), the solver's own layout: no layout change (with B a valid padded batch and zero Dirichlet
-    data, u IS the solver's iterate)."""
+    data, u IS the solver's iterate).  dirichlet: per-call Dirichlet values (diffhe.dirichlet), None: the mesh's."""
     plan: SolvePlan = solver._plan()
-    call = _Call.of(solver, plan, kappa, f, load, node_major)
+    call = _Call.of(solver, plan, kappa, f, load, node_major, dirichlet)
     path = _select_path(plan, solver, call.reaction)
     tol, mg, amg = _call_options(chain=plan.is_chain, lattice=path is _LatticeSolve, closed_boundary=plan.closed_boundary,
                                  n=plan.n, mode=call.mode, tol_user=solver._tol_user, mg_user=solver._mg_user,
@@ -988,9 +1054,18 @@ def _solve_forward(solver, kappa, f, load=None, node_major=False):
     return out.to(call.out_device), state
 
 
-def _from_node_major(eng, x, B, Bp, n, node_major):
-    """u in the caller's layout from the eliminated-system solution x (n, Bp), Dirichlet values added."""
+def _from_node_major(eng, x, B, Bp, n, node_major, bc=None):
+    """u in the caller's layout from the eliminated-system solution x (n, Bp), Dirichlet values added.  bc: per-call
+    Dirichlet data, written into the Dirichlet rows of a buffer of its own (x stays the private iterate)."""
     p = eng.p
+    if bc is not None:
+        if node_major:
+            u = (x if Bp == B else x[:, :B]).clone(memory_format=torch.contiguous_format)
+            eng.bc_scatter(bc, u, B, 1, B)
+        else:
+            u = eng.to_sample_major(x, B, Bp, n)
+            eng.bc_scatter(bc, u, 1, n, B)
+        return u
     if not node_major:
         return eng.to_sample_major(x, B, Bp, n, add=p.g)
     xo = x if Bp == B else x[:, :B]
@@ -1150,7 +1225,7 @@ def _element_forms(plan: SolvePlan):
     return el, k0, m0
 
 
-def _second_order_backward(ctx, grad_u):
+def _second_order_backward(ctx, grad_u, dirichlet=None):
     """The adjoint written with differentiable pieces, for backward(create_graph=True) / Hessian-vector products:
 
         lambda = A(kappa)^-1 gbar          a solve of the SAME solver class on the mesh with homogeneous Dirichlet data
@@ -1175,7 +1250,10 @@ def _second_order_backward(ctx, grad_u):
     _SOLVERS[id(twin)] = twin
     g = grad_u.to(torch.float64)
     lam, _ = torch.ops.diffhe.fe_solve(kappa, torch.zeros_like(g), g, id(twin), True, node_major)
-    u, _ = torch.ops.diffhe.fe_solve(kappa, f, load, ctx.handle, True, node_major)
+    if dirichlet is None:
+        u, _ = torch.ops.diffhe.fe_solve(kappa, f, load, ctx.handle, True, node_major)
+    else:       # per-call Dirichlet data, not differentiated here (diffhe.dirichlet refuses second order through it)
+        u, _ = torch.ops.diffhe.fe_solve_bc(kappa, f, load, dirichlet.detach(), ctx.handle, True, node_major)
     # (B, n) views for the element-local maps
     lam_b = (lam.t() if node_major else lam).reshape(-1, n)
     u_b = (u.t() if node_major else u).reshape(-1, n)
@@ -1345,14 +1423,19 @@ class DifferentiableFESolver(nn.Module):
         twin.mg, twin.amg, twin.warm_start = dict(self.mg), dict(self.amg), False
         return twin
 
-    def forward(self, f: torch.Tensor, load: Optional[torch.Tensor] = None, layout: str = "sample") -> torch.Tensor:
+    def forward(self, f: torch.Tensor, load: Optional[torch.Tensor] = None, layout: str = "sample",
+                dirichlet: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Solve for nodal u.  f: (n,), (n,1) or (B,n); returns float64 (n,) or (B,n)
         on f's device (reference solver.py:49-67 returns CPU float64).
         load (ours): (n,) or (B,n) nodal load added to the assembled load vector F on the free rows (differentiable) --
         the M_L u_prev / dt term of a time step, point sources, a Neumann flux integrated by the caller.
         layout (ours): "sample" = the shapes above; "node" = f, load and u are (n, B), the batch INNERMOST -- the layout
         the kernels work in, so a caller that keeps its batch that way (an optimisation loop over kappa, say) pays no
-        transposing pass in or out (3 x 16 B per node and sample of a fwd + adjoint step); 2D meshes, same results."""
+        transposing pass in or out (3 x 16 B per node and sample of a fwd + adjoint step); 2D meshes, same results.
+        dirichlet (ours): the Dirichlet values of this call in ascending node-id order (`mesh.dirichlet_index()`),
+        (n_D,) for the batch or (B, n_D) per sample -- (n_D,) or (n_D, B) with layout="node"; batch rules of `load`.
+        The values of `mesh.dirichlet_nodes` are then not used, only its keys; the solve plan is the same, and the
+        values may require grad (a shared (n_D,) tensor receives the sum over the batch).  See diffhe.dirichlet."""
         if self.mesh.dim not in self._dims:
             raise NotImplementedError("Only 1D and 2D supported")       # reference solver.py:67
         if layout not in ("sample", "node"):
@@ -1362,9 +1445,15 @@ class DifferentiableFESolver(nn.Module):
             if f.dim() != 2 or f.shape[0] != n or (load is not None and tuple(load.shape) != tuple(f.shape)):
                 raise ValueError(f"layout='node': f (and load) must be (n, B) with n={n}, got {tuple(f.shape)}")
             if self.mesh.dim == 1:     # the 1D scan works sample-major: transposing views in and out
+                if dirichlet is not None:
+                    g64 = self._dirichlet64(dirichlet, f.shape[1], True)
+                    return self.forward(f.t(), None if load is None else load.t(),
+                                        dirichlet=g64 if g64.dim() == 1 else g64.t()).t()
                 return self.forward(f.t(), None if load is None else load.t()).t()
             f64 = f.to(torch.float64)
             load64 = f64.new_empty(0) if load is None else load.to(torch.float64)
+            if dirichlet is not None:
+                return self._solve_bc_op(f64, load64, self._dirichlet64(dirichlet, f.shape[1], True), True)
             return self._solve_op(f64, load64, True)
         f64 = f.to(torch.float64)
         if f64.dim() == 2 and f64.shape == (n, 1):
@@ -1381,13 +1470,46 @@ class DifferentiableFESolver(nn.Module):
                 raise ValueError(f"load must be (n,) or (B,n) with n={n}, got {tuple(load.shape)}")
             if load64.dim() == 2 and f64.dim() == 1:
                 f64 = f64.reshape(1, n).expand(load64.shape[0], n)
+        if dirichlet is not None:
+            g64 = self._dirichlet64(dirichlet, f64.shape[0] if f64.dim() == 2 else None, False)
+            if g64.dim() == 2 and f64.dim() == 1:           # a (B, n_D) G implies the batch, like load
+                f64 = f64.reshape(1, n).expand(g64.shape[0], n)
+            return self._solve_bc_op(f64, load64, g64, False)
         return self._solve_op(f64, load64, False)
+
+    def _dirichlet64(self, dirichlet, B: Optional[int], node_major: bool) -> torch.Tensor:
+        """`dirichlet=` checked and as float64: (n_D,), or (B, n_D) / layout="node" (n_D, B) with B the batch of f (None:
+        f has none, any B)."""
+        nd = len(self.mesh.dirichlet_nodes)
+        g = dirichlet if isinstance(dirichlet, torch.Tensor) else torch.as_tensor(dirichlet)
+        if g.is_complex():
+            raise ValueError(f"dirichlet must be a real tensor, got {g.dtype}")
+        if g.dim() == 1:
+            ok = g.shape[0] == nd
+        elif g.dim() == 2:
+            gb, gn = (g.shape[1], g.shape[0]) if node_major else (g.shape[0], g.shape[1])
+            ok = gn == nd and (B is None or gb == B)
+        else:
+            ok = False
+        if not ok:
+            want = f"({nd},) or " + (f"({nd}, B)" if node_major else f"(B, {nd})") + (f" with B={B}" if B else "")
+            raise ValueError(f"dirichlet must be {want} (one value per Dirichlet node), got {tuple(g.shape)}")
+        return g.to(torch.float64)
 
     def _solve_op(self, f64: torch.Tensor, load64: torch.Tensor, node_major: bool) -> torch.Tensor:
         """u = the diffhe::fe_solve op on checked float64 inputs (load64 empty: no extra load)."""
         _SOLVERS[id(self)] = self
         save = torch.is_grad_enabled() and (self._kappa.requires_grad or f64.requires_grad or load64.requires_grad)
         u, _token = torch.ops.diffhe.fe_solve(self._kappa, f64, load64, id(self), save, node_major)
+        return u
+
+    def _solve_bc_op(self, f64: torch.Tensor, load64: torch.Tensor, g64: torch.Tensor, node_major: bool) -> torch.Tensor:
+        """u = the diffhe::fe_solve_bc op (per-call Dirichlet data g64) on checked float64 inputs."""
+        from . import dirichlet as _dirichlet  # noqa: F401  registers diffhe::fe_solve_bc
+        _SOLVERS[id(self)] = self
+        save = torch.is_grad_enabled() and (self._kappa.requires_grad or f64.requires_grad or load64.requires_grad
+                                            or g64.requires_grad)
+        u, _token = torch.ops.diffhe.fe_solve_bc(self._kappa, f64, load64, g64, id(self), save, node_major)
         return u
 
     # reference-private names kept as aliases (SURVEY 8(b)); both run the HIP path

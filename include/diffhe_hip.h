@@ -437,6 +437,36 @@ int diffhe_p1_shape_grad(const double* coords, const int* elems, int dim, int n,
                          long long kse, long long ksb, const double* f, long long fsn, long long fsb, double c,
                          const int* inc_ptr, const int* inc, double* work, double* grad, void* stream);
 
+/* Per-sample Dirichlet data G_b (added entries of ABI v8; diffhe `dirichlet=`): the path kernels solve with HOMOGENEOUS Dirichlet data
+ * and these four add what G_b changes, on the boundary band only (csrc/bc.hip).  K_b[i, j] = sum_{e ni i, j}
+ * kappa[e*kse + b*ksb] k0[(p*npe + q)*m + e] is the UNREDUCED stiffness of sample b (kappa NULL: unit kappa); elems (npe, m)
+ * and k0 (npe*npe, m) as the element kernels take them; d_slot (n): slot of a Dirichlet node in the ascending list of
+ * Dirichlet nodes, -1 on free nodes.  G_b[j] (slot j) at G[j*gsj + b*gsb] (gsb = 0: one G for the batch).  Incidence
+ * lists: per row, the codes e*npe + p of its (element, local node) pairs in a fixed order.  No atomics: bitwise
+ * reproducible.  Only samples b < B are touched.
+ * lift:    rhs[rows[r]*rsn + b*rsb] -= sum_{(e, p) of row r} kappa_eb sum_{q: Dirichlet} k0_e[p, q] G_b[slot(q)]
+ *          (rows: the free nodes with a Dirichlet neighbour; row_inc: their pairs in elements that touch D).
+ * grad:    out[j*osj + b*osb] = gbar[d_idx[j]*gsn + b*gsb] - (K_b lam_b)_{d_idx[j]}   (gbar may be NULL: 0), with lam
+ *          (0 on Dirichlet nodes; only its free entries are read) at lam[i*lsn + b*lsb] and d_inc every pair of each
+ *          Dirichlet node; dots (n_d, B) or NULL: dots[j*B + b] = G_b[j] (K_1 lam_b)_{d_idx[j]} (unit kappa).
+ * scatter: u[d_idx[j]*usn + b*usb] = G_b[j].
+ * grad_kappa: dk[e*dse + b*dsb] -= sum_{p free, q Dirichlet} lam_b[p] k0_e[p, q] G_b[slot(q)] on the elements band_elems
+ *          that touch a Dirichlet node; shared != 0: dk[e*dse] -= the same summed over b < B. */
+int diffhe_bc_lift(const int* elems, int npe, int m, const double* k0, const double* kappa, long long kse,
+                   long long ksb, const int* d_slot, const double* G, long long gsj, long long gsb, const int* rows,
+                   const int* row_ptr, const int* row_inc, int n_rows, double* rhs, long long rsn, long long rsb, int B,
+                   void* stream);
+int diffhe_bc_grad(const int* elems, int npe, int m, const double* k0, const double* kappa, long long kse,
+                   long long ksb, const int* d_slot, const int* d_idx, const int* d_ptr, const int* d_inc, int n_d,
+                   const double* lam, long long lsn, long long lsb, const double* gbar, long long gsn, long long gsb,
+                   double* out, long long osj, long long osb, const double* G, long long Gsj, long long Gsb,
+                   double* dots, int B, void* stream);
+int diffhe_bc_scatter(const int* d_idx, int n_d, const double* G, long long gsj, long long gsb, double* u,
+                      long long usn, long long usb, int B, void* stream);
+int diffhe_bc_grad_kappa(const int* elems, int npe, int m, const double* k0, const int* d_slot, const int* band_elems,
+                         int n_be, const double* lam, long long lsn, long long lsb, const double* G, long long gsj,
+                         long long gsb, double* dk, long long dse, long long dsb, int shared, int B, void* stream);
+
 /* Layout changes between the API's (B, n) and the solver's (n, Bp).
  * to_node_major: dst[i*Bp + b] = src[b*ld + i] (b < B), 0 for padding samples and
  *   where zero_mask[i] != 0 (zero_mask may be NULL; src row stride ld = 0 broadcasts).
