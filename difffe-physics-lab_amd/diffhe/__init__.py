@@ -7,11 +7,10 @@ Extras that have no reference counterpart live in submodules only
 (`diffhe.distributed`: batch sharding over ranks; `diffhe.heat`: time stepping of the heat equation, the
 reference's roadmap item; `diffhe.tet3d`: `DifferentiableFESolver3D`, solves on 3D tetrahedral meshes such as
 `FEMesh.box`; `diffhe.shape`: `ShapeDifferentiableFESolver`, gradients with respect to the node coordinates, also
-exported here; `diffhe.dirichlet`: the op behind `forward(..., dirichlet=)`, per-sample Dirichlet values with
+exported here; `diffhe.dirichlet`: the adjoint step behind `forward(..., dirichlet=)`, per-sample Dirichlet values with
 gradients; `diffhe._hip`: the ctypes binding).
 """
 from . import loss as _loss, mesh as _mesh, neural as _neural, shape as _shape, solver as _solver
-from . import dirichlet as _dirichlet  # noqa: F401  registers diffhe::fe_solve_bc (forward(..., dirichlet=))
 
 FEMesh = _mesh.FEMesh
 DifferentiableFESolver = _solver.DifferentiableFESolver

@@ -627,9 +627,13 @@ class _Call:
     # per-call Dirichlet data (`dirichlet=`): (device values, stride per Dirichlet node, stride per sample), G_b[j] at
     # j * sj + b * sb (sb = 0: one G for the batch); None: the mesh's.  Boundary-sized: the adjoint state keeps it
     bc: Optional[tuple] = None
+    # kappa and f as the band kernels (a call with `dirichlet=`) and the node-gradient kernel (`shape`) read them:
+    # (device view of the op's input, stride per element / node, stride per sample).  Views, kept with the state too
+    kappa_s: Optional[tuple] = None
+    f_s: Optional[tuple] = None
 
     @classmethod
-    def of(cls, solver, plan: SolvePlan, kappa, f, load, node_major, dirichlet=None) -> "_Call":
+    def of(cls, solver, plan: SolvePlan, kappa, f, load, node_major, dirichlet=None, shape=False) -> "_Call":
         if load is not None and load.numel() == 0:
             load = None
         batched, n, out_device = f.dim() == 2, plan.n, f.device
@@ -640,6 +644,9 @@ class _Call:
             load = load.t() if load is not None else None
         mode, B, kappa_em = _kappa_layout(kappa, plan.m, f.shape[0] if batched else None, node_major)
         f_dev = f.detach().to(plan.device, torch.float64)
+        f_s = None
+        if shape:       # one forcing for the batch, or the (B, n) view through its strides
+            f_s = (f_dev.contiguous(), 1, 0) if f_dev.dim() == 1 else (f_dev, f_dev.stride(1), f_dev.stride(0))
         f_dev = f_dev if node_major else f_dev.contiguous()      # node-major: a transposed view of contiguous (n, B) data
         load_dev = None
         if load is not None:      # extra nodal load, added to the assembled F on the free rows
@@ -657,8 +664,11 @@ class _Call:
             else:
                 raise ValueError(f"dirichlet must be ({plan.n_bc},) or "
                                  f"{(plan.n_bc, B) if node_major else (B, plan.n_bc)}, got {tuple(dirichlet.shape)}")
+        kappa_s = None
+        if shape or bc is not None:
+            kappa_s = _kappa_strided(kappa, mode, kappa_em, B, plan.m, plan.device)
         return cls(B, mode, kappa_em, batched, node_major, out_device, kappa.shape, kappa.device,
-                   load is not None and load.dim() == 2, float(solver.reaction), kappa, f_dev, load_dev, bc)
+                   load is not None and load.dim() == 2, float(solver.reaction), kappa, f_dev, load_dev, bc, kappa_s, f_s)
 
     def facts(self) -> "_Call":
         return replace(self, kappa=None, f_dev=None, load_dev=None)
@@ -719,7 +729,6 @@ class _PathSolve:
     side or assembly temporary -- and this object is the adjoint state the custom ops hold until the end of backward.
     adjoint(g, need_k, need_f, need_load) -> (lambda in the path's layout, per-sample dL/dkappa sums, per-element
     dL/dkappa as `_kappa_grad` takes them, dL/df and dL/dload per sample in the caller's layout)."""
-    shape_kappa = shape_f = None    # set by diffhe.shape: kappa and f as the node-gradient kernel reads them
 
     def __init__(self, solver, plan: SolvePlan, call: _Call, tol: float, mg: dict, amg: dict):
         self.solver, self.plan, self.call, self.mg, self.amg = solver, plan, call.facts(), mg, amg
@@ -735,13 +744,13 @@ class _ChainSolve(_PathSolve):
     def forward(self, call: _Call, info: SolveInfo) -> torch.Tensor:
         plan, L, B, n = self.plan, self.eng.L, call.B, self.plan.n
         f_dev, batched = call.f_dev, call.batched
-        self.kdev, self.kse, self.ksb = _kappa_strided(call.kappa, call.mode, False, B, plan.m, plan.device)
+        self.kdev, self.kse, self.ksb = call.kappa_s or _kappa_strided(call.kappa, call.mode, False, B, plan.m,
+                                                                       plan.device)
         load_dev = call.load_dev
         if call.bc is not None:
             # per-call Dirichlet data: the lift -K_b[F, D] G_b enters as an extra load, the scan sees homogeneous data
-            self.bc_kappa = (self.kdev, self.kse, self.ksb)
             lift = torch.zeros((B, n), dtype=torch.float64, device=plan.device)
-            self.eng.bc_lift(self.bc_kappa, call.bc, lift, 1, n, B)
+            self.eng.bc_lift(call.kappa_s, call.bc, lift, 1, n, B)
             load_dev = lift if load_dev is None else load_dev + lift
         if load_dev is not None:
             # the 1D load map of solver.py:95-96 is diagonal (h/2 from each side): an extra load is a change of forcing
@@ -805,8 +814,7 @@ class _NodeMajorSolve(_PathSolve):
         if call.load_dev is not None:
             rhs += eng.to_node_major(call.load_dev, B, Bp, plan.n, zero_mask=plan.is_bc)
         if call.bc is not None:     # per-call Dirichlet data: - K_b[F, D] G_b on the boundary band
-            self.bc_kappa = _kappa_strided(call.kappa, call.mode, call.kappa_em, B, plan.m, plan.device)
-            eng.bc_lift(self.bc_kappa, call.bc, rhs, Bp, 1, B)
+            eng.bc_lift(call.kappa_s, call.bc, rhs, Bp, 1, B)
         return rhs
 
     def _adjoint_rhs(self, g: torch.Tensor) -> torch.Tensor:
@@ -1026,13 +1034,14 @@ class _EllSolve(_NodeMajorSolve):
         return eng.cg(self.vals, rhs, self.Bp, self.Bv)
 
 
-def _solve_forward(solver, kappa, f, load=None, node_major=False, dirichlet=None):
+def _solve_forward(solver, kappa, f, load=None, node_major=False, dirichlet=None, shape=False):
     """u = (K(kappa) + c M_L)^{-1} (F(f) + load) with Dirichlet elimination (c = solver.reaction, 0 for the reference's
     problem).  Returns (u, state): the path object that keeps what the explicit adjoint needs.  node_major (2D paths):
     f, load and u are (n, B), the solver's own layout: no layout change (with B a valid padded batch and zero Dirichlet
-    data, u IS the solver's iterate).  dirichlet: per-call Dirichlet values (diffhe.dirichlet), None: the mesh's."""
+    data, u IS the solver's iterate).  dirichlet: per-call Dirichlet values (diffhe.dirichlet), None: the mesh's.
+    shape: the state also keeps what the node-gradient kernel reads (diffhe.shape)."""
     plan: SolvePlan = solver._plan()
-    call = _Call.of(solver, plan, kappa, f, load, node_major, dirichlet)
+    call = _Call.of(solver, plan, kappa, f, load, node_major, dirichlet, shape)
     path = _select_path(plan, solver, call.reaction)
     tol, mg, amg = _call_options(chain=plan.is_chain, lattice=path is _LatticeSolve, closed_boundary=plan.closed_boundary,
                                  n=plan.n, mode=call.mode, tol_user=solver._tol_user, mg_user=solver._mg_user,
@@ -1072,23 +1081,30 @@ def _from_node_major(eng, x, B, Bp, n, node_major, bc=None):
     return xo + p.g.unsqueeze(1) if p.has_dirichlet_data else xo   # zero Dirichlet data: u IS x, nothing is copied
 
 
-def _solve_backward(state: _PathSolve, gbar, need_k, need_f, need_load=False):
+def _solve_backward(state: _PathSolve, gbar, need_k, need_f, need_load=False, need_g=False, need_x=False):
     """Explicit adjoint: lambda = K_free^{-1} gbar_free with the saved operators,
-    dL/dkappa = -lambda^T k0 u, dL/df = M^T lambda, dL/dload = lambda -- the path's adjoint, then the gradients shaped,
-    summed over the batch where the input had none, and placed like the inputs.
-    Returns (grad_kappa | None, grad_f | None, grad_load | None, lambda in the path's layout, for state.shape_fields)."""
+    dL/dkappa = -lambda^T k0 u, dL/df = M^T lambda, dL/dload = lambda -- the path's adjoint ONCE, then what the same
+    lambda gives for a call with `dirichlet=` (diffhe.dirichlet: dL/dG and the G part of dL/dkappa) and for the node
+    coordinates (diffhe.shape), then the gradients shaped, summed over the batch where the input had none, and placed
+    like the inputs (dL/dX stays (n, dim) fp64 on the plan's device: the mesh's nodes may live elsewhere).
+    Returns (grad_kappa, grad_f, grad_load, grad_G, grad_X), None for each one not asked for."""
     call, plan = state.call, state.plan
     g = gbar.detach().to(plan.device, torch.float64)
     g = g.reshape(plan.n, call.B) if call.node_major else g.reshape(call.B, plan.n).contiguous()
     lam, dk_sample, dk_elem, df, dload = state.adjoint(g, need_k, need_f, need_load)
-    grad_k = grad_f = grad_load = None
+    dg = None
+    if call.bc is not None:
+        dk_sample, dg = _dirichlet.band_grads(state, g, lam, dk_sample, dk_elem, need_k, need_g)
+    grad_k = grad_f = grad_load = grad_g = None
     if need_k:
         grad_k = _kappa_grad(call.mode, call.kappa_shape, dk_sample, dk_elem).to(call.kappa_device)
     if need_f:
         grad_f = (df if call.batched else df.sum(dim=0)).to(call.out_device)
     if need_load:
         grad_load = (dload if call.load_batched else dload.sum(dim=1 if call.node_major else 0)).to(call.out_device)
-    return grad_k, grad_f, grad_load, lam
+    if need_g:      # a (n_D,) G shared by the batch receives the sum over the samples
+        grad_g = dg if call.bc[0].dim() == 2 else dg.sum(dim=1 if call.node_major else 0)
+    return grad_k, grad_f, grad_load, grad_g, _shape._node_grad(state, lam) if need_x else None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1119,15 +1135,16 @@ def _state_of(token: torch.Tensor):
     return state
 
 
-def _save_for_adjoint(ctx, inputs, output, handle, node_major):
-    """setup_context of the solve ops: save (token, *inputs) and u when node-major (it may BE the saved iterate: autograd
-    then refuses a backward after an in-place edit), and tie the adjoint state to them."""
+def _fe_setup_context(ctx, inputs, output):
+    """Save (token, kappa, f, load, dirichlet | None, nodes | None) and u when node-major (it may BE the saved iterate:
+    autograd then refuses a backward after an in-place edit), and tie the adjoint state to them."""
+    kappa, f, load, handle, _save, node_major, dirichlet, nodes, _version = inputs
     real = not isinstance(output[1], torch._subclasses.FakeTensor)
     # A sentinel among the saved tensors dies with them at the end of a backward that does not retain the graph and
     # takes the adjoint state along, BEFORE the caller lets go of u: a state that overlaps the next step's forward
     # solve costs new device allocations (DESIGN section 4, "Lifetime of the adjoint state").
     sentinel = (torch.empty(0),) if real else ()
-    ctx.save_for_backward(output[1], *inputs, *((output[0],) if node_major else ()), *sentinel)
+    ctx.save_for_backward(output[1], kappa, f, load, dirichlet, nodes, *((output[0],) if node_major else ()), *sentinel)
     ctx.handle, ctx.node_major = handle, bool(node_major)
     if real:
         weakref.finalize(sentinel[0], _STATES.pop, int(output[1]), None)
@@ -1135,12 +1152,19 @@ def _save_for_adjoint(ctx, inputs, output, handle, node_major):
 
 
 @torch.library.custom_op("diffhe::fe_solve", mutates_args=())
-def fe_solve(kappa: torch.Tensor, f: torch.Tensor, load: torch.Tensor, handle: int,
-             save: bool, node_major: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+def fe_solve(kappa: torch.Tensor, f: torch.Tensor, load: torch.Tensor, handle: int, save: bool, node_major: bool = False,
+             dirichlet: Optional[torch.Tensor] = None, nodes: Optional[torch.Tensor] = None,
+             nodes_version: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """(u, token) = solve with the solver registered under `handle`; `token` names the saved
     adjoint state (0 when `save` is false).  `load`: extra nodal load vector, empty for none.
-    node_major: f, load and u are (n, B) instead of (B, n)."""
-    u, state = _solve_forward(_SOLVERS[handle], kappa, f, load, node_major)
+    node_major: f, load and u are (n, B) instead of (B, n).
+    dirichlet: the Dirichlet values of this call, (n_D,), (B, n_D), or (n_D, B) when node_major; None: the mesh's.
+    nodes: the node coordinates as a differentiable input -- the solver's mesh.nodes at version `nodes_version` (the
+    tensor the plan is built from); None: no node gradient."""
+    solver = _SOLVERS[handle]
+    if nodes is not None:
+        _shape._check_nodes(solver.mesh, nodes, nodes_version)
+    u, state = _solve_forward(solver, kappa, f, load, node_major, dirichlet, nodes is not None)
     token = next(_TOKENS) if save else 0
     if save:
         _STATES[token] = state     # freed with the autograd graph of this solve (_StateGuard): no cap on pending solves
@@ -1148,7 +1172,7 @@ def fe_solve(kappa: torch.Tensor, f: torch.Tensor, load: torch.Tensor, handle: i
 
 
 @fe_solve.register_fake
-def _fe_solve_fake(kappa, f, load, handle, save, node_major=False):
+def _fe_solve_fake(kappa, f, load, handle, save, node_major=False, dirichlet=None, nodes=None, nodes_version=0):
     solver = _SOLVERS[handle]
     n, m = solver.mesh.n_nodes, solver.mesh.n_elements
     if node_major:
@@ -1158,27 +1182,25 @@ def _fe_solve_fake(kappa, f, load, handle, save, node_major=False):
     return f.new_empty(shape, dtype=torch.float64), torch.empty((), dtype=torch.int64)
 
 
+_Grads = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]
+
+
 @torch.library.custom_op("diffhe::fe_solve_backward", mutates_args=())
 def fe_solve_backward(gbar: torch.Tensor, token: torch.Tensor, need_k: bool, need_f: bool, need_load: bool,
-                      kappa_like: torch.Tensor, f_like: torch.Tensor,
-                      load_like: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """(dL/dkappa, dL/df, dL/dload) for the forward call named by `token`; unused gradients come back empty."""
-    gk, gf, gl = _solve_backward(_state_of(token), gbar, need_k, need_f, need_load)[:3]
-    return (gk if gk is not None else kappa_like.new_empty(0), gf if gf is not None else f_like.new_empty(0),
-            gl.to(load_like.dtype) if gl is not None else load_like.new_empty(0))
+                      need_g: bool, need_x: bool, kappa_like: torch.Tensor, f_like: torch.Tensor, load_like: torch.Tensor,
+                      g_like: Optional[torch.Tensor] = None, nodes_like: Optional[torch.Tensor] = None) -> _Grads:
+    """(dL/dkappa, dL/df, dL/dload, dL/dG, dL/dX) of the forward call named by `token` from ONE adjoint solve, each with
+    the device and dtype of its `*_like`; unused gradients come back empty."""
+    likes = (kappa_like, f_like, load_like, g_like, nodes_like)
+    grads = _solve_backward(_state_of(token), gbar, need_k, need_f, need_load, need_g, need_x)
+    return tuple(gbar.new_empty(0) if g is None else g.to(like.device, like.dtype) for g, like in zip(grads, likes))
 
 
 @fe_solve_backward.register_fake
-def _fe_solve_backward_fake(gbar, token, need_k, need_f, need_load, kappa_like, f_like, load_like):
-    return (torch.empty_like(kappa_like) if need_k else kappa_like.new_empty(0),
-            torch.empty_like(f_like) if need_f else f_like.new_empty(0),
-            torch.empty_like(load_like) if need_load else load_like.new_empty(0))
-
-
-def _fe_setup_context(ctx, inputs, output):
-    kappa, f, load, handle, _, node_major = inputs
-    _save_for_adjoint(ctx, (kappa, f, load), output, handle, node_major)
-
+def _fe_solve_backward_fake(gbar, token, need_k, need_f, need_load, need_g, need_x, kappa_like, f_like, load_like,
+                            g_like=None, nodes_like=None):
+    needs, likes = (need_k, need_f, need_load, need_g, need_x), (kappa_like, f_like, load_like, g_like, nodes_like)
+    return tuple(torch.empty_like(like) if need else gbar.new_empty(0) for need, like in zip(needs, likes))
 
 
 def _element_forms(plan: SolvePlan):
@@ -1225,7 +1247,7 @@ def _element_forms(plan: SolvePlan):
     return el, k0, m0
 
 
-def _second_order_backward(ctx, grad_u, dirichlet=None):
+def _second_order_backward(ctx, grad_u, need_k, need_f, need_load):
     """The adjoint written with differentiable pieces, for backward(create_graph=True) / Hessian-vector products:
 
         lambda = A(kappa)^-1 gbar          a solve of the SAME solver class on the mesh with homogeneous Dirichlet data
@@ -1240,9 +1262,8 @@ def _second_order_backward(ctx, grad_u, dirichlet=None):
     solver = _SOLVERS.get(ctx.handle)
     if solver is None:
         raise RuntimeError("diffhe: the solver of this solve is gone; second-order backward needs it alive")
-    _token, kappa, f, load = ctx.saved_tensors[:4]
+    _token, kappa, f, load, dirichlet = ctx.saved_tensors[:5]
     node_major = ctx.node_major
-    need_k, need_f, need_load = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
     plan = solver._plan()
     el, k0, m0 = _element_forms(plan)
     m, n = plan.m, plan.n
@@ -1250,10 +1271,9 @@ def _second_order_backward(ctx, grad_u, dirichlet=None):
     _SOLVERS[id(twin)] = twin
     g = grad_u.to(torch.float64)
     lam, _ = torch.ops.diffhe.fe_solve(kappa, torch.zeros_like(g), g, id(twin), True, node_major)
-    if dirichlet is None:
-        u, _ = torch.ops.diffhe.fe_solve(kappa, f, load, ctx.handle, True, node_major)
-    else:       # per-call Dirichlet data, not differentiated here (diffhe.dirichlet refuses second order through it)
-        u, _ = torch.ops.diffhe.fe_solve_bc(kappa, f, load, dirichlet.detach(), ctx.handle, True, node_major)
+    # per-call Dirichlet data is not differentiated here (`_fe_backward` refuses second order through it)
+    u, _ = torch.ops.diffhe.fe_solve(kappa, f, load, ctx.handle, True, node_major,
+                                     None if dirichlet is None else dirichlet.detach())
     # (B, n) views for the element-local maps
     lam_b = (lam.t() if node_major else lam).reshape(-1, n)
     u_b = (u.t() if node_major else u).reshape(-1, n)
@@ -1269,19 +1289,46 @@ def _second_order_backward(ctx, grad_u, dirichlet=None):
         gf = (gf_b.t() if node_major else gf_b).reshape(f.shape) if f.dim() == lam.dim() else gf_b.sum(0).reshape(f.shape)
     if need_load:
         gl = lam.reshape(load.shape) if load.dim() == lam.dim() else lam_b.sum(0).reshape(load.shape)
-    return gk, gf, gl, None, None, None
+    return gk, gf, gl
+
+
+_GRAD_ARGS = (0, 1, 2, 6, 7)      # kappa, f, load, dirichlet, nodes among the arguments of diffhe::fe_solve
+
+
+def _input_grads(needs_input_grad, grads=None):
+    """`needs_input_grad` has one entry per argument that REACHED the op -- the dispatcher drops trailing arguments equal
+    to their defaults, so a call without dirichlet / nodes sees 5 or 6 of the schema's 9 -- and autograd wants as many
+    values back.  Without `grads`: (need_k, need_f, need_load, need_g, need_x), False for what was not passed; with
+    them: the five gradients placed among that many values, None where not needed."""
+    n = len(needs_input_grad)
+    needs = tuple(i < n and needs_input_grad[i] for i in _GRAD_ARGS)
+    if grads is None:
+        return needs
+    out = [None] * n
+    for i, need, g in zip(_GRAD_ARGS, needs, grads):
+        if need:
+            out[i] = g
+    return tuple(out)
 
 
 def _fe_backward(ctx, grad_u, _grad_token):
+    need_k, need_f, need_load, need_g, need_x = _input_grads(ctx.needs_input_grad)
     if torch.is_grad_enabled():
         # backward(create_graph=True) / autograd.grad(..., create_graph=True): the caller wants a gradient it can
         # differentiate again.  The explicit adjoint below is not recorded by autograd (what it returns would carry no
         # graph, a Hessian-vector product through it would silently be zero): take the differentiable restatement.
-        return _second_order_backward(ctx, grad_u)
-    token, kappa, f, load = ctx.saved_tensors[:4]
-    need_k, need_f, need_load = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-    gk, gf, gl = torch.ops.diffhe.fe_solve_backward(grad_u, token, need_k, need_f, need_load, kappa, f, load)
-    return (gk if need_k else None), (gf if need_f else None), (gl if need_load else None), None, None, None
+        if need_x:
+            raise NotImplementedError("diffhe: second-order derivatives through the node coordinates are not "
+                                      "implemented (backward with create_graph=True while mesh.nodes requires grad)")
+        if need_g:
+            raise NotImplementedError("diffhe: second-order derivatives through the Dirichlet values are not implemented "
+                                      "(backward with create_graph=True while dirichlet= requires grad)")
+        grads = _second_order_backward(ctx, grad_u, need_k, need_f, need_load)
+    else:
+        token, kappa, f, load, dirichlet, nodes = ctx.saved_tensors[:6]
+        grads = torch.ops.diffhe.fe_solve_backward(grad_u, token, need_k, need_f, need_load, need_g, need_x, kappa, f,
+                                                   load, dirichlet, nodes)
+    return _input_grads(ctx.needs_input_grad, grads)
 
 
 torch.library.register_autograd("diffhe::fe_solve", _fe_backward, setup_context=_fe_setup_context)
@@ -1444,17 +1491,13 @@ class DifferentiableFESolver(nn.Module):
         if layout == "node":
             if f.dim() != 2 or f.shape[0] != n or (load is not None and tuple(load.shape) != tuple(f.shape)):
                 raise ValueError(f"layout='node': f (and load) must be (n, B) with n={n}, got {tuple(f.shape)}")
+            g64 = None if dirichlet is None else self._dirichlet64(dirichlet, f.shape[1], True)
             if self.mesh.dim == 1:     # the 1D scan works sample-major: transposing views in and out
-                if dirichlet is not None:
-                    g64 = self._dirichlet64(dirichlet, f.shape[1], True)
-                    return self.forward(f.t(), None if load is None else load.t(),
-                                        dirichlet=g64 if g64.dim() == 1 else g64.t()).t()
-                return self.forward(f.t(), None if load is None else load.t()).t()
+                return self.forward(f.t(), None if load is None else load.t(),
+                                    dirichlet=g64 if g64 is None or g64.dim() == 1 else g64.t()).t()
             f64 = f.to(torch.float64)
             load64 = f64.new_empty(0) if load is None else load.to(torch.float64)
-            if dirichlet is not None:
-                return self._solve_bc_op(f64, load64, self._dirichlet64(dirichlet, f.shape[1], True), True)
-            return self._solve_op(f64, load64, True)
+            return self._solve_op(f64, load64, g64, True)
         f64 = f.to(torch.float64)
         if f64.dim() == 2 and f64.shape == (n, 1):
             f64 = f64.reshape(n)                                          # (n,1) works in the reference too
@@ -1470,12 +1513,10 @@ class DifferentiableFESolver(nn.Module):
                 raise ValueError(f"load must be (n,) or (B,n) with n={n}, got {tuple(load.shape)}")
             if load64.dim() == 2 and f64.dim() == 1:
                 f64 = f64.reshape(1, n).expand(load64.shape[0], n)
-        if dirichlet is not None:
-            g64 = self._dirichlet64(dirichlet, f64.shape[0] if f64.dim() == 2 else None, False)
-            if g64.dim() == 2 and f64.dim() == 1:           # a (B, n_D) G implies the batch, like load
-                f64 = f64.reshape(1, n).expand(g64.shape[0], n)
-            return self._solve_bc_op(f64, load64, g64, False)
-        return self._solve_op(f64, load64, False)
+        g64 = None if dirichlet is None else self._dirichlet64(dirichlet, f64.shape[0] if f64.dim() == 2 else None, False)
+        if g64 is not None and g64.dim() == 2 and f64.dim() == 1:           # a (B, n_D) G implies the batch, like load
+            f64 = f64.reshape(1, n).expand(g64.shape[0], n)
+        return self._solve_op(f64, load64, g64, False)
 
     def _dirichlet64(self, dirichlet, B: Optional[int], node_major: bool) -> torch.Tensor:
         """`dirichlet=` checked and as float64: (n_D,), or (B, n_D) / layout="node" (n_D, B) with B the batch of f (None:
@@ -1496,20 +1537,13 @@ class DifferentiableFESolver(nn.Module):
             raise ValueError(f"dirichlet must be {want} (one value per Dirichlet node), got {tuple(g.shape)}")
         return g.to(torch.float64)
 
-    def _solve_op(self, f64: torch.Tensor, load64: torch.Tensor, node_major: bool) -> torch.Tensor:
-        """u = the diffhe::fe_solve op on checked float64 inputs (load64 empty: no extra load)."""
-        _SOLVERS[id(self)] = self
-        save = torch.is_grad_enabled() and (self._kappa.requires_grad or f64.requires_grad or load64.requires_grad)
-        u, _token = torch.ops.diffhe.fe_solve(self._kappa, f64, load64, id(self), save, node_major)
-        return u
-
-    def _solve_bc_op(self, f64: torch.Tensor, load64: torch.Tensor, g64: torch.Tensor, node_major: bool) -> torch.Tensor:
-        """u = the diffhe::fe_solve_bc op (per-call Dirichlet data g64) on checked float64 inputs."""
-        from . import dirichlet as _dirichlet  # noqa: F401  registers diffhe::fe_solve_bc
+    def _solve_op(self, f64: torch.Tensor, load64: torch.Tensor, g64: Optional[torch.Tensor],
+                  node_major: bool) -> torch.Tensor:
+        """u = the diffhe::fe_solve op on checked float64 inputs (load64 empty: no extra load; g64: `dirichlet=` or None)."""
         _SOLVERS[id(self)] = self
         save = torch.is_grad_enabled() and (self._kappa.requires_grad or f64.requires_grad or load64.requires_grad
-                                            or g64.requires_grad)
-        u, _token = torch.ops.diffhe.fe_solve_bc(self._kappa, f64, load64, g64, id(self), save, node_major)
+                                            or (g64 is not None and g64.requires_grad))
+        u, _token = torch.ops.diffhe.fe_solve(self._kappa, f64, load64, id(self), save, node_major, g64)
         return u
 
     # reference-private names kept as aliases (SURVEY 8(b)); both run the HIP path
@@ -1518,3 +1552,8 @@ class DifferentiableFESolver(nn.Module):
 
     def _solve_2d(self, f: torch.Tensor) -> torch.Tensor:
         return self.forward(f)
+
+
+# The two steps of `_solve_backward` that live with their derivations (and `_check_nodes`).  Both modules import this one,
+# hence at the end; their functions are looked up at call time.
+from . import dirichlet as _dirichlet, shape as _shape  # noqa: E402

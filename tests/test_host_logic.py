@@ -350,10 +350,64 @@ def test_custom_ops_are_registered_with_shape_inference():
         assert u.shape == (6, 25)
         u, _ = torch.ops.diffhe.fe_solve(kb, f1, f1.new_empty(0), id(s), False)          # kappa batch, shared f
         assert u.shape == (6, 25)
-        gk, gf, gl = torch.ops.diffhe.fe_solve_backward(u, tok, True, False, False, kb, f1, f1.new_empty(0))
+        gk, gf, gl, dG, dX = torch.ops.diffhe.fe_solve_backward(u, tok, True, False, False, False, False, kb, f1,
+                                                                f1.new_empty(0))
         assert gk.shape == (6,) and gf.numel() == 0 and gl.numel() == 0
-        gk, gf, gl = torch.ops.diffhe.fe_solve_backward(u, tok, False, True, True, kb, f1, fb)   # load (B, n)
+        assert dG.numel() == 0 and dX.numel() == 0
+        gk, gf, gl, dG, dX = torch.ops.diffhe.fe_solve_backward(u, tok, False, True, True, False, False, kb, f1,
+                                                                fb)                              # load (B, n)
         assert gk.numel() == 0 and gf.shape == (25,) and gl.shape == (6, 25)
+        assert dG.numel() == 0 and dX.numel() == 0
+        # per-call Dirichlet values (B, n_D) and the node coordinates as inputs of the same two ops
+        nd = len(mesh.dirichlet_nodes)
+        G = torch.empty(6, nd, dtype=torch.float64)
+        u, tok = torch.ops.diffhe.fe_solve(kb, fb, fb.new_empty(0), id(s), True, False, G)
+        assert u.shape == (6, 25) and u.dtype == torch.float64
+        gk, gf, gl, dG, dX = torch.ops.diffhe.fe_solve_backward(u, tok, True, False, False, True, False, kb, fb,
+                                                                fb.new_empty(0), G)
+        assert gk.shape == (6,) and gf.numel() == 0 and gl.numel() == 0 and dG.shape == (6, nd) and dX.numel() == 0
+        X = torch.empty(25, 2, dtype=torch.float64)
+        u, tok = torch.ops.diffhe.fe_solve(kb, fb, fb.new_empty(0), id(s), True, False, nodes=X, nodes_version=0)
+        assert u.shape == (6, 25) and u.dtype == torch.float64
+        gk, gf, gl, dG, dX = torch.ops.diffhe.fe_solve_backward(u, tok, False, False, False, False, True, kb, fb,
+                                                                fb.new_empty(0), None, X)
+        assert gk.numel() == 0 and gf.numel() == 0 and gl.numel() == 0 and dG.numel() == 0 and dX.shape == (25, 2)
+
+
+def test_unified_op_gradients_without_trailing_arguments():
+    """Autograd sees only the arguments that reach the op: the dispatcher drops trailing arguments equal to their
+    defaults, so `needs_input_grad` has 5 to 9 entries for the nine-argument schema.  A direct caller who leaves out
+    `dirichlet` / `nodes` (or `node_major`) gets gradients, not an IndexError or a tuple-length error from autograd."""
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    from diffhe import solver as S
+    mesh = FEMesh.rectangle(4, 4)
+    s = DifferentiableFESolver(mesh)
+    S._SOLVERS[id(s)] = s
+    nd = len(mesh.dirichlet_nodes)
+    with FakeTensorMode():
+        def inputs():
+            return (torch.empty(6, dtype=torch.float64, requires_grad=True),
+                    torch.empty(6, 25, dtype=torch.float64, requires_grad=True),
+                    torch.empty(6, 25, dtype=torch.float64, requires_grad=True))
+        tails = {"5 arguments": (), "node_major at its default": (False,), "everything at its default": (False, None, None, 0),
+                 "dirichlet": (False, torch.empty(6, nd, dtype=torch.float64, requires_grad=True)),
+                 "nodes": (False, None, torch.empty(25, 2, dtype=torch.float64, requires_grad=True), 0)}
+        for name, tail in tails.items():
+            k, f, load = inputs()
+            u, _ = torch.ops.diffhe.fe_solve(k, f, load, id(s), True, *tail)
+            assert u.requires_grad, name
+            leaves = [k, f, load] + [t for t in tail if isinstance(t, torch.Tensor)]
+            grads = torch.autograd.grad(u.sum(), leaves)
+            assert [tuple(g.shape) for g in grads] == [tuple(t.shape) for t in leaves], name
+            k, f, load = inputs()                                     # and a subset: kappa alone
+            u, _ = torch.ops.diffhe.fe_solve(k, f.detach(), load.detach(), id(s), True, *tail)
+            assert torch.autograd.grad(u.sum(), k)[0].shape == (6,), name
+    # the helper itself: as many values back as arguments reached the op, in their places
+    assert S._input_grads((True, False, True, False, False)) == (True, False, True, False, False)
+    assert S._input_grads((True, False, True, False, False), "abcde") == ("a", None, "c", None, None)
+    assert S._input_grads((False, True, False, False, False, False), "abcde") == (None, "b", None, None, None, None)
+    assert S._input_grads((True,) * 3 + (False,) * 3 + (True, False)) == (True, True, True, True, False)
+    assert S._input_grads((False,) * 6 + (True, True, False), "abcde") == (None,) * 6 + ("d", "e", None)
 
 
 def test_coarsening_step_rules():

@@ -202,7 +202,7 @@ def test_nodes_version_mismatch_raises():
     solver_mod._SOLVERS[id(solver)] = solver
     f = torch.ones(mesh.n_nodes, dtype=T64)
     with pytest.raises(ValueError, match="modified in place"):
-        torch.ops.diffhe.fe_solve_shape(solver.kappa, f, f.new_empty(0), nodes, v, id(solver), True, False)
+        torch.ops.diffhe.fe_solve(solver.kappa, f, f.new_empty(0), id(solver), True, False, nodes=nodes, nodes_version=v)
 
 
 def test_plain_solver_classes_are_unchanged():
