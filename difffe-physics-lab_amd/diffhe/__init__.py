@@ -8,15 +8,18 @@ Extras that have no reference counterpart live in submodules only
 reference's roadmap item; `diffhe.tet3d`: `DifferentiableFESolver3D`, solves on 3D tetrahedral meshes such as
 `FEMesh.box`; `diffhe.shape`: `ShapeDifferentiableFESolver`, gradients with respect to the node coordinates, also
 exported here; `diffhe.dirichlet`: the adjoint step behind `forward(..., dirichlet=)`, per-sample Dirichlet values with
-gradients; `diffhe._hip`: the ctypes binding).
+gradients; `diffhe.aniso`: `AnisotropicFESolver`, solves with a conductivity tensor per element and its gradient, also
+exported here; `diffhe._hip`: the ctypes binding).
 """
-from . import loss as _loss, mesh as _mesh, neural as _neural, shape as _shape, solver as _solver
+from . import aniso as _aniso, loss as _loss, mesh as _mesh, neural as _neural, shape as _shape, solver as _solver
 
 FEMesh = _mesh.FEMesh
 DifferentiableFESolver = _solver.DifferentiableFESolver
 PhysicsLoss = _loss.PhysicsLoss
 NeuralPDE = _neural.NeuralPDE
 ShapeDifferentiableFESolver = _shape.ShapeDifferentiableFESolver
+AnisotropicFESolver = _aniso.AnisotropicFESolver
 
-__all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver")
+__all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
+           "AnisotropicFESolver")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

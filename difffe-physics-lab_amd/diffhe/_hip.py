@@ -77,6 +77,10 @@ SIGNATURES = {
     "diffhe_grad_kappa_blocks": (_I, [_I, _I]),
     "diffhe_p1_grad_kappa": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "diffhe_p1_grad_kappa_shared": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "diffhe_aniso_gradient_table": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "diffhe_aniso_assemble_rows": (_I, [_P, _P, _I, _P, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "diffhe_aniso_grad": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _L, _L, _P, _P, _P]),
+    "diffhe_aniso_grad_shared": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _L, _L, _P]),
     "diffhe_p1_shape_grad": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _D, _P, _P, _P,
                                   _P, _P]),
     "diffhe_bc_lift": (_I, [_P, _I, _I, _P, _P, _L, _L, _P, _P, _L, _L, _P, _P, _P, _I, _P, _L, _L, _I, _P]),

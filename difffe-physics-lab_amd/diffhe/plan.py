@@ -489,9 +489,13 @@ class LatticeLevel:
 class SolvePlan:
     """Device-resident metadata of one mesh (see module docstring)."""
 
-    def __init__(self, mesh, device: torch.device):
+    def __init__(self, mesh, device: torch.device, prune: bool = True):
         L = _hip.lib()
         self.device = device
+        # prune=False (tensor coefficients on tetrahedra, diffhe.aniso): the stiffness pattern keeps the couplings that
+        # are exact zeros for every SCALAR kappa -- a tensor fills them -- and with it the aggregation hierarchy and its
+        # Galerkin lists, which are built from the pattern the values are stored in
+        self.prune = bool(prune)
         self.dim = mesh.dim
         self.n = mesh.n_nodes
         self.m = mesh.n_elements
@@ -746,7 +750,7 @@ class SolvePlan:
         # keeps them exact on axis-aligned boxes) are left out of the STIFFNESS pattern -- zero for every finite kappa, so
         # the solution, the Dirichlet lift and the gradients are unchanged, and the sweeps gather 7 instead of 15 columns
         # per node on FEMesh.box.  DIFFHE_TET_PRUNE=0 keeps the full pattern (the A/B switch of tools/box3d_bench.py).
-        prune = self.dim == 3 and os.environ.get("DIFFHE_TET_PRUNE", "1") != "0"
+        prune = self.dim == 3 and self.prune and os.environ.get("DIFFHE_TET_PRUNE", "1") != "0"
         pat = build_ell_pattern(self._elements, self.n, zero=(tn == 0.0) if prune else None)
         self.W = pat["W"]
         self.cols = dev(pat["cols"])
@@ -783,6 +787,22 @@ class SolvePlan:
                                               _hip.ptr(self.Mvals), None, self.n, self.m, self.MW, 1, stream),
                    "diffhe_ell_assemble_rows(M)")
         self._ell_ready = True
+
+    def gradient_table(self):
+        """(gtab (npe*dim, m), vol (m)) on the device: grad phi_p and the size of every P1 triangle / tetrahedron
+        (diffhe_aniso_gradient_table), what the tensor assembly and its gradient read.  Built once per plan."""
+        cached = self.__dict__.get("_gradient_table")
+        if cached is None:
+            with self._build_lock:
+                cached = self.__dict__.get("_gradient_table")
+                if cached is None:
+                    gtab = torch.empty((self.npe * self.dim, self.m), dtype=torch.float64, device=self.device)
+                    vol = torch.empty(self.m, dtype=torch.float64, device=self.device)
+                    _hip.check(_hip.lib().diffhe_aniso_gradient_table(_hip.ptr(self.coords), _hip.ptr(self.elems), self.dim,
+                                                                      self.n, self.m, _hip.ptr(gtab), _hip.ptr(vol),
+                                                                      _stream(self.device)), "diffhe_aniso_gradient_table")
+                    cached = self.__dict__["_gradient_table"] = (gtab, vol)
+        return cached
 
     def closed_boundary_general(self) -> bool:
         """Every node of the mesh boundary is a Dirichlet node (general meshes, P1: a boundary edge belongs to exactly one
@@ -885,15 +905,19 @@ def _fingerprint(mesh):
 _PLAN_LOCK = threading.Lock()
 
 
-def get_plan(mesh, device: torch.device) -> SolvePlan:
+def get_plan(mesh, device: torch.device, prune: bool = True) -> SolvePlan:
     """Cached plan for (mesh, device); rebuilt when nodes/elements/BCs change.  One builder at a time: two threads
-    that meet on a new mesh get the same plan."""
-    key = (str(device), _fingerprint(mesh))
+    that meet on a new mesh get the same plan.  prune=False: the plan of tensor-coefficient solves on a 3D mesh, with the
+    unpruned stiffness pattern (see SolvePlan); it lives next to the scalar-kappa plan of the same mesh, which keeps
+    its pruned pattern and cached hierarchy.  On 1D and 2D meshes nothing is pruned: one plan serves both."""
+    fp = _fingerprint(mesh)
+    key = (str(device), fp) if prune or mesh.dim != 3 else (str(device), fp, "full")
     with _PLAN_LOCK:
         cache = mesh.__dict__.setdefault("_diffhe_plans", {})
         plan: Optional[SolvePlan] = cache.get(key)
         if plan is None:
-            cache.clear()
-            plan = SolvePlan(mesh, device)
+            for stale in [k for k in cache if k[:2] != key[:2]]:     # plans of another state of the mesh
+                del cache[stale]
+            plan = SolvePlan(mesh, device, prune=len(key) == 2)
             cache[key] = plan
     return plan

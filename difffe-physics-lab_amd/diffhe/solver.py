@@ -87,6 +87,30 @@ def _kappa_mode(kappa: torch.Tensor, m: int, B: Optional[int]):
     raise ValueError(f"kappa shape {tuple(kappa.shape)} not understood for a mesh with {m} elements")
 
 
+def _tensor_mode(kappa: torch.Tensor, nc: int, m: int, B: Optional[int], node_major: bool = False):
+    """Classify a conductivity TENSOR in Voigt components (diffhe.aniso; nc = 3 in 2D, 6 in 3D) -> (mode, B implied or
+    None, element-major).  (nc,) one tensor for mesh and batch; (m, nc) a field shared by the batch; (B, nc) one tensor
+    per sample; (B, m, nc) a field per sample -- with layout='node' also (nc, m, B), batch innermost (a shape that reads
+    both ways is read that way, as a square scalar field is).  (X, nc) with X == m is the element field, as a scalar
+    (m,) kappa is in `_kappa_mode` -- also when m happens to equal the batch B, UNLESS that batch comes with f: then,
+    exactly as there, B == m reads as one tensor per sample."""
+    shape = tuple(kappa.shape)
+    if shape == (nc,):
+        return K_SCALAR, None, False
+    if kappa.dim() == 2 and shape[1] == nc:
+        if shape[0] == m and (B is None or B == 1 or B != m):
+            return K_ELEM, None, False
+        return K_SAMPLE, shape[0], False
+    if kappa.dim() == 3:
+        if node_major and B is not None and shape == (nc, m, B):
+            return K_SAMPLE_ELEM, B, True
+        if shape[1:] == (m, nc):
+            return K_SAMPLE_ELEM, shape[0], False
+    raise ValueError(f"conductivity tensor shape {shape} not understood for a mesh with {m} elements: expected "
+                     f"({nc},), ({m}, {nc}), (B, {nc}) or (B, {m}, {nc}) in Voigt components"
+                     + (f", or ({nc}, {m}, B) with layout='node'" if node_major else ""))
+
+
 class _Engine:
     """Thin, stateless driver of the C ABI for one plan and one batch geometry."""
 
@@ -167,6 +191,80 @@ class _Engine:
                                                       _hip.ptr(p.is_bc), _hip.ptr(self.g), _hip.ptr(vals), _hip.ptr(lift),
                                                       p.n, p.m, p.W, Bv, st), "diffhe_ell_assemble_rows_ref")
         return vals, lift
+
+    def tensor_device(self, kappa, mode, B, Bp, nc, em=False):
+        """-> (tensor, stride per component, per element, per sample, Bv) as the kernels of csrc/aniso.hip index it.
+        Batch-shared tensors are used as they come; per-sample ones go batch-innermost with the padding samples set to
+        the identity: (nc, Bp), a field given (nc, m, B) (layout='node') as it is -- padded if B needs it -- and the
+        API's (B, m, nc) by the one transposing pass of scalar fields, which leaves it (m, nc, Bp)."""
+        p = self.p
+        k = kappa.detach().to(p.device, torch.float64)
+        d = p.dim
+        if mode == K_SCALAR:
+            return k.reshape(nc).contiguous(), 1, 0, 0, 1
+        if mode == K_ELEM:
+            return k.reshape(p.m, nc).contiguous(), 1, nc, 0, 1
+        eye = torch.zeros(nc, dtype=torch.float64, device=p.device)
+        eye[:d] = 1.0
+        if mode == K_SAMPLE:
+            kp = eye.reshape(nc, 1).repeat(1, Bp)
+            kp[:, :B] = k.reshape(B, nc).t()
+            return kp, Bp, 0, 1, Bp
+        if em:
+            if Bp == B and k.is_contiguous():
+                return k, p.m * Bp, Bp, 1, Bp
+            kp = eye.reshape(nc, 1, 1).repeat(1, p.m, Bp)
+            kp[:, :, :B] = k
+            return kp, p.m * Bp, Bp, 1, Bp
+        kp = self.to_node_major(k.reshape(B, p.m * nc).contiguous(), B, Bp, p.m * nc)      # (m, nc, Bp)
+        if Bp > B:
+            kp.view(p.m, nc, Bp)[:, :, B:] = eye.reshape(1, nc, 1)
+        return kp, Bp, nc * Bp, 1, Bp
+
+    def assemble_tensor(self, kdev, ksc, kse, ksb, Bv):
+        """vals (W, n, Bv), lift (n, Bv) of K_e[p,q] = |e| grad phi_p^T K_e grad phi_q (csrc/aniso.hip)."""
+        p = self.p
+        gtab, vol = p.gradient_table()
+        vals = torch.empty((p.W, p.n, Bv), dtype=torch.float64, device=p.device)
+        lift = torch.empty((p.n, Bv), dtype=torch.float64, device=p.device)
+        _hip.check(self.L.diffhe_aniso_assemble_rows(_hip.ptr(gtab), _hip.ptr(vol), p.dim, _hip.ptr(kdev), ksc, kse, ksb,
+                                                     _hip.ptr(p.ent_ptr), _hip.ptr(p.contrib), _hip.ptr(p.cols),
+                                                     _hip.ptr(p.is_bc), _hip.ptr(self.g), _hip.ptr(vals), _hip.ptr(lift),
+                                                     p.n, p.m, p.W, Bv, _stream(p.device)), "diffhe_aniso_assemble_rows")
+        return vals, lift
+
+    def grad_tensor(self, lam, x, B, Bp, nc, mode, em):
+        """dL/dK = -|e| sym(grad lambda (x) grad u) in the shape of the caller's tensor: per element and sample, summed
+        over the batch inside the kernel (a shared field), or summed over the elements per sample in two stages (one
+        tensor per sample; the tensor of the whole batch is the sum of those)."""
+        p, L = self.p, self.L
+        gtab, vol = p.gradient_table()
+        st = _stream(p.device)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=p.device)  # noqa: E731
+        if mode == K_ELEM:
+            dk = new(p.m, nc)
+            _hip.check(L.diffhe_aniso_grad_shared(_hip.ptr(p.elems), _hip.ptr(gtab), _hip.ptr(vol), p.dim, _hip.ptr(lam),
+                                                  _hip.ptr(x), _hip.ptr(self.g), p.n, p.m, B, Bp, _hip.ptr(dk), 1, nc, st),
+                       "diffhe_aniso_grad_shared")
+            return dk
+        dk_e = part = dk_sum = None
+        osc = ose = 0
+        if mode != K_SAMPLE_ELEM:
+            part, dk_sum = new(L.diffhe_grad_kappa_blocks(p.m, Bp), nc, Bp), new(nc, Bp)
+        elif em:
+            dk_e, osc, ose = new(nc, p.m, Bp), p.m * Bp, Bp
+        else:
+            dk_e, osc, ose = new(p.m * nc, Bp), Bp, nc * Bp
+        _hip.check(L.diffhe_aniso_grad(_hip.ptr(p.elems), _hip.ptr(gtab), _hip.ptr(vol), p.dim, _hip.ptr(lam), _hip.ptr(x),
+                                       _hip.ptr(self.g), p.n, p.m, Bp, _hip.ptr(dk_e), osc, ose, _hip.ptr(part),
+                                       _hip.ptr(dk_sum), st), "diffhe_aniso_grad")
+        if mode == K_SCALAR:
+            return dk_sum[:, :B].sum(dim=1)
+        if mode == K_SAMPLE:
+            return dk_sum[:, :B].t().contiguous()
+        if em:
+            return dk_e if Bp == B else dk_e[:, :, :B]
+        return self.to_sample_major(dk_e, B, Bp, p.m * nc).reshape(B, p.m, nc)
 
     def reaction_shifts(self, c, n_levels):
         """Per-level (n,) diagonal shifts c * M_L (0 on Dirichlet rows) of a FACTORED lattice operator, cached on the plan."""
@@ -567,12 +665,16 @@ def _rule_counts(rule: torch.Tensor, B: int) -> dict:
 
 
 
-def _kappa_layout(kappa: torch.Tensor, m: int, B_f: Optional[int], node_major: bool):
+def _kappa_layout(kappa: torch.Tensor, m: int, B_f: Optional[int], node_major: bool, nc: int = 0):
     """-> (mode, B, kappa_em) of one call; B_f is f's batch, None for one unbatched forcing.  layout='node': per-sample
     kappa fields may come element-major, (m, B), like f and u -- no transposing pass for kappa or its gradient either
-    (a square (m, m) tensor is read that way)."""
-    kappa_em = bool(node_major and kappa.dim() == 2 and tuple(kappa.shape) == (m, B_f))
-    mode, B_k = (K_SAMPLE_ELEM, B_f) if kappa_em else _kappa_mode(kappa, m, B_f)
+    (a square (m, m) tensor is read that way).  nc > 0: kappa is a conductivity tensor of nc Voigt components
+    (`_tensor_mode`)."""
+    if nc:
+        mode, B_k, kappa_em = _tensor_mode(kappa, nc, m, B_f, node_major)
+    else:
+        kappa_em = bool(node_major and kappa.dim() == 2 and tuple(kappa.shape) == (m, B_f))
+        mode, B_k = (K_SAMPLE_ELEM, B_f) if kappa_em else _kappa_mode(kappa, m, B_f)
     B = B_f if B_f is not None else (B_k if B_k is not None else 1)
     if B_k is not None and B_k != B:
         raise ValueError(f"kappa batch {B_k} does not match f batch {B}")
@@ -631,6 +733,7 @@ class _Call:
     # (device view of the op's input, stride per element / node, stride per sample).  Views, kept with the state too
     kappa_s: Optional[tuple] = None
     f_s: Optional[tuple] = None
+    nc: int = 0                     # kappa is a conductivity tensor of nc Voigt components (diffhe.aniso); 0: a scalar
 
     @classmethod
     def of(cls, solver, plan: SolvePlan, kappa, f, load, node_major, dirichlet=None, shape=False) -> "_Call":
@@ -642,7 +745,8 @@ class _Call:
         if node_major:
             f = f.t()                       # a (B, n) VIEW for the shape logic below; the data stays (n, B)
             load = load.t() if load is not None else None
-        mode, B, kappa_em = _kappa_layout(kappa, plan.m, f.shape[0] if batched else None, node_major)
+        nc = solver._tensor_components()
+        mode, B, kappa_em = _kappa_layout(kappa, plan.m, f.shape[0] if batched else None, node_major, nc)
         f_dev = f.detach().to(plan.device, torch.float64)
         f_s = None
         if shape:       # one forcing for the batch, or the (B, n) view through its strides
@@ -668,7 +772,8 @@ class _Call:
         if shape or bc is not None:
             kappa_s = _kappa_strided(kappa, mode, kappa_em, B, plan.m, plan.device)
         return cls(B, mode, kappa_em, batched, node_major, out_device, kappa.shape, kappa.device,
-                   load is not None and load.dim() == 2, float(solver.reaction), kappa, f_dev, load_dev, bc, kappa_s, f_s)
+                   load is not None and load.dim() == 2, float(solver.reaction), kappa, f_dev, load_dev, bc, kappa_s, f_s,
+                   nc)
 
     def facts(self) -> "_Call":
         return replace(self, kappa=None, f_dev=None, load_dev=None)
@@ -852,6 +957,8 @@ class _NodeMajorSolve(_PathSolve):
     def _grad_kappa(self, lam):
         """-> (per-sample sums, per-element gradient) of dL/dkappa = -lambda^T k0 u, as `_kappa_grad` takes them."""
         eng, call, B, Bp = self.eng, self.call, self.call.B, self.Bp
+        if call.nc:     # a conductivity tensor: the gradient comes back in the caller's shape (`_solve_backward`)
+            return None, eng.grad_tensor(lam, self.x, B, Bp, call.nc, call.mode, call.kappa_em)
         if call.mode == K_ELEM:
             return None, eng.grad_kappa_shared(lam, self.x, B, Bp)       # (m,): summed over the batch in the kernel
         dk_nm, dk_sum = eng.grad_kappa(lam, self.x, Bp, call.mode == K_SAMPLE_ELEM)
@@ -973,7 +1080,7 @@ class _EllSolve(_NodeMajorSolve):
         # scalar kappa per sample on a boundary closed by Dirichlet data: FACTORED like on closed lattices, ONE unit
         # matrix K_1 for the batch and K_1 x = F_b / kappa_b, its aggregation hierarchy plan-constant.  Not with a
         # reaction term, operator="assembled" or Neumann parts ("General meshes")
-        factored = (mode in (K_SCALAR, K_SAMPLE) and call.reaction == 0.0 and solver.operator != "assembled"
+        factored = (not call.nc and mode in (K_SCALAR, K_SAMPLE) and call.reaction == 0.0 and solver.operator != "assembled"
                     and not plan.is_p2 and solver.method != "ell-jacobi" and plan.closed_boundary_general())
         self.inv_kappa = None
         if factored:
@@ -985,8 +1092,12 @@ class _EllSolve(_NodeMajorSolve):
             rhs = self._rhs(call, lift, 1, kpad)                   # F_b = M f_b - kappa_b lift_1
             rhs *= self.inv_kappa                                  # ... / kappa_b: K_1 x = F_b / kappa_b
         else:
-            kdev, kse, ksb, Bv = eng.kappa_device(call.kappa, mode, B, Bp, em=call.kappa_em)
-            vals, lift = eng.assemble(kdev, kse, ksb, Bv)
+            if call.nc:     # conductivity tensor (diffhe.aniso): one matrix for the batch, or one per sample
+                kdev, ksc, kse, ksb, Bv = eng.tensor_device(call.kappa, mode, B, Bp, call.nc, em=call.kappa_em)
+                vals, lift = eng.assemble_tensor(kdev, ksc, kse, ksb, Bv)
+            else:
+                kdev, kse, ksb, Bv = eng.kappa_device(call.kappa, mode, B, Bp, em=call.kappa_em)
+                vals, lift = eng.assemble(kdev, kse, ksb, Bv)
             if call.reaction:
                 eng.add_reaction([vals], call.reaction, lattice=False)
             rhs = self._rhs(call, lift, Bv)
@@ -1042,7 +1153,9 @@ def _solve_forward(solver, kappa, f, load=None, node_major=False, dirichlet=None
     shape: the state also keeps what the node-gradient kernel reads (diffhe.shape)."""
     plan: SolvePlan = solver._plan()
     call = _Call.of(solver, plan, kappa, f, load, node_major, dirichlet, shape)
-    path = _select_path(plan, solver, call.reaction)
+    # a tensor coefficient (diffhe.aniso) always takes the general path, lattice meshes included (as with method="ell"):
+    # the lattice fast path has no tensor assembly and no coarse re-discretisation of a tensor (DESIGN section 7)
+    path = _EllSolve if call.nc else _select_path(plan, solver, call.reaction)
     tol, mg, amg = _call_options(chain=plan.is_chain, lattice=path is _LatticeSolve, closed_boundary=plan.closed_boundary,
                                  n=plan.n, mode=call.mode, tol_user=solver._tol_user, mg_user=solver._mg_user,
                                  mg=solver.mg, amg=solver.amg)
@@ -1097,7 +1210,8 @@ def _solve_backward(state: _PathSolve, gbar, need_k, need_f, need_load=False, ne
         dk_sample, dg = _dirichlet.band_grads(state, g, lam, dk_sample, dk_elem, need_k, need_g)
     grad_k = grad_f = grad_load = grad_g = None
     if need_k:
-        grad_k = _kappa_grad(call.mode, call.kappa_shape, dk_sample, dk_elem).to(call.kappa_device)
+        grad_k = dk_elem.reshape(call.kappa_shape) if call.nc else _kappa_grad(call.mode, call.kappa_shape, dk_sample, dk_elem)
+        grad_k = grad_k.to(call.kappa_device)
     if need_f:
         grad_f = (df if call.batched else df.sum(dim=0)).to(call.out_device)
     if need_load:
@@ -1177,7 +1291,7 @@ def _fe_solve_fake(kappa, f, load, handle, save, node_major=False, dirichlet=Non
     n, m = solver.mesh.n_nodes, solver.mesh.n_elements
     if node_major:
         return f.new_empty(tuple(f.shape), dtype=torch.float64), torch.empty((), dtype=torch.int64)
-    _, B, _ = _kappa_layout(kappa, m, f.shape[0] if f.dim() == 2 else None, False)
+    _, B, _ = _kappa_layout(kappa, m, f.shape[0] if f.dim() == 2 else None, False, solver._tensor_components())
     shape = (B, n) if (f.dim() == 2 or B > 1) else (n,)
     return f.new_empty(shape, dtype=torch.float64), torch.empty((), dtype=torch.int64)
 
@@ -1323,6 +1437,10 @@ def _fe_backward(ctx, grad_u, _grad_token):
         if need_g:
             raise NotImplementedError("diffhe: second-order derivatives through the Dirichlet values are not implemented "
                                       "(backward with create_graph=True while dirichlet= requires grad)")
+        solver = _SOLVERS.get(ctx.handle)
+        if solver is not None and solver._tensor_components():
+            raise NotImplementedError("diffhe: second-order derivatives of a solve with a conductivity tensor are not "
+                                      "implemented (backward with create_graph=True, diffhe.aniso)")
         grads = _second_order_backward(ctx, grad_u, need_k, need_f, need_load)
     else:
         token, kappa, f, load, dirichlet, nodes = ctx.saved_tensors[:6]
@@ -1451,6 +1569,10 @@ class DifferentiableFESolver(nn.Module):
 
     def _plan(self) -> SolvePlan:
         return get_plan(self.mesh, _resolve_device(self._device))
+
+    def _tensor_components(self) -> int:
+        """Voigt components of the coefficient when it is a conductivity tensor (diffhe.aniso), 0 for a scalar kappa."""
+        return 0
 
     def _adjoint_twin(self) -> "DifferentiableFESolver":
         """This solver on the same mesh with HOMOGENEOUS Dirichlet data: u = A^-1 load, the adjoint solve as a

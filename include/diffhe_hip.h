@@ -422,6 +422,36 @@ int diffhe_p1_grad_kappa(const int* elems, const double* k0, const double* lam, 
 int diffhe_p1_grad_kappa_shared(const int* elems, const double* k0, const double* lam, const double* u, const double* g,
                                 int npe, int m, int B, int Bp, double* dk, void* stream);
 
+/* Anisotropic conductivity (csrc/aniso.hip): a symmetric tensor K per element in Voigt components, nc = 3 in 2D ordered
+ * (xx, yy, xy), nc = 6 in 3D ordered (xx, yy, zz, yz, xz, xy); an off-diagonal component is one parameter for both
+ * symmetric entries.  P1 triangles (dim 2) and tetrahedra (dim 3).  Added without a change of DIFFHE_ABI_VERSION: no
+ * existing entry changed, and the binding resolves every symbol by name when it loads the library.
+ *
+ * Gradient-form element table: gtab (npe*dim, m), entry (p*dim + k, e) = d phi_p / d x_k up to the orientation sign of
+ * the element (it cancels in every product of two gradients), vol (m) = area / volume; a degenerate element (the rules
+ * of diffhe_p1_element_integrals) gets zeros in both. */
+int diffhe_aniso_gradient_table(const double* coords, const int* elems, int dim, int n, int m, double* gtab, double* vol,
+                                void* stream);
+/* Row-gather assembly vals (W, n, Bv), lift (n, Bv) of K_e[p,q] = vol_e g_p^T K_e g_q over the lists of
+ * diffhe_ell_assemble_rows, with its Dirichlet handling.  K component c of element e and sample b at
+ * c*k_sc + e*k_se + b*k_sb (k_se = 0: one tensor for the mesh; k_sb = 0 with Bv = 1: one for the batch).  The pattern
+ * must hold every coupling of the connectivity (no pruning of scalar-kappa zeros). */
+int diffhe_aniso_assemble_rows(const double* gtab, const double* vol, int dim, const double* K, long long k_sc,
+                               long long k_se, long long k_sb, const int* ent_ptr, const int* contrib, const int* cols,
+                               const unsigned char* is_bc, const double* g, double* vals, double* lift, int n, int m,
+                               int W, int Bv, void* stream);
+/* dK_c[e,b] = -vol_e sym_c(grad lambda_eb (x) grad u_eb), grad lambda = sum_p lambda[elem_p, b] g_p, u likewise with
+ * g (n, may be NULL) added on Dirichlet nodes; lam and u are (n, Bp).  dk_e optional: component c of (e, b) at
+ * c*o_sc + e*o_se + b.  dk_part (diffhe_grad_kappa_blocks(m, Bp), nc, Bp) and dk_sum (nc, Bp), both or neither: the
+ * sums over the elements per sample, two stages in a fixed order.  No atomics: bitwise reproducible. */
+int diffhe_aniso_grad(const int* elems, const double* gtab, const double* vol, int dim, const double* lam,
+                      const double* u, const double* g, int n, int m, int Bp, double* dk_e, long long o_sc,
+                      long long o_se, double* dk_part, double* dk_sum, void* stream);
+/* The same gradient summed over the samples b < B in a fixed order: dk component c of element e at c*o_sc + e*o_se. */
+int diffhe_aniso_grad_shared(const int* elems, const double* gtab, const double* vol, int dim, const double* lam,
+                             const double* u, const double* g, int n, int m, int B, int Bp, double* dk, long long o_sc,
+                             long long o_se, void* stream);
+
 /* Shape derivative dL/dX of a P1 solve (1D segments, triangles, tetrahedra; ABI v8):
  *   grad[i, k] = sum over the elements e at node i of A_e [ (q_e - tr T_e) I + T_e + T_e^T ] grad phi_i,
  *   T_e = sum_{b<B} kappa[e*kse + b*ksb] grad u_eb (x) grad lambda_eb,   q_e = sum_{b<B} (load_eb - c lambda_eb . u_eb / (d+1)),

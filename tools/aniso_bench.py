@@ -1,0 +1,122 @@
+"""Tensor-coefficient timing next to the scalar solver, one process, alternated round by round.  Prints JSON lines.
+
+    python tools/aniso_bench.py pair2d [N] [B] [steps] [rounds]    jittered N x N general-path mesh of tools/amg_bench.py
+    python tools/aniso_bench.py pair3d [N] [B] [steps] [rounds]    FEMesh.box(N, N, N), scalar side with the full pattern
+    python tools/aniso_bench.py sweep  [N] [B]                     iteration counts at eigenvalue ratio 1, 10, 100
+
+pair*: (a) a fwd + adjoint step of the scalar per-sample field (B, m) with method="ell" and (b) the same step of
+AnisotropicFESolver with K = kappa_e I built from the same field: the two matrices are equal up to rounding, so the
+iteration counts should be equal and the difference isolates the tensor assembly and gradient kernels.  Also prints
+the algorithmic bytes of those kernels (assembly 8 W n + 8 nc m, gradient 16 n + 8 nc m per sample) to set against a
+`rocprofv3 --kernel-trace --stats` run of this tool (a run of its own).
+"""
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "difffe-physics-lab_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from diffhe import AnisotropicFESolver, FEMesh  # noqa: E402
+from diffhe import aniso  # noqa: E402
+from diffhe.tet3d import DifferentiableFESolver3D  # noqa: E402
+
+mode = sys.argv[1] if len(sys.argv) > 1 else "pair2d"
+arg = lambda i, default: int(sys.argv[i]) if len(sys.argv) > i else default  # noqa: E731
+dev = torch.device("cuda", 0)
+
+
+def jittered_square(N):
+    m = FEMesh.rectangle(N, N)
+    rng = np.random.default_rng(0)
+    nodes = m.nodes.numpy().copy()
+    h = 1.0 / N
+    interior = (nodes[:, 0] > 1e-9) & (nodes[:, 0] < 1 - 1e-9) & (nodes[:, 1] > 1e-9) & (nodes[:, 1] < 1 - 1e-9)
+    nodes[interior] += rng.uniform(-0.25 * h, 0.25 * h, (int(interior.sum()), 2))
+    return FEMesh(nodes=torch.from_numpy(nodes), elements=m.elements, dirichlet_nodes=dict(m.dirichlet_nodes))
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def stepper(solver, kappa, f, B):
+    def step():
+        kappa.grad = None
+        u = solver(f)
+        (0.5 * (u * u).sum() / B).backward()
+    return step
+
+
+def pair(mesh, B, steps, rounds, label):
+    d, n, m = mesh.dim, mesh.n_nodes, mesh.n_elements
+    nc = d * (d + 1) // 2
+    gen = torch.Generator(device=dev).manual_seed(0)
+    f = 1 + 0.3 * torch.randn(B, n, generator=gen, dtype=torch.float64, device=dev)
+    field = 0.5 + 1.5 * torch.rand(B, m, generator=gen, dtype=torch.float64, device=dev)
+    ks = field.clone().requires_grad_(True)
+    kt = torch.zeros(B, m, nc, dtype=torch.float64, device=dev)
+    kt[..., :d] = field[..., None]
+    kt.requires_grad_(True)
+    scalar = DifferentiableFESolver3D(mesh, ks, device=dev, method="ell")
+    tensor = AnisotropicFESolver(mesh, kt, device=dev)
+    sides = {"scalar": stepper(scalar, ks, f, B), "tensor": stepper(tensor, kt, f, B)}
+    first = {k: round(timed(fn), 3) for k, fn in sides.items()}          # plan, hierarchy, code objects
+    for fn in sides.values():                                             # warm-up of the timed shapes
+        fn()
+    times = {k: [] for k in sides}
+    for r in range(rounds):
+        for k in (("scalar", "tensor") if r % 2 == 0 else ("tensor", "scalar")):
+            times[k] += [timed(sides[k]) for _ in range(steps)]
+    W = tensor._plan().W
+    out = dict(tool="aniso_bench", mode=label, n=n, m=m, B=B, W=W, W_scalar=scalar._plan().W, steps=steps, rounds=rounds,
+               first_step_s=first)
+    for k, s in (("scalar", scalar), ("tensor", tensor)):
+        t = times[k]
+        out[k] = dict(step_ms=round(1e3 * statistics.median(t), 2), min_ms=round(1e3 * min(t), 2),
+                      max_ms=round(1e3 * max(t), 2), iters=s.last_info.iterations, adj_iters=s.last_info.adj_iterations,
+                      path=s.last_info.path, not_converged=s.last_info.not_converged, max_relres=s.last_info.max_relres)
+    out["ratio_tensor_over_scalar"] = round(out["tensor"]["step_ms"] / out["scalar"]["step_ms"], 4)
+    trace = kt.grad[..., :d].sum(-1)
+    out["trace_grad_vs_scalar_grad"] = float((trace - ks.grad).abs().max() / ks.grad.abs().max())
+    out["algorithmic_bytes"] = dict(assemble_tensor=8.0 * B * (W * n + n + nc * m), assemble_scalar=8.0 * B * (W * n + n + m),
+                                    grad_tensor=8.0 * B * (2 * n + nc * m), grad_scalar=8.0 * B * (2 * n + m))
+    print(json.dumps(out), flush=True)
+
+
+def sweep(N, B):
+    """Iterations of the aggregation-multigrid PCG against the eigenvalue ratio of a smooth fibre field."""
+    mesh = jittered_square(N)
+    n = mesh.n_nodes
+    c = mesh.nodes[mesh.elements].mean(1).to(dev)
+    theta = 1.2 * torch.sin(2.0 * c[:, 0]) + 0.8 * torch.cos(3.0 * c[:, 1])
+    f = torch.ones(B, n, dtype=torch.float64, device=dev)
+    for ratio in (1.0, 10.0, 100.0):
+        kv = aniso.rotated(ratio, 1.0, theta).requires_grad_(True)                  # (m, 3), shared by the batch
+        s = AnisotropicFESolver(mesh, kv, device=dev)
+        import warnings
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            u = s(f)
+            (0.5 * (u * u).sum() / B).backward()
+        print(json.dumps(dict(tool="aniso_bench", mode="sweep", N=N, B=B, ratio=ratio, iters=s.last_info.iterations,
+                              adj_iters=s.last_info.adj_iterations, not_converged=s.last_info.not_converged,
+                              max_relres=s.last_info.max_relres, warnings=len(caught))), flush=True)
+
+
+if mode == "pair2d":
+    pair(jittered_square(arg(2, 512)), arg(3, 64), arg(4, 5), arg(5, 2), "pair2d")
+elif mode == "pair3d":
+    os.environ["DIFFHE_TET_PRUNE"] = "0"         # the scalar side stores the full pattern too
+    N = arg(2, 64)
+    pair(FEMesh.box(N, N, N), arg(3, 64), arg(4, 5), arg(5, 2), "pair3d")
+elif mode == "sweep":
+    sweep(arg(2, 64), arg(3, 8))
+else:
+    raise SystemExit(f"unknown mode {mode!r}")
