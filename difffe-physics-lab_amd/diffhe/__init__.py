@@ -9,9 +9,11 @@ reference's roadmap item; `diffhe.tet3d`: `DifferentiableFESolver3D`, solves on 
 `FEMesh.box`; `diffhe.shape`: `ShapeDifferentiableFESolver`, gradients with respect to the node coordinates, also
 exported here; `diffhe.dirichlet`: the adjoint step behind `forward(..., dirichlet=)`, per-sample Dirichlet values with
 gradients; `diffhe.aniso`: `AnisotropicFESolver`, solves with a conductivity tensor per element and its gradient, also
-exported here; `diffhe._hip`: the ctypes binding).
+exported here; `diffhe.robin`: `RobinFESolver`, Robin (convective) and flux boundary conditions on boundary facets with
+gradients to the film coefficient, the ambient value and the flux, also exported here; `diffhe._hip`: the ctypes binding).
 """
-from . import aniso as _aniso, loss as _loss, mesh as _mesh, neural as _neural, shape as _shape, solver as _solver
+from . import (aniso as _aniso, loss as _loss, mesh as _mesh, neural as _neural, robin as _robin, shape as _shape,
+               solver as _solver)
 
 FEMesh = _mesh.FEMesh
 DifferentiableFESolver = _solver.DifferentiableFESolver
@@ -19,7 +21,8 @@ PhysicsLoss = _loss.PhysicsLoss
 NeuralPDE = _neural.NeuralPDE
 ShapeDifferentiableFESolver = _shape.ShapeDifferentiableFESolver
 AnisotropicFESolver = _aniso.AnisotropicFESolver
+RobinFESolver = _robin.RobinFESolver
 
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
-           "AnisotropicFESolver")
+           "AnisotropicFESolver", "RobinFESolver")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

@@ -88,6 +88,13 @@ SIGNATURES = {
                             _L, _P, _I, _P]),
     "diffhe_bc_scatter": (_I, [_P, _I, _P, _L, _L, _P, _L, _L, _I, _P]),
     "diffhe_bc_grad_kappa": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _P]),
+    "diffhe_robin_facet_table": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "diffhe_robin_assemble": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _I,
+                                   _I, _I, _I, _P]),
+    "diffhe_robin_grad": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L,
+                               _L, _P]),
+    "diffhe_robin_sum_blocks": (_I, [_I]),
+    "diffhe_robin_sum_facets": (_I, [_P, _I, _I, _P, _P, _P]),
     "diffhe_to_node_major": (_I, [_P, _L, _P, _P, _I, _I, _I, _P]),
     "diffhe_to_sample_major": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),
 }

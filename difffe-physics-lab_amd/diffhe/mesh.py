@@ -144,6 +144,36 @@ class FEMesh:
         bc = self.dirichlet_nodes
         return torch.tensor([float(bc[k]) for k in sorted(bc.keys())], dtype=torch.float64).reshape(-1)
 
+    def boundary_facets(self) -> torch.Tensor:
+        """(n_F, d) int64 node ids of the boundary facets -- ours; what `diffhe.robin.RobinFESolver` indexes: the facets
+        that belong to exactly one element.  d = dim: the edges of triangles, the faces of tetrahedra, and on a 1D mesh
+        the end points (the nodes that belong to exactly one element).  Order: by owning element, then by local facet --
+        edges (0, 1), (1, 2), (2, 0) of a triangle; faces (1, 2, 3), (0, 2, 3), (0, 1, 3), (0, 1, 2) of a tetrahedron
+        (the face opposite local vertex 0, 1, 2, 3); local nodes 0, 1 of a segment -- with the nodes in that local
+        order.  Connectivity only (moving nodes does not change it); cached until `elements` changes.  P2 meshes
+        (`rectangle_p2`) raise NotImplementedError."""
+        if self.elements.shape[1] != self.dim + 1:
+            raise NotImplementedError("boundary_facets() is implemented for P1 elements only")
+        key = (id(self.elements), self.elements._version)
+        cached = self.__dict__.get("_boundary_facets")
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        el = self.elements.detach().to("cpu", torch.int64).numpy()
+        local = {1: ((0,), (1,)), 2: ((0, 1), (1, 2), (2, 0)), 3: ((1, 2, 3), (0, 2, 3), (0, 1, 3), (0, 1, 2))}[self.dim]
+        fac = np.stack([el[:, list(l)] for l in local], axis=1).reshape(-1, self.dim)      # (m * n_local, d), element-major
+        srt = np.sort(fac, axis=1)
+        n = self.n_nodes
+        if n < 2 ** 21:                                   # one int64 key per facet
+            code = srt[:, 0].copy()
+            for k in range(1, self.dim):
+                code = code * n + srt[:, k]
+            _, inv, cnt = np.unique(code, return_inverse=True, return_counts=True)
+        else:
+            _, inv, cnt = np.unique(srt, axis=0, return_inverse=True, return_counts=True)
+        out = torch.from_numpy(np.ascontiguousarray(fac[cnt[inv.reshape(-1)] == 1]))
+        self.__dict__["_boundary_facets"] = (key, out)
+        return out
+
     def h(self) -> float:
         """Smallest element length, 1D only (reference mesh.py:131-136)."""
         if self.dim == 1:

@@ -732,6 +732,54 @@ class SolvePlan:
             band_elems=dev(np.nonzero(touch)[0]), n_be=int(touch.sum()))
         return cached
 
+    def robin_table(self, key, facets: np.ndarray):
+        """The boundary band of Robin / flux data on the facets `facets` (n_F, d) int64 (csrc/robin.hip), built once per
+        (plan, facet set `key`), int32 / fp64 on the device:
+          fac (d, n_F) facet nodes, area (n_F) = |F| (diffhe_robin_facet_table);
+          rows / row_ptr: the FREE nodes on a facet and, per row, its entries (facet F, local row p, local column c) in
+            facet order: ent_code = F * 16 + p * 4 + c, ent_slot = the ELL slot of the coupling (row, node c of F), -1
+            when that column is a Dirichlet node (it is lifted);
+          the gradient kernel runs over fac itself, one group of lanes per facet.
+        Returns None when a coupling has no slot in this plan's pattern (a pruned pattern on FEMesh.box lacks the
+        diagonal of a boundary face's square): the caller takes the prune=False plan of the mesh."""
+        cache = self.__dict__.setdefault("_robin_tables", {})
+        with self._build_lock:
+            if key in cache:
+                return cache[key]
+            self._ensure_ell()
+            nF, d = facets.shape
+            if nF < 1 or nF >= 2 ** 27:
+                raise ValueError(f"diffhe: {nF} Robin facets (expected 1 .. 2**27 - 1)")
+            if d != self.dim or facets.min() < 0 or facets.max() >= self.n:
+                raise ValueError("diffhe: Robin facets must be (n_F, dim) node ids of this mesh")
+            is_bc = self.is_bc.cpu().numpy().astype(bool)
+            cols = self.cols.cpu().numpy()                                   # (W, n)
+            F = np.repeat(np.arange(nF, dtype=np.int64), d * d)
+            pc = np.tile(np.arange(d * d, dtype=np.int64), nF)
+            p, c = pc // d, pc % d
+            row, col = facets[F, p], facets[F, c]
+            keep = ~is_bc[row]
+            F, p, c, row, col = F[keep], p[keep], c[keep], row[keep], col[keep]
+            hit = cols[:, row] == col[None, :]                               # (W, entries); the diagonal is slot 0
+            lifted = is_bc[col]
+            if bool((~lifted & ~hit.any(axis=0)).any()):
+                cache[key] = None
+                return None
+            slot = np.where(lifted, -1, hit.argmax(axis=0))
+            order = np.argsort(row, kind="stable")                           # by row, facet order inside
+            rows, counts = np.unique(row, return_counts=True)
+            row_ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+            np.cumsum(counts, out=row_ptr[1:])
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)  # noqa: E731
+            fac = dev(facets.T)
+            area = torch.empty(nF, dtype=torch.float64, device=self.device)
+            _hip.check(_hip.lib().diffhe_robin_facet_table(_hip.ptr(self.coords), _hip.ptr(fac), d, self.n, nF,
+                                                           _hip.ptr(area), _stream(self.device)),
+                       "diffhe_robin_facet_table")
+            cache[key] = dict(d=d, n_f=nF, fac=fac, area=area, rows=dev(rows), n_rows=len(rows), row_ptr=dev(row_ptr),
+                              ent_code=dev((F * 16 + p * 4 + c)[order]), ent_slot=dev(slot[order]))
+            return cache[key]
+
     def ensure_ell(self):
         """ELL pattern, gather lists, element integrals and the ELL load matrix of the general path."""
         with self._build_lock:

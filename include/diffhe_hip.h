@@ -497,6 +497,36 @@ int diffhe_bc_grad_kappa(const int* elems, int npe, int m, const double* k0, con
                          int n_be, const double* lam, long long lsn, long long lsb, const double* G, long long gsj,
                          long long gsb, double* dk, long long dse, long long dsb, int shared, int B, void* stream);
 
+/* Robin (convective) and flux boundary conditions, kappa du/dn + h_F (u - uinf_F) = q_F on boundary facets (csrc/robin.hip;
+ * diffhe.robin).  Added without a change of DIFFHE_ABI_VERSION, like the aniso entries: no existing entry changed.  A facet
+ * has d nodes (1: an end point of a chain, 2: an edge, 3: a face of a tetrahedron), fac (d, nF); its consistent P1 mass is
+ * M_F[p, q] = area[F] (1 + delta_pq) / (d (d + 1)).  h, uinf, q of facet F and sample b sit at F*sf + b*sb of their array
+ * (sf = 0: one value for all facets, sb = 0: one for the batch; a NULL array is all zeros).  No atomics: bitwise
+ * reproducible.
+ * facet_table: area[F] = 1 (d = 1), the edge length (d = 2; 0 below 1e-15) or the triangle area (d = 3; 0 when
+ *   |a x b| <= 1e-12 l^2, l the longer of the edges a, b from the first node); coords (dim, n) with dim = d.
+ * assemble: for every band row r (a FREE node rows[r] on a facet) and its entries t in [row_ptr[r], row_ptr[r+1]), code
+ *   ent_code[t] = F*16 + p*4 + c (p the row's local index in F, c the column's): vals[(ent_slot[t]*n + row)*Bv + b] +=
+ *   h_Fb M_F[p, c], or with ent_slot[t] < 0 (Dirichlet column) rhs -= h_Fb M_F[p, c] g[node c]; entries with p == c also
+ *   add (h_Fb uinf_Fb + q_Fb) area[F] / d to rhs[row*Bp + b].  vals (W, n, Bv) as the ELL assembly left them, rhs
+ *   (n, Bp); Bv = 1 needs a batch-shared h.  Padding samples B <= b < Bp: h = 1 where h comes per sample, no load.
+ * grad: lam, u (n, Bp), g (n) or NULL added to u; with s = (area[F] / d) sum_p lam_p:  dq = s,  du = h_Fb s,
+ *   dh = uinf_Fb s - lam_F^T M_F u_F.  Each output may be NULL; (F, b) is written at F*of + b*ob, and ob = 0 asks for the
+ *   sum over the samples b < B (fixed order) at F*of.
+ * sum_facets: out[b] = sum_F src[F*B + b] in two fixed-order stages; part holds diffhe_robin_sum_blocks(nF) * B doubles. */
+int diffhe_robin_facet_table(const double* coords, const int* fac, int dim, int n, int nF, double* area, void* stream);
+int diffhe_robin_assemble(const int* fac, int d, int nF, const double* area, const int* rows, const int* row_ptr,
+                          const int* ent_code, const int* ent_slot, int n_rows, const double* g, const double* h,
+                          long long hsf, long long hsb, const double* uinf, long long usf, long long usb, const double* q,
+                          long long qsf, long long qsb, double* vals, double* rhs, int n, int Bv, int B, int Bp,
+                          void* stream);
+int diffhe_robin_grad(const int* fac, int d, int nF, const double* area, const double* lam, const double* u,
+                      const double* g, int B, int Bp, const double* h, long long hsf, long long hsb, const double* uinf,
+                      long long usf, long long usb, double* dh, long long dhf, long long dhb, double* du, long long duf,
+                      long long dub, double* dq, long long dqf, long long dqb, void* stream);
+int diffhe_robin_sum_blocks(int nF);
+int diffhe_robin_sum_facets(const double* src, int nF, int B, double* part, double* out, void* stream);
+
 /* Layout changes between the API's (B, n) and the solver's (n, Bp).
  * to_node_major: dst[i*Bp + b] = src[b*ld + i] (b < B), 0 for padding samples and
  *   where zero_mask[i] != 0 (zero_mask may be NULL; src row stride ld = 0 broadcasts).
