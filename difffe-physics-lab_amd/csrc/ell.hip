@@ -1177,6 +1177,7 @@ struct AmgHier {
   diffhe_amg_level lev[kAmgMaxLevels];
   int nl, Bv, Bp, n_coarse, gamma;
   double w0, w1, scale;
+  double wl0[kAmgMaxLevels], wl1[kAmgMaxLevels];   // the Jacobi weights of each level (amg_weights)
   void *xa[kAmgMaxLevels], *xb[kAmgMaxLevels], *res[kAmgMaxLevels], *rhs[kAmgMaxLevels];  // TV vectors
 };
 
@@ -1405,7 +1406,7 @@ TV* amg_cycle(const AmgHier& H, int l, const TV* rhs, double* rz_part, hipStream
       ALAUNCH((ell_jacobi_kernel<TV, double>), L.n, L.vals, L.cols, rhs, xin_, xout_, w_, part_, L.n, L.W, H.Bp, H.Bv);  \
   } while (0)
   for (int s = 0; s < pre; ++s) {
-    const double w = (s & 1) ? H.w1 : H.w0;
+    const double w = (s & 1) ? H.wl1[l] : H.wl0[l];
     const bool fin = last && s == pre - 1;
     if (s == 0) {
       AMG_JACOBI((const TV*)nullptr, a, w, fin ? rz_part : (double*)nullptr);
@@ -1437,7 +1438,7 @@ TV* amg_cycle(const AmgHier& H, int l, const TV* rhs, double* rz_part, hipStream
       ALAUNCH(agg_prolong_add_kernel<TV>, L.n, ec, L.agg, a, H.scale, L.n, H.Bp);
   }
   for (int s = 0; s < 2; ++s) {
-    const double w = (s & 1) ? H.w0 : H.w1;  // reverse order: symmetric cycle
+    const double w = (s & 1) ? H.wl0[l] : H.wl1[l];  // reverse order: symmetric cycle
     AMG_JACOBI((const TV*)a, b2, w, (l == 0 && s == 1) ? rz_part : (double*)nullptr);
     TV* t = a; a = b2; b2 = t;
   }
@@ -1707,6 +1708,17 @@ extern "C" int diffhe_ell_amg_pcg_solve(const diffhe_amg_level* levels, int n_le
   if (rc) return rc;
   H.n_coarse = n_coarse; H.gamma = gamma; H.scale = scale;
   H.w0 = 0.56; H.w1 = 1.39;  // Chebyshev weights for the interval [0.5, 2] of D^-1 A
+  // ... which holds for scalar kappa on reasonable meshes (lambda_max ~ 2.05).  A level that comes with a bound of its
+  // own above 2 (diffhe_amg_level.reserved, in thousandths: the coefficient-aware hierarchy records it; positive
+  // off-diagonals of an anisotropic tensor push lambda_max to 2.6 and the pair of sweeps would AMPLIFY the top modes)
+  // gets the same weights for [lambda / 4, lambda].  reserved == 0: the weights above, bit for bit.
+  for (int l = 0; l < H.nl; ++l) {
+    H.wl0[l] = H.w0; H.wl1[l] = H.w1;
+    if (H.lev[l].reserved > 2000) {
+      const double f = 2000.0 / (double)H.lev[l].reserved;
+      H.wl0[l] = H.w0 * f; H.wl1[l] = H.w1 * f;
+    }
+  }
   hipStream_t st = (hipStream_t)stream;
   const diffhe_amg_level& L0 = H.lev[0];
   const int n = L0.n, W = L0.W;

@@ -95,6 +95,9 @@ SIGNATURES = {
                                _L, _P]),
     "diffhe_robin_sum_blocks": (_I, [_I]),
     "diffhe_robin_sum_facets": (_I, [_P, _I, _I, _P, _P, _P]),
+    "diffhe_ell_sample_scales": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "diffhe_ell_mean_operator": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "diffhe_ell_strength_filter": (_I, [_P, _P, _I, _I, _D, _P, _P, _P]),
     "diffhe_to_node_major": (_I, [_P, _L, _P, _P, _I, _I, _I, _P]),
     "diffhe_to_sample_major": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),
 }
@@ -107,6 +110,7 @@ class HipExtensionError(RuntimeError):
 
 
 CHAIN_REFERENCE_ORDER = 1   # DIFFHE_CHAIN_REFERENCE_ORDER
+ELL_SCALE_CHUNK = 256       # DIFFHE_ELL_SCALE_CHUNK
 
 
 def lib():

@@ -192,18 +192,27 @@ def _csr_to_ell(A):
     return ell, slot * n + rows
 
 
-def smoothed_level(A1, ell_index_f, cols_f, active, seed, omega=2.0 / 3.0, drop=0.0):
+def smoothed_level(A1, ell_index_f, cols_f, active, seed, omega=2.0 / 3.0, drop=0.0, agg=None, AF=None):
     """One coarsening step.  A1: unit-kappa CSR matrix of the fine level; ell_index_f: ELL entry index (k*n_f + i) of each
     of its nonzeros (CSR order); cols_f: its ELL pattern (for the aggregation).  Returns the level dict (device arrays as
-    numpy) and the coarse unit matrix with ITS ell index."""
+    numpy) and the coarse unit matrix with ITS ell index.
+    Coefficient-aware hierarchy: A1 is the representative operator of the level, `agg` its aggregates on the strong graph
+    and `AF` its strength-filtered matrix, which smooths the prolongation instead of A1 (rows of AF without an
+    off-diagonal are not smoothed); the gather lists and the coarse matrix still run over the full pattern of A1."""
     import scipy.sparse as sp
     nf = A1.shape[0]
-    agg = aggregate(cols_f, active, seed=seed)
+    if agg is None:
+        agg = aggregate(cols_f, active, seed=seed)
     nc = int(agg.max()) + 1
     rows = np.nonzero(agg >= 0)[0]
     P0 = sp.csr_matrix((np.ones(len(rows)), (rows, agg[rows])), shape=(nf, nc))
-    d = A1.diagonal()
-    S = sp.identity(nf, format="csr") - sp.diags(omega / d) @ A1
+    if AF is None:
+        d = A1.diagonal()
+        S = sp.identity(nf, format="csr") - sp.diags(omega / d) @ A1
+    else:
+        d = AF.diagonal()
+        smooth = (np.diff(AF.indptr) > 1) & (d > 0)
+        S = sp.identity(nf, format="csr") - sp.diags(np.where(smooth, omega / np.where(smooth, d, 1.0), 0.0)) @ AF
     P = (sp.diags((agg >= 0).astype(np.float64)) @ S @ P0).tocsr()       # inactive (Dirichlet) rows interpolate nothing
     if drop > 0.0:
         P.data[np.abs(P.data) < drop] = 0.0
@@ -265,11 +274,18 @@ def smoothed_level(A1, ell_index_f, cols_f, active, seed, omega=2.0 / 3.0, drop=
 
 
 def build_hierarchy_sa(cols: np.ndarray, unit_vals: np.ndarray, is_bc: np.ndarray, min_coarse: int = 64,
-                       max_levels: int = 12) -> List[Dict]:
+                       max_levels: int = 12, strength: float = 0.0, rep_vals: np.ndarray = None,
+                       fine_filter=None) -> List[Dict]:
     """Smoothed-aggregation levels below the fine one.  cols (W, n), unit_vals (W, n): ELL pattern and UNIT-kappa values
     of the Dirichlet-eliminated fine matrix (identity rows on Dirichlet nodes).  Each dict: the coarse pattern and
     weighted Galerkin lists (n, W, cols, ent_ptr, contrib, weights) and the transfers from the level above (p_cols,
-    p_vals: P as ELL rows; agg_ptr, agg_members, agg_weights: P^T as CSR; agg: the underlying aggregates)."""
+    p_vals: P as ELL rows; agg_ptr, agg_members, agg_weights: P^T as CSR; agg: the underlying aggregates).
+    strength > 0: the coefficient-aware hierarchy of `rep_vals` (W, n), the representative operator of the batch in the
+    same pattern (None: unit_vals) -- `_build_hierarchy_operator`.  fine_filter: (strong_cols, filtered values) of the
+    fine level when the device has computed them already (diffhe_ell_strength_filter), else `strength_filter` does."""
+    if strength and strength > 0.0:
+        return _build_hierarchy_operator(cols, unit_vals if rep_vals is None else rep_vals, is_bc, float(strength),
+                                         min_coarse, max_levels, fine_filter)
     levels: List[Dict] = []
     A1, ell_idx = _ell_to_csr(cols, unit_vals)
     active = ~is_bc.astype(bool)
@@ -285,3 +301,137 @@ def build_hierarchy_sa(cols: np.ndarray, unit_vals: np.ndarray, is_bc: np.ndarra
         A1, ell_idx, cur_cols = Ac, ell_c, lev["cols"]
         active = np.ones(lev["n"], dtype=bool)
     return levels
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Coefficient-aware hierarchy (amg=dict(strength=theta)): aggregates on the graph of STRONG couplings of the operator
+# that is being solved, prolongation smoothed by its strength-filtered matrix.  The classical recipe of smoothed
+# aggregation (Vanek, Mandel, Brezina 1996), with a symmetrised row-relative strength measure.  Aggregates and P stay
+# batch-shared: they come from ONE representative matrix (csrc/coarsen.hip), the per-sample coarse operators stay the
+# exact P^T A_b P over the full pattern.
+# ---------------------------------------------------------------------------------------------------------------------
+def couplings(cols: np.ndarray, vals: np.ndarray, rows=None) -> np.ndarray:
+    """c_ij = max(-a_ij, 0) / sqrt(a_ii a_jj) per slot, (W, n) -- or (W, len(rows)) for the given rows; 0 on the diagonal
+    slot, on padding slots and where a_ii a_jj <= 0."""
+    W, n = cols.shape
+    i_idx = np.arange(n) if rows is None else np.asarray(rows)
+    cj, a = (cols, vals) if rows is None else (cols[:, i_idx], vals[:, i_idx])
+    real = (np.arange(W)[:, None] > 0) & (cj != i_idx[None, :])
+    d = vals[0]
+    prod = d[i_idx][None, :] * d[cj]
+    ok = real & (prod > 0)
+    c = np.zeros(cj.shape)
+    c[ok] = np.maximum(-a[ok], 0.0) / np.sqrt(prod[ok])
+    return c
+
+
+def strength_filter(cols: np.ndarray, vals: np.ndarray, theta: float):
+    """numpy restatement of diffhe_ell_strength_filter (include/diffhe_hip.h), operation for operation: -> (strong_cols
+    (W, n) int32 with weak and padding slots pointing at the row itself, filtered values (W, n) with the weak
+    off-diagonals lumped to the diagonal in slot order)."""
+    W, n = cols.shape
+    i_idx = np.arange(n)[None, :]
+    real = (np.arange(W)[:, None] > 0) & (cols != i_idx)
+    c = couplings(cols, vals)
+    own = real & (c > 0) & (c >= theta * c.max(axis=0)[None, :])
+    back = np.zeros((W, n), dtype=bool)              # does row j = cols[k, i] call i strong?
+    for kk in range(1, W):
+        back |= (cols[kk][cols] == i_idx) & own[kk][cols]
+    strong = own & back & real
+    filt = np.where(strong, vals, 0.0)
+    diag = vals[0].copy()
+    for k in range(1, W):
+        diag = diag + np.where(real[k] & ~strong[k], vals[k], 0.0)
+    filt[0] = diag
+    strong_cols = np.where(strong, cols, np.broadcast_to(i_idx, (W, n))).astype(np.int32)
+    return strong_cols, filt
+
+
+def aggregate_strong(strong_cols: np.ndarray, cols: np.ndarray, vals: np.ndarray, active: np.ndarray,
+                     seed: int = 0) -> np.ndarray:
+    """`aggregate` on the strong graph.  A node without a strong neighbour is no root: it joins the adjacent aggregate
+    (full pattern) it is most strongly coupled to; only a node with no aggregated neighbour at all stays a singleton."""
+    n = cols.shape[1]
+    has = (strong_cols != np.arange(n)[None, :]).any(axis=0)
+    agg = aggregate(strong_cols, active & has, seed=seed)
+    lone = np.nonzero(active & ~has)[0]
+    for _ in range(8):
+        if not len(lone):
+            break
+        nb = agg[cols[:, lone]]                      # the node's own slots read -1: it has no aggregate yet
+        score = np.where(nb >= 0, couplings(cols, vals, lone), -1.0)
+        best = score.argmax(axis=0)
+        ar = np.arange(len(lone))
+        ok = score[best, ar] >= 0.0
+        if not ok.any():
+            break
+        agg[lone[ok]] = nb[best, ar][ok]
+        lone = lone[~ok]
+    if len(lone):
+        agg[lone] = int(agg.max()) + 1 + np.arange(len(lone))
+    return agg
+
+
+def _build_hierarchy_operator(cols, rep_vals, is_bc, theta, min_coarse, max_levels, fine_filter):
+    """Levels of the coefficient-aware hierarchy: per level, strength filter at theta * 0.5^l -> aggregates on the strong
+    graph -> P = (I - omega D_F^-1 A_F) P_0 -> weighted gather lists over the FULL pattern -> coarse representative
+    P^T Abar P, the next level's operator."""
+    levels: List[Dict] = []
+    rep_vals = np.ascontiguousarray(rep_vals, dtype=np.float64)
+    A1, ell_idx = _ell_to_csr(cols, rep_vals)
+    active = ~is_bc.astype(bool)
+    cur_cols, cur_vals = cols, rep_vals
+    while len(levels) < max_levels - 1:
+        n_active = int(active.sum())
+        if n_active <= min_coarse:
+            break
+        if fine_filter is not None and not levels:
+            strong_cols, filt = fine_filter
+        else:
+            strong_cols, filt = strength_filter(cur_cols, cur_vals, theta * 0.5 ** len(levels))
+        agg = aggregate_strong(strong_cols, cur_cols, cur_vals, active, seed=len(levels))
+        AF, _ = _ell_to_csr(cur_cols, np.ascontiguousarray(filt))
+        AF.eliminate_zeros()
+        lev, Ac, ell_c = smoothed_level(A1, ell_idx, cur_cols, active, seed=len(levels), agg=agg, AF=AF)
+        if lev["n"] >= 0.7 * n_active:
+            break
+        lev["lam_parent"], lev["lam"] = jacobi_bound(A1), jacobi_bound(Ac)
+        levels.append(lev)
+        A1, ell_idx, cur_cols = Ac, ell_c, lev["cols"]
+        cur_vals = np.zeros(lev["W"] * lev["n"])
+        cur_vals[ell_c] = Ac.data
+        cur_vals = cur_vals.reshape(lev["W"], lev["n"])
+        active = np.ones(lev["n"], dtype=bool)
+    return levels
+
+
+def jacobi_bound(A, safety: float = 1.1) -> float:
+    """safety x lambda_max(D^-1 A) of a symmetric CSR matrix with a positive diagonal: what the cycle's Jacobi weights
+    have to cover on this level.  2.05 for a scalar kappa on a reasonable mesh; positive off-diagonals (anisotropic
+    tensors, obtuse triangles) raise it.  Lanczos from a fixed start vector (deterministic); capped by Gershgorin."""
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+    n = A.shape[0]
+    d = A.diagonal()
+    if n == 0 or not np.all(d > 0):
+        return 0.0
+    gersh = float((np.asarray(abs(A).sum(axis=1)).reshape(-1) / d).max())
+    Dm = sp.diags(1.0 / np.sqrt(d))
+    M = (Dm @ A @ Dm).tocsr()
+    if n <= 64:
+        lam = float(np.linalg.eigvalsh(M.toarray())[-1])
+    else:
+        try:
+            lam = float(spla.eigsh(M, k=1, which="LA", tol=1e-3, v0=np.ones(n), return_eigenvectors=False)[0])
+        except spla.ArpackNoConvergence:
+            return gersh
+    return min(safety * lam, gersh)
+
+
+def hierarchy_stats(cols: np.ndarray, levels: List[Dict]):
+    """(number of levels, the fine one included; operator complexity sum_l nnz_l / nnz_0) of a hierarchy."""
+    def nnz(c):
+        c = np.asarray(c)
+        return int(c.shape[1] + (c[1:] != np.arange(c.shape[1])[None, :]).sum())
+    n0 = nnz(cols)
+    return len(levels) + 1, float((n0 + sum(nnz(lv["cols"]) for lv in levels)) / n0)

@@ -902,22 +902,38 @@ class SolvePlan:
             return getattr(self, attr)
         from .amg import build_hierarchy, build_hierarchy_sa
         self._ensure_ell()
-        device = self.device
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
         if smoothed:
             host = build_hierarchy_sa(self.cols.cpu().numpy(), self._unit_ell_values(), self.is_bc.cpu().numpy())
         else:
             host = build_hierarchy(self.cols.cpu().numpy(), self.is_bc.cpu().numpy())
-        levels = []
-        for lv in host:
-            d = dict(n=lv["n"], W=lv["W"], cols=dev(lv["cols"]), ent_ptr=dev(lv["ent_ptr"]), contrib=dev(lv["contrib"]),
-                     agg=dev(lv["agg"]), agg_ptr=dev(lv["agg_ptr"]), agg_members=dev(lv["agg_members"]))
-            if smoothed:
-                d.update(weights=dev(lv["weights"]), agg_weights=dev(lv["agg_weights"]), p_cols=dev(lv["p_cols"]),
-                         p_vals=dev(lv["p_vals"]))
-            levels.append(d)
+        levels = [self.upload_amg_level(lv, smoothed) for lv in host]
         setattr(self, attr, levels)
         return levels
+
+    def upload_amg_level(self, lv, smoothed: bool):
+        """One host-side level dict of diffhe/amg.py as device tensors."""
+        device = self.device
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+        d = dict(n=lv["n"], W=lv["W"], cols=dev(lv["cols"]), ent_ptr=dev(lv["ent_ptr"]), contrib=dev(lv["contrib"]),
+                 agg=dev(lv["agg"]), agg_ptr=dev(lv["agg_ptr"]), agg_members=dev(lv["agg_members"]))
+        if smoothed:
+            d.update(weights=dev(lv["weights"]), agg_weights=dev(lv["agg_weights"]), p_cols=dev(lv["p_cols"]),
+                     p_vals=dev(lv["p_vals"]))
+        for key in ("lam", "lam_parent"):        # coefficient-aware hierarchy: eigenvalue bounds of D^-1 A per level
+            if key in lv:
+                d[key] = float(lv[key])
+        return d
+
+    def unit_amg_complexity(self, smoothed: bool) -> float:
+        """Operator complexity sum_l nnz_l / nnz_0 of the uploaded unit hierarchy (SolveInfo), counted once per plan."""
+        cache = self.__dict__.setdefault("_amg_complexity", {})
+        if smoothed not in cache:
+            def nnz(c):
+                return int(c.shape[1] + (c[1:] != torch.arange(c.shape[1], device=c.device)).sum())
+            levels = self.ensure_amg(smoothed)
+            n0 = nnz(self.cols)
+            cache[smoothed] = (n0 + sum(nnz(lv["cols"]) for lv in levels)) / n0
+        return cache[smoothed]
 
     def _unit_ell_values(self) -> np.ndarray:
         """(W, n) host copy of the Dirichlet-eliminated UNIT-kappa matrix in the ELL pattern (identity rows on Dirichlet

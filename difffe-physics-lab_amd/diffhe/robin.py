@@ -132,6 +132,7 @@ class _RobinSolve(_EllSolve):
         self.amg_hier = self._amg_hierarchy(vals, Bv, False) if solver.method != "ell-jacobi" else None
         if self.amg_hier is not None:
             info.path = "ell-amgpcg"
+            info.hierarchy, info.hierarchy_levels, info.operator_complexity, info.hierarchy_age = self.hier_info
             x, its, bad, relres = eng.amg_pcg(self.amg_hier, rhs, Bp, Bv, self.amg)
         else:
             info.path = "ell-pcg"

@@ -17,7 +17,9 @@ from __future__ import annotations
 
 import ctypes
 import itertools
+import math
 import os
+import threading
 import warnings
 import weakref
 from dataclasses import dataclass, replace
@@ -58,6 +60,13 @@ class SolveInfo:
     factored: bool = False      # one scalar kappa per sample (or for all) kept as K_b = kappa_b K_1: ONE unit matrix for the batch
     flags: int = 0              # lattice path: the `precond_fp32` word handed to diffhe_lattice_pcg_solve (include/diffhe_hip.h)
     precision: str = ""         # what is stored / computed in which precision in THIS solve, derived from those flags
+    # general path with a multigrid preconditioner: "unit" (hierarchy of the unit-kappa operator, plan-cached) or "operator"
+    # (amg=dict(strength=theta): built from the operator that was being solved, kept on the solver); its levels, the fine
+    # one included; its operator complexity sum_l nnz_l / nnz_0; the calls since it was built (0: built by this call)
+    hierarchy: str = ""
+    hierarchy_levels: int = 0
+    operator_complexity: float = 0.0
+    hierarchy_age: int = 0
 
 
 def _resolve_device(device) -> torch.device:
@@ -494,11 +503,15 @@ class _Engine:
                        "diffhe_ell_galerkin")
             chain[-1].update(agg=lv["agg"], agg_ptr=lv["agg_ptr"], agg_members=lv["agg_members"],
                              agg_weights=lv.get("agg_weights"), p_cols=lv.get("p_cols"), p_vals=lv.get("p_vals"))
-            chain.append(dict(n=lv["n"], W=lv["W"], vals=vc, cols=lv["cols"]))
+            if "lam_parent" in lv:
+                chain[-1]["lam"] = lv["lam_parent"]
+            chain.append(dict(n=lv["n"], W=lv["W"], vals=vc, cols=lv["cols"], lam=lv.get("lam")))
         arr = (_hip.AmgLevel * len(chain))()
         for i, lv in enumerate(chain):
             arr[i].n, arr[i].W = lv["n"], lv["W"]
             arr[i].vals, arr[i].cols = lv["vals"].data_ptr(), lv["cols"].data_ptr()
+            if lv.get("lam"):       # the level's own bound of lambda_max(D^-1 A), thousandths rounded up (diffhe_amg_level)
+                arr[i].reserved = int(math.ceil(1000.0 * lv["lam"]))
             if fp32 and Bv != 1:
                 lv["vals32"] = lv["vals"].to(torch.float32)
                 arr[i].vals32 = lv["vals32"].data_ptr()
@@ -520,6 +533,46 @@ class _Engine:
                 last["dense_inv"] = inv.contiguous()
                 arr[len(chain) - 1].dense_inv = last["dense_inv"].data_ptr()
         return arr, chain      # keep `chain` alive: it owns the coarse value tensors
+
+    def representative_operator(self, vals, Bv, B):
+        """abar (W, n) = mean over the REAL samples of a_b / s_b, s_b the mean free-row diagonal of sample b: the one
+        matrix the batch-shared aggregates and prolongation are built from (csrc/coarsen.hip)."""
+        p, L = self.p, self.L
+        st = _stream(p.device)
+        Br = B if Bv > 1 else 1
+        nblk = (p.n + _hip.ELL_SCALE_CHUNK - 1) // _hip.ELL_SCALE_CHUNK
+        part = torch.empty((nblk, Bv), dtype=torch.float64, device=p.device)
+        sums = torch.empty(Bv, dtype=torch.float64, device=p.device)
+        _hip.check(L.diffhe_ell_sample_scales(_hip.ptr(vals), _hip.ptr(p.is_bc), p.n, Bv, _hip.ptr(part), _hip.ptr(sums),
+                                              st), "diffhe_ell_sample_scales")
+        weight = (max(p.n - p.n_bc, 1) / sums).contiguous()          # 1 / s_b
+        abar = torch.empty((p.W, p.n), dtype=torch.float64, device=p.device)
+        _hip.check(L.diffhe_ell_mean_operator(_hip.ptr(vals), _hip.ptr(weight), p.n, p.W, Bv, Br, _hip.ptr(abar), st),
+                   "diffhe_ell_mean_operator")
+        return abar
+
+    def strength_filter(self, abar, theta):
+        """-> (strong columns (W, n) int32, filtered values (W, n)) of diffhe_ell_strength_filter on the plan's pattern."""
+        p = self.p
+        strong = torch.empty((p.W, p.n), dtype=torch.int32, device=p.device)
+        filt = torch.empty((p.W, p.n), dtype=torch.float64, device=p.device)
+        _hip.check(self.L.diffhe_ell_strength_filter(_hip.ptr(abar), _hip.ptr(p.cols), p.n, p.W, float(theta),
+                                                     _hip.ptr(strong), _hip.ptr(filt), _stream(p.device)),
+                   "diffhe_ell_strength_filter")
+        return strong, filt
+
+    def operator_levels(self, vals, Bv, B, theta):
+        """Device-side level dicts of the coefficient-aware hierarchy of THIS call's operator (diffhe.amg), and its
+        (levels, operator complexity).  Representative operator and fine-level filter on the device, the levels on the
+        host, as the unit hierarchy's are."""
+        from .amg import build_hierarchy_sa, hierarchy_stats
+        p = self.p
+        abar = self.representative_operator(vals, Bv, B)
+        strong, filt = self.strength_filter(abar, theta)
+        cols = p.cols.cpu().numpy()
+        host = build_hierarchy_sa(cols, None, p.is_bc.cpu().numpy(), strength=theta, rep_vals=abar.cpu().numpy(),
+                                  fine_filter=(strong.cpu().numpy(), filt.cpu().numpy()))
+        return [p.upload_amg_level(lv, True) for lv in host], hierarchy_stats(cols, host)
 
     def amg_pcg(self, amg, rhs, Bp, Bv, opts):
         p, L = self.p, self.L
@@ -1104,6 +1157,7 @@ class _EllSolve(_NodeMajorSolve):
         self.amg_hier = self._amg_hierarchy(vals, Bv, factored) if solver.method != "ell-jacobi" else None
         if self.amg_hier is not None:
             info.path = "ell-amgpcg"
+            info.hierarchy, info.hierarchy_levels, info.operator_complexity, info.hierarchy_age = self.hier_info
             x, its, bad, relres = eng.amg_pcg(self.amg_hier, rhs, Bp, Bv, self.amg)
         else:
             info.path = "ell-pcg"
@@ -1121,6 +1175,9 @@ class _EllSolve(_NodeMajorSolve):
         if factored and "fp32" not in solver._amg_user:
             # the fp32-stored cycle, off for kappa FIELDS (contrast breaks it), suits the contrast-free unit operator
             amg["fp32"] = 1
+        theta = float(amg.get("strength", 0) or 0)
+        if theta > 0.0:
+            return self._operator_hierarchy(vals, Bv, factored, theta)
         smoothed = bool(amg.get("smoothed", 1))
         amg_levels = plan.ensure_amg(smoothed=smoothed)
         if amg.get("scale") is None:
@@ -1129,11 +1186,38 @@ class _EllSolve(_NodeMajorSolve):
             # W-cycle where the fine level dominates the cycle (>= 12 M node-samples), V-cycle below
             amg["gamma"] = 2 if smoothed and plan.n * self.Bp >= 12_000_000 else 1
         fp32 = bool(amg.get("fp32", 0))
+        self.hier_info = ("unit", len(amg_levels) + 1, plan.unit_amg_complexity(smoothed), 0) if amg_levels else None
         if amg_levels and factored:          # plan-constant hierarchy of the unit operator: built once
             return plan.unit_amg((smoothed, fp32), lambda: eng.amg_setup(vals, 1, fp32, amg_levels, dense_coarse=True))
         if amg_levels:                       # at least one coarse level: aggregation-AMG PCG
             return eng.amg_setup(vals, Bv, fp32, amg_levels)
         return None
+
+    def _operator_hierarchy(self, vals, Bv, factored, theta):
+        """amg=dict(strength=theta): the hierarchy of the operator being solved ("Coefficient-aware
+        hierarchy").  It depends on the coefficient, so it lives on the SOLVER: built by the first general-path call from
+        that call's assembled operator (reaction and facet terms included), reused by later calls -- a stale hierarchy is
+        still an SPD preconditioner, only iteration counts drift -- until `refresh_hierarchy()` or every
+        amg["refresh"]-th call.  A factored solve's operator is the plan-constant K_1: its hierarchy is plan-cached."""
+        solver, plan, eng, amg = self.solver, self.plan, self.eng, self.amg
+        if not amg.get("smoothed", 1):
+            raise ValueError("amg strength > 0 builds a smoothed-aggregation hierarchy: it needs smoothed=1")
+        if amg.get("scale") is None:
+            amg["scale"] = 1.3
+        if amg.get("gamma") is None:
+            amg["gamma"] = 2 if plan.n * self.Bp >= 12_000_000 else 1
+        fp32 = bool(amg.get("fp32", 0))
+        if factored:
+            def build():
+                levels, stats = eng.operator_levels(vals, 1, 1, theta)
+                return (eng.amg_setup(vals, 1, fp32, levels, dense_coarse=True) if levels else None), stats
+            hier, stats = plan.unit_amg((True, fp32, theta), build)
+            self.hier_info = ("operator", stats[0], stats[1], 0) if hier else None
+            return hier
+        levels, stats, age = solver._hierarchy_levels(plan, theta, int(amg.get("refresh", 0) or 0),
+                                                      lambda: eng.operator_levels(vals, Bv, self.call.B, theta))
+        self.hier_info = ("operator", stats[0], stats[1], age) if levels else None
+        return eng.amg_setup(vals, Bv, fp32, levels) if levels else None
 
     def _adjoint_solve(self, rhs, info):
         """The forward's preconditioner and saved (per-sample) coarse operators; factored: lambda_b = K_1^-1 (g_b / kappa_b)."""
@@ -1530,10 +1614,14 @@ class DifferentiableFESolver(nn.Module):
         # Jacobi step of the unit-kappa operator (batch-shared), coarse operators as weighted Galerkin sums per sample:
         # about half the iterations of the piecewise-constant hierarchy (512^2 through this path: 82 -> see DESIGN);
         # scale None = 1.3 smoothed / 1.8 piecewise constant
+        # strength = theta > 0 (opt-in, absent = 0): aggregates and prolongation from the operator being solved instead of
+        # the unit-kappa one -- strong couplings c_ij >= theta max_k c_ik, theta halved per level; the hierarchy is kept on
+        # this solver (`refresh_hierarchy`, refresh = k: rebuilt every k-th call, 0 = never).  For anisotropic tensors
+        # and scalar fields of high contrast ("Coefficient-aware hierarchy")
         self.amg = dict(n_coarse=16, gamma=None, scale=None, fp32=0, max_iter=20000, smoothed=1)   # gamma None: 1, or 2 on big problems
         for item in filter(None, os.environ.get("DIFFHE_AMG", "").split(",")):  # e.g. "scale=1.0,gamma=2,max_iter=20000"
             key, val = item.split("=")
-            self.amg[key] = float(val) if key == "scale" else int(val)
+            self.amg[key] = float(val) if key in ("scale", "strength") else int(val)
         self.amg.update(amg or {})
         self._amg_user = set((amg or {}).keys()) | {i.split("=")[0] for i in os.environ.get("DIFFHE_AMG", "").split(",") if i}
         # fp32 = 1: the V-cycle (a preconditioner) STORES its vectors in fp32; all arithmetic, the
@@ -1562,6 +1650,30 @@ class DifferentiableFESolver(nn.Module):
         self._tol_user = tol
         self.tol, self.max_iter, self.check_every, self.assembly = tol, max_iter, check_every, assembly
         self.last_info = SolveInfo()
+        self._hier_lock = threading.Lock()
+        self._hier_cache: Dict[tuple, dict] = {}
+
+    def refresh_hierarchy(self) -> None:
+        """Drop the coefficient-aware hierarchies this solver keeps (amg=dict(strength=theta)): the next general-path call
+        builds one from its own operator.  Adjoint states of earlier calls keep the hierarchy they solved with."""
+        with self._hier_lock:
+            self._hier_cache.clear()
+
+    def _hierarchy_levels(self, plan: SolvePlan, theta: float, refresh: int, build):
+        """(levels, (n_levels, operator complexity), age) of the operator hierarchy for (plan, theta): cached under the
+        solver's lock, `build()` on the first call and -- refresh = k > 0 -- again once k calls have used it."""
+        key = (id(plan), float(theta), True)
+        with self._hier_lock:
+            ent = self._hier_cache.get(key)
+            if ent is not None and ent["plan"] is plan:
+                ent["age"] += 1
+                if not (refresh > 0 and ent["age"] >= refresh):
+                    return ent["levels"], ent["stats"], ent["age"]
+            while len(self._hier_cache) >= 4:
+                self._hier_cache.pop(next(iter(self._hier_cache)))
+            levels, stats = build()
+            self._hier_cache[key] = dict(plan=plan, levels=levels, stats=stats, age=0)
+            return levels, stats, 0
 
     @property
     def kappa(self) -> torch.Tensor:

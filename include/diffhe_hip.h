@@ -209,6 +209,8 @@ typedef struct diffhe_amg_level {
   const int* p_cols;         /* (p_width, n) next-level node of each entry of P's row, -1 = none */
   const double* p_vals;      /* (p_width, n) */
   int p_width;
+  /* 0, or 1000 x an upper bound of lambda_max(D^-1 A) of this level (coefficient-aware hierarchy): above 2000 the
+   * cycle's Jacobi weights, Chebyshev for [0.5, 2], are scaled by 2000 / reserved on this level */
   int reserved;
   /* LAST level of a batch-shared hierarchy (Bv == 1), optional: the (n, n) row-major INVERSE of this level's matrix,
    * n <= 128 -- the level is then solved by one dense product instead of n_coarse Jacobi sweeps (NULL: sweeps) */
@@ -526,6 +528,27 @@ int diffhe_robin_grad(const int* fac, int d, int nF, const double* area, const d
                       long long dub, double* dq, long long dqf, long long dqb, void* stream);
 int diffhe_robin_sum_blocks(int nF);
 int diffhe_robin_sum_facets(const double* src, int nF, int B, double* part, double* out, void* stream);
+
+/* Coefficient-aware aggregation hierarchy of the general path: its set-up passes (csrc/coarsen.hip; diffhe.amg).  Added
+ * without a change of DIFFHE_ABI_VERSION, like the aniso and robin entries: no existing entry changed.  vals (W, n, Bv) are
+ * the assembled ELL values of a call (slot 0 = diagonal, padding slots point at the row itself and hold 0).  No atomics:
+ * bitwise reproducible.
+ * sample_scales: out[b] = sum over the rows i with is_bc[i] == 0 (is_bc NULL: all rows) of vals[i*Bv + b], the diagonal,
+ *   in two fixed-order stages; part holds ceil(n / DIFFHE_ELL_SCALE_CHUNK) * Bv doubles.
+ * mean_operator: out[k*n + i] = (sum_{b < B} vals[(k*n + i)*Bv + b] * weight[b]) / B -- with weight[b] = 1 / (mean
+ *   free-row diagonal of sample b) the representative operator of the batch; the samples b >= B (padding) are not read.
+ *   Bv == 1 (B == 1): a scaled copy.
+ * strength_filter: on one matrix abar (W, n), W <= 64.  c_ij = max(-a_ij, 0) / sqrt(a_ii a_jj); slot k of row i (column
+ *   j) is STRONG when c_ij > 0, c_ij >= theta * max_k c_ik and, looked up in row j, c_ji > 0, c_ji >= theta * max_l c_jl.
+ *   strong_cols[k*n + i] = j on strong slots, i elsewhere (the graph diffhe.amg.aggregate reads); filt: abar with the
+ *   weak off-diagonals set to 0 and added to the diagonal in slot order (row sums kept). */
+#define DIFFHE_ELL_SCALE_CHUNK 256
+int diffhe_ell_sample_scales(const double* vals, const unsigned char* is_bc, int n, int Bv, double* part, double* out,
+                             void* stream);
+int diffhe_ell_mean_operator(const double* vals, const double* weight, int n, int W, int Bv, int B, double* out,
+                             void* stream);
+int diffhe_ell_strength_filter(const double* abar, const int* cols, int n, int W, double theta, int* strong_cols,
+                               double* filt, void* stream);
 
 /* Layout changes between the API's (B, n) and the solver's (n, Bp).
  * to_node_major: dst[i*Bp + b] = src[b*ld + i] (b < B), 0 for padding samples and

@@ -2,7 +2,9 @@
 
     python tools/aniso_bench.py pair2d [N] [B] [steps] [rounds]    jittered N x N general-path mesh of tools/amg_bench.py
     python tools/aniso_bench.py pair3d [N] [B] [steps] [rounds]    FEMesh.box(N, N, N), scalar side with the full pattern
-    python tools/aniso_bench.py sweep  [N] [B]                     iteration counts at eigenvalue ratio 1, 10, 100
+    python tools/aniso_bench.py sweep  [N] [B] [--strength THETA] [--ratios 1,10,100]
+                                                                   iteration counts against the eigenvalue ratio; with
+                                                                   --strength also for the coefficient-aware hierarchy
 
 pair*: (a) a fwd + adjoint step of the scalar per-sample field (B, m) with method="ell" and (b) the same step of
 AnisotropicFESolver with K = kappa_e I built from the same field: the two matrices are equal up to rounding, so the
@@ -23,6 +25,17 @@ from diffhe import AnisotropicFESolver, FEMesh  # noqa: E402
 from diffhe import aniso  # noqa: E402
 from diffhe.tet3d import DifferentiableFESolver3D  # noqa: E402
 
+def _option(name, default, kind=float):
+    if name in sys.argv:
+        i = sys.argv.index(name)
+        value = kind(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
+        return value
+    return default
+
+
+strength = _option("--strength", 0.0)
+ratios = [float(r) for r in _option("--ratios", "1,10,100", str).split(",")]
 mode = sys.argv[1] if len(sys.argv) > 1 else "pair2d"
 arg = lambda i, default: int(sys.argv[i]) if len(sys.argv) > i else default  # noqa: E731
 dev = torch.device("cuda", 0)
@@ -97,17 +110,29 @@ def sweep(N, B):
     c = mesh.nodes[mesh.elements].mean(1).to(dev)
     theta = 1.2 * torch.sin(2.0 * c[:, 0]) + 0.8 * torch.cos(3.0 * c[:, 1])
     f = torch.ones(B, n, dtype=torch.float64, device=dev)
-    for ratio in (1.0, 10.0, 100.0):
-        kv = aniso.rotated(ratio, 1.0, theta).requires_grad_(True)                  # (m, 3), shared by the batch
-        s = AnisotropicFESolver(mesh, kv, device=dev)
-        import warnings
-        with warnings.catch_warnings(record=True) as caught:
-            warnings.simplefilter("always")
-            u = s(f)
-            (0.5 * (u * u).sum() / B).backward()
-        print(json.dumps(dict(tool="aniso_bench", mode="sweep", N=N, B=B, ratio=ratio, iters=s.last_info.iterations,
-                              adj_iters=s.last_info.adj_iterations, not_converged=s.last_info.not_converged,
-                              max_relres=s.last_info.max_relres, warnings=len(caught))), flush=True)
+    import warnings
+    for ratio in ratios:
+        for th in ([0.0, strength] if strength else [0.0]):
+            if th == 0.0 and os.environ.get("ANISO_BENCH_SKIP_UNIT"):      # the unit side is already on record
+                continue
+            kv = aniso.rotated(ratio, 1.0, theta).requires_grad_(True)              # (m, 3), shared by the batch
+            s = AnisotropicFESolver(mesh, kv, device=dev, amg=dict(strength=th) if th else None)
+
+            def step():
+                kv.grad = None
+                u = s(f)
+                (0.5 * (u * u).sum() / B).backward()
+            with warnings.catch_warnings(record=True) as caught:
+                warnings.simplefilter("always")
+                first = timed(step)                                                 # builds plan and hierarchy
+                t = timed(step)
+            i = s.last_info
+            its = max(i.iterations + i.adj_iterations, 1)
+            print(json.dumps(dict(tool="aniso_bench", mode="sweep", N=N, B=B, ratio=ratio, strength=th, iters=i.iterations,
+                                  adj_iters=i.adj_iterations, not_converged=i.not_converged, max_relres=i.max_relres,
+                                  warnings=len(caught), hierarchy=i.hierarchy, levels=i.hierarchy_levels,
+                                  operator_complexity=round(i.operator_complexity, 3), first_step_s=round(first, 2),
+                                  step_ms=round(1e3 * t, 1), ms_per_iteration=round(1e3 * t / its, 4))), flush=True)
 
 
 if mode == "pair2d":
