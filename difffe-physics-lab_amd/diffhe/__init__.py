@@ -10,9 +10,11 @@ reference's roadmap item; `diffhe.tet3d`: `DifferentiableFESolver3D`, solves on 
 exported here; `diffhe.dirichlet`: the adjoint step behind `forward(..., dirichlet=)`, per-sample Dirichlet values with
 gradients; `diffhe.aniso`: `AnisotropicFESolver`, solves with a conductivity tensor per element and its gradient, also
 exported here; `diffhe.robin`: `RobinFESolver`, Robin (convective) and flux boundary conditions on boundary facets with
-gradients to the film coefficient, the ambient value and the flux, also exported here; `diffhe._hip`: the ctypes binding).
+gradients to the film coefficient, the ambient value and the flux, also exported here; `diffhe.eigen`: `EigenFESolver`,
+the smallest eigenpairs of K phi = lambda M_L phi per sample with d lambda / d kappa, also exported here; `diffhe._hip`:
+the ctypes binding).
 """
-from . import (aniso as _aniso, loss as _loss, mesh as _mesh, neural as _neural, robin as _robin, shape as _shape,
+from . import (aniso as _aniso, eigen as _eigen, loss as _loss, mesh as _mesh, neural as _neural, robin as _robin, shape as _shape,
                solver as _solver)
 
 FEMesh = _mesh.FEMesh
@@ -22,7 +24,8 @@ NeuralPDE = _neural.NeuralPDE
 ShapeDifferentiableFESolver = _shape.ShapeDifferentiableFESolver
 AnisotropicFESolver = _aniso.AnisotropicFESolver
 RobinFESolver = _robin.RobinFESolver
+EigenFESolver = _eigen.EigenFESolver
 
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
-           "AnisotropicFESolver", "RobinFESolver")
+           "AnisotropicFESolver", "RobinFESolver", "EigenFESolver")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

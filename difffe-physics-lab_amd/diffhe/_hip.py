@@ -98,6 +98,12 @@ SIGNATURES = {
     "diffhe_ell_sample_scales": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "diffhe_ell_mean_operator": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "diffhe_ell_strength_filter": (_I, [_P, _P, _I, _I, _D, _P, _P, _P]),
+    "diffhe_eig_gram_blocks": (_I, [_I, _I]),
+    "diffhe_eig_gram": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "diffhe_eig_ritz": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "diffhe_eig_rotate": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "diffhe_eig_residual": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "diffhe_eig_fix_sign": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "diffhe_to_node_major": (_I, [_P, _L, _P, _P, _I, _I, _I, _P]),
     "diffhe_to_sample_major": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),
 }

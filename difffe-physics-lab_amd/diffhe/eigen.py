@@ -1,0 +1,439 @@
+"""Smallest eigenpairs of K(kappa) phi = lambda M_L phi per sample, with d lambda / d kappa (ours: the reference has no
+eigensolver; its habit would be a dense `torch.linalg.eigh` of an assembled matrix, O(n^3)).
+
+`EigenFESolver(mesh, kappa, k)` finds, for every sample b, the k smallest eigenvalues and their vectors of the P1
+stiffness operator of `DifferentiableFESolver` against the LUMPED mass M_L (`plan.lumped_mass()`, the mean-value rule of
+`reaction=` and `diffhe.heat`): the fundamental frequencies of a membrane, the slowest decay rates of `HeatEquation`.
+Boundary conditions are HOMOGENEOUS Dirichlet on the mesh's Dirichlet nodes: only the keys of `mesh.dirichlet_nodes`
+are used, its values are ignored (the kernels read `plan.zero_g()`).
+
+Method: block inverse iteration with Rayleigh-Ritz on p = k + guard <= 16 vectors ("Eigenpairs").
+The operator is assembled and its multigrid hierarchy built ONCE per call, by the inner solver's own path object, whose
+saved operators every later solve reuses.  Each outer iteration solves A d_i = theta_i M x_i - A x_i for the p columns
+(A = K + shift M_L; the correction form of A y_i = theta_i M x_i started from x_i) to the loose relative tolerance
+`inner_tol`, applies A to Y = X + D explicitly, and runs four HIP passes of csrc/eigen.hip: per-sample Gram matrices,
+a dense Ritz step per sample (Cholesky + cyclic Jacobi, one sample per lane), the block rotation X = Y C, and the
+residual norms rho = |A x - theta M x|_{M^-1} / theta of the M-normalised Ritz vectors -- computed from the explicit
+A Y, so they certify the result whatever the inner tolerance was.  The iteration stops when rho <= tol for the first k
+columns of every sample (one host read per outer iteration); what is left above `tol` at `max_iter` is counted in
+`last_info.not_converged` and warned about.
+
+kappa layouts are the scalar ones of the base class, read as for a call whose f carries no batch: () one value,
+(m,) per element, (B,) or (B, 1) per sample, (B, m) per sample and element; `batch=B` forces the per-sample reading of
+a (B,) kappa when B == m.  Returns `lam` (B, k) ascending -- (k,) when neither kappa nor `batch=` carries a batch -- and
+`phi` (B, k, n), or with layout="node" (k, n, B), the block's own layout, without a transposing pass.  phi is
+M_L-orthonormal per sample, zero on the Dirichlet nodes, and signed so that sum_i m_i phi_i > 0 (where that sum is below
+1e-8 in magnitude: the entry of largest magnitude is positive).
+
+Gradients.  `lam` is differentiable with respect to kappa in every layout by the Hellmann-Feynman formula
+d lambda_i / d kappa_e = phi_i^T k0_e phi_i (phi M-normalised), evaluated by the gradient kernels of the solve
+(u = phi_i, adjoint vector = -lambda_bar_i phi_i): deterministic, no solve in backward.  `phi` is returned
+NON-differentiable: its derivative needs deflated indefinite solves (out of scope).  For a cluster of equal eigenvalues
+the returned vectors are an arbitrary M-orthonormal basis of the eigenspace and the gradient is that of their Rayleigh
+quotients: correct for symmetric functions of the cluster such as its sum, NOT for a single member of a degenerate pair.
+
+Not covered (NotImplementedError): 1D meshes (a tridiagonal pencil is dense-eigh territory), P2 meshes (row-sum lumping
+is not positive there), conductivity tensors, Robin terms, the `diffhe.distributed` helpers; interior eigenvalues and the
+consistent mass matrix are not offered.  A mesh without Dirichlet nodes needs `shift > 0` (ValueError otherwise): the
+inner solves then run on K + shift M_L through the `reaction=` mechanism, the returned lambda exclude the shift, and the
+lambda_1 = 0 mode is found like any other.
+"""
+from __future__ import annotations
+
+import warnings
+import weakref
+from dataclasses import dataclass, field
+from typing import Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _hip
+from .plan import padded_batch, _stream
+from .solver import (DifferentiableFESolver, K_ELEM, K_SAMPLE, K_SAMPLE_ELEM, K_SCALAR, SolveInfo, _Call, _LatticeSolve,
+                     _SOLVERS, _STATES, _StateGuard, _TOKENS, _call_options, _kappa_grad, _kappa_mode, _select_path,
+                     _state_of)
+from .tet3d import DifferentiableFESolver3D
+
+__all__ = ("EigenFESolver", "EigenInfo")
+
+MAX_BLOCK = 16          # kMaxP of csrc/eigen.hip
+JACOBI_SWEEPS = 30      # cap of the cyclic Jacobi sweeps (quadratic convergence: 6-9 are taken at p = 16)
+
+
+@dataclass
+class EigenInfo:
+    """Diagnostics of the last eigen call."""
+    path: str = ""
+    outer_iterations: int = 0
+    inner_solves: int = 0
+    inner_iterations: int = 0           # PCG iterations summed over the inner solves (each counts its slowest sample)
+    inner_not_converged: int = 0        # (solve, sample) pairs whose inner solve missed `inner_tol`
+    inner_tol: float = 0.0
+    block: int = 0                      # p = k + guard
+    residual: Optional[torch.Tensor] = None     # (B, k) final rho per (sample, mode), on the CPU
+    not_converged: int = 0              # (sample, mode) pairs above `tol` when the iteration ended
+    gram_failures: int = 0              # samples whose Gram matrix was not positive definite in the last Ritz step
+    inner: SolveInfo = field(default_factory=SolveInfo)     # the inner solver's record of the set-up solve
+
+
+def _eigen_layout(kappa: torch.Tensor, m: int, batch: Optional[int]):
+    """-> (mode, B, batched) of an eigen call: `_kappa_mode` as for a call whose f carries no batch, unless `batch` is
+    given (it then decides how a (B,) kappa with B == m reads, and is the batch of a kappa that carries none)."""
+    if batch is not None and int(batch) < 1:
+        raise ValueError(f"batch must be >= 1, got {batch!r}")
+    if kappa.dim() >= 3 or (kappa.dim() == 2 and kappa.shape[1] not in (1, m) and kappa.shape[1] in (3, 6)):
+        raise NotImplementedError("diffhe: eigenpairs with a conductivity tensor are not implemented (scalar kappa only)")
+    mode, Bk = _kappa_mode(kappa, m, None if batch is None else int(batch))
+    if batch is not None and Bk is not None and Bk != int(batch):
+        raise ValueError(f"kappa batch {Bk} does not match batch={batch}")
+    B = Bk if Bk is not None else (int(batch) if batch is not None else 1)
+    return mode, B, (Bk is not None or batch is not None)
+
+
+class _EigenRun:
+    """One eigen call: the inner solver's path state (assembled operators, hierarchy) plus the block buffers.  After
+    `run()` it keeps what the Hellmann-Feynman backward reads -- the k returned columns and the call's facts."""
+
+    def __init__(self, es: "EigenFESolver", kappa: torch.Tensor, batch: Optional[int]):
+        inner = es.inner
+        if inner._tensor_components():
+            raise NotImplementedError("diffhe: eigenpairs with a conductivity tensor are not implemented")
+        self.es, self.plan = es, inner._plan()
+        plan = self.plan
+        self.mode, self.B, self.batched = _eigen_layout(kappa, plan.m, batch)
+        self.Bp = padded_batch(self.B)
+        self.k, self.p = es.k, es.k + es.guard
+        if self.p > plan.n - plan.n_bc:
+            raise ValueError(f"block of {self.p} vectors on a mesh with {plan.n - plan.n_bc} free nodes")
+        self.kappa_shape, self.kappa_device = kappa.shape, kappa.device
+        self.L = _hip.lib()
+        self.mass = plan.lumped_mass()
+        self.state = None
+        self.X = None
+
+    # -- buffers and kernels ----------------------------------------------------------------------------------------
+    def _new(self, *shape, dtype=torch.float64):
+        return torch.empty(shape, dtype=dtype, device=self.plan.device)
+
+    def _start_block(self, x0, node_layout: bool) -> torch.Tensor:
+        """(p, n, Bp): seeded random columns (one draw per column, shared by the samples), the leading ones replaced
+        by `x0` where given; zero on the Dirichlet rows."""
+        plan, p, n, B, Bp = self.plan, self.p, self.plan.n, self.B, self.Bp
+        gen = torch.Generator().manual_seed(int(self.es.seed))
+        cols = torch.randn(p, n, generator=gen, dtype=torch.float64).to(plan.device)
+        Y = cols[:, :, None].expand(p, n, Bp).contiguous()
+        if x0 is not None:
+            x = x0.detach().to(plan.device, torch.float64)
+            if node_layout:
+                ok = x.dim() == 3 and x.shape[1] == n and x.shape[2] == B
+            else:
+                if x.dim() == 2 and not self.batched:
+                    x = x[None]
+                ok = x.dim() == 3 and x.shape[0] == B and x.shape[2] == n
+                x = x.permute(1, 2, 0) if ok else x
+            if not ok or not (self.k <= x.shape[0] <= p):
+                want = f"(c, {n}, {B})" if node_layout else f"({B}, c, {n})"
+                raise ValueError(f"x0 must be a previous phi, {want} with {self.k} <= c <= {p}, got {tuple(x0.shape)}")
+            Y[:x.shape[0], :, :B] = x
+        if plan.n_bc:
+            Y[:, plan.bc_index(), :] = 0.0
+        return Y
+
+    def _setup(self, kappa: torch.Tensor, Y: torch.Tensor, keep: bool = False) -> None:
+        """Assemble once and build (or reuse) the hierarchy once: the inner solver's path object solves the LAST column,
+        A y = M y_{p-1} to `inner_tol` -- one step of inverse iteration on a guard column, not wasted -- and keeps the
+        operators every later solve and every application of A reads.  keep: leave the column as it is (a warm start
+        without guard columns: a solve to `inner_tol` would throw its accuracy away)."""
+        inner, plan, B, n = self.es.inner, self.plan, self.B, self.plan.n
+        f0 = torch.zeros((B, n), dtype=torch.float64, device=plan.device)
+        load0 = (self.mass[:, None] * Y[-1])[:, :B].t().contiguous()
+        call = _Call.of(inner, plan, kappa, f0, load0, False)
+        path = _select_path(plan, inner, call.reaction)
+        tol, mg, amg = _call_options(chain=plan.is_chain, lattice=path is _LatticeSolve,
+                                     closed_boundary=plan.closed_boundary, n=plan.n, mode=call.mode,
+                                     tol_user=inner._tol_user, mg_user=inner._mg_user, mg=inner.mg, amg=inner.amg)
+        inner.tol = tol
+        state = path(inner, plan, call, tol, mg, amg)
+        state.eng.g = plan.zero_g()              # homogeneous Dirichlet data, whatever the mesh carries
+        info = SolveInfo()
+        state.forward(call, info)
+        inner.last_info = info
+        if not keep:
+            Y[-1][:, :B] = state.x[:, :B]
+        self.state, self.lattice = state, isinstance(state, _LatticeSolve)
+        if self.lattice:
+            eng = state.eng
+            shift = state.shift[:1] if state.shift is not None else None
+            self._lev = eng.lattice_levels(state.vals[:1], shift=shift)
+            self._apart = self._new(self.L.diffhe_lattice_blocks(n, self.Bp) * self.Bp)
+        else:
+            self._apart = self._new(self.L.diffhe_grad_kappa_blocks(n, self.Bp) * self.Bp)
+            self._kscale = None if state.inv_kappa is None else (1.0 / state.inv_kappa)
+
+    def _apply(self, x: torch.Tensor, y: torch.Tensor) -> None:
+        """y = A x with the saved operator (identity on the Dirichlet rows, where x is 0)."""
+        state, plan, L, st = self.state, self.plan, self.L, _stream(self.plan.device)
+        if self.lattice:
+            _hip.check(L.diffhe_lattice_apply(self._lev, state.Bv, _hip.ptr(state.scale), _hip.ptr(x), _hip.ptr(y),
+                                              _hip.ptr(self._apart), self.Bp, st), "diffhe_lattice_apply")
+            return
+        _hip.check(L.diffhe_ell_apply(_hip.ptr(state.vals), _hip.ptr(plan.cols), _hip.ptr(x), _hip.ptr(y),
+                                      _hip.ptr(self._apart), plan.n, plan.W, self.Bp, state.Bv, st), "diffhe_ell_apply")
+        if self._kscale is not None:             # factored general path: A_b = kappa_b K_1
+            y *= self._kscale
+
+    def _rayleigh_ritz(self, Y, AY) -> None:
+        """Gram -> Ritz -> rotate -> residual: X, AX, R = theta M X - A X, theta, rho from the block Y and A Y."""
+        L, plan, p, n, Bp, st = self.L, self.plan, self.p, self.plan.n, self.Bp, _stream(self.plan.device)
+        b = self.buf
+        _hip.check(L.diffhe_eig_gram(_hip.ptr(Y), _hip.ptr(AY), _hip.ptr(self.mass), _hip.ptr(plan.is_bc), p, n, Bp,
+                                     _hip.ptr(b["part"]), _hip.ptr(b["GA"]), _hip.ptr(b["GM"]), st), "diffhe_eig_gram")
+        _hip.check(L.diffhe_eig_ritz(_hip.ptr(b["GA"]), _hip.ptr(b["GM"]), p, Bp, JACOBI_SWEEPS, _hip.ptr(b["work"]),
+                                     _hip.ptr(b["C"]), _hip.ptr(b["theta"]), _hip.ptr(b["flag"]), st), "diffhe_eig_ritz")
+        _hip.check(L.diffhe_eig_rotate(_hip.ptr(Y), _hip.ptr(AY), _hip.ptr(b["C"]), _hip.ptr(b["theta"]),
+                                       _hip.ptr(self.mass), p, n, Bp, _hip.ptr(b["X"]), _hip.ptr(b["AX"]), None,
+                                       _hip.ptr(b["R"]), st), "diffhe_eig_rotate")
+        _hip.check(L.diffhe_eig_residual(_hip.ptr(b["R"]), _hip.ptr(b["theta"]), _hip.ptr(self.mass), p, n, Bp,
+                                         _hip.ptr(b["part"]), _hip.ptr(b["rho"]), st), "diffhe_eig_residual")
+
+    def _status(self) -> Tuple[int, int]:
+        """The one host read of an outer iteration: ((sample, mode) pairs above tol, samples with a failed Gram matrix).
+        A rho that is not a number counts as above tol."""
+        b, k, B = self.buf, self.k, self.B
+        above = (~(b["rho"][:k, :B] <= self.es.tol)).sum()
+        both = torch.stack([above, b["flag"][:B].sum().to(above.dtype)]).cpu()
+        return int(both[0]), int(both[1])
+
+    # -- the iteration --------------------------------------------------------------------------------------------------
+    def run(self, kappa: torch.Tensor, x0, node_layout: bool):
+        es, plan, L = self.es, self.plan, self.L
+        p, k, n, B, Bp = self.p, self.k, plan.n, self.B, self.Bp
+        info = EigenInfo(inner_tol=float(es.inner_tol), block=p)
+        Y = self._start_block(x0, node_layout)
+        self._setup(kappa, Y, keep=x0 is not None and self.p == self.k)
+        state = self.state
+        info.inner, info.path = es.inner.last_info, es.inner.last_info.path
+        info.inner_solves, info.inner_iterations = 1, int(info.inner.iterations)
+        info.inner_not_converged = int(info.inner.not_converged)
+        nblk = L.diffhe_eig_gram_blocks(n, Bp)
+        nq = p * (p + 1) // 2
+        self.buf = dict(X=self._new(p, n, Bp), AX=self._new(p, n, Bp), R=self._new(p, n, Bp), GA=self._new(nq, Bp),
+                        GM=self._new(nq, Bp), part=self._new(nblk * 2 * nq * Bp), work=self._new(2 * p * p * Bp),
+                        C=self._new(p, p, Bp), theta=self._new(p, Bp), rho=self._new(p, Bp),
+                        flag=self._new(Bp, dtype=torch.int32))
+        b = self.buf
+        AY = self._new(p, n, Bp)
+        for i in range(p):
+            self._apply(Y[i], AY[i])
+        self._rayleigh_ritz(Y, AY)
+        above, failed = self._status()
+        scratch = SolveInfo()
+        while above and info.outer_iterations < es.max_iter:
+            info.outer_iterations += 1
+            for i in range(p):
+                d, its, bad, _relres = state._adjoint_solve(b["R"][i], scratch)
+                info.inner_solves += 1
+                info.inner_iterations += int(its)
+                info.inner_not_converged += int(bad)
+                torch.add(b["X"][i], d, out=Y[i])
+                self._apply(Y[i], AY[i])
+            self._rayleigh_ritz(Y, AY)
+            above, failed = self._status()
+        sgn = self._new(k, Bp)
+        _hip.check(L.diffhe_eig_fix_sign(_hip.ptr(b["X"]), _hip.ptr(self.mass), k, n, Bp, _hip.ptr(b["part"]),
+                                         _hip.ptr(sgn), _stream(plan.device)), "diffhe_eig_fix_sign")
+        info.not_converged, info.gram_failures = above, failed
+        info.residual = b["rho"][:k, :B].t().cpu()
+        es.last_info = info
+        if failed:
+            warnings.warn(f"diffhe: the Gram matrix of {failed} of {B} samples was not positive definite in the last Ritz "
+                          "step (linearly dependent or non-finite block); their eigenpairs are not valid", RuntimeWarning)
+        if above:
+            warnings.warn(f"diffhe: {above} of {B * k} eigenpairs did not reach tol={es.tol:g} in {es.max_iter} outer "
+                          f"iterations (max relative residual {float(info.residual.max()):.2e}, path {info.path})",
+                          RuntimeWarning)
+        lam = (b["theta"][:k, :B] - es.shift).t().contiguous()                 # (B, k)
+        self.X = b["X"][:k]
+        if node_layout:
+            phi = self.X if Bp == B else self.X[:, :, :B]
+        else:
+            phi = self._new(B, k, n)
+            for i in range(k):      # column i of every sample into phi[:, i, :]: one transposing pass per column
+                _hip.check(L.diffhe_to_sample_major(_hip.ptr(self.X[i]), None, phi.data_ptr() + 8 * i * n, k * n, n, B, Bp,
+                                                    _stream(plan.device)), "diffhe_to_sample_major")
+            if not self.batched:
+                phi = phi[0]
+        if not self.batched:
+            lam = lam[0]
+        # what backward needs: the k columns and the engine (element tables, zero Dirichlet data); nothing else stays
+        self.eng = state.eng
+        self.state = self.buf = self._lev = self._apart = None
+        return lam, phi
+
+    def backward(self, glam: torch.Tensor) -> torch.Tensor:
+        """dL/dkappa = sum_i lambda_bar_{b,i} phi_{b,i}^T k0_e phi_{b,i} in the shape of kappa, by the solve's gradient
+        kernels (which compute -lam^T k0 u) with u = phi_i and lam = -lambda_bar_i phi_i."""
+        plan, eng, B, Bp, k, mode = self.plan, self.eng, self.B, self.Bp, self.k, self.mode
+        g = glam.detach().to(plan.device, torch.float64).reshape(B, k)
+        gp = torch.zeros((k, Bp), dtype=torch.float64, device=plan.device)
+        gp[:, :B] = g.t()
+        acc = None
+        for i in range(k):
+            lamv = self.X[i] * (-gp[i])[None, :]
+            if mode == K_ELEM:
+                part = eng.grad_kappa_shared(lamv, self.X[i], B, Bp)            # (m,), summed over the batch
+            else:
+                dk_nm, dk_sum = eng.grad_kappa(lamv, self.X[i], Bp, mode == K_SAMPLE_ELEM)
+                part = dk_nm if mode == K_SAMPLE_ELEM else dk_sum
+            acc = part if acc is None else acc + part
+        if mode == K_SAMPLE_ELEM:
+            grad = _kappa_grad(mode, self.kappa_shape, None, eng.to_sample_major(acc, B, Bp, plan.m))
+        elif mode == K_ELEM:
+            grad = _kappa_grad(mode, self.kappa_shape, None, acc)
+        else:
+            grad = _kappa_grad(mode, self.kappa_shape, acc[:B], None)
+        return grad.to(self.kappa_device)
+
+
+# ---------------------------------------------------------------------------------------------
+# torch.library custom ops diffhe::eig_solve / diffhe::eig_solve_backward: the solver and the state of the call travel as
+# integer handles, exactly as in diffhe::fe_solve (whose registries they share).
+# ---------------------------------------------------------------------------------------------
+@torch.library.custom_op("diffhe::eig_solve", mutates_args=())
+def eig_solve(kappa: torch.Tensor, x0: Optional[torch.Tensor], handle: int, batch: int, node_layout: bool,
+              save: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(lam, phi, token) of the `EigenFESolver` registered under `handle`; batch < 1: none given; `token` names the saved
+    state of the call (0 when `save` is false)."""
+    es = _SOLVERS[handle]
+    run = _EigenRun(es, kappa, batch if batch >= 1 else None)
+    lam, phi = run.run(kappa, x0, node_layout)
+    token = next(_TOKENS) if save else 0
+    if save:
+        _STATES[token] = run
+    # fresh tensors (an op's outputs may not alias one another); with layout="node" phi is the block itself
+    return lam.to(kappa.device), phi.to(kappa.device), torch.tensor(token, dtype=torch.int64)
+
+
+@eig_solve.register_fake
+def _eig_solve_fake(kappa, x0, handle, batch, node_layout, save):
+    es = _SOLVERS[handle]
+    n, m, k = es.mesh.n_nodes, es.mesh.n_elements, es.k
+    _, B, batched = _eigen_layout(kappa, m, batch if batch >= 1 else None)
+    lam = kappa.new_empty((B, k) if batched else (k,), dtype=torch.float64)
+    if node_layout:
+        phi = kappa.new_empty((k, n, B), dtype=torch.float64)
+    else:
+        phi = kappa.new_empty((B, k, n) if batched else (k, n), dtype=torch.float64)
+    return lam, phi, torch.empty((), dtype=torch.int64)
+
+
+@torch.library.custom_op("diffhe::eig_solve_backward", mutates_args=())
+def eig_solve_backward(glam: torch.Tensor, token: torch.Tensor, kappa_like: torch.Tensor) -> torch.Tensor:
+    """dL/dkappa of the call named by `token` from the cotangent of lam; no solve."""
+    return _state_of(token).backward(glam).to(kappa_like.device, kappa_like.dtype)
+
+
+@eig_solve_backward.register_fake
+def _eig_solve_backward_fake(glam, token, kappa_like):
+    return torch.empty_like(kappa_like)
+
+
+def _setup_context(ctx, inputs, output):
+    """As `solver._fe_setup_context`: kappa, the token and a sentinel that takes the saved state along when the graph is
+    freed.  phi (and the token) are marked non-differentiable."""
+    kappa = inputs[0]
+    lam, phi, token = output
+    ctx.mark_non_differentiable(phi, token)
+    real = not isinstance(token, torch._subclasses.FakeTensor)
+    sentinel = (torch.empty(0),) if real else ()
+    ctx.save_for_backward(token, kappa, *sentinel)
+    if real:
+        weakref.finalize(sentinel[0], _STATES.pop, int(token), None)
+        ctx.state_guard = _StateGuard(int(token))
+
+
+def _backward(ctx, glam, _gphi, _gtoken):
+    if torch.is_grad_enabled():
+        raise NotImplementedError("diffhe: second-order derivatives of eigenvalues are not implemented (backward with "
+                                  "create_graph=True, diffhe.eigen)")
+    token, kappa = ctx.saved_tensors[:2]
+    grad = torch.ops.diffhe.eig_solve_backward(glam, token, kappa) if ctx.needs_input_grad[0] else None
+    return grad, None, None, None, None, None
+
+
+torch.library.register_autograd("diffhe::eig_solve", _backward, setup_context=_setup_context)
+
+
+class EigenFESolver(nn.Module):
+    """The k smallest eigenpairs of K(kappa) phi = lambda M_L phi per sample, `lam` differentiable with respect to kappa
+    (see the module docstring for the problem, the layouts, the gradient and its limits on degenerate clusters; phi is
+    returned non-differentiable).
+
+    Parameters
+    ----------
+    mesh : FEMesh -- P1 triangles (lattice or general path) or P1 tetrahedra; the VALUES of `mesh.dirichlet_nodes` are
+        ignored, the boundary conditions are homogeneous.
+    kappa : float or tensor or Parameter -- (), (m,), (B,) / (B, 1) or (B, m); may require grad.
+    k : number of eigenpairs; guard : extra block columns (block p = k + guard <= 16; the convergence rate of mode i per
+        outer iteration is lambda_i / lambda_{p+1}).
+    tol : stop when |A x - theta M x|_{M^-1} / theta <= tol for the k columns of every sample; max_iter : outer iterations.
+    shift : sigma >= 0, the inner solves run on K + sigma M_L (`reaction=` of the inner solver); required > 0 on a mesh
+        without Dirichlet nodes.  The returned lambda exclude it.
+    seed : of the CPU generator the start block is drawn from.
+    inner_tol : relative residual of the inner correction solves (their right-hand side is the current eigen-residual, so
+        the absolute accuracy asked of them tightens as the iteration converges).
+    solver_options : passed to the inner `DifferentiableFESolver` (2D) / `DifferentiableFESolver3D` (3D): device, method,
+        mg, amg, operator, assembly, ...
+    """
+
+    def __init__(self, mesh, kappa=1.0, k: int = 4, *, guard: int = 4, tol: float = 1e-8, max_iter: int = 200,
+                 shift: float = 0.0, seed: int = 0, inner_tol: float = 1e-2, **solver_options):
+        super().__init__()
+        if mesh.dim == 1:
+            raise NotImplementedError("diffhe: eigenpairs on 1D meshes are not implemented (a tridiagonal pencil is "
+                                      "dense-eigh territory)")
+        if mesh.dim not in (2, 3):
+            raise NotImplementedError("Only 2D and 3D meshes supported")
+        if mesh.elements.shape[1] != mesh.dim + 1:
+            raise NotImplementedError("diffhe: eigenpairs are implemented for P1 elements only (the row-sum lumped mass "
+                                      f"of a mesh with {mesh.elements.shape[1]} nodes per element is not positive)")
+        k, guard = int(k), int(guard)
+        if k < 1 or guard < 0 or k + guard > MAX_BLOCK:
+            raise ValueError(f"need 1 <= k and guard >= 0 with k + guard <= {MAX_BLOCK}, got k={k}, guard={guard}")
+        if not (float(tol) > 0.0) or not (0.0 < float(inner_tol) < 1.0) or int(max_iter) < 0:
+            raise ValueError(f"need tol > 0, 0 < inner_tol < 1, max_iter >= 0, got {tol!r}, {inner_tol!r}, {max_iter!r}")
+        if not (float(shift) >= 0.0):
+            raise ValueError(f"shift must be >= 0, got {shift!r}")
+        if not mesh.dirichlet_nodes and float(shift) == 0.0:
+            raise ValueError("diffhe: a mesh without Dirichlet nodes needs shift > 0 (K alone is singular there)")
+        for name in ("reaction", "warm_start"):
+            if name in solver_options:
+                raise ValueError(f"{name}= is not an option of EigenFESolver" + (" (use shift=)" if name == "reaction" else ""))
+        if isinstance(kappa, torch.Tensor) and (kappa.dim() >= 3 or (kappa.dim() == 2 and kappa.shape[1] in (3, 6)
+                                                                      and kappa.shape[1] not in (1, mesh.n_elements))):
+            raise NotImplementedError("diffhe: eigenpairs with a conductivity tensor are not implemented (scalar kappa only)")
+        self.mesh, self.k, self.guard = mesh, k, guard
+        self.tol, self.max_iter, self.shift, self.seed = float(tol), int(max_iter), float(shift), int(seed)
+        self.inner_tol = float(inner_tol)
+        cls = DifferentiableFESolver if mesh.dim == 2 else DifferentiableFESolver3D
+        self.inner = cls(mesh, kappa, tol=self.inner_tol, reaction=self.shift, **solver_options)
+        self.last_info = EigenInfo()
+
+    @property
+    def kappa(self) -> torch.Tensor:
+        return self.inner.kappa
+
+    def forward(self, batch: Optional[int] = None, x0: Optional[torch.Tensor] = None, layout: str = "sample"):
+        """-> (lam, phi).  batch: the number of samples, where kappa does not say (or reads both ways); x0: a previous
+        phi in the same `layout` as a warm start -- with k columns it is padded with seeded random guard columns, with
+        k + guard columns it is the whole start block; layout: "sample" = phi (B, k, n), "node" = phi (k, n, B)."""
+        if layout not in ("sample", "node"):
+            raise ValueError(f"Unknown layout: {layout!r}")
+        kappa = self.inner.kappa
+        _eigen_layout(kappa, self.mesh.n_elements, batch)
+        _SOLVERS[id(self)] = self
+        save = torch.is_grad_enabled() and kappa.requires_grad
+        lam, phi, _token = torch.ops.diffhe.eig_solve(kappa, None if x0 is None else x0.detach(), id(self),
+                                                      -1 if batch is None else int(batch), layout == "node", save)
+        return lam, phi

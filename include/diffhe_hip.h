@@ -550,6 +550,37 @@ int diffhe_ell_mean_operator(const double* vals, const double* weight, int n, in
 int diffhe_ell_strength_filter(const double* abar, const int* cols, int n, int W, double theta, int* strong_cols,
                                double* filt, void* stream);
 
+/* Block machinery of the batched eigensolver, K phi = lambda M_L phi per sample (csrc/eigen.hip; diffhe.eigen).  Added
+ * without a change of DIFFHE_ABI_VERSION, like the aniso, robin and coarsen entries: no existing entry changed.  A block of
+ * p <= 16 vectors is (p, n, Bp): column c is an (n, Bp) array at c * n * Bp.  Small per-sample matrices are (p, p, Bp), entry
+ * (r, c) of sample b at (r*p + c)*Bp + b; symmetric ones are packed by the rows of their upper triangle,
+ * q(i, j) = i*p - i*(i-1)/2 + (j - i) for i <= j, as (p(p+1)/2, Bp).  Every sum over the nodes runs in two fixed-order
+ * stages over diffhe_eig_gram_blocks(n, Bp) block partials; no atomics: bitwise reproducible.
+ * gram:     GA[q(i,j)] = y_i . (AY)_j, GM[q(i,j)] = y_i . (mass * y_j) over the rows with is_bc == 0 (is_bc NULL: all rows);
+ *           part holds blocks * p(p+1) * Bp doubles.  The (i, j) pairs are tiled 4 x 4 over the grid: Y and AY are read
+ *           (2 d + 3 o) / (2 t) times, t = ceil(p/4) tiles, d = t diagonal and o = t(t-1)/2 off-diagonal pairs (1.75 at p = 8,
+ *           3.25 at p = 16).
+ * ritz:     one sample per lane: Cholesky GM = L L^T, cyclic Jacobi (at most `sweeps` sweeps) on L^-1 GA L^-T, eigenvalues
+ *           ascending in theta (p, Bp), C (p, p, Bp) = L^-T V so that C^T GA C = diag(theta), C^T GM C = I.  work: 2 p p Bp
+ *           doubles.  flag[b] = 1 where GM is not positive definite or an input is not finite: C = I and theta = 0 there.
+ * rotate:   X = Y C, AX = AY C, and from the same registers MX = mass * X and R = theta * MX - AX (each of the two may be
+ *           NULL; theta is read for R only).  The outputs must not alias the inputs.  C is staged in LDS, at most 128 / p
+ *           columns per pass: p > 11 re-reads Y and AY once more.
+ * residual: rho[c, b] = sqrt(sum_i R[c, i, b]^2 / mass_i) / |theta[c, b]| (1e300 where theta is 0); part: blocks * p * Bp.
+ * fix_sign: in place on the first k columns: column c of sample b is negated unless sum_i mass_i x_i > 0 -- where that sum
+ *           is below 1e-8 in magnitude, unless its entry of largest magnitude is positive.  sgn (k, Bp) receives the
+ *           factors; part: blocks * 2 k * Bp doubles. */
+int diffhe_eig_gram_blocks(int n, int Bp);
+int diffhe_eig_gram(const double* Y, const double* AY, const double* mass, const unsigned char* is_bc, int p, int n,
+                    int Bp, double* part, double* GA, double* GM, void* stream);
+int diffhe_eig_ritz(const double* GA, const double* GM, int p, int Bp, int sweeps, double* work, double* C, double* theta,
+                    int* flag, void* stream);
+int diffhe_eig_rotate(const double* Y, const double* AY, const double* C, const double* theta, const double* mass, int p,
+                      int n, int Bp, double* X, double* AX, double* MX, double* R, void* stream);
+int diffhe_eig_residual(const double* R, const double* theta, const double* mass, int p, int n, int Bp, double* part,
+                        double* rho, void* stream);
+int diffhe_eig_fix_sign(double* X, const double* mass, int k, int n, int Bp, double* part, double* sgn, void* stream);
+
 /* Layout changes between the API's (B, n) and the solver's (n, Bp).
  * to_node_major: dst[i*Bp + b] = src[b*ld + i] (b < B), 0 for padding samples and
  *   where zero_mask[i] != 0 (zero_mask may be NULL; src row stride ld = 0 broadcasts).
