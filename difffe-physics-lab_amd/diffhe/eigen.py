@@ -8,8 +8,8 @@ Boundary conditions are HOMOGENEOUS Dirichlet on the mesh's Dirichlet nodes: onl
 are used, its values are ignored (the kernels read `plan.zero_g()`).
 
 Method: block inverse iteration with Rayleigh-Ritz on p = k + guard <= 16 vectors ("Eigenpairs").
-The operator is assembled and its multigrid hierarchy built ONCE per call, by the inner solver's own path object, whose
-saved operators every later solve reuses.  Each outer iteration solves A d_i = theta_i M x_i - A x_i for the p columns
+The operator is assembled and its multigrid hierarchy built ONCE per call, by the inner solver's own path object (set up
+by `solver._begin_call`, as for any solve), whose saved operators every later solve reuses.  Each outer iteration solves A d_i = theta_i M x_i - A x_i for the p columns
 (A = K + shift M_L; the correction form of A y_i = theta_i M x_i started from x_i) to the loose relative tolerance
 `inner_tol`, applies A to Y = X + D explicitly, and runs four HIP passes of csrc/eigen.hip: per-sample Gram matrices,
 a dense Ritz step per sample (Cholesky + cyclic Jacobi, one sample per lane), the block rotation X = Y C, and the
@@ -41,7 +41,6 @@ lambda_1 = 0 mode is found like any other.
 from __future__ import annotations
 
 import warnings
-import weakref
 from dataclasses import dataclass, field
 from typing import Optional, Tuple
 
@@ -50,9 +49,8 @@ import torch.nn as nn
 
 from . import _hip
 from .plan import padded_batch, _stream
-from .solver import (DifferentiableFESolver, K_ELEM, K_SAMPLE, K_SAMPLE_ELEM, K_SCALAR, SolveInfo, _Call, _LatticeSolve,
-                     _SOLVERS, _STATES, _StateGuard, _TOKENS, _call_options, _kappa_grad, _kappa_mode, _select_path,
-                     _state_of)
+from .solver import (DifferentiableFESolver, K_ELEM, K_SAMPLE_ELEM, SolveInfo, _Call, _LatticeSolve, _SOLVERS, _begin_call,
+                     _kappa_grad, _kappa_mode, _register_state, _state_of, _tie_state)
 from .tet3d import DifferentiableFESolver3D
 
 __all__ = ("EigenFESolver", "EigenInfo")
@@ -149,15 +147,10 @@ class _EigenRun:
         f0 = torch.zeros((B, n), dtype=torch.float64, device=plan.device)
         load0 = (self.mass[:, None] * Y[-1])[:, :B].t().contiguous()
         call = _Call.of(inner, plan, kappa, f0, load0, False)
-        path = _select_path(plan, inner, call.reaction)
-        tol, mg, amg = _call_options(chain=plan.is_chain, lattice=path is _LatticeSolve,
-                                     closed_boundary=plan.closed_boundary, n=plan.n, mode=call.mode,
-                                     tol_user=inner._tol_user, mg_user=inner._mg_user, mg=inner.mg, amg=inner.amg)
-        inner.tol = tol
-        state = path(inner, plan, call, tol, mg, amg)
+        state = _begin_call(inner, plan, call)
         state.eng.g = plan.zero_g()              # homogeneous Dirichlet data, whatever the mesh carries
         info = SolveInfo()
-        state.forward(call, info)
+        state.forward(call, info)                # no warning per inner solve: `run` reports what the iteration missed
         inner.last_info = info
         if not keep:
             Y[-1][:, :B] = state.x[:, :B]
@@ -298,7 +291,7 @@ class _EigenRun:
 
 # ---------------------------------------------------------------------------------------------
 # torch.library custom ops diffhe::eig_solve / diffhe::eig_solve_backward: the solver and the state of the call travel as
-# integer handles, exactly as in diffhe::fe_solve (whose registries they share).
+# integer handles through the registries of diffhe.solver.
 # ---------------------------------------------------------------------------------------------
 @torch.library.custom_op("diffhe::eig_solve", mutates_args=())
 def eig_solve(kappa: torch.Tensor, x0: Optional[torch.Tensor], handle: int, batch: int, node_layout: bool,
@@ -308,11 +301,8 @@ def eig_solve(kappa: torch.Tensor, x0: Optional[torch.Tensor], handle: int, batc
     es = _SOLVERS[handle]
     run = _EigenRun(es, kappa, batch if batch >= 1 else None)
     lam, phi = run.run(kappa, x0, node_layout)
-    token = next(_TOKENS) if save else 0
-    if save:
-        _STATES[token] = run
     # fresh tensors (an op's outputs may not alias one another); with layout="node" phi is the block itself
-    return lam.to(kappa.device), phi.to(kappa.device), torch.tensor(token, dtype=torch.int64)
+    return lam.to(kappa.device), phi.to(kappa.device), _register_state(run, save)
 
 
 @eig_solve.register_fake
@@ -340,17 +330,11 @@ def _eig_solve_backward_fake(glam, token, kappa_like):
 
 
 def _setup_context(ctx, inputs, output):
-    """As `solver._fe_setup_context`: kappa, the token and a sentinel that takes the saved state along when the graph is
-    freed.  phi (and the token) are marked non-differentiable."""
-    kappa = inputs[0]
+    """Save (token, kappa) and tie the saved state of the call to them.  phi (and the token) are marked
+    non-differentiable."""
     lam, phi, token = output
     ctx.mark_non_differentiable(phi, token)
-    real = not isinstance(token, torch._subclasses.FakeTensor)
-    sentinel = (torch.empty(0),) if real else ()
-    ctx.save_for_backward(token, kappa, *sentinel)
-    if real:
-        weakref.finalize(sentinel[0], _STATES.pop, int(token), None)
-        ctx.state_guard = _StateGuard(int(token))
+    _tie_state(ctx, token, inputs[0])
 
 
 def _backward(ctx, glam, _gphi, _gtoken):

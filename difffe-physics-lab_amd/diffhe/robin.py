@@ -36,7 +36,9 @@ are pruned lacks the diagonal of a boundary face's square, which a facet mass fi
 unpruned plan tensor solves use.  The "singular system" warning of a mesh without Dirichlet nodes is not raised when some
 h_F > 0 (one device synchronisation, on such meshes only).  `validate=True` refuses negative or non-finite h (ValueError;
 one device synchronisation per call).  The solve travels through the custom ops `diffhe::robin_solve` /
-`diffhe::robin_solve_backward`, next to `diffhe::fe_solve`, which is unchanged.
+`diffhe::robin_solve_backward`, next to `diffhe::fe_solve`, which is unchanged.  Only what facet data adds is here: the
+call itself -- options, state lifetime, warnings, the adjoint and the shaping of dL/dkappa, dL/df, dL/dload, the input
+checks -- runs through the steps of diffhe.solver, and `_RobinSolve` is the general path's forward with two hooks filled.
 
 Not implemented (NotImplementedError): `dirichlet=` (per-call Dirichlet values), backward with create_graph=True, P2
 meshes, classes that combine this solver with `AnisotropicFESolver` or `ShapeDifferentiableFESolver` (conductivity
@@ -46,17 +48,15 @@ from __future__ import annotations
 
 import hashlib
 import warnings
-import weakref
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
 
 from . import _hip
-from . import solver as _solver
-from .plan import get_plan, padded_batch, _stream
-from .solver import (SolveInfo, _Call, _EllSolve, _SOLVERS, _STATES, _StateGuard, _TOKENS, _call_options, _from_node_major,
-                     _kappa_grad, _kappa_layout, _resolve_device, _state_of)
+from .plan import get_plan, _stream
+from .solver import (_Call, _EllSolve, _SOLVERS, _adjoint_grads, _begin_call, _fake_grads, _fake_solve, _like_grads,
+                     _register_state, _resolve_device, _run_call, _state_of, _tie_state)
 from .tet3d import DifferentiableFESolver3D
 
 __all__ = ("RobinFESolver",)
@@ -111,36 +111,17 @@ class _RobinSolve(_EllSolve):
     """The general path with the facet terms added to the stored operator and the right-hand side (csrc/robin.hip).
     `tab`: the plan's facet table; `h`, `u_inf`, `flux`: the call's `_Datum`s -- boundary-sized, kept for the adjoint."""
 
-    def forward(self, call: _Call, info: SolveInfo) -> torch.Tensor:
-        solver, plan, eng, B, mode = self.solver, self.plan, self.eng, call.B, call.mode
-        plan.ensure_ell()
-        Bp = self.Bp = padded_batch(B)
-        self.inv_kappa = None                   # never factored: h M_F does not scale with kappa
-        kdev, kse, ksb, Bv = eng.kappa_device(call.kappa, mode, B, Bp, em=call.kappa_em)
-        if self.h.per_sample:                   # one stored matrix per sample; a shared kappa is read with ksb = 0
-            Bv = Bp
-        vals, lift = eng.assemble(kdev, kse, ksb, Bv)
-        if call.reaction:
-            eng.add_reaction([vals], call.reaction, lattice=False)
-        rhs = self._rhs(call, lift, Bv)
-        tab, h, ui, q = self.tab, self.h, self.u_inf, self.flux
+    def _operator_form(self) -> Tuple[bool, bool]:
+        """Never factored: h M_F does not scale with kappa.  One stored matrix per sample when h differs between them."""
+        return False, self.h.per_sample
+
+    def _boundary_terms(self, vals, rhs, Bv) -> None:
+        plan, eng, tab, h, ui, q = self.plan, self.eng, self.tab, self.h, self.u_inf, self.flux
         _hip.check(eng.L.diffhe_robin_assemble(
             _hip.ptr(tab["fac"]), tab["d"], tab["n_f"], _hip.ptr(tab["area"]), _hip.ptr(tab["rows"]),
             _hip.ptr(tab["row_ptr"]), _hip.ptr(tab["ent_code"]), _hip.ptr(tab["ent_slot"]), tab["n_rows"], _hip.ptr(eng.g),
             _hip.ptr(h.dev), h.sf, h.sb, _hip.ptr(ui.dev), ui.sf, ui.sb, _hip.ptr(q.dev), q.sf, q.sb, _hip.ptr(vals),
-            _hip.ptr(rhs), plan.n, Bv, B, Bp, _stream(plan.device)), "diffhe_robin_assemble")
-        self.amg_hier = self._amg_hierarchy(vals, Bv, False) if solver.method != "ell-jacobi" else None
-        if self.amg_hier is not None:
-            info.path = "ell-amgpcg"
-            info.hierarchy, info.hierarchy_levels, info.operator_complexity, info.hierarchy_age = self.hier_info
-            x, its, bad, relres = eng.amg_pcg(self.amg_hier, rhs, Bp, Bv, self.amg)
-        else:
-            info.path = "ell-pcg"
-            x, its, bad, relres = eng.cg(vals, rhs, Bp, Bv)
-        info.iterations, info.not_converged = its, bad
-        info.max_relres = float(relres[:B].max())
-        self.vals, self.x, self.Bv = vals, x, Bv
-        return _from_node_major(eng, x, B, Bp, plan.n, call.node_major)
+            _hip.ptr(rhs), plan.n, Bv, self.call.B, self.Bp, _stream(plan.device)), "diffhe_robin_assemble")
 
     def facet_grads(self, lam: torch.Tensor, needs):
         """(dL/dh, dL/du_inf, dL/dflux), each in the shape of its input or None, from the adjoint lambda (n, Bp)."""
@@ -179,52 +160,30 @@ class _RobinSolve(_EllSolve):
 
 
 def _robin_forward(solver, kappa, f, load, h, u_inf, flux, node_major):
-    """`solver._solve_forward` for a call with facet data: always the general path, never factored.  -> (u, state)."""
+    """The forward of a call with facet data: always the general path, as `_RobinSolve`.  -> (u, state)."""
     plan = solver._plan()
     tab = plan.robin_table(solver._facet_key, solver._facets_host)
     call = _Call.of(solver, plan, kappa, f, load, node_major)
     data = [_Datum.of(t, name, tab["n_f"], call.B, node_major, plan.device)
             for t, name in ((h, "h"), (u_inf, "u_inf"), (flux, "flux"))]
-    tol, mg, amg = _call_options(chain=plan.is_chain, lattice=False, closed_boundary=plan.closed_boundary, n=plan.n,
-                                 mode=call.mode, tol_user=solver._tol_user, mg_user=solver._mg_user, mg=solver.mg,
-                                 amg=solver.amg)
-    solver.tol = tol
+    state = _begin_call(solver, plan, call, _RobinSolve)
+    state.tab, (state.h, state.u_inf, state.flux) = tab, data
     if plan.n_bc == 0 and call.reaction == 0.0 and not bool((data[0].dev > 0).any()):
         warnings.warn("diffhe: the system is singular (pure Neumann problem: no Dirichlet node, no reaction term, no "
                       "facet with h > 0); the returned values are not a solution", RuntimeWarning)
-    state = _RobinSolve(solver, plan, call, tol, mg, amg)
-    state.tab, (state.h, state.u_inf, state.flux) = tab, data
-    info = SolveInfo()
-    u = state.forward(call, info)
-    solver.last_info = info
-    if info.not_converged:
-        warnings.warn(f"diffhe: {info.not_converged} of {call.B} systems did not reach tol={solver.tol:g} "
-                      f"(max relative residual {info.max_relres:.2e}, path {info.path})", RuntimeWarning)
-    out = u if call.batched or call.B > 1 or node_major else u[0]
-    return out.to(call.out_device), state
+    return _run_call(state, call), state
 
 
 def _robin_backward(state: _RobinSolve, gbar, needs):
     """(dL/dkappa, dL/df, dL/dload, dL/dh, dL/du_inf, dL/dflux) from ONE adjoint solve, None where not needed."""
-    need_k, need_f, need_load = needs[:3]
-    call, plan = state.call, state.plan
-    g = gbar.detach().to(plan.device, torch.float64)
-    g = g.reshape(plan.n, call.B) if call.node_major else g.reshape(call.B, plan.n).contiguous()
-    lam, dk_sample, dk_elem, df, dload = state.adjoint(g, need_k, need_f, need_load)
-    grad_k = grad_f = grad_load = None
-    if need_k:
-        grad_k = _kappa_grad(call.mode, call.kappa_shape, dk_sample, dk_elem).to(call.kappa_device)
-    if need_f:
-        grad_f = (df if call.batched else df.sum(dim=0)).to(call.out_device)
-    if need_load:
-        grad_load = (dload if call.load_batched else dload.sum(dim=1 if call.node_major else 0)).to(call.out_device)
+    lam, *grads = _adjoint_grads(state, gbar, *needs[:3])
     facet = state.facet_grads(lam, needs[3:]) if any(needs[3:]) else [None, None, None]
-    return (grad_k, grad_f, grad_load, *facet)
+    return (*grads[:3], *facet)
 
 
 # ---------------------------------------------------------------------------------------------
-# torch.library custom ops diffhe::robin_solve / diffhe::robin_solve_backward: the solver and the adjoint state travel as
-# integer handles, exactly as in diffhe::fe_solve (whose registries they share).
+# torch.library custom ops diffhe::robin_solve / diffhe::robin_solve_backward, next to diffhe::fe_solve: the solver and the
+# adjoint state travel as integer handles through the registries of diffhe.solver.
 # ---------------------------------------------------------------------------------------------
 @torch.library.custom_op("diffhe::robin_solve", mutates_args=())
 def robin_solve(kappa: torch.Tensor, f: torch.Tensor, load: torch.Tensor, h: torch.Tensor, u_inf: torch.Tensor,
@@ -232,21 +191,12 @@ def robin_solve(kappa: torch.Tensor, f: torch.Tensor, load: torch.Tensor, h: tor
     """(u, token) = solve with the `RobinFESolver` registered under `handle`; arguments as diffhe::fe_solve, plus the
     facet data h, u_inf, flux in one of the layouts of the module docstring (a 0-dim zero for none)."""
     u, state = _robin_forward(_SOLVERS[handle], kappa, f, load, h, u_inf, flux, node_major)
-    token = next(_TOKENS) if save else 0
-    if save:
-        _STATES[token] = state
-    return u, torch.tensor(token, dtype=torch.int64)
+    return u, _register_state(state, save)
 
 
 @robin_solve.register_fake
 def _robin_solve_fake(kappa, f, load, h, u_inf, flux, handle, save, node_major):
-    solver = _SOLVERS[handle]
-    n, m = solver.mesh.n_nodes, solver.mesh.n_elements
-    if node_major:
-        return f.new_empty(tuple(f.shape), dtype=torch.float64), torch.empty((), dtype=torch.int64)
-    _, B, _ = _kappa_layout(kappa, m, f.shape[0] if f.dim() == 2 else None, False)
-    shape = (B, n) if (f.dim() == 2 or B > 1) else (n,)
-    return f.new_empty(shape, dtype=torch.float64), torch.empty((), dtype=torch.int64)
+    return _fake_solve(_SOLVERS[handle], kappa, f, node_major)
 
 
 _Grads6 = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]
@@ -259,29 +209,22 @@ def robin_solve_backward(gbar: torch.Tensor, token: torch.Tensor, need_k: bool, 
                          q_like: torch.Tensor) -> _Grads6:
     """The six gradients of the forward call named by `token`, each with the device and dtype of its `*_like`; unused
     ones come back empty."""
-    likes = (kappa_like, f_like, load_like, h_like, u_like, q_like)
     grads = _robin_backward(_state_of(token), gbar, (need_k, need_f, need_load, need_h, need_u, need_q))
-    return tuple(gbar.new_empty(0) if g is None else g.to(like.device, like.dtype) for g, like in zip(grads, likes))
+    return _like_grads(gbar, grads, (kappa_like, f_like, load_like, h_like, u_like, q_like))
 
 
 @robin_solve_backward.register_fake
 def _robin_solve_backward_fake(gbar, token, need_k, need_f, need_load, need_h, need_u, need_q, kappa_like, f_like,
                                load_like, h_like, u_like, q_like):
-    needs = (need_k, need_f, need_load, need_h, need_u, need_q)
-    likes = (kappa_like, f_like, load_like, h_like, u_like, q_like)
-    return tuple(torch.empty_like(like) if need else gbar.new_empty(0) for need, like in zip(needs, likes))
+    return _fake_grads(gbar, (need_k, need_f, need_load, need_h, need_u, need_q),
+                       (kappa_like, f_like, load_like, h_like, u_like, q_like))
 
 
 def _setup_context(ctx, inputs, output):
-    """As `solver._fe_setup_context`: the inputs, u when node-major (it may BE the saved iterate) and a sentinel that
-    takes the adjoint state along when the graph is freed."""
+    """Save (token, kappa, f, load, h, u_inf, flux) and u when node-major (it may BE the saved iterate), and tie the
+    adjoint state to them."""
     *tensors, _handle, _save, node_major = inputs
-    real = not isinstance(output[1], torch._subclasses.FakeTensor)
-    sentinel = (torch.empty(0),) if real else ()
-    ctx.save_for_backward(output[1], *tensors, *((output[0],) if node_major else ()), *sentinel)
-    if real:
-        weakref.finalize(sentinel[0], _STATES.pop, int(output[1]), None)
-        ctx.state_guard = _StateGuard(int(output[1]))
+    _tie_state(ctx, output[1], *tensors, *((output[0],) if node_major else ()))
 
 
 def _backward(ctx, grad_u, _grad_token):
@@ -350,42 +293,18 @@ class RobinFESolver(DifferentiableFESolver3D):
         if dirichlet is not None:
             raise NotImplementedError("diffhe: dirichlet= together with Robin / flux data is not implemented; put the "
                                       "values into the mesh")
-        if self.mesh.dim not in self._dims:
-            raise NotImplementedError("Only 1D, 2D and 3D supported")
-        if layout not in ("sample", "node"):
-            raise ValueError(f"Unknown layout: {layout!r}")
-        n, node_major = self.mesh.n_nodes, layout == "node"
         data = [None if t is None else (t if isinstance(t, torch.Tensor) else torch.as_tensor(t)) for t in (h, u_inf, flux)]
         for t, name in zip(data, ("h", "u_inf", "flux")):
             if t is not None and (t.is_complex() or t.dim() > 2):
                 raise ValueError(f"{name} must be a real tensor of at most two dimensions, got {tuple(t.shape)} {t.dtype}")
-        if node_major:
-            if f.dim() != 2 or f.shape[0] != n or (load is not None and tuple(load.shape) != tuple(f.shape)):
-                raise ValueError(f"layout='node': f (and load) must be (n, B) with n={n}, got {tuple(f.shape)}")
-            if self.mesh.dim == 1:      # the general path of a chain works sample-major: transposing views in and out
-                tr = [t.t() if t is not None and t.dim() == 2 else t for t in data]
-                return self.forward(f.t(), *tr, load=None if load is None else load.t()).t()
-            f64 = f.to(torch.float64)
-            load64 = f64.new_empty(0) if load is None else load.to(torch.float64)
-        else:
-            f64 = f.to(torch.float64)
-            if f64.dim() == 2 and f64.shape == (n, 1):
-                f64 = f64.reshape(n)
-            elif f64.dim() == 2 and f64.shape[1] != n:
-                raise ValueError(f"f must be (n,) or (B,n) with n={n}, got {tuple(f.shape)}")
-            elif f64.dim() == 1 and f64.shape[0] != n:
-                raise ValueError(f"f must have {n} nodal values, got {f64.shape[0]}")
-            if load is None:
-                load64 = f64.new_empty(0)
-            else:
-                load64 = load.to(torch.float64)
-                if load64.shape[-1] != n or load64.dim() not in (1, 2):
-                    raise ValueError(f"load must be (n,) or (B,n) with n={n}, got {tuple(load.shape)}")
-            if f64.dim() == 1:          # a (B, n) load or (B, n_F) facet data imply the batch
-                implied = [load64.shape[0]] if load64.dim() == 2 else []
-                implied += [t.shape[0] for t in data if t is not None and t.dim() == 2]
-                if implied:
-                    f64 = f64.reshape(1, n).expand(implied[0], n)
+        f64, load64, node_major, transposed = self._checked_inputs(f, load, layout, "1D, 2D and 3D")
+        if transposed:      # the general path of a chain works sample-major: transposing views in and out
+            tr = [t.t() if t is not None and t.dim() == 2 else t for t in data]
+            return self.forward(f.t(), *tr, load=None if load is None else load.t()).t()
+        if f64.dim() == 1:              # (B, n_F) facet data imply the batch, like a (B, n) load
+            implied = [t.shape[0] for t in data if t is not None and t.dim() == 2]
+            if implied:
+                f64 = f64.reshape(1, -1).expand(implied[0], -1)
         if self.validate and data[0] is not None:
             hv = data[0].detach()
             if not bool((torch.isfinite(hv) & (hv >= 0)).all()):

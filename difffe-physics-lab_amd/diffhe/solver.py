@@ -1126,15 +1126,26 @@ class _LatticeSolve(_NodeMajorSolve):
 class _EllSolve(_NodeMajorSolve):
     """General meshes: ELL operator, aggregation-multigrid PCG ("ell-amgpcg") or Jacobi PCG ("ell-pcg")."""
 
+    def _operator_form(self) -> Tuple[bool, bool]:
+        """-> (the call may keep its operator factored, it stores one matrix per sample even for a kappa the batch
+        shares).  For subclasses that add terms of their own to the operator (`_boundary_terms`)."""
+        return True, False
+
+    def _boundary_terms(self, vals, rhs, Bv) -> None:
+        """Terms a subclass adds to the stored operator `vals` (W, n, Bv) and the right-hand side `rhs` (n, Bp) in place:
+        after the assembly, the reaction term and `_rhs`, before the hierarchy is built from `vals`."""
+
     def forward(self, call: _Call, info: SolveInfo) -> torch.Tensor:
         solver, plan, eng, B, mode = self.solver, self.plan, self.eng, call.B, call.mode
         plan.ensure_ell()
         Bp = self.Bp = padded_batch(B)
+        may_factor, per_sample = self._operator_form()
         # scalar kappa per sample on a boundary closed by Dirichlet data: FACTORED like on closed lattices, ONE unit
         # matrix K_1 for the batch and K_1 x = F_b / kappa_b, its aggregation hierarchy plan-constant.  Not with a
         # reaction term, operator="assembled" or Neumann parts (DESIGN section 4, "General meshes")
-        factored = (not call.nc and mode in (K_SCALAR, K_SAMPLE) and call.reaction == 0.0 and solver.operator != "assembled"
-                    and not plan.is_p2 and solver.method != "ell-jacobi" and plan.closed_boundary_general())
+        factored = (may_factor and not call.nc and mode in (K_SCALAR, K_SAMPLE) and call.reaction == 0.0
+                    and solver.operator != "assembled" and not plan.is_p2 and solver.method != "ell-jacobi"
+                    and plan.closed_boundary_general())
         self.inv_kappa = None
         if factored:
             vals, lift = eng.assemble(torch.ones(1, dtype=torch.float64, device=plan.device), 0, 0, 1)
@@ -1150,10 +1161,13 @@ class _EllSolve(_NodeMajorSolve):
                 vals, lift = eng.assemble_tensor(kdev, ksc, kse, ksb, Bv)
             else:
                 kdev, kse, ksb, Bv = eng.kappa_device(call.kappa, mode, B, Bp, em=call.kappa_em)
+                if per_sample:      # a kappa shared by the batch is read with ksb = 0 into every sample's matrix
+                    Bv = Bp
                 vals, lift = eng.assemble(kdev, kse, ksb, Bv)
             if call.reaction:
                 eng.add_reaction([vals], call.reaction, lattice=False)
             rhs = self._rhs(call, lift, Bv)
+            self._boundary_terms(vals, rhs, Bv)
         self.amg_hier = self._amg_hierarchy(vals, Bv, factored) if solver.method != "ell-jacobi" else None
         if self.amg_hier is not None:
             info.path = "ell-amgpcg"
@@ -1229,6 +1243,31 @@ class _EllSolve(_NodeMajorSolve):
         return eng.cg(self.vals, rhs, self.Bp, self.Bv)
 
 
+def _begin_call(solver, plan: SolvePlan, call: _Call, path: Optional[type] = None) -> _PathSolve:
+    """The path object of one call, before its forward: the path class (`_select_path`, unless the caller forces one),
+    the per-call options (`_call_options`), `solver.tol`."""
+    if path is None:
+        path = _select_path(plan, solver, call.reaction)
+    tol, mg, amg = _call_options(chain=plan.is_chain, lattice=path is _LatticeSolve, closed_boundary=plan.closed_boundary,
+                                 n=plan.n, mode=call.mode, tol_user=solver._tol_user, mg_user=solver._mg_user,
+                                 mg=solver.mg, amg=solver.amg)
+    solver.tol = tol          # `solver.tol` reports the tolerance of the last call
+    return path(solver, plan, call, tol, mg, amg)
+
+
+def _run_call(state: _PathSolve, call: _Call) -> torch.Tensor:
+    """The forward solve of a call that `_begin_call` set up: u as the caller gets it (a call without a batch loses the
+    batch dimension; on f's device), the solver's `last_info`, the warning when a system missed the tolerance."""
+    solver, info = state.solver, SolveInfo()
+    u = state.forward(call, info)
+    solver.last_info = info
+    if info.not_converged:
+        warnings.warn(f"diffhe: {info.not_converged} of {call.B} systems did not reach tol={solver.tol:g} "
+                      f"(max relative residual {info.max_relres:.2e}, path {info.path})", RuntimeWarning)
+    out = u if call.batched or call.B > 1 or call.node_major else u[0]
+    return out.to(call.out_device)
+
+
 def _solve_forward(solver, kappa, f, load=None, node_major=False, dirichlet=None, shape=False):
     """u = (K(kappa) + c M_L)^{-1} (F(f) + load) with Dirichlet elimination (c = solver.reaction, 0 for the reference's
     problem).  Returns (u, state): the path object that keeps what the explicit adjoint needs.  node_major (2D paths):
@@ -1239,25 +1278,13 @@ def _solve_forward(solver, kappa, f, load=None, node_major=False, dirichlet=None
     call = _Call.of(solver, plan, kappa, f, load, node_major, dirichlet, shape)
     # a tensor coefficient (diffhe.aniso) always takes the general path, lattice meshes included (as with method="ell"):
     # the lattice fast path has no tensor assembly and no coarse re-discretisation of a tensor
-    path = _EllSolve if call.nc else _select_path(plan, solver, call.reaction)
-    tol, mg, amg = _call_options(chain=plan.is_chain, lattice=path is _LatticeSolve, closed_boundary=plan.closed_boundary,
-                                 n=plan.n, mode=call.mode, tol_user=solver._tol_user, mg_user=solver._mg_user,
-                                 mg=solver.mg, amg=solver.amg)
-    solver.tol = tol          # `solver.tol` reports the tolerance of the last call
+    state = _begin_call(solver, plan, call, _EllSolve if call.nc else None)
     if plan.n_bc == 0 and call.reaction == 0.0:
         # K is singular (constants in its null space): the reference returns garbage of size 1e15 (solver.py:174),
         # the 1D scan NaN, the iterative paths stop at the iteration cap -- either way it is said out loud
         warnings.warn("diffhe: the system is singular (pure Neumann problem: no Dirichlet node, no reaction term); "
                       "the returned values are not a solution", RuntimeWarning)
-    state = path(solver, plan, call, tol, mg, amg)
-    info = SolveInfo()
-    u = state.forward(call, info)
-    solver.last_info = info
-    if info.not_converged:
-        warnings.warn(f"diffhe: {info.not_converged} of {call.B} systems did not reach tol={solver.tol:g} "
-                      f"(max relative residual {info.max_relres:.2e}, path {info.path})", RuntimeWarning)
-    out = u if call.batched or call.B > 1 or node_major else u[0]
-    return out.to(call.out_device), state
+    return _run_call(state, call), state
 
 
 def _from_node_major(eng, x, B, Bp, n, node_major, bc=None):
@@ -1278,13 +1305,12 @@ def _from_node_major(eng, x, B, Bp, n, node_major, bc=None):
     return xo + p.g.unsqueeze(1) if p.has_dirichlet_data else xo   # zero Dirichlet data: u IS x, nothing is copied
 
 
-def _solve_backward(state: _PathSolve, gbar, need_k, need_f, need_load=False, need_g=False, need_x=False):
-    """Explicit adjoint (SURVEY Appendix A): lambda = K_free^{-1} gbar_free with the saved operators,
-    dL/dkappa = -lambda^T k0 u, dL/df = M^T lambda, dL/dload = lambda -- the path's adjoint ONCE, then what the same
-    lambda gives for a call with `dirichlet=` (diffhe.dirichlet: dL/dG and the G part of dL/dkappa) and for the node
-    coordinates (diffhe.shape), then the gradients shaped, summed over the batch where the input had none, and placed
-    like the inputs (dL/dX stays (n, dim) fp64 on the plan's device: the mesh's nodes may live elsewhere).
-    Returns (grad_kappa, grad_f, grad_load, grad_G, grad_X), None for each one not asked for."""
+def _adjoint_grads(state: _PathSolve, gbar, need_k, need_f, need_load, need_g=False):
+    """The path's adjoint ONCE for the cotangent `gbar` of u, then the gradients of the inputs every solve op has, shaped,
+    summed over the batch where the input had none, and placed like the inputs.  A call with `dirichlet=` has its band step
+    here (diffhe.dirichlet: dL/dG and the G part of dL/dkappa), between the two: it corrects the per-sample and
+    per-element dL/dkappa BEFORE they are summed into the shape of kappa.
+    Returns (lambda in the path's layout, grad_kappa, grad_f, grad_load, grad_G), None for each gradient not asked for."""
     call, plan = state.call, state.plan
     g = gbar.detach().to(plan.device, torch.float64)
     g = g.reshape(plan.n, call.B) if call.node_major else g.reshape(call.B, plan.n).contiguous()
@@ -1302,12 +1328,23 @@ def _solve_backward(state: _PathSolve, gbar, need_k, need_f, need_load=False, ne
         grad_load = (dload if call.load_batched else dload.sum(dim=1 if call.node_major else 0)).to(call.out_device)
     if need_g:      # a (n_D,) G shared by the batch receives the sum over the samples
         grad_g = dg if call.bc[0].dim() == 2 else dg.sum(dim=1 if call.node_major else 0)
-    return grad_k, grad_f, grad_load, grad_g, _shape._node_grad(state, lam) if need_x else None
+    return lam, grad_k, grad_f, grad_load, grad_g
+
+
+def _solve_backward(state: _PathSolve, gbar, need_k, need_f, need_load=False, need_g=False, need_x=False):
+    """Explicit adjoint (SURVEY Appendix A): lambda = K_free^{-1} gbar_free with the saved operators,
+    dL/dkappa = -lambda^T k0 u, dL/df = M^T lambda, dL/dload = lambda, dL/dG (`_adjoint_grads`: the path's adjoint ONCE),
+    then what the same lambda gives for the node coordinates (diffhe.shape; dL/dX stays (n, dim) fp64 on the plan's
+    device: the mesh's nodes may live elsewhere).
+    Returns (grad_kappa, grad_f, grad_load, grad_G, grad_X), None for each one not asked for."""
+    lam, *grads = _adjoint_grads(state, gbar, need_k, need_f, need_load, need_g)
+    return (*grads, _shape._node_grad(state, lam) if need_x else None)
 
 
 # ---------------------------------------------------------------------------------------------
 # torch.library custom ops: diffhe::fe_solve (forward) and diffhe::fe_solve_backward (adjoint).
-# Non-tensor context (the solver, the per-call adjoint state) travels as integer handles.
+# Non-tensor context (the solver, the per-call adjoint state) travels as integer handles.  The registries, the lifetime of
+# a saved state and the shapes the ops return are here once, for the ops of diffhe.robin and diffhe.eigen too.
 # ---------------------------------------------------------------------------------------------
 _SOLVERS: "weakref.WeakValueDictionary[int, DifferentiableFESolver]" = weakref.WeakValueDictionary()
 _STATES: Dict[int, object] = {}
@@ -1333,20 +1370,55 @@ def _state_of(token: torch.Tensor):
     return state
 
 
+def _register_state(state, save: bool) -> torch.Tensor:
+    """The token a forward op returns: it names `state` in `_STATES` until the autograd graph of the call is freed
+    (`_tie_state`: no cap on pending solves); 0, and nothing kept, when `save` is false."""
+    token = next(_TOKENS) if save else 0
+    if save:
+        _STATES[token] = state
+    return torch.tensor(token, dtype=torch.int64)
+
+
+def _tie_state(ctx, token: torch.Tensor, *saved) -> None:
+    """For a `setup_context`: save (token, *saved) for backward and tie the adjoint state that `token` names to them."""
+    real = not isinstance(token, torch._subclasses.FakeTensor)
+    # A sentinel among the saved tensors dies with them at the end of a backward that does not retain the graph and
+    # takes the adjoint state along, BEFORE the caller lets go of u: a state that overlaps the next step's forward
+    # solve costs new device allocations (DESIGN section 4, "Lifetime of the adjoint state").  It stays LAST: the
+    # backward functions read `ctx.saved_tensors[:k]`.
+    sentinel = (torch.empty(0),) if real else ()
+    ctx.save_for_backward(token, *saved, *sentinel)
+    if real:
+        weakref.finalize(sentinel[0], _STATES.pop, int(token), None)
+        ctx.state_guard = _StateGuard(int(token))           # and in any case together with the graph
+
+
+def _fake_solve(solver, kappa, f, node_major):
+    """(u, token) of a forward op's fake (meta) implementation."""
+    token = torch.empty((), dtype=torch.int64)
+    if node_major:
+        return f.new_empty(tuple(f.shape), dtype=torch.float64), token
+    n, m = solver.mesh.n_nodes, solver.mesh.n_elements
+    _, B, _ = _kappa_layout(kappa, m, f.shape[0] if f.dim() == 2 else None, False, solver._tensor_components())
+    return f.new_empty((B, n) if (f.dim() == 2 or B > 1) else (n,), dtype=torch.float64), token
+
+
+def _like_grads(gbar, grads, likes):
+    """What a backward op returns: each gradient with the device and dtype of its `*_like`, an empty tensor for None."""
+    return tuple(gbar.new_empty(0) if g is None else g.to(like.device, like.dtype) for g, like in zip(grads, likes))
+
+
+def _fake_grads(gbar, needs, likes):
+    """`_like_grads` for a backward op's fake (meta) implementation."""
+    return tuple(torch.empty_like(like) if need else gbar.new_empty(0) for need, like in zip(needs, likes))
+
+
 def _fe_setup_context(ctx, inputs, output):
     """Save (token, kappa, f, load, dirichlet | None, nodes | None) and u when node-major (it may BE the saved iterate:
     autograd then refuses a backward after an in-place edit), and tie the adjoint state to them."""
     kappa, f, load, handle, _save, node_major, dirichlet, nodes, _version = inputs
-    real = not isinstance(output[1], torch._subclasses.FakeTensor)
-    # A sentinel among the saved tensors dies with them at the end of a backward that does not retain the graph and
-    # takes the adjoint state along, BEFORE the caller lets go of u: a state that overlaps the next step's forward
-    # solve costs new device allocations (DESIGN section 4, "Lifetime of the adjoint state").
-    sentinel = (torch.empty(0),) if real else ()
-    ctx.save_for_backward(output[1], kappa, f, load, dirichlet, nodes, *((output[0],) if node_major else ()), *sentinel)
     ctx.handle, ctx.node_major = handle, bool(node_major)
-    if real:
-        weakref.finalize(sentinel[0], _STATES.pop, int(output[1]), None)
-        ctx.state_guard = _StateGuard(int(output[1]))       # and in any case together with the graph
+    _tie_state(ctx, output[1], kappa, f, load, dirichlet, nodes, *((output[0],) if node_major else ()))
 
 
 @torch.library.custom_op("diffhe::fe_solve", mutates_args=())
@@ -1363,21 +1435,12 @@ def fe_solve(kappa: torch.Tensor, f: torch.Tensor, load: torch.Tensor, handle: i
     if nodes is not None:
         _shape._check_nodes(solver.mesh, nodes, nodes_version)
     u, state = _solve_forward(solver, kappa, f, load, node_major, dirichlet, nodes is not None)
-    token = next(_TOKENS) if save else 0
-    if save:
-        _STATES[token] = state     # freed with the autograd graph of this solve (_StateGuard): no cap on pending solves
-    return u, torch.tensor(token, dtype=torch.int64)
+    return u, _register_state(state, save)
 
 
 @fe_solve.register_fake
 def _fe_solve_fake(kappa, f, load, handle, save, node_major=False, dirichlet=None, nodes=None, nodes_version=0):
-    solver = _SOLVERS[handle]
-    n, m = solver.mesh.n_nodes, solver.mesh.n_elements
-    if node_major:
-        return f.new_empty(tuple(f.shape), dtype=torch.float64), torch.empty((), dtype=torch.int64)
-    _, B, _ = _kappa_layout(kappa, m, f.shape[0] if f.dim() == 2 else None, False, solver._tensor_components())
-    shape = (B, n) if (f.dim() == 2 or B > 1) else (n,)
-    return f.new_empty(shape, dtype=torch.float64), torch.empty((), dtype=torch.int64)
+    return _fake_solve(_SOLVERS[handle], kappa, f, node_major)
 
 
 _Grads = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]
@@ -1389,16 +1452,15 @@ def fe_solve_backward(gbar: torch.Tensor, token: torch.Tensor, need_k: bool, nee
                       g_like: Optional[torch.Tensor] = None, nodes_like: Optional[torch.Tensor] = None) -> _Grads:
     """(dL/dkappa, dL/df, dL/dload, dL/dG, dL/dX) of the forward call named by `token` from ONE adjoint solve, each with
     the device and dtype of its `*_like`; unused gradients come back empty."""
-    likes = (kappa_like, f_like, load_like, g_like, nodes_like)
     grads = _solve_backward(_state_of(token), gbar, need_k, need_f, need_load, need_g, need_x)
-    return tuple(gbar.new_empty(0) if g is None else g.to(like.device, like.dtype) for g, like in zip(grads, likes))
+    return _like_grads(gbar, grads, (kappa_like, f_like, load_like, g_like, nodes_like))
 
 
 @fe_solve_backward.register_fake
 def _fe_solve_backward_fake(gbar, token, need_k, need_f, need_load, need_g, need_x, kappa_like, f_like, load_like,
                             g_like=None, nodes_like=None):
-    needs, likes = (need_k, need_f, need_load, need_g, need_x), (kappa_like, f_like, load_like, g_like, nodes_like)
-    return tuple(torch.empty_like(like) if need else gbar.new_empty(0) for need, like in zip(needs, likes))
+    return _fake_grads(gbar, (need_k, need_f, need_load, need_g, need_x),
+                       (kappa_like, f_like, load_like, g_like, nodes_like))
 
 
 def _element_forms(plan: SolvePlan):
@@ -1646,7 +1708,7 @@ class DifferentiableFESolver(nn.Module):
         self._device = device
         if os.environ.get("DIFFHE_TOL"):
             tol = float(os.environ["DIFFHE_TOL"])
-        # relative-residual stop; None = chosen per mesh at the first solve (1e-12 or 1e-13, see _solve_forward)
+        # relative-residual stop; None = chosen per mesh at the first solve (1e-12 or 1e-13, see _call_options)
         self._tol_user = tol
         self.tol, self.max_iter, self.check_every, self.assembly = tol, max_iter, check_every, assembly
         self.last_info = SolveInfo()
@@ -1717,21 +1779,35 @@ class DifferentiableFESolver(nn.Module):
         (n_D,) for the batch or (B, n_D) per sample -- (n_D,) or (n_D, B) with layout="node"; batch rules of `load`.
         The values of `mesh.dirichlet_nodes` are then not used, only its keys; the solve plan is the same, and the
         values may require grad (a shared (n_D,) tensor receives the sum over the batch).  See diffhe.dirichlet."""
+        f64, load64, node_major, transposed = self._checked_inputs(f, load, layout)
+        if transposed:      # the 1D scan works sample-major: transposing views in and out
+            g64 = None if dirichlet is None else self._dirichlet64(dirichlet, f.shape[1], True)
+            return self.forward(f.t(), None if load is None else load.t(),
+                                dirichlet=g64 if g64 is None or g64.dim() == 1 else g64.t()).t()
+        g64 = None
+        if dirichlet is not None:
+            g64 = self._dirichlet64(dirichlet, f64.shape[1 if node_major else 0] if f64.dim() == 2 else None, node_major)
+            if g64.dim() == 2 and f64.dim() == 1:                           # a (B, n_D) G implies the batch, like load
+                f64 = f64.reshape(1, -1).expand(g64.shape[0], -1)
+        return self._solve_op(f64, load64, g64, node_major)
+
+    def _checked_inputs(self, f, load, layout: str, dims: str = "1D and 2D"):
+        """f, load and layout of a `forward` call checked -> (f64, load64, node_major, transposed): float64 tensors,
+        load64 empty for no load, a (B, n) load having given its batch to an f without one.  transposed: layout="node" on
+        a 1D mesh, whose paths work sample-major -- nothing is converted, the caller calls `forward` again on transposed
+        views and transposes what comes back."""
         if self.mesh.dim not in self._dims:
-            raise NotImplementedError("Only 1D and 2D supported")       # reference solver.py:67
+            raise NotImplementedError(f"Only {dims} supported")         # reference solver.py:67
         if layout not in ("sample", "node"):
             raise ValueError(f"Unknown layout: {layout!r}")
         n = self.mesh.n_nodes
         if layout == "node":
             if f.dim() != 2 or f.shape[0] != n or (load is not None and tuple(load.shape) != tuple(f.shape)):
                 raise ValueError(f"layout='node': f (and load) must be (n, B) with n={n}, got {tuple(f.shape)}")
-            g64 = None if dirichlet is None else self._dirichlet64(dirichlet, f.shape[1], True)
-            if self.mesh.dim == 1:     # the 1D scan works sample-major: transposing views in and out
-                return self.forward(f.t(), None if load is None else load.t(),
-                                    dirichlet=g64 if g64 is None or g64.dim() == 1 else g64.t()).t()
+            if self.mesh.dim == 1:
+                return None, None, True, True
             f64 = f.to(torch.float64)
-            load64 = f64.new_empty(0) if load is None else load.to(torch.float64)
-            return self._solve_op(f64, load64, g64, True)
+            return f64, f64.new_empty(0) if load is None else load.to(torch.float64), True, False
         f64 = f.to(torch.float64)
         if f64.dim() == 2 and f64.shape == (n, 1):
             f64 = f64.reshape(n)                                          # (n,1) works in the reference too
@@ -1740,17 +1816,13 @@ class DifferentiableFESolver(nn.Module):
         elif f64.dim() == 1 and f64.shape[0] != n:
             raise ValueError(f"f must have {n} nodal values, got {f64.shape[0]}")
         if load is None:
-            load64 = f64.new_empty(0)
-        else:
-            load64 = load.to(torch.float64)
-            if load64.shape[-1] != n or load64.dim() not in (1, 2):
-                raise ValueError(f"load must be (n,) or (B,n) with n={n}, got {tuple(load.shape)}")
-            if load64.dim() == 2 and f64.dim() == 1:
-                f64 = f64.reshape(1, n).expand(load64.shape[0], n)
-        g64 = None if dirichlet is None else self._dirichlet64(dirichlet, f64.shape[0] if f64.dim() == 2 else None, False)
-        if g64 is not None and g64.dim() == 2 and f64.dim() == 1:           # a (B, n_D) G implies the batch, like load
-            f64 = f64.reshape(1, n).expand(g64.shape[0], n)
-        return self._solve_op(f64, load64, g64, False)
+            return f64, f64.new_empty(0), False, False
+        load64 = load.to(torch.float64)
+        if load64.shape[-1] != n or load64.dim() not in (1, 2):
+            raise ValueError(f"load must be (n,) or (B,n) with n={n}, got {tuple(load.shape)}")
+        if load64.dim() == 2 and f64.dim() == 1:
+            f64 = f64.reshape(1, n).expand(load64.shape[0], n)
+        return f64, load64, False, False
 
     def _dirichlet64(self, dirichlet, B: Optional[int], node_major: bool) -> torch.Tensor:
         """`dirichlet=` checked and as float64: (n_D,), or (B, n_D) / layout="node" (n_D, B) with B the batch of f (None:

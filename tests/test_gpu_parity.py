@@ -649,10 +649,25 @@ def test_empty_and_degenerate_inputs():
     assert rel_err(u2.numpy(), uo) < RTOL_U
 
 
-def test_custom_op_state_lifecycle():
+def _lifecycle_solve(kind, mesh, k, f):
+    """One call through each pair of custom ops that keeps a state for backward -> the output that carries the graph."""
+    if kind == "fe":
+        return DifferentiableFESolver(mesh, k)(f)
+    if kind == "robin":                 # Dirichlet data on the side x = 0 only: the facet terms act on the other three
+        from diffhe import RobinFESolver
+        left = {i: 0.0 for i in range(mesh.n_nodes) if float(mesh.nodes[i, 0]) == 0.0}
+        open_mesh = FEMesh(nodes=mesh.nodes, elements=mesh.elements, dirichlet_nodes=left)
+        return RobinFESolver(open_mesh, k)(f, h=torch.tensor(2.0, dtype=T64), u_inf=torch.tensor(0.5, dtype=T64))
+    from diffhe import EigenFESolver
+    return EigenFESolver(mesh, k, k=1)()[0]                     # lam; phi is not differentiable
+
+
+@pytest.mark.parametrize("kind", ["fe", "robin", "eigen"])
+def test_custom_op_state_lifecycle(kind):
     """The adjoint state lives exactly as long as the autograd graph of its solve: nothing is saved without grad,
     a plain backward frees it, retain_graph keeps it for further backward passes (the reference, being pure
-    autograd, supports that), dropped graphs do not leak, and gradcheck (many backward passes) works."""
+    autograd, supports that), dropped graphs do not leak, and gradcheck (many backward passes) works.  The same for the
+    three pairs of ops that share the registry: diffhe::fe_solve, diffhe::robin_solve, diffhe::eig_solve."""
     import gc
     from diffhe import solver as S
     mesh = FEMesh.rectangle(8, 8)
@@ -661,9 +676,9 @@ def test_custom_op_state_lifecycle():
     gc.collect()
     S._STATES.clear()
     with torch.no_grad():
-        DifferentiableFESolver(mesh, k)(f)
+        _lifecycle_solve(kind, mesh, k, f)
     assert len(S._STATES) == 0                                  # nothing saved without grad
-    u = DifferentiableFESolver(mesh, k)(f)
+    u = _lifecycle_solve(kind, mesh, k, f)
     assert len(S._STATES) == 1
     L = (u ** 2).sum()
     L.backward(retain_graph=True)
@@ -671,13 +686,18 @@ def test_custom_op_state_lifecycle():
     assert len(S._STATES) == 1                                  # graph retained: state kept
     L.backward()
     assert torch.allclose(k.grad, 2 * g1)                       # second pass accumulated the same gradient
+    assert len(S._STATES) == 0                                  # freed by the plain backward, u and L still held
+    with pytest.raises(RuntimeError):                           # ... and a further backward says so
+        L.backward()
     del u, L
     gc.collect()
     assert len(S._STATES) == 0                                  # freed with the graph
     for _ in range(10):                                         # graphs that are dropped do not leak
-        DifferentiableFESolver(mesh, k)(f)
+        _lifecycle_solve(kind, mesh, k, f)
     gc.collect()
     assert len(S._STATES) == 0
+    if kind != "fe":
+        return
     m = FEMesh.rectangle(4, 3, bc_value=0.2)
     kk = torch.tensor([0.8, 1.4], dtype=T64, requires_grad=True)
     ff = (1 + 0.1 * torch.arange(2 * m.n_nodes, dtype=T64).reshape(2, -1) / m.n_nodes).requires_grad_(True)
