@@ -9,10 +9,12 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DIFFHE_HIP_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libdiffhe_hip.so"))
 
-_P, _I, _L, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_double
+_P, _I, _L, _D = C.c_void_p, C.c_int, C.c_longlong, C.c_double     # _P: struct members (no from_param there)
 ABI_VERSION = 8     # DIFFHE_ABI_VERSION of include/diffhe_hip.h this binding was written against
 
 
@@ -34,78 +36,116 @@ class AmgLevel(C.Structure):
 
 _AV = C.POINTER(AmgLevel)
 
-# name -> (restype, argtypes); must list every symbol of include/diffhe_hip.h
+
+class _Ptr:
+    """Pointer argtype of one element type: None -> NULL, a tensor of that dtype -> its data_ptr(), a c_void_p or an
+    int address -> itself, unchecked.  Any other tensor is refused (ctypes.ArgumentError) before the call is made."""
+    dtype = None        # None: void*, any tensor
+
+    @classmethod
+    def from_param(cls, v):
+        if v is None:
+            return None
+        if type(v) is int:          # a stream or a raw address: wrapped, ctypes would pass a bare int as a C int
+            return C.c_void_p(v)
+        if isinstance(v, torch.Tensor):
+            if v.dtype is not cls.dtype and cls.dtype is not None:
+                raise TypeError(f"{v.dtype} tensor where the header declares {cls.elem}*")
+            return C.c_void_p(v.data_ptr())
+        if isinstance(v, C.c_void_p):
+            return v
+        raise TypeError(f"{type(v).__name__} where the header declares {cls.elem}*")
+
+
+def _ptr_type(elem: str, dtype) -> type:
+    return type("_Ptr_" + elem.replace(" ", "_"), (_Ptr,), {"elem": elem, "dtype": dtype})
+
+
+_PD, _PF = _ptr_type("double", torch.float64), _ptr_type("float", torch.float32)
+_PI, _PL = _ptr_type("int", torch.int32), _ptr_type("long long", torch.int64)
+_PB, _PV = _ptr_type("unsigned char", torch.uint8), _ptr_type("void", None)
+
+
+class _S:
+    """Marker restype: a C int that is a DIFFHE_OK / DIFFHE_E_* status -- `lib()` binds it as c_int with `_errcheck`."""
+
+
+# name -> (restype, argtypes); must list every symbol of include/diffhe_hip.h with the header's types
+# (tests/test_abi.py).  Plain _I where an int is a value, where the caller reads a status itself (diffhe_lattice_bilinear)
+# and on the profile / traffic accessors, whose status callers have always been free to ignore.
 SIGNATURES = {
     "diffhe_abi_version": (_I, []),
     "diffhe_status_string": (C.c_char_p, [_I]),
     "diffhe_last_hip_error": (C.c_char_p, []),
     "diffhe_traffic_account": (_I, [_I, C.POINTER(_D), C.POINTER(_L)]),
     "diffhe_chain1d_stage_doubles": (_L, [_I, _I, _I, _I]),
-    "diffhe_chain1d_solve": (_I, [_P, _P, _L, _L, _P, _L, _P, _I, _P, _P, _L, _I, _I, _I, _I, _P, _P]),
-    "diffhe_chain1d_adjoint": (_I, [_P, _P, _L, _L, _P, _L, _P, _L, _P, _I, _P, _L, _P, _L, _P, _I, _I, _I, _I, _P,
-                                    _P]),
-    "diffhe_p1_element_integrals": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
-    "diffhe_ell_assemble_rows": (_I, [_P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "diffhe_lattice_assemble_rows": (_I, [_P, _I, _P, _L, _L, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "diffhe_ell_assemble_rows_ref": (_I, [_P, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "diffhe_ell_assemble_atomic": (_I, [_P, _P, _I, _P, _L, _L, _P, _P, _I, _I, _I, _I, _P]),
-    "diffhe_ell_apply_dirichlet": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "diffhe_ell_spmv_shared": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "diffhe_chain1d_solve": (_S, [_PD, _PD, _L, _L, _PD, _L, _PI, _I, _PD, _PD, _L, _I, _I, _I, _I, _PD, _PV]),
+    "diffhe_chain1d_adjoint": (_S, [_PD, _PD, _L, _L, _PD, _L, _PD, _L, _PI, _I, _PD, _L, _PD, _L, _PD, _I, _I, _I, _I,
+                                    _PD, _PV]),
+    "diffhe_p1_element_integrals": (_S, [_PD, _PI, _I, _I, _I, _PD, _PD, _PV]),
+    "diffhe_ell_assemble_rows": (_S, [_PD, _PD, _L, _L, _PI, _PI, _PI, _PI, _PB, _PD, _PD, _PD, _I, _I, _I, _I, _PV]),
+    "diffhe_lattice_assemble_rows": (_S, [_PD, _I, _PD, _L, _L, _PB, _PD, _PD, _PD, _I, _I, _I, _I, _PV]),
+    "diffhe_ell_assemble_rows_ref": (_S, [_PD, _PD, _PD, _L, _L, _PI, _PI, _PI, _PI, _PB, _PD, _PD, _PD, _I, _I, _I, _I,
+                                          _PV]),
+    "diffhe_ell_assemble_atomic": (_S, [_PD, _PI, _I, _PD, _L, _L, _PI, _PD, _I, _I, _I, _I, _PV]),
+    "diffhe_ell_apply_dirichlet": (_S, [_PI, _PB, _PD, _PD, _PD, _I, _I, _I, _PV]),
+    "diffhe_ell_spmv_shared": (_S, [_PD, _PI, _PD, _PD, _I, _PD, _PB, _PD, _I, _I, _I, _PV]),
     "diffhe_cg_workspace_doubles": (_L, [_I, _I]),
-    "diffhe_ell_cg_solve": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P]),
-    "diffhe_ell_galerkin": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "diffhe_ell_cg_solve": (_S, [_PD, _PI, _PD, _PD, _I, _I, _I, _I, _D, _I, _I, _PD, _PD, _PI, _PI, _PV]),
+    "diffhe_ell_galerkin": (_S, [_PD, _PI, _PI, _PD, _PD, _I, _I, _I, _PV]),
     "diffhe_ell_amg_workspace_doubles": (_L, [_AV, _I, _I]),
-    "diffhe_ell_amg_pcg_solve": (_I, [_AV, _I, _I, _P, _P, _I, _D, _I, _I, _I, _D, _I, _P, _P, _P, _P, _P]),
-    "diffhe_ell_apply": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "diffhe_ell_amg_pcg_solve": (_S, [_AV, _I, _I, _PD, _PD, _I, _D, _I, _I, _I, _D, _I, _PD, _PD, _PI, _PI, _PV]),
+    "diffhe_ell_apply": (_S, [_PD, _PI, _PD, _PD, _PD, _I, _I, _I, _I, _PV]),
     "diffhe_lattice_pcg_workspace_doubles": (_L, [_LV, _I, _I]),
-    "diffhe_lattice_pcg_solve": (_I, [_LV, _I, _I, _P, _P, _P, _I, _D, _D, _I, _I, _I, C.POINTER(_D), _I, _P, _P,
-                                      _P, _P, _P, _P, _P]),
+    "diffhe_lattice_pcg_solve": (_S, [_LV, _I, _I, _PD, _PD, _PD, _I, _D, _D, _I, _I, _I, C.POINTER(_D), _I, _PD, _PD,
+                                      _PD, _PI, _PI, _PI, _PV]),
     "diffhe_lattice_pcg_profile": (_I, [_I, C.POINTER(_D), C.POINTER(_L)]),
     "diffhe_lattice_kernel_profile": (_I, [_I, C.POINTER(_D), C.POINTER(_L)]),
     "diffhe_lattice_blocks": (_I, [_I, _I]),
     "diffhe_lattice_fused_passes": (_I, []),
     "diffhe_lattice_recompute_ap": (_I, []),
-    "diffhe_lattice_apply": (_I, [_LV, _I, _P, _P, _P, _P, _I, _P]),
-    "diffhe_lattice_smooth": (_I, [_LV, _I, _P, _P, _P, _P, _D, _I, _P]),
-    "diffhe_lattice_cg_step": (_I, [_LV, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P]),
-    "diffhe_lattice_bilinear": (_I, [_LV, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
-    "diffhe_lattice_apply_shared": (_I, [_I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
-    "diffhe_lattice_restrict_kappa": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
-    "diffhe_lattice_pack_h16": (_I, [_LV, _I, _P, _P, _P, _P, _P]),
-    "diffhe_lattice_max_diag": (_I, [_LV, _I, _P, _P]),
-    "diffhe_lattice_grad_kappa": (_I, [_I, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
+    "diffhe_lattice_apply": (_S, [_LV, _I, _PD, _PD, _PD, _PD, _I, _PV]),
+    "diffhe_lattice_smooth": (_S, [_LV, _I, _PD, _PD, _PD, _PD, _D, _I, _PV]),
+    "diffhe_lattice_cg_step": (_S, [_LV, _I, _PD, _PV, _I, _PV, _PV, _PD, _PD, _PD, _I, _PD, _PD, _I, _PV]),
+    "diffhe_lattice_bilinear": (_I, [_LV, _I, _PD, _PD, _PD, _PD, _PD, _PD, _I, _PV]),
+    "diffhe_lattice_apply_shared": (_S, [_I, _I, _I, _PD, _PD, _PD, _I, _PD, _PB, _PD, _I, _PV]),
+    "diffhe_lattice_grad_kappa": (_S, [_I, _I, _PD, _I, _PD, _PD, _PD, _PD, _I, _PV]),
+    "diffhe_lattice_pack_h16": (_S, [_LV, _I, _PD, _PF, _PV, _PI, _PV]),
+    "diffhe_lattice_max_diag": (_S, [_LV, _I, _PD, _PV]),
+    "diffhe_lattice_restrict_kappa": (_S, [_PD, _PD, _I, _I, _I, _I, _I, _PV]),
     "diffhe_grad_kappa_blocks": (_I, [_I, _I]),
-    "diffhe_p1_grad_kappa": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
-    "diffhe_p1_grad_kappa_shared": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
-    "diffhe_aniso_gradient_table": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
-    "diffhe_aniso_assemble_rows": (_I, [_P, _P, _I, _P, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "diffhe_aniso_grad": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _L, _L, _P, _P, _P]),
-    "diffhe_aniso_grad_shared": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _L, _L, _P]),
-    "diffhe_p1_shape_grad": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _D, _P, _P, _P,
-                                  _P, _P]),
-    "diffhe_bc_lift": (_I, [_P, _I, _I, _P, _P, _L, _L, _P, _P, _L, _L, _P, _P, _P, _I, _P, _L, _L, _I, _P]),
-    "diffhe_bc_grad": (_I, [_P, _I, _I, _P, _P, _L, _L, _P, _P, _P, _P, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L,
-                            _L, _P, _I, _P]),
-    "diffhe_bc_scatter": (_I, [_P, _I, _P, _L, _L, _P, _L, _L, _I, _P]),
-    "diffhe_bc_grad_kappa": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _P]),
-    "diffhe_robin_facet_table": (_I, [_P, _P, _I, _I, _I, _P, _P]),
-    "diffhe_robin_assemble": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _I,
-                                   _I, _I, _I, _P]),
-    "diffhe_robin_grad": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L,
-                               _L, _P]),
+    "diffhe_p1_grad_kappa": (_S, [_PI, _PD, _PD, _PD, _PD, _I, _I, _I, _PD, _PD, _PD, _PV]),
+    "diffhe_p1_grad_kappa_shared": (_S, [_PI, _PD, _PD, _PD, _PD, _I, _I, _I, _I, _PD, _PV]),
+    "diffhe_aniso_gradient_table": (_S, [_PD, _PI, _I, _I, _I, _PD, _PD, _PV]),
+    "diffhe_aniso_assemble_rows": (_S, [_PD, _PD, _I, _PD, _L, _L, _L, _PI, _PI, _PI, _PB, _PD, _PD, _PD, _I, _I, _I,
+                                        _I, _PV]),
+    "diffhe_aniso_grad": (_S, [_PI, _PD, _PD, _I, _PD, _PD, _PD, _I, _I, _I, _PD, _L, _L, _PD, _PD, _PV]),
+    "diffhe_aniso_grad_shared": (_S, [_PI, _PD, _PD, _I, _PD, _PD, _PD, _I, _I, _I, _I, _PD, _L, _L, _PV]),
+    "diffhe_p1_shape_grad": (_S, [_PD, _PI, _I, _I, _I, _I, _PD, _PD, _PD, _L, _L, _PD, _L, _L, _PD, _L, _L, _D, _PI,
+                                  _PI, _PD, _PD, _PV]),
+    "diffhe_bc_lift": (_S, [_PI, _I, _I, _PD, _PD, _L, _L, _PI, _PD, _L, _L, _PI, _PI, _PI, _I, _PD, _L, _L, _I, _PV]),
+    "diffhe_bc_grad": (_S, [_PI, _I, _I, _PD, _PD, _L, _L, _PI, _PI, _PI, _PI, _I, _PD, _L, _L, _PD, _L, _L, _PD, _L,
+                            _L, _PD, _L, _L, _PD, _I, _PV]),
+    "diffhe_bc_scatter": (_S, [_PI, _I, _PD, _L, _L, _PD, _L, _L, _I, _PV]),
+    "diffhe_bc_grad_kappa": (_S, [_PI, _I, _I, _PD, _PI, _PI, _I, _PD, _L, _L, _PD, _L, _L, _PD, _L, _L, _I, _I, _PV]),
+    "diffhe_robin_facet_table": (_S, [_PD, _PI, _I, _I, _I, _PD, _PV]),
+    "diffhe_robin_assemble": (_S, [_PI, _I, _I, _PD, _PI, _PI, _PI, _PI, _I, _PD, _PD, _L, _L, _PD, _L, _L, _PD, _L, _L,
+                                   _PD, _PD, _I, _I, _I, _I, _PV]),
+    "diffhe_robin_grad": (_S, [_PI, _I, _I, _PD, _PD, _PD, _PD, _I, _I, _PD, _L, _L, _PD, _L, _L, _PD, _L, _L, _PD, _L,
+                               _L, _PD, _L, _L, _PV]),
     "diffhe_robin_sum_blocks": (_I, [_I]),
-    "diffhe_robin_sum_facets": (_I, [_P, _I, _I, _P, _P, _P]),
-    "diffhe_ell_sample_scales": (_I, [_P, _P, _I, _I, _P, _P, _P]),
-    "diffhe_ell_mean_operator": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "diffhe_ell_strength_filter": (_I, [_P, _P, _I, _I, _D, _P, _P, _P]),
+    "diffhe_robin_sum_facets": (_S, [_PD, _I, _I, _PD, _PD, _PV]),
+    "diffhe_ell_sample_scales": (_S, [_PD, _PB, _I, _I, _PD, _PD, _PV]),
+    "diffhe_ell_mean_operator": (_S, [_PD, _PD, _I, _I, _I, _I, _PD, _PV]),
+    "diffhe_ell_strength_filter": (_S, [_PD, _PI, _I, _I, _D, _PI, _PD, _PV]),
     "diffhe_eig_gram_blocks": (_I, [_I, _I]),
-    "diffhe_eig_gram": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
-    "diffhe_eig_ritz": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "diffhe_eig_rotate": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "diffhe_eig_residual": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "diffhe_eig_fix_sign": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
-    "diffhe_to_node_major": (_I, [_P, _L, _P, _P, _I, _I, _I, _P]),
-    "diffhe_to_sample_major": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),
+    "diffhe_eig_gram": (_S, [_PD, _PD, _PD, _PB, _I, _I, _I, _PD, _PD, _PD, _PV]),
+    "diffhe_eig_ritz": (_S, [_PD, _PD, _I, _I, _I, _PD, _PD, _PD, _PI, _PV]),
+    "diffhe_eig_rotate": (_S, [_PD, _PD, _PD, _PD, _PD, _I, _I, _I, _PD, _PD, _PD, _PD, _PV]),
+    "diffhe_eig_residual": (_S, [_PD, _PD, _PD, _I, _I, _I, _PD, _PD, _PV]),
+    "diffhe_eig_fix_sign": (_S, [_PD, _PD, _I, _I, _I, _PD, _PD, _PV]),
+    "diffhe_to_node_major": (_S, [_PD, _L, _PB, _PD, _I, _I, _I, _PV]),
+    "diffhe_to_sample_major": (_S, [_PD, _PD, _PD, _L, _I, _I, _I, _PV]),
 }
 
 _lib = None
@@ -130,11 +170,20 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
+            fn.restype, fn.argtypes = (_I if res is _S else res), args
+            if res is _S:
+                fn.errcheck = _errcheck
         if handle.diffhe_abi_version() != ABI_VERSION:
             raise HipExtensionError("libdiffhe_hip.so ABI version mismatch")
         _lib = handle
     return _lib
+
+
+def _errcheck(status, func, args):
+    """ctypes errcheck of every status entry: a failed call raises under the entry's own name."""
+    if status != 0:
+        check(status, func.__name__)
+    return status
 
 
 def check(status: int, what: str) -> None:

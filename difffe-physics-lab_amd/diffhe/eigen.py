@@ -147,8 +147,7 @@ class _EigenRun:
         f0 = torch.zeros((B, n), dtype=torch.float64, device=plan.device)
         load0 = (self.mass[:, None] * Y[-1])[:, :B].t().contiguous()
         call = _Call.of(inner, plan, kappa, f0, load0, False)
-        state = _begin_call(inner, plan, call)
-        state.eng.g = plan.zero_g()              # homogeneous Dirichlet data, whatever the mesh carries
+        state = _begin_call(inner, plan, call, homogeneous=True)
         info = SolveInfo()
         state.forward(call, info)                # no warning per inner solve: `run` reports what the iteration missed
         inner.last_info = info
@@ -168,11 +167,9 @@ class _EigenRun:
         """y = A x with the saved operator (identity on the Dirichlet rows, where x is 0)."""
         state, plan, L, st = self.state, self.plan, self.L, _stream(self.plan.device)
         if self.lattice:
-            _hip.check(L.diffhe_lattice_apply(self._lev, state.Bv, _hip.ptr(state.scale), _hip.ptr(x), _hip.ptr(y),
-                                              _hip.ptr(self._apart), self.Bp, st), "diffhe_lattice_apply")
+            L.diffhe_lattice_apply(self._lev, state.Bv, state.scale, x, y, self._apart, self.Bp, st)
             return
-        _hip.check(L.diffhe_ell_apply(_hip.ptr(state.vals), _hip.ptr(plan.cols), _hip.ptr(x), _hip.ptr(y),
-                                      _hip.ptr(self._apart), plan.n, plan.W, self.Bp, state.Bv, st), "diffhe_ell_apply")
+        L.diffhe_ell_apply(state.vals, plan.cols, x, y, self._apart, plan.n, plan.W, self.Bp, state.Bv, st)
         if self._kscale is not None:             # factored general path: A_b = kappa_b K_1
             y *= self._kscale
 
@@ -180,15 +177,10 @@ class _EigenRun:
         """Gram -> Ritz -> rotate -> residual: X, AX, R = theta M X - A X, theta, rho from the block Y and A Y."""
         L, plan, p, n, Bp, st = self.L, self.plan, self.p, self.plan.n, self.Bp, _stream(self.plan.device)
         b = self.buf
-        _hip.check(L.diffhe_eig_gram(_hip.ptr(Y), _hip.ptr(AY), _hip.ptr(self.mass), _hip.ptr(plan.is_bc), p, n, Bp,
-                                     _hip.ptr(b["part"]), _hip.ptr(b["GA"]), _hip.ptr(b["GM"]), st), "diffhe_eig_gram")
-        _hip.check(L.diffhe_eig_ritz(_hip.ptr(b["GA"]), _hip.ptr(b["GM"]), p, Bp, JACOBI_SWEEPS, _hip.ptr(b["work"]),
-                                     _hip.ptr(b["C"]), _hip.ptr(b["theta"]), _hip.ptr(b["flag"]), st), "diffhe_eig_ritz")
-        _hip.check(L.diffhe_eig_rotate(_hip.ptr(Y), _hip.ptr(AY), _hip.ptr(b["C"]), _hip.ptr(b["theta"]),
-                                       _hip.ptr(self.mass), p, n, Bp, _hip.ptr(b["X"]), _hip.ptr(b["AX"]), None,
-                                       _hip.ptr(b["R"]), st), "diffhe_eig_rotate")
-        _hip.check(L.diffhe_eig_residual(_hip.ptr(b["R"]), _hip.ptr(b["theta"]), _hip.ptr(self.mass), p, n, Bp,
-                                         _hip.ptr(b["part"]), _hip.ptr(b["rho"]), st), "diffhe_eig_residual")
+        L.diffhe_eig_gram(Y, AY, self.mass, plan.is_bc, p, n, Bp, b["part"], b["GA"], b["GM"], st)
+        L.diffhe_eig_ritz(b["GA"], b["GM"], p, Bp, JACOBI_SWEEPS, b["work"], b["C"], b["theta"], b["flag"], st)
+        L.diffhe_eig_rotate(Y, AY, b["C"], b["theta"], self.mass, p, n, Bp, b["X"], b["AX"], None, b["R"], st)
+        L.diffhe_eig_residual(b["R"], b["theta"], self.mass, p, n, Bp, b["part"], b["rho"], st)
 
     def _status(self) -> Tuple[int, int]:
         """The one host read of an outer iteration: ((sample, mode) pairs above tol, samples with a failed Gram matrix).
@@ -225,17 +217,16 @@ class _EigenRun:
         while above and info.outer_iterations < es.max_iter:
             info.outer_iterations += 1
             for i in range(p):
-                d, its, bad, _relres = state._adjoint_solve(b["R"][i], scratch)
+                res = state._adjoint_solve(b["R"][i], scratch)
                 info.inner_solves += 1
-                info.inner_iterations += int(its)
-                info.inner_not_converged += int(bad)
-                torch.add(b["X"][i], d, out=Y[i])
+                info.inner_iterations += res.iterations
+                info.inner_not_converged += res.not_converged
+                torch.add(b["X"][i], res.x, out=Y[i])
                 self._apply(Y[i], AY[i])
             self._rayleigh_ritz(Y, AY)
             above, failed = self._status()
         sgn = self._new(k, Bp)
-        _hip.check(L.diffhe_eig_fix_sign(_hip.ptr(b["X"]), _hip.ptr(self.mass), k, n, Bp, _hip.ptr(b["part"]),
-                                         _hip.ptr(sgn), _stream(plan.device)), "diffhe_eig_fix_sign")
+        L.diffhe_eig_fix_sign(b["X"], self.mass, k, n, Bp, b["part"], sgn, _stream(plan.device))
         info.not_converged, info.gram_failures = above, failed
         info.residual = b["rho"][:k, :B].t().cpu()
         es.last_info = info
@@ -253,8 +244,7 @@ class _EigenRun:
         else:
             phi = self._new(B, k, n)
             for i in range(k):      # column i of every sample into phi[:, i, :]: one transposing pass per column
-                _hip.check(L.diffhe_to_sample_major(_hip.ptr(self.X[i]), None, phi.data_ptr() + 8 * i * n, k * n, n, B, Bp,
-                                                    _stream(plan.device)), "diffhe_to_sample_major")
+                L.diffhe_to_sample_major(self.X[i], None, phi[:, i], k * n, n, B, Bp, _stream(plan.device))
             if not self.batched:
                 phi = phi[0]
         if not self.batched:

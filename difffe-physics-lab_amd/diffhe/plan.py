@@ -419,9 +419,7 @@ class LatticeLevel:
         self.cols, self.ent_ptr, self.contrib = dev(pat["cols"]), dev(pat["ent_ptr"]), dev(pat["contrib"])
         self.k0 = torch.empty((9, self.m), dtype=torch.float64, device=device)
         m0 = torch.empty((9, self.m), dtype=torch.float64, device=device)
-        _hip.check(L.diffhe_p1_element_integrals(_hip.ptr(self.coords), _hip.ptr(self.elems), 2, self.n, self.m,
-                                                 _hip.ptr(self.k0), _hip.ptr(m0), _stream(device)),
-                   "diffhe_p1_element_integrals")
+        L.diffhe_p1_element_integrals(self.coords, self.elems, 2, self.n, self.m, self.k0, m0, _stream(device))
         self._m0 = m0 if with_load_matrix else None
         flat = np.ascontiguousarray(nodes2d.reshape(self.n, 2).T)
         ref = host_arrays(f"refint_{nx}x{ny}_{hashlib.blake2b(flat.tobytes(), digest_size=8).hexdigest()}",
@@ -441,10 +439,8 @@ class LatticeLevel:
         if with_load_matrix:
             all4 = dev(np.array([0, 1, 2, 3, -1, -1, -1], dtype=np.int32))
             self.Mvals = torch.empty((4, self.n), dtype=torch.float64, device=device)
-            _hip.check(L.diffhe_ell_assemble_rows(_hip.ptr(self._m0), None, 0, 0, _hip.ptr(self.ent_ptr),
-                                                  _hip.ptr(self.contrib), _hip.ptr(self.cols), _hip.ptr(all4), None,
-                                                  None, _hip.ptr(self.Mvals), None, self.n, self.m, 7, 1,
-                                                  _stream(device)), "diffhe_ell_assemble_rows(M, lattice)")
+            L.diffhe_ell_assemble_rows(self._m0, None, 0, 0, self.ent_ptr, self.contrib, self.cols, all4, None, None,
+                                       self.Mvals, None, self.n, self.m, 7, 1, _stream(device))
             self._m0 = None
 
     def lumped_mass(self) -> torch.Tensor:
@@ -773,9 +769,7 @@ class SolvePlan:
             dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)  # noqa: E731
             fac = dev(facets.T)
             area = torch.empty(nF, dtype=torch.float64, device=self.device)
-            _hip.check(_hip.lib().diffhe_robin_facet_table(_hip.ptr(self.coords), _hip.ptr(fac), d, self.n, nF,
-                                                           _hip.ptr(area), _stream(self.device)),
-                       "diffhe_robin_facet_table")
+            _hip.lib().diffhe_robin_facet_table(self.coords, fac, d, self.n, nF, area, _stream(self.device))
             cache[key] = dict(d=d, n_f=nF, fac=fac, area=area, rows=dev(rows), n_rows=len(rows), row_ptr=dev(row_ptr),
                               ent_code=dev((F * 16 + p * 4 + c)[order]), ent_slot=dev(slot[order]))
             return cache[key]
@@ -815,9 +809,7 @@ class SolvePlan:
         else:
             self.k0 = torch.empty((nloc, self.m), dtype=torch.float64, device=device)
             self.m0 = torch.empty((nloc, self.m), dtype=torch.float64, device=device)
-            _hip.check(L.diffhe_p1_element_integrals(_hip.ptr(self.coords), _hip.ptr(self.elems), self.dim, self.n,
-                                                     self.m, _hip.ptr(self.k0), _hip.ptr(self.m0), stream),
-                       "diffhe_p1_element_integrals")
+            L.diffhe_p1_element_integrals(self.coords, self.elems, self.dim, self.n, self.m, self.k0, self.m0, stream)
             self.tnum, self.den = dev(tn), dev(dn)       # reference-order assembly
         # load matrix M (batch-shared ELL values): F = M f, df = M^T lambda.  Its own pattern where the stiffness pattern
         # was pruned: m0 = V/16 couples every pair of a tetrahedron's vertices.  M is applied twice per fwd + adjoint step
@@ -830,10 +822,8 @@ class SolvePlan:
             self.MW, self.Mcols = mpat["W"], dev(mpat["cols"])
             m_ent_ptr, m_contrib = dev(mpat["ent_ptr"]), dev(mpat["contrib"])
         self.Mvals = torch.empty((self.MW, self.n), dtype=torch.float64, device=device)
-        _hip.check(L.diffhe_ell_assemble_rows(_hip.ptr(self.m0), None, 0, 0, _hip.ptr(m_ent_ptr),
-                                              _hip.ptr(m_contrib), _hip.ptr(self.Mcols), None, None, None,
-                                              _hip.ptr(self.Mvals), None, self.n, self.m, self.MW, 1, stream),
-                   "diffhe_ell_assemble_rows(M)")
+        L.diffhe_ell_assemble_rows(self.m0, None, 0, 0, m_ent_ptr, m_contrib, self.Mcols, None, None, None, self.Mvals,
+                                   None, self.n, self.m, self.MW, 1, stream)
         self._ell_ready = True
 
     def gradient_table(self):
@@ -846,9 +836,8 @@ class SolvePlan:
                 if cached is None:
                     gtab = torch.empty((self.npe * self.dim, self.m), dtype=torch.float64, device=self.device)
                     vol = torch.empty(self.m, dtype=torch.float64, device=self.device)
-                    _hip.check(_hip.lib().diffhe_aniso_gradient_table(_hip.ptr(self.coords), _hip.ptr(self.elems), self.dim,
-                                                                      self.n, self.m, _hip.ptr(gtab), _hip.ptr(vol),
-                                                                      _stream(self.device)), "diffhe_aniso_gradient_table")
+                    _hip.lib().diffhe_aniso_gradient_table(self.coords, self.elems, self.dim, self.n, self.m, gtab, vol,
+                                                           _stream(self.device))
                     cached = self.__dict__["_gradient_table"] = (gtab, vol)
         return cached
 
@@ -944,15 +933,11 @@ class SolvePlan:
         one = torch.ones(1, dtype=torch.float64, device=self.device)
         st = _stream(self.device)
         if self.is_p2:
-            _hip.check(L.diffhe_ell_assemble_rows(_hip.ptr(self.k0), _hip.ptr(one), 0, 0, _hip.ptr(self.ent_ptr),
-                                                  _hip.ptr(self.contrib), _hip.ptr(self.cols), None, _hip.ptr(self.is_bc),
-                                                  _hip.ptr(self.g), _hip.ptr(vals), _hip.ptr(lift), self.n, self.m, self.W, 1,
-                                                  st), "diffhe_ell_assemble_rows(unit)")
+            L.diffhe_ell_assemble_rows(self.k0, one, 0, 0, self.ent_ptr, self.contrib, self.cols, None, self.is_bc,
+                                       self.g, vals, lift, self.n, self.m, self.W, 1, st)
         else:
-            _hip.check(L.diffhe_ell_assemble_rows_ref(_hip.ptr(self.tnum), _hip.ptr(self.den), _hip.ptr(one), 0, 0,
-                                                      _hip.ptr(self.ent_ptr), _hip.ptr(self.contrib), _hip.ptr(self.cols), None,
-                                                      _hip.ptr(self.is_bc), _hip.ptr(self.g), _hip.ptr(vals), _hip.ptr(lift),
-                                                      self.n, self.m, self.W, 1, st), "diffhe_ell_assemble_rows_ref(unit)")
+            L.diffhe_ell_assemble_rows_ref(self.tnum, self.den, one, 0, 0, self.ent_ptr, self.contrib, self.cols, None,
+                                           self.is_bc, self.g, vals, lift, self.n, self.m, self.W, 1, st)
         return vals.reshape(self.W, self.n).cpu().numpy()
 
 

@@ -53,7 +53,6 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _hip
 from .plan import get_plan, _stream
 from .solver import (_Call, _EllSolve, _SOLVERS, _adjoint_grads, _begin_call, _fake_grads, _fake_solve, _like_grads,
                      _register_state, _resolve_device, _run_call, _state_of, _tie_state)
@@ -117,11 +116,10 @@ class _RobinSolve(_EllSolve):
 
     def _boundary_terms(self, vals, rhs, Bv) -> None:
         plan, eng, tab, h, ui, q = self.plan, self.eng, self.tab, self.h, self.u_inf, self.flux
-        _hip.check(eng.L.diffhe_robin_assemble(
-            _hip.ptr(tab["fac"]), tab["d"], tab["n_f"], _hip.ptr(tab["area"]), _hip.ptr(tab["rows"]),
-            _hip.ptr(tab["row_ptr"]), _hip.ptr(tab["ent_code"]), _hip.ptr(tab["ent_slot"]), tab["n_rows"], _hip.ptr(eng.g),
-            _hip.ptr(h.dev), h.sf, h.sb, _hip.ptr(ui.dev), ui.sf, ui.sb, _hip.ptr(q.dev), q.sf, q.sb, _hip.ptr(vals),
-            _hip.ptr(rhs), plan.n, Bv, self.call.B, self.Bp, _stream(plan.device)), "diffhe_robin_assemble")
+        eng.L.diffhe_robin_assemble(tab["fac"], tab["d"], tab["n_f"], tab["area"], tab["rows"], tab["row_ptr"],
+                                    tab["ent_code"], tab["ent_slot"], tab["n_rows"], eng.g, h.dev, h.sf, h.sb, ui.dev,
+                                    ui.sf, ui.sb, q.dev, q.sf, q.sb, vals, rhs, plan.n, Bv, self.call.B, self.Bp,
+                                    _stream(plan.device))
 
     def facet_grads(self, lam: torch.Tensor, needs):
         """(dL/dh, dL/du_inf, dL/dflux), each in the shape of its input or None, from the adjoint lambda (n, Bp)."""
@@ -136,24 +134,21 @@ class _RobinSolve(_EllSolve):
             elif dat.kind == BOTH:
                 o = new(n_f, B) if node_major else new(B, n_f)
                 outs.append(o)
-                args += [_hip.ptr(o), *((B, 1) if node_major else (1, n_f))]
+                args += [o, *((B, 1) if node_major else (1, n_f))]
             elif dat.kind == FACET:             # summed over the batch inside the kernel
                 outs.append(new(n_f))
-                args += [_hip.ptr(outs[-1]), 1, 0]
+                args += [outs[-1], 1, 0]
             else:                               # per facet and sample, then summed over the facets in two stages
                 outs.append(new(n_f, B))
-                args += [_hip.ptr(outs[-1]), B, 1]
+                args += [outs[-1], B, 1]
         h, ui = self.h, self.u_inf
-        _hip.check(eng.L.diffhe_robin_grad(_hip.ptr(tab["fac"]), tab["d"], n_f, _hip.ptr(tab["area"]), _hip.ptr(lam),
-                                           _hip.ptr(self.x), _hip.ptr(eng.g), B, Bp, _hip.ptr(h.dev), h.sf, h.sb,
-                                           _hip.ptr(ui.dev), ui.sf, ui.sb, *args, _stream(plan.device)),
-                   "diffhe_robin_grad")
+        eng.L.diffhe_robin_grad(tab["fac"], tab["d"], n_f, tab["area"], lam, self.x, eng.g, B, Bp, h.dev, h.sf, h.sb,
+                                ui.dev, ui.sf, ui.sb, *args, _stream(plan.device))
         grads = []
         for o, dat in zip(outs, (self.h, self.u_inf, self.flux)):
             if o is not None and dat.kind in (SCALAR, SAMPLE):
                 part, tot = new(eng.L.diffhe_robin_sum_blocks(n_f), B), new(B)
-                _hip.check(eng.L.diffhe_robin_sum_facets(_hip.ptr(o), n_f, B, _hip.ptr(part), _hip.ptr(tot),
-                                                         _stream(plan.device)), "diffhe_robin_sum_facets")
+                eng.L.diffhe_robin_sum_facets(o, n_f, B, part, tot, _stream(plan.device))
                 o = tot.sum() if dat.kind == SCALAR else tot
             grads.append(None if o is None else o.reshape(dat.shape))
         return grads

@@ -61,10 +61,8 @@ def _node_grad(state, lam: torch.Tensor) -> torch.Tensor:
     fdev, fsn, fsb = state.call.f_s
     work = torch.empty((m, (dim + 1) * dim), dtype=torch.float64, device=plan.device)
     grad = torch.empty((n, dim), dtype=torch.float64, device=plan.device)
-    _hip.check(L.diffhe_p1_shape_grad(_hip.ptr(plan.coords), _hip.ptr(plan.elems), dim, n, m, B, _hip.ptr(u),
-                                      _hip.ptr(g), _hip.ptr(lam), sn, sb, _hip.ptr(kdev), kse, ksb, _hip.ptr(fdev),
-                                      fsn, fsb, float(state.call.reaction), _hip.ptr(inc_ptr), _hip.ptr(inc),
-                                      _hip.ptr(work), _hip.ptr(grad), _stream(plan.device)), "diffhe_p1_shape_grad")
+    L.diffhe_p1_shape_grad(plan.coords, plan.elems, dim, n, m, B, u, g, lam, sn, sb, kdev, kse, ksb, fdev, fsn, fsb,
+                           float(state.call.reaction), inc_ptr, inc, work, grad, _stream(plan.device))
     return grad
 
 

@@ -23,7 +23,7 @@ import threading
 import warnings
 import weakref
 from dataclasses import dataclass, replace
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -120,14 +120,28 @@ def _tensor_mode(kappa: torch.Tensor, nc: int, m: int, B: Optional[int], node_ma
                      + (f", or ({nc}, {m}, B) with layout='node'" if node_major else ""))
 
 
-class _Engine:
-    """Thin, stateless driver of the C ABI for one plan and one batch geometry."""
+class _Solved(NamedTuple):
+    """What one iterative solve of `_Engine` hands back."""
+    x: torch.Tensor                         # (n, Bp)
+    iterations: int
+    not_converged: int                      # samples that missed the tolerance
+    relres: torch.Tensor                    # (Bp,) true relative residual per sample
+    est: Optional[torch.Tensor] = None      # lattice path: (Bp,) estimated relative energy-norm error
+    rule: Optional[torch.Tensor] = None     # lattice path: (Bp,) int32, the rule that stopped each sample
+    flags: int = 0                          # lattice path: the `precond_fp32` word handed to diffhe_lattice_pcg_solve
 
-    def __init__(self, plan: SolvePlan, tol: float, max_iter: int, check_every: int, assembly: str):
+
+class _Engine:
+    """Thin, stateless driver of the C ABI for one plan and one batch geometry: nothing is assigned after construction.
+    ref_order: per-sample lattice matrices in the reference's exact operation order (operator="assembled").
+    g: the (n,) Dirichlet data the kernels read -- the plan's (None), or zeros when the data comes per call."""
+
+    def __init__(self, plan: SolvePlan, tol: float, max_iter: int, check_every: int, assembly: str, *,
+                 ref_order: bool = False, g: Optional[torch.Tensor] = None):
         self.p = plan
         self.tol, self.max_iter, self.check_every, self.assembly = tol, max_iter, check_every, assembly
-        self.ref_order = False      # per-sample lattice matrices in the reference's exact operation order (operator="assembled")
-        self.g = plan.g             # the (n,) Dirichlet data the kernels read: the plan's, or zeros when it comes per call
+        self.ref_order = ref_order
+        self.g = plan.g if g is None else g
         self.L = _hip.lib()
 
     # -- layout helpers -----------------------------------------------------------------
@@ -136,15 +150,13 @@ class _Engine:
         p = self.p
         dst = torch.empty((n, Bp), dtype=torch.float64, device=p.device)
         ld = 0 if src.dim() == 1 else src.stride(0)
-        _hip.check(self.L.diffhe_to_node_major(_hip.ptr(src), ld, _hip.ptr(zero_mask), _hip.ptr(dst), n, B, Bp,
-                                               _stream(p.device)), "diffhe_to_node_major")
+        self.L.diffhe_to_node_major(src, ld, zero_mask, dst, n, B, Bp, _stream(p.device))
         return dst
 
     def to_sample_major(self, src, B, Bp, n, add=None):
         p = self.p
         dst = torch.empty((B, n), dtype=torch.float64, device=p.device)
-        _hip.check(self.L.diffhe_to_sample_major(_hip.ptr(src), _hip.ptr(add), _hip.ptr(dst), n, n, B, Bp,
-                                                 _stream(p.device)), "diffhe_to_sample_major")
+        self.L.diffhe_to_sample_major(src, add, dst, n, n, B, Bp, _stream(p.device))
         return dst
 
     def kappa_device(self, kappa, mode, B, Bp, em=False):
@@ -179,26 +191,19 @@ class _Engine:
         lift = torch.empty((p.n, Bv), dtype=torch.float64, device=p.device)
         if p.is_p2:
             # quadratic triangles (ours; no reference operator to be bit-identical with): kappa * k0, gathered
-            _hip.check(L.diffhe_ell_assemble_rows(_hip.ptr(p.k0), _hip.ptr(kdev), kse, ksb, _hip.ptr(p.ent_ptr),
-                                                  _hip.ptr(p.contrib), _hip.ptr(p.cols), None, _hip.ptr(p.is_bc),
-                                                  _hip.ptr(self.g), _hip.ptr(vals), _hip.ptr(lift), p.n, p.m, p.W, Bv, st),
-                       "diffhe_ell_assemble_rows(P2)")
+            L.diffhe_ell_assemble_rows(p.k0, kdev, kse, ksb, p.ent_ptr, p.contrib, p.cols, None, p.is_bc, self.g, vals,
+                                       lift, p.n, p.m, p.W, Bv, st)
         elif self.assembly == "atomic" and Bv > 1:
             vals.zero_()
-            _hip.check(L.diffhe_ell_assemble_atomic(_hip.ptr(p.coords), _hip.ptr(p.elems), p.dim, _hip.ptr(kdev), kse,
-                                                    ksb, _hip.ptr(p.slot_of), _hip.ptr(vals), p.n, p.m, p.W, Bv, st),
-                       "diffhe_ell_assemble_atomic")
+            L.diffhe_ell_assemble_atomic(p.coords, p.elems, p.dim, kdev, kse, ksb, p.slot_of, vals, p.n, p.m, p.W, Bv,
+                                         st)
             lift.zero_()  # apply_dirichlet returns F - lift: feed F = 0, negate
-            _hip.check(L.diffhe_ell_apply_dirichlet(_hip.ptr(p.cols), _hip.ptr(p.is_bc), _hip.ptr(self.g),
-                                                    _hip.ptr(vals), _hip.ptr(lift), p.n, p.W, Bv, st),
-                       "diffhe_ell_apply_dirichlet")
+            L.diffhe_ell_apply_dirichlet(p.cols, p.is_bc, self.g, vals, lift, p.n, p.W, Bv, st)
             lift.neg_()
         else:
             # reference operation order: values bit-identical to the reference's K (include/diffhe_hip.h)
-            _hip.check(L.diffhe_ell_assemble_rows_ref(_hip.ptr(p.tnum), _hip.ptr(p.den), _hip.ptr(kdev), kse, ksb,
-                                                      _hip.ptr(p.ent_ptr), _hip.ptr(p.contrib), _hip.ptr(p.cols), None,
-                                                      _hip.ptr(p.is_bc), _hip.ptr(self.g), _hip.ptr(vals), _hip.ptr(lift),
-                                                      p.n, p.m, p.W, Bv, st), "diffhe_ell_assemble_rows_ref")
+            L.diffhe_ell_assemble_rows_ref(p.tnum, p.den, kdev, kse, ksb, p.ent_ptr, p.contrib, p.cols, None, p.is_bc,
+                                           self.g, vals, lift, p.n, p.m, p.W, Bv, st)
         return vals, lift
 
     def tensor_device(self, kappa, mode, B, Bp, nc, em=False):
@@ -236,10 +241,8 @@ class _Engine:
         gtab, vol = p.gradient_table()
         vals = torch.empty((p.W, p.n, Bv), dtype=torch.float64, device=p.device)
         lift = torch.empty((p.n, Bv), dtype=torch.float64, device=p.device)
-        _hip.check(self.L.diffhe_aniso_assemble_rows(_hip.ptr(gtab), _hip.ptr(vol), p.dim, _hip.ptr(kdev), ksc, kse, ksb,
-                                                     _hip.ptr(p.ent_ptr), _hip.ptr(p.contrib), _hip.ptr(p.cols),
-                                                     _hip.ptr(p.is_bc), _hip.ptr(self.g), _hip.ptr(vals), _hip.ptr(lift),
-                                                     p.n, p.m, p.W, Bv, _stream(p.device)), "diffhe_aniso_assemble_rows")
+        self.L.diffhe_aniso_assemble_rows(gtab, vol, p.dim, kdev, ksc, kse, ksb, p.ent_ptr, p.contrib, p.cols, p.is_bc,
+                                          self.g, vals, lift, p.n, p.m, p.W, Bv, _stream(p.device))
         return vals, lift
 
     def grad_tensor(self, lam, x, B, Bp, nc, mode, em):
@@ -252,9 +255,7 @@ class _Engine:
         new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=p.device)  # noqa: E731
         if mode == K_ELEM:
             dk = new(p.m, nc)
-            _hip.check(L.diffhe_aniso_grad_shared(_hip.ptr(p.elems), _hip.ptr(gtab), _hip.ptr(vol), p.dim, _hip.ptr(lam),
-                                                  _hip.ptr(x), _hip.ptr(self.g), p.n, p.m, B, Bp, _hip.ptr(dk), 1, nc, st),
-                       "diffhe_aniso_grad_shared")
+            L.diffhe_aniso_grad_shared(p.elems, gtab, vol, p.dim, lam, x, self.g, p.n, p.m, B, Bp, dk, 1, nc, st)
             return dk
         dk_e = part = dk_sum = None
         osc = ose = 0
@@ -264,9 +265,7 @@ class _Engine:
             dk_e, osc, ose = new(nc, p.m, Bp), p.m * Bp, Bp
         else:
             dk_e, osc, ose = new(p.m * nc, Bp), Bp, nc * Bp
-        _hip.check(L.diffhe_aniso_grad(_hip.ptr(p.elems), _hip.ptr(gtab), _hip.ptr(vol), p.dim, _hip.ptr(lam), _hip.ptr(x),
-                                       _hip.ptr(self.g), p.n, p.m, Bp, _hip.ptr(dk_e), osc, ose, _hip.ptr(part),
-                                       _hip.ptr(dk_sum), st), "diffhe_aniso_grad")
+        L.diffhe_aniso_grad(p.elems, gtab, vol, p.dim, lam, x, self.g, p.n, p.m, Bp, dk_e, osc, ose, part, dk_sum, st)
         if mode == K_SCALAR:
             return dk_sum[:, :B].sum(dim=1)
         if mode == K_SAMPLE:
@@ -302,31 +301,34 @@ class _Engine:
         lift None: dL/df = M^T lambda, M symmetric)."""
         p = self.p
         F = torch.empty((p.n, Bp), dtype=torch.float64, device=p.device)
-        is_bc = _hip.ptr(p.is_bc) if free_rows else None
+        is_bc = p.is_bc if free_rows else None
         if lattice:   # load matrix stored as symmetric diagonals of level 0: no ELL pattern needed
             lev = p.levels[0]
-            _hip.check(self.L.diffhe_lattice_apply_shared(lev.nx, lev.ny, 4, _hip.ptr(lev.Mvals), _hip.ptr(f_nm),
-                                                          _hip.ptr(lift), Bv, _hip.ptr(lift_scale), is_bc,
-                                                          _hip.ptr(F), Bp, _stream(p.device)),
-                       "diffhe_lattice_apply_shared")
+            self.L.diffhe_lattice_apply_shared(lev.nx, lev.ny, 4, lev.Mvals, f_nm, lift, Bv, lift_scale, is_bc, F, Bp,
+                                               _stream(p.device))
             return F
-        _hip.check(self.L.diffhe_ell_spmv_shared(_hip.ptr(p.Mvals), _hip.ptr(p.Mcols), _hip.ptr(f_nm), _hip.ptr(lift),
-                                                 Bv, _hip.ptr(lift_scale), is_bc, _hip.ptr(F), p.n, p.MW,
-                                                 Bp, _stream(p.device)), "diffhe_ell_spmv_shared")
+        self.L.diffhe_ell_spmv_shared(p.Mvals, p.Mcols, f_nm, lift, Bv, lift_scale, is_bc, F, p.n, p.MW, Bp,
+                                      _stream(p.device))
         return F
 
-    def cg(self, vals, rhs, Bp, Bv):
-        p, L = self.p, self.L
-        x = torch.empty((p.n, Bp), dtype=torch.float64, device=p.device)
-        work = torch.empty(L.diffhe_cg_workspace_doubles(p.n, Bp), dtype=torch.float64, device=p.device)
+    def _solve(self, Bp, launch, x=None, **lattice) -> _Solved:
+        """The part the three iterative solves share: x (n, Bp) unless the caller brings a start, the per-sample outputs,
+        `launch(x, relres, iters, status)`, then the counts the entry left in this thread's pinned status buffer."""
+        p = self.p
+        if x is None:
+            x = torch.empty((p.n, Bp), dtype=torch.float64, device=p.device)
         relres = torch.empty(Bp, dtype=torch.float64, device=p.device)
         iters = torch.empty(Bp, dtype=torch.int32, device=p.device)
         st = status_buffer()
-        _hip.check(L.diffhe_ell_cg_solve(_hip.ptr(vals), _hip.ptr(p.cols), _hip.ptr(rhs), _hip.ptr(x), p.n, p.W, Bp,
-                                         Bv, self.tol, self.max_iter, self.check_every, _hip.ptr(work),
-                                         _hip.ptr(relres), _hip.ptr(iters), _hip.ptr(st),
-                                         _stream(p.device)), "diffhe_ell_cg_solve")
-        return x, int(st[0]), int(st[1]), relres
+        launch(x, relres, iters, st)
+        return _Solved(x, int(st[0]), int(st[1]), relres, **lattice)
+
+    def cg(self, vals, rhs, Bp, Bv) -> _Solved:
+        p, L = self.p, self.L
+        work = torch.empty(L.diffhe_cg_workspace_doubles(p.n, Bp), dtype=torch.float64, device=p.device)
+        return self._solve(Bp, lambda x, relres, iters, st: L.diffhe_ell_cg_solve(
+            vals, p.cols, rhs, x, p.n, p.W, Bp, Bv, self.tol, self.max_iter, self.check_every, work, relres, iters, st,
+            _stream(p.device)))
 
     # -- lattice path -----------------------------------------------------------------------
     def lattice_assemble(self, kappa, mode, B, Bp, factor=True, n_levels=None, em=False):
@@ -355,9 +357,7 @@ class _Engine:
             if li > 0 and mode in (K_ELEM, K_SAMPLE_ELEM):   # coarse kappa = mean of the 4 children
                 kc = torch.empty((lev.m, Bv), dtype=torch.float64, device=p.device)
                 prev = p.levels[li - 1]
-                _hip.check(L.diffhe_lattice_restrict_kappa(_hip.ptr(kl), _hip.ptr(kc), lev.nx, lev.ny,
-                                                           prev.nx // lev.nx, prev.ny // lev.ny, Bv, st),
-                           "diffhe_lattice_restrict_kappa")
+                L.diffhe_lattice_restrict_kappa(kl, kc, lev.nx, lev.ny, prev.nx // lev.nx, prev.ny // lev.ny, Bv, st)
                 kl = kc
             v = torch.empty((lev.nd, lev.n, Bv), dtype=torch.float64, device=p.device)
             lf = torch.empty((lev.n, Bv), dtype=torch.float64, device=p.device) if li == 0 else None
@@ -372,11 +372,8 @@ class _Engine:
                 # operator="assembled" keep the bit-identical order below
                 self._lattice_rows(lev, "k0ref", kl, kse, ksb, self.g, v, lf, Bv, st)
             elif li == 0 and kl is not None:   # the operator the solution is defined by: reference operation order
-                _hip.check(L.diffhe_ell_assemble_rows_ref(_hip.ptr(lev.tnum), _hip.ptr(lev.den), _hip.ptr(kl), kse, ksb,
-                                                          _hip.ptr(lev.ent_ptr), _hip.ptr(lev.contrib),
-                                                          _hip.ptr(lev.cols), _hip.ptr(lev.store_slot),
-                                                          _hip.ptr(lev.is_bc), _hip.ptr(self.g), _hip.ptr(v), _hip.ptr(lf),
-                                                          lev.n, lev.m, 7, Bv, st), "diffhe_ell_assemble_rows_ref(lattice)")
+                L.diffhe_ell_assemble_rows_ref(lev.tnum, lev.den, kl, kse, ksb, lev.ent_ptr, lev.contrib, lev.cols,
+                                               lev.store_slot, lev.is_bc, self.g, v, lf, lev.n, lev.m, 7, Bv, st)
             else:
                 self._lattice_rows(lev, "k0", kl, kse, ksb, self.g if li == 0 else lev.zero_g(), v, lf, Bv, st)
             vals.append(v)
@@ -392,10 +389,8 @@ class _Engine:
         local = lev.k0 if which == "k0" else lev.k0ref()
         # congruent triangles (bit for bit): one (9, 2) table instead of the (9, m) array -- same values
         small = lev.compact(which)
-        _hip.check(L.diffhe_lattice_assemble_rows(_hip.ptr(small if small is not None else local),
-                                                  1 if small is not None else 0, _hip.ptr(kl), kse, ksb,
-                                                  _hip.ptr(lev.is_bc), _hip.ptr(g), _hip.ptr(v), _hip.ptr(lf), lev.nx,
-                                                  lev.ny, lev.nd, Bv, st), "diffhe_lattice_assemble_rows")
+        L.diffhe_lattice_assemble_rows(small if small is not None else local, 1 if small is not None else 0, kl, kse, ksb,
+                                       lev.is_bc, g, v, lf, lev.nx, lev.ny, lev.nd, Bv, st)
 
     def pack_cycle_coeffs(self, vals, Bv):
         """Per-sample matrices, fp32-stored V-cycle: (fp32 diagonals, fp16 off-diagonals, per-sample scales) per level --
@@ -411,7 +406,7 @@ class _Engine:
         lev0[0].nx, lev0[0].ny, lev0[0].nd = p.levels[0].nx, p.levels[0].ny, p.levels[0].nd
         lev0[0].vals, lev0[0].is_bc = vals[0].data_ptr(), p.levels[0].is_bc.data_ptr()
         dmax = torch.empty(Bv, dtype=torch.float64, device=p.device)
-        _hip.check(L.diffhe_lattice_max_diag(lev0, Bv, _hip.ptr(dmax), st), "diffhe_lattice_max_diag")
+        L.diffhe_lattice_max_diag(lev0, Bv, dmax, st)
         # power of two >= dmax (exact: frexp); samples without a positive finite diagonal (padding is kappa = 1) get 1
         mant, expo = torch.frexp(dmax)
         scales = torch.ldexp(torch.ones_like(dmax), expo - (mant == 0.5).to(expo.dtype))
@@ -424,8 +419,7 @@ class _Engine:
             one[0].nx, one[0].ny, one[0].nd, one[0].vals = lev.nx, lev.ny, lev.nd, v.data_ptr()
             d = torch.empty((lev.n, Bv), dtype=torch.float32, device=p.device)
             o = torch.empty((lev.nd - 1, lev.n, Bv), dtype=torch.float16, device=p.device)
-            _hip.check(L.diffhe_lattice_pack_h16(one, Bv, _hip.ptr(scales), _hip.ptr(d), _hip.ptr(o), _hip.ptr(flags), st),
-                       "diffhe_lattice_pack_h16")
+            L.diffhe_lattice_pack_h16(one, Bv, scales, d, o, flags, st)
             d32.append(d)
             o16.append(o)
         if not bool(ok.all()) or int(flags[0]) != 0:
@@ -458,34 +452,24 @@ class _Engine:
         arr = self.lattice_levels(vals, vals32, dense, shift, rdiag32, off16)
         nl = len(arr)
         warm = x0 is not None and x0.shape == (p.n, Bp)
-        x = x0.clone() if warm else torch.empty((p.n, Bp), dtype=torch.float64, device=p.device)
         work = torch.empty(L.diffhe_lattice_pcg_workspace_doubles(arr, nl, Bp), dtype=torch.float64, device=p.device)
-        relres = torch.empty(Bp, dtype=torch.float64, device=p.device)
-        iters = torch.empty(Bp, dtype=torch.int32, device=p.device)
         # per-sweep Jacobi damping: Chebyshev weights for the interval [0.5, 2] of D^-1 A when nu == 2
         omegas = mg.get("omegas") or ([0.56, 1.39] if mg["nu"] == 2 else [mg["omega"]] * mg["nu"])
         om = (ctypes.c_double * len(omegas))(*omegas)
-        # a multigrid-preconditioned CG that has not converged in a few hundred iterations never will:
-        # bound the loop so a defect surfaces as `not_converged` instead of minutes of GPU time
         est = torch.empty(Bp, dtype=torch.float64, device=p.device)
         rule = torch.empty(Bp, dtype=torch.int32, device=p.device)
-        st = status_buffer()
         flags = (int(mg.get("fp32", 0)) | (int(mg.get("fmg", 0)) << 1) | ((int(mg.get("fmg_cycles", 1)) - 1) << 2)
                  | ((0 if int(mg.get("floor", 1)) else 1) << 4) | (32 if warm else 0)
                  | (0 if int(mg.get("fused", 1)) else 64) | (0 if int(mg.get("dense_mfma", 1)) else 128)
                  | (0 if int(mg.get("pre4", 1)) else 512)
                  | (256 if (p.closed_boundary and p.regular_cells and p.dense_level() is not None
                             and int(mg.get("cg_fp32_steplength", 1))) else 0))
-        self.last_flags = flags
-        _hip.check(L.diffhe_lattice_pcg_solve(arr, nl, Bv, _hip.ptr(scale), _hip.ptr(rhs), _hip.ptr(x), Bp, self.tol,
-                                              float(mg.get("tol_energy", 0.0) or 0.0),
-                                              min(self.max_iter, 500), len(omegas), mg["n_coarse"], om, flags,
-                                              _hip.ptr(work),
-                                              _hip.ptr(relres), _hip.ptr(est), _hip.ptr(iters), _hip.ptr(rule),
-                                              _hip.ptr(st), _stream(p.device)), "diffhe_lattice_pcg_solve")
-        self.last_est = est
-        self.last_rule = rule
-        return x, int(st[0]), int(st[1]), relres
+        # a multigrid-preconditioned CG that has not converged in a few hundred iterations never will:
+        # bound the loop so a defect surfaces as `not_converged` instead of minutes of GPU time
+        return self._solve(Bp, lambda x, relres, iters, st: L.diffhe_lattice_pcg_solve(
+            arr, nl, Bv, scale, rhs, x, Bp, self.tol, float(mg.get("tol_energy", 0.0) or 0.0), min(self.max_iter, 500),
+            len(omegas), mg["n_coarse"], om, flags, work, relres, est, iters, rule, st, _stream(p.device)),
+            x=x0.clone() if warm else None, est=est, rule=rule, flags=flags)
 
     # -- general path with the aggregation-multigrid preconditioner ---------------------------------
     def amg_setup(self, vals, Bv, fp32=True, levels=None, dense_coarse=False):
@@ -498,9 +482,8 @@ class _Engine:
         chain = [dict(n=p.n, W=p.W, vals=vals, cols=p.cols)]
         for lv in (levels if levels is not None else p.amg_levels):
             vc = torch.empty((lv["W"], lv["n"], Bv), dtype=torch.float64, device=p.device)
-            _hip.check(L.diffhe_ell_galerkin(_hip.ptr(chain[-1]["vals"]), _hip.ptr(lv["ent_ptr"]), _hip.ptr(lv["contrib"]),
-                                             _hip.ptr(lv.get("weights")), _hip.ptr(vc), lv["n"], lv["W"], Bv, st),
-                       "diffhe_ell_galerkin")
+            L.diffhe_ell_galerkin(chain[-1]["vals"], lv["ent_ptr"], lv["contrib"], lv.get("weights"), vc, lv["n"],
+                                  lv["W"], Bv, st)
             chain[-1].update(agg=lv["agg"], agg_ptr=lv["agg_ptr"], agg_members=lv["agg_members"],
                              agg_weights=lv.get("agg_weights"), p_cols=lv.get("p_cols"), p_vals=lv.get("p_vals"))
             if "lam_parent" in lv:
@@ -543,12 +526,10 @@ class _Engine:
         nblk = (p.n + _hip.ELL_SCALE_CHUNK - 1) // _hip.ELL_SCALE_CHUNK
         part = torch.empty((nblk, Bv), dtype=torch.float64, device=p.device)
         sums = torch.empty(Bv, dtype=torch.float64, device=p.device)
-        _hip.check(L.diffhe_ell_sample_scales(_hip.ptr(vals), _hip.ptr(p.is_bc), p.n, Bv, _hip.ptr(part), _hip.ptr(sums),
-                                              st), "diffhe_ell_sample_scales")
+        L.diffhe_ell_sample_scales(vals, p.is_bc, p.n, Bv, part, sums, st)
         weight = (max(p.n - p.n_bc, 1) / sums).contiguous()          # 1 / s_b
         abar = torch.empty((p.W, p.n), dtype=torch.float64, device=p.device)
-        _hip.check(L.diffhe_ell_mean_operator(_hip.ptr(vals), _hip.ptr(weight), p.n, p.W, Bv, Br, _hip.ptr(abar), st),
-                   "diffhe_ell_mean_operator")
+        L.diffhe_ell_mean_operator(vals, weight, p.n, p.W, Bv, Br, abar, st)
         return abar
 
     def strength_filter(self, abar, theta):
@@ -556,9 +537,7 @@ class _Engine:
         p = self.p
         strong = torch.empty((p.W, p.n), dtype=torch.int32, device=p.device)
         filt = torch.empty((p.W, p.n), dtype=torch.float64, device=p.device)
-        _hip.check(self.L.diffhe_ell_strength_filter(_hip.ptr(abar), _hip.ptr(p.cols), p.n, p.W, float(theta),
-                                                     _hip.ptr(strong), _hip.ptr(filt), _stream(p.device)),
-                   "diffhe_ell_strength_filter")
+        self.L.diffhe_ell_strength_filter(abar, p.cols, p.n, p.W, float(theta), strong, filt, _stream(p.device))
         return strong, filt
 
     def operator_levels(self, vals, Bv, B, theta):
@@ -574,24 +553,16 @@ class _Engine:
                                   fine_filter=(strong.cpu().numpy(), filt.cpu().numpy()))
         return [p.upload_amg_level(lv, True) for lv in host], hierarchy_stats(cols, host)
 
-    def amg_pcg(self, amg, rhs, Bp, Bv, opts):
+    def amg_pcg(self, amg, rhs, Bp, Bv, opts) -> _Solved:
         p, L = self.p, self.L
         arr, chain = amg
         nl = len(chain)
-        x = torch.empty((p.n, Bp), dtype=torch.float64, device=p.device)
         work = torch.empty(L.diffhe_ell_amg_workspace_doubles(arr, nl, Bp), dtype=torch.float64, device=p.device)
-        relres = torch.empty(Bp, dtype=torch.float64, device=p.device)
-        iters = torch.empty(Bp, dtype=torch.int32, device=p.device)
-        st = status_buffer()
-        _hip.check(L.diffhe_ell_amg_pcg_solve(arr, nl, Bv, _hip.ptr(rhs), _hip.ptr(x), Bp, self.tol,
-                                              min(self.max_iter, int(opts.get("max_iter", 20000))), int(opts["n_coarse"]),
-                                              int(opts["gamma"]),
-                                              float(opts["scale"]),
-                                              int(opts.get("fp32", 0)) | ((0 if int(opts.get("floor", 1)) else 1) << 4),
-                                              _hip.ptr(work),
-                                              _hip.ptr(relres), _hip.ptr(iters),
-                                              _hip.ptr(st), _stream(p.device)), "diffhe_ell_amg_pcg_solve")
-        return x, int(st[0]), int(st[1]), relres
+        return self._solve(Bp, lambda x, relres, iters, st: L.diffhe_ell_amg_pcg_solve(
+            arr, nl, Bv, rhs, x, Bp, self.tol, min(self.max_iter, int(opts.get("max_iter", 20000))), int(opts["n_coarse"]),
+            int(opts["gamma"]), float(opts["scale"]),
+            int(opts.get("fp32", 0)) | ((0 if int(opts.get("floor", 1)) else 1) << 4), work, relres, iters, st,
+            _stream(p.device)))
 
     def grad_kappa_factored(self, vals, lift, lam, x, Bp):
         """dL/dkappa_b = -lam^T K_1 u for a batch-shared (factored) lattice operator in one strip pass:
@@ -600,8 +571,8 @@ class _Engine:
         arr = self.lattice_levels(vals[:1])
         part = torch.empty(L.diffhe_lattice_blocks(p.n, Bp) * Bp, dtype=torch.float64, device=p.device)
         out = torch.empty(Bp, dtype=torch.float64, device=p.device)
-        rc = L.diffhe_lattice_bilinear(arr, 1, None, _hip.ptr(x), _hip.ptr(lam), _hip.ptr(lift), _hip.ptr(part),
-                                       _hip.ptr(out), Bp, _stream(p.device))
+        # bound as a plain int, not a checked status: DIFFHE_E_TOOBIG (-3) is an answer here, every other code an error
+        rc = L.diffhe_lattice_bilinear(arr, 1, None, x, lam, lift, part, out, Bp, _stream(p.device))
         if rc == -3:
             return None
         _hip.check(rc, "diffhe_lattice_bilinear")
@@ -614,18 +585,15 @@ class _Engine:
             lev = p.levels[0]
             dk_e = torch.empty((p.m, Bp), dtype=torch.float64, device=p.device)
             small = lev.compact("k0")
-            _hip.check(L.diffhe_lattice_grad_kappa(lev.nx, lev.ny, _hip.ptr(small if small is not None else lev.k0),
-                                                   1 if small is not None else 0, _hip.ptr(lam), _hip.ptr(x), _hip.ptr(self.g),
-                                                   _hip.ptr(dk_e), Bp, _stream(p.device)), "diffhe_lattice_grad_kappa")
+            L.diffhe_lattice_grad_kappa(lev.nx, lev.ny, small if small is not None else lev.k0,
+                                        1 if small is not None else 0, lam, x, self.g, dk_e, Bp, _stream(p.device))
             return dk_e, None
         nblk = L.diffhe_grad_kappa_blocks(p.m, Bp)
         dk_e = torch.empty((p.m, Bp), dtype=torch.float64, device=p.device) if want_elem else None
         part = torch.empty((nblk, Bp), dtype=torch.float64, device=p.device)
         dk_sum = torch.empty(Bp, dtype=torch.float64, device=p.device)
         k0 = p.k0 if p._ell_ready else p.levels[0].k0      # lattice meshes keep k0 on level 0
-        _hip.check(L.diffhe_p1_grad_kappa(_hip.ptr(p.elems), _hip.ptr(k0), _hip.ptr(lam), _hip.ptr(x), _hip.ptr(self.g),
-                                          p.npe, p.m, Bp, _hip.ptr(dk_e), _hip.ptr(part), _hip.ptr(dk_sum),
-                                          _stream(p.device)), "diffhe_p1_grad_kappa")
+        L.diffhe_p1_grad_kappa(p.elems, k0, lam, x, self.g, p.npe, p.m, Bp, dk_e, part, dk_sum, _stream(p.device))
         return dk_e, dk_sum
 
     def grad_kappa_shared(self, lam, x, B, Bp):
@@ -634,9 +602,7 @@ class _Engine:
         p, L = self.p, self.L
         dk = torch.empty(p.m, dtype=torch.float64, device=p.device)
         k0 = p.k0 if p._ell_ready else p.levels[0].k0
-        _hip.check(L.diffhe_p1_grad_kappa_shared(_hip.ptr(p.elems), _hip.ptr(k0), _hip.ptr(lam), _hip.ptr(x),
-                                                 _hip.ptr(self.g), p.npe, p.m, B, Bp, _hip.ptr(dk), _stream(p.device)),
-                   "diffhe_p1_grad_kappa_shared")
+        L.diffhe_p1_grad_kappa_shared(p.elems, k0, lam, x, self.g, p.npe, p.m, B, Bp, dk, _stream(p.device))
         return dk
 
     # -- per-call Dirichlet data (csrc/bc.hip): boundary band only ------------------------------------------
@@ -644,38 +610,33 @@ class _Engine:
         """rhs_b -= K_b[F, D] G_b on the free rows with a Dirichlet neighbour; rhs (i, b) at i*rsn + b*rsb."""
         p, band = self.p, self.p.dirichlet_band()
         (kdev, kse, ksb), (gdev, gsj, gsb) = kappa_s, G
-        _hip.check(self.L.diffhe_bc_lift(_hip.ptr(p.elems), p.npe, p.m, _hip.ptr(p.element_stiffness()), _hip.ptr(kdev),
-                                         kse, ksb, _hip.ptr(band["d_slot"]), _hip.ptr(gdev), gsj, gsb,
-                                         _hip.ptr(band["rows"]), _hip.ptr(band["row_ptr"]), _hip.ptr(band["row_inc"]),
-                                         band["n_rows"], _hip.ptr(rhs), rsn, rsb, B, _stream(p.device)), "diffhe_bc_lift")
+        self.L.diffhe_bc_lift(p.elems, p.npe, p.m, p.element_stiffness(), kdev, kse, ksb, band["d_slot"], gdev, gsj,
+                              gsb, band["rows"], band["row_ptr"], band["row_inc"], band["n_rows"], rhs, rsn, rsb, B,
+                              _stream(p.device))
 
     def bc_scatter(self, G, u, usn, usb, B):
         """u_b[j] = G_b[j] on the Dirichlet rows; u (i, b) at i*usn + b*usb."""
         p, band = self.p, self.p.dirichlet_band()
         gdev, gsj, gsb = G
-        _hip.check(self.L.diffhe_bc_scatter(_hip.ptr(band["d_idx"]), band["n_d"], _hip.ptr(gdev), gsj, gsb, _hip.ptr(u),
-                                            usn, usb, B, _stream(p.device)), "diffhe_bc_scatter")
+        self.L.diffhe_bc_scatter(band["d_idx"], band["n_d"], gdev, gsj, gsb, u, usn, usb, B, _stream(p.device))
 
     def bc_grad(self, kappa_s, lam, lsn, lsb, gbar, gsn, gsb, out, osj, osb, G=None, dots=None, B=1):
         """out_b[j] = gbar_b[j] - (K_b lam_b)_j on the Dirichlet nodes (dL/dG_b); dots (n_D, B): G_b[j] (K_1 lam_b)_j."""
         p, band = self.p, self.p.dirichlet_band()
         kdev, kse, ksb = kappa_s
         gdev, Gsj, Gsb = G if G is not None else (None, 0, 0)
-        _hip.check(self.L.diffhe_bc_grad(_hip.ptr(p.elems), p.npe, p.m, _hip.ptr(p.element_stiffness()), _hip.ptr(kdev),
-                                         kse, ksb, _hip.ptr(band["d_slot"]), _hip.ptr(band["d_idx"]),
-                                         _hip.ptr(band["d_ptr"]), _hip.ptr(band["d_inc"]), band["n_d"], _hip.ptr(lam),
-                                         lsn, lsb, _hip.ptr(gbar), gsn, gsb, _hip.ptr(out), osj, osb, _hip.ptr(gdev),
-                                         Gsj, Gsb, _hip.ptr(dots), B, _stream(p.device)), "diffhe_bc_grad")
+        self.L.diffhe_bc_grad(p.elems, p.npe, p.m, p.element_stiffness(), kdev, kse, ksb, band["d_slot"], band["d_idx"],
+                              band["d_ptr"], band["d_inc"], band["n_d"], lam, lsn, lsb, gbar, gsn, gsb, out, osj, osb,
+                              gdev, Gsj, Gsb, dots, B, _stream(p.device))
 
     def bc_grad_kappa(self, lam, lsn, lsb, G, dk, dse, dsb, shared, B):
         """dk (e, b) at e*dse + b*dsb -= lam_b^T k0_e G_b on the elements that touch a Dirichlet node (shared: dk (e) at
         e*dse, minus the sum over the batch)."""
         p, band = self.p, self.p.dirichlet_band()
         gdev, gsj, gsb = G
-        _hip.check(self.L.diffhe_bc_grad_kappa(_hip.ptr(p.elems), p.npe, p.m, _hip.ptr(p.element_stiffness()),
-                                               _hip.ptr(band["d_slot"]), _hip.ptr(band["band_elems"]), band["n_be"],
-                                               _hip.ptr(lam), lsn, lsb, _hip.ptr(gdev), gsj, gsb, _hip.ptr(dk), dse, dsb,
-                                               int(shared), B, _stream(p.device)), "diffhe_bc_grad_kappa")
+        self.L.diffhe_bc_grad_kappa(p.elems, p.npe, p.m, p.element_stiffness(), band["d_slot"], band["band_elems"],
+                                    band["n_be"], lam, lsn, lsb, gdev, gsj, gsb, dk, dse, dsb, int(shared), B,
+                                    _stream(p.device))
 
 
 def _precision_text(flags: int, coeff_storage: str, Bv: int, Bp: int, fused_lib: int, recompute_ap: bool) -> str:
@@ -888,12 +849,12 @@ class _PathSolve:
     adjoint(g, need_k, need_f, need_load) -> (lambda in the path's layout, per-sample dL/dkappa sums, per-element
     dL/dkappa as `_kappa_grad` takes them, dL/df and dL/dload per sample in the caller's layout)."""
 
-    def __init__(self, solver, plan: SolvePlan, call: _Call, tol: float, mg: dict, amg: dict):
+    def __init__(self, solver, plan: SolvePlan, call: _Call, tol: float, mg: dict, amg: dict, homogeneous: bool = False):
         self.solver, self.plan, self.call, self.mg, self.amg = solver, plan, call.facts(), mg, amg
-        self.eng = _Engine(plan, tol, solver.max_iter, solver.check_every, solver.assembly)
-        self.eng.ref_order = solver.operator == "assembled"
-        if call.bc is not None:     # per-call Dirichlet data: the path solves with homogeneous data, csrc/bc.hip adds G
-            self.eng.g = plan.zero_g()
+        # per-call Dirichlet data: the path solves with homogeneous data, csrc/bc.hip adds G
+        zero_g = homogeneous or call.bc is not None
+        self.eng = _Engine(plan, tol, solver.max_iter, solver.check_every, solver.assembly,
+                           ref_order=solver.operator == "assembled", g=plan.zero_g() if zero_g else None)
 
 
 class _ChainSolve(_PathSolve):
@@ -920,10 +881,9 @@ class _ChainSolve(_PathSolve):
         info.path = "chain1d-scan-ref" if self.chain_flags else "chain1d-scan"
         ns = L.diffhe_chain1d_stage_doubles(n, B, plan.max_seg_len, self.chain_flags)   # 0: every segment in registers
         stage = torch.empty(ns, dtype=torch.float64, device=plan.device) if ns > 0 else None
-        _hip.check(L.diffhe_chain1d_solve(_hip.ptr(plan.x), _hip.ptr(self.kdev), self.ksb, self.kse, _hip.ptr(f_dev),
-                                          n if batched else 0, _hip.ptr(plan.seg), plan.n_seg, _hip.ptr(self.eng.g),
-                                          _hip.ptr(self.u), n, n, B, plan.max_seg_len, self.chain_flags, _hip.ptr(stage),
-                                          _stream(plan.device)), "diffhe_chain1d_solve")
+        L.diffhe_chain1d_solve(plan.x, self.kdev, self.ksb, self.kse, f_dev, n if batched else 0, plan.seg, plan.n_seg,
+                               self.eng.g, self.u, n, n, B, plan.max_seg_len, self.chain_flags, stage,
+                               _stream(plan.device))
         if call.bc is not None:     # u keeps G in its Dirichlet rows: the adjoint's dL/dkappa reads u as it is
             self.eng.bc_scatter(call.bc, self.u, 1, n, B)
         return self.u
@@ -937,11 +897,8 @@ class _ChainSolve(_PathSolve):
         part = torch.empty((B, plan.n_seg), dtype=torch.float64, device=plan.device)
         ns = L.diffhe_chain1d_stage_doubles(n, B, plan.max_seg_len, self.chain_flags)
         stage = torch.empty(ns, dtype=torch.float64, device=plan.device) if ns > 0 else None
-        _hip.check(L.diffhe_chain1d_adjoint(_hip.ptr(plan.x), _hip.ptr(self.kdev), self.ksb, self.kse, _hip.ptr(g), n,
-                                            _hip.ptr(self.u), n, _hip.ptr(plan.seg), plan.n_seg, _hip.ptr(df), n,
-                                            _hip.ptr(dk_e), m, _hip.ptr(part), n, B, plan.max_seg_len,
-                                            self.chain_flags, _hip.ptr(stage), _stream(plan.device)),
-                   "diffhe_chain1d_adjoint")
+        L.diffhe_chain1d_adjoint(plan.x, self.kdev, self.ksb, self.kse, g, n, self.u, n, plan.seg, plan.n_seg, df, n,
+                                 dk_e, m, part, n, B, plan.max_seg_len, self.chain_flags, stage, _stream(plan.device))
         dk_sample = part.sum(dim=1)                      # (B,) tiny host-side glue
         # the chain's extra load went in as forcing: dL/dload = df / lumped mass
         return df, dk_sample, dk_e, df, df / plan.lumped_mass() if need_load else None
@@ -994,7 +951,7 @@ class _NodeMajorSolve(_PathSolve):
         """lambda = A^-1 g on the free rows with the forward's operators and preconditioner, then the gradient pieces."""
         eng, call, B, Bp, n = self.eng, self.call, self.call.B, self.Bp, self.plan.n
         info = self.solver.last_info
-        lam, its, bad, relres = self._adjoint_solve(self._adjoint_rhs(g), info)
+        lam, its, bad, relres, *_ = self._adjoint_solve(self._adjoint_rhs(g), info)
         info.adj_iterations = its
         info.adj_max_relres = float(relres[:B].max())
         info.not_converged += bad
@@ -1061,23 +1018,24 @@ class _LatticeSolve(_NodeMajorSolve):
                 self.mg = dict(self.mg, fp32=0)        # the direct product runs in fp64
             self.dense = plan.dense_coarse(didx, vals, bool(self.mg.get("fp32")))
         self.wkey = (Bp, mode, reaction)
-        x, its, bad, relres = eng.lattice_pcg(vals, Bv, scale, rhs, Bp, self.mg, self.vals32, self.dense,
-                                              x0=plan.warm_get(("u",) + self.wkey) if solver.warm_start else None,
-                                              shift=self.shift, rdiag32=self.rdiag32, off16=self.off16)
+        x, its, bad, relres, est, rule, flags = eng.lattice_pcg(
+            vals, Bv, scale, rhs, Bp, self.mg, self.vals32, self.dense,
+            x0=plan.warm_get(("u",) + self.wkey) if solver.warm_start else None, shift=self.shift, rdiag32=self.rdiag32,
+            off16=self.off16)
         if solver.warm_start and not bad:
             # the next solve starts from a copy; but with layout='node' and no padding the caller's u IS x: keep a
             # private copy then, an in-place edit of u must not move the next warm start
             shares = call.node_major and Bp == B and not plan.has_dirichlet_data and call.bc is None
             plan.warm_put(("u",) + self.wkey, x.clone() if shares else x)
-        info.stop_rules = _rule_counts(eng.last_rule, B) if not self.direct else {}
-        info.flags = eng.last_flags
-        info.precision = _precision_text(eng.last_flags, info.coeff_storage, Bv, Bp, int(eng.L.diffhe_lattice_fused_passes()),
+        info.stop_rules = _rule_counts(rule, B) if not self.direct else {}
+        info.flags = flags
+        info.precision = _precision_text(flags, info.coeff_storage, Bv, Bp, int(eng.L.diffhe_lattice_fused_passes()),
                                          bool(eng.L.diffhe_lattice_recompute_ap()))
         info.tol_energy = float(self.mg.get("tol_energy", 0.0) or 0.0)
         info.factored = bool(factored)
         info.iterations, info.not_converged = its, bad
         info.max_relres = float(relres[:B].max())
-        info.err_est = float(eng.last_est[:B].max())
+        info.err_est = float(est[:B].max())
         self.vals, self.x, self.Bv, self.scale = vals, x, Bv, scale
         self.lift = lift if Bv == 1 else None
         return _from_node_major(eng, x, B, Bp, plan.n, call.node_major, call.bc)
@@ -1101,14 +1059,14 @@ class _LatticeSolve(_NodeMajorSolve):
     def _adjoint_solve(self, rhs, info):
         plan, eng, B = self.plan, self.eng, self.call.B
         ws = self.solver.warm_start is True
-        lam, its, bad, relres = eng.lattice_pcg(self.vals, self.Bv, self.scale, rhs, self.Bp, self.mg, self.vals32,
-                                                self.dense, x0=plan.warm_get(("lambda",) + self.wkey) if ws else None,
-                                                shift=self.shift, rdiag32=self.rdiag32, off16=self.off16)
-        if ws and not bad:
-            plan.warm_put(("lambda",) + self.wkey, lam)
-        info.adj_stop_rules = _rule_counts(eng.last_rule, B) if not self.direct else {}
-        info.adj_err_est = float(eng.last_est[:B].max())
-        return lam, its, bad, relres
+        res = eng.lattice_pcg(self.vals, self.Bv, self.scale, rhs, self.Bp, self.mg, self.vals32, self.dense,
+                              x0=plan.warm_get(("lambda",) + self.wkey) if ws else None, shift=self.shift,
+                              rdiag32=self.rdiag32, off16=self.off16)
+        if ws and not res.not_converged:
+            plan.warm_put(("lambda",) + self.wkey, res.x)
+        info.adj_stop_rules = _rule_counts(res.rule, B) if not self.direct else {}
+        info.adj_err_est = float(res.est[:B].max())
+        return res
 
     def _grad_kappa(self, lam):
         """Scalar kappa per sample or for all with ONE stored matrix: dL/dkappa_b in one strip pass, above the strip
@@ -1172,10 +1130,10 @@ class _EllSolve(_NodeMajorSolve):
         if self.amg_hier is not None:
             info.path = "ell-amgpcg"
             info.hierarchy, info.hierarchy_levels, info.operator_complexity, info.hierarchy_age = self.hier_info
-            x, its, bad, relres = eng.amg_pcg(self.amg_hier, rhs, Bp, Bv, self.amg)
+            x, its, bad, relres, *_ = eng.amg_pcg(self.amg_hier, rhs, Bp, Bv, self.amg)
         else:
             info.path = "ell-pcg"
-            x, its, bad, relres = eng.cg(vals, rhs, Bp, Bv)
+            x, its, bad, relres, *_ = eng.cg(vals, rhs, Bp, Bv)
         info.iterations, info.not_converged = its, bad
         info.max_relres = float(relres[:B].max())
         info.factored = bool(factored)
@@ -1243,16 +1201,18 @@ class _EllSolve(_NodeMajorSolve):
         return eng.cg(self.vals, rhs, self.Bp, self.Bv)
 
 
-def _begin_call(solver, plan: SolvePlan, call: _Call, path: Optional[type] = None) -> _PathSolve:
+def _begin_call(solver, plan: SolvePlan, call: _Call, path: Optional[type] = None,
+                homogeneous: bool = False) -> _PathSolve:
     """The path object of one call, before its forward: the path class (`_select_path`, unless the caller forces one),
-    the per-call options (`_call_options`), `solver.tol`."""
+    the per-call options (`_call_options`), `solver.tol`.  homogeneous: solve with zero Dirichlet data, whatever the mesh
+    carries."""
     if path is None:
         path = _select_path(plan, solver, call.reaction)
     tol, mg, amg = _call_options(chain=plan.is_chain, lattice=path is _LatticeSolve, closed_boundary=plan.closed_boundary,
                                  n=plan.n, mode=call.mode, tol_user=solver._tol_user, mg_user=solver._mg_user,
                                  mg=solver.mg, amg=solver.amg)
     solver.tol = tol          # `solver.tol` reports the tolerance of the last call
-    return path(solver, plan, call, tol, mg, amg)
+    return path(solver, plan, call, tol, mg, amg, homogeneous)
 
 
 def _run_call(state: _PathSolve, call: _Call) -> torch.Tensor:

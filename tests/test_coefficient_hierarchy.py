@@ -232,8 +232,7 @@ def test_abi_lists_the_coarsening_entries():
     import re
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "diffhe_hip.h")).read()
     for name in ("diffhe_ell_sample_scales", "diffhe_ell_mean_operator", "diffhe_ell_strength_filter"):
-        decl = re.search(r"int %s\(([^;]*)\);" % name, header)
-        assert decl is not None and len(decl.group(1).split(",")) == len(_hip.SIGNATURES[name][1]), name
+        assert name in _hip.SIGNATURES      # their signatures: tests/test_abi.py, with every other entry's
     assert int(re.search(r"#define\s+DIFFHE_ELL_SCALE_CHUNK\s+(\d+)", header).group(1)) == _hip.ELL_SCALE_CHUNK
 
 

@@ -98,11 +98,8 @@ def test_abi_lists_the_dirichlet_entries():
     src = open(HEADER).read()
     m = re.search(r"#define\s+DIFFHE_ABI_VERSION\s+(\d+)", src)
     assert m and int(m.group(1)) == _hip.ABI_VERSION
-    for name in BC_ENTRIES:
+    for name in BC_ENTRIES:     # their signatures: tests/test_abi.py, with every other entry's
         assert name in _hip.SIGNATURES
-        decl = re.search(r"int %s\(([^;]*)\);" % name, src)
-        assert decl is not None, name
-        assert len(decl.group(1).split(",")) == len(_hip.SIGNATURES[name][1]), name
 
 
 def test_dirichlet_index_and_values_are_in_ascending_node_order():

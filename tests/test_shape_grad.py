@@ -131,12 +131,12 @@ def test_shape_grad_entry_in_header_and_binding():
     args = _header_args("diffhe_p1_shape_grad")
     res, argtypes = _hip.SIGNATURES["diffhe_p1_shape_grad"]
     assert len(args) == len(argtypes) == 23
-    kind = {"int": _hip._I, "long long": _hip._L, "double": _hip._D}
+    kind = {"int": _hip._I, "long long": _hip._L, "double": _hip._D,
+            "double*": _hip._PD, "int*": _hip._PI, "void*": _hip._PV}
     for a, t in zip(args, argtypes):
         decl = a.rsplit(" ", 1)[0].replace("const ", "").strip()
-        expect = _hip._P if "*" in a else kind[decl]
-        assert t is expect, (a, t)
-    assert res is _hip._I
+        assert t is kind[decl], (a, t)
+    assert res is _hip._S
     m = re.search(r"#define\s+DIFFHE_ABI_VERSION\s+(\d+)", open(HEADER).read())
     assert int(m.group(1)) == _hip.ABI_VERSION == 8
 
