@@ -1700,7 +1700,7 @@ extern "C" long long diffhe_ell_amg_workspace_doubles(const diffhe_amg_level* le
 
 extern "C" int diffhe_ell_amg_pcg_solve(const diffhe_amg_level* levels, int n_levels, int Bv, const double* b, double* x,
                                         int Bp, double tol, int max_iter, int n_coarse, int gamma, double scale,
-                                        int precond_fp32, double* work, double* relres, int* iters, int* status_host, void* stream) {
+                                        int flags, double* work, double* relres, int* iters, int* status_host, void* stream) {
   if (!b || !x || !work || !relres || !iters || !status_host || max_iter < 0 || n_coarse < 1 || gamma < 1)
     return DIFFHE_E_BADARG;
   AmgHier H;
@@ -1740,8 +1740,8 @@ extern "C" int diffhe_ell_amg_pcg_solve(const diffhe_amg_level* levels, int n_le
   S.active = (int*)(sc + 7 * Bp);
   S.iters = iters;
   S.n_active = (int*)(sc + 8 * Bp);
-  S.rs = (precond_fp32 & 1) ? sc + 11 * Bp : nullptr;
-  S.xx = (precond_fp32 & 16) ? nullptr : sc + 9 * Bp;  // bit 4: stop on `tol` alone
+  S.rs = (flags & DIFFHE_PCG_FP32) ? sc + 11 * Bp : nullptr;
+  S.xx = (flags & DIFFHE_PCG_NO_FLOOR) ? nullptr : sc + 9 * Bp;  // stop on `tol` alone
   S.maxdiag = sc + 10 * Bp;
   S.Bv = Bv;
   const dim3 sgrid((Bp + 63) / 64);
@@ -1757,7 +1757,7 @@ extern "C" int diffhe_ell_amg_pcg_solve(const diffhe_amg_level* levels, int n_le
 
   // fp32 cycle: the preconditioner STORES its vectors (and, for per-sample matrices, reads copies of the values) in
   // fp32; the CG, its residual, the iterate and every dot product stay fp64 (as in diffhe_lattice_pcg_solve)
-  const bool f32 = (precond_fp32 & 1) != 0;
+  const bool f32 = (flags & DIFFHE_PCG_FP32) != 0;
   float* r32 = f32 ? (float*)H.rhs[0] : nullptr;
   const void* z = nullptr;
   auto precondition = [&]() {

@@ -16,87 +16,10 @@
 #include <type_traits>
 #include <string.h>
 
-#include "common.h"
+#include "lattice.h"
 
+namespace diffhe_lattice __attribute__((visibility("hidden"))) {
 namespace {
-
-using namespace diffhe;
-typedef long long i64;
-
-struct Level {
-  int nx, ny, n, W, nd;
-  const double* v;          // (nd, n, Bv)
-  const float* v32;         // optional fp32 copy of v, used by the fp32 V-cycle's strip kernels
-  const _Float16* o16;      // optional fp16 off-diagonals (nd - 1, n, Bv), times 1 / osc[b], of a per-sample matrix (Bv == Bp):
-                            // with it v32 holds ONLY the main diagonal (n, Bv), adjusted so that every row sum equals
-                            // the fp64 matrix's
-  const double* osc;        // (Bv) per-sample powers of two >= the sample's largest free-row diagonal entry: stored
-                            // off-diagonals lie in [-1, 1] whatever the magnitude of that sample's kappa
-  const float* rd32;        // optional (n) fp32 reciprocal of the main diagonal of a batch-SHARED level matrix (Bv == 1):
-                            // with v32 and mk32 it switches the fp32 V-cycle to the two-samples-per-lane strip kernels
-  const float* mk32;        // (n) 0.0f on Dirichlet rows, 1.0f elsewhere (scalar-loadable form of bc)
-  const unsigned char* bc;  // (n)
-  const void* inv;          // optional dense inverse (n, n) of a batch-shared level matrix, in the V-cycle's storage type
-  const double* shift;      // optional (n) batch-shared diagonal shift: A_b = scale_b * K + diag(shift) (reaction term
-                            // c M_L on a FACTORED operator; 0 on Dirichlet rows); NULL = none
-};
-
-__device__ inline double shift_at(const Level& L, int i) { return L.shift ? L.shift[i] : 0.0; }
-
-// Matrix-value storage of the strip kernels: fp64; fp32 copies (fp32 V-cycle, per-sample matrices); or `h16m`: fp32 main
-// diagonal + fp16 off-diagonals (8 instead of 12 B per node and sample for 3 diagonals).  The preconditioner only has to
-// be spectrally close to A: rounding an edge weight to fp16 (2^-11 relative) while the diagonal keeps every ROW SUM of
-// the fp64 matrix perturbs A by a graph Laplacian with edge weights 2^-11 |a_ij| -- spectrally equivalent within 0.1 %,
-// the null-space behaviour of the smooth modes untouched (a rounded diagonal would shift them by 2^-11 |a_ii| >>
-// lambda_min).  Range: the off-diagonals of sample b are stored divided by a power of two >= that sample's largest
-// free-row diagonal entry (|a_ij| <= max a_ii for an SPD matrix), so kappa of any magnitude -- and samples of very
-// different magnitudes in one batch -- fit; what fp16 cannot hold is contrast INSIDE a sample: couplings below
-// 2^-19 of the scale keep fewer than 5 bits (subnormals) and flush to 0 below 2^-25, so the packing kernel reports them and
-// the host falls back to plain fp32 copies for that solve (dia_pack_h16_kernel).  bf16 (no scaling needed) was measured
-// one PCG iteration worse on the bench workload (10 + 10 against 9 + 9).
-struct h16m {};   // tag type
-template <typename TM> struct MatTypes { typedef TM diag; typedef TM off; };
-template <> struct MatTypes<h16m> { typedef float diag; typedef _Float16 off; };
-__device__ __forceinline__ double ldc(const double* __restrict__ p, unsigned lv) { return p[lv]; }
-__device__ __forceinline__ double ldc(const float* __restrict__ p, unsigned lv) { return (double)p[lv]; }
-__device__ __forceinline__ double ldc(const _Float16* __restrict__ p, unsigned lv) { return (double)(float)p[lv]; }
-
-// 1/d for the smoother: hardware v_rcp_f64 (~2^-23 relative) + one Newton step (~1e-14) -- 4 instructions
-// instead of the ~30 of an IEEE fp64 division.  D^-1 only has to be the same positive diagonal everywhere in
-// the preconditioner, so the remaining 1e-14 is immaterial.
-__device__ inline double fast_rcp(double d) {
-  const double r0 = __builtin_amdgcn_rcp(d);
-  return fma(r0, fma(-d, r0, 1.0), r0);
-}
-
-__device__ inline int dia_off(const Level& L, int k) { return k == 1 ? 1 : (k == 2 ? L.W : L.nx); }
-
-// sum_j K[i,j] x[j] for sample b (unscaled)
-template <typename TV>
-__device__ inline double dia_row(const Level& L, int Bv, int vb, const TV* __restrict__ x, int i, int b, int Bp) {
-  const i64 n = L.n;
-  double acc = L.v[(i64)i * Bv + vb] * (double)x[(i64)i * Bp + b];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) {
-    if (k < L.nd) {
-      const int off = dia_off(L, k);
-      if (i + off < L.n) acc += L.v[((i64)k * n + i) * Bv + vb] * (double)x[(i64)(i + off) * Bp + b];
-      if (i - off >= 0) acc += L.v[((i64)k * n + (i - off)) * Bv + vb] * (double)x[(i64)(i - off) * Bp + b];
-    }
-  }
-  return acc;
-}
-
-__device__ inline double row_scale(const Level& L, const double* __restrict__ scale, int i, int b) {
-  return (scale && !L.bc[i]) ? scale[b] : 1.0;
-}
-
-#define STORE_PARTIAL(part, val)                                                          \
-  do {                                                                                    \
-    const double t__ = block_sum_per_sample((val), Bp, lds);                              \
-    if ((threadIdx.x >> 6) == 0 && (threadIdx.x & 63) < (Bp < kWave ? Bp : kWave))        \
-      (part)[(i64)blockIdx.x * Bp + nm.b] = t__;                                          \
-  } while (0)
 
 // y = A x ; part = per-sample partial of x.y
 __global__ __launch_bounds__(256) void dia_apply_dot_kernel(Level L, int Bv, const double* __restrict__ scale,
@@ -163,1787 +86,6 @@ __global__ __launch_bounds__(256) void dia_jacobi_kernel(Level L, int Bv, const 
     s += bi * xo;
   }
   if (part) STORE_PARTIAL(part, s);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Strip kernels: the same three stencil operations with register-level reuse.
-//
-// A wave owns RW consecutive grid COLUMNS x 64 samples (lanes) and marches down the rows of its
-// tile keeping a 3-row window of x in registers: every x value is loaded once per wave (plus
-// the 2 halo columns per strip, (RW+2)/RW loads per output) instead of once per stencil leg;
-// the 4 waves of a block own 4 adjacent strips, so halo columns hit L1/L2.  Along a row the
-// coefficients of a strip are CONTIGUOUS, so with a batch-shared matrix (Bv == 1) they arrive
-// as scalar loads off one SGPR base per diagonal -- no per-lane traffic at all.
-//
-// Invariant relied upon (and kept by every kernel of the solver): all vectors vanish on
-// Dirichlet rows, whose matrix rows are identity rows.  It lets the per-sample scale s_b be
-// applied to every row without looking up the Dirichlet flag (0 * s_b == 0).
-// ---------------------------------------------------------------------------------------------
-enum { M_APPLY = 0, M_RESID = 1, M_JACOBI = 2 };
-// Fusions folded into the window load:
-//   F_PROLONG: the operand is x + P e (coarse-grid correction added on the fly; with M_JACOBI this
-//              is "prolongate, correct and post-smooth" in one pass);
-//   F_PUPD:    the operand is the NEW search direction p = z + beta p_old of the CG (with M_APPLY
-//              this is "update p, apply A, dot p.Ap" in one pass); the kernel also stores p and
-//              applies the pending iterate update x += alpha_prev p_old.
-//   F_RESTRICT (with M_RESID): the residual is not stored; it is restricted on the fly (P1 full
-//              weighting) into the coarse right-hand side.  The strip then covers the 2 CW + 1 fine
-//              columns 2 J0 - 1 .. 2 J0 + 2 CW - 1 that feed the wave's CW coarse columns (one fine
-//              column is shared with -- and recomputed by -- each neighbour strip) and the tile the
-//              fine rows 2 I0 - 1 .. 2 I1 - 1 of the coarse rows I0 .. I1 - 1.
-enum { F_NONE = 0, F_PROLONG = 1, F_PUPD = 2, F_RESTRICT = 3, F_PUPD_NX = 4, F_RUPD = 5 };
-// F_RUPD (with M_APPLY): the CG's residual update with A p RECOMPUTED from the stored direction p (TA, ex.p_in) instead of
-// read back: r -= alpha (A p), the fp32 copy of r and the partials of r.r in one pass -- for a batch-shared matrix (scalar
-// loads, no coefficient traffic) reading p's window (4 B + halo) is cheaper than writing and re-reading A p (8 + 8 B).
-// F_PUPD_NX: F_PUPD without the iterate update (the solver's form: x is assembled from the kept directions at the
-// end); a compile-time variant so that the x stream costs neither registers nor instructions
-constexpr bool is_pupd(int fuse) { return fuse == F_PUPD || fuse == F_PUPD_NX; }
-
-struct Extra {
-  const void* a0;           // F_PROLONG: coarse correction e (TA);  F_PUPD: z (TA)
-  const void* p_in;         // F_PUPD: previous search direction, stored as TA (the type of z)
-  void* p_out;              // F_PUPD: new search direction, stored as TA
-  double* x;                // F_PUPD: iterate, updated in place (NULL: left alone -- the solver keeps its directions
-                            //   and forms x once at the end, pcg_finish_kernel)
-  const double* alpha;      // F_PUPD: per-sample alpha of the previous iteration
-  const double* beta;       // F_PUPD
-  int first;                // F_PUPD: first iteration (p = z, nothing pending)
-  int cW;                   // F_PROLONG, F_RESTRICT: row width of the coarse level
-  const unsigned char* bc;  // F_PROLONG: fine Dirichlet flags (no correction there); F_RESTRICT: coarse flags
-  const double* dotv;       // M_APPLY, F_NONE: dot (A x + addv) against this vector instead of x
-  const double* addv;       // M_APPLY, F_NONE: batch-shared (n) vector added to A x (may be NULL)
-  float* r32;               // M_RESID, F_NONE, fp64 vectors: also store the residual rounded to fp32 (may be NULL)
-  const double* rscale;     //   ... multiplied by this per-sample power of two first (may be NULL: 1)
-  const double* sub;        // M_APPLY, F_NONE: y = A x - sub_scale[b] * sub[i], sub batch-shared (n) (may be NULL) ...
-  const double* sub_scale;  //   per-sample factor of `sub` (NULL: 1)
-  int sub_pb;               //   ... or, sub_pb != 0, one value per sample: sub is (n, Bp) (the Dirichlet lift of per-sample matrices)
-  const unsigned char* mask;  // M_APPLY, F_NONE: rows with mask[i] != 0 are stored as 0 (may be NULL)
-  int dot_bx;               // M_RESID, F_NONE: the partial sums hold b.x (energy of the iterate) instead of r.r ...
-  double* part2;            //   ... and these (same layout as `part`) x.(A x)
-};
-
-template <typename TV, typename TA, typename TM, int MODE, int FUSE, int ND, bool SHARED, bool XFROMB, int RW,
-          bool TAIL, bool SHIFT = false>
-__device__ __forceinline__ double strip_body(const Level& L, double sb, const TV* __restrict__ src,
-                                             const TV* __restrict__ bvec, TV* __restrict__ out, double omega,
-                                             double omega_in, const Extra& ex, int Bp, int b, int c0w, int r0,
-                                             int r1, double& s2) {
-  const int W = L.W, nyp = L.ny + 1;
-  const i64 n = L.n;
-  const i64 Bv = SHARED ? 1 : Bp;
-  // Addressing discipline: every pointer below is WAVE-UNIFORM (lives in SGPRs) and the lane's
-  // sample index is added last as a 32-bit offset, so loads/stores use the "SGPR base + VGPR
-  // offset" form and the kernel needs one address VGPR instead of one 64-bit pair per stream.
-  const unsigned lb = (unsigned)b;            // lane offset into (.., Bp) vectors
-  const unsigned lv = SHARED ? 0u : (unsigned)b;  // lane offset into the matrix values
-  double s = 0.0;
-
-  // Column offsets of the window (q <-> grid column c0w - 1 + q) and of the strip (k <-> c0w + k),
-  // relative to column c0w.  The first strip's left halo and the columns past the right edge are clamped (both
-  // only in the TAIL instantiation, which every edge strip takes); their window values are forced to 0.
-  int dq[RW + 2];
-  bool okq[RW + 2];
-#pragma unroll
-  for (int q = 0; q < RW + 2; ++q) {
-    int c = c0w - 1 + q;
-    okq[q] = c >= 0 && (!TAIL || c < W);
-    if (c < 0) c = 0;
-    if (TAIL && c > W - 1) c = W - 1;
-    dq[q] = c - c0w;
-  }
-  // D_k[i] lives at V[(k*n + i)*Bv + vb].  Row r0 - 1 of D_2 / D_3 is read for the south couplings also when r0 == 0:
-  // that is the tail of the previous diagonal in the same array (finite, multiplied by a window value of 0).  Nothing is
-  // read in front of an array: the east coupling of column c0w - 1 is an in-grid entry for every non-TAIL strip.
-  const i64 i0 = (i64)r0 * W + c0w;          // node (r0, c0w)
-  typedef typename MatTypes<TM>::diag TD;
-  typedef typename MatTypes<TM>::off TO;
-  constexpr bool kSplit = sizeof(TO) == 2;   // h16m: diagonal in L.v32, off-diagonals in L.o16 (times 1 / L.osc[b])
-  const double osc = kSplit ? L.osc[b] : 1.0;
-  const TD* __restrict__ p0 = (sizeof(TD) == 4 ? (const TD*)L.v32 : (const TD*)L.v) + i0 * Bv;
-  const TO* __restrict__ p1 = kSplit ? (const TO*)L.o16 + i0 * Bv : (const TO*)(const void*)(p0 + n * Bv);
-  const TO* __restrict__ p2 = p1 + n * Bv;
-  const TO* __restrict__ p3 = p2 + n * Bv;
-  const double* __restrict__ psh = SHIFT ? L.shift + i0 : nullptr;   // diagonal shift at (row, c0w): wave-uniform loads
-  const TV* __restrict__ px = src + i0 * Bp;
-  const TV* __restrict__ pb = bvec ? bvec + i0 * Bp : nullptr;
-  TV* __restrict__ po = (out && FUSE != F_RESTRICT) ? out + i0 * Bp : nullptr;
-  const i64 rowV = (i64)W * Bv, rowX = (i64)W * Bp;
-
-  const double inv_omega_in = XFROMB ? 1.0 / omega_in : 0.0;
-  const double sub_fac = (MODE == M_APPLY && FUSE == F_NONE && ex.sub && ex.sub_scale) ? ex.sub_scale[b] : 1.0;
-  const double rsc = (MODE == M_RESID && FUSE == F_NONE && ex.r32 && ex.rscale) ? ex.rscale[b] : 1.0;
-  const double beta = (is_pupd(FUSE) && !ex.first) ? ex.beta[b] : 0.0;
-  const double alpha_prev = (FUSE == F_PUPD && !ex.first && ex.x) ? ex.alpha[b] : 0.0;  // alpha is NULL when x is
-  const TA* __restrict__ aux = (const TA*)ex.a0;
-  // F_PUPD row pointers at (row, c0w), advanced with the others
-  const TA* __restrict__ pz = (is_pupd(FUSE)) ? aux + i0 * Bp : nullptr;
-  const TA* __restrict__ ppi = (is_pupd(FUSE) || FUSE == F_RUPD) ? (const TA*)ex.p_in + i0 * Bp : nullptr;
-  double* __restrict__ pr = (FUSE == F_RUPD) ? ex.x + i0 * Bp : nullptr;          // F_RUPD: ex.x is the residual r
-  float* __restrict__ pr32 = (FUSE == F_RUPD && ex.r32) ? ex.r32 + i0 * Bp : nullptr;
-  const double alpha_cur = (FUSE == F_RUPD) ? ex.alpha[b] : 0.0;
-  const double rsc_u = (FUSE == F_RUPD && ex.r32 && ex.rscale) ? ex.rscale[b] : 1.0;
-  TA* __restrict__ ppo = (is_pupd(FUSE)) ? (TA*)ex.p_out + i0 * Bp : nullptr;
-  double* __restrict__ pxx = (FUSE == F_PUPD && ex.x) ? ex.x + i0 * Bp : nullptr;  // NULL: the iterate is not touched
-
-  // `row` is the grid row being loaded; xrow / d0row point at (row, c0w); roff = offset of that
-  // row from the current one in vector elements
-  auto load_window = [&](int row, i64 roff, const TV* __restrict__ xrow, const TD* __restrict__ d0row,
-                         double* dst, const double* __restrict__ shrow = nullptr) {
-    double ce[RW / 2 + 2], ce2[RW / 2 + 2];
-    if (FUSE == F_PROLONG) {  // coarse values around this strip: coarse columns c0w/2 - 1 + j
-      const int cr = row >> 1;
-#pragma unroll
-      for (int j = 0; j < RW / 2 + 2; ++j) {
-        int cj = (c0w >> 1) - 1 + j;
-        cj = cj < 0 ? 0 : (cj > ex.cW - 1 ? ex.cW - 1 : cj);
-        ce[j] = (double)(aux + ((i64)cr * ex.cW + cj) * Bp)[lb];
-        ce2[j] = (row & 1) ? (double)(aux + ((i64)(cr + 1) * ex.cW + cj) * Bp)[lb] : 0.0;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < RW + 2; ++q) {
-      double v;
-      if (is_pupd(FUSE)) {
-        const i64 o = roff + (i64)dq[q] * Bp;
-        v = (double)(pz + o)[lb];
-        if (!ex.first) v += beta * (double)(ppi + o)[lb];
-        // the direction is STORED as TA: use the stored (rounded) value everywhere, so that Ap = A p,
-        // x += alpha p and r -= alpha Ap stay exactly consistent (r == b - A x is independent of p)
-        v = (double)(TA)v;
-      } else if (FUSE == F_RUPD) {
-        v = (double)(ppi + roff + (i64)dq[q] * Bp)[lb];
-      } else {
-        v = (double)(xrow + (i64)dq[q] * Bp)[lb];
-      }
-      if (XFROMB) v = omega_in * v * fast_rcp(sb * ldc(d0row + (i64)dq[q] * Bv, lv) + (SHIFT ? shrow[dq[q]] : 0.0));
-      if (FUSE == F_PROLONG) {
-        double corr;  // c0w is even: window column q has the parity of q + 1
-        if (q & 1)
-          corr = (row & 1) ? 0.5 * (ce[(q - 1) / 2 + 1] + ce2[(q - 1) / 2 + 1]) : ce[(q - 1) / 2 + 1];
-        else
-          corr = (row & 1) ? 0.5 * (ce[q / 2 + 1] + ce2[q / 2]) : 0.5 * (ce[q / 2] + ce[q / 2 + 1]);
-        if (ex.bc[(i64)row * W + c0w + dq[q]]) corr = 0.0;
-        v += corr;
-      }
-      dst[q] = okq[q] ? v : 0.0;
-    }
-  };
-
-  double xm[RW + 2], xc[RW + 2], xp[RW + 2];
-  double n2p[RW], d3p[RW + 1];
-#pragma unroll
-  for (int q = 0; q < RW + 2; ++q) xm[q] = 0.0;
-  if (r0 > 0) load_window(r0 - 1, -rowX, px - rowX, p0 - rowV, xm, SHIFT ? psh - W : nullptr);
-  load_window(r0, 0, px, p0, xc, psh);
-#pragma unroll
-  for (int k = 0; k < RW; ++k) n2p[k] = kSplit ? osc * ldc(p2 - rowV + (i64)dq[k + 1] * Bv, lv) : ldc(p2 - rowV + (i64)dq[k + 1] * Bv, lv);
-#pragma unroll
-  for (int k = 0; k < RW + 1; ++k)
-    d3p[k] = (ND == 4) ? (kSplit ? osc * ldc(p3 - rowV + (i64)dq[k + 1] * Bv, lv) : ldc(p3 - rowV + (i64)dq[k + 1] * Bv, lv)) : 0.0;
-
-  constexpr int CWR = (FUSE == F_RESTRICT) ? (RW - 1) / 2 : 1;  // coarse columns of an F_RESTRICT strip
-  double racc[CWR], rnext[CWR];
-#pragma unroll
-  for (int j = 0; j < CWR; ++j) racc[j] = rnext[j] = 0.0;
-  const int cI0 = (r0 + 1) >> 1, cJ0 = (c0w + 1) >> 1;          // F_RESTRICT: first coarse row / column
-
-  for (int row = r0; row < r1; ++row) {
-    if (row + 1 < nyp) {
-      load_window(row + 1, rowX, px + rowX, p0 + rowV, xp, SHIFT ? psh + W : nullptr);
-    } else {
-#pragma unroll
-      for (int q = 0; q < RW + 2; ++q) xp[q] = 0.0;
-    }
-    double d0[RW], e1[RW + 1], n2c[RW], d3c[RW + 1];
-    double resrow[(FUSE == F_RESTRICT) ? RW : 1];
-    if (FUSE == F_RESTRICT) {
-#pragma unroll
-      for (int k = 0; k < RW; ++k) resrow[k] = 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < RW; ++k) {
-      d0[k] = ldc(p0 + (i64)dq[k + 1] * Bv, lv);
-      n2c[k] = kSplit ? osc * ldc(p2 + (i64)dq[k + 1] * Bv, lv) : ldc(p2 + (i64)dq[k + 1] * Bv, lv);
-    }
-#pragma unroll
-    for (int k = 0; k < RW + 1; ++k) {
-      // east coupling of column c0w - 1 + k (interior strips: c0w >= RW, the column exists; edge strips: clamped)
-      const int dc = TAIL ? dq[k] : k - 1;
-      e1[k] = kSplit ? osc * ldc(p1 + (i64)dc * Bv, lv) : ldc(p1 + (i64)dc * Bv, lv);
-      d3c[k] = (ND == 4) ? (kSplit ? osc * ldc(p3 + (i64)dq[k + 1] * Bv, lv) : ldc(p3 + (i64)dq[k + 1] * Bv, lv)) : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < RW; ++k) {
-      const int q = k + 1;
-      if (TAIL && (c0w + k >= W || c0w + k < 0)) continue;
-      double acc = d0[k] * xc[q];
-      acc += e1[k + 1] * xc[q + 1] + e1[k] * xc[q - 1];
-      acc += n2c[k] * xp[q] + n2p[k] * xm[q];
-      if (ND == 4) acc += d3c[k] * xp[q - 1] + d3p[k + 1] * xm[q + 1];
-      const i64 o = (i64)k * Bp;
-      const double sh = SHIFT ? psh[dq[k + 1]] : 0.0;   // A = sb K + diag(shift)
-      const double diag = SHIFT ? sb * d0[k] + sh : sb * d0[k];
-      const double Ax = SHIFT ? sb * acc + sh * xc[q] : sb * acc;
-      if (MODE == M_APPLY && FUSE == F_RUPD) {
-        double* ra = &(pr + o)[lb];
-        const double ri = __builtin_nontemporal_load(ra) - alpha_cur * Ax;
-        __builtin_nontemporal_store(ri, ra);
-        if (pr32) (pr32 + o)[lb] = (float)(ri * rsc_u);   // read again right away by the V-cycle: left cacheable
-        s += ri * ri;
-      } else if (MODE == M_APPLY) {
-        double y = Ax;
-        if (FUSE == F_NONE && (ex.sub || ex.mask)) {  // load vector of a lattice mesh: F = M f - lift, 0 on Dirichlet rows
-          const i64 ig = (i64)row * W + c0w + k;
-          if (ex.sub) y -= sub_fac * (ex.sub_pb ? (ex.sub + ig * Bp)[lb] : ex.sub[ig]);
-          if (ex.mask && ex.mask[ig]) y = 0.0;
-        }
-        if (po) {
-          // CG-step streams (Ap, p, x) are touched once per iteration, 1-2 GB each: nontemporal accesses keep them
-          // from evicting the halo columns and the V-cycle's vectors from L2 / Infinity Cache (fused step -4 %)
-          if (is_pupd(FUSE)) __builtin_nontemporal_store((TV)y, &(po + o)[lb]);
-          else (po + o)[lb] = (TV)y;
-        }
-        if (FUSE == F_NONE && ex.dotv) {  // bilinear form lam^T (A x + add): dL/dkappa of a factored operator
-          const i64 ig = (i64)row * W + c0w + k;
-          s += (y + (ex.addv ? ex.addv[ig] : 0.0)) * (ex.dotv + ig * Bp)[lb];
-        } else {
-          s += y * xc[q];
-        }
-        if (is_pupd(FUSE)) {  // store the new direction; apply the pending x += alpha_prev * p_old
-          __builtin_nontemporal_store((TA)xc[q], &(ppo + o)[lb]);
-          if (FUSE == F_PUPD && !ex.first && pxx) {
-            double* xa_ = &(pxx + o)[lb];
-            __builtin_nontemporal_store(__builtin_nontemporal_load(xa_) + alpha_prev * (double)(ppi + o)[lb], xa_);
-          }
-        }
-      } else {
-        const double dinv = (MODE == M_JACOBI) ? fast_rcp(diag) : 0.0;
-        // XFROMB: the window holds x1 = omega_in * rhs * dinv, so rhs = x1 / (omega_in * dinv)
-        const double bi = XFROMB ? xc[q] * diag * inv_omega_in : (double)(pb + o)[lb];
-        const double res = bi - Ax;
-        if (MODE == M_RESID && FUSE == F_RESTRICT) {
-          resrow[k] = res;
-        } else if (MODE == M_RESID) {
-          if (po) (po + o)[lb] = (TV)res;
-          if (FUSE == F_NONE && sizeof(TV) == 8 && ex.r32) (ex.r32 + ((i64)row * W + c0w + k) * Bp)[lb] = (float)(res * rsc);
-          if (FUSE == F_NONE && ex.dot_bx) {
-            s += bi * xc[q];
-            s2 += xc[q] * (bi - res);   // x.(A x)
-          } else {
-            s += res * res;
-          }
-        } else {
-          const double xo = xc[q] + omega * res * dinv;
-          (po + o)[lb] = (TV)xo;
-          s += bi * xo;
-        }
-      }
-    }
-    if (FUSE == F_RESTRICT) {
-      // strip column k <-> fine column 2 cJ0 - 1 + k, so coarse column cJ0 + j sits at k = 2 j + 1.
-      // Full weighting of the P1 lattice: centre 1; W, E, N, S, NE-of-the-row-above, SW-of-the-row-below 1/2.
-      const bool store = (row & 1) || row + 1 >= nyp;  // coarse row complete after its odd row (or at the last row)
-      if (!(row & 1)) {
-#pragma unroll
-        for (int j = 0; j < CWR; ++j) racc[j] += resrow[2 * j + 1] + 0.5 * (resrow[2 * j] + resrow[2 * j + 2]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < CWR; ++j) {
-          racc[j] += 0.5 * (resrow[2 * j + 1] + resrow[2 * j]);
-          rnext[j] = 0.5 * (resrow[2 * j + 1] + resrow[2 * j + 2]);
-        }
-      }
-      if (store) {
-        const int I = row >> 1;
-        if (I >= cI0) {
-#pragma unroll
-          for (int j = 0; j < CWR; ++j) {
-            const int J = cJ0 + j;
-            if (J < ex.cW) {
-              const i64 Ic = (i64)I * ex.cW + J;
-              (out + Ic * Bp)[lb] = (TV)(ex.bc[Ic] ? 0.0 : racc[j]);
-            }
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < CWR; ++j) {
-          racc[j] = rnext[j];
-          rnext[j] = 0.0;
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < RW + 2; ++q) {
-      xm[q] = xc[q];
-      xc[q] = xp[q];
-    }
-#pragma unroll
-    for (int k = 0; k < RW; ++k) n2p[k] = n2c[k];
-#pragma unroll
-    for (int k = 0; k < RW + 1; ++k) d3p[k] = d3c[k];
-    p0 += rowV; p1 += rowV; p2 += rowV; p3 += rowV;
-    if (SHIFT) psh += W;
-    px += rowX;
-    if (pb) pb += rowX;
-    if (po) po += rowX;
-    if (is_pupd(FUSE)) { pz += rowX; ppi += rowX; ppo += rowX; if (FUSE == F_PUPD && pxx) pxx += rowX; }
-    if (FUSE == F_RUPD) { ppi += rowX; pr += rowX; if (pr32) pr32 += rowX; }
-  }
-  return s;
-}
-
-// Workgroups are handed to the 8 XCDs round-robin by linear id, so blocks x = k (mod 8) share one L2.
-// Give each such class a contiguous range of tiles: spatially adjacent strips (which read each other's
-// halo columns / rows) then run on the same XCD at about the same time and the halo hits its L2.
-__device__ inline int xcd_tile(int x, int gx) {
-  const int q = gx >> 3, rem = gx & 7;
-  const int k = x & 7, j = x >> 3;
-  return k * q + (k < rem ? k : rem) + j;
-}
-
-// Body of the strip kernels: tile -> (column strip, row chunk) of this wave, the strip march, the per-sample partials.
-// One call level below the __global__ functions on purpose: written directly into the kernel the same code gets a
-// different register allocation for the batch-shared (SHARED) fp64 variants -- 72 VGPRs + 60 B of scratch instead of
-// 62 for the fused CG step, 141-148 instead of 75-95 for the fp64 residual / apply strips -- and the step measures
-// 2 % slower that way (A/B on one MI355X, 1024^2 x 256: 116.1 vs 113.9 ms; fused CG step 1.20 vs 1.17 ms; only the
-// fp64-stored Jacobi sweep of mg fp32=0 prefers the direct form, 1.27 vs 1.31 ms).
-template <typename TV, typename TA, typename TM, int MODE, int FUSE, int ND, bool SHARED, bool XFROMB, int RW, bool SHIFT>
-__device__ __forceinline__ void strip_kernel_body(Level L, const double* __restrict__ scale,
-                                                  const TV* __restrict__ xin, const TV* __restrict__ bvec,
-                                                  TV* __restrict__ out, double omega, double omega_in, Extra ex,
-                                                  double* __restrict__ part, int Bp, int ncb, int TR) {
-  __shared__ double lds[4 * kWave];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.y * kWave + lane;
-  const int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int rc = tile / ncb, cb = tile - rc * ncb;
-  const int nyp = L.ny + 1;
-  int c0w, r0, r1;
-  bool active;
-  if (FUSE == F_RESTRICT) {  // TR counts COARSE rows, the wave owns (RW - 1) / 2 coarse columns
-    const int J0 = (cb * 4 + wave) * ((RW - 1) / 2), I0 = rc * TR;
-    const int cnyp = (nyp + 1) >> 1;
-    const int I1 = (I0 + TR < cnyp) ? I0 + TR : cnyp;
-    c0w = 2 * J0 - 1;
-    r0 = I0 > 0 ? 2 * I0 - 1 : 0;
-    r1 = (2 * I1 < nyp) ? 2 * I1 : nyp;
-    active = J0 < ex.cW && I0 < I1;
-  } else {
-    c0w = (cb * 4 + wave) * RW;
-    r0 = rc * TR;
-    r1 = (r0 + TR < nyp) ? r0 + TR : nyp;
-    active = c0w < L.W && r0 < r1;
-  }
-  const double sb = scale ? scale[b] : 1.0;
-  const TV* __restrict__ src = XFROMB ? bvec : xin;
-  double s = 0.0, s2 = 0.0;
-  if (active) {
-    // strips that touch the left or right edge take the clamped body -- the first strip (c0w == 0) too: its window column
-    // -1 would otherwise read the east coupling one element BEFORE the row, which for row 0 lies in front of the array
-    if (c0w + RW + 1 > L.W || c0w <= 0)
-      s = strip_body<TV, TA, TM, MODE, FUSE, ND, SHARED, XFROMB, RW, true, SHIFT>(L, sb, src, bvec, out, omega, omega_in, ex,
-                                                                              Bp, b, c0w, r0, r1, s2);
-    else
-      s = strip_body<TV, TA, TM, MODE, FUSE, ND, SHARED, XFROMB, RW, false, SHIFT>(L, sb, src, bvec, out, omega, omega_in, ex,
-                                                                               Bp, b, c0w, r0, r1, s2);
-  }
-  if (part) {
-    const double t = block_sum_per_sample(s, Bp, lds);
-    if (wave == 0) part[(i64)blockIdx.x * Bp + b] = t;
-  }
-  if (MODE == M_RESID && FUSE == F_NONE && ex.part2) {
-    const double t = block_sum_per_sample(s2, Bp, lds);
-    if (wave == 0) ex.part2[(i64)blockIdx.x * Bp + b] = t;
-  }
-}
-
-template <typename TV, typename TA, typename TM, int MODE, int FUSE, int ND, bool SHARED, bool XFROMB, int RW,
-          int MINW = 1>
-__global__ __launch_bounds__(256, MINW) void dia_strip_kernel(Level L, const double* __restrict__ scale,
-                                                         const TV* __restrict__ xin, const TV* __restrict__ bvec,
-                                                         TV* __restrict__ out, double omega, double omega_in,
-                                                         Extra ex, double* __restrict__ part, int Bp, int ncb,
-                                                         int TR) {
-  strip_kernel_body<TV, TA, TM, MODE, FUSE, ND, SHARED, XFROMB, RW, false>(L, scale, xin, bvec, out, omega, omega_in, ex, part,
-                                                                          Bp, ncb, TR);
-}
-
-// The same strips for a FACTORED operator with a batch-shared diagonal shift, A_b = scale_b K_1 + diag(L.shift)
-// (reaction term / heat-equation steps with one scalar kappa per sample): coefficients stay scalar loads.
-template <typename TV, typename TA, int MODE, int FUSE, int ND, bool XFROMB, int RW, int MINW = 1>
-__global__ __launch_bounds__(256, MINW) void dia_strip_shift_kernel(Level L, const double* __restrict__ scale,
-                                                               const TV* __restrict__ xin, const TV* __restrict__ bvec,
-                                                               TV* __restrict__ out, double omega, double omega_in,
-                                                               Extra ex, double* __restrict__ part, int Bp, int ncb,
-                                                               int TR) {
-  strip_kernel_body<TV, TA, double, MODE, FUSE, ND, true, XFROMB, RW, true>(L, scale, xin, bvec, out, omega, omega_in, ex, part,
-                                                                           Bp, ncb, TR);
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Two samples per lane: the strip kernels of the fp32-stored V-cycle for a batch-SHARED matrix
-// (factored operator K_b = s_b K_1, or one per-element field for the whole batch).
-//
-// A lane owns TWO adjacent samples, a wave 128: every vector access is 8 B per lane / 512 B per wave
-// instead of 4 / 256 (this GPU streams 4 B-per-lane accesses at ~4.8 TB/s, 8 B at 5.3-5.5:
-// profiles/r02_stream_bench.txt), and the arithmetic is PACKED fp32 (v_pk_fma_f32: both samples per
-// instruction) on fp32 coefficient copies that arrive as scalar loads -- about a fifth of the
-// instructions per sample of the fp64-in-registers form.  The vectors of this cycle are stored
-// fp32 anyway: a stored x carries a 2^-24 relative rounding that enters A x with weight |A||x|, and
-// fp32 accumulation of the seven stencil terms adds the same order (measured: same iteration
-// counts, same parity).  Written in "unit" form: with ib = 1 / s_b,
-//     Jacobi   x' = x + omega rd0 (b ib - K_1 x)          (rd0 = 1 / diag K_1, batch-shared)
-//     residual r  = b - s_b (K_1 x)
-// so a sweep needs no division at all.  Same strips, tiles, window and fusions as strip_body.
-// ---------------------------------------------------------------------------------------------
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ v2f ld2(const float* __restrict__ p, unsigned lb) { return *(const v2f*)(p + lb); }
-__device__ __forceinline__ void st2(float* __restrict__ p, unsigned lb, v2f v) { *(v2f*)(p + lb) = v; }
-// Buffer addressing: one resource descriptor per stream (base = the tile's first window row, one column left of the
-// strip), a loop-invariant 32-bit per-lane byte offset per column (VGPR) and a wave-uniform 32-bit byte offset per
-// row (SGPR, one s_add per iteration): "buffer_load_dwordx2 v, v_off, s[rsrc], s_row offen" -- no 64-bit address
-// arithmetic per access (the flat-pointer form cost a v_lshl_add_u64 per load and ~50 scalar adds per row).
-// Offsets are relative to the TILE, so they stay far below 2^32 whatever the size of the vector (checked on the host).
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, -1, 0x00020000);
-}
-__device__ __forceinline__ v2f bld(rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-}
-__device__ __forceinline__ void bst(rsrc_t r, unsigned voff, unsigned soff, v2f v) {
-  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), r, voff, soff, 0);
-}
-
-template <int MODE, int FUSE, int ND, bool XFROMB, int RW, bool TAIL, bool DOT, bool BST>
-__device__ __forceinline__ void strip2_body(const Level& L, v2f ib, v2f sb, const float* __restrict__ src,
-                                            const float* __restrict__ bvec, float* __restrict__ out, float omega,
-                                            float omega_in, const Extra& ex, int Bp, unsigned lb, int c0w, int r0,
-                                            int r1, double& s0, double& s1) {
-  const int W = L.W, nyp = L.ny + 1;
-  const i64 n = L.n;
-  const v2f zero2 = {0.0f, 0.0f};
-  // Bases sit at window row r0 - 1, one column LEFT of the strip: window column q (grid column c0w - 1 + q) has the
-  // non-negative lane offset (dq[q] + 1) * Bp, row `row` the uniform offset (row - r0 + 1) * W * Bp.
-  int dq[RW + 2];
-  bool okq[RW + 2];
-  unsigned offq[RW + 2];
-#pragma unroll
-  for (int q = 0; q < RW + 2; ++q) {
-    int c = c0w - 1 + q;
-    okq[q] = !TAIL || (c >= 0 && c < W);   // interior strips (TAIL = false) have every window column inside the grid
-    if (TAIL && c < 0) c = 0;
-    if (TAIL && c > W - 1) c = W - 1;
-    dq[q] = c - c0w;
-    offq[q] = 4u * ((unsigned)((dq[q] + 1) * Bp) + lb);   // bytes
-  }
-  const i64 i0 = (i64)r0 * W + c0w;          // node (r0, c0w)
-  const float* __restrict__ p0 = L.v32 + i0;
-  const float* __restrict__ p1 = p0 + n;
-  const float* __restrict__ p2 = p1 + n;
-  const float* __restrict__ p3 = p2 + n;
-  const float* __restrict__ prd = L.rd32 + i0;
-  const float* __restrict__ pmk = (FUSE == F_PROLONG) ? L.mk32 + i0 : nullptr;
-  const i64 tile0 = (i0 - W - 1) * Bp;                                     // element (r0 - 1, c0w - 1)
-  const rsrc_t rx = make_rsrc(src + tile0);
-  const rsrc_t rb = make_rsrc(bvec ? bvec + tile0 : nullptr);
-  const rsrc_t ro = make_rsrc((out && FUSE != F_RESTRICT) ? out + tile0 : nullptr);
-  float* __restrict__ po = (out && FUSE != F_RESTRICT) ? out + tile0 + (i64)W * Bp : nullptr;   // row r0, column c0w - 1
-  const unsigned rowB = 4u * (unsigned)W * (unsigned)Bp;                   // bytes per grid row
-  const float inv_omega_in = XFROMB ? 1.0f / omega_in : 0.0f;
-  const float* __restrict__ aux = (const float*)ex.a0;
-  unsigned offc[RW / 2 + 2];   // F_PROLONG: coarse columns c0w/2 - 1 + j (clamped), as offsets into a coarse row
-#pragma unroll
-  for (int j = 0; j < RW / 2 + 2; ++j) {
-    int cj = (c0w >> 1) - 1 + j;
-    cj = cj < 0 ? 0 : (cj > ex.cW - 1 ? ex.cW - 1 : cj);
-    offc[j] = (FUSE == F_PROLONG) ? 4u * ((unsigned)(cj * Bp) + lb) : 0u;
-  }
-  const int cr0 = (r0 > 0 ? r0 - 1 : 0) >> 1;                              // first coarse row this tile reads
-  const rsrc_t rc = make_rsrc(FUSE == F_PROLONG ? aux + (i64)cr0 * ex.cW * Bp : nullptr);
-  const unsigned rowCB = 4u * (unsigned)ex.cW * (unsigned)Bp;
-
-  // sx = byte offset of window row `row` in the tile
-  auto load_window = [&](int row, unsigned sx, const float* __restrict__ rdrow, const float* __restrict__ mkrow,
-                         v2f* dst) {
-    v2f ce[RW / 2 + 2], ce2[RW / 2 + 2];
-    if (FUSE == F_PROLONG) {  // coarse values around this strip
-      const unsigned sc = (unsigned)((row >> 1) - cr0) * rowCB;
-#pragma unroll
-      for (int j = 0; j < RW / 2 + 2; ++j) {
-        ce[j] = bld(rc, offc[j], sc);
-        ce2[j] = (row & 1) ? bld(rc, offc[j], sc + rowCB) : zero2;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < RW + 2; ++q) {
-      v2f v = bld(rx, offq[q], sx);
-      if (XFROMB) v = (v * ib) * (omega_in * rdrow[dq[q]]);   // x1 = omega_in D^-1 rhs, formed on the fly
-      if (FUSE == F_PROLONG) {
-        v2f corr;  // c0w is even: window column q has the parity of q + 1
-        if (q & 1)
-          corr = (row & 1) ? 0.5f * (ce[(q - 1) / 2 + 1] + ce2[(q - 1) / 2 + 1]) : ce[(q - 1) / 2 + 1];
-        else
-          corr = (row & 1) ? 0.5f * (ce[q / 2 + 1] + ce2[q / 2]) : 0.5f * (ce[q / 2] + ce[q / 2 + 1]);
-        v += mkrow[dq[q]] * corr;   // mask: 0 on Dirichlet rows (no correction there), 1 elsewhere
-      }
-      dst[q] = okq[q] ? v : zero2;
-    }
-  };
-
-  v2f xm[RW + 2], xc[RW + 2], xp[RW + 2];
-  float n2p[RW], d3p[RW + 1];
-#pragma unroll
-  for (int q = 0; q < RW + 2; ++q) xm[q] = zero2;
-  if (r0 > 0) load_window(r0 - 1, 0u, prd - W, pmk ? pmk - W : nullptr, xm);
-  load_window(r0, rowB, prd, pmk, xc);
-  unsigned sx = rowB;                                                      // byte offset of the current row
-#pragma unroll
-  for (int k = 0; k < RW; ++k) n2p[k] = (p2 - W)[dq[k + 1]];
-#pragma unroll
-  for (int k = 0; k < RW + 1; ++k) d3p[k] = (ND == 4) ? (p3 - W)[dq[k + 1]] : 0.0f;
-
-  constexpr int CWR = (FUSE == F_RESTRICT) ? (RW - 1) / 2 : 1;  // coarse columns of an F_RESTRICT strip
-  v2f racc[CWR], rnext[CWR];
-#pragma unroll
-  for (int j = 0; j < CWR; ++j) racc[j] = rnext[j] = zero2;
-  const int cI0 = (r0 + 1) >> 1, cJ0 = (c0w + 1) >> 1;          // F_RESTRICT: first coarse row / column
-
-  for (int row = r0; row < r1; ++row) {
-    if (row + 1 < nyp) {
-      load_window(row + 1, sx + rowB, prd + W, pmk ? pmk + W : nullptr, xp);
-    } else {
-#pragma unroll
-      for (int q = 0; q < RW + 2; ++q) xp[q] = zero2;
-    }
-    float d0[RW], e1[RW + 1], n2c[RW], d3c[RW + 1];
-    v2f resrow[(FUSE == F_RESTRICT) ? RW : 1];
-    if (FUSE == F_RESTRICT) {
-#pragma unroll
-      for (int k = 0; k < RW; ++k) resrow[k] = zero2;
-    }
-#pragma unroll
-    for (int k = 0; k < RW; ++k) {
-      d0[k] = p0[dq[k + 1]];
-      n2c[k] = p2[dq[k + 1]];
-    }
-#pragma unroll
-    for (int k = 0; k < RW + 1; ++k) {
-      const int dc = TAIL ? dq[k] : k - 1;  // east coupling of column c0w - 1 + k (TAIL covers c0w < 1: clamped)
-      e1[k] = p1[dc];
-      d3c[k] = (ND == 4) ? p3[dq[k + 1]] : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < RW; ++k) {
-      const int q = k + 1;
-      if (TAIL && (c0w + k >= W || c0w + k < 0)) continue;
-      if (MODE == M_JACOBI) {
-        // unit form: bu = b / s_b; XFROMB: the window holds x1 = omega_in rd0 bu, so bu = x1 d0 / omega_in
-        v2f braw = zero2, res;
-        if (XFROMB) {
-          res = xc[q] * (d0[k] * inv_omega_in);
-          if (DOT) braw = res * sb;
-        } else {
-          braw = bld(rb, offq[q], sx);
-          res = braw * ib;
-        }
-        res -= d0[k] * xc[q];
-        res -= e1[k + 1] * xc[q + 1];
-        res -= e1[k] * xc[q - 1];
-        res -= n2c[k] * xp[q];
-        res -= n2p[k] * xm[q];
-        if (ND == 4) {
-          res -= d3c[k] * xp[q - 1];
-          res -= d3p[k + 1] * xm[q + 1];
-        }
-        const v2f xo = xc[q] + (omega * prd[dq[q]]) * res;
-        if (BST) bst(ro, offq[q], sx, xo);
-        else *(v2f*)((char*)po + offq[q]) = xo;
-        if (DOT) {
-          const v2f pr = braw * xo;
-          s0 += (double)pr.x;
-          s1 += (double)pr.y;
-        }
-      } else {  // M_RESID (+ F_RESTRICT): r = b - s_b (K_1 x)
-        v2f acc = d0[k] * xc[q];
-        acc += e1[k + 1] * xc[q + 1];
-        acc += e1[k] * xc[q - 1];
-        acc += n2c[k] * xp[q];
-        acc += n2p[k] * xm[q];
-        if (ND == 4) {
-          acc += d3c[k] * xp[q - 1];
-          acc += d3p[k + 1] * xm[q + 1];
-        }
-        const v2f res = bld(rb, offq[q], sx) - sb * acc;
-        if (FUSE == F_RESTRICT) resrow[k] = res;
-        else if (BST) bst(ro, offq[q], sx, res);
-        else *(v2f*)((char*)po + offq[q]) = res;
-      }
-    }
-    if (FUSE == F_RESTRICT) {
-      // strip column k <-> fine column 2 cJ0 - 1 + k, so coarse column cJ0 + j sits at k = 2 j + 1.
-      // Full weighting of the P1 lattice: centre 1; W, E, N, S, NE-of-the-row-above, SW-of-the-row-below 1/2.
-      const bool store = (row & 1) || row + 1 >= nyp;  // coarse row complete after its odd row (or at the last row)
-      if (!(row & 1)) {
-#pragma unroll
-        for (int j = 0; j < CWR; ++j) racc[j] += resrow[2 * j + 1] + 0.5f * (resrow[2 * j] + resrow[2 * j + 2]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < CWR; ++j) {
-          racc[j] += 0.5f * (resrow[2 * j + 1] + resrow[2 * j]);
-          rnext[j] = 0.5f * (resrow[2 * j + 1] + resrow[2 * j + 2]);
-        }
-      }
-      if (store) {
-        const int I = row >> 1;
-        if (I >= cI0) {
-#pragma unroll
-          for (int j = 0; j < CWR; ++j) {
-            const int J = cJ0 + j;
-            if (J < ex.cW) {
-              const i64 Ic = (i64)I * ex.cW + J;
-              st2(out + Ic * Bp, lb, ex.bc[Ic] ? zero2 : racc[j]);
-            }
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < CWR; ++j) {
-          racc[j] = rnext[j];
-          rnext[j] = zero2;
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < RW + 2; ++q) {
-      xm[q] = xc[q];
-      xc[q] = xp[q];
-    }
-#pragma unroll
-    for (int k = 0; k < RW; ++k) n2p[k] = n2c[k];
-#pragma unroll
-    for (int k = 0; k < RW + 1; ++k) d3p[k] = d3c[k];
-    p0 += W; p1 += W; p2 += W; p3 += W; prd += W;
-    if (FUSE == F_PROLONG) pmk += W;
-    sx += rowB;
-    if (!BST && po) po += (i64)W * Bp;
-  }
-}
-
-template <int MODE, int FUSE, int ND, bool XFROMB, int RW, bool DOT, bool BST>
-__global__ __launch_bounds__(256) void dia_strip2_kernel(Level L, const double* __restrict__ scale,
-                                                          const float* __restrict__ xin, const float* __restrict__ bvec,
-                                                          float* __restrict__ out, float omega, float omega_in, Extra ex,
-                                                          double* __restrict__ part, int Bp, int ncb, int TR) {
-  __shared__ double lds[4 * kWave];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned lb = blockIdx.y * (2 * kWave) + 2 * lane;   // first of this lane's two samples
-  const int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int rc = tile / ncb, cb = tile - rc * ncb;
-  const int nyp = L.ny + 1;
-  int c0w, r0, r1;
-  bool active;
-  if (FUSE == F_RESTRICT) {  // TR counts COARSE rows, the wave owns (RW - 1) / 2 coarse columns
-    const int J0 = (cb * 4 + wave) * ((RW - 1) / 2), I0 = rc * TR;
-    const int cnyp = (nyp + 1) >> 1;
-    const int I1 = (I0 + TR < cnyp) ? I0 + TR : cnyp;
-    c0w = 2 * J0 - 1;
-    r0 = I0 > 0 ? 2 * I0 - 1 : 0;
-    r1 = (2 * I1 < nyp) ? 2 * I1 : nyp;
-    active = J0 < ex.cW && I0 < I1;
-  } else {
-    c0w = (cb * 4 + wave) * RW;
-    r0 = rc * TR;
-    r1 = (r0 + TR < nyp) ? r0 + TR : nyp;
-    active = c0w < L.W && r0 < r1;
-  }
-  v2f sb = {1.0f, 1.0f};
-  if (scale) {
-    sb.x = (float)scale[lb];
-    sb.y = (float)scale[lb + 1];
-  }
-  const v2f ib = 1.0f / sb;
-  const float* __restrict__ src = XFROMB ? bvec : xin;
-  double s0 = 0.0, s1 = 0.0;
-  if (active) {
-    if (c0w + RW + 1 > L.W || c0w < 1)    // strips that touch the left or right edge: clamped window columns
-      strip2_body<MODE, FUSE, ND, XFROMB, RW, true, DOT, BST>(L, ib, sb, src, bvec, out, omega, omega_in, ex, Bp, lb, c0w, r0, r1,
-                                                         s0, s1);
-    else
-      strip2_body<MODE, FUSE, ND, XFROMB, RW, false, DOT, BST>(L, ib, sb, src, bvec, out, omega, omega_in, ex, Bp, lb, c0w, r0,
-                                                          r1, s0, s1);
-  }
-  if (DOT) {
-    const double t0 = block_sum_per_sample(s0, Bp, lds);
-    const double t1 = block_sum_per_sample(s1, Bp, lds);
-    if (wave == 0) {
-      part[(i64)blockIdx.x * Bp + lb] = t0;
-      part[(i64)blockIdx.x * Bp + lb + 1] = t1;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// FUSED two-stage passes of the fp32 V-cycle (batch-shared matrix), round 3.
-//
-// The four strip passes of a level -- first two sweeps, residual + restriction, prolongation + sweep, sweep -- read the
-// right-hand side four times and write / re-read two intermediate iterates: 42 B per node and sample, all of it HBM
-// traffic, at the HBM rate (section 6 of DESIGN.md: these kernels run at 4.4-5.2 TB/s of REAL traffic; their inner
-// loops are not the limit).  The packed-fp32 form leaves most of the issue slots idle, so they are spent on
-// RECOMPUTATION instead: two chained stencil stages per pass, the intermediate iterate kept in registers on a
-// one-column / one-row wider window and never stored.
-//   PRE : x2 = two sweeps from 0, coarse rhs = R (r - A x2)       reads r; writes x2 and the coarse rhs:     9 B  (was 17)
-//   POST: z  = two sweeps on (x2 + P e)                           reads x2, r, e; writes z:                 13 B  (was 25)
-// 22 instead of 42 B per node and sample and cycle.  Same arithmetic per node as the unfused kernels (unit form, packed
-// fp32), evaluated once more on the halo ring; results agree with them to fp32 rounding (different association only).
-// A wave owns its columns for both stages; VT = v2f (two samples per lane) or float (one).
-// ---------------------------------------------------------------------------------------------
-// per-sample sum over the NW waves of a block (lanes hold distinct samples); valid in wave 0.  NW == 4: the same order
-// of additions as block_sum_per_sample (results of the default geometry stay bitwise what they were)
-template <int NW>
-__device__ __forceinline__ double block_sum_waves(double v, double* lds /* >= NW * 64 doubles */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  lds[wave * kWave + lane] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (wave == 0) {
-    if (NW == 4) {
-      s = (lds[lane] + lds[kWave + lane]) + (lds[2 * kWave + lane] + lds[3 * kWave + lane]);
-    } else {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) s += lds[w * kWave + lane];
-    }
-  }
-  __syncthreads();
-  return s;
-}
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-struct Acc { double v[4] = {0.0, 0.0, 0.0, 0.0}; };   // per-sample dot-product accumulators of one lane (kSpl used)
-
-template <typename VT> struct VLane;
-template <> struct VLane<float> {
-  static constexpr int kSpl = 1;
-  static __device__ __forceinline__ float zero() { return 0.0f; }
-  static __device__ __forceinline__ float ld(rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-  }
-  static __device__ __forceinline__ float from_scale(const double* __restrict__ s, unsigned lb) { return s ? (float)s[lb] : 1.0f; }
-  static __device__ __forceinline__ void dot(Acc& s, float a, float b) { s.v[0] += (double)(a * b); }
-};
-template <> struct VLane<v2f> {
-  static constexpr int kSpl = 2;
-  static __device__ __forceinline__ v2f zero() { return v2f{0.0f, 0.0f}; }
-  static __device__ __forceinline__ v2f ld(rsrc_t r, unsigned voff, unsigned soff) { return bld(r, voff, soff); }
-  static __device__ __forceinline__ v2f from_scale(const double* __restrict__ s, unsigned lb) {
-    return s ? v2f{(float)s[lb], (float)s[lb + 1]} : v2f{1.0f, 1.0f};
-  }
-  static __device__ __forceinline__ void dot(Acc& s, v2f a, v2f b) {
-    const v2f p = a * b;
-    s.v[0] += (double)p.x;
-    s.v[1] += (double)p.y;
-  }
-};
-// FOUR samples per lane, 256 per wave: one 16-byte access per lane and node -- half the vector-memory instructions per
-// byte of the two-sample form (the fused passes are bound by the NUMBER of those instructions),
-// twice the registers per lane (2 waves per SIMD instead of 4: the same bytes in flight per SIMD).
-template <> struct VLane<v4f> {
-  static constexpr int kSpl = 4;
-  static __device__ __forceinline__ v4f zero() { return v4f{0.0f, 0.0f, 0.0f, 0.0f}; }
-  static __device__ __forceinline__ v4f ld(rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-  }
-  static __device__ __forceinline__ v4f from_scale(const double* __restrict__ s, unsigned lb) {
-    return s ? v4f{(float)s[lb], (float)s[lb + 1], (float)s[lb + 2], (float)s[lb + 3]} : v4f{1.0f, 1.0f, 1.0f, 1.0f};
-  }
-  static __device__ __forceinline__ void dot(Acc& s, v4f a, v4f b) {
-    const v4f p = a * b;
-    s.v[0] += (double)p.x;
-    s.v[1] += (double)p.y;
-    s.v[2] += (double)p.z;
-    s.v[3] += (double)p.w;
-  }
-};
-
-// A vector stream of the fused kernels: buffer-resource addressing (raw_buffer_load, 32-bit per-lane offset + uniform
-// SGPR row offset).  Global loads off a wave-uniform 64-bit base (the form strip_body uses) spilled and ran slower
-// (DESIGN.md section 6, round 4), although the PMC counters show the texture-addresser FIFOs full 28-35 % of the time in
-// the buffer-load kernels and never in strip_body's.
-struct Src {
-  rsrc_t r;
-};
-__device__ __forceinline__ Src make_src(const void* p) { return Src{make_rsrc(p)}; }
-template <typename VT>
-__device__ __forceinline__ VT ldsrc(const Src& s, unsigned voff, unsigned soff) { return VLane<VT>::ld(s.r, voff, soff); }
-
-// Where the matrix coefficients of the fused passes come from.
-//   SHARED: batch-shared fp32 copies + reciprocal diagonal, wave-uniform scalar loads (values are plain floats);
-//   per sample: fp32 diagonal + scaled fp16 off-diagonals (Level.v32 / o16 / osc), one value per sample and lane,
-//   buffer loads with tile-relative offsets; the reciprocal diagonal is v_rcp_f32 of the loaded diagonal.
-template <typename VT, bool SHARED> struct Coef;
-template <typename VT> struct Coef<VT, true> {
-  typedef float T;
-  const float *v0, *v1, *v2, *v3, *rdp;
-  __device__ __forceinline__ Coef(const Level& L, i64, unsigned, int) : v0(L.v32), v1(L.v32 + L.n), v2(L.v32 + 2 * (i64)L.n),
-                                                                        v3(L.v32 + 3 * (i64)L.n), rdp(L.rd32) {}
-  __device__ __forceinline__ T d(i64 i) const { return v0[i]; }
-  __device__ __forceinline__ T e(i64 i) const { return v1[i]; }
-  __device__ __forceinline__ T n2(i64 i) const { return v2[i]; }
-  __device__ __forceinline__ T q3(i64 i) const { return v3[i]; }
-  __device__ __forceinline__ T rd(i64 i, T) const { return rdp[i]; }
-};
-__device__ __forceinline__ float ldh(rsrc_t r, unsigned voff, float) {
-  return (float)__builtin_bit_cast(_Float16, __builtin_amdgcn_raw_buffer_load_b16(r, voff, 0, 0));
-}
-__device__ __forceinline__ v2f ldh(rsrc_t r, unsigned voff, v2f) {
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-  const h2 h = __builtin_bit_cast(h2, __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
-  return v2f{(float)h.x, (float)h.y};
-}
-__device__ __forceinline__ unsigned ldraw(rsrc_t r, unsigned voff, float) {
-  return (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, voff, 0, 0);
-}
-__device__ __forceinline__ unsigned ldraw(rsrc_t r, unsigned voff, v2f) {
-  return (unsigned)__builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0);
-}
-__device__ __forceinline__ float unraw(unsigned raw, float) { return (float)__builtin_bit_cast(_Float16, (unsigned short)raw); }
-__device__ __forceinline__ v2f unraw(unsigned raw, v2f) {
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-  const h2 h = __builtin_bit_cast(h2, raw);
-  return v2f{(float)h.x, (float)h.y};
-}
-template <typename VT> struct Coef<VT, false> {
-  typedef VT T;
-  rsrc_t r0, r1, r2, r3;
-  i64 base;       // node index the resources are based at (<= every index the tile touches)
-  unsigned lb, Bp;
-  VT osc;         // this lane's sample scale(s) of the fp16 couplings
-  __device__ __forceinline__ Coef(const Level& L, i64 base_, unsigned lb_, int Bp_)
-      : base(base_), lb(lb_), Bp((unsigned)Bp_), osc(VLane<VT>::from_scale(L.osc, lb_)) {
-    const i64 n = L.n;
-    r0 = make_rsrc(L.v32 + base * Bp_);
-    r1 = make_rsrc(L.o16 + base * Bp_);
-    r2 = make_rsrc(L.o16 + (n + base) * Bp_);
-    r3 = make_rsrc(L.o16 + (2 * n + base) * Bp_);
-  }
-  __device__ __forceinline__ unsigned off(i64 i) const { return (unsigned)(i - base) * Bp + lb; }
-  __device__ __forceinline__ T d(i64 i) const { return VLane<VT>::ld(r0, 4u * off(i), 0u); }
-  __device__ __forceinline__ T e(i64 i) const { return osc * ldh(r1, 2u * off(i), VT{}); }
-  __device__ __forceinline__ T n2(i64 i) const { return osc * ldh(r2, 2u * off(i), VT{}); }
-  __device__ __forceinline__ T q3(i64 i) const { return osc * ldh(r3, 2u * off(i), VT{}); }
-  __device__ __forceinline__ T rd(i64, T dv) const { return 1.0f / dv; }
-  // raw fp16 storage words (one per sample of the lane), for the register-cached coefficient rows of the fused POST pass
-  __device__ __forceinline__ unsigned e_raw(i64 i) const { return ldraw(r1, 2u * off(i), VT{}); }
-  __device__ __forceinline__ unsigned n2_raw(i64 i) const { return ldraw(r2, 2u * off(i), VT{}); }
-  __device__ __forceinline__ T cvt(unsigned raw) const { return osc * unraw(raw, VT{}); }
-};
-
-// K_1 x at the NC columns col0 .. col0 + NC - 1 of grid row R, handed column by column to `use(k, K1x, d0, rd)`.
-// xm / xc / xp hold x on rows R - 1 / R / R + 1 at the NC + 2 columns col0 - 1 .. col0 + NC (index j <-> column
-// col0 - 1 + j); out-of-grid positions must hold 0.  EDGE: the strip / tile touches a grid edge, so the coefficient
-// indices of non-existent couplings are clamped into the arrays (their values meet a zero x).
-template <typename VT, int NC, int ND, bool EDGE, typename CF, typename F>
-__device__ __forceinline__ void k1_row(const CF& cf, i64 n, int W, int R, int col0, const VT* xm, const VT* xc,
-                                       const VT* xp, F&& use) {
-  const i64 base = (i64)R * W + col0;
-  auto at = [&](i64 i) -> i64 { return EDGE ? (i < 0 ? 0 : (i > n - 1 ? n - 1 : i)) : i; };
-  typename CF::T ew = cf.e(at(base - 1));       // west coupling of the first column; then carried along the row
-#pragma unroll
-  for (int k = 0; k < NC; ++k) {
-    const i64 i = base + k;
-    const typename CF::T d0 = cf.d(at(i));
-    const typename CF::T ee = cf.e(at(i));
-    VT acc = d0 * xc[k + 1];
-    acc += ee * xc[k + 2];                       // east  (R, c) - (R, c + 1)
-    acc += ew * xc[k];                           // west
-    acc += cf.n2(at(i)) * xp[k + 1];             // north (R, c) - (R + 1, c)
-    acc += cf.n2(at(i - W)) * xm[k + 1];         // south
-    if (ND == 4) {
-      acc += cf.q3(at(i)) * xp[k];               // (R, c) - (R + 1, c - 1)
-      acc += cf.q3(at(i - W + 1)) * xm[k + 2];   // (R - 1, c + 1) - (R, c)
-    }
-    use(k, acc, d0, cf.rd(at(i), d0));
-    ew = ee;
-  }
-}
-
-// ---- PRE: first two sweeps from a zero guess + residual + full-weighting restriction -------------------------------
-// Geometry of the F_RESTRICT strips: the wave owns CW coarse columns J0 .. J0 + CW - 1, i.e. the RW = 2 CW + 1 fine
-// residual columns c0w = 2 J0 - 1 .. 2 J0 + 2 CW - 1 (the last one shared with -- and recomputed by -- the next strip),
-// and stores x2 on the first 2 CW of them; tile rows: coarse I0 .. I1 - 1 = fine residual rows r0 .. r1 - 1
-// (r0 = 2 I0 - 1, r1 = 2 I1), x2 stored on rows r0 .. r1 - 2 (all the way up on the last tile).
-template <typename VT, int ND, int CW, bool EDGE, bool SHARED>
-__device__ __forceinline__ void fused_pre_body(const Level& L, VT ib, VT sb, const float* __restrict__ rhs,
-                                               float* __restrict__ x2out, float* __restrict__ crhs, float w0, float w1,
-                                               int cW, const unsigned char* __restrict__ cbc, int Bp, unsigned lb, int c0w,
-                                               int r0, int r1) {
-  constexpr int RW = 2 * CW + 1;
-  constexpr int N1 = RW + 4, N2 = RW + 2;    // columns of the x1 / x2 windows: c0w - 2 + j / c0w - 1 + j
-  const int W = L.W, nyp = L.ny + 1;
-  const i64 n = L.n;
-  const VT Z = VLane<VT>::zero();
-  typedef Coef<VT, SHARED> CF;
-  i64 cbase = (i64)(r0 - 3) * W;             // coefficient resources: based below everything the tile touches
-  if (cbase < 0) cbase = 0;
-  const CF cf(L, cbase, lb, Bp);
-  bool ok1[N1];
-  unsigned off1[N1];
-#pragma unroll
-  for (int j = 0; j < N1; ++j) {
-    int c = c0w - 2 + j;
-    ok1[j] = !EDGE || (c >= 0 && c < W);
-    if (EDGE) c = c < 0 ? 0 : (c > W - 1 ? W - 1 : c);
-    off1[j] = 4u * ((unsigned)(c - (c0w - 2) + 2) * (unsigned)Bp + lb);   // base sits two columns further left
-  }
-  // base: element (r0 - 2, c0w - 4): every offset below is non-negative
-  const i64 tile0 = ((i64)(r0 - 2) * W + (c0w - 4)) * Bp;
-  const Src rr = make_src(rhs + tile0);
-  const unsigned rowB = 4u * (unsigned)W * (unsigned)Bp;
-  const float inv_w0 = 1.0f / w0;
-
-  // x1 on grid row R (window N1): w0 rd (r ib); 0 outside the grid
-  auto x1_row = [&](int R, VT* dst) {
-    if (EDGE && (R < 0 || R >= nyp)) {
-#pragma unroll
-      for (int j = 0; j < N1; ++j) dst[j] = Z;
-      return;
-    }
-    const unsigned sx = (unsigned)(R - (r0 - 2)) * rowB;
-    const i64 rb = (i64)R * W + (c0w - 2);
-#pragma unroll
-    for (int j = 0; j < N1; ++j) {
-      const VT v = ldsrc<VT>(rr, off1[j], sx);
-      i64 i = rb + j;
-      if (EDGE) i = i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
-      const typename CF::T dv = SHARED ? typename CF::T{} : cf.d(i);
-      dst[j] = ok1[j] ? (v * ib) * (w0 * cf.rd(i, dv)) : Z;
-    }
-  };
-  // x2 on grid row R (window N2) from x1 rows R - 1, R, R + 1
-  auto x2_row = [&](int R, const VT* am, const VT* ac, const VT* ap, VT* dst) {
-    if (EDGE && (R < 0 || R >= nyp)) {
-#pragma unroll
-      for (int j = 0; j < N2; ++j) dst[j] = Z;
-      return;
-    }
-    k1_row<VT, N2, ND, EDGE>(cf, n, W, R, c0w - 1, am, ac, ap, [&](int j, VT kx, typename CF::T d0, typename CF::T rd) {
-      const VT bu = ac[j + 1] * (d0 * inv_w0);              // x1 = w0 rd bu  ->  bu = x1 d0 / w0
-      const VT v = ac[j + 1] + (w1 * rd) * (bu - kx);
-      dst[j] = ok1[j + 1] ? v : Z;
-    });
-  };
-
-  VT a0[N1], a1[N1], a2[N1];   // x1 rows R - 1, R, R + 1 of the x2 row being formed
-  VT b0[N2], b1[N2], b2[N2];   // x2 rows row - 1, row, row + 1
-  if constexpr (!SHARED && ND == 3) {
-    // Per-sample coefficients: every coefficient row loaded ONCE into a register window (as in fused_post_body): the
-    // diagonal when the row's x1 is formed (9 columns), its couplings one iteration later for the x2 stage (raw fp16
-    // words), both kept one more iteration for the residual stage; the row below contributes its north couplings.
-    struct CR { VT d[N2]; unsigned e[N2 + 1]; unsigned n[N2]; };   // columns c0w - 1 + j; e[t] = east coupling of column c0w - 2 + t
-    auto at = [&](i64 i) -> i64 { return EDGE ? (i < 0 ? 0 : (i > n - 1 ? n - 1 : i)) : i; };
-    auto load_d = [&](int R, VT* D) {          // diagonal of row R on the N1 columns c0w - 2 + j
-      const i64 base = (i64)R * W + (c0w - 2);
-#pragma unroll
-      for (int j = 0; j < N1; ++j) D[j] = cf.d(at(base + j));
-    };
-    auto load_en = [&](int R, const VT* D, CR& c) {
-      const i64 base = (i64)R * W + (c0w - 2);
-#pragma unroll
-      for (int t = 0; t < N2 + 1; ++t) c.e[t] = cf.e_raw(at(base + t));
-#pragma unroll
-      for (int j = 0; j < N2; ++j) {
-        c.n[j] = cf.n2_raw(at(base + 1 + j));
-        c.d[j] = D[j + 1];
-      }
-    };
-    auto x1c = [&](int R, const VT* D, VT* dst) {
-      if (EDGE && (R < 0 || R >= nyp)) {
-#pragma unroll
-        for (int j = 0; j < N1; ++j) dst[j] = Z;
-        return;
-      }
-      const unsigned sx = (unsigned)(R - (r0 - 2)) * rowB;
-#pragma unroll
-      for (int j = 0; j < N1; ++j) {
-        const VT v = ldsrc<VT>(rr, off1[j], sx);
-        dst[j] = ok1[j] ? (v * ib) * (w0 * (1.0f / D[j])) : Z;
-      }
-    };
-    auto k1c = [&](auto nc_tag, auto off_tag, const CR& c, const unsigned* sn, const VT* xm, const VT* xc, const VT* xq,
-                   auto&& use) {
-      constexpr int NC = decltype(nc_tag)::value, OFF = decltype(off_tag)::value;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) {
-        const int j = k + OFF;
-        const VT d0 = c.d[j];
-        VT acc = d0 * xc[k + 1];
-        acc += cf.cvt(c.e[j + 1]) * xc[k + 2];
-        acc += cf.cvt(c.e[j]) * xc[k];
-        acc += cf.cvt(c.n[j]) * xq[k + 1];
-        acc += cf.cvt(sn[j]) * xm[k + 1];
-        use(k, acc, d0, 1.0f / d0);
-      }
-    };
-    typedef std::integral_constant<int, N2> tN2;
-    typedef std::integral_constant<int, RW> tRW;
-    typedef std::integral_constant<int, 0> t0;
-    typedef std::integral_constant<int, 1> t1;
-    auto x2c = [&](int R, const CR& c, const unsigned* sn, const VT* am, const VT* ac, const VT* ap, VT* dst) {
-      if (EDGE && (R < 0 || R >= nyp)) {
-#pragma unroll
-        for (int j = 0; j < N2; ++j) dst[j] = Z;
-        return;
-      }
-      k1c(tN2{}, t0{}, c, sn, am, ac, ap, [&](int j, VT kx, VT d0, VT rd) {
-        const VT bu = ac[j + 1] * (d0 * inv_w0);
-        const VT v = ac[j + 1] + (w1 * rd) * (bu - kx);
-        dst[j] = ok1[j + 1] ? v : Z;
-      });
-    };
-    VT Dq[N1], Dn[N1];           // diagonals of the newest two x1 rows
-    CR cA, cB;                   // coefficient rows of the x2 row being formed / of the residual row
-    unsigned sS[N2];             // north couplings of the row below the residual row
-    load_d(r0 - 2, Dq);
-    x1c(r0 - 2, Dq, a0);
-    load_en(r0 - 2, Dq, cB);     // only its n is used: south of row r0 - 1
-    load_d(r0 - 1, Dq);
-    x1c(r0 - 1, Dq, a1);
-    load_en(r0 - 1, Dq, cA);
-    load_d(r0, Dn);
-    x1c(r0, Dn, a2);
-    x2c(r0 - 1, cA, cB.n, a0, a1, a2, b0);
-#pragma unroll
-    for (int j = 0; j < N2; ++j) sS[j] = cA.n[j];      // n of row r0 - 1
-#pragma unroll
-    for (int j = 0; j < N1; ++j) { a0[j] = a1[j]; a1[j] = a2[j]; }
-    load_d(r0 + 1, Dq);
-    x1c(r0 + 1, Dq, a2);
-    load_en(r0, Dn, cB);         // coefficient row r0
-    x2c(r0, cB, sS, a0, a1, a2, b1);
-    // loop invariant at the top of iteration `row`: cB = coefficient row `row`, sS = n of row - 1, Dq = diagonal of row + 1
-
-    VT racc[CW], rnext[CW];
-#pragma unroll
-    for (int j = 0; j < CW; ++j) racc[j] = rnext[j] = Z;
-    const int cI0 = (r0 + 1) >> 1, cJ0 = (c0w + 1) >> 1;
-    const int last_store = (r1 >= nyp) ? nyp - 1 : r1 - 2;
-    float* __restrict__ px2 = x2out + ((i64)r0 * W + c0w) * Bp;
-    for (int row = r0; row < r1; ++row) {
-#pragma unroll
-      for (int j = 0; j < N1; ++j) { a0[j] = a1[j]; a1[j] = a2[j]; }
-      load_d(row + 2, Dn);
-      x1c(row + 2, Dn, a2);
-      load_en(row + 1, Dq, cA);
-      x2c(row + 1, cA, cB.n, a0, a1, a2, b2);
-      VT res[RW];
-      k1c(tRW{}, t1{}, cB, sS, b0, b1, b2, [&](int k, VT kx, VT d0, VT) {
-        const VT bu = a0[k + 2] * (d0 * inv_w0);
-        res[k] = (!EDGE || (c0w + k >= 0 && c0w + k < W)) ? bu - kx : Z;
-      });
-      if (row <= last_store) {
-#pragma unroll
-        for (int k = 0; k < RW - 1; ++k) {
-          if (!EDGE || (c0w + k >= 0 && c0w + k < W)) *(VT*)(px2 + (i64)k * Bp + lb) = b1[k + 1];
-        }
-      }
-      px2 += (i64)W * Bp;
-      const bool store = (row & 1) || row + 1 >= nyp;
-      if (!(row & 1)) {
-#pragma unroll
-        for (int j = 0; j < CW; ++j) racc[j] += res[2 * j + 1] + 0.5f * (res[2 * j] + res[2 * j + 2]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < CW; ++j) {
-          racc[j] += 0.5f * (res[2 * j + 1] + res[2 * j]);
-          rnext[j] = 0.5f * (res[2 * j + 1] + res[2 * j + 2]);
-        }
-      }
-      if (store) {
-        const int I = row >> 1;
-        if (I >= cI0) {
-#pragma unroll
-          for (int j = 0; j < CW; ++j) {
-            const int J = cJ0 + j;
-            if (J < cW) {
-              const i64 Ic = (i64)I * cW + J;
-              *(VT*)(crhs + Ic * Bp + lb) = cbc[Ic] ? Z : sb * racc[j];
-            }
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < CW; ++j) { racc[j] = rnext[j]; rnext[j] = Z; }
-      }
-#pragma unroll
-      for (int j = 0; j < N2; ++j) { b0[j] = b1[j]; b1[j] = b2[j]; sS[j] = cB.n[j]; }
-      cB = cA;
-#pragma unroll
-      for (int j = 0; j < N1; ++j) Dq[j] = Dn[j];
-    }
-    return;
-  }
-  x1_row(r0 - 2, a0);
-  x1_row(r0 - 1, a1);
-  x1_row(r0, a2);
-  x2_row(r0 - 1, a0, a1, a2, b0);
-#pragma unroll
-  for (int j = 0; j < N1; ++j) { a0[j] = a1[j]; a1[j] = a2[j]; }
-  x1_row(r0 + 1, a2);
-  x2_row(r0, a0, a1, a2, b1);
-
-  VT racc[CW], rnext[CW];
-#pragma unroll
-  for (int j = 0; j < CW; ++j) racc[j] = rnext[j] = Z;
-  const int cI0 = (r0 + 1) >> 1, cJ0 = (c0w + 1) >> 1;
-  const int last_store = (r1 >= nyp) ? nyp - 1 : r1 - 2;
-  float* __restrict__ px2 = x2out + ((i64)r0 * W + c0w) * Bp;
-
-  for (int row = r0; row < r1; ++row) {
-    // x1 row + 2 -> x2 row + 1
-#pragma unroll
-    for (int j = 0; j < N1; ++j) { a0[j] = a1[j]; a1[j] = a2[j]; }
-    x1_row(row + 2, a2);
-    x2_row(row + 1, a0, a1, a2, b2);
-    // residual of row `row` on the RW columns c0w .. c0w + RW - 1 (unit form, times s_b at the store)
-    VT res[RW];
-    k1_row<VT, RW, ND, EDGE>(cf, n, W, row, c0w, b0, b1, b2, [&](int k, VT kx, typename CF::T d0, typename CF::T) {
-      // bu at (row, c0w + k) from the x1 window kept for this row (a0 after the shift above = x1 row `row`)
-      const VT bu = a0[k + 2] * (d0 * inv_w0);
-      res[k] = (!EDGE || (c0w + k >= 0 && c0w + k < W)) ? bu - kx : Z;
-    });
-    // store x2 of this row on the owned columns
-    if (row <= last_store) {
-#pragma unroll
-      for (int k = 0; k < RW - 1; ++k) {
-        if (!EDGE || (c0w + k >= 0 && c0w + k < W)) *(VT*)(px2 + (i64)k * Bp + lb) = b1[k + 1];
-      }
-    }
-    px2 += (i64)W * Bp;
-    // full weighting, as in strip2_body
-    const bool store = (row & 1) || row + 1 >= nyp;
-    if (!(row & 1)) {
-#pragma unroll
-      for (int j = 0; j < CW; ++j) racc[j] += res[2 * j + 1] + 0.5f * (res[2 * j] + res[2 * j + 2]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < CW; ++j) {
-        racc[j] += 0.5f * (res[2 * j + 1] + res[2 * j]);
-        rnext[j] = 0.5f * (res[2 * j + 1] + res[2 * j + 2]);
-      }
-    }
-    if (store) {
-      const int I = row >> 1;
-      if (I >= cI0) {
-#pragma unroll
-        for (int j = 0; j < CW; ++j) {
-          const int J = cJ0 + j;
-          if (J < cW) {
-            const i64 Ic = (i64)I * cW + J;
-            *(VT*)(crhs + Ic * Bp + lb) = cbc[Ic] ? Z : sb * racc[j];
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < CW; ++j) { racc[j] = rnext[j]; rnext[j] = Z; }
-    }
-#pragma unroll
-    for (int j = 0; j < N2; ++j) { b0[j] = b1[j]; b1[j] = b2[j]; }
-  }
-}
-
-// NW = waves per block (a block owns NW * CW adjacent coarse columns).  Round 4 measured 8 and 16 against 4 on the
-// 1024^2 x 256 bench (gpurun_out/r4c): WIDER blocks read MORE from the fabric, not less (POST 1.56 -> 1.65 / 1.66 read
-// passes: the waves of a larger block drift apart and miss each other's halo lines) and run slower (PRE 0.708 -> 0.740 /
-// 0.818 ms, POST 1.000 -> 0.978 / 1.101 ms, step 81.7 -> 82.6 / 86.6 ms).  4 stays; the parameter documents the experiment.
-template <typename VT, int ND, int CW, bool SHARED, int NW = 4, int MW = (SHARED ? 4 : 1)>
-__global__ __launch_bounds__(64 * NW, MW) void fused_pre_kernel(Level L, const double* __restrict__ scale,
-                                                         const float* __restrict__ rhs, float* __restrict__ x2out,
-                                                         float* __restrict__ crhs, float w0, float w1, int cW,
-                                                         const unsigned char* __restrict__ cbc, int Bp, int ncb, int TR) {
-  constexpr int SPL = VLane<VT>::kSpl;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned lb = blockIdx.y * (SPL * kWave) + SPL * lane;
-  const int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int rc = tile / ncb, cb = tile - rc * ncb;
-  const int nyp = L.ny + 1;
-  const int J0 = (cb * NW + wave) * CW, I0 = rc * TR;
-  const int cnyp = (nyp + 1) >> 1;
-  const int I1 = (I0 + TR < cnyp) ? I0 + TR : cnyp;
-  if (!(J0 < cW && I0 < I1)) return;
-  const int c0w = 2 * J0 - 1;
-  const int r0 = I0 > 0 ? 2 * I0 - 1 : 0;
-  const int r1 = (2 * I1 < nyp) ? 2 * I1 : nyp;
-  const VT sb = VLane<VT>::from_scale(scale, lb);
-  const VT ib = 1.0f / sb;
-  constexpr int RW = 2 * CW + 1;
-  // interior tiles: every window column (c0w - 2 .. c0w + RW + 1) and row (r0 - 2 .. r1 + 1) lies inside the grid
-  const bool edge = c0w - 2 < 0 || c0w + RW + 1 > L.W - 1 || r0 - 2 < 0 || r1 + 1 > nyp - 1;
-  if (edge) fused_pre_body<VT, ND, CW, true, SHARED>(L, ib, sb, rhs, x2out, crhs, w0, w1, cW, cbc, Bp, lb, c0w, r0, r1);
-  else fused_pre_body<VT, ND, CW, false, SHARED>(L, ib, sb, rhs, x2out, crhs, w0, w1, cW, cbc, Bp, lb, c0w, r0, r1);
-}
-
-// ---- POST: prolongation + correction + both post-smoothing sweeps (+ the partials of rhs . z) ------------------------
-// The wave owns the RW columns c0w .. c0w + RW - 1 (c0w a multiple of RW, even); rows r0 .. r1 - 1.
-// Round 4 built and measured a variant in which the 4 waves of a block EXCHANGE their halo columns through LDS instead of
-// each loading (and prolongating) them again: 12 instead of 23 vector-memory loads per wave and fine row, x' and r / s_b
-// written to a two-slot exchange area, ONE workgroup barrier per row.  Correct (28 GPU tests, same iteration counts) and
-// TWICE as slow: 0.999 -> 2.035 ms per fine-level launch at 1024^2 x 256 (gpurun_out/r4o).  The barrier puts the block's
-// waves in lockstep, and these passes live on their waves being at DIFFERENT points of the row loop (one wave's loads in
-// flight under another's arithmetic); any block-cooperative staging of rows pays the same price.  Removed.
-template <typename VT, int ND, int RW, bool EDGE, bool DOT, bool SHARED, bool XZ>
-__device__ __forceinline__ void fused_post_body(const Level& L, VT ib, const float* __restrict__ xin,
-                                                const float* __restrict__ rhs, const float* __restrict__ ec,
-                                                float* __restrict__ zout, float wA, float wB, int cW, int Bp, unsigned lb,
-                                                int c0w, int r0, int r1, Acc& acc) {
-  constexpr int N1 = RW + 4, N2 = RW + 2;    // x' window: columns c0w - 2 + j; x3 window: c0w - 1 + j
-  constexpr int NCE = RW / 2 + 3;            // coarse columns (c0w - 2) / 2 .. (c0w + RW + 1 + 1) / 2
-  const int W = L.W, nyp = L.ny + 1;
-  const i64 n = L.n;
-  const VT Z = VLane<VT>::zero();
-  typedef Coef<VT, SHARED> CF;
-  i64 cbase = (i64)(r0 - 3) * W;
-  if (cbase < 0) cbase = 0;
-  const CF cf(L, cbase, lb, Bp);
-  bool ok1[N1];
-  unsigned off1[N1];
-#pragma unroll
-  for (int j = 0; j < N1; ++j) {
-    int c = c0w - 2 + j;
-    ok1[j] = !EDGE || (c >= 0 && c < W);
-    if (EDGE) c = c < 0 ? 0 : (c > W - 1 ? W - 1 : c);
-    off1[j] = 4u * ((unsigned)(c - (c0w - 2) + 2) * (unsigned)Bp + lb);
-  }
-  const int cj0 = (c0w >> 1) - 1;            // first coarse column of the window (c0w is even)
-  unsigned offc[NCE];
-#pragma unroll
-  for (int j = 0; j < NCE; ++j) {
-    int cj = cj0 + j;
-    cj = cj < 0 ? 0 : (cj > cW - 1 ? cW - 1 : cj);
-    offc[j] = 4u * ((unsigned)cj * (unsigned)Bp + lb);
-  }
-  const i64 tile0 = ((i64)(r0 - 2) * W + (c0w - 4)) * Bp;
-  const Src rx = make_src(XZ ? rhs + tile0 : xin + tile0);   // XZ: x = 0, never loaded
-  const Src rr = make_src(rhs + tile0);
-  const int cr0 = (r0 - 2 > 0 ? r0 - 2 : 0) >> 1;
-  const Src rc = make_src(ec + (i64)cr0 * cW * Bp);
-  const unsigned rowB = 4u * (unsigned)W * (unsigned)Bp, rowCB = 4u * (unsigned)cW * (unsigned)Bp;
-
-  // x' = x + mask (P e) on grid row R
-  auto xp_row = [&](int R, VT* dst) {
-    if (EDGE && (R < 0 || R >= nyp)) {
-#pragma unroll
-      for (int j = 0; j < N1; ++j) dst[j] = Z;
-      return;
-    }
-    const unsigned sx = (unsigned)(R - (r0 - 2)) * rowB;
-    const unsigned sc = (unsigned)((R >> 1) - cr0) * rowCB;
-    // (Keeping the coarse row in registers between fine rows -- it is loaded three times, 7.5 of a row's 23 loads -- was
-    // built and measured in round 4: + 10 live VGPRs spill (100 B of scratch at the 128-VGPR cap of the shared form, 16-100 B
-    // at the 168 cap of the per-sample one): POST 1.000 -> 1.034 ms, per-element-field step 213.5 -> 232.0 ms; gpurun_out/r4i.)
-    // ... and kept in a lane-private LDS ring instead (no barrier, no cross-lane traffic: LDS as a second register file
-    // that bypasses the texture addresser; 2.5 instead of 7.5 memory loads per fine row): correct and 1.002 -> 1.417 ms --
-    // LDS and scalar loads share one counter (lgkmcnt), and the waits for the ring serialise the coefficient loads of
-    // both stages (gpurun_out/r4r).  Removed as well.
-    VT ce[NCE], ce2[NCE];
-#pragma unroll
-    for (int j = 0; j < NCE; ++j) {
-      ce[j] = ldsrc<VT>(rc, offc[j], sc);
-      ce2[j] = (R & 1) ? ldsrc<VT>(rc, offc[j], sc + rowCB) : Z;
-    }
-    const i64 rb = (i64)R * W + (c0w - 2);
-#pragma unroll
-    for (int j = 0; j < N1; ++j) {
-      VT corr;
-      if (!(j & 1))                      // even window column <-> coarse column cj0 + j / 2
-        corr = (R & 1) ? 0.5f * (ce[j / 2] + ce2[j / 2]) : ce[j / 2];
-      else                               // between coarse columns cj0 + (j - 1) / 2 and + 1
-        corr = (R & 1) ? 0.5f * (ce[(j + 1) / 2] + ce2[(j - 1) / 2]) : 0.5f * (ce[(j - 1) / 2] + ce[(j + 1) / 2]);
-      i64 i = rb + j;
-      if (EDGE) i = i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
-      const VT v = XZ ? L.mk32[i] * corr : ldsrc<VT>(rx, off1[j], sx) + L.mk32[i] * corr;
-      dst[j] = ok1[j] ? v : Z;
-    }
-  };
-  // bu = r / s_b on grid row R at the N2 columns c0w - 1 + j
-  auto bu_row = [&](int R, VT* dst) {
-    if (EDGE && (R < 0 || R >= nyp)) {
-#pragma unroll
-      for (int j = 0; j < N2; ++j) dst[j] = Z;
-      return;
-    }
-    const unsigned sx = (unsigned)(R - (r0 - 2)) * rowB;
-#pragma unroll
-    for (int j = 0; j < N2; ++j) dst[j] = ok1[j + 1] ? ldsrc<VT>(rr, off1[j + 1], sx) * ib : Z;
-  };
-  // x3 on grid row R (window N2) from x' rows R - 1, R, R + 1 and bu row R
-  auto x3_row = [&](int R, const VT* am, const VT* ac, const VT* ap, const VT* bu, VT* dst) {
-    if (EDGE && (R < 0 || R >= nyp)) {
-#pragma unroll
-      for (int j = 0; j < N2; ++j) dst[j] = Z;
-      return;
-    }
-    k1_row<VT, N2, ND, EDGE>(cf, n, W, R, c0w - 1, am, ac, ap, [&](int j, VT kx, typename CF::T, typename CF::T rd) {
-      const VT v = ac[j + 1] + (wA * rd) * (bu[j] - kx);
-      dst[j] = ok1[j + 1] ? v : Z;
-    });
-  };
-
-  VT a0[N1], a1[N1], a2[N1];   // x' rows
-  VT b0[N2], b1[N2], b2[N2];   // x3 rows row - 1, row, row + 1
-  VT u1[N2], u2[N2];           // bu rows row, row + 1
-  if constexpr (!SHARED && ND == 3) {
-    // Per-sample coefficients (fp32 diagonal + fp16 couplings, one value per lane and sample): every coefficient row is
-    // needed four times -- by the x3 stage and the z stage, as the row's own couplings and as the south couplings of the
-    // row above -- and re-loading it each time missed the caches about half the time (PMC: 4.54 passes of traffic for
-    // 2.6 algorithmic, 5.4 TB/s: bandwidth-bound on wasted re-reads).  Rows are loaded ONCE into a register window, the
-    // couplings kept as raw fp16 words (one VGPR per pair of samples).
-    struct CRow { VT d[N2]; unsigned e[N2 + 1]; unsigned n[N2]; };   // columns c0w - 1 + j; e[j + 1] = east coupling of column j
-    auto load_crow = [&](int R, CRow& c) {
-      const i64 base = (i64)R * W + (c0w - 1);
-      auto at = [&](i64 i) -> i64 { return EDGE ? (i < 0 ? 0 : (i > n - 1 ? n - 1 : i)) : i; };
-      c.e[0] = cf.e_raw(at(base - 1));
-#pragma unroll
-      for (int j = 0; j < N2; ++j) {
-        const i64 i = at(base + j);
-        c.d[j] = cf.d(i);
-        c.e[j + 1] = cf.e_raw(i);
-        c.n[j] = cf.n2_raw(i);
-      }
-    };
-    // K_1 x on NC columns starting at cached column OFF, row couplings c, south couplings sn (the n of the row below)
-    auto k1c = [&](auto nc_tag, auto off_tag, const CRow& c, const unsigned* sn, const VT* xm, const VT* xc, const VT* xq,
-                   auto&& use) {
-      constexpr int NC = decltype(nc_tag)::value, OFF = decltype(off_tag)::value;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) {
-        const int j = k + OFF;
-        const VT d0 = c.d[j];
-        VT acc = d0 * xc[k + 1];
-        acc += cf.cvt(c.e[j + 1]) * xc[k + 2];
-        acc += cf.cvt(c.e[j]) * xc[k];
-        acc += cf.cvt(c.n[j]) * xq[k + 1];
-        acc += cf.cvt(sn[j]) * xm[k + 1];
-        use(k, acc, d0, 1.0f / d0);
-      }
-    };
-    typedef std::integral_constant<int, N2> tN2;
-    typedef std::integral_constant<int, RW> tRW;
-    typedef std::integral_constant<int, 0> t0;
-    typedef std::integral_constant<int, 1> t1;
-    auto x3c = [&](int R, const CRow& c, const unsigned* sn, const VT* am, const VT* ac, const VT* ap, const VT* bu, VT* dst) {
-      if (EDGE && (R < 0 || R >= nyp)) {
-#pragma unroll
-        for (int j = 0; j < N2; ++j) dst[j] = Z;
-        return;
-      }
-      k1c(tN2{}, t0{}, c, sn, am, ac, ap, [&](int j, VT kx, VT, VT rd) {
-        const VT v = ac[j + 1] + (wA * rd) * (bu[j] - kx);
-        dst[j] = ok1[j + 1] ? v : Z;
-      });
-    };
-    CRow cS, cC, cN;             // coefficient rows R - 1, R, R + 1 of the x3 row being formed
-    load_crow(r0 - 2, cS);
-    load_crow(r0 - 1, cC);
-    xp_row(r0 - 2, a0);
-    xp_row(r0 - 1, a1);
-    xp_row(r0, a2);
-    bu_row(r0 - 1, u1);
-    x3c(r0 - 1, cC, cS.n, a0, a1, a2, u1, b0);
-#pragma unroll
-    for (int j = 0; j < N1; ++j) { a0[j] = a1[j]; a1[j] = a2[j]; }
-    xp_row(r0 + 1, a2);
-    bu_row(r0, u1);
-    load_crow(r0, cN);
-    x3c(r0, cN, cC.n, a0, a1, a2, u1, b1);
-    // from here on: cS = row - 1 (only its n is used), cC = row, cN = row + 1
-#pragma unroll
-    for (int j = 0; j < N2; ++j) cS.n[j] = cC.n[j];
-    cC = cN;
-    float* __restrict__ pz = zout + ((i64)r0 * W + c0w) * Bp;
-    for (int row = r0; row < r1; ++row) {
-#pragma unroll
-      for (int j = 0; j < N1; ++j) { a0[j] = a1[j]; a1[j] = a2[j]; }
-      xp_row(row + 2, a2);
-      bu_row(row + 1, u2);
-      load_crow(row + 1, cN);
-      x3c(row + 1, cN, cC.n, a0, a1, a2, u2, b2);
-      k1c(tRW{}, t1{}, cC, cS.n, b0, b1, b2, [&](int k, VT kx, VT, VT rd) {
-        if (!EDGE || c0w + k < W) {
-          const VT z = b1[k + 1] + (wB * rd) * (u1[k + 1] - kx);
-          *(VT*)(pz + (i64)k * Bp + lb) = z;
-          if (DOT) VLane<VT>::dot(acc, u1[k + 1], z);
-        }
-      });
-      pz += (i64)W * Bp;
-#pragma unroll
-      for (int j = 0; j < N2; ++j) { b0[j] = b1[j]; b1[j] = b2[j]; u1[j] = u2[j]; cS.n[j] = cC.n[j]; }
-      cC = cN;
-    }
-    return;
-  }
-  xp_row(r0 - 2, a0);
-  xp_row(r0 - 1, a1);
-  xp_row(r0, a2);
-  bu_row(r0 - 1, u1);
-  x3_row(r0 - 1, a0, a1, a2, u1, b0);
-#pragma unroll
-  for (int j = 0; j < N1; ++j) { a0[j] = a1[j]; a1[j] = a2[j]; }
-  xp_row(r0 + 1, a2);
-  bu_row(r0, u1);
-  x3_row(r0, a0, a1, a2, u1, b1);
-  float* __restrict__ pz = zout + ((i64)r0 * W + c0w) * Bp;
-
-  // (A software-pipelined form of this loop -- the raw loads of the next row requested before this row's two stencil stages,
-  // 48 more live VGPRs, 3 instead of 4 waves per SIMD -- was built and measured at the end of round 4: correct, 168 VGPRs with
-  // 80 B of scratch, 0.999 -> 1.321 ms per fine-level launch, step 80.8 -> 87.5 ms, gpurun_out/r4bj.  Independent waves hide the
-  // row's load latency better than one wave overlapping its own rows.)
-  for (int row = r0; row < r1; ++row) {
-#pragma unroll
-    for (int j = 0; j < N1; ++j) { a0[j] = a1[j]; a1[j] = a2[j]; }
-    xp_row(row + 2, a2);
-    bu_row(row + 1, u2);
-    x3_row(row + 1, a0, a1, a2, u2, b2);
-    k1_row<VT, RW, ND, EDGE>(cf, n, W, row, c0w, b0, b1, b2, [&](int k, VT kx, typename CF::T, typename CF::T rd) {
-      if (!EDGE || c0w + k < W) {
-        const VT z = b1[k + 1] + (wB * rd) * (u1[k + 1] - kx);
-        *(VT*)(pz + (i64)k * Bp + lb) = z;
-        if (DOT) VLane<VT>::dot(acc, u1[k + 1], z);     // (r / s_b) . z; times s_b after the loop
-      }
-    });
-    pz += (i64)W * Bp;
-#pragma unroll
-    for (int j = 0; j < N2; ++j) { b0[j] = b1[j]; b1[j] = b2[j]; u1[j] = u2[j]; }
-  }
-}
-
-// XZ: the operand is P e alone (x = 0 is not read): two sweeps from a prolonged initial guess, the first stage of a
-// full-multigrid level (vcycle with `guess`)
-template <typename VT, int ND, int RW, bool DOT, bool SHARED, bool XZ = false, int NW = 4, int MW = (SHARED ? 4 : 1)>
-__global__ __launch_bounds__(64 * NW, MW) void fused_post_kernel(Level L, const double* __restrict__ scale,
-                                                          const float* __restrict__ xin, const float* __restrict__ rhs,
-                                                          const float* __restrict__ ec, float* __restrict__ zout, float wA,
-                                                          float wB, int cW, double* __restrict__ part, int Bp, int ncb,
-                                                          int TR) {
-  __shared__ double lds[NW * kWave];
-  constexpr int SPL = VLane<VT>::kSpl;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned lb = blockIdx.y * (SPL * kWave) + SPL * lane;
-  const int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int rc = tile / ncb, cb = tile - rc * ncb;
-  const int nyp = L.ny + 1;
-  const int c0w = (cb * NW + wave) * RW;
-  const int r0 = rc * TR;
-  const int r1 = (r0 + TR < nyp) ? r0 + TR : nyp;
-  const bool active = c0w < L.W && r0 < r1;
-  const VT sb = VLane<VT>::from_scale(scale, lb);
-  const VT ib = 1.0f / sb;
-  Acc acc;
-  if (active) {
-    const bool edge = c0w - 2 < 0 || c0w + RW + 1 > L.W - 1 || r0 - 2 < 0 || r1 + 1 > nyp - 1;
-    if (edge)
-      fused_post_body<VT, ND, RW, true, DOT, SHARED, XZ>(L, ib, xin, rhs, ec, zout, wA, wB, cW, Bp, lb, c0w, r0, r1, acc);
-    else
-      fused_post_body<VT, ND, RW, false, DOT, SHARED, XZ>(L, ib, xin, rhs, ec, zout, wA, wB, cW, Bp, lb, c0w, r0, r1, acc);
-  }
-  if (DOT) {
-#pragma unroll
-    for (int q = 0; q < SPL; ++q) {
-      const double f = scale ? scale[lb + q] : 1.0;
-      const double t = block_sum_waves<NW>(acc.v[q] * f, lds);
-      if (wave == 0) part[(i64)blockIdx.x * Bp + lb + q] = t;
-    }
-  }
-}
-
-// ---- CG step of a batch-shared matrix with fp32-stored directions, two samples per lane -------------------------------
-// p = z + beta p_old (fp32 fused multiply-add: the stored value), p . (K_1 p) with the stencil in packed fp32 on the fp32
-// coefficient copies, accumulated per sample in fp64; A p itself is never stored (the residual update recomputes it in
-// fp64 from the stored p, F_RUPD).  The fp32 stencil only enters the STEP LENGTH alpha = r.z / p.Ap: x += alpha p and
-// r -= alpha A p use the same alpha and the exact (fp64) A p, so r = b - A x holds to fp64 whatever alpha is, and an
-// error delta in alpha costs delta^2 of the energy reduction of the step (the minimum of a parabola).
-template <typename VT, int ND, int RW, bool EDGE>
-__device__ __forceinline__ void cgstep2_body(const Level& L, VT beta, bool first, const float* __restrict__ z,
-                                             const float* __restrict__ pin, float* __restrict__ pout, int Bp, unsigned lb,
-                                             int c0w, int r0, int r1, Acc& acc) {
-  constexpr int N = RW + 2;                  // window columns c0w - 1 + j
-  const int W = L.W, nyp = L.ny + 1;
-  const i64 n = L.n;
-  const VT Z = VLane<VT>::zero();
-  const Coef<VT, true> cf(L, 0, lb, Bp);
-  bool ok[N];
-  unsigned off[N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    int c = c0w - 1 + j;
-    ok[j] = !EDGE || (c >= 0 && c < W);
-    if (EDGE) c = c < 0 ? 0 : (c > W - 1 ? W - 1 : c);
-    off[j] = 4u * ((unsigned)(c - (c0w - 1) + 1) * (unsigned)Bp + lb);      // base sits one column further left
-  }
-  const i64 tile0 = ((i64)(r0 - 1) * W + (c0w - 2)) * Bp;                  // element (r0 - 1, c0w - 2)
-  const Src rz = make_src(z + tile0);
-  const Src rp = make_src(first ? z + tile0 : pin + tile0);
-  const unsigned rowB = 4u * (unsigned)W * (unsigned)Bp;
-  auto p_row = [&](int R, VT* dst) {
-    if (EDGE && (R < 0 || R >= nyp)) {
-#pragma unroll
-      for (int j = 0; j < N; ++j) dst[j] = Z;
-      return;
-    }
-    const unsigned sx = (unsigned)(R - (r0 - 1)) * rowB;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      VT v = ldsrc<VT>(rz, off[j], sx);
-      if (!first) v += beta * ldsrc<VT>(rp, off[j], sx);
-      dst[j] = ok[j] ? v : Z;
-    }
-  };
-  VT a0[N], a1[N], a2[N];
-  p_row(r0 - 1, a0);
-  p_row(r0, a1);
-  float* __restrict__ pp = pout + ((i64)r0 * W + c0w) * Bp;
-  for (int row = r0; row < r1; ++row) {
-    p_row(row + 1, a2);
-    k1_row<VT, RW, ND, EDGE>(cf, n, W, row, c0w, a0, a1, a2, [&](int k, VT kx, float, float) {
-      if (!EDGE || c0w + k < W) {
-        __builtin_nontemporal_store(a1[k + 1], (VT*)(pp + (i64)k * Bp + lb));
-        VLane<VT>::dot(acc, a1[k + 1], kx);
-      }
-    });
-    pp += (i64)W * Bp;
-#pragma unroll
-    for (int j = 0; j < N; ++j) { a0[j] = a1[j]; a1[j] = a2[j]; }
-  }
-}
-
-template <typename VT, int ND, int RW, int MW>
-__global__ __launch_bounds__(256, MW) void cgstep2_kernel(Level L, const double* __restrict__ scale,
-                                                           const double* __restrict__ beta, int first,
-                                                           const float* __restrict__ z, const float* __restrict__ pin,
-                                                           float* __restrict__ pout, double* __restrict__ part, int Bp,
-                                                           int ncb, int TR) {
-  __shared__ double lds[4 * kWave];
-  constexpr int SPL = VLane<VT>::kSpl;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned lb = blockIdx.y * (SPL * kWave) + SPL * lane;
-  const int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int rc = tile / ncb, cb = tile - rc * ncb;
-  const int nyp = L.ny + 1;
-  const int c0w = (cb * 4 + wave) * RW;
-  const int r0 = rc * TR;
-  const int r1 = (r0 + TR < nyp) ? r0 + TR : nyp;
-  Acc acc;
-  if (c0w < L.W && r0 < r1) {
-    const VT bt = first ? VLane<VT>::zero() : VLane<VT>::from_scale(beta, lb);
-    const bool edge = c0w - 1 < 0 || c0w + RW > L.W - 1 || r0 - 1 < 0 || r1 > nyp - 1;
-    if (edge) cgstep2_body<VT, ND, RW, true>(L, bt, first != 0, z, pin, pout, Bp, lb, c0w, r0, r1, acc);
-    else cgstep2_body<VT, ND, RW, false>(L, bt, first != 0, z, pin, pout, Bp, lb, c0w, r0, r1, acc);
-  }
-#pragma unroll
-  for (int q = 0; q < SPL; ++q) {
-    const double f = scale ? scale[lb + q] : 1.0;
-    const double t = block_sum_per_sample(acc.v[q] * f, Bp, lds);
-    if (wave == 0) part[(i64)blockIdx.x * Bp + lb + q] = t;
-  }
-}
-
-constexpr int kStripCols = 8;
-// fp32-stored V-cycle vectors run best on 4-column strips (kernel trace, same box: prolongation + sweep -7 %,
-// first two sweeps -5 % against 8 columns); fp64 vectors keep 8 (half the register footprint per column there)
-template <typename TV>
-constexpr int strip_cols() { return sizeof(TV) == 4 ? 4 : kStripCols; }
-constexpr int kRestrictCols = 2;  // coarse columns per wave of the fused residual + restriction (5 fine columns; 3, 4, 6: slower)
-constexpr int kPupdCols = 4;  // narrower strips for the 3-stream fused CG kernel: fewer VGPRs, more waves
-constexpr int kPartBlocks = 2048;  // capacity (in blocks) of every partial-sum buffer
-// blocks (of 4 waves) a strip-kernel launch aims at; the tile height follows from it
-constexpr int kStripBlocks = 6144;
-// small levels: one wave marching down a strip is latency-bound; the simple kernels win below ~200^2
-// 128: the 129^2 level of a 1024^2 hierarchy takes the strip / fused kernels too (-0.7 ms per step; 64: slower again)
-constexpr int kStripMinW = 128;
-
-struct StripGeom {
-  bool use;
-  int ncb, nrc, TR;
-};
-
-inline StripGeom strip_geom(const Level& L, int Bp, int rw = kStripCols, int spl = 1, int nw = 4) {
-  StripGeom g{false, 0, 0, 0};
-  if (Bp < kWave || L.W < kStripMinW || L.ny + 1 < 64) return g;
-  g.use = true;
-  g.ncb = (L.W + nw * rw - 1) / (nw * rw);   // nw = waves (strips) per block
-  const int gy = Bp / (kWave * spl);   // spl = samples per lane (2: dia_strip2_kernel)
-  if (gy < 1) { g.use = false; return g; }   // fewer samples than one wave of that form holds
-  const int target = kStripBlocks * 4 / nw;   // the same number of WAVES (and tile height) whatever the block width
-  int nrc = (target + g.ncb * gy - 1) / (g.ncb * gy);
-  const int nyp = L.ny + 1;
-  if (nrc > nyp / 8) nrc = nyp / 8;
-  if (nrc < 1) nrc = 1;
-  while (g.ncb * nrc > kPartBlocks) --nrc;
-  g.TR = (nyp + nrc - 1) / nrc;
-  g.nrc = (nyp + g.TR - 1) / g.TR;
-  return g;
-}
-
-template <typename TV, int MODE, bool XFROMB, int FUSE = F_NONE, typename TA = TV, int RW = kStripCols, int MINW = 1>
-void launch_strip(const Level& L, int Bv, const double* scale, const TV* xin, const TV* bvec, TV* out,
-                  double omega, double omega_in, double* part, int Bp, const StripGeom& g, hipStream_t st,
-                  const Extra& ex = Extra{}) {
-  dim3 grid(g.ncb * g.nrc, Bp / kWave);
-  // per-sample matrices inside the fp32 V-cycle read the fp32 copy of the coefficients
-  const bool m32 = (sizeof(TV) == 4) && Bv != 1 && L.v32 != nullptr;
-  const bool m16 = m32 && L.o16 != nullptr;   // fp32 diagonal + fp16 off-diagonals
-  {  // algorithmic bytes per (node, sample) of this launch (diffhe_traffic_account)
-    const double tv = sizeof(TV), ta = sizeof(TA);
-    double bpn;
-    if (MODE == M_JACOBI) bpn = (XFROMB ? 2.0 : 3.0) * tv + (FUSE == F_PROLONG ? 0.25 * tv : 0.0);
-    else if (MODE == M_RESID) bpn = 2.0 * tv + (FUSE == F_RESTRICT ? 0.25 * tv : (out ? tv : 0.0) + (ex.r32 ? 4.0 : 0.0));
-    else if (is_pupd(FUSE)) bpn = (ex.first ? 2.0 * ta : 3.0 * ta) + (out ? 8.0 : 0.0) + ((FUSE == F_PUPD && ex.x) ? 16.0 : 0.0);
-    else if (FUSE == F_RUPD) bpn = ta + 16.0 + (ex.r32 ? 4.0 : 0.0);
-    else bpn = tv + (out ? tv : 0.0) + (ex.dotv ? 8.0 : 0.0);
-    if (Bv != 1) bpn += m16 ? 4.0 + 2.0 * (L.nd - 1) : L.nd * (m32 ? 4.0 : 8.0);
-    diffhe::account(bpn * (double)L.n * Bp);
-  }
-#define STRIP(ND_, SH_, TM_)                                                                                       \
-  hipLaunchKernelGGL((dia_strip_kernel<TV, TA, TM_, MODE, FUSE, ND_, SH_, XFROMB, RW, MINW>), grid, dim3(256), 0, st, L,   \
-                     scale, xin, bvec, out, omega, omega_in, ex, part, Bp, g.ncb, g.TR)
-#define STRIP_SHIFT(ND_)                                                                                           \
-  hipLaunchKernelGGL((dia_strip_shift_kernel<TV, TA, MODE, FUSE, ND_, XFROMB, RW, MINW>), grid, dim3(256), 0, st, L, scale, \
-                     xin, bvec, out, omega, omega_in, ex, part, Bp, g.ncb, g.TR)
-  // fp32 / fp16 coefficient copies only in a cycle with fp32 vectors (m32): other instantiations could never launch
-#define STRIP_ND(ND_)                                                                                              \
-  do {                                                                                                             \
-    if (Bv == 1) STRIP(ND_, true, double);                                                                         \
-    else if constexpr (sizeof(TV) == 4) {                                                                          \
-      if (m16) STRIP(ND_, false, h16m); else if (m32) STRIP(ND_, false, float); else STRIP(ND_, false, double);   \
-    } else STRIP(ND_, false, double);                                                                              \
-  } while (0)
-  if (Bv == 1 && L.shift) {
-    if (L.nd == 3) STRIP_SHIFT(3); else STRIP_SHIFT(4);
-  } else if (L.nd == 3) {
-    STRIP_ND(3);
-  } else {
-    STRIP_ND(4);
-  }
-#undef STRIP_ND
-#undef STRIP
-#undef STRIP_SHIFT
-}
-
-// fp32 V-cycle, batch-shared matrix with fp32 coefficient copies and reciprocal diagonal, batch a multiple of 128,
-// no diagonal shift: the two-samples-per-lane kernels apply
-inline bool shared32_ok(const Level& L, int Bv, int Bp) {   // the fp32 copies of a batch-shared matrix are there, whole waves
-  return Bv == 1 && L.v32 && L.rd32 && L.mk32 && !L.shift && Bp % kWave == 0;
-}
-inline bool strip2_ok(const Level& L, int Bv, int Bp) { return shared32_ok(L, Bv, Bp) && Bp % (2 * kWave) == 0; }
-// the kernels address their tile (`rows` fine rows + the window's two halo rows) with 32-bit byte offsets
-inline bool strip2_tile_fits(const Level& L, int Bp, int rows) { return 4LL * (rows + 3) * L.W * Bp < (1LL << 31); }
-// geometry for the two-samples-per-lane kernels if they apply to this level (and its tiles fit), else the usual one
-template <typename TV>
-inline bool strip2_pick(const Level& L, int Bv, int Bp, int rw, StripGeom* g) {
-  if (sizeof(TV) == 4 && strip2_ok(L, Bv, Bp)) {
-    *g = strip_geom(L, Bp, rw, 2);
-    if (!g->use || strip2_tile_fits(L, Bp, g->TR)) return g->use;
-  }
-  *g = strip_geom(L, Bp, rw, 1);
-  return false;
-}
-
-template <int MODE, bool XFROMB, int FUSE, int RW>
-void launch_strip2(const Level& L, const double* scale, const float* xin, const float* bvec, float* out, double omega,
-                   double omega_in, double* part, int Bp, const StripGeom& g, hipStream_t st, const Extra& ex = Extra{}) {
-  dim3 grid(g.ncb * g.nrc, Bp / (2 * kWave));
-  double bpn;  // algorithmic bytes per (node, sample), as launch_strip
-  if (MODE == M_JACOBI) bpn = (XFROMB ? 2.0 : 3.0) * 4.0 + (FUSE == F_PROLONG ? 1.0 : 0.0);
-  else bpn = 8.0 + (FUSE == F_RESTRICT ? 1.0 : 4.0);
-  diffhe::account(bpn * (double)L.n * Bp);
-  // 40 000 B of dynamic LDS per block cap the residency at 4 blocks (16 waves) per CU: measured best for these kernels
-  // (sweep over 3 .. 7 blocks per CU on one box, gpurun_out/r3d: first two sweeps 0.506 / prolongation 0.803 / restriction
-  // 0.582 ms at 4 against 0.514-0.523 / 0.815-0.818 / 0.589-0.590 unrestricted)
-  constexpr unsigned dyn_lds = 40000u;
-#define STRIP2(ND_, DOT_)                                                                                                  \
-  hipLaunchKernelGGL((dia_strip2_kernel<MODE, FUSE, ND_, XFROMB, RW, DOT_, false>), grid, dim3(256), dyn_lds, st, L, scale, xin, \
-                     bvec, out, (float)omega, (float)omega_in, ex, part, Bp, g.ncb, g.TR)
-  if (MODE == M_JACOBI && part) {   // the sweep that leaves the partials of rhs . x (the CG's r.z)
-    if (L.nd == 3) STRIP2(3, MODE == M_JACOBI); else STRIP2(4, MODE == M_JACOBI);
-  } else {
-    if (L.nd == 3) STRIP2(3, false); else STRIP2(4, false);
-  }
-#undef STRIP2
-}
-
-// Fused two-stage passes (fused_pre_kernel / fused_post_kernel), two samples per lane where the batch allows (fill_hier).
-// They run without dynamic LDS: a cap on the blocks resident per CU only slowed them (118-125 VGPRs: 4 waves per SIMD
-// anyway; run r3w: 93.9 ms per step uncapped, 94.4 at 40 000 B per block, 103.8 at 54 000).
-// They apply to: a batch-shared matrix with its fp32 copy, reciprocal diagonal and mask (strip2_ok), or a
-// per-sample matrix with the compact copies (fp32 diagonal + scaled fp16 off-diagonals) and the mask, no per-sample scale
-// returns a bit mask: 1 = the PRE pass may be fused, 2 = the POST pass
-inline int fused_ok(const Level& L, int Bv, int Bp, const double* scale) {
-  // batch-shared matrix: two samples per lane for multiples of 128, else ONE per lane (batches of 64 or 192 per GPU --
-  // BASELINE config 5's shard: same fused passes, fp32 arithmetic, 4-byte accesses)
-  if (shared32_ok(L, Bv, Bp)) return 3;
-  // per-sample matrices: both passes fused, with the coefficient rows cached in registers (fp16 couplings as raw words:
-  // 174 / 206 VGPRs, 2 waves per SIMD, no spills).  Without the cache the PRE pass needed 256 VGPRs and measured slower
-  // than its two single passes (forward solve 153 ms against 140), and the POST pass re-read every coefficient row four
-  // times (PMC 4.5 passes of traffic for 2.6 algorithmic); 1024^2 x 256 step: 245 (POST only, uncached) -> 236 (POST
-  // cached) -> 219 ms (both, cached; runs r5b, r5d).
-  return (Bv == Bp && Bp % (2 * kWave) == 0 && L.v32 && L.o16 && L.mk32 && !L.shift && !scale) ? 3 : 0;
-}
-
-void launch_fused_pre(const Level& L, const Level& C, int Bv, const double* scale, const float* rhs, float* x2, float* crhs,
-                      double w0, double w1, int Bp, const StripGeom& g, int spl, hipStream_t st, int nw = 4) {
-  constexpr int CW = kRestrictCols;
-  // r read, x2 and the coarse rhs written; per-sample matrices: + the compact coefficients (read by both stages)
-  diffhe::account((9.0 + (Bv == 1 ? 0.0 : 4.0 + 2.0 * (L.nd - 1))) * (double)L.n * Bp);
-  const dim3 grid(g.ncb * g.nrc, Bp / (spl * kWave));
-#define FPRE(VT_, ND_, SH_)                                                                                               \
-  hipLaunchKernelGGL((fused_pre_kernel<VT_, ND_, CW, SH_>), grid, dim3(256), 0, st, L, scale, rhs, x2, crhs,              \
-                     (float)w0, (float)w1, C.W, C.bc, Bp, g.ncb, g.TR)
-  // per-sample coefficients: 206 VGPRs = 2 waves per SIMD; capped at 168 (3 waves) it spills and loses (launch_fused_post)
-  if (Bv != 1) { if (L.nd == 3) FPRE(v2f, 3, false); else FPRE(v2f, 4, false); }
-  else if (spl == 4 && L.nd == 3)
-    hipLaunchKernelGGL((fused_pre_kernel<v4f, 3, CW, true, 4, 2>), grid, dim3(256), 0, st, L, scale, rhs, x2, crhs,
-                       (float)w0, (float)w1, C.W, C.bc, Bp, g.ncb, g.TR);
-  else if (spl >= 2) { if (L.nd == 3) FPRE(v2f, 3, true); else FPRE(v2f, 4, true); }
-  else { if (L.nd == 3) FPRE(float, 3, true); else FPRE(float, 4, true); }
-#undef FPRE
-}
-
-void launch_fused_post(const Level& L, const Level& C, int Bv, const double* scale, const float* xin, const float* rhs,
-                       const float* ec, float* z, double wA, double wB, double* part, int Bp, const StripGeom& g, int spl,
-                       hipStream_t st, int nw = 4) {
-  // x2, r, a quarter of e read; z written (+ compact coefficients of a per-sample matrix); xin == NULL: x2 = 0, not read
-  diffhe::account(((xin ? 13.0 : 9.0) + (Bv == 1 ? 0.0 : 4.0 + 2.0 * (L.nd - 1))) * (double)L.n * Bp);
-  const dim3 grid(g.ncb * g.nrc, Bp / (spl * kWave));
-#define FPOST(VT_, ND_, DOT_, SH_, XZ_)                                                                                      \
-  hipLaunchKernelGGL((fused_post_kernel<VT_, ND_, 4, DOT_, SH_, XZ_>), grid, dim3(256), 0, st, L, scale, xin, rhs, ec,         \
-                     z, (float)wA, (float)wB, C.W, part, Bp, g.ncb, g.TR)
-#define FPOSTD(VT_, ND_, SH_)                                                                                              \
-  do {                                                                                                                     \
-    if (!xin) FPOST(VT_, ND_, false, SH_, true);                                                                          \
-    else if (part) FPOST(VT_, ND_, true, SH_, false);                                                                     \
-    else FPOST(VT_, ND_, false, SH_, false);                                                                              \
-  } while (0)
-  // per-sample coefficients: the POST pass needs 173 VGPRs uncapped (176 allocated: 2 waves per SIMD); capped at 168 it runs
-  // 3 waves per SIMD without spills: 218.1 -> 213.5 ms per 1024^2 x 256 step of the per-element-field workload; the PRE pass
-  // (206 VGPRs) spills under the same cap: 248.9 ms (run r4e)
-  if (Bv != 1 && L.nd == 3) {
-#define FPOSTM(DOT_, XZ_)                                                                                                  \
-  hipLaunchKernelGGL((fused_post_kernel<v2f, 3, 4, DOT_, false, XZ_, 4, 3>), grid, dim3(256), 0, st, L, scale, xin,         \
-                     rhs, ec, z, (float)wA, (float)wB, C.W, part, Bp, g.ncb, g.TR)
-    if (!xin) FPOSTM(false, true); else if (part) FPOSTM(true, false); else FPOSTM(false, false);
-#undef FPOSTM
-  }
-  else if (Bv != 1) { if (L.nd == 3) FPOSTD(v2f, 3, false); else FPOSTD(v2f, 4, false); }
-  else if (spl >= 2) { if (L.nd == 3) FPOSTD(v2f, 3, true); else FPOSTD(v2f, 4, true); }
-  else { if (L.nd == 3) FPOSTD(float, 3, true); else FPOSTD(float, 4, true); }
-#undef FPOSTD
-#undef FPOST
 }
 
 // One step of the Chebyshev semi-iteration (three-term form) on the coarsest level:
@@ -2110,34 +252,6 @@ inline bool transfers2_ok(const Level& F, const Level& C, int Bp, size_t esz) {
   return esz == 4 && F.nx == 2 * C.nx && F.ny == 2 * C.ny && Bp % (2 * kWave) == 0;
 }
 inline dim3 transfer2_grid(int n, int Bp) { return dim3((unsigned)(((i64)n + 3) / 4 < 4096 ? ((i64)n + 3) / 4 : 4096), Bp / (2 * kWave)); }
-
-// per-element kappa of the coarse triangulation.  Full coarsening (sx = sy = 2): mean of the 4 children
-// (Galerkin for nested P1).  Semi-coarsening: both coarse triangles of a cell take the mean of the 4 fine
-// triangles of the 2 fine cells it covers.
-__global__ __launch_bounds__(256) void mg_restrict_kappa_kernel(const double* __restrict__ kf, double* __restrict__ kc,
-                                                                 int nxc, int nyc, int sx, int sy, int Bv) {
-  const NodeMap nm = node_map(Bv);
-  const int mc = 2 * nxc * nyc, nxf = sx * nxc;
-  for (int E = nm.node0; E < mc; E += nm.stride) {
-    const int q = E >> 1, up = E & 1;
-    const int I = q / nxc, J = q - I * nxc;
-    // fine element id = 2*(row*nxf + col) + upper
-    auto fe = [&](int r, int c, int u) { return (i64)(2 * ((i64)r * nxf + c) + u) * Bv + nm.b; };
-    double s;
-    if (sx == 2 && sy == 2) {
-      if (!up)
-        s = kf[fe(2 * I, 2 * J, 0)] + kf[fe(2 * I, 2 * J, 1)] + kf[fe(2 * I, 2 * J + 1, 0)] + kf[fe(2 * I + 1, 2 * J, 0)];
-      else
-        s = kf[fe(2 * I + 1, 2 * J + 1, 1)] + kf[fe(2 * I + 1, 2 * J + 1, 0)] + kf[fe(2 * I, 2 * J + 1, 1)] +
-            kf[fe(2 * I + 1, 2 * J, 1)];
-    } else if (sx == 2) {
-      s = kf[fe(I, 2 * J, 0)] + kf[fe(I, 2 * J, 1)] + kf[fe(I, 2 * J + 1, 0)] + kf[fe(I, 2 * J + 1, 1)];
-    } else {
-      s = kf[fe(2 * I, J, 0)] + kf[fe(2 * I, J, 1)] + kf[fe(2 * I + 1, J, 0)] + kf[fe(2 * I + 1, J, 1)];
-    }
-    kc[(i64)E * Bv + nm.b] = 0.25 * s;
-  }
-}
 
 
 // Gershgorin bound of D^-1 A: max over rows (and samples) of sum_j |a_ij| / a_ii, as the bit pattern of a
@@ -2607,8 +721,6 @@ struct Hier {
   void *bF[kMaxLevels], *xF[kMaxLevels];  // full-multigrid start: restricted right-hand sides, iterates
 };
 
-inline dim3 lgrid(int n, int Bp) { return node_grid(n, Bp, 2048); }  // <= kPartBlocks partial rows
-
 // bpn = algorithmic bytes per (node, sample) of the launch, for diffhe_traffic_account
 #define LAUNCH(bpn, kernel, n, ...)                                                  \
   do {                                                                               \
@@ -2921,15 +1033,10 @@ void resid_restrict(const Hier& H, int l, const TV* x, const TV* rhs_l, hipStrea
   const Level& C = H.lev[l + 1];
   constexpr int CW = kRestrictCols;
   bool two = sizeof(TV) == 4 && strip2_ok(L, H.Bv, H.Bp);
-  StripGeom g{true, 0, 0, 0};
-  g.ncb = (C.W + 4 * CW - 1) / (4 * CW);
+  StripGeom g;
   for (int pass = 0; pass < 2; ++pass) {
-    const int gy = H.Bp / (two ? 2 * kWave : kWave);
-    int nrc = (kStripBlocks + g.ncb * gy - 1) / (g.ncb * gy);
-    if (nrc > (C.ny + 1) / 4) nrc = (C.ny + 1) / 4;
-    if (nrc < 1) nrc = 1;
-    g.TR = (C.ny + 1 + nrc - 1) / nrc;  // coarse rows per tile
-    g.nrc = (C.ny + 1 + g.TR - 1) / g.TR;
+    // tiles of coarse rows, at least 4 in the mean; no partial sums
+    g = tile_geom(C.ny + 1, (C.W + 4 * CW - 1) / (4 * CW), H.Bp / (two ? 2 * kWave : kWave), kStripBlocks, 4, 0);
     if (!two || strip2_tile_fits(L, H.Bp, 2 * g.TR + 1)) break;
     two = false;                         // tiles beyond 32-bit offsets: the one-sample-per-lane kernel
   }
@@ -2970,21 +1077,15 @@ int fused_level(const Hier& H, int l, StripGeom* gpre, StripGeom* gpost) {
   const int spl = fused_spl(H, L, false), spl_pre = fused_spl(H, L, true);
   const int nw = 4;   // waves per block (fused_pre_kernel: wider blocks measured slower)
   constexpr int CW = kRestrictCols;
-  StripGeom g{true, 0, 0, 0};
-  g.ncb = (C.W + nw * CW - 1) / (nw * CW);
-  const int gy = H.Bp / (spl_pre * kWave);
   // ~6144 blocks whatever the samples per lane: the four-sample form gets tiles of half the height (6 instead of 11 coarse
   // rows at 1024^2 x 256).  Measured (gpurun_out/r4l, same box): 6 rows 0.660 ms, 11 rows 0.681, 16 rows 0.778 -- the
   // number of independent marches matters more than the halo rows
-  int nrc = (kStripBlocks * 4 / nw + g.ncb * gy - 1) / (g.ncb * gy);
   // Levels of <= 300 columns cannot fill the GPU with 4-coarse-row tiles: shorter tiles (2 coarse rows going down, ~5 fine
   // rows going up) double the independent marches; -1.4 ms per 1024^2 step, neutral on the 513^2 level (gpurun_out/r5j, r5k)
   const bool small = L.W <= 300;
-  const int cap = small ? (C.ny + 1) / 2 : (C.ny + 1) / 4;
-  if (nrc > cap) nrc = cap;
-  if (nrc < 1) nrc = 1;
-  g.TR = (C.ny + 1 + nrc - 1) / nrc;  // coarse rows per tile
-  g.nrc = (C.ny + 1 + g.TR - 1) / g.TR;
+  // tiles of coarse rows; no partial sums
+  const StripGeom g = tile_geom(C.ny + 1, (C.W + nw * CW - 1) / (nw * CW), H.Bp / (spl_pre * kWave), kStripBlocks * 4 / nw,
+                                small ? 2 : 4, 0);
   *gpre = g;
   *gpost = strip_geom(L, H.Bp, 4, spl, nw);
   if (small) {
@@ -3182,6 +1283,9 @@ TV* fmg_start(const Hier& H, const TV* b0, hipStream_t st, const TV** pending = 
 
 
 }  // namespace
+}  // namespace diffhe_lattice
+
+using namespace diffhe_lattice;
 
 extern "C" int diffhe_lattice_pcg_profile(int enable, double* total_ms, long long* launches) {
   if (total_ms) *total_ms = g_kp.ms[KP_CGSTEP];
@@ -3268,15 +1372,13 @@ extern "C" long long diffhe_lattice_pcg_workspace_doubles(const diffhe_mg_level*
   const double w1 = 0.8;
   if (fill_hier(H, levels, n_levels, 1, Bp, nullptr, &w1, 1, 1)) return -1;
   const long long nb = (long long)H.lev[0].n * Bp;
-  const long long nblk = lgrid(H.lev[0].n, Bp).x;
-  (void)nblk;
   // r, the direction ring (kRingSlots fp32 = kRingSlots / 2 fp64 vectors), A p; the fp64 layout of the cycle is the larger
   return carve(H, nullptr, false) + (2 + kRingSlots / 2) * nb + 2LL * kPartBlocks * Bp + (32LL + kScalarSlices) * Bp + 64;
 }
 
 extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_levels, int Bv, const double* scale,
                                         const double* b, double* x, int Bp, double tol, double tol_energy, int max_iter,
-                                        int nu, int n_coarse, const double* omegas_host, int precond_fp32, double* work,
+                                        int nu, int n_coarse, const double* omegas_host, int flags, double* work,
                                         double* relres, double* err_est, int* iters, int* stop_rule, int* status_host,
                                         void* stream) {
   if (!b || !x || !work || !relres || !iters || !status_host || max_iter < 0) return DIFFHE_E_BADARG;
@@ -3288,13 +1390,13 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   const int n = L0.n;
   const long long nb = (long long)n * Bp;
   const int nblk = lgrid(n, Bp).x;
-  const bool f32 = (precond_fp32 & 1) != 0;
-  const bool use_fmg = (precond_fp32 & 2) != 0 && H.nl > 1;
-  const bool warm = (precond_fp32 & 32) != 0;   // x holds an initial guess (e.g. the previous step of an optimisation)
-  H.fmg_coarse_cycles = 1 + ((precond_fp32 >> 2) & 3);
-  if (precond_fp32 & 64) H.fuse = 0;             // bit 6: keep the four single-stage passes (A/B runs, tests)
-  if (precond_fp32 & 128) H.dense_mfma = 0;      // bit 7: scalar-load dense coarse solve
-  if (precond_fp32 & 512) H.pre4 = 0;            // bit 9: fused PRE pass with two samples per lane as well (A/B runs, tests)
+  const bool f32 = (flags & DIFFHE_PCG_FP32) != 0;
+  const bool use_fmg = (flags & DIFFHE_PCG_FMG) != 0 && H.nl > 1;
+  const bool warm = (flags & DIFFHE_PCG_WARM) != 0;   // x holds an initial guess (e.g. the previous step of an optimisation)
+  H.fmg_coarse_cycles = 1 + ((flags >> DIFFHE_PCG_FMG_CYCLES_SHIFT) & 3);
+  if (flags & DIFFHE_PCG_UNFUSED) H.fuse = 0;             // keep the four single-stage passes (A/B runs, tests)
+  if (flags & DIFFHE_PCG_DENSE_SCALAR) H.dense_mfma = 0;  // scalar-load dense coarse solve
+  if (flags & DIFFHE_PCG_PRE2) H.pre4 = 0;                // fused PRE pass with two samples per lane as well (A/B runs, tests)
   double* w = work + carve(H, work, f32);
   float* r32 = f32 ? (float*)H.rhs[0] : nullptr;
   double* r = w;
@@ -3314,7 +1416,7 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   S.active = (int*)(sc + 5 * Bp);
   S.iters = iters;
   S.n_active = (int*)(sc + 6 * Bp);
-  const bool use_floor = (precond_fp32 & 16) == 0;  // bit 4 set: stop on `tol` alone
+  const bool use_floor = (flags & DIFFHE_PCG_NO_FLOOR) == 0;  // set: stop on `tol` alone
   S.maxdiag = sc + 9 * Bp;  // Bv entries (Bv <= Bp)
   S.rs = f32 ? sc + 11 * Bp : nullptr;
   S.scale = scale;
@@ -3445,29 +1547,20 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
       ex.p_out = ring + (size_t)(it % n_slots) * slot_stride * esz;
       ex.x = nullptr;            // deferred (flush_directions)
       ex.alpha = nullptr; ex.beta = S.beta; ex.first = first;
-#define NXV(MINW_)                                                                                                    \
-  launch_strip<double, M_APPLY, false, F_PUPD_NX, float, kPupdCols, MINW_>(L0, Bv, scale, (const double*)nullptr,          \
-                                                                         (const double*)nullptr, rupd ? (double*)nullptr : Ap, \
-                                                                         0.0, 0.0, partA, Bp, g0, st, ex)
-      // flag bit 8: the caller vouches for a lattice closed by Dirichlet data (lambda_min of the scaled operator bounded
+#define NXV(MINW_, MATS_)                                                                                             \
+  launch_strip<double, M_APPLY, false, F_PUPD_NX, float, kPupdCols, MINW_, MATS_>(                                         \
+      L0, Bv, scale, (const double*)nullptr, (const double*)nullptr, rupd ? (double*)nullptr : Ap, 0.0, 0.0, partA, Bp, g0, \
+      st, ex)
+      // DIFFHE_PCG_CLOSED_FP32_STEP: the caller vouches for a lattice closed by Dirichlet data (lambda_min of the scaled operator bounded
       // away from 0).  With large Neumann parts the search directions are dominated by near-null modes, for which the
       // fp32 stencil cancels to noise: measured 13 / 11 instead of 12 / 9 iterations to 1e-14 there (gpurun_out/r6g)
       // (the host also asks for near-square cells and a hierarchy that reaches the dense coarsest level: on a 382 x 259
       // lattice, which coarsens once, 36 iterations to 1e-14 became 38 -- tools/stress.py seed 6301 case 39)
-      if (f32 && rupd && (precond_fp32 & 256) && g2.use && shared32_ok(L0, Bv, Bp) &&
+      if (f32 && rupd && (flags & DIFFHE_PCG_CLOSED_FP32_STEP) && g2.use && shared32_ok(L0, Bv, Bp) &&
           strip2_tile_fits(L0, Bp, g2.TR + 3)) {
         // fp32 stencil for p.Ap (cgstep2_kernel; packed, two samples per lane, where the batch allows): the step length only
-        const dim3 grid(g2.ncb * g2.nrc, Bp / (cspl * kWave));
-        diffhe::account((first ? 8.0 : 12.0) * (double)n * Bp);
-        const float* zz = (const float*)z;
-        const float* pi_ = (const float*)ex.p_in;
-        float* po_ = (float*)ex.p_out;
-#define CG2(VT_, ND_, MW_) hipLaunchKernelGGL((cgstep2_kernel<VT_, ND_, 4, MW_>), grid, dim3(256), 0, st, L0, scale, \
-                                              (const double*)S.beta, first, zz, pi_, po_, partA, Bp, g2.ncb, g2.TR)
-        // 8 waves per SIMD: 0.70 ms at 1024^2 x 256 (6: 0.75, 4: 0.75; the one-sample fp64 strip: 0.87; gpurun_out/r6e)
-        if (cspl == 2) { if (L0.nd == 3) CG2(v2f, 3, 8); else CG2(v2f, 4, 8); }
-        else { if (L0.nd == 3) CG2(float, 3, 8); else CG2(float, 4, 8); }
-#undef CG2
+        launch_cgstep2(L0, scale, (const double*)S.beta, first, (const float*)z, (const float*)ex.p_in, (float*)ex.p_out,
+                       partA, Bp, g2, cspl, st);
         S.alpha = alpha_ring + (long long)(it % n_slots) * Bp;
         nba = g2.ncb * g2.nrc;
         if (!first) kp_end(KP_CGSTEP, st);
@@ -3479,7 +1572,7 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
         // The same cap on the V-cycle's strip kernels (already 6-7 waves) made them slower: -2...-6 % end to end.
         // per-sample matrices (coefficients in VGPRs): 4 waves per SIMD, 245.2 ms per step of the per-element-field variant
         // against 249.5 at 7 (gpurun_out/r4w)
-        if (Bv != 1) NXV(4); else NXV(7);
+        if (Bv != 1) NXV(4, MAT_PER_SAMPLE); else NXV(7, MAT_ANY);
       }
 #undef NXV
       else
@@ -3557,9 +1650,8 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
       ex.rscale = S.rs;
       ex.alpha = S.alpha;
       // 5 waves per SIMD: 1.30 ms at 1024^2 x 256 (compiler's own choice 1.30, 7 waves 2.31 with spills; gpurun_out/r4q)
-      launch_strip<double, M_APPLY, false, F_RUPD, float, kPupdCols, 5>(L0, Bv, scale, (const double*)nullptr,
-                                                                         (const double*)nullptr, (double*)nullptr, 0.0, 0.0,
-                                                                         partA, Bp, g0, st, ex);
+      launch_strip<double, M_APPLY, false, F_RUPD, float, kPupdCols, 5, MAT_SHARED>(   // rupd: Bv == 1
+          L0, Bv, scale, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, 0.0, 0.0, partA, Bp, g0, st, ex);
     } else {
       LAUNCH(24.0 + (r32 ? 4.0 : 0.0) + (fused ? 0.0 : 24.0), pcg_update_kernel, n, (const double*)p, (const double*)Ap, (const double*)S.alpha, fused ? (double*)nullptr : x,
              r, r32, (const double*)S.rs, partA, n, Bp);
@@ -3662,48 +1754,6 @@ extern "C" int diffhe_lattice_cg_step(const diffhe_mg_level* level, int Bv, cons
   return diffhe::check_launch();
 }
 
-// y = is_bc ? 0 : (M x - sub_scale[b] * sub) for a batch-shared symmetric-diagonal matrix M (the load
-// matrix of a lattice mesh): F = M f - lift and df = M^T lambda without the general ELL pattern.
-__global__ __launch_bounds__(256) void dia_shared_apply_kernel(Level L, const double* __restrict__ x,
-                                                                const double* __restrict__ sub, int sub_B,
-                                                                const double* __restrict__ sub_scale,
-                                                                const unsigned char* __restrict__ mask,
-                                                                double* __restrict__ y, int Bp) {
-  const NodeMap nm = node_map(Bp);
-  for (int i = nm.node0; i < L.n; i += nm.stride) {
-    double acc = dia_row(L, 1, 0, x, i, nm.b, Bp);
-    if (sub) acc -= (sub_scale ? sub_scale[nm.b] : 1.0) * sub[(i64)i * sub_B + (sub_B == 1 ? 0 : nm.b)];
-    if (mask && mask[i]) acc = 0.0;
-    y[(i64)i * Bp + nm.b] = acc;
-  }
-}
-
-extern "C" int diffhe_lattice_apply_shared(int nx, int ny, int nd, const double* vals, const double* x,
-                                           const double* sub, int sub_B, const double* sub_scale,
-                                           const unsigned char* mask, double* y, int Bp, void* stream) {
-  if (!vals || !x || !y || nx < 2 || ny < 2 || (nd != 3 && nd != 4)) return DIFFHE_E_BADARG;
-  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
-  if (sub && sub_B != 1 && sub_B != Bp) return DIFFHE_E_BADARG;
-  Level L{};   // inv, shift: none
-  L.nx = nx; L.ny = ny; L.W = nx + 1; L.n = (nx + 1) * (ny + 1); L.nd = nd; L.v = vals; L.v32 = nullptr; L.bc = nullptr;
-  L.rd32 = nullptr; L.mk32 = nullptr; L.o16 = nullptr; L.osc = nullptr;
-  const StripGeom g = strip_geom(L, Bp);
-  if (g.use) {
-    Extra ex{};
-    ex.sub = sub; ex.sub_scale = sub_scale; ex.mask = mask;
-    ex.sub_pb = (sub && sub_B != 1) ? 1 : 0;   // per-sample lift: read in the strip pass too (it used to fall to the
-                                               // gather kernel below: 2.67 instead of ~1.4 ms at 1024^2 x 256)
-    if (ex.sub_pb) diffhe::account(8.0 * (double)L.n * Bp);
-    launch_strip<double, M_APPLY, false>(L, 1, nullptr, x, (const double*)nullptr, y, 0.0, 0.0, nullptr, Bp, g,
-                                         (hipStream_t)stream, ex);
-    return diffhe::check_launch();
-  }
-  diffhe::account((16.0 + (sub && sub_B != 1 ? 8.0 : 0.0)) * (double)L.n * Bp);
-  hipLaunchKernelGGL(dia_shared_apply_kernel, lgrid(L.n, Bp), dim3(256), 0, (hipStream_t)stream, L, x, sub, sub_B,
-                     sub_scale, mask, y, Bp);
-  return diffhe::check_launch();
-}
-
 extern "C" int diffhe_lattice_smooth(const diffhe_mg_level* level, int Bv, const double* scale, const double* rhs,
                                      const double* xin, double* xout, double omega, int Bp, void* stream) {
   if (!rhs || !xout) return DIFFHE_E_BADARG;
@@ -3711,201 +1761,5 @@ extern "C" int diffhe_lattice_smooth(const diffhe_mg_level* level, int Bv, const
   int rc = fill_hier(H, level, 1, Bv, Bp, scale, &omega, 1, 1);
   if (rc) return rc;
   op_jacobi<double>(H, 0, rhs, xin, xout, omega, nullptr, (hipStream_t)stream);
-  return diffhe::check_launch();
-}
-
-// dL/dkappa per element and sample on a lattice mesh (reverse of solver.py:137-140; Appendix A step 2):
-//   dk[e, b] = - sum_{p,q} lambda[node_p, b] k0[p*3+q, e] (u[node_q, b] + g[node_q])
-// Quad (r, c) = nodes a (r, c), b (r, c+1), c (r+1, c+1), d (r+1, c) carries T0 = [a, b, d] = element 2q and
-// T1 = [b, c, d] = element 2q + 1 (mesh.py:100-105).  A wave owns GW quad columns x 64 samples and marches down the quad
-// rows with a two-row window of lambda and u in registers: every nodal value is loaded once per wave (+ one halo
-// column) instead of once per incident element (6x), k0 arrives as scalar loads, dk leaves as 512 B rows.
-// 32 B per node and sample of algorithmic traffic (lambda, u, two dk): the element-loop kernel ran it at 1.2 TB/s.
-constexpr int kGradCols = 4;
-__global__ __launch_bounds__(256) void lattice_grad_kappa_kernel(int nx, int ny, const double* __restrict__ k0, i64 lm,
-                                                                  i64 emask, const double* __restrict__ lam,
-                                                                  const double* __restrict__ u,
-                                                                  const double* __restrict__ g, double* __restrict__ dk,
-                                                                  int Bp, int ncb, int TR) {
-  constexpr int GW = kGradCols;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned lb = blockIdx.y * kWave + lane;
-  const int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int rc = tile / ncb, cb = tile - rc * ncb;
-  const int c0 = (cb * 4 + wave) * GW;                 // first quad column
-  const int r0 = rc * TR;
-  const int r1 = (r0 + TR < ny) ? r0 + TR : ny;        // quad rows r0 .. r1 - 1
-  if (c0 >= nx || r0 >= r1) return;
-  const int W = nx + 1;
-  int dc[GW + 1];                                       // node columns c0 .. c0 + GW, clamped at the right edge
-#pragma unroll
-  for (int j = 0; j < GW + 1; ++j) dc[j] = (c0 + j < W) ? j : W - 1 - c0;
-  double la[GW + 1], ua[GW + 1], lbn[GW + 1], ubn[GW + 1];   // node rows r (a, b) and r + 1 (d, c)
-  const double* __restrict__ pl = lam + ((i64)r0 * W + c0) * Bp;
-  const double* __restrict__ pu = u + ((i64)r0 * W + c0) * Bp;
-  const double* __restrict__ pg = g ? g + (i64)r0 * W + c0 : nullptr;
-  const i64 rowX = (i64)W * Bp;
-#pragma unroll
-  for (int j = 0; j < GW + 1; ++j) {
-    la[j] = (pl + (i64)dc[j] * Bp)[lb];
-    ua[j] = (pu + (i64)dc[j] * Bp)[lb] + (pg ? pg[dc[j]] : 0.0);
-  }
-  for (int r = r0; r < r1; ++r) {
-#pragma unroll
-    for (int j = 0; j < GW + 1; ++j) {
-      lbn[j] = (pl + rowX + (i64)dc[j] * Bp)[lb];
-      ubn[j] = (pu + rowX + (i64)dc[j] * Bp)[lb] + (pg ? pg[W + dc[j]] : 0.0);
-    }
-    const i64 e0 = 2 * ((i64)r * nx + c0);               // element 2 q of quad (r, c0)
-#pragma unroll
-    for (int j = 0; j < GW; ++j) {
-      if (c0 + j >= nx) continue;
-      const i64 e = e0 + 2 * j;
-      // T0 = [a, b, d]: a = (r, c), b = (r, c + 1), d = (r + 1, c)
-      {
-        const double lp[3] = {la[j], la[j + 1], lbn[j]}, uq[3] = {ua[j], ua[j + 1], ubn[j]};
-        double acc = 0.0;
-#pragma unroll
-        for (int p_ = 0; p_ < 3; ++p_)
-#pragma unroll
-          for (int q = 0; q < 3; ++q) acc += lp[p_] * k0[(i64)(p_ * 3 + q) * lm + (e & emask)] * uq[q];
-        (dk + e * Bp)[lb] = -acc;
-      }
-      // T1 = [b, c, d]: b = (r, c + 1), c = (r + 1, c + 1), d = (r + 1, c)
-      {
-        const double lp[3] = {la[j + 1], lbn[j + 1], lbn[j]}, uq[3] = {ua[j + 1], ubn[j + 1], ubn[j]};
-        double acc = 0.0;
-#pragma unroll
-        for (int p_ = 0; p_ < 3; ++p_)
-#pragma unroll
-          for (int q = 0; q < 3; ++q) acc += lp[p_] * k0[(i64)(p_ * 3 + q) * lm + ((e + 1) & emask)] * uq[q];
-        (dk + (e + 1) * Bp)[lb] = -acc;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < GW + 1; ++j) {
-      la[j] = lbn[j];
-      ua[j] = ubn[j];
-    }
-    pl += rowX;
-    pu += rowX;
-    if (pg) pg += W;
-  }
-}
-
-extern "C" int diffhe_lattice_grad_kappa(int nx, int ny, const double* k0, int k0_compact, const double* lam,
-                                         const double* u, const double* g, double* dk, int Bp, void* stream) {
-  if (!k0 || !lam || !u || !dk || nx < 2 || ny < 2) return DIFFHE_E_BADARG;
-  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
-  if (Bp < kWave) return DIFFHE_E_TOOBIG;              // small batches: diffhe_p1_grad_kappa
-  const int ncb = (nx + 4 * kGradCols - 1) / (4 * kGradCols);
-  const int gy = Bp / kWave;
-  int nrc = (kStripBlocks + ncb * gy - 1) / (ncb * gy);
-  if (nrc > ny / 8) nrc = ny / 8;
-  if (nrc < 1) nrc = 1;
-  const int TR = (ny + nrc - 1) / nrc;
-  nrc = (ny + TR - 1) / TR;
-  diffhe::account(32.0 * (double)(nx + 1) * (ny + 1) * Bp);   // lambda, u once per node; two dk per node
-  const i64 mm = 2LL * nx * ny;
-  hipLaunchKernelGGL(lattice_grad_kappa_kernel, dim3(ncb * nrc, gy), dim3(256), 0, (hipStream_t)stream, nx, ny, k0,
-                     (i64)(k0_compact ? 2 : mm), (i64)(k0_compact ? 1 : -1), lam, u, g, dk, Bp, ncb, TR);
-  return diffhe::check_launch();
-}
-
-// fp32 diagonal + fp16 off-diagonals of a per-sample symmetric-diagonal matrix (h16m above): the off-diagonals of sample b
-// divided by `oscale[b]` and rounded to fp16, the diagonal moved by the sum of the rounding differences of the row's
-// 2 (nd - 1) couplings so that the row sum is the fp64 matrix's (to the fp32 rounding of the diagonal itself, 6e-8
-// relative).  flags[0] is set when a non-zero coupling falls below 2^-19 of its sample's scale: fp16 subnormals keep fewer
-// than 5 bits there (and flush to 0 from 2^-25 on: the row-sum rule would then leave a row with a vanishing diagonal), so
-// the caller must not use the packed copies of that matrix (high contrast INSIDE a sample; the fp32 copies have no such limit).
-__global__ __launch_bounds__(256) void dia_pack_h16_kernel(Level L, int Bv, const double* __restrict__ oscale,
-                                                            float* __restrict__ d32, _Float16* __restrict__ o16,
-                                                            int* __restrict__ flags) {
-  const NodeMap nm = node_map(Bv);
-  if (nm.b >= Bv) return;
-  const i64 n = L.n;
-  const double osc = oscale[nm.b];
-  const double inv = 1.0 / osc;   // power of two: exact
-  const double tiny = 1.9073486328125e-06;   // 2^-19
-  bool under = false;
-  for (int i = nm.node0; i < L.n; i += nm.stride) {
-    double d = L.v[(i64)i * Bv + nm.b];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-      if (k < L.nd) {
-        const int off = dia_off(L, k);
-        const double up = L.v[((i64)k * n + i) * Bv + nm.b];            // coupling (i, i + off): stored here
-        const _Float16 h = (_Float16)(float)(up * inv);
-        o16[((i64)(k - 1) * n + i) * Bv + nm.b] = h;
-        if (i + off < L.n) {
-          d += up - osc * (double)(float)h;
-          under = under || (up != 0.0 && fabs(up * inv) < tiny);
-        }
-        if (i - off >= 0) {                                             // coupling (i - off, i): stored at the other end
-          const double lo = L.v[((i64)k * n + (i - off)) * Bv + nm.b];
-          d += lo - osc * (double)(float)(_Float16)(float)(lo * inv);
-        }
-      }
-    }
-    d32[(i64)i * Bv + nm.b] = (float)d;
-  }
-  if (flags && __any(under) && (threadIdx.x & 63) == 0) atomicOr(flags, 1);
-}
-
-extern "C" int diffhe_lattice_pack_h16(const diffhe_mg_level* level, int Bv, const double* offdiag_scales, float* diag32,
-                                       void* offdiag16, int* flags, void* stream) {
-  if (!level || !diag32 || !offdiag16 || !level->vals || (level->nd != 3 && level->nd != 4) || !offdiag_scales)
-    return DIFFHE_E_BADARG;
-  if (!diffhe::valid_batch_pad(Bv)) return DIFFHE_E_BATCHPAD;
-  Level L{};
-  L.nx = level->nx; L.ny = level->ny; L.W = level->nx + 1; L.n = (level->nx + 1) * (level->ny + 1); L.nd = level->nd;
-  L.v = level->vals;
-  diffhe::account((8.0 * L.nd + 4.0 + 2.0 * (L.nd - 1)) * (double)L.n * Bv);
-  hipLaunchKernelGGL(dia_pack_h16_kernel, node_grid(L.n, Bv), dim3(256), 0, (hipStream_t)stream, L, Bv, offdiag_scales,
-                     diag32, (_Float16*)offdiag16, flags);
-  return diffhe::check_launch();
-}
-
-// Per-sample maximum of the main diagonal over the FREE rows (identity rows of Dirichlet nodes carry 1.0 whatever the
-// magnitude of kappa and are skipped): the quantity the per-sample fp16 scale is derived from.  out: Bv doubles.
-__global__ __launch_bounds__(256) void dia_maxdiag_free_kernel(Level L, int Bv, unsigned long long* __restrict__ out) {
-  const NodeMap nm = node_map(Bv);
-  double m = 0.0;
-  if (nm.b < Bv)
-    for (int i = nm.node0; i < L.n; i += nm.stride) {
-      const double d = L.bc[i] ? 0.0 : L.v[(i64)i * Bv + nm.b];
-      m = d > m ? d : m;
-    }
-  const int LB = Bv < kWave ? Bv : kWave;
-  for (int off = LB; off < kWave; off <<= 1) {  // lanes that hold the same sample
-    const double o = __shfl_xor(m, off);
-    m = o > m ? o : m;
-  }
-  if ((int)(threadIdx.x & 63) < LB && nm.b < Bv) atomicMax(out + nm.b, (unsigned long long)__double_as_longlong(m));
-}
-
-extern "C" int diffhe_lattice_max_diag(const diffhe_mg_level* level, int Bv, double* out, void* stream) {
-  if (!level || !out || !level->vals || !level->is_bc || (level->nd != 3 && level->nd != 4)) return DIFFHE_E_BADARG;
-  if (!diffhe::valid_batch_pad(Bv)) return DIFFHE_E_BATCHPAD;
-  Level L{};
-  L.nx = level->nx; L.ny = level->ny; L.W = level->nx + 1; L.n = (level->nx + 1) * (level->ny + 1); L.nd = level->nd;
-  L.v = level->vals; L.bc = level->is_bc;
-  int rc = diffhe::check(hipMemsetAsync(out, 0, sizeof(double) * Bv, (hipStream_t)stream));
-  if (rc) return rc;
-  diffhe::account(8.0 * (double)L.n * Bv);
-  hipLaunchKernelGGL(dia_maxdiag_free_kernel, node_grid(L.n, Bv, 512), dim3(256), 0, (hipStream_t)stream, L, Bv,
-                     (unsigned long long*)out);
-  return diffhe::check_launch();
-}
-
-extern "C" int diffhe_lattice_restrict_kappa(const double* kappa_fine, double* kappa_coarse, int nx_coarse,
-                                             int ny_coarse, int sx, int sy, int Bv, void* stream) {
-  if (!kappa_fine || !kappa_coarse || nx_coarse < 1 || ny_coarse < 1) return DIFFHE_E_BADARG;
-  if ((sx != 1 && sx != 2) || (sy != 1 && sy != 2) || (sx == 1 && sy == 1)) return DIFFHE_E_BADARG;
-  if (!diffhe::valid_batch_pad(Bv)) return DIFFHE_E_BATCHPAD;
-  diffhe::account(8.0 * Bv * (2.0 * nx_coarse * ny_coarse) * (1.0 + sx * sy));
-  hipLaunchKernelGGL(mg_restrict_kappa_kernel, node_grid(2 * nx_coarse * ny_coarse, Bv), dim3(256), 0,
-                     (hipStream_t)stream, kappa_fine, kappa_coarse, nx_coarse, ny_coarse, sx, sy, Bv);
   return diffhe::check_launch();
 }

@@ -157,6 +157,16 @@ class HipExtensionError(RuntimeError):
 
 CHAIN_REFERENCE_ORDER = 1   # DIFFHE_CHAIN_REFERENCE_ORDER
 ELL_SCALE_CHUNK = 256       # DIFFHE_ELL_SCALE_CHUNK
+# option bits of the `flags` word of diffhe_lattice_pcg_solve / diffhe_ell_amg_pcg_solve (DIFFHE_PCG_* in diffhe_hip.h)
+PCG_FP32 = 1
+PCG_FMG = 2
+PCG_FMG_CYCLES_SHIFT = 2    # two bits
+PCG_NO_FLOOR = 16
+PCG_WARM = 32
+PCG_UNFUSED = 64
+PCG_DENSE_SCALAR = 128
+PCG_CLOSED_FP32_STEP = 256
+PCG_PRE2 = 512
 
 
 def lib():

@@ -58,7 +58,7 @@ class SolveInfo:
     # copies: asked for, or the fallback when a sample's couplings span more than fp16 holds), "fp64" (no copies)
     coeff_storage: str = ""
     factored: bool = False      # one scalar kappa per sample (or for all) kept as K_b = kappa_b K_1: ONE unit matrix for the batch
-    flags: int = 0              # lattice path: the `precond_fp32` word handed to diffhe_lattice_pcg_solve (include/diffhe_hip.h)
+    flags: int = 0              # lattice path: the `flags` word handed to diffhe_lattice_pcg_solve (DIFFHE_PCG_* in include/diffhe_hip.h)
     precision: str = ""         # what is stored / computed in which precision in THIS solve, derived from those flags
     # general path with a multigrid preconditioner: "unit" (hierarchy of the unit-kappa operator, plan-cached) or "operator"
     # (amg=dict(strength=theta): built from the operator that was being solved, kept on the solver); its levels, the fine
@@ -128,7 +128,7 @@ class _Solved(NamedTuple):
     relres: torch.Tensor                    # (Bp,) true relative residual per sample
     est: Optional[torch.Tensor] = None      # lattice path: (Bp,) estimated relative energy-norm error
     rule: Optional[torch.Tensor] = None     # lattice path: (Bp,) int32, the rule that stopped each sample
-    flags: int = 0                          # lattice path: the `precond_fp32` word handed to diffhe_lattice_pcg_solve
+    flags: int = 0                          # lattice path: the `flags` word handed to diffhe_lattice_pcg_solve
 
 
 class _Engine:
@@ -458,12 +458,16 @@ class _Engine:
         om = (ctypes.c_double * len(omegas))(*omegas)
         est = torch.empty(Bp, dtype=torch.float64, device=p.device)
         rule = torch.empty(Bp, dtype=torch.int32, device=p.device)
-        flags = (int(mg.get("fp32", 0)) | (int(mg.get("fmg", 0)) << 1) | ((int(mg.get("fmg_cycles", 1)) - 1) << 2)
-                 | ((0 if int(mg.get("floor", 1)) else 1) << 4) | (32 if warm else 0)
-                 | (0 if int(mg.get("fused", 1)) else 64) | (0 if int(mg.get("dense_mfma", 1)) else 128)
-                 | (0 if int(mg.get("pre4", 1)) else 512)
-                 | (256 if (p.closed_boundary and p.regular_cells and p.dense_level() is not None
-                            and int(mg.get("cg_fp32_steplength", 1))) else 0))
+        closed_step = (p.closed_boundary and p.regular_cells and p.dense_level() is not None
+                       and int(mg.get("cg_fp32_steplength", 1)))
+        flags = (int(mg.get("fp32", 0)) * _hip.PCG_FP32 | int(mg.get("fmg", 0)) * _hip.PCG_FMG
+                 | ((int(mg.get("fmg_cycles", 1)) - 1) << _hip.PCG_FMG_CYCLES_SHIFT)
+                 | (0 if int(mg.get("floor", 1)) else _hip.PCG_NO_FLOOR)
+                 | (_hip.PCG_WARM if warm else 0)
+                 | (0 if int(mg.get("fused", 1)) else _hip.PCG_UNFUSED)
+                 | (0 if int(mg.get("dense_mfma", 1)) else _hip.PCG_DENSE_SCALAR)
+                 | (0 if int(mg.get("pre4", 1)) else _hip.PCG_PRE2)
+                 | (_hip.PCG_CLOSED_FP32_STEP if closed_step else 0))
         # a multigrid-preconditioned CG that has not converged in a few hundred iterations never will:
         # bound the loop so a defect surfaces as `not_converged` instead of minutes of GPU time
         return self._solve(Bp, lambda x, relres, iters, st: L.diffhe_lattice_pcg_solve(
@@ -561,7 +565,8 @@ class _Engine:
         return self._solve(Bp, lambda x, relres, iters, st: L.diffhe_ell_amg_pcg_solve(
             arr, nl, Bv, rhs, x, Bp, self.tol, min(self.max_iter, int(opts.get("max_iter", 20000))), int(opts["n_coarse"]),
             int(opts["gamma"]), float(opts["scale"]),
-            int(opts.get("fp32", 0)) | ((0 if int(opts.get("floor", 1)) else 1) << 4), work, relres, iters, st,
+            (_hip.PCG_FP32 if int(opts.get("fp32", 0)) else 0) | (0 if int(opts.get("floor", 1)) else _hip.PCG_NO_FLOOR),
+            work, relres, iters, st,
             _stream(p.device)))
 
     def grad_kappa_factored(self, vals, lift, lam, x, Bp):
@@ -642,17 +647,17 @@ class _Engine:
 def _precision_text(flags: int, coeff_storage: str, Bv: int, Bp: int, fused_lib: int, recompute_ap: bool) -> str:
     """Plain-words account of the precisions of one lattice solve, from the flag word actually passed to
     diffhe_lattice_pcg_solve and the library's own switches (nothing here is a literal about 'the' configuration)."""
-    if not flags & 1:
+    if not flags & _hip.PCG_FP32:
         return "fp64 throughout: every vector stored fp64, all arithmetic fp64"
     spl2 = Bp % 128 == 0 and fused_lib == 2
-    packed = not flags & 64 and fused_lib != 0 and ((coeff_storage == "shared-fp32" and Bp % 64 == 0)
-                                                    or (coeff_storage == "fp16-rowsum" and spl2))
+    packed = not flags & _hip.PCG_UNFUSED and fused_lib != 0 and (
+        (coeff_storage == "shared-fp32" and Bp % 64 == 0) or (coeff_storage == "fp16-rowsum" and spl2))
     parts = ["iterate x, residual r, right-hand side, the updates x += alpha p and r -= alpha A p and EVERY reduction "
              "(r.r, r.z, p.Ap accumulation, energy estimate): fp64",
              "CG search directions p and all V-cycle (preconditioner) vectors: STORED fp32"]
     if packed:
         parts.append("V-cycle arithmetic: fp32 (" + (("packed, two samples per lane" + (
-            " (four in the way-down pass)" if Bp % 256 == 0 and not flags & 512 and coeff_storage == "shared-fp32" else ""))
+            " (four in the way-down pass)" if Bp % 256 == 0 and not flags & _hip.PCG_PRE2 and coeff_storage == "shared-fp32" else ""))
             if spl2 else "one sample per lane")
                      + "; coefficients: "
                      + {"shared-fp32": "batch-shared fp32 copies, scalar loads",
@@ -663,7 +668,7 @@ def _precision_text(flags: int, coeff_storage: str, Bv: int, Bp: int, fused_lib:
                      + ("" if coeff_storage in ("", "fp64") else f" (coefficients: {coeff_storage})"))
     if Bv == 1 and recompute_ap:
         parts.append("A p is never stored: the residual update recomputes it in fp64 from the stored fp32 p")
-        if flags & 256 and Bp % 64 == 0 and coeff_storage == "shared-fp32":
+        if flags & _hip.PCG_CLOSED_FP32_STEP and Bp % 64 == 0 and coeff_storage == "shared-fp32":
             parts.append("p.Ap: stencil in fp32 on the stored p, accumulated fp64 -- enters the STEP LENGTH alpha only "
                          "(closed regular lattice); r = b - A x holds in fp64 whatever alpha is")
         else:

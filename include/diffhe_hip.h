@@ -224,14 +224,14 @@ int diffhe_ell_galerkin(const double* vals_fine, const int* ent_ptr, const int* 
 /* Batched CG preconditioned by one aggregation-multigrid cycle: V(2,2) Chebyshev-weighted Jacobi,
  * `gamma` coarse corrections per level (2 = W-cycle), coarse correction scaled by `scale`, n_coarse
  * sweeps on the last level.  Replaces torch.linalg.solve (solver.py:174) on general meshes.
- * precond_fp32 bit 0: the cycle stores its vectors in fp32 (arithmetic fp64 in registers) and reads levels[].vals32
- * where given; the CG vectors, residuals and dot products stay fp64.  Bit 4: stop on `tol` alone (no floor).
+ * flags: DIFFHE_PCG_FP32: the cycle stores its vectors in fp32 (arithmetic fp64 in registers) and reads levels[].vals32
+ * where given; the CG vectors, residuals and dot products stay fp64.  DIFFHE_PCG_NO_FLOOR: stop on `tol` alone.
  * Arguments as diffhe_ell_cg_solve; levels is a HOST array.  The stop is floored like
  * diffhe_lattice_pcg_solve's: sample b stops at |r| <= max(tol |b|, 0.5 u |A_b| |x_b|), with the running
  * iterate x (this path starts from 0). */
 long long diffhe_ell_amg_workspace_doubles(const diffhe_amg_level* levels, int n_levels, int Bp);
 int diffhe_ell_amg_pcg_solve(const diffhe_amg_level* levels, int n_levels, int Bv, const double* b, double* x, int Bp,
-                             double tol, int max_iter, int n_coarse, int gamma, double scale, int precond_fp32,
+                             double tol, int max_iter, int n_coarse, int gamma, double scale, int flags,
                              double* work,
                              double* relres, int* iters, int* status_host, void* stream);
 
@@ -281,6 +281,18 @@ typedef struct diffhe_mg_level {
                                   NULL = offdiag16 unused */
 } diffhe_mg_level;
 
+/* Option bits of `flags` (diffhe_lattice_pcg_solve; diffhe_ell_amg_pcg_solve reads FP32 and NO_FLOOR of the same word).
+ * x, r, Ap and every dot product are fp64 whatever the bits; bench.py records the word as solver_flags. */
+#define DIFFHE_PCG_FP32 1              /* V-cycle and CG search directions stored in fp32 (arithmetic fp64 in registers) */
+#define DIFFHE_PCG_FMG 2               /* start from a full-multigrid iterate instead of 0 */
+#define DIFFHE_PCG_FMG_CYCLES_SHIFT 2  /* two bits: extra V-cycles per coarse level of that start (0..3) */
+#define DIFFHE_PCG_NO_FLOOR 16         /* stop on `tol` alone; default: |r| <= max(tol |b|, 0.5 u |A_b| |x0_b|), u = 2^-53 */
+#define DIFFHE_PCG_WARM 32             /* `x` holds an initial guess: start from x + FMG(b - A x) (with FMG) or from x */
+#define DIFFHE_PCG_UNFUSED 64          /* fp32 cycle: four single-stage strip passes per level, not the fused two-stage ones */
+#define DIFFHE_PCG_DENSE_SCALAR 128    /* fp32 cycle: coarsest dense solve by the scalar-load kernel, not the MFMA one */
+#define DIFFHE_PCG_CLOSED_FP32_STEP 256 /* lattice closed by Dirichlet data, near-square cells: p.Ap in packed fp32 (cgstep2) */
+#define DIFFHE_PCG_PRE2 512            /* fused PRE pass at two samples per lane (default: four where the batch allows) */
+
 /* Batched CG preconditioned by one multigrid V(nu,nu) cycle (weighted Jacobi with the
  * per-sweep damping factors omegas_host[0..nu-1] -- Chebyshev weights; post-smoothing runs
  * them in reverse so the cycle stays symmetric -- P1 transfers, n_coarse sweeps on the last
@@ -289,27 +301,7 @@ typedef struct diffhe_mg_level {
  *   levels   HOST array of n_levels descriptors (device pointers inside)
  *   Bv       Bp (matrix per sample) or 1 (shared); scale (Bp) or NULL: K_b = scale[b]*K on
  *            the free rows (one scalar kappa per sample, solver.py:88,139)
- *   precond_fp32  bit 0: the V-cycle AND the CG search direction p are stored in fp32 (arithmetic
- *            stays fp64 in registers; x, r, Ap and all dot products are fp64, and every update
- *            uses the stored p, so the recursion r = b - A x stays exact);
- *            bit 1: start the CG from a full-multigrid iterate x0 instead of 0;
- *            bits 2-3: extra V-cycles per coarse level of that start (0..3);
- *            bit 5: WARM START -- `x` holds an initial guess on entry (the previous solution of an optimisation
- *            loop): the solve starts from x + FMG(b - A x) (bit 1 set) or from x itself;
- *            bit 6: keep the four single-stage strip passes per level in the fp32 V-cycle of a batch-shared matrix
- *            (default: the fused two-stage passes, 22 instead of 42 B per node and sample and cycle);
- *            bit 7: coarsest-level dense solve of the fp32 cycle with the scalar-load kernel (fp64 accumulation)
- *            instead of the MFMA kernel (fp32 accumulation; the default for batches of >= 64);
- *            bit 8: the lattice is closed by Dirichlet data on all four edges, its cells are near-square and its
- *            hierarchy reaches a small coarsest level (multigrid at its textbook rate): the CG step of a batch-shared matrix may
- *            form p.Ap -- the step length only -- with a packed-fp32 stencil, two samples per lane (cgstep2_kernel);
- *            x and r are updated with the exact fp64 A p either way;
- *            bit 9 (ABI v7): keep the fused PRE pass at two samples per lane (default: four where the batch has whole
- *            waves of 256 samples and the level has 3 diagonals -- half the vector-memory instructions per byte);
- *            bit 4: stop on `tol` alone.  By default (bit 4 clear, bit 1 set) sample b stops at
- *            |r| <= max(tol |b|, 0.5 u |A_b| |x0_b|), u = 2^-53, |A_b| = 2 scale[b] max_i K_ii: fp64 cannot
- *            bring |b - A x| below ~ u |A| |x|, the recurrence residual keeps falling past that level but the
- *            iterate no longer improves (the same backward error a direct fp64 solve, solver.py:174, reaches)
+ *   flags    OR of the DIFFHE_PCG_* bits above
  *   tol      relative residual |r|_2 / |b|_2 per sample
  *   tol_energy  > 0: sample b ALSO stops once the estimated relative energy-norm error of its iterate,
  *            sqrt(r.z / u^T A u), is <= tol_energy.  r.z = r^T M^-1 r is the dot the CG needs for beta anyway;
@@ -320,13 +312,13 @@ typedef struct diffhe_mg_level {
  *   err_est  (Bp) out or NULL: the last estimate per sample
  *   stop_rule (Bp) out or NULL (ABI v6): the rule that ended each sample -- 1 residual, 2 energy-norm estimate,
  *            0 neither (iteration cap reached, or the direct dense path where nothing iterates)
- *   b, x     (n, Bp) right-hand side / solution (x is read only with flag bit 5; otherwise the start is 0 / FMG(b))
+ *   b, x     (n, Bp) right-hand side / solution (x is read only with DIFFHE_PCG_WARM; otherwise the start is 0 / FMG(b))
  *   work     diffhe_lattice_pcg_workspace_doubles(...) doubles
  *   relres, iters, status_host: as diffhe_ell_cg_solve */
 long long diffhe_lattice_pcg_workspace_doubles(const diffhe_mg_level* levels, int n_levels, int Bp);
 int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_levels, int Bv, const double* scale,
                              const double* b, double* x, int Bp, double tol, double tol_energy, int max_iter, int nu,
-                             int n_coarse, const double* omegas_host, int precond_fp32, double* work, double* relres,
+                             int n_coarse, const double* omegas_host, int flags, double* work, double* relres,
                              double* err_est, int* iters, int* stop_rule, int* status_host, void* stream);
 /* Opt-in timing of the fused CG-step kernel (the dominant one) inside diffhe_lattice_pcg_solve's own loop, for
  * bench.py's roofline entry: enable = 1 creates two HIP events (per calling thread, the only hidden state in the
@@ -342,7 +334,7 @@ int diffhe_lattice_kernel_profile(int id, double* total_ms, long long* launches)
  * xout = xin + omega (rhs - A xin)/D  (xin NULL = 0). */
 int diffhe_lattice_blocks(int n, int Bp);
 /* 2: the fp32 V-cycle of a batch-shared matrix runs the fused two-stage passes (pre-smoothing + residual + restriction;
- * prolongation + post-smoothing) with two samples per lane (one where the batch is no multiple of 128); flag bit 6 of
+ * prolongation + post-smoothing) with two samples per lane (one where the batch is no multiple of 128); DIFFHE_PCG_UNFUSED of
  * diffhe_lattice_pcg_solve switches them off per call (four single-stage strip passes per level).  Always 2 since the
  * development switches were retired.  With them, kernel-profile id 2 times the fused PRE pass (9 B per node and
  * sample), id 4 the fused POST pass (13 B), ids 3 and 5 see no launches. */

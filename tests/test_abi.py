@@ -40,6 +40,22 @@ def test_binding_and_header_agree_on_the_abi_version():
     assert m and int(m.group(1)) == _hip.ABI_VERSION
 
 
+def test_pcg_option_bits_match_the_header():
+    """Every DIFFHE_PCG_* value of the header equals the binding's constant of the same name, and the names are pairwise
+    disjoint bit sets (the two-bit cycle count enters as the field its shift places)."""
+    defs = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+DIFFHE_(PCG_\w+)\s+(\d+)", open(HEADER).read())}
+    assert len(defs) == 9, defs
+    for name, value in defs.items():
+        assert getattr(_hip, name) == value, name
+    masks = {n: (3 << v if n == "PCG_FMG_CYCLES_SHIFT" else v) for n, v in defs.items()}
+    names = sorted(masks)
+    for i, a in enumerate(names):
+        assert masks[a] > 0
+        for b in names[i + 1:]:
+            assert masks[a] & masks[b] == 0, (a, b)
+    assert sum(masks.values()) == (1 << 10) - 1   # nine names cover the ten bits of the word, no gap
+
+
 def test_struct_layouts_match_the_header(tmp_path):
     """sizeof / offsetof of the two structs that cross the boundary, as a C compiler sees the header, against the ctypes
     mirrors in diffhe/_hip.py (the header is plain C: gcc compiles it without HIP)."""
