@@ -1,6 +1,28 @@
 // Shared device/host helpers for libdiffhe_hip (gfx950 only, wave = 64).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define DIFFHE_HD __host__ __device__
+#else
+#define DIFFHE_HD
+#endif
+
+namespace diffhe {
+
+// A double carried as the unevaluated sum of two floats (the CG residual of the lattice solver, lattice_strip.h F_RPAIR):
+// hi is exactly (float)R -- what a plain fp32 copy of R would hold -- and lo the float nearest to the remainder R - hi
+// (exact in fp64: hi has 24 of R's 53 bits).  hi + lo keeps 48 bits of R, |join(split(R)) - R| <= 2^-48 |R|, as long as
+// lo is a normal float; a remainder below the fp32 range flushes towards 0 and costs nothing but those bits.
+// Plain C++ below this line up to the HIP-only part: a host compiler may include this header for the two functions alone.
+DIFFHE_HD inline void split(double R, float& hi, float& lo) {
+  hi = (float)R;
+  lo = (float)(R - (double)hi);
+}
+DIFFHE_HD inline double join(float hi, float lo) { return (double)hi + (double)lo; }
+
+}  // namespace diffhe
+
+#if defined(__HIPCC__)
 #include <stdint.h>
 
 #include "diffhe_hip.h"
@@ -88,3 +110,5 @@ inline dim3 node_grid(int n, int Bp, int max_blocks_x = 2048) {
 }
 
 }  // namespace diffhe
+
+#endif  // __HIPCC__

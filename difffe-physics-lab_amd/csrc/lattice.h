@@ -67,13 +67,26 @@ enum { M_APPLY = 0, M_RESID = 1, M_JACOBI = 2 };
 //              columns 2 J0 - 1 .. 2 J0 + 2 CW - 1 that feed the wave's CW coarse columns (one fine
 //              column is shared with -- and recomputed by -- each neighbour strip) and the tile the
 //              fine rows 2 I0 - 1 .. 2 I1 - 1 of the coarse rows I0 .. I1 - 1.
-enum { F_NONE = 0, F_PROLONG = 1, F_PUPD = 2, F_RESTRICT = 3, F_PUPD_NX = 4, F_RUPD = 5 };
+enum { F_NONE = 0, F_PROLONG = 1, F_PUPD = 2, F_RESTRICT = 3, F_PUPD_NX = 4, F_RUPD = 5, F_RPAIR = 6 };
 // F_RUPD (with M_APPLY): the CG's residual update with A p RECOMPUTED from the stored direction p (TA, ex.p_in) instead of
 // read back: r -= alpha (A p), the fp32 copy of r and the partials of r.r in one pass -- for a batch-shared matrix (scalar
 // loads, no coefficient traffic) reading p's window (4 B + halo) is cheaper than writing and re-reading A p (8 + 8 B).
 // F_PUPD_NX: F_PUPD without the iterate update (the solver's form: x is assembled from the kept directions at the
 // end); a compile-time variant so that the x stream costs neither registers nor instructions
+// F_RPAIR: the residual is carried as a PAIR of fp32 vectors instead of one fp64 and its fp32 copy: R = rs r (rs the
+// per-sample power of two of ex.rscale, so R is exact) as hi + lo with hi = (float)R -- the very vector the V-cycle
+// reads, ex.r32 -- and lo = (float)(R - hi) in ex.rlo (common.h split / join; 2^-48 relative per update).  With M_APPLY
+// it is F_RUPD on the pair (p 4 B, hi and lo read and written: 20 B per node and sample instead of 24), with M_RESID
+// the residual pass that opens the CG loop (x, b read, hi and lo written: 24 B instead of 28; the partials are those
+// of F_NONE).  The solver's default on the path where F_RUPD applies; DIFFHE_PCG_RESID_FP64 keeps the fp64 residual.
+static_assert((DIFFHE_PCG_RESID_FP64 & (DIFFHE_PCG_FP32 | DIFFHE_PCG_FMG | (3 << DIFFHE_PCG_FMG_CYCLES_SHIFT) | DIFFHE_PCG_NO_FLOOR |
+                                        DIFFHE_PCG_WARM | DIFFHE_PCG_UNFUSED | DIFFHE_PCG_DENSE_SCALAR |
+                                        DIFFHE_PCG_CLOSED_FP32_STEP | DIFFHE_PCG_PRE2)) == 0,
+              "DIFFHE_PCG_RESID_FP64 must be a bit of its own");
 constexpr bool is_pupd(int fuse) { return fuse == F_PUPD || fuse == F_PUPD_NX; }
+constexpr bool is_rupd(int fuse) { return fuse == F_RUPD || fuse == F_RPAIR; }
+// M_RESID, F_RPAIR differs from M_RESID, F_NONE in what it stores only
+constexpr bool plain_resid(int mode, int fuse) { return mode == M_RESID && (fuse == F_NONE || fuse == F_RPAIR); }
 
 struct Extra {
   const void* a0;           // F_PROLONG: coarse correction e (TA);  F_PUPD: z (TA)
@@ -96,6 +109,7 @@ struct Extra {
   const unsigned char* mask;  // M_APPLY, F_NONE: rows with mask[i] != 0 are stored as 0 (may be NULL)
   int dot_bx;               // M_RESID, F_NONE: the partial sums hold b.x (energy of the iterate) instead of r.r ...
   double* part2;            //   ... and these (same layout as `part`) x.(A x)
+  float* rlo;               // F_RPAIR: low parts of the residual pair (the high parts are r32; rscale applies)
 };
 
 // Workgroups are handed to the 8 XCDs round-robin by linear id, so blocks x = k (mod 8) share one L2.

@@ -415,11 +415,24 @@ __global__ __launch_bounds__(256) void dia_maxdiag_kernel(Level L, int Bv, unsig
 // r32 = fp32(rs * r): the fp32 copies that feed the preconditioner are taken of the residual scaled by a per-sample
 // power of two rs ~ 1 / |b| (S_INIT), so they stay inside the fp32 range whatever the magnitude of the data
 // (forcing of amplitude 1e-35 used to underflow them); powers of two make the scaling exact, so nothing else changes.
+// rlo (optional): the low parts of the pair as well, r32 + rlo = rs * r to 2^-48 (F_RPAIR; a zero start without the
+// full-multigrid iterate, where no residual pass opens the loop).
 __global__ __launch_bounds__(256) void pcg_cvt_kernel(const double* __restrict__ r, const double* __restrict__ rs,
-                                                       float* __restrict__ r32, int n, int Bp) {
+                                                       float* __restrict__ r32, int n, int Bp,
+                                                       float* __restrict__ rlo = nullptr) {
   const NodeMap nm = node_map(Bp);
   const double sc = rs ? rs[nm.b] : 1.0;
   int i = nm.node0;
+  if (rlo) {
+    for (; i < n; i += nm.stride) {
+      const i64 o = (i64)i * Bp + nm.b;
+      float hi, lo;
+      split(r[o] * sc, hi, lo);
+      r32[o] = hi;
+      rlo[o] = lo;
+    }
+    return;
+  }
   for (; (i64)i + 3LL * nm.stride < n; i += 4 * nm.stride) {   // four nodes per trip: four loads in flight per wave
     double rv[4];
 #pragma unroll
@@ -1397,9 +1410,11 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   if (flags & DIFFHE_PCG_UNFUSED) H.fuse = 0;             // keep the four single-stage passes (A/B runs, tests)
   if (flags & DIFFHE_PCG_DENSE_SCALAR) H.dense_mfma = 0;  // scalar-load dense coarse solve
   if (flags & DIFFHE_PCG_PRE2) H.pre4 = 0;                // fused PRE pass with two samples per lane as well (A/B runs, tests)
+  const bool resid64 = (flags & DIFFHE_PCG_RESID_FP64) != 0;  // keep the fp64 residual where the pair would apply (A/B runs, tests)
   double* w = work + carve(H, work, f32);
   float* r32 = f32 ? (float*)H.rhs[0] : nullptr;
   double* r = w;
+  float* rlo = (float*)(void*)r;   // `rpair`: the residual's low parts live in the first half of r's region, r itself is unused
   // Search directions.  Fused loop: the iterate is NOT touched inside the loop (that cost 16 of the fused step's 36
   // bytes per node); the directions p_j stay in a ring of slots (10 fp32 / 5 fp64 vectors in these 5 nb doubles) with
   // their step lengths alpha_j, and x += sum_j alpha_j p_j is formed when the ring is full or the solve ends.
@@ -1498,10 +1513,6 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   }
 
   int nbz = 0, nba = 0;
-  const bool light_init = (use_fmg && f32) || warm;  // the start overwrites x and r (cold) / x is the caller's guess (warm)
-  LAUNCH(light_init ? 8.0 : 24.0, pcg_init_kernel, n, b, light_init ? (double*)nullptr : x, r, partA, n, Bp);
-  SCALAR(S_INIT, partA, nblk);
-  if (f32 && !warm) LAUNCH(12.0, pcg_cvt_kernel, n, b, (const double*)S.rs, r32, n, Bp);  // fp32 copy of rs * b (rs from S_INIT)
   // Fused loop (fine level runs the strip kernels): per iteration
   //   [p = z + beta p ; x += alpha_prev p_old ; Ap = A p ; p.Ap]  ->  alpha  ->  [r -= alpha Ap ; r.r]
   //   -> convergence flags  ->  z = V(r) (last sweep leaves r.z)  ->  beta
@@ -1510,6 +1521,20 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   const bool fused = g0.use;
   // batch-shared matrix, fp32-stored directions: A p is never stored -- the residual update recomputes it from p (F_RUPD)
   const bool rupd = fused && f32 && Bv == 1;
+  // ... and there the residual is carried as a pair of fp32 vectors, r32 (what the V-cycle reads) + rlo, not as fp64 r
+  // plus r32 (F_RPAIR, lattice.h): nothing but the residual update and the pass that opens the loop touches it
+  // (the pass that opens the loop must be the strip one too: it is what writes the pair -- residual_pass; today the two
+  // geometries' `use` cannot differ, the condition keeps the pair from ever depending on that)
+  const bool rpair = rupd && !resid64 && strip_geom(L0, Bp).use;
+  const bool light_init = (use_fmg && f32) || warm;  // the start overwrites x and r (cold) / x is the caller's guess (warm)
+  LAUNCH(light_init ? 8.0 : 24.0, pcg_init_kernel, n, b, light_init ? (double*)nullptr : x, r, partA, n, Bp);
+  SCALAR(S_INIT, partA, nblk);
+  // fp32 copy of rs * b (rs from S_INIT): the full-multigrid start's right-hand side, or r0 of a zero start -- of which
+  // the pair path needs the low parts too (they go where pcg_init_kernel has just put the fp64 r0, unused on that path)
+  if (f32 && !warm) {
+    const bool lo_too = rpair && !use_fmg;
+    LAUNCH(lo_too ? 16.0 : 12.0, pcg_cvt_kernel, n, b, (const double*)S.rs, r32, n, Bp, lo_too ? rlo : (float*)nullptr);
+  }
   // cgstep2_kernel: two samples per lane for batches that are multiples of 128, else one
   // (four samples per lane -- what pays in the fused PRE pass -- measured here too: 0.699 -> 0.711 ms at 4 waves per SIMD
   // instead of 8, gpurun_out/r4n; not kept)
@@ -1590,14 +1615,20 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   // r = b - A x (+ its fp32 copy, + the partials b.x and x.(A x) of the energy bound when asked for)
   auto residual_pass = [&](bool energy) {
     const StripGeom gr = strip_geom(L0, Bp);
-    if (gr.use && f32) {  // r and its fp32 copy in one pass
+    if (gr.use && f32) {  // r and its fp32 copy in one pass (rpair: the two halves of the pair)
       Extra ex{};
       ex.r32 = r32;
       ex.rscale = S.rs;
       ex.dot_bx = energy ? 1 : 0;   // partial sums of this pass: b.x0 and x0.(A x0) (S_ENERGY / S_ENERGY2)
       ex.part2 = energy ? partB : nullptr;
-      launch_strip<double, M_RESID, false>(L0, Bv, scale, (const double*)x, b, r, 0.0, 0.0, energy ? partA : (double*)nullptr,
-                                           Bp, gr, st, ex);
+      if (rpair) {
+        ex.rlo = rlo;
+        launch_strip<double, M_RESID, false, F_RPAIR, double, kStripCols, 1, MAT_SHARED>(
+            L0, Bv, scale, (const double*)x, b, (double*)nullptr, 0.0, 0.0, energy ? partA : (double*)nullptr, Bp, gr, st, ex);
+      } else {
+        launch_strip<double, M_RESID, false>(L0, Bv, scale, (const double*)x, b, r, 0.0, 0.0, energy ? partA : (double*)nullptr,
+                                             Bp, gr, st, ex);
+      }
       nba = gr.ncb * gr.nrc;
     } else {
       nba = op_residual<double>(H, 0, b, (const double*)x, r, energy ? partA : (double*)nullptr, st, energy ? 1 : 0,
@@ -1649,9 +1680,15 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
       ex.r32 = r32;
       ex.rscale = S.rs;
       ex.alpha = S.alpha;
+      ex.rlo = rlo;
       // 5 waves per SIMD: 1.30 ms at 1024^2 x 256 (compiler's own choice 1.30, 7 waves 2.31 with spills; gpurun_out/r4q)
-      launch_strip<double, M_APPLY, false, F_RUPD, float, kPupdCols, 5, MAT_SHARED>(   // rupd: Bv == 1
-          L0, Bv, scale, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, 0.0, 0.0, partA, Bp, g0, st, ex);
+      // the pair form: 1.13 ms; the compiler's own choice measured 0.8 ms per step slower
+      if (rpair)
+        launch_strip<double, M_APPLY, false, F_RPAIR, float, kPupdCols, 5, MAT_SHARED>(   // rupd: Bv == 1
+            L0, Bv, scale, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, 0.0, 0.0, partA, Bp, g0, st, ex);
+      else
+        launch_strip<double, M_APPLY, false, F_RUPD, float, kPupdCols, 5, MAT_SHARED>(
+            L0, Bv, scale, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, 0.0, 0.0, partA, Bp, g0, st, ex);
     } else {
       LAUNCH(24.0 + (r32 ? 4.0 : 0.0) + (fused ? 0.0 : 24.0), pcg_update_kernel, n, (const double*)p, (const double*)Ap, (const double*)S.alpha, fused ? (double*)nullptr : x,
              r, r32, (const double*)S.rs, partA, n, Bp);

@@ -73,17 +73,20 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
 
   const double inv_omega_in = XFROMB ? 1.0 / omega_in : 0.0;
   const double sub_fac = (MODE == M_APPLY && FUSE == F_NONE && ex.sub && ex.sub_scale) ? ex.sub_scale[b] : 1.0;
-  const double rsc = (MODE == M_RESID && FUSE == F_NONE && ex.r32 && ex.rscale) ? ex.rscale[b] : 1.0;
+  const double rsc = (plain_resid(MODE, FUSE) && ex.r32 && ex.rscale) ? ex.rscale[b] : 1.0;
   const double beta = (is_pupd(FUSE) && !ex.first) ? ex.beta[b] : 0.0;
   const double alpha_prev = (FUSE == F_PUPD && !ex.first && ex.x) ? ex.alpha[b] : 0.0;  // alpha is NULL when x is
   const TA* __restrict__ aux = (const TA*)ex.a0;
   // F_PUPD row pointers at (row, c0w), advanced with the others
   const TA* __restrict__ pz = (is_pupd(FUSE)) ? aux + i0 * Bp : nullptr;
-  const TA* __restrict__ ppi = (is_pupd(FUSE) || FUSE == F_RUPD) ? (const TA*)ex.p_in + i0 * Bp : nullptr;
+  constexpr bool kRupd = MODE == M_APPLY && is_rupd(FUSE);   // residual update: fp64 r (F_RUPD) or the pair (F_RPAIR)
+  const TA* __restrict__ ppi = (is_pupd(FUSE) || kRupd) ? (const TA*)ex.p_in + i0 * Bp : nullptr;
   double* __restrict__ pr = (FUSE == F_RUPD) ? ex.x + i0 * Bp : nullptr;          // F_RUPD: ex.x is the residual r
-  float* __restrict__ pr32 = (FUSE == F_RUPD && ex.r32) ? ex.r32 + i0 * Bp : nullptr;
-  const double alpha_cur = (FUSE == F_RUPD) ? ex.alpha[b] : 0.0;
-  const double rsc_u = (FUSE == F_RUPD && ex.r32 && ex.rscale) ? ex.rscale[b] : 1.0;
+  float* __restrict__ pr32 = (kRupd && ex.r32) ? ex.r32 + i0 * Bp : nullptr;     // F_RPAIR: the high parts (never NULL)
+  float* __restrict__ plo = (kRupd && FUSE == F_RPAIR) ? ex.rlo + i0 * Bp : nullptr;
+  const double alpha_cur = kRupd ? ex.alpha[b] : 0.0;
+  const double rsc_u = (kRupd && ex.r32 && ex.rscale) ? ex.rscale[b] : 1.0;
+  const double ralpha = rsc_u * alpha_cur, inv_rsc_u = 1.0 / rsc_u;   // F_RPAIR; rsc_u is a power of two: both exact
   TA* __restrict__ ppo = (is_pupd(FUSE)) ? (TA*)ex.p_out + i0 * Bp : nullptr;
   double* __restrict__ pxx = (FUSE == F_PUPD && ex.x) ? ex.x + i0 * Bp : nullptr;  // NULL: the iterate is not touched
 
@@ -112,7 +115,7 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
         // the direction is STORED as TA: use the stored (rounded) value everywhere, so that Ap = A p,
         // x += alpha p and r -= alpha Ap stay exactly consistent (r == b - A x is independent of p)
         v = (double)(TA)v;
-      } else if (FUSE == F_RUPD) {
+      } else if (kRupd) {
         v = (double)(ppi + roff + (i64)dq[q] * Bp)[lb];
       } else {
         v = (double)(xrow + (i64)dq[q] * Bp)[lb];
@@ -186,7 +189,18 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
       const double sh = SHIFT ? psh[dq[k + 1]] : 0.0;   // A = sb K + diag(shift)
       const double diag = SHIFT ? sb * d0[k] + sh : sb * d0[k];
       const double Ax = SHIFT ? sb * acc + sh * xc[q] : sb * acc;
-      if (MODE == M_APPLY && FUSE == F_RUPD) {
+      if (MODE == M_APPLY && FUSE == F_RPAIR) {
+        // R = rs r as hi + lo: hi is the V-cycle's input (left cacheable), lo is touched here only (nontemporal, as
+        // the fp64 r of F_RUPD).  r.r is taken from the STORED pair: S_CONV judges the residual the solver carries.
+        float* ha = &(pr32 + o)[lb];
+        float* la = &(plo + o)[lb];
+        float hi, lo;
+        split(join(*ha, __builtin_nontemporal_load(la)) - ralpha * Ax, hi, lo);
+        *ha = hi;
+        __builtin_nontemporal_store(lo, la);
+        const double ri = join(hi, lo) * inv_rsc_u;
+        s += ri * ri;
+      } else if (MODE == M_APPLY && FUSE == F_RUPD) {
         double* ra = &(pr + o)[lb];
         const double ri = __builtin_nontemporal_load(ra) - alpha_cur * Ax;
         __builtin_nontemporal_store(ri, ra);
@@ -226,9 +240,16 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
         if (MODE == M_RESID && FUSE == F_RESTRICT) {
           resrow[k] = res;
         } else if (MODE == M_RESID) {
+          if (FUSE == F_RPAIR) {   // the residual as a pair only (po is NULL)
+            const i64 ig = ((i64)row * W + c0w + k) * Bp;
+            float hi, lo;
+            split(res * rsc, hi, lo);
+            (ex.r32 + ig)[lb] = hi;
+            __builtin_nontemporal_store(lo, &(ex.rlo + ig)[lb]);
+          }
           if (po) (po + o)[lb] = (TV)res;
           if (FUSE == F_NONE && sizeof(TV) == 8 && ex.r32) (ex.r32 + ((i64)row * W + c0w + k) * Bp)[lb] = (float)(res * rsc);
-          if (FUSE == F_NONE && ex.dot_bx) {
+          if (plain_resid(MODE, FUSE) && ex.dot_bx) {
             s += bi * xc[q];
             s2 += xc[q] * (bi - res);   // x.(A x)
           } else {
@@ -289,7 +310,7 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
     if (pb) pb += rowX;
     if (po) po += rowX;
     if (is_pupd(FUSE)) { pz += rowX; ppi += rowX; ppo += rowX; if (FUSE == F_PUPD && pxx) pxx += rowX; }
-    if (FUSE == F_RUPD) { ppi += rowX; pr += rowX; if (pr32) pr32 += rowX; }
+    if (kRupd) { ppi += rowX; if (pr) pr += rowX; if (pr32) pr32 += rowX; if (plo) plo += rowX; }
   }
   return s;
 }
@@ -345,7 +366,7 @@ __device__ __forceinline__ void strip_kernel_body(Level L, const double* __restr
     const double t = block_sum_per_sample(s, Bp, lds);
     if (wave == 0) part[(i64)blockIdx.x * Bp + b] = t;
   }
-  if (MODE == M_RESID && FUSE == F_NONE && ex.part2) {
+  if (plain_resid(MODE, FUSE) && ex.part2) {
     const double t = block_sum_per_sample(s2, Bp, lds);
     if (wave == 0) ex.part2[(i64)blockIdx.x * Bp + b] = t;
   }
@@ -389,9 +410,10 @@ void launch_strip(const Level& L, int Bv, const double* scale, const TV* xin, co
     const double tv = sizeof(TV), ta = sizeof(TA);
     double bpn;
     if (MODE == M_JACOBI) bpn = (XFROMB ? 2.0 : 3.0) * tv + (FUSE == F_PROLONG ? 0.25 * tv : 0.0);
-    else if (MODE == M_RESID) bpn = 2.0 * tv + (FUSE == F_RESTRICT ? 0.25 * tv : (out ? tv : 0.0) + (ex.r32 ? 4.0 : 0.0));
+    else if (MODE == M_RESID) bpn = 2.0 * tv + (FUSE == F_RESTRICT ? 0.25 * tv : (out ? tv : 0.0) + (ex.r32 ? 4.0 : 0.0) + (FUSE == F_RPAIR ? 4.0 : 0.0));
     else if (is_pupd(FUSE)) bpn = (ex.first ? 2.0 * ta : 3.0 * ta) + (out ? 8.0 : 0.0) + ((FUSE == F_PUPD && ex.x) ? 16.0 : 0.0);
-    else if (FUSE == F_RUPD) bpn = ta + 16.0 + (ex.r32 ? 4.0 : 0.0);
+    else if (FUSE == F_RUPD) bpn = ta + 16.0 + (ex.r32 ? 4.0 : 0.0);   // p; r read and written; its fp32 copy
+    else if (FUSE == F_RPAIR) bpn = ta + 16.0;                            // p; hi and lo read and written
     else bpn = tv + (out ? tv : 0.0) + (ex.dotv ? 8.0 : 0.0);
     if (Bv != 1) bpn += m16 ? 4.0 + 2.0 * (L.nd - 1) : L.nd * (m32 ? 4.0 : 8.0);
     diffhe::account(bpn * (double)L.n * Bp);

@@ -167,6 +167,7 @@ PCG_UNFUSED = 64
 PCG_DENSE_SCALAR = 128
 PCG_CLOSED_FP32_STEP = 256
 PCG_PRE2 = 512
+PCG_RESID_FP64 = 1 << 10   # DIFFHE_PCG_RESID_FP64
 
 
 def lib():

@@ -467,6 +467,7 @@ class _Engine:
                  | (0 if int(mg.get("fused", 1)) else _hip.PCG_UNFUSED)
                  | (0 if int(mg.get("dense_mfma", 1)) else _hip.PCG_DENSE_SCALAR)
                  | (0 if int(mg.get("pre4", 1)) else _hip.PCG_PRE2)
+                 | (0 if int(mg.get("resid_pair", 1)) else _hip.PCG_RESID_FP64)
                  | (_hip.PCG_CLOSED_FP32_STEP if closed_step else 0))
         # a multigrid-preconditioned CG that has not converged in a few hundred iterations never will:
         # bound the loop so a defect surfaces as `not_converged` instead of minutes of GPU time
@@ -668,6 +669,9 @@ def _precision_text(flags: int, coeff_storage: str, Bv: int, Bp: int, fused_lib:
                      + ("" if coeff_storage in ("", "fp64") else f" (coefficients: {coeff_storage})"))
     if Bv == 1 and recompute_ap:
         parts.append("A p is never stored: the residual update recomputes it in fp64 from the stored fp32 p")
+        if not flags & _hip.PCG_RESID_FP64:
+            parts.append("r is carried as a pair of fp32 vectors (hi = the V-cycle's input, lo = the remainder: 48 bits, "
+                         "updated in fp64 registers) where the fused CG loop runs; mg={'resid_pair': 0} keeps it fp64")
         if flags & _hip.PCG_CLOSED_FP32_STEP and Bp % 64 == 0 and coeff_storage == "shared-fp32":
             parts.append("p.Ap: stencil in fp32 on the stored p, accumulated fp64 -- enters the STEP LENGTH alpha only "
                          "(closed regular lattice); r = b - A x holds in fp64 whatever alpha is")

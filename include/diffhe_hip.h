@@ -282,7 +282,8 @@ typedef struct diffhe_mg_level {
 } diffhe_mg_level;
 
 /* Option bits of `flags` (diffhe_lattice_pcg_solve; diffhe_ell_amg_pcg_solve reads FP32 and NO_FLOOR of the same word).
- * x, r, Ap and every dot product are fp64 whatever the bits; bench.py records the word as solver_flags. */
+ * x, Ap and every dot product are fp64 whatever the bits, r is fp64 or an fp32 pair worth 48 bits (DIFFHE_PCG_RESID_FP64);
+ * bench.py records the word as solver_flags. */
 #define DIFFHE_PCG_FP32 1              /* V-cycle and CG search directions stored in fp32 (arithmetic fp64 in registers) */
 #define DIFFHE_PCG_FMG 2               /* start from a full-multigrid iterate instead of 0 */
 #define DIFFHE_PCG_FMG_CYCLES_SHIFT 2  /* two bits: extra V-cycles per coarse level of that start (0..3) */
@@ -292,6 +293,8 @@ typedef struct diffhe_mg_level {
 #define DIFFHE_PCG_DENSE_SCALAR 128    /* fp32 cycle: coarsest dense solve by the scalar-load kernel, not the MFMA one */
 #define DIFFHE_PCG_CLOSED_FP32_STEP 256 /* lattice closed by Dirichlet data, near-square cells: p.Ap in packed fp32 (cgstep2) */
 #define DIFFHE_PCG_PRE2 512            /* fused PRE pass at two samples per lane (default: four where the batch allows) */
+#define DIFFHE_PCG_RESID_FP64 (1 << 10) /* keep the CG residual as one fp64 vector + its fp32 copy where the default carries it
+                                          as a pair of fp32 vectors (see diffhe_lattice_recompute_ap); A/B runs, tests */
 
 /* Batched CG preconditioned by one multigrid V(nu,nu) cycle (weighted Jacobi with the
  * per-sweep damping factors omegas_host[0..nu-1] -- Chebyshev weights; post-smoothing runs
@@ -341,7 +344,10 @@ int diffhe_lattice_blocks(int n, int Bp);
 int diffhe_lattice_fused_passes(void);
 /* 1: with a batch-shared matrix and fp32-stored search directions the PCG never stores A p -- the fused CG step keeps it
  * in registers for p.Ap (12 B per node and sample: z, p_old read, p written) and the residual update recomputes it from
- * the stored p (24 B: p, r read; r and its fp32 copy written; kernel-profile id 1).  Always 1 since the development
+ * the stored p (kernel-profile id 1).  On that path the residual is carried as the unevaluated sum of two fp32 vectors,
+ * rs r = hi + lo with hi = (float)(rs r) the vector the V-cycle reads and rs the per-sample power of two of the fp32
+ * copies: 48 bits (2^-48 relative per update), 20 B per node and sample (p read; hi, lo read and written) instead of the
+ * 24 B of an fp64 r with its fp32 copy, which DIFFHE_PCG_RESID_FP64 keeps.  Always 1 since the development
  * switches were retired; fp64 directions, per-sample matrices and the unfused loop still write A p (20 B) and read it
  * back in pcg_update_kernel (28 B). */
 int diffhe_lattice_recompute_ap(void);
