@@ -11,10 +11,12 @@ exported here; `diffhe.dirichlet`: the adjoint step behind `forward(..., dirichl
 gradients; `diffhe.aniso`: `AnisotropicFESolver`, solves with a conductivity tensor per element and its gradient, also
 exported here; `diffhe.robin`: `RobinFESolver`, Robin (convective) and flux boundary conditions on boundary facets with
 gradients to the film coefficient, the ambient value and the flux, also exported here; `diffhe.eigen`: `EigenFESolver`,
-the smallest eigenpairs of K phi = lambda M_L phi per sample with d lambda / d kappa, also exported here; `diffhe._hip`:
-the ctypes binding).
+the smallest eigenpairs of K phi = lambda M_L phi per sample with d lambda / d kappa, also exported here;
+`diffhe.elastic`: `ElasticFESolver`, linear elasticity on P1 triangles and tetrahedra -- the first vector-valued problem,
+d displacement components per node -- with gradients to a Young's modulus per element, the body force and the nodal
+load, also exported here (its kernels are declared in include/diffhe_elastic.h); `diffhe._hip`: the ctypes binding).
 """
-from . import (aniso as _aniso, eigen as _eigen, loss as _loss, mesh as _mesh, neural as _neural, robin as _robin, shape as _shape,
+from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, loss as _loss, mesh as _mesh, neural as _neural, robin as _robin, shape as _shape,
                solver as _solver)
 
 FEMesh = _mesh.FEMesh
@@ -25,7 +27,8 @@ ShapeDifferentiableFESolver = _shape.ShapeDifferentiableFESolver
 AnisotropicFESolver = _aniso.AnisotropicFESolver
 RobinFESolver = _robin.RobinFESolver
 EigenFESolver = _eigen.EigenFESolver
+ElasticFESolver = _elastic.ElasticFESolver
 
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
-           "AnisotropicFESolver", "RobinFESolver", "EigenFESolver")
+           "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

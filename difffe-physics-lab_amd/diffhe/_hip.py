@@ -1,4 +1,4 @@
-"""ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h).
+"""ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h).
 
 The library is built in-tree by `__graft_entry__.build()` /
 `make -C difffe-physics-lab_amd/csrc`.  There is NO fallback: if the library or a
@@ -148,6 +148,16 @@ SIGNATURES = {
     "diffhe_to_sample_major": (_S, [_PD, _PD, _PD, _L, _I, _I, _I, _PV]),
 }
 
+# name -> (restype, argtypes) of every symbol of include/diffhe_elastic.h, the library's second header (linear
+# elasticity, csrc/elastic.hip): bound by the same loop of `lib()`, with the same pointer classes and status marker
+# (tests/test_elasticity.py holds this table against that header)
+ELASTIC_SIGNATURES = {
+    "diffhe_elast_assemble_rows": (_S, [_PD, _PD, _I, _D, _D, _PD, _L, _L, _PI, _PI, _PI, _PB, _PD, _PD, _PD, _I, _I,
+                                        _I, _I, _PV]),
+    "diffhe_elast_grad": (_S, [_PI, _PD, _PD, _I, _D, _D, _PD, _PD, _PD, _I, _I, _I, _PD, _PD, _PD, _PV]),
+    "diffhe_elast_grad_shared": (_S, [_PI, _PD, _PD, _I, _D, _D, _PD, _PD, _PD, _I, _I, _I, _I, _PD, _PV]),
+}
+
 _lib = None
 
 
@@ -179,7 +189,7 @@ def lib():
                 f"libdiffhe_hip.so not found at {LIB_PATH}: build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (*SIGNATURES.items(), *ELASTIC_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = (_I if res is _S else res), args
             if res is _S:

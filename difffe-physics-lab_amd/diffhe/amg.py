@@ -428,6 +428,66 @@ def jacobi_bound(A, safety: float = 1.1) -> float:
     return min(safety * lam, gersh)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Vector-valued unknowns (diffhe.elastic): d components per node, dof = node * d + component on the fine level.  The
+# aggregates are NODE aggregates expanded per component, so no aggregate mixes components and the tentative prolongation
+# is P_node (x) I_d: it carries the d translations exactly (no rotations).  Coarse dofs keep a (node, component) label --
+# coarse node = aggregate of nodes -- so the rule recurses.  An (aggregate, component) pair whose members are all fixed
+# gets no coarse dof: coarse dofs are numbered over the pairs that have a free member, sorted by (node, component).
+# ---------------------------------------------------------------------------------------------------------------------
+def node_graph(cols: np.ndarray, node_of: np.ndarray, n_nodes: int) -> np.ndarray:
+    """ELL pattern (slot 0 = the node itself, unused slots point at the node itself) of the node graph under a dof
+    pattern `cols` (W, n): nodes I != J are adjacent when some dof of I couples to some dof of J."""
+    import scipy.sparse as sp
+    W, n = cols.shape
+    r = np.broadcast_to(node_of[None, :], (W, n)).reshape(-1)
+    c = node_of[cols.reshape(-1)]
+    A = sp.csr_matrix((np.ones(len(r)), (r, c)), shape=(n_nodes, n_nodes))
+    A = (A + sp.identity(n_nodes, format="csr")).tocsr()
+    A.sum_duplicates()
+    return _csr_to_ell(A)[0]
+
+
+def build_hierarchy_blocks(cols: np.ndarray, unit_vals: np.ndarray, is_bc: np.ndarray, d: int, min_coarse: int = 64,
+                           max_levels: int = 12) -> List[Dict]:
+    """Smoothed-aggregation levels below the fine one for d unknowns per node.  cols (W, n), unit_vals (W, n): ELL pattern
+    and unit-coefficient values of the Dirichlet-eliminated fine matrix over the n = nodes * d dofs, dof = node * d +
+    component; is_bc (n,) per dof.  Per level: `aggregate` on the node graph (a node is active when one of its dofs is),
+    the aggregates expanded per component, the prolongation smoothed with the level's unit operator
+    (`smoothed_level(..., agg=...)`).  Level dicts as `build_hierarchy_sa` returns them, plus `node` / `comp` (the label
+    of every coarse dof) and `lam_parent` / `lam`: `jacobi_bound` of the unit operator above and on this level -- these
+    operators have positive off-diagonals, the cycle's Jacobi weights need the bound (diffhe_amg_level.reserved)."""
+    levels: List[Dict] = []
+    A1, ell_idx = _ell_to_csr(cols, np.ascontiguousarray(unit_vals, dtype=np.float64))
+    n = cols.shape[1]
+    node_of, comp_of = np.arange(n, dtype=np.int64) // d, np.arange(n, dtype=np.int64) % d
+    active = ~is_bc.astype(bool)
+    cur_cols = cols
+    lam_parent = jacobi_bound(A1)
+    while len(levels) < max_levels - 1:
+        n_active = int(active.sum())
+        if n_active <= min_coarse:
+            break
+        n_nodes = int(node_of.max()) + 1
+        node_active = np.zeros(n_nodes, dtype=bool)
+        node_active[node_of[active]] = True
+        agg_node = aggregate(node_graph(cur_cols, node_of, n_nodes), node_active, seed=len(levels))
+        pair = agg_node[node_of] * d + comp_of                      # (aggregate, component) of every dof
+        label, inv = np.unique(pair[active], return_inverse=True)   # ... numbered over the pairs with a free member
+        agg = np.full(len(node_of), -1, dtype=np.int64)
+        agg[active] = inv.reshape(-1)
+        lev, Ac, ell_c = smoothed_level(A1, ell_idx, cur_cols, active, seed=len(levels), agg=agg)
+        if lev["n"] >= 0.7 * n_active:
+            break
+        lev["node"], lev["comp"] = (label // d).astype(np.int64), (label % d).astype(np.int64)
+        lev["lam_parent"], lev["lam"] = lam_parent, jacobi_bound(Ac)
+        levels.append(lev)
+        A1, ell_idx, cur_cols, lam_parent = Ac, ell_c, lev["cols"], lev["lam"]
+        node_of, comp_of = lev["node"], lev["comp"]
+        active = np.ones(lev["n"], dtype=bool)
+    return levels
+
+
 def hierarchy_stats(cols: np.ndarray, levels: List[Dict]):
     """(number of levels, the fine one included; operator complexity sum_l nnz_l / nnz_0) of a hierarchy."""
     def nnz(c):

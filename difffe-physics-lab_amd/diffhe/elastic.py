@@ -1,0 +1,559 @@
+"""Linear elasticity per sample with dL/dE (ours: the reference solves scalar equations only).
+
+`ElasticFESolver(mesh, E, nu)` solves -div sigma(u) = f, sigma = 2 mu eps(u) + lambda tr eps(u) I, for the displacement
+u of a linear-elastic body on P1 triangles (d = 2) and P1 tetrahedra (d = 3), with a Young's modulus E per element and
+sample that may require grad:
+
+    mu = E / (2 (1 + nu)),   lambda = E nu / ((1 + nu)(1 - 2 nu))   in 3D and for plane="strain",
+                             lambda = E nu / (1 - nu^2)             for plane="stress" (2D, the default).
+
+nu is a Python float with -1 < nu < 0.5 (ValueError otherwise), not differentiated.  K(E) = sum_e E_e K_e0(nu) is linear
+in E exactly as the scalar operator is linear in kappa, so the layouts, the explicit adjoint and the gradient story of
+`DifferentiableFESolver` carry over: ONE adjoint solve gives dL/dE, dL/df and dL/dload.
+
+Layouts.  E: (), (B,), (m,), (B, m), and (m, B) with layout="node" -- resolved by `solver._kappa_layout`, so the (B,) /
+(m,) rule is the scalar solver's; the gradient comes back in the shape of E, and a field shared by the batch gets its
+gradient summed over the batch inside the kernel, in a fixed order.  f (a nodal body-force density, None = zero) and
+load (a nodal force vector: point loads, tractions integrated by the caller) are (n, d) or (B, n, d), with layout="node"
+(n, d, B); u has the shape of the right-hand side.  F_a = M f_a + load_a per component a with the load map M of the
+scalar solvers (`plan.Mvals`).  dL/dload = lambda and dL/df = M lambda with the adjoint lambda, which vanishes on fixed
+dofs: dL/dload is zero there, and a fixed dof's f still reaches its free neighbours through M.
+
+Dirichlet data per component: `fixed=None` clamps every node of `mesh.dirichlet_nodes` in all d components at zero
+(non-zero values there are temperatures and raise ValueError); otherwise `fixed` maps (node, component) -> value: a
+roller is one component, non-zero prescribed displacements go through the lift.  A rigid-body mode left free is the
+caller's error and surfaces as the non-convergence warning.
+
+Degrees of freedom: dof(i, a) = i d + a; device vectors are (n d, Bp), batch innermost: the contiguous node-major
+(n, d, Bp).  The operator is stored as ELL rows of width d W in the pattern of include/diffhe_elastic.h, derived from
+the plan's UNPRUNED node pattern (the Lame term fills couplings that vanish for a scalar kappa), assembled and
+differentiated by csrc/elastic.hip (fp64, no atomics, bitwise reproducible) and solved by the generic entries of the
+general path: aggregation-multigrid PCG ("ell-amgpcg"), or Jacobi PCG with method="ell-jacobi" ("ell-pcg") -- always
+the general path, also on `FEMesh.rectangle` connectivity.  The hierarchy aggregates NODES and expands the aggregates
+per component (`amg.build_hierarchy_blocks`): no aggregate mixes components, the tentative prolongation carries the d
+translations exactly.  It is built from the unit-E operator and cached per (plan, nu, plane, fixed set); every level
+carries `amg.jacobi_bound` of its unit operator for the cycle's Jacobi weights (elastic operators have positive
+off-diagonals).  The coarse space has no rotations ("Elasticity").
+
+Not implemented (NotImplementedError): 1D meshes, P2 meshes, backward with create_graph=True, a per-call `dirichlet=`,
+node gradients (mesh.nodes requiring grad), Robin / flux data (h=, u_inf=, flux=); `amg=dict(strength=...)`.
+"""
+from __future__ import annotations
+
+import math
+import threading
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _hip
+from .plan import get_plan, padded_batch, _stream
+from .solver import (K_ELEM, K_SAMPLE_ELEM, SolveInfo, _Engine, _SOLVERS, _call_options, _kappa_grad, _kappa_layout,
+                     _like_grads, _fake_grads, _register_state, _resolve_device, _run_call, _state_of, _tie_state)
+
+__all__ = ("ElasticFESolver", "lame_unit", "parse_fixed", "dof_pattern")
+
+
+# ---------------------------------------------------------------------------------------------
+# Host logic (numpy; no device, no library)
+# ---------------------------------------------------------------------------------------------
+def lame_unit(nu: float, dim: int, plane: Optional[str] = None) -> Tuple[float, float]:
+    """(lambda', mu') of E = 1: mu' = 1 / (2 (1 + nu)); lambda' = nu / ((1 + nu)(1 - 2 nu)) in 3D and plane strain,
+    nu / (1 - nu^2) in plane stress."""
+    nu = float(nu)
+    if not (-1.0 < nu < 0.5):
+        raise ValueError(f"nu must satisfy -1 < nu < 0.5, got {nu!r}")
+    if dim == 3 or plane == "strain":
+        lam = nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
+    elif plane == "stress":
+        lam = nu / (1.0 - nu * nu)
+    else:
+        raise ValueError(f"Unknown plane: {plane!r} (\"stress\" or \"strain\")")
+    return lam, 1.0 / (2.0 * (1.0 + nu))
+
+
+def parse_fixed(mesh, fixed=None) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (is_bc (n d,) uint8, g (n d,) float64) per dof.  None: every node of `mesh.dirichlet_nodes` clamped in all d
+    components at zero; otherwise a mapping {(node, component): value}."""
+    n, d = mesh.n_nodes, mesh.dim
+    is_bc = np.zeros(n * d, dtype=np.uint8)
+    g = np.zeros(n * d, dtype=np.float64)
+    if fixed is None:
+        bc = mesh.dirichlet_nodes
+        if any(float(v) != 0.0 for v in bc.values()):
+            raise ValueError("diffhe: mesh.dirichlet_nodes carries non-zero values; they are temperatures and mean "
+                             "nothing for a displacement -- give the prescribed displacements per component with fixed=")
+        if bc:
+            idx = np.fromiter(bc.keys(), dtype=np.int64, count=len(bc))
+            if idx.min() < 0 or idx.max() >= n:
+                raise ValueError(f"mesh.dirichlet_nodes: node ids must lie in [0, {n})")
+            is_bc.reshape(n, d)[idx] = 1
+        return is_bc, g
+    if not hasattr(fixed, "items"):
+        raise ValueError("fixed= must be a mapping {(node, component): value}")
+    for key, value in fixed.items():
+        try:
+            node, comp = key
+            node, comp = int(node), int(comp)
+        except (TypeError, ValueError):
+            raise ValueError(f"fixed=: keys are (node, component) pairs, got {key!r}") from None
+        if not 0 <= node < n:
+            raise ValueError(f"fixed=: node {node} out of range [0, {n})")
+        if not 0 <= comp < d:
+            raise ValueError(f"fixed=: component {comp} out of range [0, {d}) on a {d}D mesh")
+        value = float(value)
+        if not math.isfinite(value):
+            raise ValueError(f"fixed=: value of {key!r} is not finite")
+        is_bc[node * d + comp] = 1
+        g[node * d + comp] = value
+    return is_bc, g
+
+
+def dof_pattern(node_cols: np.ndarray, d: int) -> np.ndarray:
+    """The dof ELL pattern (d W, n d) int32 of include/diffhe_elastic.h from the node pattern (W, n): row (i, a), slot
+    s < d -> column (i, (a + s) mod d), the node's own block rotated so that slot 0 is the diagonal; slot k d + b, k >= 1
+    -> column (node_cols[k, i], b); the d slots of an unused node slot point at the row itself."""
+    W, n = node_cols.shape
+    rows = np.arange(n * d, dtype=np.int64)
+    i, a = rows // d, rows % d
+    out = np.empty((d * W, n * d), dtype=np.int64)
+    for s in range(d):
+        out[s] = i * d + (a + s) % d
+    for k in range(1, W):
+        j = node_cols[k].astype(np.int64)[i]
+        for b in range(d):
+            out[k * d + b] = np.where(j == i, rows, j * d + b)
+    if n * d * d * W >= 2 ** 31:
+        raise ValueError("mesh too large for int32 dof entries")
+    return out.astype(np.int32)
+
+
+# ---------------------------------------------------------------------------------------------
+# Per (plan, nu, plane, fixed set): the dof system and its hierarchy
+# ---------------------------------------------------------------------------------------------
+class _DofSystem:
+    """What `_Engine` reads of a plan, for the n d dofs: its solve and layout helpers are generic in (n, W, cols)."""
+
+    def __init__(self, plan, cols, is_bc, g):
+        self.device, self.dim, self.m = plan.device, plan.dim, plan.m
+        self.n, self.W, self.cols, self.is_bc, self.g = plan.n * plan.dim, plan.W * plan.dim, cols, is_bc, g
+
+
+class _ElasticSetup:
+    """The dof system of one (plan, nu, plane, fixed set) and the hierarchy of its unit-E operator, built on first use."""
+
+    def __init__(self, plan, lam1, mu1, is_bc: np.ndarray, g: np.ndarray):
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(plan.device)  # noqa: E731
+        plan.ensure_ell()
+        self.plan, self.lam1, self.mu1 = plan, float(lam1), float(mu1)
+        self.cols_host = dof_pattern(plan.cols.cpu().numpy(), plan.dim)
+        self.is_bc_host = is_bc
+        self.dofs = _DofSystem(plan, dev(self.cols_host), dev(is_bc), dev(g))
+        self.has_data = bool(np.any(g != 0.0))
+        self.free = ~self.dofs.is_bc.bool()
+        self._lock = threading.Lock()
+        self._levels = None
+
+    def assemble(self, kdev, kse, ksb, Bv):
+        """vals (d W, n d, Bv), lift (n d, Bv) of the block row-gather assembly (csrc/elastic.hip)."""
+        plan, dofs = self.plan, self.dofs
+        gtab, vol = plan.gradient_table()
+        vals = torch.empty((dofs.W, dofs.n, Bv), dtype=torch.float64, device=plan.device)
+        lift = torch.empty((dofs.n, Bv), dtype=torch.float64, device=plan.device)
+        _hip.lib().diffhe_elast_assemble_rows(gtab, vol, plan.dim, self.lam1, self.mu1, kdev, kse, ksb, plan.ent_ptr,
+                                              plan.contrib, plan.cols, dofs.is_bc, dofs.g, vals, lift, plan.n, plan.m,
+                                              plan.W, Bv, _stream(plan.device))
+        return vals, lift
+
+    def levels(self):
+        """(device level dicts, (levels with the fine one, operator complexity)) of the unit-E hierarchy."""
+        with self._lock:
+            if self._levels is None:
+                from .amg import build_hierarchy_blocks, hierarchy_stats
+                one = torch.ones(1, dtype=torch.float64, device=self.plan.device)
+                unit, _ = self.assemble(one, 0, 0, 1)
+                host = build_hierarchy_blocks(self.cols_host, unit.reshape(self.dofs.W, self.dofs.n).cpu().numpy(),
+                                              self.is_bc_host, self.plan.dim)
+                self._levels = ([self.plan.upload_amg_level(lv, True) for lv in host],
+                                hierarchy_stats(self.cols_host, host))
+            return self._levels
+
+
+def _setup_of(plan, nu, plane, lam1, mu1, is_bc, g) -> _ElasticSetup:
+    key = (float(nu), plane, is_bc.tobytes(), g.tobytes())
+    with plan._build_lock:
+        cache = plan.__dict__.setdefault("_elastic_setups", {})
+        if key not in cache:
+            while len(cache) >= 4:
+                cache.pop(next(iter(cache)))
+            cache[key] = _ElasticSetup(plan, lam1, mu1, is_bc, g)
+        return cache[key]
+
+
+# ---------------------------------------------------------------------------------------------
+# One call
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class _ElasticCall:
+    """The facts of one call `_run_call` and the adjoint read (none of the input tensors)."""
+    B: int
+    mode: int
+    kappa_em: bool
+    batched: bool
+    node_major: bool
+    out_device: torch.device
+    e_shape: torch.Size
+    e_device: torch.device
+    f_batched: bool
+    load_batched: bool
+
+
+class _ElasticSolve:
+    """One call's solve: forward() keeps what adjoint() needs -- the assembled operator, the hierarchy, the iterate -- and
+    this object is the adjoint state the custom ops hold until the end of backward."""
+
+    def __init__(self, solver: "ElasticFESolver", setup: _ElasticSetup, call: _ElasticCall, tol: float, amg: dict):
+        self.solver, self.setup, self.call, self.amg = solver, setup, call, amg
+        self.plan = setup.plan
+        self.eng = _Engine(setup.dofs, tol, solver.max_iter, solver.check_every, "gather", g=setup.dofs.g)
+        self.node_eng = _Engine(self.plan, tol, solver.max_iter, solver.check_every, "gather")
+
+    # -- layout -----------------------------------------------------------------------------------
+    def _to_dofs(self, t: torch.Tensor, batched: bool, zero_fixed: bool = False) -> torch.Tensor:
+        """(n, d) | (B, n, d) | node-major (n, d, B) -> (n d, Bp), padding samples zero."""
+        call, dofs, Bp, B = self.call, self.setup.dofs, self.Bp, self.call.B
+        t = t.detach().to(self.plan.device, torch.float64)
+        mask = dofs.is_bc if zero_fixed else None
+        if call.node_major:
+            src = t.reshape(dofs.n, B)
+            if Bp == B and src.is_contiguous() and not zero_fixed:
+                return src
+            out = torch.zeros((dofs.n, Bp), dtype=torch.float64, device=self.plan.device)
+            out[:, :B] = src
+            if zero_fixed:
+                out[dofs.is_bc.bool()] = 0.0
+            return out
+        src = t.reshape(B, dofs.n).contiguous() if batched else t.reshape(dofs.n).contiguous()
+        return self.eng.to_node_major(src, B, Bp, dofs.n, zero_mask=mask)
+
+    def _from_dofs(self, x: torch.Tensor, add: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(n d, Bp) -> (B, n, d), or node-major (n, d, B); `add` (n d,) is added to every sample."""
+        call, plan, B, Bp = self.call, self.plan, self.call.B, self.Bp
+        if call.node_major:
+            xo = x if Bp == B else x[:, :B]
+            if add is not None:
+                xo = xo + add.unsqueeze(1)
+            return xo.reshape(plan.n, plan.dim, B)
+        return self.eng.to_sample_major(x, B, Bp, self.setup.dofs.n, add=add).reshape(B, plan.n, plan.dim)
+
+    def _apply_load_map(self, x: torch.Tensor) -> torch.Tensor:
+        """y_a = M x_a per component a with the node-level load map of the plan: the (n, d, Bp) array is an (n, d Bp)
+        node vector; where d Bp is no valid batch width the components go through one by one."""
+        plan, Bp, d = self.plan, self.Bp, self.plan.dim
+        if _valid_batch(d * Bp):
+            return self.node_eng.load_vector(x, None, 1, d * Bp, free_rows=False).reshape(plan.n * d, Bp)
+        xc = x.reshape(plan.n, d, Bp).permute(1, 0, 2).contiguous()
+        yc = torch.stack([self.node_eng.load_vector(xc[a], None, 1, Bp, free_rows=False) for a in range(d)])
+        return yc.permute(1, 0, 2).reshape(plan.n * d, Bp).contiguous()
+
+    # -- forward ----------------------------------------------------------------------------------
+    def forward(self, call_in, info: SolveInfo) -> torch.Tensor:
+        E, f, load = call_in.E, call_in.f, call_in.load
+        solver, setup, plan, call, eng = self.solver, self.setup, self.plan, self.call, self.eng
+        dofs, B = setup.dofs, call.B
+        Bp = self.Bp = padded_batch(B)
+        kdev, kse, ksb, Bv = self.node_eng.kappa_device(E, call.mode, B, Bp, em=call.kappa_em)
+        vals, lift = setup.assemble(kdev, kse, ksb, Bv)
+        rhs = -lift if Bv == Bp else (-lift).expand(dofs.n, Bp).contiguous()
+        if f is not None:
+            rhs += self._apply_load_map(self._to_dofs(f, call.f_batched))
+        if load is not None:
+            rhs += self._to_dofs(load, call.load_batched)
+        rhs[dofs.is_bc.bool()] = 0.0
+        if Bp > B:
+            rhs[:, B:] = 0.0
+        self.hier = None
+        if solver.method != "ell-jacobi":
+            levels, stats = setup.levels()
+            if levels:
+                amg = self.amg
+                if amg.get("scale") is None:
+                    amg["scale"] = 1.3
+                if amg.get("gamma") is None:
+                    amg["gamma"] = 2 if dofs.n * Bp >= 12_000_000 else 1
+                self.hier = eng.amg_setup(vals, Bv, bool(amg.get("fp32", 0)), levels)
+                info.hierarchy, info.hierarchy_levels, info.operator_complexity = "unit", stats[0], stats[1]
+        if self.hier is not None:
+            info.path = "ell-amgpcg"
+            x, its, bad, relres, *_ = eng.amg_pcg(self.hier, rhs, Bp, Bv, self.amg)
+        else:
+            info.path = "ell-pcg"
+            x, its, bad, relres, *_ = eng.cg(vals, rhs, Bp, Bv)
+        info.iterations, info.not_converged = its, bad
+        info.max_relres = float(relres[:B].max())
+        self.vals, self.x, self.Bv = vals, x, Bv
+        return self._from_dofs(x, dofs.g if (setup.has_data or not call.node_major) else None)
+
+    # -- adjoint ----------------------------------------------------------------------------------
+    def adjoint(self, gbar: torch.Tensor, need_e: bool, need_f: bool, need_load: bool):
+        """lambda = A^-1 gbar on the free dofs with the forward's operator and hierarchy, then dL/dE in the shape of E,
+        dL/df = M lambda and dL/dload = lambda in the caller's layout."""
+        call, setup, plan, eng, B, Bp = self.call, self.setup, self.plan, self.eng, self.call.B, self.Bp
+        L, st = eng.L, _stream(plan.device)
+        info = self.solver.last_info
+        rhs = self._to_dofs(gbar, True, zero_fixed=True)
+        if self.hier is not None:
+            res = eng.amg_pcg(self.hier, rhs, Bp, self.Bv, self.amg)
+        else:
+            res = eng.cg(self.vals, rhs, Bp, self.Bv)
+        lam = res.x
+        info.adj_iterations, info.adj_max_relres = res.iterations, float(res.relres[:B].max())
+        info.not_converged += res.not_converged
+        grad_e = grad_f = grad_load = None
+        if need_e:
+            gtab, vol = plan.gradient_table()
+            new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=plan.device)  # noqa: E731
+            args = (plan.elems, gtab, vol, plan.dim, setup.lam1, setup.mu1, lam, self.x, setup.dofs.g, plan.n, plan.m)
+            if call.mode == K_ELEM:         # a field the batch shares: summed over the batch inside the kernel
+                de = new(plan.m)
+                L.diffhe_elast_grad_shared(*args, B, Bp, de, st)
+                grad_e = _kappa_grad(call.mode, call.e_shape, None, de)
+            elif call.mode == K_SAMPLE_ELEM:
+                de = new(plan.m, Bp)
+                L.diffhe_elast_grad(*args, Bp, de, None, None, st)
+                if call.kappa_em:
+                    de = de if Bp == B else de[:, :B]
+                else:
+                    de = self.node_eng.to_sample_major(de, B, Bp, plan.m)
+                grad_e = _kappa_grad(call.mode, call.e_shape, None, de)
+            else:
+                part, total = new(L.diffhe_grad_kappa_blocks(plan.m, Bp), Bp), new(Bp)
+                L.diffhe_elast_grad(*args, Bp, None, part, total, st)
+                grad_e = _kappa_grad(call.mode, call.e_shape, total[:B], None)
+            grad_e = grad_e.to(call.e_device)
+        if need_f:
+            df = self._from_dofs(self._apply_load_map(lam))
+            grad_f = (df if call.f_batched else df.sum(dim=0)).to(call.out_device)
+        if need_load:
+            dl = self._from_dofs(lam)
+            dl = dl.clone() if call.node_major else dl
+            grad_load = (dl if call.load_batched else dl.sum(dim=0)).to(call.out_device)
+        return grad_e, grad_f, grad_load
+
+
+def _valid_batch(Bp: int) -> bool:
+    """A batch width the node kernels take: a power of two <= 64 or a multiple of 64 (include/diffhe_hip.h)."""
+    return Bp > 0 and ((Bp & (Bp - 1)) == 0 if Bp <= 64 else Bp % 64 == 0)
+
+
+@dataclass
+class _Inputs:
+    E: torch.Tensor
+    f: Optional[torch.Tensor]
+    load: Optional[torch.Tensor]
+    B: int
+    batched: bool
+    node_major: bool
+    out_device: torch.device
+
+
+def _batch_of(solver, f: torch.Tensor, load: torch.Tensor, node_major: bool):
+    """-> (B of the right-hand side or None, f batched, load batched) from the op's inputs (empty = absent)."""
+    fb = f.numel() > 0 and f.dim() == 3
+    lb = load.numel() > 0 and load.dim() == 3
+    if node_major:
+        return (f if f.numel() else load).shape[2], fb, lb
+    B = f.shape[0] if fb else (load.shape[0] if lb else None)
+    if fb and lb and f.shape[0] != load.shape[0]:
+        raise ValueError(f"load batch {load.shape[0]} does not match f batch {f.shape[0]}")
+    return B, fb, lb
+
+
+def _elastic_forward(solver: "ElasticFESolver", E, f, load, node_major):
+    plan = solver._plan()
+    setup = _setup_of(plan, solver.nu, solver.plane, solver._lam1, solver._mu1, solver._is_bc, solver._g)
+    B_rhs, fb, lb = _batch_of(solver, f, load, node_major)
+    mode, B, em = _kappa_layout(E, plan.m, B_rhs, node_major)
+    src = f if f.numel() else load
+    call = _ElasticCall(B, mode, em, B_rhs is not None, node_major, src.device if src.numel() else E.device, E.shape,
+                        E.device, fb, lb)
+    tol, _, amg = _call_options(chain=False, lattice=False, closed_boundary=False, n=setup.dofs.n, mode=mode,
+                                tol_user=solver._tol_user, mg_user=set(), mg={}, amg=solver.amg)
+    solver.tol = tol
+    state = _ElasticSolve(solver, setup, call, tol, amg)
+    u = _run_call(state, _Inputs(E, f if f.numel() else None, load if load.numel() else None, B, call.batched,
+                                 node_major, call.out_device))
+    return u, state
+
+
+def _out_shape(solver, E, f, load, node_major):
+    n, d, m = solver.mesh.n_nodes, solver.mesh.dim, solver.mesh.n_elements
+    B_rhs, _, _ = _batch_of(solver, f, load, node_major)
+    if node_major:
+        return (n, d, B_rhs)
+    _, B, _ = _kappa_layout(E, m, B_rhs, False)
+    return (B, n, d) if (B_rhs is not None or B > 1) else (n, d)
+
+
+# ---------------------------------------------------------------------------------------------
+# torch.library custom ops diffhe::elastic_solve / diffhe::elastic_solve_backward; the solver and the state of the call
+# travel as integer handles through the registries of diffhe.solver.  f / load: empty tensor = absent.
+# ---------------------------------------------------------------------------------------------
+@torch.library.custom_op("diffhe::elastic_solve", mutates_args=())
+def elastic_solve(E: torch.Tensor, f: torch.Tensor, load: torch.Tensor, handle: int, save: bool,
+                  node_major: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(u, token) of the `ElasticFESolver` registered under `handle`; `token` names the saved adjoint state (0 when
+    `save` is false)."""
+    u, state = _elastic_forward(_SOLVERS[handle], E, f, load, node_major)
+    return u.clone() if u._base is not None or u.data_ptr() == state.x.data_ptr() else u, _register_state(state, save)
+
+
+@elastic_solve.register_fake
+def _elastic_solve_fake(E, f, load, handle, save, node_major):
+    shape = _out_shape(_SOLVERS[handle], E, f, load, node_major)
+    like = f if f.numel() else (load if load.numel() else E)
+    return like.new_empty(shape, dtype=torch.float64), torch.empty((), dtype=torch.int64)
+
+
+@torch.library.custom_op("diffhe::elastic_solve_backward", mutates_args=())
+def elastic_solve_backward(gbar: torch.Tensor, token: torch.Tensor, need_e: bool, need_f: bool, need_load: bool,
+                           e_like: torch.Tensor, f_like: torch.Tensor,
+                           load_like: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dL/dE, dL/df, dL/dload) of the forward call named by `token` from ONE adjoint solve; unused ones come back empty."""
+    state = _state_of(token)
+    call = state.call
+    g = gbar.detach()
+    if not call.node_major and not call.batched and call.B == 1:
+        g = g.unsqueeze(0)
+    grads = state.adjoint(g, need_e, need_f, need_load)
+    return _like_grads(gbar, grads, (e_like, f_like, load_like))
+
+
+@elastic_solve_backward.register_fake
+def _elastic_solve_backward_fake(gbar, token, need_e, need_f, need_load, e_like, f_like, load_like):
+    return _fake_grads(gbar, (need_e, need_f, need_load), (e_like, f_like, load_like))
+
+
+def _setup_context(ctx, inputs, output):
+    E, f, load = inputs[:3]
+    _tie_state(ctx, output[1], E, f, load)
+
+
+def _backward(ctx, grad_u, _grad_token):
+    if torch.is_grad_enabled():
+        raise NotImplementedError("diffhe: second-order derivatives of an elastic solve are not implemented (backward "
+                                  "with create_graph=True, diffhe.elastic)")
+    token, E, f, load = ctx.saved_tensors[:4]
+    needs = tuple(bool(v) for v in ctx.needs_input_grad[:3])
+    if not any(needs):
+        return (None,) * 6
+    ge, gf, gl = torch.ops.diffhe.elastic_solve_backward(grad_u.contiguous(), token, *needs, E, f, load)
+    return (ge if needs[0] else None, gf if needs[1] else None, gl if needs[2] else None, None, None, None)
+
+
+torch.library.register_autograd("diffhe::elastic_solve", _backward, setup_context=_setup_context)
+
+
+class ElasticFESolver(nn.Module):
+    """Displacement of a linear-elastic body per sample, differentiable with respect to the Young's modulus E per element,
+    the body force f and the nodal load (see the module docstring).
+
+    Parameters
+    ----------
+    mesh : FEMesh -- P1 triangles or P1 tetrahedra.
+    E : float or tensor or Parameter -- (), (B,), (m,), (B, m); (m, B) with layout="node".  May require grad.
+    nu : float, -1 < nu < 0.5.  plane : "stress" (default) or "strain", 2D meshes only.
+    fixed : None (clamp the nodes of mesh.dirichlet_nodes) or {(node, component): value}.
+    device, tol, max_iter, method ("auto" or "ell-jacobi"), amg : as on `DifferentiableFESolver`.
+    """
+
+    def __init__(self, mesh, E=1.0, nu: float = 0.3, *, plane: Optional[str] = None, fixed=None, device=None,
+                 tol: Optional[float] = None, max_iter: int = 20000, method: str = "auto", amg: Optional[dict] = None,
+                 check_every: int = 25):
+        super().__init__()
+        if mesh.dim == 1:
+            raise NotImplementedError("diffhe: elasticity needs a 2D or 3D mesh (a 1D bar is the scalar problem of "
+                                      "DifferentiableFESolver with kappa = E A)")
+        if mesh.dim not in (2, 3):
+            raise NotImplementedError("Only 2D and 3D supported")
+        if mesh.elements.shape[1] != mesh.dim + 1:
+            raise NotImplementedError("diffhe: elasticity is implemented for P1 elements only (this mesh has "
+                                      f"{mesh.elements.shape[1]} nodes per element)")
+        if mesh.dim == 3 and plane is not None:
+            raise ValueError("plane= applies to 2D meshes only (a 3D body needs no plane-stress / plane-strain choice)")
+        self.plane = None if mesh.dim == 3 else ("stress" if plane is None else plane)
+        self.nu = float(nu)
+        self._lam1, self._mu1 = lame_unit(self.nu, mesh.dim, self.plane)
+        if method not in ("auto", "ell", "ell-jacobi"):
+            raise ValueError(f"Unknown method: {method!r}")
+        self.mesh, self.method = mesh, method
+        self._E = torch.tensor(float(E), dtype=torch.float64) if isinstance(E, (int, float)) else E.to(dtype=torch.float64)
+        self._is_bc, self._g = parse_fixed(mesh, fixed)
+        # the options of the general path's aggregation-multigrid PCG, as on DifferentiableFESolver
+        self.amg = dict(n_coarse=16, gamma=None, scale=None, fp32=0, max_iter=20000, smoothed=1)
+        self.amg.update(amg or {})
+        if float(self.amg.get("strength", 0) or 0) > 0.0:
+            raise NotImplementedError("diffhe: amg=dict(strength=...) is not implemented for elasticity (the hierarchy "
+                                      "is built from the unit-E operator)")
+        if not self.amg.get("smoothed", 1):
+            raise NotImplementedError("diffhe: elasticity builds a smoothed-aggregation hierarchy (amg smoothed=0 is not "
+                                      "implemented)")
+        self._device = device
+        self._tol_user = tol
+        self.tol, self.max_iter, self.check_every = tol, int(max_iter), int(check_every)
+        self.last_info = SolveInfo()
+
+    @property
+    def E(self) -> torch.Tensor:
+        return self._E
+
+    def _plan(self):
+        return get_plan(self.mesh, _resolve_device(self._device), prune=False)
+
+    def _checked(self, t, name: str, layout: str):
+        n, d = self.mesh.n_nodes, self.mesh.dim
+        if t is None:
+            return None
+        t = t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+        if layout == "node":
+            if t.dim() != 3 or tuple(t.shape[:2]) != (n, d):
+                raise ValueError(f"layout='node': f (and load) must be (n, d, B) with n={n}, d={d}, got {tuple(t.shape)}")
+        elif t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (n, d):
+            raise ValueError(f"{name} must be (n, d) or (B, n, d) with n={n}, d={d}, got {tuple(t.shape)}")
+        return t.to(torch.float64)
+
+    def forward(self, f: Optional[torch.Tensor] = None, load: Optional[torch.Tensor] = None, layout: str = "sample",
+                dirichlet=None, h=None, u_inf=None, flux=None) -> torch.Tensor:
+        """u for the body force f and the nodal load: (n, d), (B, n, d), or (n, d, B) with layout="node" -- the shape of
+        the right-hand side.  f None: zero."""
+        if dirichlet is not None:
+            raise NotImplementedError("diffhe: dirichlet= is not implemented for elasticity (the boundary-band kernels "
+                                      "read scalar element tables); give prescribed displacements with fixed=")
+        if h is not None or u_inf is not None or flux is not None:
+            raise NotImplementedError("diffhe: Robin / flux data (h=, u_inf=, flux=) are not implemented for elasticity; "
+                                      "integrate a traction into load=")
+        if layout not in ("sample", "node"):
+            raise ValueError(f"Unknown layout: {layout!r}")
+        if self.mesh.nodes.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("diffhe: node gradients are not implemented for elasticity (mesh.nodes requires "
+                                      "grad)")
+        f64, load64 = self._checked(f, "f", layout), self._checked(load, "load", layout)
+        if layout == "node":
+            if f64 is None and load64 is None:
+                raise ValueError("layout='node' needs f or load to carry the batch: (n, d, B)")
+            if f64 is not None and load64 is not None and f64.shape != load64.shape:
+                raise ValueError(f"layout='node': f (and load) must be (n, d, B) with one B, got {tuple(f64.shape)} and "
+                                 f"{tuple(load64.shape)}")
+        E = self._E
+        empty = E.new_empty(0)
+        if f64 is None and load64 is None:
+            f64 = torch.zeros((self.mesh.n_nodes, self.mesh.dim), dtype=torch.float64, device=E.device)
+        f_in, load_in = (empty if f64 is None else f64), (empty if load64 is None else load64)
+        _kappa_layout(E, self.mesh.n_elements, _batch_of(self, f_in, load_in, layout == "node")[0], layout == "node")
+        _SOLVERS[id(self)] = self
+        save = torch.is_grad_enabled() and (E.requires_grad or f_in.requires_grad or load_in.requires_grad)
+        u, _token = torch.ops.diffhe.elastic_solve(E, f_in, load_in, id(self), save, layout == "node")
+        return u
