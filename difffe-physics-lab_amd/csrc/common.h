@@ -13,12 +13,29 @@ namespace diffhe {
 // hi is exactly (float)R -- what a plain fp32 copy of R would hold -- and lo the float nearest to the remainder R - hi
 // (exact in fp64: hi has 24 of R's 53 bits).  hi + lo keeps 48 bits of R, |join(split(R)) - R| <= 2^-48 |R|, as long as
 // lo is a normal float; a remainder below the fp32 range flushes towards 0 and costs nothing but those bits.
-// Plain C++ below this line up to the HIP-only part: a host compiler may include this header for the two functions alone.
+// Plain C++ below this line up to the HIP-only part: a host compiler may include this header for these functions alone.
 DIFFHE_HD inline void split(double R, float& hi, float& lo) {
   hi = (float)R;
   lo = (float)(R - (double)hi);
 }
 DIFFHE_HD inline double join(float hi, float lo) { return (double)hi + (double)lo; }
+
+// One residual update R <- R - t on that pair (t = rs alpha (A p), fp64), in the three forms of lattice.h:
+//   READ_LO, WRITE_LO  (F_RPAIR)    R = hi + lo - t, stored as split(R): 2^-48 relative;
+//   READ_LO only       (F_RDROP)    R = hi + lo - t, stored as hi = (float)R alone: lo is dead afterwards;
+//   neither            (F_RSINGLE)  R = hi - t,      stored as hi = (float)R: a plain fp32 residual, 2^-25 relative.
+// hi (and lo where written) are updated in place; returns the value actually STORED, what r.r is taken from.
+template <bool READ_LO, bool WRITE_LO>
+DIFFHE_HD inline double pair_update(float& hi, float& lo, double t) {
+  static_assert(READ_LO || !WRITE_LO, "a pair that is written is read by the next update");
+  const double R = (READ_LO ? join(hi, lo) : (double)hi) - t;
+  if (WRITE_LO) {
+    split(R, hi, lo);
+    return join(hi, lo);
+  }
+  hi = (float)R;
+  return (double)hi;
+}
 
 }  // namespace diffhe
 

@@ -67,7 +67,7 @@ enum { M_APPLY = 0, M_RESID = 1, M_JACOBI = 2 };
 //              columns 2 J0 - 1 .. 2 J0 + 2 CW - 1 that feed the wave's CW coarse columns (one fine
 //              column is shared with -- and recomputed by -- each neighbour strip) and the tile the
 //              fine rows 2 I0 - 1 .. 2 I1 - 1 of the coarse rows I0 .. I1 - 1.
-enum { F_NONE = 0, F_PROLONG = 1, F_PUPD = 2, F_RESTRICT = 3, F_PUPD_NX = 4, F_RUPD = 5, F_RPAIR = 6 };
+enum { F_NONE = 0, F_PROLONG = 1, F_PUPD = 2, F_RESTRICT = 3, F_PUPD_NX = 4, F_RUPD = 5, F_RPAIR = 6, F_RDROP = 7, F_RSINGLE = 8 };
 // F_RUPD (with M_APPLY): the CG's residual update with A p RECOMPUTED from the stored direction p (TA, ex.p_in) instead of
 // read back: r -= alpha (A p), the fp32 copy of r and the partials of r.r in one pass -- for a batch-shared matrix (scalar
 // loads, no coefficient traffic) reading p's window (4 B + halo) is cheaper than writing and re-reading A p (8 + 8 B).
@@ -79,12 +79,24 @@ enum { F_NONE = 0, F_PROLONG = 1, F_PUPD = 2, F_RESTRICT = 3, F_PUPD_NX = 4, F_R
 // it is F_RUPD on the pair (p 4 B, hi and lo read and written: 20 B per node and sample instead of 24), with M_RESID
 // the residual pass that opens the CG loop (x, b read, hi and lo written: 24 B instead of 28; the partials are those
 // of F_NONE).  The solver's default on the path where F_RUPD applies; DIFFHE_PCG_RESID_FP64 keeps the fp64 residual.
-static_assert((DIFFHE_PCG_RESID_FP64 & (DIFFHE_PCG_FP32 | DIFFHE_PCG_FMG | (3 << DIFFHE_PCG_FMG_CYCLES_SHIFT) | DIFFHE_PCG_NO_FLOOR |
-                                        DIFFHE_PCG_WARM | DIFFHE_PCG_UNFUSED | DIFFHE_PCG_DENSE_SCALAR |
-                                        DIFFHE_PCG_CLOSED_FP32_STEP | DIFFHE_PCG_PRE2)) == 0,
-              "DIFFHE_PCG_RESID_FP64 must be a bit of its own");
+// F_RDROP, F_RSINGLE (with M_APPLY): the same update once the solve is within 2^16 of the level its energy rule stops at
+// (pcg_scalar_kernel, S_BETA), where the low half no longer buys anything the stop rules can see.  F_RDROP is the
+// transition: it reads the pair and stores hi = (float)R alone (16 B), rlo is dead afterwards; F_RSINGLE reads and
+// writes hi only (12 B).  One template, told apart by rupd_reads_lo / rupd_writes_lo (common.h pair_update); r.r is
+// taken from the value stored in every form.  DIFFHE_PCG_RESID_KEEP_LO keeps F_RPAIR throughout.
+constexpr int kPcgKnownBits = DIFFHE_PCG_FP32 | DIFFHE_PCG_FMG | (3 << DIFFHE_PCG_FMG_CYCLES_SHIFT) | DIFFHE_PCG_NO_FLOOR |
+                              DIFFHE_PCG_WARM | DIFFHE_PCG_UNFUSED | DIFFHE_PCG_DENSE_SCALAR | DIFFHE_PCG_CLOSED_FP32_STEP |
+                              DIFFHE_PCG_PRE2;
+static_assert((DIFFHE_PCG_RESID_FP64 & kPcgKnownBits) == 0, "DIFFHE_PCG_RESID_FP64 must be a bit of its own");
+static_assert((DIFFHE_PCG_RESID_KEEP_LO & (kPcgKnownBits | DIFFHE_PCG_RESID_FP64)) == 0,
+              "DIFFHE_PCG_RESID_KEEP_LO must be a bit of its own");
+static_assert(((15 << DIFFHE_PCG_TRUST_ITS_SHIFT) & (kPcgKnownBits | DIFFHE_PCG_RESID_FP64 | DIFFHE_PCG_RESID_KEEP_LO)) == 0,
+              "the four bits at DIFFHE_PCG_TRUST_ITS_SHIFT must be their own");
 constexpr bool is_pupd(int fuse) { return fuse == F_PUPD || fuse == F_PUPD_NX; }
-constexpr bool is_rupd(int fuse) { return fuse == F_RUPD || fuse == F_RPAIR; }
+constexpr bool is_rpair(int fuse) { return fuse == F_RPAIR || fuse == F_RDROP || fuse == F_RSINGLE; }   // hi (+ lo) forms
+constexpr bool rupd_reads_lo(int fuse) { return fuse == F_RPAIR || fuse == F_RDROP; }
+constexpr bool rupd_writes_lo(int fuse) { return fuse == F_RPAIR; }
+constexpr bool is_rupd(int fuse) { return fuse == F_RUPD || is_rpair(fuse); }
 // M_RESID, F_RPAIR differs from M_RESID, F_NONE in what it stores only
 constexpr bool plain_resid(int mode, int fuse) { return mode == M_RESID && (fuse == F_NONE || fuse == F_RPAIR); }
 
@@ -109,7 +121,7 @@ struct Extra {
   const unsigned char* mask;  // M_APPLY, F_NONE: rows with mask[i] != 0 are stored as 0 (may be NULL)
   int dot_bx;               // M_RESID, F_NONE: the partial sums hold b.x (energy of the iterate) instead of r.r ...
   double* part2;            //   ... and these (same layout as `part`) x.(A x)
-  float* rlo;               // F_RPAIR: low parts of the residual pair (the high parts are r32; rscale applies)
+  float* rlo;               // F_RPAIR, F_RDROP: low parts of the residual pair (the high parts are r32; rscale applies)
 };
 
 // Workgroups are handed to the 8 XCDs round-robin by linear id, so blocks x = k (mod 8) share one L2.

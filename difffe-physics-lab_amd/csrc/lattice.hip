@@ -542,6 +542,15 @@ struct PcgScalars {
   int e_max_it;           // the energy rule is trusted within this many iterations (10 at tol_energy 1e-11, one more per decade)
   int have_energy;        // energy[] was set from the full-multigrid start (S_ENERGY)
   int* rule;              // out: which rule ended each sample: 0 none (iteration cap), 1 residual, 2 energy-norm estimate
+  // The residual pair's low half is dropped near the end of an energy-rule solve (F_RDROP / F_RSINGLE, lattice.h).
+  // S_BETA counts in n_active[1] the samples still active that are NOT yet within 2^16 of the level the energy rule stops
+  // them at (est_b^2 <= 2^32 tol_e2), or for which that rule is not in force: the host drops once n_active[1] == 0.
+  // Each dropped update rounds an entry of r by <= 2^-25 relative and r shrinks >= 10x per iteration, so what
+  // accumulates is <= 2^-24 |r| of the transition, 2^-8 of the exit level: inside the estimate's own accuracy.
+  double* gap;            // per sample g_b = 2^-24 sqrt(r_b.r_b) of the transition update: bound of that accumulated rounding
+  int lo_state;           // S_CONV: 0 the pair is whole; 1 this update was the transition (sets gap); 2 after it.  From
+                          // the transition on the residual rule tests (sqrt(rr_b) + g_b)^2: the rounding can delay a
+                          // residual-rule stop, never fake one
 };
 enum { S_INIT = 0, S_RZ0 = 1, S_ALPHA = 2, S_CONV = 3, S_BETA = 4, S_RELRES = 5, S_SUM = 6, S_FLOOR = 7, S_ENERGY = 8,
        S_ENERGY2 = 9 };
@@ -627,19 +636,26 @@ __global__ __launch_bounds__(1024) void pcg_scalar_kernel(int phase, const doubl
       // with scaled fp32 copies z, p and Ap carry the factor rs and both dots rs^2: alpha is unchanged, and the
       // updates x += alpha p, r -= alpha Ap take alpha / rs
       S.alpha[b] = (S.active[b] && a > 0.0) ? (S.rz[b] / a) / (S.rs ? S.rs[b] : 1.0) : 0.0;
-      if (b == 0) *S.n_active = 0;
+      if (b == 0) S.n_active[0] = S.n_active[1] = 0;
       break;
     case S_CONV:  // a = r.r after the update
+      if (S.lo_state == 1) S.gap[b] = 5.9604644775390625e-08 * sqrt(a);   // 2^-24 |r_b|
       if (S.active[b]) {
         S.iters[b] += 1;
         S.rr[b] = a;
-        if (a <= S.tol2[b]) {
+        double seen = a;   // what the residual rule is shown
+        if (S.lo_state) {
+          const double up = sqrt(a) + S.gap[b];
+          seen = up * up;
+        }
+        if (seen <= S.tol2[b]) {
           S.active[b] = 0;
           S.rule[b] = 1;
         }
       }
       break;
-    case S_BETA:  // a = r.z (new)
+    case S_BETA: {  // a = r.z (new)
+      bool far = false;   // still active and too far from the energy rule's stop to drop the residual's low half
       if (S.active[b]) {
         S.beta[b] = a / S.rz[b];
         S.rz[b] = a;
@@ -659,11 +675,15 @@ __global__ __launch_bounds__(1024) void pcg_scalar_kernel(int phase, const doubl
           S.active[b] = 0;
           S.rule[b] = 2;
         }
+        far = S.active[b] && !(S.tol_e2 > 0.0 && a > 0.0 && S.energy[b] > 0.0 && S.iters[b] < S.e_max_it &&
+                               e2 <= 4294967296.0 * S.tol_e2 * S.energy[b]);   // est_b <= 2^16 x the stop level
       } else {
         S.beta[b] = 0.0;
       }
-      if (S.active[b]) atomicAdd(S.n_active, 1);                      // read by the host after this phase
+      if (S.active[b]) atomicAdd(S.n_active, 1);                      // both read by the host after this phase
+      if (far) atomicAdd(S.n_active + 1, 1);
       break;
+    }
     case S_SUM:  // plain per-sample total
       relres[b] = a;
       break;
@@ -1411,6 +1431,8 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   if (flags & DIFFHE_PCG_DENSE_SCALAR) H.dense_mfma = 0;  // scalar-load dense coarse solve
   if (flags & DIFFHE_PCG_PRE2) H.pre4 = 0;                // fused PRE pass with two samples per lane as well (A/B runs, tests)
   const bool resid64 = (flags & DIFFHE_PCG_RESID_FP64) != 0;  // keep the fp64 residual where the pair would apply (A/B runs, tests)
+  const bool keep_lo = (flags & DIFFHE_PCG_RESID_KEEP_LO) != 0;   // ... and the pair whole to the end of the solve (the same)
+  const int trust_its = (flags >> DIFFHE_PCG_TRUST_ITS_SHIFT) & 15;   // development, tests: the energy rule's trusted iterations
   double* w = work + carve(H, work, f32);
   float* r32 = f32 ? (float*)H.rhs[0] : nullptr;
   double* r = w;
@@ -1430,7 +1452,7 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   S.rz = sc; S.alpha = sc + Bp; S.beta = sc + 2 * Bp; S.bb = sc + 3 * Bp; S.tol2 = sc + 4 * Bp;
   S.active = (int*)(sc + 5 * Bp);
   S.iters = iters;
-  S.n_active = (int*)(sc + 6 * Bp);
+  S.n_active = (int*)(sc + 6 * Bp);   // two ints: [0] active samples, [1] those of them too far to drop the low half
   const bool use_floor = (flags & DIFFHE_PCG_NO_FLOOR) == 0;  // set: stop on `tol` alone
   S.maxdiag = sc + 9 * Bp;  // Bv entries (Bv <= Bp)
   S.rs = f32 ? sc + 11 * Bp : nullptr;
@@ -1439,6 +1461,8 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   S.energy = sc + 12 * Bp;
   S.est = err_est ? err_est : sc + 13 * Bp;
   S.rr = sc + 14 * Bp;
+  S.gap = sc + 15 * Bp;
+  S.lo_state = 0;
   S.rule = stop_rule ? stop_rule : (int*)(sc + 7 * Bp);
   double* alpha_ring = sc + 16 * Bp;              // n_slots (<= 10) rows of Bp step lengths (the scalar block has 32 rows)
   double* const alpha_single = S.alpha;
@@ -1447,6 +1471,7 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   // cycle's convergence factor; measured reductions of the nodal error by that step: 5-8x)
   S.tol_e2 = tol_energy > 0.0 ? (tol_energy / 0.3) * (tol_energy / 0.3) : 0.0;
   S.e_max_it = 10 + ((tol_energy > 0.0 && tol_energy < 1e-11) ? (int)ceil(log10(1e-11 / tol_energy) - 1e-9) : 0);
+  if (trust_its) S.e_max_it = trust_its;
   S.have_energy = 0;
   if (use_floor && use_fmg) {
     rc = diffhe::check(hipMemsetAsync((void*)S.maxdiag, 0, sizeof(double) * Bv, st));
@@ -1509,6 +1534,7 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
     if (rc) return rc;
     status_host[0] = 0;
     status_host[1] = 0;
+    status_host[3] = 0;
     return DIFFHE_OK;
   }
 
@@ -1669,6 +1695,11 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   if (rc) return rc;
 
   int n_active = -1;
+  // The pair's low half (PcgScalars::gap has the argument): whole until the batch is near its energy-rule stop, then ONE
+  // update that reads the pair and stores hi alone (F_RDROP), then hi alone (F_RSINGLE).  Only where that rule is in force.
+  bool may_drop = rpair && !keep_lo && S.tol_e2 > 0.0;
+  int lo_state = 0;      // form of the next update: 0 F_RPAIR, 1 F_RDROP, 2 F_RSINGLE
+  int n_single = 0;      // updates that wrote no low half (status_host[3])
   while (it < max_iter) {
     apply_step(it == 0);
     SCALAR(S_ALPHA, partA, nba);
@@ -1683,9 +1714,13 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
       ex.rlo = rlo;
       // 5 waves per SIMD: 1.30 ms at 1024^2 x 256 (compiler's own choice 1.30, 7 waves 2.31 with spills; gpurun_out/r4q)
       // the pair form: 1.13 ms; the compiler's own choice measured 0.8 ms per step slower
-      if (rpair)
-        launch_strip<double, M_APPLY, false, F_RPAIR, float, kPupdCols, 5, MAT_SHARED>(   // rupd: Bv == 1
-            L0, Bv, scale, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, 0.0, 0.0, partA, Bp, g0, st, ex);
+#define RUPD_PAIR(FUSE_)                                                                                   \
+  launch_strip<double, M_APPLY, false, FUSE_, float, kPupdCols, 5, MAT_SHARED>(   /* rupd: Bv == 1 */        \
+      L0, Bv, scale, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, 0.0, 0.0, partA, Bp, g0, st, ex)
+      if (rpair && lo_state == 0) RUPD_PAIR(F_RPAIR);
+      else if (rpair && lo_state == 1) RUPD_PAIR(F_RDROP);
+      else if (rpair) RUPD_PAIR(F_RSINGLE);
+#undef RUPD_PAIR
       else
         launch_strip<double, M_APPLY, false, F_RUPD, float, kPupdCols, 5, MAT_SHARED>(
             L0, Bv, scale, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, 0.0, 0.0, partA, Bp, g0, st, ex);
@@ -1694,18 +1729,33 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
              r, r32, (const double*)S.rs, partA, n, Bp);
     }
     kp_end(KP_UPDATE, st);
+    S.lo_state = lo_state;
     SCALAR(S_CONV, partA, rupd ? g0.ncb * g0.nrc : nblk);
     ++it;
+    if (lo_state) {
+      ++n_single;
+      lo_state = 2;
+      if (it >= S.e_max_it) {
+        // the energy rule is no longer trusted from here on, and with it the argument that let the low half go: replace
+        // the residual ONCE by b - A x of the iterate (which rewrites the pair) and keep it whole for the rest of the solve
+        flush_directions(false);
+        residual_pass(false);
+        lo_state = 0;
+        may_drop = false;
+      }
+    }
     // z = V(r) and r.z: the new search direction's ingredients AND the energy-norm error estimate of the iterate;
     // the samples still active are counted in the scalar phase behind it (S_BETA)
     precondition(0);
-    rc = diffhe::check(hipMemcpyAsync(&status_host[2], S.n_active, sizeof(int), hipMemcpyDeviceToHost, st));
+    // [2] the active samples, [3] those of them that still need the low half: one copy, as before
+    rc = diffhe::check(hipMemcpyAsync(&status_host[2], S.n_active, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (rc) return rc;
     rc = diffhe::check(hipStreamSynchronize(st));
     if (rc) return rc;
     n_active = status_host[2];
     kp_collect();  // the stream is idle here
     if (n_active == 0) break;
+    if (may_drop && lo_state == 0 && status_host[3] == 0) lo_state = 1;   // sticky: only the replacement above undoes it
   }
   // fold the directions still in the ring into x and add the final V-cycle's correction z (pcg_finish_kernel);
   // the unfused loop kept x current: only z is due there
@@ -1718,6 +1768,7 @@ extern "C" int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_lev
   if (rc) return rc;
   status_host[0] = it;
   status_host[1] = n_active < 0 ? 0 : n_active;
+  status_host[3] = n_single;
   return DIFFHE_OK;
 }
 

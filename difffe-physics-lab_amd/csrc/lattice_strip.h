@@ -79,14 +79,15 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
   const TA* __restrict__ aux = (const TA*)ex.a0;
   // F_PUPD row pointers at (row, c0w), advanced with the others
   const TA* __restrict__ pz = (is_pupd(FUSE)) ? aux + i0 * Bp : nullptr;
-  constexpr bool kRupd = MODE == M_APPLY && is_rupd(FUSE);   // residual update: fp64 r (F_RUPD) or the pair (F_RPAIR)
+  constexpr bool kRupd = MODE == M_APPLY && is_rupd(FUSE);   // residual update: fp64 r (F_RUPD) or the pair's forms (is_rpair)
+  constexpr bool kRdLo = rupd_reads_lo(FUSE), kWrLo = rupd_writes_lo(FUSE);
   const TA* __restrict__ ppi = (is_pupd(FUSE) || kRupd) ? (const TA*)ex.p_in + i0 * Bp : nullptr;
   double* __restrict__ pr = (FUSE == F_RUPD) ? ex.x + i0 * Bp : nullptr;          // F_RUPD: ex.x is the residual r
-  float* __restrict__ pr32 = (kRupd && ex.r32) ? ex.r32 + i0 * Bp : nullptr;     // F_RPAIR: the high parts (never NULL)
-  float* __restrict__ plo = (kRupd && FUSE == F_RPAIR) ? ex.rlo + i0 * Bp : nullptr;
+  float* __restrict__ pr32 = (kRupd && ex.r32) ? ex.r32 + i0 * Bp : nullptr;     // is_rpair: the high parts (never NULL)
+  float* __restrict__ plo = (kRupd && kRdLo) ? ex.rlo + i0 * Bp : nullptr;
   const double alpha_cur = kRupd ? ex.alpha[b] : 0.0;
   const double rsc_u = (kRupd && ex.r32 && ex.rscale) ? ex.rscale[b] : 1.0;
-  const double ralpha = rsc_u * alpha_cur, inv_rsc_u = 1.0 / rsc_u;   // F_RPAIR; rsc_u is a power of two: both exact
+  const double ralpha = rsc_u * alpha_cur, inv_rsc_u = 1.0 / rsc_u;   // is_rpair; rsc_u is a power of two: both exact
   TA* __restrict__ ppo = (is_pupd(FUSE)) ? (TA*)ex.p_out + i0 * Bp : nullptr;
   double* __restrict__ pxx = (FUSE == F_PUPD && ex.x) ? ex.x + i0 * Bp : nullptr;  // NULL: the iterate is not touched
 
@@ -189,16 +190,16 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
       const double sh = SHIFT ? psh[dq[k + 1]] : 0.0;   // A = sb K + diag(shift)
       const double diag = SHIFT ? sb * d0[k] + sh : sb * d0[k];
       const double Ax = SHIFT ? sb * acc + sh * xc[q] : sb * acc;
-      if (MODE == M_APPLY && FUSE == F_RPAIR) {
+      if (MODE == M_APPLY && is_rpair(FUSE)) {
         // R = rs r as hi + lo: hi is the V-cycle's input (left cacheable), lo is touched here only (nontemporal, as
-        // the fp64 r of F_RUPD).  r.r is taken from the STORED pair: S_CONV judges the residual the solver carries.
+        // the fp64 r of F_RUPD) -- read by F_RPAIR and F_RDROP, written by F_RPAIR alone.  r.r is taken from what is
+        // STORED, pair or hi: S_CONV judges the residual the solver carries.
         float* ha = &(pr32 + o)[lb];
-        float* la = &(plo + o)[lb];
-        float hi, lo;
-        split(join(*ha, __builtin_nontemporal_load(la)) - ralpha * Ax, hi, lo);
+        float hi = *ha, lo = 0.0f;
+        if (kRdLo) lo = __builtin_nontemporal_load(&(plo + o)[lb]);
+        const double ri = pair_update<kRdLo, kWrLo>(hi, lo, ralpha * Ax) * inv_rsc_u;
         *ha = hi;
-        __builtin_nontemporal_store(lo, la);
-        const double ri = join(hi, lo) * inv_rsc_u;
+        if (kWrLo) __builtin_nontemporal_store(lo, &(plo + o)[lb]);
         s += ri * ri;
       } else if (MODE == M_APPLY && FUSE == F_RUPD) {
         double* ra = &(pr + o)[lb];
@@ -413,7 +414,8 @@ void launch_strip(const Level& L, int Bv, const double* scale, const TV* xin, co
     else if (MODE == M_RESID) bpn = 2.0 * tv + (FUSE == F_RESTRICT ? 0.25 * tv : (out ? tv : 0.0) + (ex.r32 ? 4.0 : 0.0) + (FUSE == F_RPAIR ? 4.0 : 0.0));
     else if (is_pupd(FUSE)) bpn = (ex.first ? 2.0 * ta : 3.0 * ta) + (out ? 8.0 : 0.0) + ((FUSE == F_PUPD && ex.x) ? 16.0 : 0.0);
     else if (FUSE == F_RUPD) bpn = ta + 16.0 + (ex.r32 ? 4.0 : 0.0);   // p; r read and written; its fp32 copy
-    else if (FUSE == F_RPAIR) bpn = ta + 16.0;                            // p; hi and lo read and written
+    else if (is_rpair(FUSE))   // p; hi read and written; lo read (F_RPAIR, F_RDROP) and written (F_RPAIR): 20, 16, 12 B
+      bpn = ta + 8.0 + (rupd_reads_lo(FUSE) ? 4.0 : 0.0) + (rupd_writes_lo(FUSE) ? 4.0 : 0.0);
     else bpn = tv + (out ? tv : 0.0) + (ex.dotv ? 8.0 : 0.0);
     if (Bv != 1) bpn += m16 ? 4.0 + 2.0 * (L.nd - 1) : L.nd * (m32 ? 4.0 : 8.0);
     diffhe::account(bpn * (double)L.n * Bp);

@@ -21,6 +21,8 @@ INST(double, M_APPLY, false, F_PUPD_NX, float, 4, 7, MAT_ANY);        // solve: 
 INST(double, M_APPLY, false, F_PUPD_NX, float, 4, 4, MAT_PER_SAMPLE); // CG step, fp32 directions, Bv != 1
 INST(double, M_APPLY, false, F_RUPD, float, 4, 5, MAT_SHARED);        // residual update with A p recomputed (rupd: Bv == 1)
 INST(double, M_APPLY, false, F_RPAIR, float, 4, 5, MAT_SHARED);       // ... on the fp32 pair (the default of that path)
+INST(double, M_APPLY, false, F_RDROP, float, 4, 5, MAT_SHARED);       // ... reading the pair, storing hi alone (the transition)
+INST(double, M_APPLY, false, F_RSINGLE, float, 4, 5, MAT_SHARED);     // ... on hi alone (after it)
 INST(double, M_RESID, false, F_RPAIR, double, 8, 1, MAT_SHARED);      // residual_pass writing the pair
 INST(double, M_APPLY, false, F_PUPD, float, 4, 1, MAT_ANY);           // diffhe_lattice_cg_step with the iterate update, fp32 z
 INST(double, M_APPLY, false, F_PUPD, double, 4, 1, MAT_ANY);          // diffhe_lattice_cg_step with the iterate update, fp64 z

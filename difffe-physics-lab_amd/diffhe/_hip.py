@@ -178,6 +178,8 @@ PCG_DENSE_SCALAR = 128
 PCG_CLOSED_FP32_STEP = 256
 PCG_PRE2 = 512
 PCG_RESID_FP64 = 1 << 10   # DIFFHE_PCG_RESID_FP64
+PCG_RESID_KEEP_LO = 1 << 11   # DIFFHE_PCG_RESID_KEEP_LO
+PCG_TRUST_ITS_SHIFT = 12    # DIFFHE_PCG_TRUST_ITS_SHIFT: four bits
 
 
 def lib():

@@ -52,6 +52,10 @@ class SolveInfo:
     # ("cap" = neither rule fired before the iteration cap; the direct dense path iterates nothing and reports {})
     stop_rules: Optional[dict] = None
     adj_stop_rules: Optional[dict] = None
+    # lattice path, residual carried as a pair of fp32 vectors: how many of the solve's residual updates wrote no low
+    # half (one that still read it, then hi alone); 0 where the pair is kept whole or not carried at all
+    resid_single_updates: int = 0
+    adj_resid_single_updates: int = 0
     tol_energy: float = 0.0     # the energy-norm tolerance in force for this call (0: residual rule alone)
     # lattice path, fp32-stored V-cycle: where its coefficients come from -- "shared-fp32" (batch-shared matrix, scalar
     # loads), "fp16-rowsum" (per-sample matrices: fp32 diagonal + scaled fp16 couplings), "fp32" (per-sample plain fp32
@@ -129,6 +133,7 @@ class _Solved(NamedTuple):
     est: Optional[torch.Tensor] = None      # lattice path: (Bp,) estimated relative energy-norm error
     rule: Optional[torch.Tensor] = None     # lattice path: (Bp,) int32, the rule that stopped each sample
     flags: int = 0                          # lattice path: the `flags` word handed to diffhe_lattice_pcg_solve
+    single_updates: int = 0                 # lattice path: residual updates that wrote no low half (status word 3)
 
 
 class _Engine:
@@ -321,6 +326,8 @@ class _Engine:
         iters = torch.empty(Bp, dtype=torch.int32, device=p.device)
         st = status_buffer()
         launch(x, relres, iters, st)
+        if lattice:
+            lattice["single_updates"] = int(st[3])
         return _Solved(x, int(st[0]), int(st[1]), relres, **lattice)
 
     def cg(self, vals, rhs, Bp, Bv) -> _Solved:
@@ -468,6 +475,8 @@ class _Engine:
                  | (0 if int(mg.get("dense_mfma", 1)) else _hip.PCG_DENSE_SCALAR)
                  | (0 if int(mg.get("pre4", 1)) else _hip.PCG_PRE2)
                  | (0 if int(mg.get("resid_pair", 1)) else _hip.PCG_RESID_FP64)
+                 | (0 if int(mg.get("resid_drop_lo", 1)) else _hip.PCG_RESID_KEEP_LO)
+                 | ((int(mg.get("trust_its", 0)) & 15) << _hip.PCG_TRUST_ITS_SHIFT)   # development, tests
                  | (_hip.PCG_CLOSED_FP32_STEP if closed_step else 0))
         # a multigrid-preconditioned CG that has not converged in a few hundred iterations never will:
         # bound the loop so a defect surfaces as `not_converged` instead of minutes of GPU time
@@ -672,6 +681,10 @@ def _precision_text(flags: int, coeff_storage: str, Bv: int, Bp: int, fused_lib:
         if not flags & _hip.PCG_RESID_FP64:
             parts.append("r is carried as a pair of fp32 vectors (hi = the V-cycle's input, lo = the remainder: 48 bits, "
                          "updated in fp64 registers) where the fused CG loop runs; mg={'resid_pair': 0} keeps it fp64")
+            if not flags & _hip.PCG_RESID_KEEP_LO:
+                parts.append("with the energy rule in force lo is dropped once every active sample's estimate is within "
+                             "2^16 of its stop level (r is then hi alone, 24 bits per update; info.resid_single_updates "
+                             "counts those updates); mg={'resid_drop_lo': 0} keeps both halves")
         if flags & _hip.PCG_CLOSED_FP32_STEP and Bp % 64 == 0 and coeff_storage == "shared-fp32":
             parts.append("p.Ap: stencil in fp32 on the stored p, accumulated fp64 -- enters the STEP LENGTH alpha only "
                          "(closed regular lattice); r = b - A x holds in fp64 whatever alpha is")
@@ -1027,7 +1040,7 @@ class _LatticeSolve(_NodeMajorSolve):
                 self.mg = dict(self.mg, fp32=0)        # the direct product runs in fp64
             self.dense = plan.dense_coarse(didx, vals, bool(self.mg.get("fp32")))
         self.wkey = (Bp, mode, reaction)
-        x, its, bad, relres, est, rule, flags = eng.lattice_pcg(
+        x, its, bad, relres, est, rule, flags, info.resid_single_updates = eng.lattice_pcg(
             vals, Bv, scale, rhs, Bp, self.mg, self.vals32, self.dense,
             x0=plan.warm_get(("u",) + self.wkey) if solver.warm_start else None, shift=self.shift, rdiag32=self.rdiag32,
             off16=self.off16)
@@ -1075,6 +1088,7 @@ class _LatticeSolve(_NodeMajorSolve):
             plan.warm_put(("lambda",) + self.wkey, res.x)
         info.adj_stop_rules = _rule_counts(res.rule, B) if not self.direct else {}
         info.adj_err_est = float(res.est[:B].max())
+        info.adj_resid_single_updates = res.single_updates
         return res
 
     def _grad_kappa(self, lam):

@@ -180,7 +180,8 @@ int diffhe_ell_spmv_shared(const double* vals, const int* cols, const double* x,
  * its autograd backward.  x is the output (initial guess 0).
  *   vals     (W, n, Bv), Bv = Bp or 1 (matrix shared by the batch)
  *   work     diffhe_cg_workspace_doubles(n, Bp) doubles
- *   status_host  pinned host int[4]: [0] iterations run, [1] samples not converged, [2] scratch
+ *   status_host  pinned host int[4]: [0] iterations run, [1] samples not converged, [2] scratch,
+ *            [3] scratch inside diffhe_lattice_pcg_solve, which leaves a count there (see it); untouched by the others
  *   relres   (Bp) out: true relative residual |b - A x| / |b| per sample
  *   iters    (Bp) out: iterations each sample was active
  */
@@ -282,7 +283,8 @@ typedef struct diffhe_mg_level {
 } diffhe_mg_level;
 
 /* Option bits of `flags` (diffhe_lattice_pcg_solve; diffhe_ell_amg_pcg_solve reads FP32 and NO_FLOOR of the same word).
- * x, Ap and every dot product are fp64 whatever the bits, r is fp64 or an fp32 pair worth 48 bits (DIFFHE_PCG_RESID_FP64);
+ * x, Ap and every dot product are fp64 whatever the bits, r is fp64 or an fp32 pair worth 48 bits (DIFFHE_PCG_RESID_FP64)
+ * whose low half is dropped near the end of an energy-rule solve (DIFFHE_PCG_RESID_KEEP_LO);
  * bench.py records the word as solver_flags. */
 #define DIFFHE_PCG_FP32 1              /* V-cycle and CG search directions stored in fp32 (arithmetic fp64 in registers) */
 #define DIFFHE_PCG_FMG 2               /* start from a full-multigrid iterate instead of 0 */
@@ -295,6 +297,12 @@ typedef struct diffhe_mg_level {
 #define DIFFHE_PCG_PRE2 512            /* fused PRE pass at two samples per lane (default: four where the batch allows) */
 #define DIFFHE_PCG_RESID_FP64 (1 << 10) /* keep the CG residual as one fp64 vector + its fp32 copy where the default carries it
                                           as a pair of fp32 vectors (see diffhe_lattice_recompute_ap); A/B runs, tests */
+#define DIFFHE_PCG_RESID_KEEP_LO (1 << 11) /* keep BOTH halves of that pair to the end of the solve; default: once every active
+                                          sample's energy estimate is within 2^16 of the level the energy rule stops at, the
+                                          residual update stops writing (then reading) the low half -- 16, then 12 instead of
+                                          20 B per node and sample (status_host[3]); A/B runs, tests */
+#define DIFFHE_PCG_TRUST_ITS_SHIFT (12) /* four bits, development and tests only: k > 0 trusts the energy rule for k iterations
+                                          instead of the 10 (+ 1 per decade of tol_energy below 1e-11) of the default, 0 */
 
 /* Batched CG preconditioned by one multigrid V(nu,nu) cycle (weighted Jacobi with the
  * per-sweep damping factors omegas_host[0..nu-1] -- Chebyshev weights; post-smoothing runs
@@ -317,7 +325,8 @@ typedef struct diffhe_mg_level {
  *            0 neither (iteration cap reached, or the direct dense path where nothing iterates)
  *   b, x     (n, Bp) right-hand side / solution (x is read only with DIFFHE_PCG_WARM; otherwise the start is 0 / FMG(b))
  *   work     diffhe_lattice_pcg_workspace_doubles(...) doubles
- *   relres, iters, status_host: as diffhe_ell_cg_solve */
+ *   relres, iters, status_host: as diffhe_ell_cg_solve; status_host[3] = the residual updates of this solve that wrote no
+ *            low half (forms F_RDROP / F_RSINGLE of csrc/lattice.h; 0 wherever the pair is not carried or is kept whole) */
 long long diffhe_lattice_pcg_workspace_doubles(const diffhe_mg_level* levels, int n_levels, int Bp);
 int diffhe_lattice_pcg_solve(const diffhe_mg_level* levels, int n_levels, int Bv, const double* scale,
                              const double* b, double* x, int Bp, double tol, double tol_energy, int max_iter, int nu,
@@ -347,7 +356,9 @@ int diffhe_lattice_fused_passes(void);
  * the stored p (kernel-profile id 1).  On that path the residual is carried as the unevaluated sum of two fp32 vectors,
  * rs r = hi + lo with hi = (float)(rs r) the vector the V-cycle reads and rs the per-sample power of two of the fp32
  * copies: 48 bits (2^-48 relative per update), 20 B per node and sample (p read; hi, lo read and written) instead of the
- * 24 B of an fp64 r with its fp32 copy, which DIFFHE_PCG_RESID_FP64 keeps.  Always 1 since the development
+ * 24 B of an fp64 r with its fp32 copy, which DIFFHE_PCG_RESID_FP64 keeps.  Where the energy rule is in force the low half
+ * is dropped once every active sample is within 2^16 of its stop level: one update of 16 B, then 12 B (hi alone;
+ * DIFFHE_PCG_RESID_KEEP_LO keeps the 20 B form).  Always 1 since the development
  * switches were retired; fp64 directions, per-sample matrices and the unfused loop still write A p (20 B) and read it
  * back in pcg_update_kernel (28 B). */
 int diffhe_lattice_recompute_ap(void);

@@ -22,8 +22,9 @@ def main():
             grid = "x".join(str(r.get(k, "?")) for k in ("Grid_Size_X", "Grid_Size_Y"))
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"]) + " [" + grid + "]"))
     rows.sort()
-    marks = [i for i, r in enumerate(rows) if "pcg_update_kernel" in r[2] or "double, float, double, 0, 5," in r[2]
-             or "double, float, double, 0, 6," in r[2]]   # the residual update: fp64 r (F_RUPD) or the fp32 pair (F_RPAIR)
+    # the residual update: fp64 r (F_RUPD, 5), the fp32 pair (F_RPAIR, 6), its forms without a low half (F_RDROP 7, F_RSINGLE 8)
+    marks = [i for i, r in enumerate(rows) if "pcg_update_kernel" in r[2]
+             or any(f"double, float, double, 0, {k}," in r[2] for k in (5, 6, 7, 8))]
     # steps: pcg_update launches come in bursts of (fwd its + adj its); split bursts by gaps > 20 ms
     starts = [marks[0]]
     for a, b in zip(marks, marks[1:]):
