@@ -11,7 +11,7 @@
 // sym_c(a (x) b) = a_i b_i on a diagonal component and a_i b_j + a_j b_i on an off-diagonal one.  Both read the
 // gradient-form element table (g_p as (npe*d, m), |e| as (m)) instead of nc tables of npe^2 entries.
 //
-// Data layout as in ell.hip: node-major, batch innermost; lanes run over samples, so table entries and list indices are
+// Data layout as in ell.h: node-major, batch innermost; lanes run over samples, so table entries and list indices are
 // wave-uniform and every tensor / nodal load is one contiguous segment.  The tensor is read through three strides
 // (component, element, sample) and the gradient written through two (component, element; sample stride 1), so the
 // batch-innermost layouts (nc, m, Bv) and (m, nc, Bv) and the batch-shared (m, nc) and (nc) all go through one kernel.
@@ -24,7 +24,7 @@ using namespace diffhe;
 typedef long long i64;
 
 // ---------------------------------------------------------------------------------------
-// Gradient table: the cofactor arithmetic and the degenerate-element rules of tri_integrals / tet_integrals (ell.hip).
+// Gradient table: the cofactor arithmetic and the degenerate-element rules of tri_integrals / tet_integrals (ell_assemble.hip).
 // A degenerate element gets zero gradients and zero size: it contributes nothing.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void aniso_table_kernel(const double* __restrict__ coords, const int* __restrict__ elems,
@@ -97,7 +97,7 @@ __device__ __forceinline__ void sym_products(const double* a, const double* b, d
 
 // ---------------------------------------------------------------------------------------
 // Deterministic row-gather assembly over the plan's ent_ptr / contrib / cols lists, with the Dirichlet handling of
-// assemble_rows_kernel (ell.hip): identity rows, lift = sum K[free, bc] g, couplings to Dirichlet columns zeroed.
+// assemble_rows_kernel (ell_assemble.hip): identity rows, lift = sum K[free, bc] g, couplings to Dirichlet columns zeroed.
 // The pattern must hold EVERY coupling of the connectivity (a tensor fills the entries a scalar kappa leaves exactly
 // zero on axis-aligned tetrahedra: diffhe/plan.py keeps an unpruned plan for tensor solves).
 // ---------------------------------------------------------------------------------------
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(256) void aniso_sum_partials_kernel(const double* _
 
 // ---------------------------------------------------------------------------------------
 // The same gradient SUMMED OVER THE BATCH, dk (c, e) at c*osc + e*ose: one wave per element at a time, its lanes walk
-// the samples b < B in a fixed order and meet in a fixed-order wave reduction (grad_kappa_shared_kernel of ell.hip).
+// the samples b < B in a fixed order and meet in a fixed-order wave reduction (grad_kappa_shared_kernel of ell_assemble.hip).
 // ---------------------------------------------------------------------------------------
 template <int DIM>
 __global__ __launch_bounds__(256) void aniso_grad_shared_kernel(const int* __restrict__ elems,

@@ -37,6 +37,17 @@ DIFFHE_HD inline double pair_update(float& hi, float& lo, double t) {
   return (double)hi;
 }
 
+constexpr int kWave = 64;
+
+// grid.x of node_grid below: blocks of 4 waves over the nodes, each wave holding kWave / min(Bp, kWave) nodes
+inline int node_blocks(int n, int Bp, int max_blocks_x = 2048) {
+  const int LB = Bp < kWave ? Bp : kWave;
+  const int npw = kWave / LB;
+  long long groups = ((long long)n + 4 * npw - 1) / (4 * npw);
+  int gx = (int)(groups < max_blocks_x ? groups : max_blocks_x);
+  return gx < 1 ? 1 : gx;
+}
+
 }  // namespace diffhe
 
 #if defined(__HIPCC__)
@@ -45,8 +56,6 @@ DIFFHE_HD inline double pair_update(float& hi, float& lo, double t) {
 #include "diffhe_hip.h"
 
 namespace diffhe {
-
-constexpr int kWave = 64;
 
 void set_last_error(hipError_t e);
 
@@ -116,14 +125,16 @@ __device__ inline double block_sum_per_sample(double v, int Bp, double* lds /* >
   return s;
 }
 
+// The epilogue of a kernel that leaves one partial sum per block and sample: row blockIdx.x of `part` gets the block's sum
+// of `s` for sample b (ok: this lane holds a sample).  Every thread of the block must call it (two barriers inside).
+__device__ inline void store_block_partial(double s, double* __restrict__ part, int Bp, int b, bool ok, double* lds) {
+  const double t = block_sum_per_sample(s, Bp, lds);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave == 0 && lane < (Bp < kWave ? Bp : kWave) && ok) part[(long long)blockIdx.x * Bp + b] = t;
+}
+
 inline dim3 node_grid(int n, int Bp, int max_blocks_x = 2048) {
-  const int LB = Bp < kWave ? Bp : kWave;
-  const int npw = kWave / LB;
-  long long groups = ((long long)n + 4 * npw - 1) / (4 * npw);
-  int gx = (int)(groups < max_blocks_x ? groups : max_blocks_x);
-  if (gx < 1) gx = 1;
-  int gy = (Bp + kWave - 1) / kWave;
-  return dim3(gx, gy, 1);
+  return dim3(node_blocks(n, Bp, max_blocks_x), (Bp + kWave - 1) / kWave, 1);
 }
 
 }  // namespace diffhe

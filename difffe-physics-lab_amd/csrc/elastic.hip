@@ -7,7 +7,7 @@
 //
 // Both read the gradient table of aniso.hip (g_p as (npe*d, m), |e| as (m)).  The operator is stored as ELL rows over
 // the n*d dofs in the pattern include/diffhe_elastic.h describes (a node's own d x d block rotated so that slot 0 is the
-// diagonal, then d slots per neighbouring node); the solves run on it through the generic entries of ell.hip.
+// diagonal, then d slots per neighbouring node); the solves run on it through the generic entries of ell_pcg.hip / ell_amg.hip.
 //
 // Data layout as in aniso.hip: dof-major, batch innermost.  With one matrix per sample (Bv = Bp) lanes run over samples,
 // so table entries and list indices are wave-uniform and every store is one contiguous segment; with one matrix for the
@@ -23,7 +23,7 @@ typedef long long i64;
 
 // ---------------------------------------------------------------------------------------
 // Block row-gather assembly: one lane owns node i of sample b, walks the node's W slots and builds the d x d block of
-// each from the node-level contribution lists (assemble_rows_kernel of ell.hip, aniso_assemble_rows_kernel), then
+// each from the node-level contribution lists (assemble_rows_kernel of ell_assemble.hip, aniso_assemble_rows_kernel), then
 // writes its d rows with the per-dof Dirichlet handling: identity rows, zeroed columns, lift.
 // ---------------------------------------------------------------------------------------
 template <int DIM>
@@ -181,9 +181,7 @@ __global__ __launch_bounds__(256) void elast_grad_kernel(const int* __restrict__
       s += d;
     }
   if (!de_part) return;   // kernel argument: the whole block leaves together
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double r = block_sum_per_sample(s, Bp, lds);
-  if (wave == 0 && lane < (Bp < kWave ? Bp : kWave) && ok) de_part[(i64)blockIdx.x * Bp + nm.b] = r;
+  store_block_partial(s, de_part, Bp, nm.b, ok, lds);
 }
 
 // Second stage: out[b] = sum over the blocks of part[k, b], b < Bp, in a fixed order.
@@ -244,7 +242,7 @@ extern "C" int diffhe_elast_assemble_rows(const double* gtab, const double* vol,
   if ((is_bc == nullptr) != (g == nullptr)) return DIFFHE_E_BADARG;
   if (e_se < 0 || e_sb < 0 || (Bv == 1 && e_sb != 0)) return DIFFHE_E_BADARG;
   if (!diffhe::valid_batch_pad(Bv)) return DIFFHE_E_BATCHPAD;
-  if ((long long)n * dim > 2147483647LL / ((long long)dim * W)) return DIFFHE_E_TOOBIG;   // dof entries index as int32 in ell.hip
+  if ((long long)n * dim > 2147483647LL / ((long long)dim * W)) return DIFFHE_E_TOOBIG;   // dof entries index as int32 in the ell_* units
   // values, lift, the field
   diffhe::account(8.0 * Bv * ((double)dim * dim * W * n + (lift ? (double)dim * n : 0) + (e_se ? (double)m : 0)));
   const dim3 grid = diffhe::node_grid(n, Bv);

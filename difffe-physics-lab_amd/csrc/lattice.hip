@@ -2,7 +2,7 @@
 // node positions may be arbitrary).  The assembled operator is a 7-point stencil, stored as
 // SYMMETRIC DIAGONALS (DIA-sym): D0[i] = K[i,i], D1[i] = K[i,i+1], D2[i] = K[i,i+W] (W = nx+1),
 // D3[i] = K[i,i+nx] (the quad diagonal b-d; dropped when all triangles are right-angled, where
-// it is exactly 0).  No column indices at all; batch-innermost (n, Bp) vectors as in ell.hip.
+// it is exactly 0).  No column indices at all; batch-innermost (n, Bp) vectors as in ell.h.
 //
 // Solver: batched CG preconditioned by one geometric-multigrid V-cycle (P1 interpolation on the
 // nested triangulations, R = P^T, re-discretised coarse operators = Galerkin for nested P1,

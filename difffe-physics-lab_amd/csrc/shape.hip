@@ -5,7 +5,7 @@
 //   g_i += A_e [ (q_e - tr T_e) I + T_e + T_e^T ] grad phi_i,
 //   T_e = sum_b kappa_eb grad u_eb (x) grad lambda_eb,
 //   q_e = sum_b [ load_eb - c sum_p lambda_pb u_pb / (d+1) ],
-//   load_eb = (sum_p lambda_pb)(sum_p f_pb) / (d+1)^2     (2D, 3D: F_p = A_e/(d+1) * mean f, the m0 of ell.hip)
+//   load_eb = (sum_p lambda_pb)(sum_p f_pb) / (d+1)^2     (2D, 3D: F_p = A_e/(d+1) * mean f, the m0 of ell_assemble.hip)
 //           = sum_p lambda_pb f_pb / 2                     (1D: the reference's trapezoid F_i = h/2 f_i).
 //
 // Two passes, no floating-point atomics (bitwise reproducible):
@@ -22,7 +22,7 @@ using namespace diffhe;
 typedef long long i64;
 
 // grad phi_p (G[p][k]) and the element size of a P1 simplex; false for a degenerate element, with the thresholds of the
-// assembly (ell.hip: tri_integrals area < 1e-15, tet_integrals |det| <= 1e-12 l^3; a zero-length segment in 1D).
+// assembly (ell_assemble.hip: tri_integrals area < 1e-15, tet_integrals |det| <= 1e-12 l^3; a zero-length segment in 1D).
 template <int D>
 __device__ inline bool simplex_geometry(const double* __restrict__ coords, int n, const int* v, double (*G)[D],
                                         double* size) {

@@ -317,7 +317,7 @@ def reference_order_integrals(coords: np.ndarray, elems: np.ndarray):
     3D (P1 tetrahedra, ours -- the reference has no 3D operator): t[pq] = g_p . g_q with the cofactor vectors
     g_1 = b x c, g_2 = c x a, g_3 = a x b, g_0 = -((g_1 + g_2) + g_3) of the edge vectors a, b, c from vertex 0, the dot
     product summed x + y + z left to right; den = 6 |det| = 36 V, det = a . g_1; degenerate (|det| <= 1e-12 l^3, l the
-    longest of a, b, c) -> t = 0, den = 1.  The same operations in the same order as tet_integrals (csrc/ell.hip)."""
+    longest of a, b, c) -> t = 0, den = 1.  The same operations in the same order as tet_integrals (csrc/ell_assemble.hip)."""
     dim = coords.shape[0]
     e = elems.astype(np.int64)
     if dim == 1:

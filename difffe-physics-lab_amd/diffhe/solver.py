@@ -1449,7 +1449,7 @@ def _fe_solve_backward_fake(gbar, token, need_k, need_f, need_load, need_g, need
 def _element_forms(plan: SolvePlan):
     """Unit-kappa element stiffness and load matrices (m, npe, npe) and the (m, npe) connectivity, as torch tensors
     built from the plan's coordinates -- the differentiable restatement of reference solver.py:86-96 (1D) and :125-145
-    (2D P1), and of the P1 tetrahedra of csrc/ell.hip (3D), used by the second-order path only."""
+    (2D P1), and of the P1 tetrahedra of csrc/ell_assemble.hip (3D), used by the second-order path only."""
     cached = plan.__dict__.get("_element_forms")
     if cached is not None:
         return cached
@@ -1468,7 +1468,7 @@ def _element_forms(plan: SolvePlan):
         G = torch.stack([-(g1 + g2 + g3), g1, g2, g3], 1)            # (m, 4, 3): 6 V grad phi_p
         det = (a * g1).sum(1)
         l2 = torch.maximum(torch.maximum((a * a).sum(1), (b * b).sum(1)), (c * c).sum(1))
-        keep = det.abs() > 1e-12 * (l2 * l2.sqrt())                  # degenerate tetrahedra: nothing, as in ell.hip
+        keep = det.abs() > 1e-12 * (l2 * l2.sqrt())                  # degenerate tetrahedra: nothing, as in ell_assemble.hip
         safe = torch.where(keep, det.abs(), torch.ones_like(det))
         zero = torch.zeros((), dtype=torch.float64, device=det.device)
         k0 = torch.where(keep[:, None, None], G @ G.transpose(1, 2) / (6.0 * safe)[:, None, None], zero)
@@ -1479,7 +1479,7 @@ def _element_forms(plan: SolvePlan):
         c = torch.stack([x[:, 2] - x[:, 1], x[:, 0] - x[:, 2], x[:, 1] - x[:, 0]], 1)
         area = 0.5 * ((x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (x[:, 2] - x[:, 0]) * (y[:, 1] - y[:, 0])).abs()
         # degenerate triangles are skipped silently, as in the reference (solver.py:120-121), the first-order kernels
-        # (ell.hip) and plan.py: no contribution to K or F instead of a division by ~0
+        # (ell_assemble.hip) and plan.py: no contribution to K or F instead of a division by ~0
         keep = (area >= 1e-15)[:, None, None]
         safe = torch.where(area >= 1e-15, area, torch.ones_like(area))
         k0 = torch.where(keep, (b[:, :, None] * b[:, None, :] + c[:, :, None] * c[:, None, :]) / (4.0 * safe)[:, None, None],

@@ -4,7 +4,7 @@
 `forward(f, load=None, layout=...)`, options, kappa layouts and gradients; on 1D and 2D meshes it behaves exactly like
 the base class, which stays the faithful mirror of the reference (it keeps refusing 3D meshes).  A 3D mesh -- P1
 tetrahedra, `FEMesh.box` or any (n, 3) nodes with (m, 4) elements -- takes the general path: the element integrals of
-`tet_integrals` (csrc/ell.hip), the deterministic gather assembly into an ELL pattern from which structurally zero
+`tet_integrals` (csrc/ell_assemble.hip), the deterministic gather assembly into an ELL pattern from which structurally zero
 couplings are pruned (diffhe/plan.py), and the aggregation-multigrid PCG with its explicit adjoint.
 
 Element convention (the reference has none to copy in 3D): stiffness k_pq = kappa g_p . g_q / (36 V) with the cofactor
