@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void cg_scalar_kernel(int phase, const double*
     }
   } else if (phase == PH_XX) {  // a = x.x
     S.xx[b] = a;
-  } else if (phase == PH_SCALE) {  // a = b.b: power of two rs with rs |b| in [1, 2) (see pcg_cvt_kernel in lattice.hip)
+  } else if (phase == PH_SCALE) {  // a = b.b: power of two rs with rs |b| in [1, 2) (see pcg_cvt_kernel in lattice_pcg.hip)
     S.rs[b] = a > 0.0 ? ldexp(1.0, -ilogb(sqrt(a))) : 1.0;
   } else {  // PH_RELRES: a = |b - A x|^2
     relres[b] = S.bb[b] > 0.0 ? sqrt(a / S.bb[b]) : 0.0;

@@ -1,15 +1,15 @@
 // Internal header of the lattice fast path: what its units share -- level and fusion types, constants, the device
 // helpers more than one kernel family uses, the predicates and tile geometry of the dispatch, and the declarations of
-// the launchers each unit defines.
+// the launchers each unit defines.  The workspace layout of the solve is lattice_layout.h's.
 #pragma once
 #include "common.h"
+#include "lattice_layout.h"
 
 // One internal namespace for all lattice units; nothing in it is exported from the library.  Kernels sit in an
 // anonymous namespace inside their unit.
 namespace diffhe_lattice __attribute__((visibility("hidden"))) {
 
 using namespace diffhe;
-typedef long long i64;
 
 struct Level {
   int nx, ny, n, W, nd;
@@ -140,7 +140,6 @@ template <typename TV>
 constexpr int strip_cols() { return sizeof(TV) == 4 ? 4 : kStripCols; }
 constexpr int kRestrictCols = 2;  // coarse columns per wave of the fused residual + restriction (5 fine columns; 3, 4, 6: slower)
 constexpr int kPupdCols = 4;  // narrower strips for the 3-stream fused CG kernel: fewer VGPRs, more waves
-constexpr int kPartBlocks = 2048;  // capacity (in blocks) of every partial-sum buffer
 // blocks (of 4 waves) a strip-kernel launch aims at; the tile height follows from it
 constexpr int kStripBlocks = 6144;
 // small levels: one wave marching down a strip is latency-bound; the simple kernels win below ~200^2
@@ -457,5 +456,59 @@ void launch_fused_pre(const Level& L, const Level& C, int Bv, const double* scal
 void launch_fused_post(const Level& L, const Level& C, int Bv, const double* scale, const float* xin, const float* rhs,
                        const float* ec, float* z, double wA, double wB, double* part, int Bp, const StripGeom& g, int spl,
                        hipStream_t st);
+
+// ---- host-side hierarchy (lattice_cycle.hip) ----------------------------------------------------------------------------
+struct Hier : CycleWork {   // + the per-level work vectors (cycle_carve)
+  Level lev[kMaxLevels];
+  int nl, Bv, Bp;
+  const double* scale;
+  double omega[8];  // per-sweep damping (Chebyshev-weighted Jacobi); post-smoothing runs them in reverse
+  int nu, n_coarse, fmg_coarse_cycles;
+  int fuse;  // 0: four single-stage strip passes per level; 1 / 2: fused two-stage passes, samples per lane
+  int pre4;  // the fused PRE pass may take four samples per lane (fused_spl)
+  int dense_mfma;  // coarsest-level dense solve of an fp32 cycle on the matrix cores (0: scalar-load kernel)
+  double coarse_lmax;  // upper bound of the spectrum of D^-1 A on the coarsest level (2 for an M-matrix)
+};
+
+// bpn = algorithmic bytes per (node, sample) of the launch, for diffhe_traffic_account.  The kernel's arguments are
+// passed in full (a kernel's default arguments do not travel through a function pointer).
+template <typename K, typename... Args>
+inline void launch_nodes(const Hier& H, hipStream_t st, double bpn, K kernel, int n, Args... args) {
+  diffhe::account(bpn * (double)n * H.Bp);
+  hipLaunchKernelGGL(kernel, lgrid(n, H.Bp), dim3(256), 0, st, args...);
+}
+// per-sample matrices: bytes of the nd stored diagonals (fp64) per node; a batch-shared matrix is amortised to 0
+inline double mat_bytes(const Hier& H, const Level& L) { return H.Bv == 1 ? 0.0 : 8.0 * L.nd; }
+
+int fill_hier(Hier& H, const diffhe_mg_level* levels, int n_levels, int Bv, int Bp, const double* scale,
+              const double* omegas, int nu, int n_coarse);
+// the one-level hierarchy of the entries that run a single kernel family on one level (apply, bilinear, cg_step; smooth
+// sets its own weight afterwards)
+int single_level(Hier& H, const diffhe_mg_level* level, int Bv, int Bp, const double* scale);
+i64 carve_cycle(Hier& H, double* work, bool fp32);   // cycle_carve over H's levels
+
+// What the driver (lattice_pcg.hip) asks of the cycle unit.  fp32 = storage type of the cycle's vectors; the branch on it
+// is taken once, inside.  Those that leave partial sums return the number of partial blocks they wrote.
+// z = V(r): the buffer holding z; the last fine sweep leaves the partials of r.z in `part` (*nblocks of them)
+const void* cycle_precondition(const Hier& H, bool fp32, const void* r, double* part, int* nblocks, hipStream_t st);
+// full-multigrid start from the right-hand side b0: the iterate (NULL: error recorded), *pending = the fine level's last
+// correction, not yet added (may come back NULL)
+const void* cycle_fmg_start(const Hier& H, bool fp32, const void* b0, hipStream_t st, const void** pending);
+// level 0, fp64: res = rhs - A x (res may be NULL), partials of r.r -- or, dot_bx, of b.x and (part2) x.(A x)
+int cycle_residual(const Hier& H, const double* rhs, const double* x, double* res, double* part, hipStream_t st,
+                   int dot_bx = 0, double* part2 = nullptr);
+int cycle_apply_dot(const Hier& H, const double* x, double* y, double* part, hipStream_t st);   // level 0: y = A x, x.y
+bool direct_ok(const Hier& H, bool fp32);   // one level with the dense inverse of its batch-shared matrix, fp64
+void cycle_direct_solve(const Hier& H, const double* b, double* x, hipStream_t st);   // x = (1 / s_b) K_1^{-1} b
+int cycle_maxdiag(const Hier& H, double* out /* Bv */, hipStream_t st);   // per-sample max diagonal of level 0
+// spectrum bound for the coarsest-level Chebyshev solve (H.coarse_lmax): 2 unless the mesh has obtuse triangles, where
+// the Gershgorin bound is taken on the device (`scratch`: one word) and read back (synchronises the stream)
+int cycle_coarse_bound(Hier& H, unsigned long long* scratch, hipStream_t st);
+
+// ---- opt-in timing of the step's main kernels INSIDE the solver loop (bench.py's roofline entries; lattice_pcg.hip) -------
+enum { KP_CGSTEP = 0, KP_UPDATE = 1, KP_FIRST2 = 2, KP_RESTRICT = 3, KP_PROLONG = 4, KP_SWEEP = 5, KP_COUNT = 6 };
+void kp_begin(int id, hipStream_t st);
+void kp_end(int id, hipStream_t st);
+void kp_collect();  // call with the stream idle: every recorded event has completed
 
 }  // namespace diffhe_lattice

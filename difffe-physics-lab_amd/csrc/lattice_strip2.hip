@@ -419,8 +419,8 @@ void launch_strip2(const Level& L, const double* scale, const float* xin, const 
 #undef STRIP2
 }
 
-// Every launch_strip2 the driver (lattice.hip) calls, once: with cgstep2_kernel the kernel inventory of this unit.  Each
-// line instantiates the kernels for 3 and 4 diagonals (M_JACOBI: with and without the partials of rhs . x).
+// Every launch_strip2 the cycle (lattice_cycle.hip) calls, once: with cgstep2_kernel (the driver's, lattice_pcg.hip) the
+// kernel inventory of this unit.  Each line instantiates the kernels for 3 and 4 diagonals (M_JACOBI: with and without the partials of rhs . x).
 #define INST(...)                                                                                                      \
   template void launch_strip2<__VA_ARGS__>(const Level&, const double*, const float*, const float*, float*, double, double, \
                                            double*, int, const StripGeom&, hipStream_t, const Extra&)

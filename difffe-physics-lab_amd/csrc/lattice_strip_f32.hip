@@ -3,7 +3,8 @@
 
 namespace diffhe_lattice __attribute__((visibility("hidden"))) {
 
-// Every launch_strip of this vector type the driver and the ABI entries (lattice.hip, lattice_abi.hip) call, once:
+// Every launch_strip of this vector type the cycle, the driver and the ABI entries (lattice_cycle.hip, lattice_pcg.hip,
+// lattice_abi.hip) call, once:
 // the kernel inventory of this unit (lattice_strip_f64.hip has the other type).  Each line instantiates the batch-shared,
 // shifted and per-sample coefficient variants for 3 and 4 diagonals that its MATS admits.
 #define INST(TV_, ...)                                                                                              \
