@@ -16,7 +16,11 @@
 // (component, element, sample) and the gradient written through two (component, element; sample stride 1), so the
 // batch-innermost layouts (nc, m, Bv) and (m, nc, Bv) and the batch-shared (m, nc) and (nc) all go through one kernel.
 // No floating-point atomics anywhere: every sum has a fixed order and the results are bitwise reproducible.
+//
+// The gradient's element loop, its two-stage per-sample total and its batch reduction are the kernels of element_grad.h;
+// this unit holds their form, AnisoForm<DIM>, next to the table and the assembly.
 #include "common.h"
+#include "element_grad.h"
 
 namespace {
 
@@ -146,132 +150,55 @@ __global__ __launch_bounds__(256) void aniso_assemble_rows_kernel(
   }
 }
 
-// grad lambda and grad u of element e for the sample of this lane, then the NC products -|e| sym_c(grad lambda (x) grad u)
+// ---------------------------------------------------------------------------------------
+// dL/dK: the form of element_grad.h.  Per element the nodes, their Dirichlet values (0 without data), the gradients g_p
+// and |e|; per sample grad lambda and grad u, then the NC products -|e| sym_c(grad lambda (x) grad u).
+// ---------------------------------------------------------------------------------------
 template <int DIM>
-__device__ __forceinline__ void element_grad(const int* node, const double (*G)[DIM], double ve, const double* gq,
-                                             const double* __restrict__ lam, const double* __restrict__ u, int Bp, int b,
-                                             double* dk) {
-  constexpr int NPE = DIM + 1;
-  double gl[DIM], gu[DIM];
+struct AnisoForm {
+  static constexpr int NPE = DIM + 1, NC = DIM * (DIM + 1) / 2;
+  const int* __restrict__ elems;
+  const double* __restrict__ gtab;
+  const double* __restrict__ vol;
+  const double* __restrict__ lam;
+  const double* __restrict__ u;
+  const double* __restrict__ g;
+  int m;
+
+  struct Elem {
+    int node[NPE];
+    double G[NPE][DIM], gq[NPE], ve;
+  };
+
+  __device__ __forceinline__ void load(int e, Elem& el) const {
 #pragma unroll
-  for (int d = 0; d < DIM; ++d) gl[d] = gu[d] = 0.0;
+    for (int p = 0; p < NPE; ++p) {
+      el.node[p] = elems[(i64)p * m + e];
+      el.gq[p] = g ? g[el.node[p]] : 0.0;
 #pragma unroll
-  for (int p = 0; p < NPE; ++p) {
-    const i64 o = (i64)node[p] * Bp + b;
-    const double lp = lam[o];
-    const double up = u[o] + gq[p];   // full u: Dirichlet values included, as grad_kappa_kernel adds them
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-      gl[d] = fma(lp, G[p][d], gl[d]);
-      gu[d] = fma(up, G[p][d], gu[d]);
+      for (int d = 0; d < DIM; ++d) el.G[p][d] = gtab[(i64)(p * DIM + d) * m + e];
     }
+    el.ve = vol[e];
   }
-  sym_products<DIM>(gl, gu, -ve, dk);
-}
 
-template <int DIM>
-__device__ __forceinline__ void load_element(const int* __restrict__ elems, const double* __restrict__ gtab,
-                                             const double* __restrict__ g, int m, int e, int* node, double (*G)[DIM],
-                                             double* gq) {
-  constexpr int NPE = DIM + 1;
+  __device__ __forceinline__ void eval(const Elem& el, int Bp, int b, double* dk) const {
+    double gl[DIM], gu[DIM];
 #pragma unroll
-  for (int p = 0; p < NPE; ++p) {
-    node[p] = elems[(i64)p * m + e];
-    gq[p] = g ? g[node[p]] : 0.0;
+    for (int d = 0; d < DIM; ++d) gl[d] = gu[d] = 0.0;
 #pragma unroll
-    for (int d = 0; d < DIM; ++d) G[p][d] = gtab[(i64)(p * DIM + d) * m + e];
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// dL/dK per element and sample, dk_e (c, e, b) at c*osc + e*ose + b (optional), and its block partial sums over the
-// elements per sample, dk_part (nblk, NC, Bp) (optional): first stage of the per-sample total.
-// ---------------------------------------------------------------------------------------
-template <int DIM>
-__global__ __launch_bounds__(256) void aniso_grad_kernel(const int* __restrict__ elems, const double* __restrict__ gtab,
-                                                          const double* __restrict__ vol, const double* __restrict__ lam,
-                                                          const double* __restrict__ u, const double* __restrict__ g,
-                                                          int m, int Bp, double* __restrict__ dk_e, i64 osc, i64 ose,
-                                                          double* __restrict__ dk_part) {
-  constexpr int NPE = DIM + 1, NC = DIM * (DIM + 1) / 2;
-  __shared__ double lds[4 * kWave];
-  const NodeMap nm = node_map(Bp);  // "nodes" are elements here
-  const bool ok = nm.b < Bp;
-  double s[NC];
+    for (int p = 0; p < NPE; ++p) {
+      const i64 o = (i64)el.node[p] * Bp + b;
+      const double lp = lam[o];
+      const double up = u[o] + el.gq[p];   // full u: Dirichlet values included, as KappaForm adds them
 #pragma unroll
-  for (int t = 0; t < NC; ++t) s[t] = 0.0;
-  if (ok)
-    for (int e = nm.node0; e < m; e += nm.stride) {
-      int node[NPE];
-      double G[NPE][DIM], gq[NPE], dk[NC];
-      load_element<DIM>(elems, gtab, g, m, e, node, G, gq);
-      element_grad<DIM>(node, G, vol[e], gq, lam, u, Bp, nm.b, dk);
-#pragma unroll
-      for (int t = 0; t < NC; ++t) {
-        if (dk_e) dk_e[(i64)t * osc + (i64)e * ose + nm.b] = dk[t];
-        s[t] += dk[t];
+      for (int d = 0; d < DIM; ++d) {
+        gl[d] = fma(lp, el.G[p][d], gl[d]);
+        gu[d] = fma(up, el.G[p][d], gu[d]);
       }
     }
-  if (!dk_part) return;   // kernel argument: the whole block leaves together
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < NC; ++t) {
-    const double r = block_sum_per_sample(s[t], Bp, lds);
-    if (wave == 0 && lane < (Bp < kWave ? Bp : kWave) && ok) dk_part[((i64)blockIdx.x * NC + t) * Bp + nm.b] = r;
+    sym_products<DIM>(gl, gu, -el.ve, dk);
   }
-}
-
-// Second stage: out[j] = sum over the blocks of part[k, j], j < width (= NC * Bp), in a fixed order.
-__global__ __launch_bounds__(256) void aniso_sum_partials_kernel(const double* __restrict__ part, int nblk, int width,
-                                                                  double* __restrict__ out) {
-  __shared__ double lds[4 * kWave];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int j = blockIdx.x * kWave + lane;
-  double s = 0.0;
-  if (j < width)
-    for (int k = wave; k < nblk; k += 4) s += part[(i64)k * width + j];
-  lds[wave * kWave + lane] = s;
-  __syncthreads();
-  if (wave == 0 && j < width) out[j] = (lds[lane] + lds[kWave + lane]) + (lds[2 * kWave + lane] + lds[3 * kWave + lane]);
-}
-
-// ---------------------------------------------------------------------------------------
-// The same gradient SUMMED OVER THE BATCH, dk (c, e) at c*osc + e*ose: one wave per element at a time, its lanes walk
-// the samples b < B in a fixed order and meet in a fixed-order wave reduction (grad_kappa_shared_kernel of ell_assemble.hip).
-// ---------------------------------------------------------------------------------------
-template <int DIM>
-__global__ __launch_bounds__(256) void aniso_grad_shared_kernel(const int* __restrict__ elems,
-                                                                 const double* __restrict__ gtab,
-                                                                 const double* __restrict__ vol,
-                                                                 const double* __restrict__ lam,
-                                                                 const double* __restrict__ u,
-                                                                 const double* __restrict__ g, int m, int B, int Bp,
-                                                                 double* __restrict__ dk, i64 osc, i64 ose) {
-  constexpr int NPE = DIM + 1, NC = DIM * (DIM + 1) / 2;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int e = blockIdx.x * 4 + wave; e < m; e += gridDim.x * 4) {
-    int node[NPE];
-    double G[NPE][DIM], gq[NPE], s[NC];
-    load_element<DIM>(elems, gtab, g, m, e, node, G, gq);
-    const double ve = vol[e];
-#pragma unroll
-    for (int t = 0; t < NC; ++t) s[t] = 0.0;
-    for (int b = lane; b < B; b += kWave) {   // padding samples (b >= B) carry no gradient
-      double d[NC];
-      element_grad<DIM>(node, G, ve, gq, lam, u, Bp, b, d);
-#pragma unroll
-      for (int t = 0; t < NC; ++t) s[t] += d[t];
-    }
-#pragma unroll
-    for (int t = 0; t < NC; ++t) {
-      double r = s[t];
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) r += __shfl_xor(r, d);
-      if (lane == 0) dk[(i64)t * osc + (i64)e * ose] = r;
-    }
-  }
-}
+};
 
 }  // namespace
 
@@ -314,22 +241,13 @@ extern "C" int diffhe_aniso_grad(const int* elems, const double* gtab, const dou
   if (!elems || !gtab || !vol || !lam || !u || (dim != 2 && dim != 3) || n < 1 || m < 1) return DIFFHE_E_BADARG;
   if (!dk_e && !dk_part) return DIFFHE_E_BADARG;
   if ((dk_part == nullptr) != (dk_sum == nullptr)) return DIFFHE_E_BADARG;
-  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
   const int nc = dim == 2 ? 3 : 6;
-  const dim3 grid = diffhe::node_grid(m, Bp);
-  diffhe::account(8.0 * Bp * (2.0 * n + (dk_e ? (double)nc * m : 0)));  // lambda and u once per node, dK per element
+  const double bytes = 8.0 * Bp * (2.0 * n + (dk_e ? (double)nc * m : 0));  // lambda and u once per node, dK per element
   if (dim == 2)
-    hipLaunchKernelGGL(aniso_grad_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, elems, gtab, vol, lam, u, g, m, Bp,
-                       dk_e, o_sc, o_se, dk_part);
-  else
-    hipLaunchKernelGGL(aniso_grad_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, elems, gtab, vol, lam, u, g, m, Bp,
-                       dk_e, o_sc, o_se, dk_part);
-  if (dk_part) {
-    const int width = nc * Bp;
-    hipLaunchKernelGGL(aniso_sum_partials_kernel, dim3((width + 63) / 64), dim3(256), 0, (hipStream_t)stream,
-                       (const double*)dk_part, (int)grid.x, width, dk_sum);
-  }
-  return diffhe::check_launch();
+    return diffhe::launch_element_grad(AnisoForm<2>{elems, gtab, vol, lam, u, g, m}, m, Bp, dk_e, o_sc, o_se, dk_part,
+                                       dk_sum, bytes, stream);
+  return diffhe::launch_element_grad(AnisoForm<3>{elems, gtab, vol, lam, u, g, m}, m, Bp, dk_e, o_sc, o_se, dk_part,
+                                     dk_sum, bytes, stream);
 }
 
 extern "C" int diffhe_aniso_grad_shared(const int* elems, const double* gtab, const double* vol, int dim,
@@ -337,16 +255,11 @@ extern "C" int diffhe_aniso_grad_shared(const int* elems, const double* gtab, co
                                         double* dk, long long o_sc, long long o_se, void* stream) {
   if (!elems || !gtab || !vol || !lam || !u || !dk || (dim != 2 && dim != 3) || n < 1 || m < 1 || B < 1 || B > Bp)
     return DIFFHE_E_BADARG;
-  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
   const int nc = dim == 2 ? 3 : 6;
-  long long blocks = ((long long)m + 3) / 4;
-  if (blocks > 16384) blocks = 16384;
-  diffhe::account(8.0 * (Bp * 2.0 * n + (double)nc * m));
+  const double bytes = 8.0 * (Bp * 2.0 * n + (double)nc * m);
   if (dim == 2)
-    hipLaunchKernelGGL(aniso_grad_shared_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, elems,
-                       gtab, vol, lam, u, g, m, B, Bp, dk, o_sc, o_se);
-  else
-    hipLaunchKernelGGL(aniso_grad_shared_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, elems,
-                       gtab, vol, lam, u, g, m, B, Bp, dk, o_sc, o_se);
-  return diffhe::check_launch();
+    return diffhe::launch_element_grad_shared(AnisoForm<2>{elems, gtab, vol, lam, u, g, m}, m, B, Bp, dk, o_sc, o_se,
+                                              bytes, stream);
+  return diffhe::launch_element_grad_shared(AnisoForm<3>{elems, gtab, vol, lam, u, g, m}, m, B, Bp, dk, o_sc, o_se, bytes,
+                                            stream);
 }

@@ -13,8 +13,12 @@
 // so table entries and list indices are wave-uniform and every store is one contiguous segment; with one matrix for the
 // batch (Bv = 1) lanes run over nodes.  fp64, no atomics anywhere: every sum has a fixed order, results are bitwise
 // reproducible.
+//
+// dL/dE keeps its own two kernels: on the element loop of element_grad.h they measured slower (2D at Bp = 256, the 3D
+// batch-shared kernel at B = 64).  Only the second stage of the per-sample total is the header's.
 #include "common.h"
 #include "diffhe_elastic.h"
+#include "element_grad.h"
 
 namespace {
 
@@ -158,7 +162,7 @@ __device__ __forceinline__ double element_grad(const int* node, const double (*G
 
 // ---------------------------------------------------------------------------------------
 // dL/dE per element and sample, de_e (m, Bp) (optional), and its block partial sums over the elements per sample,
-// de_part (nblk, Bp) (optional): first stage of the per-sample total.
+// de_part (nblk, Bp) (optional): first stage of the per-sample total (second stage: element_grad.h).
 // ---------------------------------------------------------------------------------------
 template <int DIM>
 __global__ __launch_bounds__(256) void elast_grad_kernel(const int* __restrict__ elems, const double* __restrict__ gtab,
@@ -184,23 +188,9 @@ __global__ __launch_bounds__(256) void elast_grad_kernel(const int* __restrict__
   store_block_partial(s, de_part, Bp, nm.b, ok, lds);
 }
 
-// Second stage: out[b] = sum over the blocks of part[k, b], b < Bp, in a fixed order.
-__global__ __launch_bounds__(256) void elast_sum_partials_kernel(const double* __restrict__ part, int nblk, int width,
-                                                                  double* __restrict__ out) {
-  __shared__ double lds[4 * kWave];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int j = blockIdx.x * kWave + lane;
-  double s = 0.0;
-  if (j < width)
-    for (int k = wave; k < nblk; k += 4) s += part[(i64)k * width + j];
-  lds[wave * kWave + lane] = s;
-  __syncthreads();
-  if (wave == 0 && j < width) out[j] = (lds[lane] + lds[kWave + lane]) + (lds[2 * kWave + lane] + lds[3 * kWave + lane]);
-}
-
 // ---------------------------------------------------------------------------------------
 // The same gradient SUMMED OVER THE BATCH, de (m): one wave per element at a time, its lanes walk the samples b < B in a
-// fixed order and meet in a fixed-order wave reduction (aniso_grad_shared_kernel).
+// fixed order and meet in a fixed-order wave reduction (as element_grad_shared_kernel of element_grad.h).
 // ---------------------------------------------------------------------------------------
 template <int DIM>
 __global__ __launch_bounds__(256) void elast_grad_shared_kernel(const int* __restrict__ elems,
@@ -272,7 +262,7 @@ extern "C" int diffhe_elast_grad(const int* elems, const double* gtab, const dou
     hipLaunchKernelGGL(elast_grad_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, elems, gtab, vol, lam1, mu1, lam, u,
                        g, m, Bp, de_e, de_part);
   if (de_part)
-    hipLaunchKernelGGL(elast_sum_partials_kernel, dim3((Bp + 63) / 64), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(diffhe::element_sum_partials_kernel, dim3((Bp + 63) / 64), dim3(256), 0, (hipStream_t)stream,
                        (const double*)de_part, (int)grid.x, Bp, de_sum);
   return diffhe::check_launch();
 }

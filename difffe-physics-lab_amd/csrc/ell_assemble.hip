@@ -1,7 +1,9 @@
 // General path, assembly: element integrals, assembly into a batch-shared ELL pattern, Dirichlet elimination, the
-// batch-shared product, Galerkin coarse values, gradient contraction, layout changes.
+// batch-shared product, Galerkin coarse values, gradient contraction (batch-shared: KappaForm, the scalar form of element_grad.h),
+// layout changes.
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
+#include "element_grad.h"
 #include "ell.h"
 
 namespace {
@@ -423,44 +425,41 @@ __global__ __launch_bounds__(256) void grad_kappa_kernel(const int* __restrict__
   store_block_partial(s, dk_part, Bp, nm.b, ok, lds);
 }
 
-// The same contraction summed over the batch, for a kappa field SHARED by all samples (kappa (m,)):
-//   dk[e] = sum_b dk[e, b].  One wave per element at a time; its lanes walk the sample chunks in a fixed order and
-// meet in a fixed-order wave reduction, so the result is bitwise reproducible and the (m, Bp) per-sample gradient
-// (4.3 GB at 1024^2 x 256) is never written.
-__global__ __launch_bounds__(256) void grad_kappa_shared_kernel(const int* __restrict__ elems,
-                                                                 const double* __restrict__ k0,
-                                                                 const double* __restrict__ lam,
-                                                                 const double* __restrict__ u,
-                                                                 const double* __restrict__ g, int npe, int m, int B,
-                                                                 int Bp, double* __restrict__ dk) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int e = blockIdx.x * 4 + wave; e < m; e += gridDim.x * 4) {
-    int node[6];
-    double gq[6], kk[36];
+// The same contraction summed over the batch, for a kappa field SHARED by all samples (kappa (m,)): the batch-shared
+// kernel of element_grad.h with this form, dk[e, b] = -lam_e^T k0_e u_e.  npe is a runtime 2, 3, 4 or 6, so nothing indexed
+// by it is carried across the call: eval reads the element's nodes and k0 itself -- wave-uniform loads there -- and no array
+// spills to scratch.  (The per-sample kernel above stays as it is: on the header's element loop it measured 1 % slower
+// at Bp = 256.)
+struct KappaForm {
+  static constexpr int NC = 1;
+  const int* __restrict__ elems;
+  const double* __restrict__ k0;
+  const double* __restrict__ lam;
+  const double* __restrict__ u;
+  const double* __restrict__ g;
+  int npe, m;
+
+  struct Elem {
+    int e;
+  };
+
+  __device__ __forceinline__ void load(int e, Elem& el) const { el.e = e; }
+
+  __device__ __forceinline__ void eval(const Elem& el, int Bp, int b, double* dk) const {
+    const int e = el.e;
+    double le[6], ue[6];   // npe <= 6 (P2 triangles)
     for (int p = 0; p < npe; ++p) {
-      node[p] = elems[(i64)p * m + e];
-      gq[p] = g ? g[node[p]] : 0.0;
+      const int node = elems[(i64)p * m + e];
+      const i64 o = (i64)node * Bp + b;
+      le[p] = lam[o];
+      ue[p] = u[o] + (g ? g[node] : 0.0);  // full u: Dirichlet values included (Appendix A step 2)
     }
-    for (int pq = 0; pq < npe * npe; ++pq) kk[pq] = k0[(i64)pq * m + e];
-    double s = 0.0;
-    for (int b = lane; b < B; b += kWave) {   // padding samples (b >= B) carry no gradient
-      double le[6], ue[6];
-      for (int p = 0; p < npe; ++p) {
-        const i64 o = (i64)node[p] * Bp + b;
-        le[p] = lam[o];
-        ue[p] = u[o] + gq[p];
-      }
-      double acc = 0.0;
-      for (int p = 0; p < npe; ++p)
-        for (int q = 0; q < npe; ++q) acc += le[p] * kk[p * npe + q] * ue[q];
-      s -= acc;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-    if (lane == 0) dk[e] = s;
+    double acc = 0.0;
+    for (int p = 0; p < npe; ++p)
+      for (int q = 0; q < npe; ++q) acc += le[p] * k0[(i64)(p * npe + q) * m + e] * ue[q];
+    dk[0] = -acc;
   }
-}
+};
 
 __global__ __launch_bounds__(256) void sum_partials_kernel(const double* __restrict__ part, int nblk, int Bp,
                                                             double* __restrict__ out) {
@@ -685,13 +684,9 @@ extern "C" int diffhe_p1_grad_kappa(const int* elems, const double* k0, const do
 extern "C" int diffhe_p1_grad_kappa_shared(const int* elems, const double* k0, const double* lam, const double* u,
                                            const double* g, int npe, int m, int B, int Bp, double* dk, void* stream) {
   if (!elems || !k0 || !lam || !u || !dk || (npe != 2 && npe != 3 && npe != 4 && npe != 6) || m < 1 || B < 1 || B > Bp) return DIFFHE_E_BADARG;
-  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
-  long long blocks = ((long long)m + 3) / 4;
-  if (blocks > 16384) blocks = 16384;
-  diffhe::account(8.0 * (Bp * 2.0 * m * (npe == 3 ? 0.5 : 1.0) + m));  // lambda and u once per node, dk once per element
-  hipLaunchKernelGGL(grad_kappa_shared_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, elems, k0, lam, u,
-                     g, npe, m, B, Bp, dk);
-  return diffhe::check_launch();
+  // lambda and u once per node, dk once per element
+  const double bytes = 8.0 * (Bp * 2.0 * m * (npe == 3 ? 0.5 : 1.0) + m);
+  return diffhe::launch_element_grad_shared(KappaForm{elems, k0, lam, u, g, npe, m}, m, B, Bp, dk, 0, 1, bytes, stream);
 }
 
 extern "C" int diffhe_to_node_major(const double* src, long long ld, const unsigned char* zero_mask, double* dst, int n,

@@ -264,18 +264,15 @@ class _EigenRun:
         acc = None
         for i in range(k):
             lamv = self.X[i] * (-gp[i])[None, :]
-            if mode == K_ELEM:
-                part = eng.grad_kappa_shared(lamv, self.X[i], B, Bp)            # (m,), summed over the batch
-            else:
-                dk_nm, dk_sum = eng.grad_kappa(lamv, self.X[i], Bp, mode == K_SAMPLE_ELEM)
-                part = dk_nm if mode == K_SAMPLE_ELEM else dk_sum
+            sums, elem = eng.grad_kappa(lamv, self.X[i], B, Bp, mode, True)     # (B,) | (m,) | element-major (m, B)
+            part = elem if sums is None else sums
             acc = part if acc is None else acc + part
         if mode == K_SAMPLE_ELEM:
-            grad = _kappa_grad(mode, self.kappa_shape, None, eng.to_sample_major(acc, B, Bp, plan.m))
+            grad = _kappa_grad(mode, self.kappa_shape, None, acc.t().contiguous())
         elif mode == K_ELEM:
             grad = _kappa_grad(mode, self.kappa_shape, None, acc)
         else:
-            grad = _kappa_grad(mode, self.kappa_shape, acc[:B], None)
+            grad = _kappa_grad(mode, self.kappa_shape, acc, None)
         return grad.to(self.kappa_device)
 
 

@@ -50,7 +50,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
-from .plan import get_plan, padded_batch, _stream
+from .plan import get_plan, padded_batch, valid_batch_pad, _stream
 from .solver import (K_ELEM, K_SAMPLE_ELEM, SolveInfo, _Engine, _SOLVERS, _call_options, _kappa_grad, _kappa_layout,
                      _like_grads, _fake_grads, _register_state, _resolve_device, _run_call, _state_of, _tie_state)
 
@@ -253,7 +253,7 @@ class _ElasticSolve:
         """y_a = M x_a per component a with the node-level load map of the plan: the (n, d, Bp) array is an (n, d Bp)
         node vector; where d Bp is no valid batch width the components go through one by one."""
         plan, Bp, d = self.plan, self.Bp, self.plan.dim
-        if _valid_batch(d * Bp):
+        if valid_batch_pad(d * Bp):
             return self.node_eng.load_vector(x, None, 1, d * Bp, free_rows=False).reshape(plan.n * d, Bp)
         xc = x.reshape(plan.n, d, Bp).permute(1, 0, 2).contiguous()
         yc = torch.stack([self.node_eng.load_vector(xc[a], None, 1, Bp, free_rows=False) for a in range(d)])
@@ -315,24 +315,12 @@ class _ElasticSolve:
         grad_e = grad_f = grad_load = None
         if need_e:
             gtab, vol = plan.gradient_table()
-            new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=plan.device)  # noqa: E731
             args = (plan.elems, gtab, vol, plan.dim, setup.lam1, setup.mu1, lam, self.x, setup.dofs.g, plan.n, plan.m)
-            if call.mode == K_ELEM:         # a field the batch shares: summed over the batch inside the kernel
-                de = new(plan.m)
-                L.diffhe_elast_grad_shared(*args, B, Bp, de, st)
-                grad_e = _kappa_grad(call.mode, call.e_shape, None, de)
-            elif call.mode == K_SAMPLE_ELEM:
-                de = new(plan.m, Bp)
-                L.diffhe_elast_grad(*args, Bp, de, None, None, st)
-                if call.kappa_em:
-                    de = de if Bp == B else de[:, :B]
-                else:
-                    de = self.node_eng.to_sample_major(de, B, Bp, plan.m)
-                grad_e = _kappa_grad(call.mode, call.e_shape, None, de)
-            else:
-                part, total = new(L.diffhe_grad_kappa_blocks(plan.m, Bp), Bp), new(Bp)
-                L.diffhe_elast_grad(*args, Bp, None, part, total, st)
-                grad_e = _kappa_grad(call.mode, call.e_shape, total[:B], None)
+            sums, de = self.node_eng.element_grad(
+                call.mode, call.kappa_em, B, Bp, None,
+                lambda de_e, osc, ose, part, total: L.diffhe_elast_grad(*args, Bp, de_e, part, total, st),
+                lambda de, osc, ose: L.diffhe_elast_grad_shared(*args, B, Bp, de, st))
+            grad_e = _kappa_grad(call.mode, call.e_shape, sums, de)
             grad_e = grad_e.to(call.e_device)
         if need_f:
             df = self._from_dofs(self._apply_load_map(lam))
@@ -342,11 +330,6 @@ class _ElasticSolve:
             dl = dl.clone() if call.node_major else dl
             grad_load = (dl if call.load_batched else dl.sum(dim=0)).to(call.out_device)
         return grad_e, grad_f, grad_load
-
-
-def _valid_batch(Bp: int) -> bool:
-    """A batch width the node kernels take: a power of two <= 64 or a multiple of 64 (include/diffhe_hip.h)."""
-    return Bp > 0 and ((Bp & (Bp - 1)) == 0 if Bp <= 64 else Bp % 64 == 0)
 
 
 @dataclass

@@ -77,6 +77,11 @@ def padded_batch(B: int) -> int:
     return ((B + 63) // 64) * 64
 
 
+def valid_batch_pad(Bp: int) -> bool:
+    """A batch width the node kernels take: a power of two <= 64 or a multiple of 64 (include/diffhe_hip.h)."""
+    return Bp > 0 and ((Bp & (Bp - 1)) == 0 if Bp <= 64 else Bp % 64 == 0)
+
+
 def _bc_arrays(mesh):
     n = mesh.n_nodes
     is_bc = np.zeros(n, dtype=np.uint8)

@@ -250,34 +250,49 @@ class _Engine:
                                           self.g, vals, lift, p.n, p.m, p.W, Bv, _stream(p.device))
         return vals, lift
 
+    def element_grad(self, mode, em, B, Bp, nc, per_sample, shared):
+        """The one dispatch of the coefficient gradients (csrc/element_grad.h) -> (per-sample sums, per-element gradient),
+        one of the two None.  A field the batch shares (K_ELEM): summed over the batch inside the kernel, (m,).  One
+        field per sample (K_SAMPLE_ELEM): per element and sample, left element-major (m, B) for `em`, else transposed
+        back to (B, m).  Otherwise the sums over the elements per sample in two stages, (B,).
+        nc: None, or the components per element of a tensor: (m, nc), (nc, m, B) or (B, m * nc), (nc, B).
+        per_sample(dk_e, osc, ose, part, dk_sum) and shared(dk, osc, ose) launch the family's two entries."""
+        p = self.p
+        m, w = p.m, nc or 1
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=p.device)  # noqa: E731
+        lead = (nc,) if nc else ()
+        if mode == K_ELEM:
+            dk = new(m, *lead)
+            shared(dk, 1, w)
+            return None, dk
+        if mode != K_SAMPLE_ELEM:
+            part, dk_sum = new(self.L.diffhe_grad_kappa_blocks(m, Bp), w, Bp), new(*lead, Bp)
+            per_sample(None, 0, 0, part, dk_sum)
+            return dk_sum[..., :B], None
+        if em:
+            dk_e = new(*lead, m, Bp)
+            per_sample(dk_e, m * Bp, Bp, None, None)
+            return None, dk_e if Bp == B else dk_e[..., :B]
+        dk_e = new(m * w, Bp)
+        per_sample(dk_e, Bp, w * Bp, None, None)
+        return None, self.to_sample_major(dk_e, B, Bp, m * w)
+
     def grad_tensor(self, lam, x, B, Bp, nc, mode, em):
         """dL/dK = -|e| sym(grad lambda (x) grad u) in the shape of the caller's tensor: per element and sample, summed
         over the batch inside the kernel (a shared field), or summed over the elements per sample in two stages (one
         tensor per sample; the tensor of the whole batch is the sum of those)."""
         p, L = self.p, self.L
         gtab, vol = p.gradient_table()
-        st = _stream(p.device)
-        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=p.device)  # noqa: E731
-        if mode == K_ELEM:
-            dk = new(p.m, nc)
-            L.diffhe_aniso_grad_shared(p.elems, gtab, vol, p.dim, lam, x, self.g, p.n, p.m, B, Bp, dk, 1, nc, st)
-            return dk
-        dk_e = part = dk_sum = None
-        osc = ose = 0
-        if mode != K_SAMPLE_ELEM:
-            part, dk_sum = new(L.diffhe_grad_kappa_blocks(p.m, Bp), nc, Bp), new(nc, Bp)
-        elif em:
-            dk_e, osc, ose = new(nc, p.m, Bp), p.m * Bp, Bp
-        else:
-            dk_e, osc, ose = new(p.m * nc, Bp), Bp, nc * Bp
-        L.diffhe_aniso_grad(p.elems, gtab, vol, p.dim, lam, x, self.g, p.n, p.m, Bp, dk_e, osc, ose, part, dk_sum, st)
+        args, st = (p.elems, gtab, vol, p.dim, lam, x, self.g, p.n, p.m), _stream(p.device)
+        dk_sum, dk_e = self.element_grad(
+            mode, em, B, Bp, nc,
+            lambda dk_e, osc, ose, part, dk_sum: L.diffhe_aniso_grad(*args, Bp, dk_e, osc, ose, part, dk_sum, st),
+            lambda dk, osc, ose: L.diffhe_aniso_grad_shared(*args, B, Bp, dk, osc, ose, st))
         if mode == K_SCALAR:
-            return dk_sum[:, :B].sum(dim=1)
+            return dk_sum.sum(dim=1)
         if mode == K_SAMPLE:
-            return dk_sum[:, :B].t().contiguous()
-        if em:
-            return dk_e if Bp == B else dk_e[:, :, :B]
-        return self.to_sample_major(dk_e, B, Bp, p.m * nc).reshape(B, p.m, nc)
+            return dk_sum.t().contiguous()
+        return dk_e if mode == K_ELEM or em else dk_e.reshape(B, p.m, nc)
 
     def reaction_shifts(self, c, n_levels):
         """Per-level (n,) diagonal shifts c * M_L (0 on Dirichlet rows) of a FACTORED lattice operator, cached on the plan."""
@@ -593,32 +608,26 @@ class _Engine:
         _hip.check(rc, "diffhe_lattice_bilinear")
         return -out
 
-    def grad_kappa(self, lam, x, Bp, want_elem):
+    def grad_kappa(self, lam, x, B, Bp, mode, em):
+        """dL/dkappa = -lambda^T k0 u -> (per-sample sums, per-element gradient) as `element_grad` leaves them."""
         p, L = self.p, self.L
-        if want_elem and p.is_lattice and Bp >= 64:
-            # lattice mesh, per-element gradient of every sample: strip pass (each nodal value read once per wave)
-            lev = p.levels[0]
-            dk_e = torch.empty((p.m, Bp), dtype=torch.float64, device=p.device)
-            small = lev.compact("k0")
-            L.diffhe_lattice_grad_kappa(lev.nx, lev.ny, small if small is not None else lev.k0,
-                                        1 if small is not None else 0, lam, x, self.g, dk_e, Bp, _stream(p.device))
-            return dk_e, None
-        nblk = L.diffhe_grad_kappa_blocks(p.m, Bp)
-        dk_e = torch.empty((p.m, Bp), dtype=torch.float64, device=p.device) if want_elem else None
-        part = torch.empty((nblk, Bp), dtype=torch.float64, device=p.device)
-        dk_sum = torch.empty(Bp, dtype=torch.float64, device=p.device)
-        k0 = p.k0 if p._ell_ready else p.levels[0].k0      # lattice meshes keep k0 on level 0
-        L.diffhe_p1_grad_kappa(p.elems, k0, lam, x, self.g, p.npe, p.m, Bp, dk_e, part, dk_sum, _stream(p.device))
-        return dk_e, dk_sum
+        args, st = (p.elems, p.element_stiffness(), lam, x, self.g, p.npe, p.m), _stream(p.device)
 
-    def grad_kappa_shared(self, lam, x, B, Bp):
-        """dL/dkappa_e summed over the batch, (m,): the gradient of ONE per-element field shared by all samples,
-        without the (m, Bp) per-sample gradient (what the multi-GPU gradient all-reduce carries)."""
-        p, L = self.p, self.L
-        dk = torch.empty(p.m, dtype=torch.float64, device=p.device)
-        k0 = p.k0 if p._ell_ready else p.levels[0].k0
-        L.diffhe_p1_grad_kappa_shared(p.elems, k0, lam, x, self.g, p.npe, p.m, B, Bp, dk, _stream(p.device))
-        return dk
+        def per_sample(dk_e, osc, ose, part, dk_sum):
+            if dk_e is not None and p.is_lattice and Bp >= 64:
+                # lattice mesh, per-element gradient of every sample: strip pass (each nodal value read once per wave)
+                lev = p.levels[0]
+                small = lev.compact("k0")
+                L.diffhe_lattice_grad_kappa(lev.nx, lev.ny, small if small is not None else lev.k0,
+                                            1 if small is not None else 0, lam, x, self.g, dk_e, Bp, st)
+                return
+            if part is None:    # this entry always leaves the totals
+                part = torch.empty((L.diffhe_grad_kappa_blocks(p.m, Bp), Bp), dtype=torch.float64, device=p.device)
+                dk_sum = torch.empty(Bp, dtype=torch.float64, device=p.device)
+            L.diffhe_p1_grad_kappa(*args, Bp, dk_e, part, dk_sum, st)
+
+        return self.element_grad(mode, em, B, Bp, None, per_sample,
+                                 lambda dk, osc, ose: L.diffhe_p1_grad_kappa_shared(*args, B, Bp, dk, st))
 
     # -- per-call Dirichlet data (csrc/bc.hip): boundary band only ------------------------------------------
     def bc_lift(self, kappa_s, G, rhs, rsn, rsb, B):
@@ -987,19 +996,12 @@ class _NodeMajorSolve(_PathSolve):
         return lam, dk_sample, dk_elem, df, dload
 
     def _grad_kappa(self, lam):
-        """-> (per-sample sums, per-element gradient) of dL/dkappa = -lambda^T k0 u, as `_kappa_grad` takes them."""
-        eng, call, B, Bp = self.eng, self.call, self.call.B, self.Bp
+        """-> (per-sample sums, per-element gradient) of dL/dkappa = -lambda^T k0 u, as `_kappa_grad` takes them: the
+        per-element one (B, m) like the API's kappa, or left element-major (m, B) when kappa came that way."""
+        eng, call = self.eng, self.call
         if call.nc:     # a conductivity tensor: the gradient comes back in the caller's shape (`_solve_backward`)
-            return None, eng.grad_tensor(lam, self.x, B, Bp, call.nc, call.mode, call.kappa_em)
-        if call.mode == K_ELEM:
-            return None, eng.grad_kappa_shared(lam, self.x, B, Bp)       # (m,): summed over the batch in the kernel
-        dk_nm, dk_sum = eng.grad_kappa(lam, self.x, Bp, call.mode == K_SAMPLE_ELEM)
-        if call.mode != K_SAMPLE_ELEM:
-            return dk_sum[:B], None
-        # (B, m) like the API's kappa, or left element-major (m, B) when kappa came that way
-        if call.kappa_em:
-            return None, dk_nm if Bp == B else dk_nm[:, :B]
-        return None, eng.to_sample_major(dk_nm, B, Bp, self.plan.m)
+            return None, eng.grad_tensor(lam, self.x, call.B, self.Bp, call.nc, call.mode, call.kappa_em)
+        return eng.grad_kappa(lam, self.x, call.B, self.Bp, call.mode, call.kappa_em)
 
     def shape_fields(self, lam):
         """(u, lambda, node stride, sample stride, Dirichlet data) for the node-gradient kernel: (n, Bp) arrays."""
