@@ -67,6 +67,10 @@ enum { M_APPLY = 0, M_RESID = 1, M_JACOBI = 2 };
 //              columns 2 J0 - 1 .. 2 J0 + 2 CW - 1 that feed the wave's CW coarse columns (one fine
 //              column is shared with -- and recomputed by -- each neighbour strip) and the tile the
 //              fine rows 2 I0 - 1 .. 2 I1 - 1 of the coarse rows I0 .. I1 - 1.
+//   F_PROLONG with M_RESID and NO x operand (xin == NULL; the full-multigrid start's fine level): the operand IS the
+//              prolonged coarse iterate rounded to the storage type -- the very values mg_prolong2_kernel /
+//              mg_prolong_add_kernel (set) store, 0 on fine Dirichlet nodes.  The strip stores them for its own
+//              columns (ex.p_out) and the residual rhs - A (P e) as the plain residual pass does: one pass for two.
 enum { F_NONE = 0, F_PROLONG = 1, F_PUPD = 2, F_RESTRICT = 3, F_PUPD_NX = 4, F_RUPD = 5, F_RPAIR = 6, F_RDROP = 7, F_RSINGLE = 8 };
 // F_RUPD (with M_APPLY): the CG's residual update with A p RECOMPUTED from the stored direction p (TA, ex.p_in) instead of
 // read back: r -= alpha (A p), the fp32 copy of r and the partials of r.r in one pass -- for a batch-shared matrix (scalar
@@ -92,6 +96,9 @@ static_assert((DIFFHE_PCG_RESID_KEEP_LO & (kPcgKnownBits | DIFFHE_PCG_RESID_FP64
               "DIFFHE_PCG_RESID_KEEP_LO must be a bit of its own");
 static_assert(((15 << DIFFHE_PCG_TRUST_ITS_SHIFT) & (kPcgKnownBits | DIFFHE_PCG_RESID_FP64 | DIFFHE_PCG_RESID_KEEP_LO)) == 0,
               "the four bits at DIFFHE_PCG_TRUST_ITS_SHIFT must be their own");
+static_assert((DIFFHE_PCG_SPLIT_START & (kPcgKnownBits | DIFFHE_PCG_RESID_FP64 | DIFFHE_PCG_RESID_KEEP_LO |
+                                         (15 << DIFFHE_PCG_TRUST_ITS_SHIFT))) == 0,
+              "DIFFHE_PCG_SPLIT_START must be a bit of its own");
 constexpr bool is_pupd(int fuse) { return fuse == F_PUPD || fuse == F_PUPD_NX; }
 constexpr bool is_rpair(int fuse) { return fuse == F_RPAIR || fuse == F_RDROP || fuse == F_RSINGLE; }   // hi (+ lo) forms
 constexpr bool rupd_reads_lo(int fuse) { return fuse == F_RPAIR || fuse == F_RDROP; }
@@ -103,7 +110,8 @@ constexpr bool plain_resid(int mode, int fuse) { return mode == M_RESID && (fuse
 struct Extra {
   const void* a0;           // F_PROLONG: coarse correction e (TA);  F_PUPD: z (TA)
   const void* p_in;         // F_PUPD: previous search direction, stored as TA (the type of z)
-  void* p_out;              // F_PUPD: new search direction, stored as TA
+  void* p_out;              // F_PUPD: new search direction, stored as TA;  M_RESID, F_PROLONG without x: the prolonged
+                            //   iterate, stored as TV
   double* x;                // F_PUPD: iterate, updated in place (NULL: left alone -- the solver keeps its directions
                             //   and forms x once at the end, pcg_finish_kernel)
   const double* alpha;      // F_PUPD: per-sample alpha of the previous iteration
@@ -447,6 +455,7 @@ void launch_strip(const Level& L, int Bv, const double* scale, const TV* xin, co
 template <int MODE, bool XFROMB, int FUSE, int RW>
 void launch_strip2(const Level& L, const double* scale, const float* xin, const float* bvec, float* out, double omega,
                    double omega_in, double* part, int Bp, const StripGeom& g, hipStream_t st, const Extra& ex = Extra{});
+// pout == z (first step only): p0 = z0 already lives in its ring slot -- read in place, nothing stored
 void launch_cgstep2(const Level& L, const double* scale, const double* beta, int first, const float* z, const float* pin,
                     float* pout, double* part, int Bp, const StripGeom& g, int spl, hipStream_t st);
 
@@ -467,6 +476,7 @@ struct Hier : CycleWork {   // + the per-level work vectors (cycle_carve)
   int fuse;  // 0: four single-stage strip passes per level; 1 / 2: fused two-stage passes, samples per lane
   int pre4;  // the fused PRE pass may take four samples per lane (fused_spl)
   int dense_mfma;  // coarsest-level dense solve of an fp32 cycle on the matrix cores (0: scalar-load kernel)
+  int split_start; // full-multigrid start: separate prolongation and residual passes on the fine level (DIFFHE_PCG_SPLIT_START)
   double coarse_lmax;  // upper bound of the spectrum of D^-1 A on the coarsest level (2 for an M-matrix)
 };
 
@@ -490,10 +500,18 @@ i64 carve_cycle(Hier& H, double* work, bool fp32);   // cycle_carve over H's lev
 // What the driver (lattice_pcg.hip) asks of the cycle unit.  fp32 = storage type of the cycle's vectors; the branch on it
 // is taken once, inside.  Those that leave partial sums return the number of partial blocks they wrote.
 // z = V(r): the buffer holding z; the last fine sweep leaves the partials of r.z in `part` (*nblocks of them)
-const void* cycle_precondition(const Hier& H, bool fp32, const void* r, double* part, int* nblocks, hipStream_t st);
+// dest (optional, fp32 cycles): where the finest level's last pass should put z; honoured where that pass is the fused POST
+// pass or a plain sweep -- the caller tells by the pointer that comes back
+const void* cycle_precondition(const Hier& H, bool fp32, const void* r, double* part, int* nblocks, hipStream_t st,
+                               void* dest = nullptr);
 // full-multigrid start from the right-hand side b0: the iterate (NULL: error recorded), *pending = the fine level's last
 // correction, not yet added (may come back NULL)
-const void* cycle_fmg_start(const Hier& H, bool fp32, const void* b0, hipStream_t st, const void** pending);
+// have_b1 (fp32 only): the level-1 right-hand side is there already (cycle_cvt_restrict)
+const void* cycle_fmg_start(const Hier& H, bool fp32, const void* b0, hipStream_t st, const void** pending,
+                            bool have_b1 = false);
+// r32 = (float)(rs b) and the level-1 right-hand side of the full-multigrid start, R r32, in one pass: fp32 cycle, level 0
+// halves in both directions, Bp a multiple of 64 (the caller's condition: Solve::fused_start)
+void cycle_cvt_restrict(const Hier& H, const double* b, const double* rs, float* r32, hipStream_t st);
 // level 0, fp64: res = rhs - A x (res may be NULL), partials of r.r -- or, dot_bx, of b.x and (part2) x.(A x)
 int cycle_residual(const Hier& H, const double* rhs, const double* x, double* res, double* part, hipStream_t st,
                    int dot_bx = 0, double* part2 = nullptr);

@@ -252,6 +252,71 @@ __global__ __launch_bounds__(256) void mg_restrict2_kernel(Level F, Level C, con
   }
 }
 
+// The right-hand side of a cold full-multigrid start in ONE pass: r32 = (float)(rs b), what pcg_cvt_kernel stores, and the
+// level-1 right-hand side R r32, what mg_restrict2_kernel / mg_restrict_kernel form from it -- the same per-sample
+// expression on the ROUNDED values in the same order of additions (W, E, S, N, SE-of-the-row-above, SW-of-the-row-below;
+// centre + h / 2), so both vectors are bit for bit theirs.  Strip-shaped like the F_RESTRICT passes: a wave owns two coarse
+// columns x 64 samples and marches down the coarse rows of its tile holding the fine rows 2 I - 1, 2 I, 2 I + 1 at the five
+// fine columns 2 J0 - 1 .. 2 J0 + 3; it stores r32 on the rows 2 I, 2 I + 1 and the columns 2 J0 .. 2 J0 + 3 (each fine
+// node has exactly one owner; the halo column and row are read again: L2).  Full coarsening only.
+__global__ __launch_bounds__(256) void cvt_restrict_kernel(Level F, Level C, const double* __restrict__ b,
+                                                            const double* __restrict__ rs, float* __restrict__ r32,
+                                                            float* __restrict__ rc, int Bp, int ncb, int TR) {
+  constexpr int CW = 2, NC = 2 * CW + 1;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned lb = blockIdx.y * kWave + lane;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
+  const int tr = tile / ncb, cb = tile - tr * ncb;
+  const int J0 = (cb * 4 + wave) * CW, I0 = tr * TR;
+  const int I1 = (I0 + TR < C.ny + 1) ? I0 + TR : C.ny + 1;
+  if (J0 >= C.W || I0 >= I1) return;
+  const double sc = rs ? rs[lb] : 1.0;
+  const int c0 = 2 * J0 - 1;   // fine column of window index 0
+  // fine row `row` at the window's columns, rounded; `own`: this wave stores its columns 1 .. NC - 1
+  auto load_row = [&](int row, float* dst, bool own) {
+    const bool rok = row >= 0 && row <= F.ny;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const int c = c0 + k;
+      float v = 0.0f;
+      if (rok && c >= 0 && c < F.W) {
+        const i64 o = ((i64)row * F.W + c) * Bp + lb;
+        v = (float)(b[o] * sc);
+        if (own && k > 0) r32[o] = v;
+      }
+      dst[k] = v;
+    }
+  };
+  float pm[NC], cu[NC], nx[NC];
+  load_row(2 * I0 - 1, pm, false);   // the tile above owns it (row -1: zeros, never used)
+  for (int I = I0; I < I1; ++I) {
+    const int fi = 2 * I;
+    load_row(fi, cu, true);
+    load_row(fi + 1, nx, true);
+#pragma unroll
+    for (int j = 0; j < CW; ++j) {
+      const int J = J0 + j, fj = 2 * J, k = 2 * j + 1;
+      if (J >= C.W) continue;
+      const i64 Ic = (i64)I * C.W + J;
+      double out = 0.0;
+      if (!C.bc[Ic]) {
+        double h = 0.0;
+        if (fj > 0) h += (double)cu[k - 1];
+        if (fj < F.nx) h += (double)cu[k + 1];
+        if (fi > 0) h += (double)pm[k];
+        if (fi < F.ny) h += (double)nx[k];
+        if (fi > 0 && fj < F.nx) h += (double)pm[k + 1];
+        if (fi < F.ny && fj > 0) h += (double)nx[k - 1];
+        out = (double)cu[k] + 0.5 * h;
+      }
+      rc[Ic * Bp + lb] = (float)out;
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) pm[k] = nx[k];
+  }
+}
+
 inline bool transfers2_ok(const Level& F, const Level& C, int Bp, size_t esz) {
   return esz == 4 && F.nx == 2 * C.nx && F.ny == 2 * C.ny && Bp % (2 * kWave) == 0;
 }
@@ -690,9 +755,11 @@ int fused_level(const Hier& H, int l, StripGeom* gpre, StripGeom* gpost) {
 // guess != NULL (only where fused_level(H, l0) & 2): the cycle starts from the initial guess P guess instead of 0 and
 // returns the new ITERATE for the right-hand side rhs0 -- in exact arithmetic P guess + V(rhs0 - A P guess), without the
 // prolongation, residual and addition passes of that form (full-multigrid start).
+// dest != NULL (l0 == 0 only): the last pass of level 0 writes z there where that pass is the fused POST pass or a plain
+// sweep (the other forms return their own buffer: the caller tells by the pointer).
 template <typename TV>
 TV* vcycle(const Hier& H, const TV* rhs0, double* rz_part, int* rz_blocks, hipStream_t st, int l0 = 0,
-           const TV* guess = nullptr) {
+           const TV* guess = nullptr, TV* dest = nullptr) {
   const TV* rhs[kMaxLevels];
   TV* cur[kMaxLevels];
   bool fused[kMaxLevels];
@@ -770,6 +837,7 @@ TV* vcycle(const Hier& H, const TV* rhs0, double* rz_part, int* rz_blocks, hipSt
     TV* b2 = (a == (TV*)H.xa[l]) ? (TV*)H.xb[l] : (TV*)H.xa[l];
     if (fused[l]) {   // prolongation + correction + both post-sweeps (+ the partials of rhs . z) in ONE pass
       const bool dot = (l == l0) && rz_part;
+      if (l == 0 && dest) b2 = dest;
       if (l == 0) kp_begin(KP_PROLONG, st);
       launch_fused_post(L, C, H.Bv, H.scale, (const float*)a, (const float*)rhs[l], (const float*)cur[l + 1], (float*)b2,
                         H.omega[1], H.omega[0], dot ? rz_part : nullptr, H.Bp, gpost[l], fused_spl(H, L, false), st);
@@ -802,6 +870,7 @@ TV* vcycle(const Hier& H, const TV* rhs0, double* rz_part, int* rz_blocks, hipSt
     }
     for (int s = s0; s < H.nu; ++s) {
       const bool lastsweep = (l == l0 && s == H.nu - 1);
+      if (lastsweep && l == 0 && dest && s > 0) b2 = dest;   // s > 0: a sweep before it has filled `a` (never dest itself)
       const int nb = op_jacobi<TV>(H, l, rhs[l], a, b2, H.omega[H.nu - 1 - s], lastsweep ? rz_part : nullptr, st);
       if (lastsweep && rz_blocks) *rz_blocks = nb;
       TV* t = a; a = b2; b2 = t;
@@ -811,18 +880,30 @@ TV* vcycle(const Hier& H, const TV* rhs0, double* rz_part, int* rz_blocks, hipSt
   return cur[l0];
 }
 
+// The fine level of the full-multigrid start takes prolongation and residual as ONE strip pass (M_RESID, F_PROLONG without
+// x, lattice.h) where the vectors are fp32, the matrix is batch-shared, the level runs the strip kernels and its
+// coarsening halves both directions; DIFFHE_PCG_SPLIT_START keeps the two passes.
+template <typename TV>
+bool prolong_resid_ok(const Hier& H, int l) {
+  if (l != 0 || H.split_start || sizeof(TV) != 4 || H.Bv != 1 || H.lev[0].shift) return false;
+  const Level& L = H.lev[0];
+  const Level& C = H.lev[1];
+  return L.nx == 2 * C.nx && L.ny == 2 * C.ny && strip_geom(L, H.Bp).use;
+}
+
 // Full multigrid start: solve on the coarsest level, then per level interpolate, take the residual
 // and apply one V-cycle.  Gives the CG an iterate whose error is already smooth (about 3-4 CG
 // iterations ahead of a zero guess) for ~0.8 of an iteration.  b0 = right-hand side in TV storage.
 // *pending (optional): the fine level's last correction is NOT added to the returned iterate but handed back -- the
 // caller's conversion pass (pcg_setx_kernel) adds the two in fp64, one pass over x less.
+// have_b1: the level-1 right-hand side is in H.bF[1] already (cycle_cvt_restrict).
 template <typename TV>
-TV* fmg_start(const Hier& H, const TV* b0, hipStream_t st, const TV** pending = nullptr) {
+TV* fmg_start(const Hier& H, const TV* b0, hipStream_t st, const TV** pending = nullptr, bool have_b1 = false) {
   const int last = H.nl - 1;
   const TV* bl[kMaxLevels];
   bl[0] = b0;
   for (int l = 0; l < last; ++l) {
-    launch_restrict<TV>(H, H.lev[l], H.lev[l + 1], bl[l], (TV*)H.bF[l + 1], st);
+    if (l > 0 || !have_b1) launch_restrict<TV>(H, H.lev[l], H.lev[l + 1], bl[l], (TV*)H.bF[l + 1], st);
     bl[l + 1] = (const TV*)H.bF[l + 1];
   }
   {  // coarsest level: the V-cycle from `last` is n_coarse Jacobi sweeps
@@ -841,6 +922,7 @@ TV* fmg_start(const Hier& H, const TV* b0, hipStream_t st, const TV** pending = 
     StripGeom g1, g2;
     TV* x = (TV*)H.xF[l];
     int c0 = 0;
+    bool have_resid = false;   // H.rhs[l] already holds the residual of x (the fused pass of the fine level)
     if (l > 0 && (fused_level<TV>(H, l, &g1, &g2) & 2)) {
       // levels with the fused passes: ONE cycle from the prolonged guess -- no prolongation, residual or addition pass
       TV* it = vcycle<TV>(H, bl[l], nullptr, nullptr, st, l, coarse);
@@ -850,11 +932,20 @@ TV* fmg_start(const Hier& H, const TV* b0, hipStream_t st, const TV** pending = 
       }
       if (diffhe::check(hipMemcpyAsync(x, it, (size_t)L.n * H.Bp * sizeof(TV), hipMemcpyDeviceToDevice, st))) return nullptr;
       c0 = 1;
+    } else if (prolong_resid_ok<TV>(H, l)) {
+      // x = P coarse and rhs - A x in ONE strip pass: the window is the prolonged iterate as the transfer kernel would
+      // have stored it, so x and the residual are bit for bit those of the two passes below
+      Extra ex{};
+      ex.a0 = coarse; ex.cW = H.lev[l + 1].W; ex.bc = L.bc; ex.p_out = x;
+      launch_strip<TV, M_RESID, false, F_PROLONG, TV, kStripCols, 1, MAT_SHARED>(
+          L, H.Bv, H.scale, (const TV*)nullptr, bl[l], (TV*)H.rhs[l], 0.0, 0.0, nullptr, H.Bp, strip_geom(L, H.Bp), st, ex);
+      have_resid = true;
     } else {
       launch_prolong<TV>(H, L, H.lev[l + 1], coarse, x, 1, st);
     }
     for (int c = c0; c < cycles; ++c) {
-      op_residual<TV>(H, l, bl[l], (const TV*)x, (TV*)H.rhs[l], nullptr, st);
+      if (!have_resid) op_residual<TV>(H, l, bl[l], (const TV*)x, (TV*)H.rhs[l], nullptr, st);
+      have_resid = false;
       TV* e = vcycle<TV>(H, (const TV*)H.rhs[l], nullptr, nullptr, st, l);
       if (l == 0 && c == cycles - 1 && pending) {
         *pending = e;
@@ -896,6 +987,7 @@ int fill_hier(Hier& H, const diffhe_mg_level* levels, int n_levels, int Bv, int 
   H.fuse = Bp % (2 * kWave) == 0 ? 2 : 1;   // one sample per lane where the batch is no multiple of 128
   H.pre4 = 1;
   H.dense_mfma = 1;
+  H.split_start = 0;
   for (int k = 0; k < 8; ++k) H.omega[k] = omegas[k < nu ? k : nu - 1];
   return DIFFHE_OK;
 }
@@ -912,15 +1004,25 @@ i64 carve_cycle(Hier& H, double* work, bool fp32) {
 }
 
 // ---- what the driver calls: the storage type is resolved here, once ---------------------------------------------------
-const void* cycle_precondition(const Hier& H, bool fp32, const void* r, double* part, int* nblocks, hipStream_t st) {
-  if (fp32) return vcycle<float>(H, (const float*)r, part, nblocks, st);
+const void* cycle_precondition(const Hier& H, bool fp32, const void* r, double* part, int* nblocks, hipStream_t st, void* dest) {
+  if (fp32) return vcycle<float>(H, (const float*)r, part, nblocks, st, 0, nullptr, (float*)dest);
   return vcycle<double>(H, (const double*)r, part, nblocks, st);
 }
 
-const void* cycle_fmg_start(const Hier& H, bool fp32, const void* b0, hipStream_t st, const void** pending) {
+void cycle_cvt_restrict(const Hier& H, const double* b, const double* rs, float* r32, hipStream_t st) {
+  const Level& F = H.lev[0];
+  const Level& C = H.lev[1];
+  // tiles of coarse rows, as the fused residual + restriction (resid_restrict)
+  const StripGeom g = tile_geom(C.ny + 1, (C.W + 4 * 2 - 1) / (4 * 2), H.Bp / kWave, kStripBlocks, 4, 0);
+  diffhe::account((12.0 * F.n + 4.0 * C.n) * H.Bp);   // b read, r32 and the coarse vector written
+  hipLaunchKernelGGL(cvt_restrict_kernel, dim3(g.ncb * g.nrc, H.Bp / kWave), dim3(256), 0, st, F, C, b, rs, r32,
+                     (float*)H.bF[1], H.Bp, g.ncb, g.TR);
+}
+
+const void* cycle_fmg_start(const Hier& H, bool fp32, const void* b0, hipStream_t st, const void** pending, bool have_b1) {
   if (fp32) {
     const float* e0 = nullptr;
-    const float* x0 = fmg_start<float>(H, (const float*)b0, st, &e0);
+    const float* x0 = fmg_start<float>(H, (const float*)b0, st, &e0, have_b1);
     *pending = e0;
     return x0;
   }

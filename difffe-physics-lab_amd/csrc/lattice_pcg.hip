@@ -451,6 +451,7 @@ struct PcgOptions {
   bool unfused;           // keep the four single-stage passes (A/B runs, tests)
   bool dense_scalar;      // scalar-load dense coarse solve
   bool pre2;              // fused PRE pass with two samples per lane as well (A/B runs, tests)
+  bool split_start;       // keep the separate passes around the full-multigrid start (A/B runs, tests)
 
   PcgOptions(int flags, int n_levels)
       : f32((flags & DIFFHE_PCG_FP32) != 0),
@@ -464,13 +465,15 @@ struct PcgOptions {
         fmg_coarse_cycles(1 + ((flags >> DIFFHE_PCG_FMG_CYCLES_SHIFT) & 3)),
         unfused((flags & DIFFHE_PCG_UNFUSED) != 0),
         dense_scalar((flags & DIFFHE_PCG_DENSE_SCALAR) != 0),
-        pre2((flags & DIFFHE_PCG_PRE2) != 0) {}
+        pre2((flags & DIFFHE_PCG_PRE2) != 0),
+        split_start((flags & DIFFHE_PCG_SPLIT_START) != 0) {}
 
   void override_hier(Hier& H) const {
     H.fmg_coarse_cycles = fmg_coarse_cycles;
     if (unfused) H.fuse = 0;
     if (dense_scalar) H.dense_mfma = 0;
     if (pre2) H.pre4 = 0;
+    if (split_start || warm) H.split_start = 1;   // the fused start passes belong to the cold start
   }
 };
 
@@ -506,6 +509,10 @@ struct Solve {
   bool rpair;   // ... and there the residual is carried as a pair of fp32 vectors, r32 (what the V-cycle reads) + rlo, not as
                 // fp64 r plus r32 (F_RPAIR, lattice.h): nothing but the residual update and the pass that opens the loop touches it
   int cspl;
+  bool step2;        // the CG step is cgstep2_kernel (p.Ap in packed fp32)
+  bool fused_start;  // cold full-multigrid start of an fp32 solve with a batch-shared matrix whose fine level takes the strip
+                     // kernels and halves in both directions: the passes around the start are fused (DIFFHE_PCG_SPLIT_START
+                     // keeps them apart)
 
   const void* z = nullptr;
   int it = 0, flushed = 0;     // iterations done / directions already folded into x (fused loop)
@@ -558,6 +565,14 @@ struct Solve {
     cspl = (Bp % (2 * kWave) == 0) ? 2 : 1;
     g2 = (Bp % kWave == 0) ? strip_geom(L0, Bp, 4, cspl) : StripGeom{false, 0, 0, 0};
     lo = LowHalf(rpair && !o.keep_lo && S.tol_e2 > 0.0);
+    // DIFFHE_PCG_CLOSED_FP32_STEP: the caller vouches for a lattice closed by Dirichlet data (lambda_min of the scaled operator bounded
+    // away from 0).  With large Neumann parts the search directions are dominated by near-null modes, for which the
+    // fp32 stencil cancels to noise: measured 13 / 11 instead of 12 / 9 iterations to 1e-14 there (gpurun_out/r6g)
+    // (the host also asks for near-square cells and a hierarchy that reaches the dense coarsest level: on a 382 x 259
+    // lattice, which coarsens once, 36 iterations to 1e-14 became 38 -- tools/stress.py seed 6301 case 39)
+    step2 = o.f32 && rupd && o.closed_fp32_step && g2.use && shared32_ok(L0, Bv, Bp) && strip2_tile_fits(L0, Bp, g2.TR + 3);
+    fused_start = !o.split_start && o.f32 && o.use_fmg && !o.warm && Bv == 1 && H.nl > 1 && strip_geom(L0, Bp).use &&
+                  L0.nx == 2 * H.lev[1].nx && L0.ny == 2 * H.lev[1].ny;
   }
 
   // One phase of the per-sample scalars over a list of nb_ partial rows (pcg_scalar_kernel; long lists in two stages)
@@ -599,8 +614,11 @@ struct Solve {
   }
 
   // z = V(r) and r.z, then the scalar phase behind it
+  // The first z of a fused start goes straight into ring slot 0, where p0 = z0 lives: the first cgstep2 reads it in place
+  // instead of copying it (4 B per node and sample instead of 8).  finish() finds z there when nothing iterates.
   void precondition(int first) {
-    z = cycle_precondition(H, o.f32, o.f32 ? (const void*)r32 : (const void*)W.r, W.partB, &nbz, st);
+    void* dest = (first && fused_start && step2) ? (void*)W.p : nullptr;
+    z = cycle_precondition(H, o.f32, o.f32 ? (const void*)r32 : (const void*)W.r, W.partB, &nbz, st, dest);
     scalar(first ? S_RZ0 : S_BETA, W.partB, nbz);
   }
 
@@ -650,13 +668,9 @@ struct Solve {
     ex.x = nullptr;            // deferred (flush_directions)
     ex.alpha = nullptr; ex.beta = S.beta; ex.first = first;
     S.alpha = alpha_ring + (long long)(it % n_slots) * Bp;   // alpha_it goes next to p_it
-    // DIFFHE_PCG_CLOSED_FP32_STEP: the caller vouches for a lattice closed by Dirichlet data (lambda_min of the scaled operator bounded
-    // away from 0).  With large Neumann parts the search directions are dominated by near-null modes, for which the
-    // fp32 stencil cancels to noise: measured 13 / 11 instead of 12 / 9 iterations to 1e-14 there (gpurun_out/r6g)
-    // (the host also asks for near-square cells and a hierarchy that reaches the dense coarsest level: on a 382 x 259
-    // lattice, which coarsens once, 36 iterations to 1e-14 became 38 -- tools/stress.py seed 6301 case 39)
-    if (o.f32 && rupd && o.closed_fp32_step && g2.use && shared32_ok(L0, Bv, Bp) && strip2_tile_fits(L0, Bp, g2.TR + 3)) {
+    if (step2) {
       // fp32 stencil for p.Ap (cgstep2_kernel; packed, two samples per lane, where the batch allows): the step length only
+      // (first step of a fused start: z already IS ring slot 0, p_out == z, nothing is stored)
       launch_cgstep2(L0, scale, (const double*)S.beta, first, (const float*)z, (const float*)ex.p_in, (float*)ex.p_out,
                      W.partA, Bp, g2, cspl, st);
       nba = g2.ncb * g2.nrc;
@@ -756,7 +770,10 @@ struct Solve {
     scalar(S_INIT, W.partA, nblk);
     // fp32 copy of rs * b (rs from S_INIT): the full-multigrid start's right-hand side, or r0 of a zero start -- of which
     // the pair path needs the low parts too (they go where pcg_init_kernel has just put the fp64 r0, unused on that path)
-    if (o.f32 && !o.warm) {
+    const bool start_rhs_fused = fused_start && Bp % kWave == 0;   // conversion and first restriction in one pass
+    if (start_rhs_fused) {
+      cycle_cvt_restrict(H, b, S.rs, r32, st);
+    } else if (o.f32 && !o.warm) {
       const bool lo_too = rpair && !o.use_fmg;
       launch_nodes(H, st, lo_too ? 16.0 : 12.0, pcg_cvt_kernel, n, b, (const double*)S.rs, r32, n, Bp,
                    lo_too ? W.rlo : (float*)nullptr);
@@ -768,7 +785,7 @@ struct Solve {
       if (o.warm) residual_pass(false);
       const void* rhs0 = o.f32 ? (const void*)r32 : (o.warm ? (const void*)W.r : (const void*)b);
       const void* e0 = nullptr;
-      const void* x0 = cycle_fmg_start(H, o.f32, rhs0, st, &e0);
+      const void* x0 = cycle_fmg_start(H, o.f32, rhs0, st, &e0, start_rhs_fused);
       if (!x0) return DIFFHE_E_LAUNCH;
       if (o.f32) set_iterate<float>(x0, e0);
       else set_iterate<double>(x0, e0);

@@ -66,7 +66,10 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
   const TO* __restrict__ p2 = p1 + n * Bv;
   const TO* __restrict__ p3 = p2 + n * Bv;
   const double* __restrict__ psh = SHIFT ? L.shift + i0 : nullptr;   // diagonal shift at (row, c0w): wave-uniform loads
-  const TV* __restrict__ px = src + i0 * Bp;
+  // M_RESID, F_PROLONG: the residual of the prolonged coarse iterate itself -- there is no x operand (lattice.h)
+  constexpr bool kProlongOnly = MODE == M_RESID && FUSE == F_PROLONG;
+  const TV* __restrict__ px = kProlongOnly ? nullptr : src + i0 * Bp;
+  TV* __restrict__ pxo = kProlongOnly ? (TV*)ex.p_out + i0 * Bp : nullptr;   // ... and the strip stores that iterate
   const TV* __restrict__ pb = bvec ? bvec + i0 * Bp : nullptr;
   TV* __restrict__ po = (out && FUSE != F_RESTRICT) ? out + i0 * Bp : nullptr;
   const i64 rowV = (i64)W * Bv, rowX = (i64)W * Bp;
@@ -118,6 +121,8 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
         v = (double)(TA)v;
       } else if (kRupd) {
         v = (double)(ppi + roff + (i64)dq[q] * Bp)[lb];
+      } else if (kProlongOnly) {
+        v = 0.0;
       } else {
         v = (double)(xrow + (i64)dq[q] * Bp)[lb];
       }
@@ -129,7 +134,8 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
         else
           corr = (row & 1) ? 0.5 * (ce[q / 2 + 1] + ce2[q / 2]) : 0.5 * (ce[q / 2] + ce[q / 2 + 1]);
         if (ex.bc[(i64)row * W + c0w + dq[q]]) corr = 0.0;
-        v += corr;
+        if (kProlongOnly) v = (double)(TV)corr;   // the STORED value of the transfer kernels: the pass reads what they wrote
+        else v += corr;
       }
       dst[q] = okq[q] ? v : 0.0;
     }
@@ -248,6 +254,7 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
             (ex.r32 + ig)[lb] = hi;
             __builtin_nontemporal_store(lo, &(ex.rlo + ig)[lb]);
           }
+          if (kProlongOnly) (pxo + o)[lb] = (TV)xc[q];
           if (po) (po + o)[lb] = (TV)res;
           if (FUSE == F_NONE && sizeof(TV) == 8 && ex.r32) (ex.r32 + ((i64)row * W + c0w + k) * Bp)[lb] = (float)(res * rsc);
           if (plain_resid(MODE, FUSE) && ex.dot_bx) {
@@ -307,7 +314,8 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
     for (int k = 0; k < RW + 1; ++k) d3p[k] = d3c[k];
     p0 += rowV; p1 += rowV; p2 += rowV; p3 += rowV;
     if (SHIFT) psh += W;
-    px += rowX;
+    if (!kProlongOnly) px += rowX;
+    else pxo += rowX;
     if (pb) pb += rowX;
     if (po) po += rowX;
     if (is_pupd(FUSE)) { pz += rowX; ppi += rowX; ppo += rowX; if (FUSE == F_PUPD && pxx) pxx += rowX; }
@@ -411,6 +419,10 @@ void launch_strip(const Level& L, int Bv, const double* scale, const TV* xin, co
     const double tv = sizeof(TV), ta = sizeof(TA);
     double bpn;
     if (MODE == M_JACOBI) bpn = (XFROMB ? 2.0 : 3.0) * tv + (FUSE == F_PROLONG ? 0.25 * tv : 0.0);
+    else if (MODE == M_RESID && FUSE == F_PROLONG) {   // rhs read, P e and the residual written; the coarse vector read once
+      bpn = 2.0 * tv + (out ? tv : 0.0);
+      diffhe::account(tv * (double)ex.cW * (L.ny / 2 + 1) * Bp);
+    }
     else if (MODE == M_RESID) bpn = 2.0 * tv + (FUSE == F_RESTRICT ? 0.25 * tv : (out ? tv : 0.0) + (ex.r32 ? 4.0 : 0.0) + (FUSE == F_RPAIR ? 4.0 : 0.0));
     else if (is_pupd(FUSE)) bpn = (ex.first ? 2.0 * ta : 3.0 * ta) + (out ? 8.0 : 0.0) + ((FUSE == F_PUPD && ex.x) ? 16.0 : 0.0);
     else if (FUSE == F_RUPD) bpn = ta + 16.0 + (ex.r32 ? 4.0 : 0.0);   // p; r read and written; its fp32 copy

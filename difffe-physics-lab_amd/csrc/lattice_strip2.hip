@@ -295,7 +295,8 @@ __global__ __launch_bounds__(256) void dia_strip2_kernel(Level L, const double* 
 // fp64 from the stored p, F_RUPD).  The fp32 stencil only enters the STEP LENGTH alpha = r.z / p.Ap: x += alpha p and
 // r -= alpha A p use the same alpha and the exact (fp64) A p, so r = b - A x holds to fp64 whatever alpha is, and an
 // error delta in alpha costs delta^2 of the energy reduction of the step (the minimum of a parabola).
-template <typename VT, int ND, int RW, bool EDGE>
+// STORE = false (first step only): z already lives in p's ring slot, the direction is read in place and not stored.
+template <typename VT, int ND, int RW, bool EDGE, bool STORE>
 __device__ __forceinline__ void cgstep2_body(const Level& L, VT beta, bool first, const float* __restrict__ z,
                                              const float* __restrict__ pin, float* __restrict__ pout, int Bp, unsigned lb,
                                              int c0w, int r0, int r1, Acc& acc) {
@@ -339,7 +340,7 @@ __device__ __forceinline__ void cgstep2_body(const Level& L, VT beta, bool first
     p_row(row + 1, a2);
     k1_row<VT, RW, ND, EDGE>(cf, n, W, row, c0w, a0, a1, a2, [&](int k, VT kx, float, float) {
       if (!EDGE || c0w + k < W) {
-        __builtin_nontemporal_store(a1[k + 1], (VT*)(pp + (i64)k * Bp + lb));
+        if (STORE) __builtin_nontemporal_store(a1[k + 1], (VT*)(pp + (i64)k * Bp + lb));
         VLane<VT>::dot(acc, a1[k + 1], kx);
       }
     });
@@ -349,7 +350,7 @@ __device__ __forceinline__ void cgstep2_body(const Level& L, VT beta, bool first
   }
 }
 
-template <typename VT, int ND, int RW, int MW>
+template <typename VT, int ND, int RW, int MW, bool STORE = true>
 __global__ __launch_bounds__(256, MW) void cgstep2_kernel(Level L, const double* __restrict__ scale,
                                                            const double* __restrict__ beta, int first,
                                                            const float* __restrict__ z, const float* __restrict__ pin,
@@ -370,8 +371,8 @@ __global__ __launch_bounds__(256, MW) void cgstep2_kernel(Level L, const double*
   if (c0w < L.W && r0 < r1) {
     const VT bt = first ? VLane<VT>::zero() : VLane<VT>::from_scale(beta, lb);
     const bool edge = c0w - 1 < 0 || c0w + RW > L.W - 1 || r0 - 1 < 0 || r1 > nyp - 1;
-    if (edge) cgstep2_body<VT, ND, RW, true>(L, bt, first != 0, z, pin, pout, Bp, lb, c0w, r0, r1, acc);
-    else cgstep2_body<VT, ND, RW, false>(L, bt, first != 0, z, pin, pout, Bp, lb, c0w, r0, r1, acc);
+    if (edge) cgstep2_body<VT, ND, RW, true, STORE>(L, bt, first != 0, z, pin, pout, Bp, lb, c0w, r0, r1, acc);
+    else cgstep2_body<VT, ND, RW, false, STORE>(L, bt, first != 0, z, pin, pout, Bp, lb, c0w, r0, r1, acc);
   }
 #pragma unroll
   for (int q = 0; q < SPL; ++q) {
@@ -387,9 +388,17 @@ __global__ __launch_bounds__(256, MW) void cgstep2_kernel(Level L, const double*
 void launch_cgstep2(const Level& L, const double* scale, const double* beta, int first, const float* z, const float* pin,
                     float* pout, double* part, int Bp, const StripGeom& g, int spl, hipStream_t st) {
   const dim3 grid(g.ncb * g.nrc, Bp / (spl * kWave));
-  diffhe::account((first ? 8.0 : 12.0) * (double)L.n * Bp);
-#define CG2(VT_, ND_, MW_) hipLaunchKernelGGL((cgstep2_kernel<VT_, ND_, 4, MW_>), grid, dim3(256), 0, st, L, scale, \
-                                              beta, first, z, pin, pout, part, Bp, g.ncb, g.TR)
+  const bool in_place = first && pout == z;   // p0 = z0 is in its slot already: read only
+  diffhe::account((in_place ? 4.0 : first ? 8.0 : 12.0) * (double)L.n * Bp);
+#define CG2(VT_, ND_, MW_)                                                                                             \
+  do {                                                                                                                 \
+    if (in_place)                                                                                                      \
+      hipLaunchKernelGGL((cgstep2_kernel<VT_, ND_, 4, MW_, false>), grid, dim3(256), 0, st, L, scale, beta, first, z, pin, \
+                         pout, part, Bp, g.ncb, g.TR);                                                                 \
+    else                                                                                                               \
+      hipLaunchKernelGGL((cgstep2_kernel<VT_, ND_, 4, MW_>), grid, dim3(256), 0, st, L, scale, beta, first, z, pin, pout, \
+                         part, Bp, g.ncb, g.TR);                                                                       \
+  } while (0)
   // 8 waves per SIMD: 0.70 ms at 1024^2 x 256 (6: 0.75, 4: 0.75; the one-sample fp64 strip: 0.87; gpurun_out/r6e)
   if (spl == 2) { if (L.nd == 3) CG2(v2f, 3, 8); else CG2(v2f, 4, 8); }
   else { if (L.nd == 3) CG2(float, 3, 8); else CG2(float, 4, 8); }

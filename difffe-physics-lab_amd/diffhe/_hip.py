@@ -180,6 +180,7 @@ PCG_PRE2 = 512
 PCG_RESID_FP64 = 1 << 10   # DIFFHE_PCG_RESID_FP64
 PCG_RESID_KEEP_LO = 1 << 11   # DIFFHE_PCG_RESID_KEEP_LO
 PCG_TRUST_ITS_SHIFT = 12    # DIFFHE_PCG_TRUST_ITS_SHIFT: four bits
+PCG_SPLIT_START = 1 << 16   # DIFFHE_PCG_SPLIT_START
 
 
 def lib():

@@ -492,6 +492,7 @@ class _Engine:
                  | (0 if int(mg.get("resid_pair", 1)) else _hip.PCG_RESID_FP64)
                  | (0 if int(mg.get("resid_drop_lo", 1)) else _hip.PCG_RESID_KEEP_LO)
                  | ((int(mg.get("trust_its", 0)) & 15) << _hip.PCG_TRUST_ITS_SHIFT)   # development, tests
+                 | (_hip.PCG_SPLIT_START if int(mg.get("split_start", 0)) else 0)    # A/B runs, tests
                  | (_hip.PCG_CLOSED_FP32_STEP if closed_step else 0))
         # a multigrid-preconditioned CG that has not converged in a few hundred iterations never will:
         # bound the loop so a defect surfaces as `not_converged` instead of minutes of GPU time

@@ -303,6 +303,11 @@ typedef struct diffhe_mg_level {
                                           20 B per node and sample (status_host[3]); A/B runs, tests */
 #define DIFFHE_PCG_TRUST_ITS_SHIFT (12) /* four bits, development and tests only: k > 0 trusts the energy rule for k iterations
                                           instead of the 10 (+ 1 per decade of tol_energy below 1e-11) of the default, 0 */
+#define DIFFHE_PCG_SPLIT_START (1 << 16) /* keep the separate passes around the full-multigrid start of an fp32 solve with a
+                                          batch-shared matrix: prolongation, then residual; conversion of the right-hand
+                                          side, then its restriction; z0 copied into the direction ring by the first CG step.
+                                          Default: each pair is one pass and z0 is written where p0 lives -- 4 B per node
+                                          and sample less each, the same stored values bit for bit; A/B runs, tests */
 
 /* Batched CG preconditioned by one multigrid V(nu,nu) cycle (weighted Jacobi with the
  * per-sweep damping factors omegas_host[0..nu-1] -- Chebyshev weights; post-smoothing runs
