@@ -1,0 +1,349 @@
+// Stress recovery of a linear-elastic solve (ours: the reference has scalar unknowns only): element stresses
+// sigma = E (2 mu1 eps + lam1 tr(eps) I) in Voigt components, the von Mises stress, and their adjoint with respect to the
+// displacement u and the Young's modulus E (definitions: include/diffhe_stress.h).  u is the full displacement, so no
+// Dirichlet data is read; the gradient table has aniso.hip's layout and, unlike that table, the true sign of grad phi_p
+// in every element: everything here is linear in it.
+//
+// Data layout as in elastic.hip: dof-major, batch innermost, lanes over samples (node_map), so element data -- node
+// ids, gradients, list entries -- is wave-uniform and every access is one contiguous segment; Bp = 1 spreads elements
+// over lanes.  fp64, no atomics anywhere: every sum has a fixed order, results are bitwise reproducible.
+//
+// The adjoint is an element pass and a node pass.  The element pass runs on the element loop of element_grad.h with the
+// form below (NC = 1: dE); the form writes the tensor T of the element, nc numbers per element and sample, as a side
+// product, and the node pass gathers T g_p over the per-node incidence list (the list of shape.hip's gather).  T costs
+// nc m values per sample where the (d+1) d vertex contributions of shape.hip's form would cost (d+1) d m.
+#include "common.h"
+#include "diffhe_stress.h"
+#include "element_grad.h"
+
+namespace {
+
+using namespace diffhe;
+typedef long long i64;
+
+// Voigt component k of a symmetric DIM x DIM tensor: (row, column); the first DIM are the diagonal.
+template <int DIM>
+__device__ __forceinline__ constexpr int voigt_row(int k) {
+  return k < DIM ? k : (DIM == 2 ? 0 : (k == 3 ? 1 : 0));
+}
+template <int DIM>
+__device__ __forceinline__ constexpr int voigt_col(int k) {
+  return k < DIM ? k : (DIM == 2 ? 1 : (k == 5 ? 1 : 2));
+}
+
+// What both directions read of an element and a sample.
+template <int DIM>
+struct StressElement {
+  static constexpr int NPE = DIM + 1, NC = DIM * (DIM + 1) / 2;
+  const int* __restrict__ elems;
+  const double* __restrict__ gtab;
+  double lam1, mu1, nu_z;
+  const double* __restrict__ u;
+  const double* __restrict__ E;
+  i64 ese, esb;
+  int m;
+
+  struct Elem {
+    int e;
+    int node[NPE];
+    double G[NPE][DIM];
+  };
+
+  __device__ __forceinline__ void load(int e, Elem& el) const {
+    el.e = e;
+#pragma unroll
+    for (int p = 0; p < NPE; ++p) {
+      el.node[p] = elems[(i64)p * m + e];
+#pragma unroll
+      for (int t = 0; t < DIM; ++t) el.G[p][t] = gtab[(i64)(p * DIM + t) * m + e];
+    }
+  }
+
+  // the unit stress s (NC) of sample b from H[a][t] = sum_p u[(p, a)] g_p[t]
+  __device__ __forceinline__ void unit_stress(const Elem& el, int Bp, int b, double* s) const {
+    double H[DIM][DIM];
+#pragma unroll
+    for (int a = 0; a < DIM; ++a)
+#pragma unroll
+      for (int t = 0; t < DIM; ++t) H[a][t] = 0.0;
+#pragma unroll
+    for (int p = 0; p < NPE; ++p)
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) {
+        const double up = u[((i64)el.node[p] * DIM + a) * Bp + b];
+#pragma unroll
+        for (int t = 0; t < DIM; ++t) H[a][t] = fma(up, el.G[p][t], H[a][t]);
+      }
+    double tr = 0.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) tr += H[a][a];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const int a = voigt_row<DIM>(k), t = voigt_col<DIM>(k);
+      s[k] = k < DIM ? fma(2.0 * mu1, H[a][a], lam1 * tr) : mu1 * (H[a][t] + H[t][a]);
+    }
+  }
+
+  __device__ __forceinline__ double modulus(int e, int b) const { return E[(i64)e * ese + (i64)b * esb]; }
+};
+
+// The three normal stresses of sigma (NC): in 2D the third is nu_z (sigma_xx + sigma_yy).
+template <int DIM>
+__device__ __forceinline__ void normal_stresses(const double* sg, double nu_z, double* nn) {
+  nn[0] = sg[0];
+  nn[1] = sg[1];
+  nn[2] = DIM == 2 ? nu_z * (sg[0] + sg[1]) : sg[2];
+}
+
+template <int DIM>
+__device__ __forceinline__ double von_mises(const double* sg, const double* nn) {
+  constexpr int NC = DIM * (DIM + 1) / 2;
+  const double d0 = nn[0] - nn[1], d1 = nn[1] - nn[2], d2 = nn[2] - nn[0];
+  double sh = 0.0;
+#pragma unroll
+  for (int k = DIM; k < NC; ++k) sh = fma(sg[k], sg[k], sh);
+  return sqrt(fma(0.5, fma(d0, d0, fma(d1, d1, d2 * d2)), 3.0 * sh));
+}
+
+// ---------------------------------------------------------------------------------------
+// sigma at c*osc + e*ose + b and / or vm (m, Bp); a NULL output is neither computed nor stored.
+// ---------------------------------------------------------------------------------------
+template <int DIM>
+__global__ __launch_bounds__(256) void stress_eval_kernel(const StressElement<DIM> el_of, int Bp,
+                                                           double* __restrict__ sigma, i64 osc, i64 ose,
+                                                           double* __restrict__ vm) {
+  constexpr int NC = DIM * (DIM + 1) / 2;
+  const NodeMap nm = node_map(Bp);  // "nodes" are elements here
+  if (nm.b >= Bp) return;
+  for (int e = nm.node0; e < el_of.m; e += nm.stride) {
+    typename StressElement<DIM>::Elem el;
+    double sg[NC];
+    el_of.load(e, el);
+    el_of.unit_stress(el, Bp, nm.b, sg);
+    const double Ee = el_of.modulus(e, nm.b);
+#pragma unroll
+    for (int k = 0; k < NC; ++k) sg[k] *= Ee;
+    if (sigma) {
+#pragma unroll
+      for (int k = 0; k < NC; ++k) sigma[k * osc + e * ose + nm.b] = sg[k];
+    }
+    if (vm) {
+      double nn[3];
+      normal_stresses<DIM>(sg, el_of.nu_z, nn);
+      vm[(i64)e * Bp + nm.b] = von_mises<DIM>(sg, nn);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// The element pass of the adjoint as a form of element_grad.h: out[0] = dE[e, b] = sum_k c_k s_k with the combined
+// cotangent c = sigma_bar + vm_bar d vm / d sigma, and, where `work` is given, T = E (2 mu1 sym(C) + lam1 tr(C) I) to
+// work (NC, m, Bp).  Samples b >= B: dE = 0, T = 0, no cotangent read.
+// ---------------------------------------------------------------------------------------
+template <int DIM>
+struct StressAdjointForm {
+  static constexpr int NC = 1;
+  static constexpr int NV = DIM * (DIM + 1) / 2;
+  typedef typename StressElement<DIM>::Elem Elem;
+  StressElement<DIM> el_of;
+  const double* __restrict__ sigma_bar;
+  i64 osc, ose;
+  const double* __restrict__ vm_bar;
+  double* __restrict__ work;
+  int B;
+
+  __device__ __forceinline__ void load(int e, Elem& el) const { el_of.load(e, el); }
+
+  __device__ __forceinline__ void eval(const Elem& el, int Bp, int b, double* out) const {
+    const i64 mb = (i64)el_of.m * Bp, at = (i64)el.e * Bp + b;
+    if (b >= B) {
+      out[0] = 0.0;
+      if (work) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) work[k * mb + at] = 0.0;
+      }
+      return;
+    }
+    double s[NV], c[NV];
+    el_of.unit_stress(el, Bp, b, s);
+    const double Ee = el_of.modulus(el.e, b);
+#pragma unroll
+    for (int k = 0; k < NV; ++k) c[k] = sigma_bar ? sigma_bar[k * osc + el.e * ose + b] : 0.0;
+    if (vm_bar) {
+      double sg[NV], nn[3];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) sg[k] = Ee * s[k];
+      normal_stresses<DIM>(sg, el_of.nu_z, nn);
+      const double vm = von_mises<DIM>(sg, nn);
+      if (vm > 0.0) {                                   // d vm / d sigma = 0 where vm == 0
+        const double w = vm_bar[at] / vm;
+        const double mean = ((nn[0] + nn[1]) + nn[2]) / 3.0;
+        double cn[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) cn[i] = 1.5 * (nn[i] - mean) * w;
+#pragma unroll
+        for (int i = 0; i < DIM; ++i) c[i] += cn[i];
+        if (DIM == 2) {                                 // sigma_zz = nu_z (sigma_xx + sigma_yy)
+          c[0] = fma(el_of.nu_z, cn[2], c[0]);
+          c[1] = fma(el_of.nu_z, cn[2], c[1]);
+        }
+#pragma unroll
+        for (int k = DIM; k < NV; ++k) c[k] = fma(3.0 * sg[k], w, c[k]);
+      }
+    }
+    double de = 0.0;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) de = fma(c[k], s[k], de);
+    out[0] = de;
+    if (work) {
+      double tr = 0.0;
+#pragma unroll
+      for (int i = 0; i < DIM; ++i) tr += c[i];
+#pragma unroll
+      for (int k = 0; k < NV; ++k)
+        work[k * mb + at] = Ee * (k < DIM ? fma(2.0 * el_of.mu1, c[k], el_of.lam1 * tr) : el_of.mu1 * c[k]);
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------------------
+// Node pass: u_bar[(i, a), b] = sum over the incidence list of node i (codes e * NPE + p, element order) of
+// sum_t T_e[a][t] g_p[t], T (NC, m, Bp).  Samples b >= B: 0.
+// ---------------------------------------------------------------------------------------
+template <int DIM>
+__global__ __launch_bounds__(256) void stress_node_kernel(const int* __restrict__ inc_ptr, const int* __restrict__ inc,
+                                                           const double* __restrict__ gtab,
+                                                           const double* __restrict__ work, int n, int m, int B, int Bp,
+                                                           double* __restrict__ u_bar) {
+  constexpr int NPE = DIM + 1, NC = DIM * (DIM + 1) / 2;
+  const NodeMap nm = node_map(Bp);
+  if (nm.b >= Bp) return;
+  const i64 mb = (i64)m * Bp;
+  for (int i = nm.node0; i < n; i += nm.stride) {
+    double acc[DIM];
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) acc[a] = 0.0;
+    if (nm.b < B)
+      for (int j = inc_ptr[i]; j < inc_ptr[i + 1]; ++j) {
+        const int code = inc[j];
+        const int e = code / NPE, p = code - e * NPE;
+        double T[DIM][DIM];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+          const double v = work[k * mb + (i64)e * Bp + nm.b];
+          T[voigt_row<DIM>(k)][voigt_col<DIM>(k)] = v;
+          T[voigt_col<DIM>(k)][voigt_row<DIM>(k)] = v;
+        }
+#pragma unroll
+        for (int t = 0; t < DIM; ++t) {
+          const double g = gtab[(i64)(p * DIM + t) * m + e];
+#pragma unroll
+          for (int a = 0; a < DIM; ++a) acc[a] = fma(T[a][t], g, acc[a]);
+        }
+      }
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) u_bar[((i64)i * DIM + a) * Bp + nm.b] = acc[a];
+  }
+}
+
+template <int DIM>
+StressElement<DIM> element_of(const int* elems, const double* gtab, double lam1, double mu1, double nu_z, const double* u,
+                              const double* E, i64 e_se, i64 e_sb, int m) {
+  return StressElement<DIM>{elems, gtab, lam1, mu1, DIM == 2 ? nu_z : 0.0, u, E, e_se, e_sb, m};
+}
+
+// what every entry refuses: pointers, dim, sizes, the E strides, the int32 codes e * npe + p
+bool bad_common(const int* elems, const double* gtab, int dim, const double* u, const double* E, i64 e_se, i64 e_sb, int n,
+                int m) {
+  return !elems || !gtab || !u || !E || (dim != 2 && dim != 3) || n < 1 || m < 1 || e_se < 0 || e_sb < 0 ||
+         (i64)m * (dim + 1) >= (1LL << 31);
+}
+
+// bytes of E as the kernels read it: a field per sample, one field, one number per sample, one number
+double modulus_bytes(i64 e_se, i64 e_sb, int m, int Bp) { return 8.0 * (e_se ? (double)m : 1.0) * (e_sb ? (double)Bp : 1.0); }
+
+}  // namespace
+
+// =========================================================================================
+// C ABI (include/diffhe_stress.h)
+// =========================================================================================
+extern "C" int diffhe_stress_eval(const int* elems, const double* gtab, int dim, double lam1, double mu1, double nu_z,
+                                  const double* u, const double* E, long long e_se, long long e_sb, int n, int m, int Bp,
+                                  double* sigma, long long osc, long long ose, double* vm, void* stream) {
+  if (bad_common(elems, gtab, dim, u, E, e_se, e_sb, n, m) || (!sigma && !vm) || (sigma && (osc < 1 || ose < 1)))
+    return DIFFHE_E_BADARG;
+  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
+  const int nc = dim * (dim + 1) / 2;
+  // u once per dof, E, the outputs
+  diffhe::account(8.0 * Bp * ((double)dim * n + (sigma ? (double)nc * m : 0.0) + (vm ? (double)m : 0.0)) +
+                  modulus_bytes(e_se, e_sb, m, Bp));
+  const dim3 grid = diffhe::node_grid(m, Bp);
+  if (dim == 2)
+    hipLaunchKernelGGL(stress_eval_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream,
+                       element_of<2>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), Bp, sigma, osc, ose, vm);
+  else
+    hipLaunchKernelGGL(stress_eval_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream,
+                       element_of<3>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), Bp, sigma, osc, ose, vm);
+  return diffhe::check_launch();
+}
+
+extern "C" int diffhe_stress_adjoint(const int* elems, const double* gtab, int dim, double lam1, double mu1, double nu_z,
+                                     const double* u, const double* E, long long e_se, long long e_sb,
+                                     const double* sigma_bar, long long osc, long long ose, const double* vm_bar,
+                                     const int* inc_ptr, const int* inc, int n, int m, int B, int Bp, double* work,
+                                     double* u_bar, double* de_e, double* de_part, double* de_sum, void* stream) {
+  if (bad_common(elems, gtab, dim, u, E, e_se, e_sb, n, m) || (!sigma_bar && !vm_bar) ||
+      (sigma_bar && (osc < 1 || ose < 1)) || B < 1 || B > Bp)
+    return DIFFHE_E_BADARG;
+  const bool nodes = u_bar != nullptr;
+  if ((work != nullptr) != nodes || (inc_ptr != nullptr) != nodes || (inc != nullptr) != nodes) return DIFFHE_E_BADARG;
+  if ((de_part == nullptr) != (de_sum == nullptr) || (!nodes && !de_e && !de_part)) return DIFFHE_E_BADARG;
+  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
+  const int nc = dim * (dim + 1) / 2;
+  // element pass: u once per dof, E, the cotangents, T and dE per element
+  const double bytes = 8.0 * Bp * ((double)dim * n + (sigma_bar ? (double)nc * m : 0.0) + (vm_bar ? (double)m : 0.0) +
+                                   (nodes ? (double)nc * m : 0.0) + (de_e ? (double)m : 0.0)) +
+                       modulus_bytes(e_se, e_sb, m, Bp);
+  int status;
+  if (dim == 2)
+    status = diffhe::launch_element_grad(
+        StressAdjointForm<2>{element_of<2>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), sigma_bar, osc, ose, vm_bar,
+                             work, B},
+        m, Bp, de_e, 0, Bp, de_part, de_sum, bytes, stream);
+  else
+    status = diffhe::launch_element_grad(
+        StressAdjointForm<3>{element_of<3>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), sigma_bar, osc, ose, vm_bar,
+                             work, B},
+        m, Bp, de_e, 0, Bp, de_part, de_sum, bytes, stream);
+  if (status != DIFFHE_OK || !nodes) return status;
+  diffhe::account(8.0 * Bp * ((double)nc * m + (double)dim * n));   // node pass: T once, u_bar once per dof
+  const dim3 grid = diffhe::node_grid(n, Bp);
+  if (dim == 2)
+    hipLaunchKernelGGL(stress_node_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, inc_ptr, inc, gtab,
+                       (const double*)work, n, m, B, Bp, u_bar);
+  else
+    hipLaunchKernelGGL(stress_node_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, inc_ptr, inc, gtab,
+                       (const double*)work, n, m, B, Bp, u_bar);
+  return diffhe::check_launch();
+}
+
+extern "C" int diffhe_stress_adjoint_shared(const int* elems, const double* gtab, int dim, double lam1, double mu1,
+                                            double nu_z, const double* u, const double* E, long long e_se, long long e_sb,
+                                            const double* sigma_bar, long long osc, long long ose, const double* vm_bar,
+                                            int n, int m, int B, int Bp, double* de, void* stream) {
+  if (bad_common(elems, gtab, dim, u, E, e_se, e_sb, n, m) || (!sigma_bar && !vm_bar) ||
+      (sigma_bar && (osc < 1 || ose < 1)) || !de || B < 1 || B > Bp)
+    return DIFFHE_E_BADARG;
+  const int nc = dim * (dim + 1) / 2;
+  const double bytes = 8.0 * (Bp * ((double)dim * n + (sigma_bar ? (double)nc * m : 0.0) + (vm_bar ? (double)m : 0.0)) +
+                              (double)m) + modulus_bytes(e_se, e_sb, m, Bp);
+  if (dim == 2)
+    return diffhe::launch_element_grad_shared(
+        StressAdjointForm<2>{element_of<2>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), sigma_bar, osc, ose, vm_bar,
+                             nullptr, B},
+        m, B, Bp, de, 0, 1, bytes, stream);
+  return diffhe::launch_element_grad_shared(
+      StressAdjointForm<3>{element_of<3>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), sigma_bar, osc, ose, vm_bar,
+                           nullptr, B},
+      m, B, Bp, de, 0, 1, bytes, stream);
+}

@@ -14,7 +14,8 @@ gradients to the film coefficient, the ambient value and the flux, also exported
 the smallest eigenpairs of K phi = lambda M_L phi per sample with d lambda / d kappa, also exported here;
 `diffhe.elastic`: `ElasticFESolver`, linear elasticity on P1 triangles and tetrahedra -- the first vector-valued problem,
 d displacement components per node -- with gradients to a Young's modulus per element, the body force and the nodal
-load, also exported here (its kernels are declared in include/diffhe_elastic.h); `diffhe._hip`: the ctypes binding).
+load, also exported here (its kernels are declared in include/diffhe_elastic.h), and its `stress` / `von_mises` with
+gradients to u and E and `pnorm` (kernels declared in include/diffhe_stress.h); `diffhe._hip`: the ctypes binding).
 """
 from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, loss as _loss, mesh as _mesh, neural as _neural, robin as _robin, shape as _shape,
                solver as _solver)

@@ -1,4 +1,4 @@
-"""ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h).
+"""ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h, include/diffhe_stress.h).
 
 The library is built in-tree by `__graft_entry__.build()` /
 `make -C difffe-physics-lab_amd/csrc`.  There is NO fallback: if the library or a
@@ -158,6 +158,16 @@ ELASTIC_SIGNATURES = {
     "diffhe_elast_grad_shared": (_S, [_PI, _PD, _PD, _I, _D, _D, _PD, _PD, _PD, _I, _I, _I, _I, _PD, _PV]),
 }
 
+# name -> (restype, argtypes) of every symbol of include/diffhe_stress.h, the library's third header (stress recovery of
+# elastic solves, csrc/stress.hip): bound by the same loop (tests/test_stress.py holds this table against that header)
+STRESS_SIGNATURES = {
+    "diffhe_stress_eval": (_S, [_PI, _PD, _I, _D, _D, _D, _PD, _PD, _L, _L, _I, _I, _I, _PD, _L, _L, _PD, _PV]),
+    "diffhe_stress_adjoint": (_S, [_PI, _PD, _I, _D, _D, _D, _PD, _PD, _L, _L, _PD, _L, _L, _PD, _PI, _PI, _I, _I, _I, _I,
+                                   _PD, _PD, _PD, _PD, _PD, _PV]),
+    "diffhe_stress_adjoint_shared": (_S, [_PI, _PD, _I, _D, _D, _D, _PD, _PD, _L, _L, _PD, _L, _L, _PD, _I, _I, _I, _I,
+                                          _PD, _PV]),
+}
+
 _lib = None
 
 
@@ -192,7 +202,7 @@ def lib():
                 f"libdiffhe_hip.so not found at {LIB_PATH}: build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in (*SIGNATURES.items(), *ELASTIC_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *ELASTIC_SIGNATURES.items(), *STRESS_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = (_I if res is _S else res), args
             if res is _S:

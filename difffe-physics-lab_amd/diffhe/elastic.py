@@ -35,6 +35,27 @@ translations exactly.  It is built from the unit-E operator and cached per (plan
 carries `amg.jacobi_bound` of its unit operator for the cycle's Jacobi weights (elastic operators have positive
 off-diagonals).  The coarse space has no rotations ("Elasticity").
 
+Stress recovery (csrc/stress.hip, include/diffhe_stress.h): `solver.stress(u, E=None)`, `solver.von_mises(u, E=None)`,
+`solver.stress_and_von_mises(u, E=None)` and `pnorm(vm, p)`, differentiable in u and E.  Per element e and sample b, with
+the element-constant displacement gradient H[a][t] = sum_p u[(p, a)] g_p[t] and eps = (H + H^T) / 2:
+
+    unit stress   s = 2 mu' eps + lambda' tr(eps) I,   (lambda', mu') = lame_unit(nu, dim, plane)
+    stress        sigma = E_e s
+    Voigt order   diffhe.aniso's: nc = 3, (xx, yy, xy) in 2D; nc = 6, (xx, yy, zz, yz, xz, xy) in 3D.  A shear component
+                  is the tensor component itself, not doubled; its cotangent is the derivative with respect to that one
+                  number.
+    out of plane  plane stress: sigma_zz = 0; plane strain: sigma_zz = E lambda' tr(eps) = nu (sigma_xx + sigma_yy).
+                  `stress` returns the in-plane components only, `von_mises` includes sigma_zz.
+    von Mises     vm^2 = 1/2 [(s_xx - s_yy)^2 + (s_yy - s_zz)^2 + (s_zz - s_xx)^2] + 3 (s_xy^2 + s_yz^2 + s_xz^2) of sigma,
+                  absent components zero; d vm / d sigma = (3/2) dev(sigma) / vm, defined as 0 where vm == 0: no NaN or
+                  Inf leaves the kernels.
+
+u is the full displacement as `forward` returns it, prescribed values included: the evaluation is a pure function of
+(u, E, mesh, nu, plane) and reads no Dirichlet data.  An explicit E evaluates the stress with another modulus than the
+solve used (the relaxed stress rho^q E_0 D eps of stress-constrained SIMP); the batch rules are those of E above, and an
+unbatched u with a batched E is broadcast.  The gradients come from one element pass (dL/dE, and a symmetric tensor per
+element) and one node pass over the per-node incidence list (dL/du), in fixed orders: bitwise reproducible.
+
 Not implemented (NotImplementedError): 1D meshes, P2 meshes, backward with create_graph=True, a per-call `dirichlet=`,
 node gradients (mesh.nodes requiring grad), Robin / flux data (h=, u_inf=, flux=); `amg=dict(strength=...)`.
 """
@@ -54,7 +75,7 @@ from .plan import get_plan, padded_batch, valid_batch_pad, _stream
 from .solver import (K_ELEM, K_SAMPLE_ELEM, SolveInfo, _Engine, _SOLVERS, _call_options, _kappa_grad, _kappa_layout,
                      _like_grads, _fake_grads, _register_state, _resolve_device, _run_call, _state_of, _tie_state)
 
-__all__ = ("ElasticFESolver", "lame_unit", "parse_fixed", "dof_pattern")
+__all__ = ("ElasticFESolver", "lame_unit", "parse_fixed", "dof_pattern", "pnorm")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -440,6 +461,213 @@ def _backward(ctx, grad_u, _grad_token):
 torch.library.register_autograd("diffhe::elastic_solve", _backward, setup_context=_setup_context)
 
 
+# ---------------------------------------------------------------------------------------------
+# Stress recovery: diffhe::elastic_stress / diffhe::elastic_stress_backward (csrc/stress.hip, include/diffhe_stress.h).
+# A pure function of (u, E) for the solver registered under `handle`: no adjoint state, backward recomputes from u and E.
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class _StressCall:
+    """One evaluation: the device views the kernels read and the facts both directions share."""
+    plan: object
+    eng: _Engine
+    B: int
+    Bp: int
+    mode: int
+    em: bool
+    batched: bool           # u came with a batch dimension
+    node_major: bool
+    head: tuple             # the leading arguments of the three entries, up to e_sb
+    nc: int
+
+    def rows_in(self, t: torch.Tensor, rows: int, batched: bool) -> torch.Tensor:
+        """(B, rows...) | (rows...) broadcast to the batch | node-major (rows..., B) -> (rows, Bp), padding samples zero."""
+        B, Bp, dev = self.B, self.Bp, self.plan.device
+        t = t.detach().to(dev, torch.float64)
+        if self.node_major:
+            src = t.reshape(rows, B)
+            if Bp == B and src.is_contiguous():
+                return src
+            out = torch.zeros((rows, Bp), dtype=torch.float64, device=dev)
+            out[:, :B] = src
+            return out
+        src = t.reshape(B, rows).contiguous() if batched else t.reshape(rows).contiguous()
+        return self.eng.to_node_major(src, B, Bp, rows)
+
+    def rows_out(self, x: torch.Tensor, rows: int) -> torch.Tensor:
+        """(rows, Bp) -> (B, rows), or node-major (rows, B): the kernel's array itself when B needs no padding."""
+        if self.node_major:
+            return x if self.Bp == self.B else x[:, :self.B].contiguous()
+        return self.eng.to_sample_major(x, self.B, self.Bp, rows)
+
+
+def _stress_batch(u: torch.Tensor, node_major: bool) -> Optional[int]:
+    return u.shape[2] if node_major else (u.shape[0] if u.dim() == 3 else None)
+
+
+def _stress_shapes(solver, u, E, node_major):
+    """-> (shape of sigma, shape of vm) for u and E as the op gets them."""
+    m, d = solver.mesh.n_elements, solver.mesh.dim
+    nc = d * (d + 1) // 2
+    B_u = _stress_batch(u, node_major)
+    _, B, _ = _kappa_layout(E, m, B_u, node_major)
+    if node_major:
+        return (m, nc, B), (m, B)
+    return ((B, m, nc), (B, m)) if (B_u is not None or B > 1) else ((m, nc), (m,))
+
+
+def _stress_call(solver: "ElasticFESolver", u, E, node_major) -> _StressCall:
+    plan = solver._plan()
+    d, n, m = plan.dim, plan.n, plan.m
+    B_u = _stress_batch(u, node_major)
+    mode, B, em = _kappa_layout(E, m, B_u, node_major)
+    Bp = padded_batch(B)
+    eng = _Engine(plan, 0.0, 0, 0, "gather")
+    call = _StressCall(plan, eng, B, Bp, mode, em, B_u is not None, node_major, (), d * (d + 1) // 2)
+    udev = call.rows_in(u, n * d, call.batched)
+    kdev, kse, ksb, _ = eng.kappa_device(E, mode, B, Bp, em=em)
+    gtab = plan.oriented_gradient_table()                        # the stress is linear in grad phi: its sign counts
+    nu_z = solver.nu if solver.plane == "strain" else 0.0       # sigma_zz = nu_z (sigma_xx + sigma_yy), 2D only
+    call.head = (plan.elems, gtab, d, solver._lam1, solver._mu1, nu_z, udev, kdev, kse, ksb)
+    return call
+
+
+def _stress_forward(solver, u, E, node_major, want_sigma, want_vm):
+    """(sigma, vm) in the caller's layout, None for the one not asked for: the kernel writes (m, nc, Bp) and (m, Bp)."""
+    call = _stress_call(solver, u, E, node_major)
+    plan, m, nc, B, Bp = call.plan, call.plan.m, call.nc, call.B, call.Bp
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=plan.device)  # noqa: E731
+    sigma, vm = (new(m * nc, Bp) if want_sigma else None), (new(m, Bp) if want_vm else None)
+    _hip.lib().diffhe_stress_eval(*call.head, plan.n, m, Bp, sigma, Bp, nc * Bp, vm, _stream(plan.device))
+    s_shape, v_shape = _stress_shapes(solver, u, E, node_major)
+    if sigma is not None:
+        sigma = call.rows_out(sigma, m * nc).reshape(s_shape).to(u.device)
+    if vm is not None:
+        vm = call.rows_out(vm, m).reshape(v_shape).to(u.device)
+    return sigma, vm
+
+
+def _stress_adjoint(solver, sigma_bar, vm_bar, u, E, node_major, need_u, need_e):
+    """(dL/du, dL/dE) in the shapes of u and E, None for the one not asked for.  One element pass feeds both where the
+    dE of the call is per sample; a field the batch shares takes its dE from the batch-summing entry."""
+    call = _stress_call(solver, u, E, node_major)
+    plan, eng, nc, B, Bp, mode = call.plan, call.eng, call.nc, call.B, call.Bp, call.mode
+    d, n, m = plan.dim, plan.n, plan.m
+    L, st = _hip.lib(), _stream(plan.device)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=plan.device)  # noqa: E731
+    sb = call.rows_in(sigma_bar, m * nc, True) if sigma_bar is not None else None
+    vb = call.rows_in(vm_bar, m, True) if vm_bar is not None else None
+    head = (*call.head, sb, Bp, nc * Bp, vb)
+    ubar = new(n * d, Bp) if need_u else None
+
+    def adjoint(nodes, de_e, part, total):
+        lists = plan.shape_incidence() if nodes else (None, None)
+        L.diffhe_stress_adjoint(*head, *lists, n, m, B, Bp, new(nc, m, Bp) if nodes else None, ubar if nodes else None,
+                                de_e, part, total, st)
+
+    grad_u = grad_e = None
+    fused = need_u and need_e and mode != K_ELEM
+    if need_e:
+        sums, de = eng.element_grad(mode, call.em, B, Bp, None,
+                                    lambda de_e, osc, ose, part, total: adjoint(fused, de_e, part, total),
+                                    lambda de, osc, ose: L.diffhe_stress_adjoint_shared(*head, n, m, B, Bp, de, st))
+        grad_e = _kappa_grad(mode, E.shape, sums, de).to(E.device)
+    if need_u:
+        if not fused:
+            adjoint(True, None, None, None)
+        du = call.rows_out(ubar, n * d)
+        if node_major:
+            grad_u = du.reshape(n, d, B)
+        else:
+            du = du.reshape(B, n, d)
+            grad_u = du if call.batched else du.sum(dim=0)
+        grad_u = grad_u.to(u.device)
+    return grad_u, grad_e
+
+
+@torch.library.custom_op("diffhe::elastic_stress", mutates_args=())
+def elastic_stress(u: torch.Tensor, E: torch.Tensor, handle: int, node_major: bool, want_sigma: bool,
+                   want_vm: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(sigma, vm) of the displacement u and the modulus E for the `ElasticFESolver` registered under `handle`; the
+    output not asked for comes back empty."""
+    sigma, vm = _stress_forward(_SOLVERS[handle], u, E, node_major, want_sigma, want_vm)
+    return (u.new_empty(0) if sigma is None else sigma), (u.new_empty(0) if vm is None else vm)
+
+
+@elastic_stress.register_fake
+def _elastic_stress_fake(u, E, handle, node_major, want_sigma, want_vm):
+    s_shape, v_shape = _stress_shapes(_SOLVERS[handle], u, E, node_major)
+    return (u.new_empty(s_shape if want_sigma else 0, dtype=torch.float64),
+            u.new_empty(v_shape if want_vm else 0, dtype=torch.float64))
+
+
+@torch.library.custom_op("diffhe::elastic_stress_backward", mutates_args=())
+def elastic_stress_backward(sigma_bar: torch.Tensor, vm_bar: torch.Tensor, u: torch.Tensor, E: torch.Tensor, handle: int,
+                            node_major: bool, need_u: bool, need_e: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dL/du, dL/dE) of `elastic_stress` for the cotangents of sigma and vm (empty = absent); unused ones come back
+    empty."""
+    grads = _stress_adjoint(_SOLVERS[handle], sigma_bar if sigma_bar.numel() else None,
+                            vm_bar if vm_bar.numel() else None, u, E, node_major, need_u, need_e)
+    return _like_grads(u, grads, (u, E))
+
+
+@elastic_stress_backward.register_fake
+def _elastic_stress_backward_fake(sigma_bar, vm_bar, u, E, handle, node_major, need_u, need_e):
+    return _fake_grads(u, (need_u, need_e), (u, E))
+
+
+def _stress_setup_context(ctx, inputs, output):
+    u, E, handle, node_major = inputs[:4]
+    ctx.handle, ctx.node_major = handle, bool(node_major)
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(u, E)
+
+
+def _stress_backward(ctx, grad_sigma, grad_vm):
+    if torch.is_grad_enabled():
+        raise NotImplementedError("diffhe: second-order derivatives of an elastic stress evaluation are not implemented "
+                                  "(backward with create_graph=True, diffhe.elastic)")
+    u, E = ctx.saved_tensors
+    need_u, need_e = (bool(v) for v in ctx.needs_input_grad[:2])
+    absent = lambda g: g is None or g.numel() == 0  # noqa: E731
+    if not (need_u or need_e) or (absent(grad_sigma) and absent(grad_vm)):
+        return (None,) * 6
+    empty = u.new_empty(0)
+    du, de = torch.ops.diffhe.elastic_stress_backward(empty if absent(grad_sigma) else grad_sigma.contiguous(),
+                                                      empty if absent(grad_vm) else grad_vm.contiguous(), u, E,
+                                                      ctx.handle, ctx.node_major, need_u, need_e)
+    return (du if need_u else None, de if need_e else None, None, None, None, None)
+
+
+torch.library.register_autograd("diffhe::elastic_stress", _stress_backward, setup_context=_stress_setup_context)
+
+
+def pnorm(vm: torch.Tensor, p: float = 8.0, weights: Optional[torch.Tensor] = None, dim: int = -1) -> torch.Tensor:
+    """The weighted p-mean (sum_e w_e vm_e^p / sum_e w_e)^(1/p) over the element axis `dim` of a non-negative field: the
+    last axis of `von_mises(..., layout="sample")`, the first (dim=0) of layout="node".  It lies between max(vm) m^(-1/p)
+    and max(vm).  Plain differentiable torch, evaluated as vmax (sum w (vm / vmax)^p / sum w)^(1/p) with vmax detached, so
+    that a large p neither overflows nor underflows; an all-zero row gives 0 with zero gradient."""
+    p = float(p)
+    if not p >= 1.0:
+        raise ValueError(f"pnorm needs p >= 1, got {p!r}")
+    if weights is None:
+        w = torch.ones((), dtype=vm.dtype, device=vm.device)
+        wsum = float(vm.shape[dim])
+    else:
+        w = torch.as_tensor(weights, dtype=vm.dtype, device=vm.device)
+        if w.dim() == 1 and vm.dim() > 1:
+            shape = [1] * vm.dim()
+            shape[dim] = w.shape[0]
+            w = w.reshape(shape)
+        wsum = w.sum(dim=dim if w.dim() == vm.dim() else -1)
+    vmax = vm.detach().abs().amax(dim=dim, keepdim=True)
+    live = vmax > 0
+    r = vm / torch.where(live, vmax, torch.ones_like(vmax))
+    s = (w * r ** p).sum(dim=dim) / wsum
+    live, vmax = live.squeeze(dim) & (s > 0), vmax.squeeze(dim)
+    root = torch.where(live, s, torch.ones_like(s)) ** (1.0 / p)
+    return torch.where(live, vmax * root, torch.zeros_like(root))
+
+
 class ElasticFESolver(nn.Module):
     """Displacement of a linear-elastic body per sample, differentiable with respect to the Young's modulus E per element,
     the body force f and the nodal load (see the module docstring).
@@ -540,3 +768,44 @@ class ElasticFESolver(nn.Module):
         save = torch.is_grad_enabled() and (E.requires_grad or f_in.requires_grad or load_in.requires_grad)
         u, _token = torch.ops.diffhe.elastic_solve(E, f_in, load_in, id(self), save, layout == "node")
         return u
+
+    # -- stress recovery ----------------------------------------------------------------------------
+    def _stress_op(self, u, E, layout: str, want_sigma: bool, want_vm: bool):
+        n, d = self.mesh.n_nodes, self.mesh.dim
+        if layout not in ("sample", "node"):
+            raise ValueError(f"Unknown layout: {layout!r}")
+        u = u if isinstance(u, torch.Tensor) else torch.as_tensor(u)
+        if layout == "node":
+            if u.dim() != 3 or tuple(u.shape[:2]) != (n, d):
+                raise ValueError(f"layout='node': u must be (n, d, B) with n={n}, d={d}, got {tuple(u.shape)}")
+        elif u.dim() not in (2, 3) or tuple(u.shape[-2:]) != (n, d):
+            raise ValueError(f"u must be (n, d) or (B, n, d) with n={n}, d={d}, got {tuple(u.shape)}")
+        if E is None:
+            E = self._E
+        elif not isinstance(E, torch.Tensor):
+            E = torch.as_tensor(E, dtype=torch.float64)
+        if self.mesh.nodes.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("diffhe: node gradients are not implemented for elasticity (mesh.nodes requires "
+                                      "grad)")
+        u, E = u.to(torch.float64), E.to(torch.float64)
+        _kappa_layout(E, self.mesh.n_elements, _stress_batch(u, layout == "node"), layout == "node")
+        _SOLVERS[id(self)] = self
+        return torch.ops.diffhe.elastic_stress(u, E, id(self), layout == "node", want_sigma, want_vm)
+
+    def stress(self, u: torch.Tensor, E=None, layout: str = "sample") -> torch.Tensor:
+        """Element stresses sigma = E (2 mu' eps + lambda' tr(eps) I) of the displacement u -- (n, d), (B, n, d), or
+        (n, d, B) with layout="node", what `forward` returns -- in Voigt components (xx, yy, xy | xx, yy, zz, yz, xz, xy;
+        shear components are tensor components): (m, nc), (B, m, nc), or (m, nc, B) with layout="node".  E: None for the
+        solver's, or another modulus in any layout E takes (the relaxed stress of stress-constrained design); an
+        unbatched u is broadcast to the batch of E.  u and E may require grad."""
+        return self._stress_op(u, E, layout, True, False)[0]
+
+    def von_mises(self, u: torch.Tensor, E=None, layout: str = "sample") -> torch.Tensor:
+        """The von Mises stress per element, (m,), (B, m), or (m, B) with layout="node"; in 2D it includes the
+        out-of-plane sigma_zz (0 in plane stress, nu (sigma_xx + sigma_yy) in plane strain).  No stress array is formed.
+        Its derivative is defined as 0 where the stress vanishes.  Arguments as `stress`."""
+        return self._stress_op(u, E, layout, False, True)[1]
+
+    def stress_and_von_mises(self, u: torch.Tensor, E=None, layout: str = "sample") -> Tuple[torch.Tensor, torch.Tensor]:
+        """(`stress`, `von_mises`) from one pass over the elements, and one backward pass for both cotangents."""
+        return self._stress_op(u, E, layout, True, True)

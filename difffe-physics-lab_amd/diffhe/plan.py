@@ -846,6 +846,23 @@ class SolvePlan:
                     cached = self.__dict__["_gradient_table"] = (gtab, vol)
         return cached
 
+    def oriented_gradient_table(self) -> torch.Tensor:
+        """gtab of `gradient_table` with the sign of every element's orientation restored: g_p = grad phi_p exactly.  The
+        table holds the gradients up to the sign of the element's determinant, which cancels in the products of two
+        gradients that the assembly and the coefficient gradients form; the stress is LINEAR in them (diffhe.elastic).
+        The table itself where every element is positively oriented, else a signed copy.  Built once per plan."""
+        cached = self.__dict__.get("_oriented_gtab")
+        if cached is None:
+            gtab, _ = self.gradient_table()
+            P = self._nodes_host[self._elements]                                 # (m, npe, dim)
+            det = np.linalg.det(P[:, 1:] - P[:, :1])
+            if np.all(det >= 0.0):
+                cached = gtab
+            else:
+                cached = gtab * torch.from_numpy(np.where(det < 0.0, -1.0, 1.0)).to(self.device)
+            self.__dict__["_oriented_gtab"] = cached
+        return cached
+
     def closed_boundary_general(self) -> bool:
         """Every node of the mesh boundary is a Dirichlet node (general meshes, P1: a boundary edge belongs to exactly one
         triangle; 3D: a boundary face to exactly one tetrahedron; 1D: a boundary node to exactly one element).  The regime in which one scalar kappa per sample may stay
