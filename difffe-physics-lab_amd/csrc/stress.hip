@@ -12,8 +12,14 @@
 // form below (NC = 1: dE); the form writes the tensor T of the element, nc numbers per element and sample, as a side
 // product, and the node pass gathers T g_p over the per-node incidence list (the list of shape.hip's gather).  T costs
 // nc m values per sample where the (d+1) d vertex contributions of shape.hip's form would cost (d+1) d m.
+//
+// Every kernel takes a compile-time EIG: with it the element carries an eigenstrain (eigen_field.h) and the stress is
+// E (s(u) - s0) with an out-of-plane component of its own (include/diffhe_eigenstrain.h, whose three stress entries are at
+// the end of this unit); without it the instantiations are the ones of diffhe_stress.h, unchanged.
 #include "common.h"
+#include "diffhe_eigenstrain.h"
 #include "diffhe_stress.h"
+#include "eigen_field.h"
 #include "element_grad.h"
 
 namespace {
@@ -21,19 +27,23 @@ namespace {
 using namespace diffhe;
 typedef long long i64;
 
-// Voigt component k of a symmetric DIM x DIM tensor: (row, column); the first DIM are the diagonal.
+// What an element with an eigenstrain carries on top: the field, and its components where the batch shares them (zb == 0).
+template <int DIM, bool EIG>
+struct EigenOf {};
 template <int DIM>
-__device__ __forceinline__ constexpr int voigt_row(int k) {
-  return k < DIM ? k : (DIM == 2 ? 0 : (k == 3 ? 1 : 0));
-}
+struct EigenOf<DIM, true> {
+  EigenField<DIM> ef;
+};
+template <int DIM, bool EIG>
+struct EigenElem {};
 template <int DIM>
-__device__ __forceinline__ constexpr int voigt_col(int k) {
-  return k < DIM ? k : (DIM == 2 ? 1 : (k == 5 ? 1 : 2));
-}
+struct EigenElem<DIM, true> {
+  double z[EigenField<DIM>::NZ];
+};
 
 // What both directions read of an element and a sample.
-template <int DIM>
-struct StressElement {
+template <int DIM, bool EIG = false>
+struct StressElement : EigenOf<DIM, EIG> {
   static constexpr int NPE = DIM + 1, NC = DIM * (DIM + 1) / 2;
   const int* __restrict__ elems;
   const double* __restrict__ gtab;
@@ -43,7 +53,7 @@ struct StressElement {
   i64 ese, esb;
   int m;
 
-  struct Elem {
+  struct Elem : EigenElem<DIM, EIG> {
     int e;
     int node[NPE];
     double G[NPE][DIM];
@@ -57,10 +67,13 @@ struct StressElement {
 #pragma unroll
       for (int t = 0; t < DIM; ++t) el.G[p][t] = gtab[(i64)(p * DIM + t) * m + e];
     }
+    if constexpr (EIG) {
+      if (this->ef.zb == 0) this->ef.read(e, 0, el.z);
+    }
   }
 
-  // the unit stress s (NC) of sample b from H[a][t] = sum_p u[(p, a)] g_p[t]
-  __device__ __forceinline__ void unit_stress(const Elem& el, int Bp, int b, double* s) const {
+  // the unit stress s (NC) of sample b from H[a][t] = sum_p u[(p, a)] g_p[t]; returns tr H
+  __device__ __forceinline__ double unit_stress(const Elem& el, int Bp, int b, double* s) const {
     double H[DIM][DIM];
 #pragma unroll
     for (int a = 0; a < DIM; ++a)
@@ -82,17 +95,39 @@ struct StressElement {
       const int a = voigt_row<DIM>(k), t = voigt_col<DIM>(k);
       s[k] = k < DIM ? fma(2.0 * mu1, H[a][a], lam1 * tr) : mu1 * (H[a][t] + H[t][a]);
     }
+    return tr;
+  }
+
+  // EIG: s <- s - s0 in plane, tr = tr H; returns the out-of-plane unit stress lam1 (tr - theta0) - 2 mu1 eps0_zz of
+  // plane strain (0 otherwise)
+  __device__ __forceinline__ double subtract_initial(const Elem& el, int b, double tr, double* s) const {
+    double szz = 0.0;
+    if constexpr (EIG) {
+      constexpr int NZ = EigenField<DIM>::NZ;
+      double z[NZ], s0[NC];
+      if (this->ef.zb) {
+        this->ef.read(el.e, b, z);
+      } else {
+#pragma unroll
+        for (int k = 0; k < NZ; ++k) z[k] = el.z[k];
+      }
+      const double th = this->ef.initial_stress(z, s0);
+#pragma unroll
+      for (int k = 0; k < NC; ++k) s[k] -= s0[k];
+      if (DIM == 2 && this->ef.pstrain) szz = fma(lam1, tr - th, -2.0 * mu1 * z[3]);
+    }
+    return szz;
   }
 
   __device__ __forceinline__ double modulus(int e, int b) const { return E[(i64)e * ese + (i64)b * esb]; }
 };
 
-// The three normal stresses of sigma (NC): in 2D the third is nu_z (sigma_xx + sigma_yy).
-template <int DIM>
-__device__ __forceinline__ void normal_stresses(const double* sg, double nu_z, double* nn) {
+// The three normal stresses of sigma (NC): in 2D the third is nu_z (sigma_xx + sigma_yy), with an eigenstrain sg_zz.
+template <int DIM, bool EIG>
+__device__ __forceinline__ void normal_stresses(const double* sg, double nu_z, double sg_zz, double* nn) {
   nn[0] = sg[0];
   nn[1] = sg[1];
-  nn[2] = DIM == 2 ? nu_z * (sg[0] + sg[1]) : sg[2];
+  nn[2] = DIM == 2 ? (EIG ? sg_zz : nu_z * (sg[0] + sg[1])) : sg[2];
 }
 
 template <int DIM>
@@ -108,18 +143,19 @@ __device__ __forceinline__ double von_mises(const double* sg, const double* nn) 
 // ---------------------------------------------------------------------------------------
 // sigma at c*osc + e*ose + b and / or vm (m, Bp); a NULL output is neither computed nor stored.
 // ---------------------------------------------------------------------------------------
-template <int DIM>
-__global__ __launch_bounds__(256) void stress_eval_kernel(const StressElement<DIM> el_of, int Bp,
+template <int DIM, bool EIG>
+__global__ __launch_bounds__(256) void stress_eval_kernel(const StressElement<DIM, EIG> el_of, int Bp,
                                                            double* __restrict__ sigma, i64 osc, i64 ose,
                                                            double* __restrict__ vm) {
   constexpr int NC = DIM * (DIM + 1) / 2;
   const NodeMap nm = node_map(Bp);  // "nodes" are elements here
   if (nm.b >= Bp) return;
   for (int e = nm.node0; e < el_of.m; e += nm.stride) {
-    typename StressElement<DIM>::Elem el;
+    typename StressElement<DIM, EIG>::Elem el;
     double sg[NC];
     el_of.load(e, el);
-    el_of.unit_stress(el, Bp, nm.b, sg);
+    const double tr = el_of.unit_stress(el, Bp, nm.b, sg);
+    const double szz = el_of.subtract_initial(el, nm.b, tr, sg);   // EIG only
     const double Ee = el_of.modulus(e, nm.b);
 #pragma unroll
     for (int k = 0; k < NC; ++k) sg[k] *= Ee;
@@ -129,7 +165,7 @@ __global__ __launch_bounds__(256) void stress_eval_kernel(const StressElement<DI
     }
     if (vm) {
       double nn[3];
-      normal_stresses<DIM>(sg, el_of.nu_z, nn);
+      normal_stresses<DIM, EIG>(sg, el_of.nu_z, Ee * szz, nn);
       vm[(i64)e * Bp + nm.b] = von_mises<DIM>(sg, nn);
     }
   }
@@ -140,12 +176,20 @@ __global__ __launch_bounds__(256) void stress_eval_kernel(const StressElement<DI
 // cotangent c = sigma_bar + vm_bar d vm / d sigma, and, where `work` is given, T = E (2 mu1 sym(C) + lam1 tr(C) I) to
 // work (NC, m, Bp).  Samples b >= B: dE = 0, T = 0, no cotangent read.
 // ---------------------------------------------------------------------------------------
-template <int DIM>
-struct StressAdjointForm {
+template <bool EIG>
+struct EigenOut {};
+template <>
+struct EigenOut<true> {
+  double* __restrict__ deps;   // d / d eps0 at c*dzc + e*dze + b, or NULL
+  i64 dzc, dze;
+};
+
+template <int DIM, bool EIG = false>
+struct StressAdjointForm : EigenOut<EIG> {
   static constexpr int NC = 1;
   static constexpr int NV = DIM * (DIM + 1) / 2;
-  typedef typename StressElement<DIM>::Elem Elem;
-  StressElement<DIM> el_of;
+  typedef typename StressElement<DIM, EIG>::Elem Elem;
+  StressElement<DIM, EIG> el_of;
   const double* __restrict__ sigma_bar;
   i64 osc, ose;
   const double* __restrict__ vm_bar;
@@ -162,10 +206,16 @@ struct StressAdjointForm {
 #pragma unroll
         for (int k = 0; k < NV; ++k) work[k * mb + at] = 0.0;
       }
+      if constexpr (EIG) {
+        if (this->deps)
+          for (int k = 0; k < el_of.ef.count(); ++k) this->deps[k * this->dzc + el.e * this->dze + b] = 0.0;
+      }
       return;
     }
     double s[NV], c[NV];
-    el_of.unit_stress(el, Bp, b, s);
+    const double tr_h = el_of.unit_stress(el, Bp, b, s);
+    const double szz = el_of.subtract_initial(el, b, tr_h, s);   // EIG only
+    double czz = 0.0;                                            // EIG only: the cotangent of sigma_zz
     const double Ee = el_of.modulus(el.e, b);
 #pragma unroll
     for (int k = 0; k < NV; ++k) c[k] = sigma_bar ? sigma_bar[k * osc + el.e * ose + b] : 0.0;
@@ -173,7 +223,7 @@ struct StressAdjointForm {
       double sg[NV], nn[3];
 #pragma unroll
       for (int k = 0; k < NV; ++k) sg[k] = Ee * s[k];
-      normal_stresses<DIM>(sg, el_of.nu_z, nn);
+      normal_stresses<DIM, EIG>(sg, el_of.nu_z, Ee * szz, nn);
       const double vm = von_mises<DIM>(sg, nn);
       if (vm > 0.0) {                                   // d vm / d sigma = 0 where vm == 0
         const double w = vm_bar[at] / vm;
@@ -183,9 +233,12 @@ struct StressAdjointForm {
         for (int i = 0; i < 3; ++i) cn[i] = 1.5 * (nn[i] - mean) * w;
 #pragma unroll
         for (int i = 0; i < DIM; ++i) c[i] += cn[i];
-        if (DIM == 2) {                                 // sigma_zz = nu_z (sigma_xx + sigma_yy)
+        if (DIM == 2 && !EIG) {                         // sigma_zz = nu_z (sigma_xx + sigma_yy)
           c[0] = fma(el_of.nu_z, cn[2], c[0]);
           c[1] = fma(el_of.nu_z, cn[2], c[1]);
+        }
+        if constexpr (EIG && DIM == 2) {                // sigma_zz on its own; identically 0 in plane stress
+          if (el_of.ef.pstrain) czz = cn[2];
         }
 #pragma unroll
         for (int k = DIM; k < NV; ++k) c[k] = fma(3.0 * sg[k], w, c[k]);
@@ -194,9 +247,19 @@ struct StressAdjointForm {
     double de = 0.0;
 #pragma unroll
     for (int k = 0; k < NV; ++k) de = fma(c[k], s[k], de);
+    if (EIG) de = fma(czz, szz, de);
     out[0] = de;
+    if constexpr (EIG) {
+      if (this->deps) {
+        double dz[EigenField<DIM>::NZ];
+        el_of.ef.transpose(-Ee, c, czz, dz);
+#pragma unroll
+        for (int k = 0; k < EigenField<DIM>::NZ; ++k)
+          if (k < el_of.ef.count()) this->deps[k * this->dzc + el.e * this->dze + b] = dz[k];
+      }
+    }
     if (work) {
-      double tr = 0.0;
+      double tr = EIG ? czz : 0.0;                      // sigma_zz = E lam1 tr eps(u) + ... feeds the trace
 #pragma unroll
       for (int i = 0; i < DIM; ++i) tr += c[i];
 #pragma unroll
@@ -246,10 +309,31 @@ __global__ __launch_bounds__(256) void stress_node_kernel(const int* __restrict_
   }
 }
 
-template <int DIM>
-StressElement<DIM> element_of(const int* elems, const double* gtab, double lam1, double mu1, double nu_z, const double* u,
-                              const double* E, i64 e_se, i64 e_sb, int m) {
-  return StressElement<DIM>{elems, gtab, lam1, mu1, DIM == 2 ? nu_z : 0.0, u, E, e_se, e_sb, m};
+// the eigenstrain of one call, as the eigen entries get it (absent: the entries of diffhe_stress.h)
+struct EigenArgs {
+  const double* eps0;
+  i64 zc, ze, zb;
+  int plane_strain;
+};
+const EigenArgs kNoEigen = {nullptr, 0, 0, 0, 0};
+
+template <int DIM, bool EIG>
+StressElement<DIM, EIG> element_of(const int* elems, const double* gtab, double lam1, double mu1, double nu_z,
+                                   const double* u, const double* E, i64 e_se, i64 e_sb, int m, const EigenArgs& z) {
+  StressElement<DIM, EIG> el;
+  el.elems = elems, el.gtab = gtab, el.lam1 = lam1, el.mu1 = mu1, el.nu_z = DIM == 2 ? nu_z : 0.0;
+  el.u = u, el.E = E, el.ese = e_se, el.esb = e_sb, el.m = m;
+  if constexpr (EIG) el.ef = EigenField<DIM>{z.eps0, z.zc, z.ze, z.zb, lam1, mu1, DIM == 2 && z.plane_strain ? 1 : 0};
+  return el;
+}
+
+template <int DIM, bool EIG>
+StressAdjointForm<DIM, EIG> form_of(const StressElement<DIM, EIG>& el, const double* sigma_bar, i64 osc, i64 ose,
+                                    const double* vm_bar, double* work, int B, double* deps, i64 dzc, i64 dze) {
+  StressAdjointForm<DIM, EIG> f;
+  f.el_of = el, f.sigma_bar = sigma_bar, f.osc = osc, f.ose = ose, f.vm_bar = vm_bar, f.work = work, f.B = B;
+  if constexpr (EIG) f.deps = deps, f.dzc = dzc, f.dze = dze;
+  return f;
 }
 
 // what every entry refuses: pointers, dim, sizes, the E strides, the int32 codes e * npe + p
@@ -262,6 +346,106 @@ bool bad_common(const int* elems, const double* gtab, int dim, const double* u, 
 // bytes of E as the kernels read it: a field per sample, one field, one number per sample, one number
 double modulus_bytes(i64 e_se, i64 e_sb, int m, int Bp) { return 8.0 * (e_se ? (double)m : 1.0) * (e_sb ? (double)Bp : 1.0); }
 
+// bytes of an eps0-shaped array (EIG) with the strides ze, zb
+template <bool EIG>
+double eigen_array_bytes(int dim, int plane_strain, i64 ze, i64 zb, int m, int Bp) {
+  return EIG ? eigen_bytes(dim == 3 ? 6 : (plane_strain ? 4 : 3), ze, zb, m, Bp) : 0.0;
+}
+
+// ---------------------------------------------------------------------------------------
+// The three entries of either header.
+// ---------------------------------------------------------------------------------------
+template <int DIM, bool EIG>
+int eval_of(const StressElement<DIM, EIG>& el, int Bp, double* sigma, i64 osc, i64 ose, double* vm, void* stream) {
+  hipLaunchKernelGGL((stress_eval_kernel<DIM, EIG>), diffhe::node_grid(el.m, Bp), dim3(256), 0, (hipStream_t)stream, el,
+                     Bp, sigma, osc, ose, vm);
+  return diffhe::check_launch();
+}
+
+template <bool EIG>
+int stress_eval(const int* elems, const double* gtab, int dim, double lam1, double mu1, double nu_z, const double* u,
+                const double* E, i64 e_se, i64 e_sb, const EigenArgs& z, int n, int m, int Bp, double* sigma, i64 osc,
+                i64 ose, double* vm, void* stream) {
+  if (bad_common(elems, gtab, dim, u, E, e_se, e_sb, n, m) || (!sigma && !vm) || (sigma && (osc < 1 || ose < 1)))
+    return DIFFHE_E_BADARG;
+  if (EIG && bad_eigen(z.eps0, z.zc, z.ze, z.zb)) return DIFFHE_E_BADARG;
+  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
+  const int nc = dim * (dim + 1) / 2;
+  // u once per dof, E, the outputs (EIG: eps0)
+  diffhe::account(8.0 * Bp * ((double)dim * n + (sigma ? (double)nc * m : 0.0) + (vm ? (double)m : 0.0)) +
+                  modulus_bytes(e_se, e_sb, m, Bp) + eigen_array_bytes<EIG>(dim, z.plane_strain, z.ze, z.zb, m, Bp));
+  if (dim == 2)
+    return eval_of(element_of<2, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), Bp, sigma, osc, ose, vm,
+                   stream);
+  return eval_of(element_of<3, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), Bp, sigma, osc, ose, vm, stream);
+}
+
+template <int DIM, bool EIG>
+int adjoint_of(const StressAdjointForm<DIM, EIG>& form, const double* gtab, const int* inc_ptr, const int* inc, int n,
+               int m, int B, int Bp, double* u_bar, double* de_e, double* de_part, double* de_sum, double bytes,
+               void* stream) {
+  constexpr int NC = DIM * (DIM + 1) / 2;
+  const int status = diffhe::launch_element_grad(form, m, Bp, de_e, 0, Bp, de_part, de_sum, bytes, stream);
+  if (status != DIFFHE_OK || !u_bar) return status;
+  diffhe::account(8.0 * Bp * ((double)NC * m + (double)DIM * n));   // node pass: T once, u_bar once per dof
+  hipLaunchKernelGGL(stress_node_kernel<DIM>, diffhe::node_grid(n, Bp), dim3(256), 0, (hipStream_t)stream, inc_ptr, inc,
+                     gtab, (const double*)form.work, n, m, B, Bp, u_bar);
+  return diffhe::check_launch();
+}
+
+template <bool EIG>
+int stress_adjoint(const int* elems, const double* gtab, int dim, double lam1, double mu1, double nu_z, const double* u,
+                   const double* E, i64 e_se, i64 e_sb, const EigenArgs& z, const double* sigma_bar, i64 osc, i64 ose,
+                   const double* vm_bar, const int* inc_ptr, const int* inc, int n, int m, int B, int Bp, double* work,
+                   double* u_bar, double* de_e, double* de_part, double* de_sum, double* deps, i64 dzc, i64 dze,
+                   void* stream) {
+  if (bad_common(elems, gtab, dim, u, E, e_se, e_sb, n, m) || (!sigma_bar && !vm_bar) ||
+      (sigma_bar && (osc < 1 || ose < 1)) || B < 1 || B > Bp)
+    return DIFFHE_E_BADARG;
+  if (EIG && (bad_eigen(z.eps0, z.zc, z.ze, z.zb) || (deps && (dzc < 1 || dze < 1)))) return DIFFHE_E_BADARG;
+  const bool nodes = u_bar != nullptr;
+  if ((work != nullptr) != nodes || (inc_ptr != nullptr) != nodes || (inc != nullptr) != nodes) return DIFFHE_E_BADARG;
+  if ((de_part == nullptr) != (de_sum == nullptr) || (!nodes && !deps && !de_e && !de_part)) return DIFFHE_E_BADARG;
+  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
+  const int nc = dim * (dim + 1) / 2;
+  // element pass: u once per dof, E, the cotangents, T and dE per element (EIG: eps0, and d eps0 per element)
+  const double bytes = 8.0 * Bp * ((double)dim * n + (sigma_bar ? (double)nc * m : 0.0) + (vm_bar ? (double)m : 0.0) +
+                                   (nodes ? (double)nc * m : 0.0) + (de_e ? (double)m : 0.0)) +
+                       modulus_bytes(e_se, e_sb, m, Bp) + eigen_array_bytes<EIG>(dim, z.plane_strain, z.ze, z.zb, m, Bp) +
+                       (deps ? eigen_array_bytes<EIG>(dim, z.plane_strain, 1, 1, m, Bp) : 0.0);
+  if (dim == 2)
+    return adjoint_of(form_of(element_of<2, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), sigma_bar, osc, ose,
+                              vm_bar, work, B, deps, dzc, dze),
+                      gtab, inc_ptr, inc, n, m, B, Bp, u_bar, de_e, de_part, de_sum, bytes, stream);
+  return adjoint_of(form_of(element_of<3, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), sigma_bar, osc, ose,
+                            vm_bar, work, B, deps, dzc, dze),
+                    gtab, inc_ptr, inc, n, m, B, Bp, u_bar, de_e, de_part, de_sum, bytes, stream);
+}
+
+template <bool EIG>
+int stress_adjoint_shared(const int* elems, const double* gtab, int dim, double lam1, double mu1, double nu_z,
+                          const double* u, const double* E, i64 e_se, i64 e_sb, const EigenArgs& z,
+                          const double* sigma_bar, i64 osc, i64 ose, const double* vm_bar, int n, int m, int B, int Bp,
+                          double* de, void* stream) {
+  if (bad_common(elems, gtab, dim, u, E, e_se, e_sb, n, m) || (!sigma_bar && !vm_bar) ||
+      (sigma_bar && (osc < 1 || ose < 1)) || !de || B < 1 || B > Bp)
+    return DIFFHE_E_BADARG;
+  if (EIG && bad_eigen(z.eps0, z.zc, z.ze, z.zb)) return DIFFHE_E_BADARG;
+  const int nc = dim * (dim + 1) / 2;
+  const double bytes = 8.0 * (Bp * ((double)dim * n + (sigma_bar ? (double)nc * m : 0.0) + (vm_bar ? (double)m : 0.0)) +
+                              (double)m) + modulus_bytes(e_se, e_sb, m, Bp) +
+                       eigen_array_bytes<EIG>(dim, z.plane_strain, z.ze, z.zb, m, Bp);
+  if (dim == 2)
+    return diffhe::launch_element_grad_shared(
+        form_of(element_of<2, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), sigma_bar, osc, ose, vm_bar,
+                nullptr, B, nullptr, 0, 0),
+        m, B, Bp, de, 0, 1, bytes, stream);
+  return diffhe::launch_element_grad_shared(
+      form_of(element_of<3, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), sigma_bar, osc, ose, vm_bar, nullptr,
+              B, nullptr, 0, 0),
+      m, B, Bp, de, 0, 1, bytes, stream);
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -270,21 +454,8 @@ double modulus_bytes(i64 e_se, i64 e_sb, int m, int Bp) { return 8.0 * (e_se ? (
 extern "C" int diffhe_stress_eval(const int* elems, const double* gtab, int dim, double lam1, double mu1, double nu_z,
                                   const double* u, const double* E, long long e_se, long long e_sb, int n, int m, int Bp,
                                   double* sigma, long long osc, long long ose, double* vm, void* stream) {
-  if (bad_common(elems, gtab, dim, u, E, e_se, e_sb, n, m) || (!sigma && !vm) || (sigma && (osc < 1 || ose < 1)))
-    return DIFFHE_E_BADARG;
-  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
-  const int nc = dim * (dim + 1) / 2;
-  // u once per dof, E, the outputs
-  diffhe::account(8.0 * Bp * ((double)dim * n + (sigma ? (double)nc * m : 0.0) + (vm ? (double)m : 0.0)) +
-                  modulus_bytes(e_se, e_sb, m, Bp));
-  const dim3 grid = diffhe::node_grid(m, Bp);
-  if (dim == 2)
-    hipLaunchKernelGGL(stress_eval_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream,
-                       element_of<2>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), Bp, sigma, osc, ose, vm);
-  else
-    hipLaunchKernelGGL(stress_eval_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream,
-                       element_of<3>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), Bp, sigma, osc, ose, vm);
-  return diffhe::check_launch();
+  return stress_eval<false>(elems, gtab, dim, lam1, mu1, nu_z, u, E, e_se, e_sb, kNoEigen, n, m, Bp, sigma, osc, ose, vm,
+                            stream);
 }
 
 extern "C" int diffhe_stress_adjoint(const int* elems, const double* gtab, int dim, double lam1, double mu1, double nu_z,
@@ -292,58 +463,49 @@ extern "C" int diffhe_stress_adjoint(const int* elems, const double* gtab, int d
                                      const double* sigma_bar, long long osc, long long ose, const double* vm_bar,
                                      const int* inc_ptr, const int* inc, int n, int m, int B, int Bp, double* work,
                                      double* u_bar, double* de_e, double* de_part, double* de_sum, void* stream) {
-  if (bad_common(elems, gtab, dim, u, E, e_se, e_sb, n, m) || (!sigma_bar && !vm_bar) ||
-      (sigma_bar && (osc < 1 || ose < 1)) || B < 1 || B > Bp)
-    return DIFFHE_E_BADARG;
-  const bool nodes = u_bar != nullptr;
-  if ((work != nullptr) != nodes || (inc_ptr != nullptr) != nodes || (inc != nullptr) != nodes) return DIFFHE_E_BADARG;
-  if ((de_part == nullptr) != (de_sum == nullptr) || (!nodes && !de_e && !de_part)) return DIFFHE_E_BADARG;
-  if (!diffhe::valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
-  const int nc = dim * (dim + 1) / 2;
-  // element pass: u once per dof, E, the cotangents, T and dE per element
-  const double bytes = 8.0 * Bp * ((double)dim * n + (sigma_bar ? (double)nc * m : 0.0) + (vm_bar ? (double)m : 0.0) +
-                                   (nodes ? (double)nc * m : 0.0) + (de_e ? (double)m : 0.0)) +
-                       modulus_bytes(e_se, e_sb, m, Bp);
-  int status;
-  if (dim == 2)
-    status = diffhe::launch_element_grad(
-        StressAdjointForm<2>{element_of<2>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), sigma_bar, osc, ose, vm_bar,
-                             work, B},
-        m, Bp, de_e, 0, Bp, de_part, de_sum, bytes, stream);
-  else
-    status = diffhe::launch_element_grad(
-        StressAdjointForm<3>{element_of<3>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), sigma_bar, osc, ose, vm_bar,
-                             work, B},
-        m, Bp, de_e, 0, Bp, de_part, de_sum, bytes, stream);
-  if (status != DIFFHE_OK || !nodes) return status;
-  diffhe::account(8.0 * Bp * ((double)nc * m + (double)dim * n));   // node pass: T once, u_bar once per dof
-  const dim3 grid = diffhe::node_grid(n, Bp);
-  if (dim == 2)
-    hipLaunchKernelGGL(stress_node_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, inc_ptr, inc, gtab,
-                       (const double*)work, n, m, B, Bp, u_bar);
-  else
-    hipLaunchKernelGGL(stress_node_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, inc_ptr, inc, gtab,
-                       (const double*)work, n, m, B, Bp, u_bar);
-  return diffhe::check_launch();
+  return stress_adjoint<false>(elems, gtab, dim, lam1, mu1, nu_z, u, E, e_se, e_sb, kNoEigen, sigma_bar, osc, ose, vm_bar,
+                               inc_ptr, inc, n, m, B, Bp, work, u_bar, de_e, de_part, de_sum, nullptr, 0, 0, stream);
 }
 
 extern "C" int diffhe_stress_adjoint_shared(const int* elems, const double* gtab, int dim, double lam1, double mu1,
                                             double nu_z, const double* u, const double* E, long long e_se, long long e_sb,
                                             const double* sigma_bar, long long osc, long long ose, const double* vm_bar,
                                             int n, int m, int B, int Bp, double* de, void* stream) {
-  if (bad_common(elems, gtab, dim, u, E, e_se, e_sb, n, m) || (!sigma_bar && !vm_bar) ||
-      (sigma_bar && (osc < 1 || ose < 1)) || !de || B < 1 || B > Bp)
-    return DIFFHE_E_BADARG;
-  const int nc = dim * (dim + 1) / 2;
-  const double bytes = 8.0 * (Bp * ((double)dim * n + (sigma_bar ? (double)nc * m : 0.0) + (vm_bar ? (double)m : 0.0)) +
-                              (double)m) + modulus_bytes(e_se, e_sb, m, Bp);
-  if (dim == 2)
-    return diffhe::launch_element_grad_shared(
-        StressAdjointForm<2>{element_of<2>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), sigma_bar, osc, ose, vm_bar,
-                             nullptr, B},
-        m, B, Bp, de, 0, 1, bytes, stream);
-  return diffhe::launch_element_grad_shared(
-      StressAdjointForm<3>{element_of<3>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m), sigma_bar, osc, ose, vm_bar,
-                           nullptr, B},
-      m, B, Bp, de, 0, 1, bytes, stream);
+  return stress_adjoint_shared<false>(elems, gtab, dim, lam1, mu1, nu_z, u, E, e_se, e_sb, kNoEigen, sigma_bar, osc, ose,
+                                      vm_bar, n, m, B, Bp, de, stream);
+}
+
+// =========================================================================================
+// C ABI (include/diffhe_eigenstrain.h): the same three with an eigenstrain
+// =========================================================================================
+extern "C" int diffhe_stress_eval_eigen(const int* elems, const double* gtab, int dim, double lam1, double mu1,
+                                        int plane_strain, const double* u, const double* E, long long e_se,
+                                        long long e_sb, const double* eps0, long long zc, long long ze, long long zb,
+                                        int n, int m, int Bp, double* sigma, long long osc, long long ose, double* vm,
+                                        void* stream) {
+  return stress_eval<true>(elems, gtab, dim, lam1, mu1, 0.0, u, E, e_se, e_sb, EigenArgs{eps0, zc, ze, zb, plane_strain},
+                           n, m, Bp, sigma, osc, ose, vm, stream);
+}
+
+extern "C" int diffhe_stress_adjoint_eigen(const int* elems, const double* gtab, int dim, double lam1, double mu1,
+                                           int plane_strain, const double* u, const double* E, long long e_se,
+                                           long long e_sb, const double* eps0, long long zc, long long ze, long long zb,
+                                           const double* sigma_bar, long long osc, long long ose, const double* vm_bar,
+                                           const int* inc_ptr, const int* inc, int n, int m, int B, int Bp, double* work,
+                                           double* u_bar, double* de_e, double* de_part, double* de_sum, double* deps,
+                                           long long dzc, long long dze, void* stream) {
+  return stress_adjoint<true>(elems, gtab, dim, lam1, mu1, 0.0, u, E, e_se, e_sb,
+                              EigenArgs{eps0, zc, ze, zb, plane_strain}, sigma_bar, osc, ose, vm_bar, inc_ptr, inc, n, m, B,
+                              Bp, work, u_bar, de_e, de_part, de_sum, deps, dzc, dze, stream);
+}
+
+extern "C" int diffhe_stress_adjoint_eigen_shared(const int* elems, const double* gtab, int dim, double lam1, double mu1,
+                                                  int plane_strain, const double* u, const double* E, long long e_se,
+                                                  long long e_sb, const double* eps0, long long zc, long long ze,
+                                                  long long zb, const double* sigma_bar, long long osc, long long ose,
+                                                  const double* vm_bar, int n, int m, int B, int Bp, double* de,
+                                                  void* stream) {
+  return stress_adjoint_shared<true>(elems, gtab, dim, lam1, mu1, 0.0, u, E, e_se, e_sb,
+                                     EigenArgs{eps0, zc, ze, zb, plane_strain}, sigma_bar, osc, ose, vm_bar, n, m, B, Bp, de,
+                                     stream);
 }

@@ -15,7 +15,10 @@ the smallest eigenpairs of K phi = lambda M_L phi per sample with d lambda / d k
 `diffhe.elastic`: `ElasticFESolver`, linear elasticity on P1 triangles and tetrahedra -- the first vector-valued problem,
 d displacement components per node -- with gradients to a Young's modulus per element, the body force and the nodal
 load, also exported here (its kernels are declared in include/diffhe_elastic.h), and its `stress` / `von_mises` with
-gradients to u and E and `pnorm` (kernels declared in include/diffhe_stress.h); `diffhe._hip`: the ctypes binding).
+gradients to u and E and `pnorm` (kernels declared in include/diffhe_stress.h), and its eigenstrain (initial strain:
+thermal expansion, swelling, pre-stress) -- `eigenstrain_load`, `eigenstrain=` on the solve and on the stress methods,
+with gradients to eps0 and E, and the torch helpers `thermal_strain` / `element_mean` that carry the temperature of a
+heat solve to it (kernels declared in include/diffhe_eigenstrain.h); `diffhe._hip`: the ctypes binding).
 """
 from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, loss as _loss, mesh as _mesh, neural as _neural, robin as _robin, shape as _shape,
                solver as _solver)

@@ -1,4 +1,5 @@
-"""ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h, include/diffhe_stress.h).
+"""ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h, include/diffhe_stress.h,
+include/diffhe_eigenstrain.h).
 
 The library is built in-tree by `__graft_entry__.build()` /
 `make -C difffe-physics-lab_amd/csrc`.  There is NO fallback: if the library or a
@@ -168,6 +169,23 @@ STRESS_SIGNATURES = {
                                           _PD, _PV]),
 }
 
+# name -> (restype, argtypes) of every symbol of include/diffhe_eigenstrain.h, the library's fourth header (eigenstrain
+# loads, csrc/eigenstrain.hip, and the eigen variants of the stress entries, csrc/stress.hip): bound by the same loop
+# (tests/test_eigenstrain.py holds this table against that header)
+_EIGEN_HEAD = [_D, _D, _I, _PD, _L, _L, _PD, _L, _L, _L]    # lam1, mu1, plane_strain, E and its strides, eps0 and its strides
+EIGENSTRAIN_SIGNATURES = {
+    "diffhe_eigenstrain_load": (_S, [_PI, _PI, _PD, _PD, _I, *_EIGEN_HEAD, _I, _I, _I, _I, _PD, _PV]),
+    "diffhe_eigenstrain_load_adjoint": (_S, [_PI, _PD, _PD, _I, *_EIGEN_HEAD, _PD, _I, _I, _I, _I, _PD, _L, _L, _PD, _PD,
+                                             _PD, _PV]),
+    "diffhe_eigenstrain_load_adjoint_shared": (_S, [_PI, _PD, _PD, _I, *_EIGEN_HEAD, _PD, _I, _I, _I, _I, _PD, _PV]),
+    "diffhe_stress_eval_eigen": (_S, [_PI, _PD, _I, _D, _D, _I, _PD, _PD, _L, _L, _PD, _L, _L, _L, _I, _I, _I, _PD, _L, _L,
+                                      _PD, _PV]),
+    "diffhe_stress_adjoint_eigen": (_S, [_PI, _PD, _I, _D, _D, _I, _PD, _PD, _L, _L, _PD, _L, _L, _L, _PD, _L, _L, _PD, _PI,
+                                         _PI, _I, _I, _I, _I, _PD, _PD, _PD, _PD, _PD, _PD, _L, _L, _PV]),
+    "diffhe_stress_adjoint_eigen_shared": (_S, [_PI, _PD, _I, _D, _D, _I, _PD, _PD, _L, _L, _PD, _L, _L, _L, _PD, _L, _L,
+                                                _PD, _I, _I, _I, _I, _PD, _PV]),
+}
+
 _lib = None
 
 
@@ -202,7 +220,8 @@ def lib():
                 f"libdiffhe_hip.so not found at {LIB_PATH}: build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in (*SIGNATURES.items(), *ELASTIC_SIGNATURES.items(), *STRESS_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *ELASTIC_SIGNATURES.items(), *STRESS_SIGNATURES.items(),
+                                  *EIGENSTRAIN_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = (_I if res is _S else res), args
             if res is _S:

@@ -56,6 +56,24 @@ solve used (the relaxed stress rho^q E_0 D eps of stress-constrained SIMP); the 
 unbatched u with a batched E is broadcast.  The gradients come from one element pass (dL/dE, and a symmetric tensor per
 element) and one node pass over the per-node incidence list (dL/du), in fixed orders: bitwise reproducible.
 
+Eigenstrain (csrc/eigenstrain.hip, the eigen instantiations of csrc/stress.hip, include/diffhe_eigenstrain.h): an initial
+strain eps0 per element and sample -- thermal expansion, swelling, shrinkage, pre-stress.  nc0 = 3 components (xx, yy, xy)
+in plane stress, 4 in plane strain, (xx, yy, xy, zz): the total eps_zz is 0 there, so an eps0_zz is constrained and loads
+the body in plane; 6 in 3D; shear components are tensor components.  Layouts: (nc0,), (B, nc0), (m, nc0), (B, m, nc0), and
+(nc0, m, B) with layout="node" -- `AnisotropicFESolver`'s -- with the batch rules of `_kappa_layout`.
+
+    unit initial stress   s0 = 2 mu' eps0 + lambda' theta0 I in plane, theta0 = tr eps0 over ALL stored normal components
+    load                  F0[(i, a)] = sum_{(e, p) at i} vol_e E_e sum_t s0_e[a][t] grad phi_p[t]: K(E) u = M f + load + F0
+    stress                sigma = E (s(u) - s0) in plane; sigma_zz = E [lambda' (tr eps(u) - theta0) - 2 mu' eps0_zz] in
+                          plane strain (NOT nu (sigma_xx + sigma_yy)), 0 in plane stress
+
+`solver.eigenstrain_load(eps0, E=None)` is F0, differentiable in eps0 and E; `solver(f, load, eigenstrain=eps0)` adds it
+to `load` in front of the unchanged solve, so that dL/dload = lambda flows back into dL/deps0 and the second E path, which
+autograd adds to the solve's; `stress` / `von_mises` / `stress_and_von_mises(..., eigenstrain=eps0)` evaluate the stress
+above with gradients to u, E and eps0.  `thermal_strain(alpha, dT, dim, plane)` and `element_mean(T, mesh)` (plain torch)
+carry the temperature of a heat solve to eps0.  The gradient of an eps0 shared over elements or samples is a torch `sum`
+of the kernel's per-element, per-sample array over the shared axes.
+
 Not implemented (NotImplementedError): 1D meshes, P2 meshes, backward with create_graph=True, a per-call `dirichlet=`,
 node gradients (mesh.nodes requiring grad), Robin / flux data (h=, u_inf=, flux=); `amg=dict(strength=...)`.
 """
@@ -72,10 +90,12 @@ import torch.nn as nn
 
 from . import _hip
 from .plan import get_plan, padded_batch, valid_batch_pad, _stream
-from .solver import (K_ELEM, K_SAMPLE_ELEM, SolveInfo, _Engine, _SOLVERS, _call_options, _kappa_grad, _kappa_layout,
-                     _like_grads, _fake_grads, _register_state, _resolve_device, _run_call, _state_of, _tie_state)
+from .solver import (K_ELEM, K_SAMPLE, K_SAMPLE_ELEM, K_SCALAR, SolveInfo, _Engine, _SOLVERS, _call_options, _kappa_grad,
+                     _kappa_layout, _kappa_mode, _like_grads, _fake_grads, _register_state, _resolve_device, _run_call,
+                     _state_of, _tensor_mode, _tie_state)
 
-__all__ = ("ElasticFESolver", "lame_unit", "parse_fixed", "dof_pattern", "pnorm")
+__all__ = ("ElasticFESolver", "lame_unit", "parse_fixed", "dof_pattern", "pnorm", "thermal_strain", "element_mean",
+           "eigen_components")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -641,6 +661,324 @@ def _stress_backward(ctx, grad_sigma, grad_vm):
 torch.library.register_autograd("diffhe::elastic_stress", _stress_backward, setup_context=_stress_setup_context)
 
 
+# ---------------------------------------------------------------------------------------------
+# Eigenstrain (csrc/eigenstrain.hip and the eigen instantiations of csrc/stress.hip, include/diffhe_eigenstrain.h):
+# diffhe::eigenstrain_load / eigenstrain_load_backward, the load F0(eps0, E), and diffhe::elastic_stress_eigen /
+# elastic_stress_eigen_backward, the stress E (s(u) - s0).  Pure functions of their tensors for the solver registered under
+# `handle`: backward recomputes from the saved inputs.
+# ---------------------------------------------------------------------------------------------
+def eigen_components(dim: int, plane: Optional[str]) -> int:
+    """nc0: 6 in 3D, 4 in plane strain (xx, yy, xy, zz), 3 in plane stress."""
+    return 6 if dim == 3 else (4 if plane == "strain" else 3)
+
+
+def _eigen_batch(eps0, E, m: int, nc0: int, node_major: bool, B_hint: Optional[int]) -> Optional[int]:
+    """The batch of one call: the hint (the batch of f, load or u), else that of whichever of eps0 and E shows one, the
+    shapes that read only one way first; None: nothing is batched.  The shapes that read both ways -- (m, nc0) and (m,)
+    with m equal to the batch -- are then classified WITH that batch, by the tie rule of `_kappa_layout`."""
+    if B_hint is not None:
+        return B_hint
+    if eps0.dim() == 3:
+        return eps0.shape[2] if (node_major and tuple(eps0.shape[:2]) == (nc0, m)) else eps0.shape[0]
+    if E.dim() == 2:
+        return E.shape[1] if (node_major and E.shape[0] == m) else E.shape[0]
+    _, B_z, _ = _tensor_mode(eps0, nc0, m, None, node_major)
+    return B_z if B_z is not None else _kappa_mode(E, m, None)[1]
+
+
+@dataclass
+class _EigenCall(_StressCall):
+    """`_StressCall` (mode, em: those of E) with the eigenstrain of the call."""
+    mode_z: int = 0
+    em_z: bool = False
+    nc0: int = 0
+    zhead: tuple = ()       # lam1, mu1, plane_strain, E and its strides, eps0 and its strides
+
+    def eps0_out(self):
+        """(array, stride per component, per element) of the kernels' d / d eps0: (m, nc0, Bp) where the caller's
+        (B, m, nc0) is one transposing pass away, else (nc0, m, Bp)."""
+        m, nc0, Bp = self.plan.m, self.nc0, self.Bp
+        if self.mode_z == K_SAMPLE_ELEM and not self.em_z:
+            return torch.empty((m, nc0, Bp), dtype=torch.float64, device=self.plan.device), Bp, nc0 * Bp
+        return torch.empty((nc0, m, Bp), dtype=torch.float64, device=self.plan.device), m * Bp, Bp
+
+    def eps0_grad(self, d: torch.Tensor, shape) -> torch.Tensor:
+        """That array in the shape of the caller's eps0.  A tensor shared over elements or samples is a torch `sum` of the
+        contiguous (nc0, m, Bp) array (padding samples hold zeros) over the shared axes: a reduction whose order torch
+        decides, like the batch sum of an unbatched u's gradient and autograd's sum over a broadcast load (DESIGN
+        section 7, "Eigenstrain")."""
+        m, nc0, B, Bp = self.plan.m, self.nc0, self.B, self.Bp
+        if self.mode_z == K_SAMPLE_ELEM:
+            if self.em_z:
+                return (d if Bp == B else d[..., :B].contiguous()).reshape(shape)
+            return self.eng.to_sample_major(d.view(m * nc0, Bp), B, Bp, m * nc0).reshape(shape)
+        if self.mode_z == K_ELEM:
+            return d.sum(dim=2).t().reshape(shape)
+        if self.mode_z == K_SAMPLE:
+            return d.sum(dim=1)[:, :B].t().reshape(shape)
+        return d.sum(dim=(1, 2)).reshape(shape)
+
+
+def _eigen_call(solver: "ElasticFESolver", eps0, E, node_major: bool, B_hint: Optional[int], collapse: bool,
+                u=None) -> _EigenCall:
+    """The device views and facts of one eigenstrain call.  collapse: with neither eps0 nor E batched the call is one
+    sample whatever the hint says (a load every sample shares)."""
+    plan = solver._plan()
+    d, n, m = plan.dim, plan.n, plan.m
+    nc0 = eigen_components(d, solver.plane)
+    B0 = _eigen_batch(eps0, E, m, nc0, node_major, B_hint)
+    mode_z, B, em_z = _kappa_layout(eps0, m, B0, node_major, nc0)
+    mode, B_e, em = _kappa_layout(E, m, B0, node_major)
+    if B_e != B:
+        raise ValueError(f"E batch {B_e} does not match eigenstrain batch {B}")
+    batched = B0 is not None
+    if collapse and mode_z in (K_SCALAR, K_ELEM) and mode in (K_SCALAR, K_ELEM):
+        B, batched = 1, False
+    Bp = padded_batch(B)
+    eng = _Engine(plan, 0.0, 0, 0, "gather")
+    call = _EigenCall(plan, eng, B, Bp, mode, em, batched, node_major, (), d * (d + 1) // 2, mode_z, em_z, nc0)
+    kdev, kse, ksb, _ = eng.kappa_device(E, mode, B, Bp, em=em)
+    zdev, zc, ze, zb, _ = eng.tensor_device(eps0, mode_z, B, Bp, nc0, em=em_z)
+    call.zhead = (solver._lam1, solver._mu1, int(solver.plane == "strain"), kdev, kse, ksb, zdev, zc, ze, zb)
+    if u is not None:
+        udev = call.rows_in(u, n * d, u.dim() == 3)
+        call.head = (plan.elems, plan.oriented_gradient_table(), d, *call.zhead[:3], udev, *call.zhead[3:])
+    return call
+
+
+def _load_shape(call: _EigenCall):
+    n, d = call.plan.n, call.plan.dim
+    return (n, d, call.B) if call.node_major else ((call.B, n, d) if call.batched else (n, d))
+
+
+def _hint(B_hint: int) -> Optional[int]:
+    return None if B_hint < 0 else B_hint
+
+
+@torch.library.custom_op("diffhe::eigenstrain_load", mutates_args=())
+def eigenstrain_load_op(eps0: torch.Tensor, E: torch.Tensor, handle: int, node_major: bool, B_hint: int) -> torch.Tensor:
+    """F0 of the eigenstrain eps0 and the modulus E for the `ElasticFESolver` registered under `handle`; B_hint: the
+    batch of the right-hand side the load joins, -1 for none."""
+    call = _eigen_call(_SOLVERS[handle], eps0, E, node_major, _hint(B_hint), True)
+    plan = call.plan
+    F0 = torch.empty((plan.n * plan.dim, call.Bp), dtype=torch.float64, device=plan.device)
+    _, vol = plan.gradient_table()
+    _hip.lib().diffhe_eigenstrain_load(*plan.shape_incidence(), plan.oriented_gradient_table(), vol, plan.dim, *call.zhead,
+                                       plan.n, plan.m, call.B, call.Bp, F0, _stream(plan.device))
+    return call.rows_out(F0, plan.n * plan.dim).reshape(_load_shape(call)).to(eps0.device)
+
+
+@eigenstrain_load_op.register_fake
+def _eigenstrain_load_fake(eps0, E, handle, node_major, B_hint):
+    solver = _SOLVERS[handle]
+    n, d, m = solver.mesh.n_nodes, solver.mesh.dim, solver.mesh.n_elements
+    nc0 = eigen_components(d, solver.plane)
+    B0 = _eigen_batch(eps0, E, m, nc0, node_major, _hint(B_hint))
+    mode_z, B, _ = _kappa_layout(eps0, m, B0, node_major, nc0)
+    mode, _, _ = _kappa_layout(E, m, B0, node_major)
+    if mode_z in (K_SCALAR, K_ELEM) and mode in (K_SCALAR, K_ELEM):
+        B, B0 = 1, None
+    return eps0.new_empty((n, d, B) if node_major else ((B, n, d) if B0 is not None else (n, d)), dtype=torch.float64)
+
+
+@torch.library.custom_op("diffhe::eigenstrain_load_backward", mutates_args=())
+def eigenstrain_load_backward(gbar: torch.Tensor, eps0: torch.Tensor, E: torch.Tensor, handle: int, node_major: bool,
+                              B_hint: int, need_z: bool, need_e: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dL/deps0, dL/dE) of `eigenstrain_load` for the cotangent of F0; unused ones come back empty."""
+    call = _eigen_call(_SOLVERS[handle], eps0, E, node_major, _hint(B_hint), True)
+    plan, B, Bp = call.plan, call.B, call.Bp
+    L, st = _hip.lib(), _stream(plan.device)
+    _, vol = plan.gradient_table()
+    w = call.rows_in(gbar, plan.n * plan.dim, call.batched)
+    head = (plan.elems, plan.oriented_gradient_table(), vol, plan.dim, *call.zhead, w, plan.n, plan.m, B, Bp)
+    deps, osc, ose = call.eps0_out() if need_z else (None, 0, 0)
+    grad_z = grad_e = None
+    fused = need_z and need_e and call.mode != K_ELEM           # one element pass for both
+    if need_e:
+        sums, de = call.eng.element_grad(
+            call.mode, call.em, B, Bp, None,
+            lambda de_e, _osc, _ose, part, total: L.diffhe_eigenstrain_load_adjoint(
+                *head, deps if fused else None, osc, ose, de_e, part, total, st),
+            lambda de, _osc, _ose: L.diffhe_eigenstrain_load_adjoint_shared(*head, de, st))
+        grad_e = _kappa_grad(call.mode, E.shape, sums, de).to(E.device)
+    if need_z:
+        if not fused:
+            L.diffhe_eigenstrain_load_adjoint(*head, deps, osc, ose, None, None, None, st)
+        grad_z = call.eps0_grad(deps, eps0.shape).to(eps0.device)
+    return _like_grads(gbar, (grad_z, grad_e), (eps0, E))
+
+
+@eigenstrain_load_backward.register_fake
+def _eigenstrain_load_backward_fake(gbar, eps0, E, handle, node_major, B_hint, need_z, need_e):
+    return _fake_grads(gbar, (need_z, need_e), (eps0, E))
+
+
+def _load_setup_context(ctx, inputs, output):
+    eps0, E, ctx.handle, node_major, ctx.B_hint = inputs
+    ctx.node_major = bool(node_major)
+    ctx.solver = _SOLVERS[ctx.handle]       # the registry holds it weakly: the graph keeps it alive for backward
+    ctx.save_for_backward(eps0, E)
+
+
+def _load_backward(ctx, grad_F):
+    if torch.is_grad_enabled():
+        raise NotImplementedError("diffhe: second-order derivatives of an eigenstrain load are not implemented (backward "
+                                  "with create_graph=True, diffhe.elastic)")
+    eps0, E = ctx.saved_tensors
+    need_z, need_e = (bool(v) for v in ctx.needs_input_grad[:2])
+    if not (need_z or need_e):
+        return (None,) * 5
+    _SOLVERS[ctx.handle] = ctx.solver
+    dz, de = torch.ops.diffhe.eigenstrain_load_backward(grad_F.contiguous(), eps0, E, ctx.handle, ctx.node_major,
+                                                        ctx.B_hint, need_z, need_e)
+    return (dz if need_z else None, de if need_e else None, None, None, None)
+
+
+torch.library.register_autograd("diffhe::eigenstrain_load", _load_backward, setup_context=_load_setup_context)
+
+
+def _stress_shapes_eigen(solver, u, E, eps0, node_major):
+    m, d = solver.mesh.n_elements, solver.mesh.dim
+    nc, nc0 = d * (d + 1) // 2, eigen_components(d, solver.plane)
+    B0 = _eigen_batch(eps0, E, m, nc0, node_major, _stress_batch(u, node_major))
+    _, B, _ = _kappa_layout(eps0, m, B0, node_major, nc0)
+    if node_major:
+        return (m, nc, B), (m, B)
+    return ((B, m, nc), (B, m)) if B0 is not None else ((m, nc), (m,))
+
+
+@torch.library.custom_op("diffhe::elastic_stress_eigen", mutates_args=())
+def elastic_stress_eigen(u: torch.Tensor, E: torch.Tensor, eps0: torch.Tensor, handle: int, node_major: bool,
+                         want_sigma: bool, want_vm: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(sigma, vm) of `elastic_stress` with the eigenstrain eps0: sigma = E (s(u) - s0)."""
+    solver = _SOLVERS[handle]
+    call = _eigen_call(solver, eps0, E, node_major, _stress_batch(u, node_major), False, u=u)
+    plan, m, nc, Bp = call.plan, call.plan.m, call.nc, call.Bp
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=plan.device)  # noqa: E731
+    sigma, vm = (new(m * nc, Bp) if want_sigma else None), (new(m, Bp) if want_vm else None)
+    _hip.lib().diffhe_stress_eval_eigen(*call.head, plan.n, m, Bp, sigma, Bp, nc * Bp, vm, _stream(plan.device))
+    s_shape, v_shape = _stress_shapes_eigen(solver, u, E, eps0, node_major)
+    sigma = u.new_empty(0) if sigma is None else call.rows_out(sigma, m * nc).reshape(s_shape).to(u.device)
+    vm = u.new_empty(0) if vm is None else call.rows_out(vm, m).reshape(v_shape).to(u.device)
+    return sigma, vm
+
+
+@elastic_stress_eigen.register_fake
+def _elastic_stress_eigen_fake(u, E, eps0, handle, node_major, want_sigma, want_vm):
+    s_shape, v_shape = _stress_shapes_eigen(_SOLVERS[handle], u, E, eps0, node_major)
+    return (u.new_empty(s_shape if want_sigma else 0, dtype=torch.float64),
+            u.new_empty(v_shape if want_vm else 0, dtype=torch.float64))
+
+
+@torch.library.custom_op("diffhe::elastic_stress_eigen_backward", mutates_args=())
+def elastic_stress_eigen_backward(sigma_bar: torch.Tensor, vm_bar: torch.Tensor, u: torch.Tensor, E: torch.Tensor,
+                                  eps0: torch.Tensor, handle: int, node_major: bool, need_u: bool, need_e: bool,
+                                  need_z: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dL/du, dL/dE, dL/deps0) of `elastic_stress_eigen` for the cotangents of sigma and vm (empty = absent); unused
+    ones come back empty.  One element pass feeds all three where the dE of the call is per sample."""
+    call = _eigen_call(_SOLVERS[handle], eps0, E, node_major, _stress_batch(u, node_major), False, u=u)
+    plan, eng, nc, B, Bp, mode = call.plan, call.eng, call.nc, call.B, call.Bp, call.mode
+    d, n, m = plan.dim, plan.n, plan.m
+    L, st = _hip.lib(), _stream(plan.device)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=plan.device)  # noqa: E731
+    sb = call.rows_in(sigma_bar, m * nc, True) if sigma_bar.numel() else None
+    vb = call.rows_in(vm_bar, m, True) if vm_bar.numel() else None
+    head = (*call.head, sb, Bp, nc * Bp, vb)
+    ubar = new(n * d, Bp) if need_u else None
+    deps, dzc, dze = call.eps0_out() if need_z else (None, 0, 0)
+
+    def adjoint(side, de_e, part, total):
+        """The element pass (and the node pass) with the side products u_bar and d / d eps0, or with dE alone."""
+        nodes = side and need_u
+        lists = plan.shape_incidence() if nodes else (None, None)
+        L.diffhe_stress_adjoint_eigen(*head, *lists, n, m, B, Bp, new(nc, m, Bp) if nodes else None,
+                                      ubar if nodes else None, de_e, part, total, deps if side else None, dzc, dze, st)
+
+    grad_u = grad_e = grad_z = None
+    side = need_u or need_z
+    fused = side and need_e and mode != K_ELEM
+    if need_e:
+        sums, de = eng.element_grad(mode, call.em, B, Bp, None,
+                                    lambda de_e, osc, ose, part, total: adjoint(fused, de_e, part, total),
+                                    lambda de, osc, ose: L.diffhe_stress_adjoint_eigen_shared(*head, n, m, B, Bp, de, st))
+        grad_e = _kappa_grad(mode, E.shape, sums, de).to(E.device)
+    if side and not fused:
+        adjoint(True, None, None, None)
+    if need_u:
+        du = call.rows_out(ubar, n * d)
+        if node_major:
+            grad_u = du.reshape(n, d, B)
+        else:
+            du = du.reshape(B, n, d)
+            grad_u = du if u.dim() == 3 else du.sum(dim=0)
+        grad_u = grad_u.to(u.device)
+    if need_z:
+        grad_z = call.eps0_grad(deps, eps0.shape).to(eps0.device)
+    return _like_grads(u, (grad_u, grad_e, grad_z), (u, E, eps0))
+
+
+@elastic_stress_eigen_backward.register_fake
+def _elastic_stress_eigen_backward_fake(sigma_bar, vm_bar, u, E, eps0, handle, node_major, need_u, need_e, need_z):
+    return _fake_grads(u, (need_u, need_e, need_z), (u, E, eps0))
+
+
+def _stress_eigen_setup_context(ctx, inputs, output):
+    u, E, eps0, handle, node_major = inputs[:5]
+    ctx.handle, ctx.node_major = handle, bool(node_major)
+    ctx.solver = _SOLVERS[handle]           # the registry holds it weakly: the graph keeps it alive for backward
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(u, E, eps0)
+
+
+def _stress_eigen_backward(ctx, grad_sigma, grad_vm):
+    if torch.is_grad_enabled():
+        raise NotImplementedError("diffhe: second-order derivatives of an elastic stress evaluation are not implemented "
+                                  "(backward with create_graph=True, diffhe.elastic)")
+    u, E, eps0 = ctx.saved_tensors
+    needs = tuple(bool(v) for v in ctx.needs_input_grad[:3])
+    absent = lambda g: g is None or g.numel() == 0  # noqa: E731
+    if not any(needs) or (absent(grad_sigma) and absent(grad_vm)):
+        return (None,) * 7
+    empty = u.new_empty(0)
+    _SOLVERS[ctx.handle] = ctx.solver
+    grads = torch.ops.diffhe.elastic_stress_eigen_backward(empty if absent(grad_sigma) else grad_sigma.contiguous(),
+                                                           empty if absent(grad_vm) else grad_vm.contiguous(), u, E, eps0,
+                                                           ctx.handle, ctx.node_major, *needs)
+    return (*(g if need else None for g, need in zip(grads, needs)), None, None, None, None)
+
+
+torch.library.register_autograd("diffhe::elastic_stress_eigen", _stress_eigen_backward,
+                                setup_context=_stress_eigen_setup_context)
+
+
+def thermal_strain(alpha, dT: torch.Tensor, dim: int, plane: Optional[str] = None) -> torch.Tensor:
+    """The isotropic eigenstrain eps0 = alpha dT on the normal components, shears zero: (m, nc0) or (B, m, nc0) for dT (m,)
+    or (B, m), nc0 = 6 in 3D, 3 in plane stress (the 2D default), 4 in plane strain (zz included: the expansion out of
+    the plane is constrained).  alpha: a number or a tensor that broadcasts against dT, e.g. per element (m,).  Plain
+    differentiable torch."""
+    if dim not in (2, 3):
+        raise ValueError(f"thermal_strain: dim must be 2 or 3, got {dim!r}")
+    if dim == 3 and plane is not None:
+        raise ValueError("plane= applies to 2D only")
+    plane = None if dim == 3 else ("stress" if plane is None else plane)
+    if dim == 2 and plane not in ("stress", "strain"):
+        raise ValueError(f"Unknown plane: {plane!r} (\"stress\" or \"strain\")")
+    if dT.dim() not in (1, 2):
+        raise ValueError(f"thermal_strain: dT must be (m,) or (B, m), got {tuple(dT.shape)}")
+    v = torch.as_tensor(alpha, dtype=dT.dtype, device=dT.device) * dT
+    zero = torch.zeros_like(v)
+    parts = {6: (v, v, v, zero, zero, zero), 4: (v, v, zero, v), 3: (v, v, zero)}[eigen_components(dim, plane)]
+    return torch.stack(parts, dim=-1)
+
+
+def element_mean(T: torch.Tensor, mesh) -> torch.Tensor:
+    """The mean of a nodal field (n,) or (B, n) over the vertices of every element: (m,) or (B, m).  Plain differentiable
+    torch; with `thermal_strain` it carries the temperature of a heat solve to an eigenstrain."""
+    if T.dim() not in (1, 2) or T.shape[-1] != mesh.n_nodes:
+        raise ValueError(f"element_mean: T must be (n,) or (B, n) with n={mesh.n_nodes}, got {tuple(T.shape)}")
+    return T[..., mesh.elements.to(T.device).long()].mean(dim=-1)
+
+
 def pnorm(vm: torch.Tensor, p: float = 8.0, weights: Optional[torch.Tensor] = None, dim: int = -1) -> torch.Tensor:
     """The weighted p-mean (sum_e w_e vm_e^p / sum_e w_e)^(1/p) over the element axis `dim` of a non-negative field: the
     last axis of `von_mises(..., layout="sample")`, the first (dim=0) of layout="node".  It lies between max(vm) m^(-1/p)
@@ -737,9 +1075,10 @@ class ElasticFESolver(nn.Module):
         return t.to(torch.float64)
 
     def forward(self, f: Optional[torch.Tensor] = None, load: Optional[torch.Tensor] = None, layout: str = "sample",
-                dirichlet=None, h=None, u_inf=None, flux=None) -> torch.Tensor:
+                dirichlet=None, h=None, u_inf=None, flux=None, eigenstrain=None) -> torch.Tensor:
         """u for the body force f and the nodal load: (n, d), (B, n, d), or (n, d, B) with layout="node" -- the shape of
-        the right-hand side.  f None: zero."""
+        the right-hand side.  f None: zero.  eigenstrain: an initial strain eps0 (layouts: `eigenstrain_load`), whose
+        load F0(eps0, E) joins `load` in front of the unchanged solve; None takes exactly the path without it."""
         if dirichlet is not None:
             raise NotImplementedError("diffhe: dirichlet= is not implemented for elasticity (the boundary-band kernels "
                                       "read scalar element tables); give prescribed displacements with fixed=")
@@ -752,6 +1091,8 @@ class ElasticFESolver(nn.Module):
             raise NotImplementedError("diffhe: node gradients are not implemented for elasticity (mesh.nodes requires "
                                       "grad)")
         f64, load64 = self._checked(f, "f", layout), self._checked(load, "load", layout)
+        if eigenstrain is not None:
+            load64 = self._with_eigenstrain_load(eigenstrain, f64, load64, layout)
         if layout == "node":
             if f64 is None and load64 is None:
                 raise ValueError("layout='node' needs f or load to carry the batch: (n, d, B)")
@@ -769,8 +1110,65 @@ class ElasticFESolver(nn.Module):
         u, _token = torch.ops.diffhe.elastic_solve(E, f_in, load_in, id(self), save, layout == "node")
         return u
 
+    # -- eigenstrain ----------------------------------------------------------------------------------
+    def _checked_eps0(self, eps0, layout: str) -> torch.Tensor:
+        m, d = self.mesh.n_elements, self.mesh.dim
+        nc0 = eigen_components(d, self.plane)
+        eps0 = eps0 if isinstance(eps0, torch.Tensor) else torch.as_tensor(eps0, dtype=torch.float64)
+        if layout == "node" and eps0.dim() == 3 and tuple(eps0.shape[:2]) == (nc0, m):
+            return eps0.to(torch.float64)
+        if eps0.dim() not in (1, 2, 3) or eps0.shape[-1] != nc0 or (eps0.dim() == 3 and eps0.shape[1] != m):
+            if self.plane == "stress" and eps0.dim() >= 1 and eps0.shape[-1] == 4:
+                raise ValueError("eigenstrain: plane stress takes 3 components (xx, yy, xy); a zz component has no effect "
+                                 "there (it is plane strain that constrains it)")
+            raise ValueError(f"eigenstrain must be ({nc0},), (B, {nc0}), ({m}, {nc0}) or (B, {m}, {nc0}) in Voigt components"
+                             + (f", or ({nc0}, {m}, B) with layout='node'" if layout == "node" else "")
+                             + f", got {tuple(eps0.shape)}")
+        return eps0.to(torch.float64)
+
+    def _modulus(self, E) -> torch.Tensor:
+        if E is None:
+            return self._E
+        return (E if isinstance(E, torch.Tensor) else torch.as_tensor(E, dtype=torch.float64)).to(torch.float64)
+
+    def _eigenstrain_load(self, eps0, E, layout: str, B_hint: Optional[int]) -> torch.Tensor:
+        if layout not in ("sample", "node"):
+            raise ValueError(f"Unknown layout: {layout!r}")
+        if self.mesh.nodes.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("diffhe: node gradients are not implemented for elasticity (mesh.nodes requires "
+                                      "grad)")
+        eps0, E = self._checked_eps0(eps0, layout), self._modulus(E)
+        m, nc0, node = self.mesh.n_elements, eigen_components(self.mesh.dim, self.plane), layout == "node"
+        B0 = _eigen_batch(eps0, E, m, nc0, node, B_hint)                     # the refusals, before the op
+        if _kappa_layout(eps0, m, B0, node, nc0)[1] != _kappa_layout(E, m, B0, node)[1]:
+            raise ValueError("E batch does not match eigenstrain batch")
+        _SOLVERS[id(self)] = self
+        return torch.ops.diffhe.eigenstrain_load(eps0, E, id(self), node, -1 if B_hint is None else int(B_hint))
+
+    def eigenstrain_load(self, eps0, E=None, layout: str = "sample") -> torch.Tensor:
+        """The nodal load F0 = sum_e vol_e E_e B_e^T D eps0_e of an eigenstrain (initial strain: thermal expansion,
+        swelling, pre-stress), as `load=` takes it: (n, d), (B, n, d), or (n, d, B) with layout="node".  eps0 in Voigt
+        components -- (xx, yy, xy) in plane stress, (xx, yy, xy, zz) in plane strain, (xx, yy, zz, yz, xz, xy) in 3D, shear
+        components not doubled -- as (nc0,), (B, nc0), (m, nc0), (B, m, nc0), or (nc0, m, B) with layout="node"; E: None
+        for the solver's, or any layout E takes.  The batch is that of whichever shows one; an (m, nc0) or (m,) operand
+        next to a batch of m reads as one value per sample, as kappa does next to f.  Differentiable in eps0 and E."""
+        return self._eigenstrain_load(eps0, E, layout, None)
+
+    def _with_eigenstrain_load(self, eps0, f64, load64, layout: str):
+        """load + F0(eps0, E) for `forward`: the batch of f / load decides how eps0 reads; a load every sample shares stays
+        unbatched where that layout exists."""
+        node = layout == "node"
+        src = f64 if f64 is not None else load64
+        B_rhs = None if src is None else (src.shape[2] if node else (src.shape[0] if src.dim() == 3 else None))
+        if load64 is not None and load64.dim() == 3 and not node:
+            B_rhs = load64.shape[0]
+        F0 = self._eigenstrain_load(eps0, None, layout, B_rhs)
+        if node and src is not None and F0.shape[2] == 1 and src.shape[2] != 1:
+            F0 = F0.expand(src.shape)
+        return F0 if load64 is None else load64.to(F0.device) + F0
+
     # -- stress recovery ----------------------------------------------------------------------------
-    def _stress_op(self, u, E, layout: str, want_sigma: bool, want_vm: bool):
+    def _stress_op(self, u, E, layout: str, want_sigma: bool, want_vm: bool, eigenstrain=None):
         n, d = self.mesh.n_nodes, self.mesh.dim
         if layout not in ("sample", "node"):
             raise ValueError(f"Unknown layout: {layout!r}")
@@ -788,24 +1186,35 @@ class ElasticFESolver(nn.Module):
             raise NotImplementedError("diffhe: node gradients are not implemented for elasticity (mesh.nodes requires "
                                       "grad)")
         u, E = u.to(torch.float64), E.to(torch.float64)
+        if eigenstrain is not None:
+            eps0 = self._checked_eps0(eigenstrain, layout)
+            m, nc0, node = self.mesh.n_elements, eigen_components(self.mesh.dim, self.plane), layout == "node"
+            B0 = _eigen_batch(eps0, E, m, nc0, node, _stress_batch(u, node))
+            if _kappa_layout(eps0, m, B0, node, nc0)[1] != _kappa_layout(E, m, B0, node)[1]:
+                raise ValueError("E batch does not match eigenstrain batch")
+            _SOLVERS[id(self)] = self
+            return torch.ops.diffhe.elastic_stress_eigen(u, E, eps0, id(self), node, want_sigma, want_vm)
         _kappa_layout(E, self.mesh.n_elements, _stress_batch(u, layout == "node"), layout == "node")
         _SOLVERS[id(self)] = self
         return torch.ops.diffhe.elastic_stress(u, E, id(self), layout == "node", want_sigma, want_vm)
 
-    def stress(self, u: torch.Tensor, E=None, layout: str = "sample") -> torch.Tensor:
+    def stress(self, u: torch.Tensor, E=None, layout: str = "sample", eigenstrain=None) -> torch.Tensor:
         """Element stresses sigma = E (2 mu' eps + lambda' tr(eps) I) of the displacement u -- (n, d), (B, n, d), or
         (n, d, B) with layout="node", what `forward` returns -- in Voigt components (xx, yy, xy | xx, yy, zz, yz, xz, xy;
         shear components are tensor components): (m, nc), (B, m, nc), or (m, nc, B) with layout="node".  E: None for the
         solver's, or another modulus in any layout E takes (the relaxed stress of stress-constrained design); an
-        unbatched u is broadcast to the batch of E.  u and E may require grad."""
-        return self._stress_op(u, E, layout, True, False)[0]
+        unbatched u is broadcast to the batch of E.  eigenstrain: None, or the initial strain eps0 of the solve (layouts:
+        `eigenstrain_load`): sigma = E (s(u) - s0), and in plane strain sigma_zz = E [lambda' (tr eps(u) - tr eps0) -
+        2 mu' eps0_zz] enters `von_mises`.  u, E and eps0 may require grad."""
+        return self._stress_op(u, E, layout, True, False, eigenstrain)[0]
 
-    def von_mises(self, u: torch.Tensor, E=None, layout: str = "sample") -> torch.Tensor:
+    def von_mises(self, u: torch.Tensor, E=None, layout: str = "sample", eigenstrain=None) -> torch.Tensor:
         """The von Mises stress per element, (m,), (B, m), or (m, B) with layout="node"; in 2D it includes the
         out-of-plane sigma_zz (0 in plane stress, nu (sigma_xx + sigma_yy) in plane strain).  No stress array is formed.
         Its derivative is defined as 0 where the stress vanishes.  Arguments as `stress`."""
-        return self._stress_op(u, E, layout, False, True)[1]
+        return self._stress_op(u, E, layout, False, True, eigenstrain)[1]
 
-    def stress_and_von_mises(self, u: torch.Tensor, E=None, layout: str = "sample") -> Tuple[torch.Tensor, torch.Tensor]:
+    def stress_and_von_mises(self, u: torch.Tensor, E=None, layout: str = "sample",
+                             eigenstrain=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(`stress`, `von_mises`) from one pass over the elements, and one backward pass for both cotangents."""
-        return self._stress_op(u, E, layout, True, True)
+        return self._stress_op(u, E, layout, True, True, eigenstrain)
