@@ -6,7 +6,13 @@
 // partials in a fixed order, then a sum over the blocks in block order -- and nothing uses atomics: results are bitwise
 // reproducible.  Small per-sample matrices are (rows, cols, Bp), entry (r, c) of sample b at (r * p + c) * Bp + b; the
 // symmetric Gram matrices are packed by rows of their upper triangle, q(i, j) = i p - i (i - 1) / 2 + (j - i), i <= j.
+//
+// The passes that weigh rows by the mass read it through an accessor, a template argument: NodalMass is one (n,) vector
+// the batch shares, mass[row] -- the diffhe_eig_* entries (diffhe.eigen) -- and SampleMass<D> a nodal mass per sample
+// under D unknowns per node, mass[(row / D) * ms + b * mb] with row = node * D + component -- the diffhe_modal_* entries
+// (diffhe.modal, include/diffhe_modal.h).  D is a compile-time constant: no integer division runs in the row loops.
 #include "common.h"
+#include "diffhe_modal.h"
 
 #include <math.h>
 
@@ -20,6 +26,18 @@ constexpr int kTile = 4;        // column tile of the Gram pass: 2 x 16 accumula
 constexpr int kLdsEntries = 128;  // p x (output columns per pass) of the rotation: 128 x 64 lanes x 8 B = 64 KiB of LDS
 
 __host__ __device__ inline int packed(int i, int j, int p) { return i * p - i * (i - 1) / 2 + (j - i); }
+
+struct NodalMass {
+  const double* __restrict__ m;
+  __device__ __forceinline__ double operator()(int row, int) const { return m[row]; }
+};
+
+template <int D>
+struct SampleMass {
+  const double* __restrict__ m;
+  i64 ms, mb;
+  __device__ __forceinline__ double operator()(int row, int b) const { return m[(i64)(row / D) * ms + (i64)b * mb]; }
+};
 
 inline int lanes_of(int Bp) { return Bp < kWave ? Bp : kWave; }
 
@@ -35,8 +53,9 @@ inline int reduce_blocks(int n, int Bp) {
 // of column tiles of kTile; a diagonal pair reads 2 kTile columns per node, an off-diagonal one 3 kTile.
 // part: (blocks, 2, nq, Bp) block partials, GA first.
 // ---------------------------------------------------------------------------------------------------------------------
+template <class Mass>
 __global__ __launch_bounds__(256) void gram_kernel(const double* __restrict__ Y, const double* __restrict__ AY,
-                                                   const double* __restrict__ mass,
+                                                   const Mass mass,
                                                    const unsigned char* __restrict__ is_bc, int p, int n, int Bp, int nt,
                                                    double* __restrict__ part) {
   __shared__ double lds[4 * kWave];
@@ -56,7 +75,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const double* __restrict__ Y,
   for (int i = nm.node0; i < n; i += nm.stride) {
     if (is_bc && is_bc[i]) continue;
     const i64 o = (i64)i * Bp + nm.b;
-    const double mi = mass[i];
+    const double mi = mass(i, nm.b);
     double yi[kTile], yj[kTile], aj[kTile];
 #pragma unroll
     for (int t = 0; t < kTile; ++t) {
@@ -250,10 +269,10 @@ __global__ __launch_bounds__(64) void ritz_kernel(const double* __restrict__ GA,
 // Rotate: X = Y C, AX = AY C and, from the same registers, MX = M X and R = theta M X - A X (each optional).  The block's
 // 64 samples share `oc` columns of C in LDS (p * oc <= kLdsEntries); blockIdx.z walks the output-column chunks.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int PT>
+template <int PT, class Mass>
 __global__ __launch_bounds__(256) void rotate_kernel(const double* __restrict__ Y, const double* __restrict__ AY,
                                                      const double* __restrict__ C, const double* __restrict__ theta,
-                                                     const double* __restrict__ mass, int p, int n, int Bp, int oc,
+                                                     const Mass mass, int p, int n, int Bp, int oc,
                                                      double* __restrict__ X, double* __restrict__ AX,
                                                      double* __restrict__ MX, double* __restrict__ R) {
   extern __shared__ double Cs[];
@@ -272,7 +291,7 @@ __global__ __launch_bounds__(256) void rotate_kernel(const double* __restrict__ 
   const i64 cs = (i64)n * Bp;
   for (int i = nm.node0; i < n; i += nm.stride) {
     const i64 o = (i64)i * Bp + nm.b;
-    const double mi = mass[i];
+    const double mi = mass(i, nm.b);
     double y[PT], a[PT];
 #pragma unroll
     for (int j = 0; j < PT; ++j) {
@@ -300,7 +319,8 @@ __global__ __launch_bounds__(256) void rotate_kernel(const double* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------------
 // Residual: part[blk, c, b] = sum over the nodes of the block of R[c, i, b]^2 / m_i; blockIdx.z = column.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void resid_kernel(const double* __restrict__ R, const double* __restrict__ mass, int p,
+template <class Mass>
+__global__ __launch_bounds__(256) void resid_kernel(const double* __restrict__ R, const Mass mass, int p,
                                                     int n, int Bp, double* __restrict__ part) {
   __shared__ double lds[4 * kWave];
   const NodeMap nm = node_map(Bp);
@@ -309,7 +329,7 @@ __global__ __launch_bounds__(256) void resid_kernel(const double* __restrict__ R
   double acc = 0.0;
   for (int i = nm.node0; i < n; i += nm.stride) {
     const double v = r[(i64)i * Bp + nm.b];
-    const double mi = mass[i];
+    const double mi = mass(i, nm.b);
     if (mi > 0.0) acc += v * v / mi;
   }
   const double s = block_sum_per_sample(acc, Bp, lds);
@@ -334,7 +354,8 @@ __global__ __launch_bounds__(64) void resid_final_kernel(const double* __restric
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ inline double larger_mag(double a, double b) { return fabs(b) > fabs(a) ? b : a; }
 
-__global__ __launch_bounds__(256) void sign_kernel(const double* __restrict__ X, const double* __restrict__ mass, int k,
+template <class Mass>
+__global__ __launch_bounds__(256) void sign_kernel(const double* __restrict__ X, const Mass mass, int k,
                                                    int n, int Bp, double* __restrict__ part) {
   __shared__ double lds[4 * kWave];
   const NodeMap nm = node_map(Bp);
@@ -343,7 +364,7 @@ __global__ __launch_bounds__(256) void sign_kernel(const double* __restrict__ X,
   double acc = 0.0, e = 0.0;
   for (int i = nm.node0; i < n; i += nm.stride) {
     const double v = x[(i64)i * Bp + nm.b];
-    acc += mass[i] * v;
+    acc += mass(i, nm.b) * v;
     e = larger_mag(e, v);
   }
   const int LB = Bp < kWave ? Bp : kWave;
@@ -388,6 +409,99 @@ __global__ __launch_bounds__(256) void flip_kernel(double* __restrict__ X, const
 
 bool bad_block(int p, int n, int Bp) { return p < 1 || p > kMaxP || n < 1 || (i64)p * n * Bp >= (1LL << 40); }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side of the four mass-weighted passes, once for both accessors.  mass_bytes: the algorithmic bytes of the mass, read once (0 for
+// a vector the batch shares, as everywhere in account()).
+// ---------------------------------------------------------------------------------------------------------------------
+template <class Mass>
+int launch_gram(const double* Y, const double* AY, const Mass mass, double mass_bytes, const unsigned char* is_bc, int p,
+                int n, int Bp, double* part, double* GA, double* GM, void* stream) {
+  if (!Y || !AY || !mass.m || !part || !GA || !GM || bad_block(p, n, Bp)) return DIFFHE_E_BADARG;
+  if (!valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
+  const int nblk = reduce_blocks(n, Bp);
+  const int nt = (p + kTile - 1) / kTile, nq = p * (p + 1) / 2;
+  const unsigned gy = (unsigned)((Bp + kWave - 1) / kWave);
+  account(8.0 * Bp * (2.0 * p * n + 2.0 * nq * (2.0 * nblk + 1.0)) + mass_bytes);
+  hipLaunchKernelGGL(gram_kernel<Mass>, dim3((unsigned)nblk, gy, (unsigned)(nt * (nt + 1) / 2)), dim3(256), 0,
+                     (hipStream_t)stream, Y, AY, mass, is_bc, p, n, Bp, nt, part);
+  hipLaunchKernelGGL(sum_blocks_kernel, dim3(gy, (unsigned)(2 * nq)), dim3(64), 0, (hipStream_t)stream,
+                     (const double*)part, nblk, 2 * nq, Bp, GA, GM, nq);
+  return check_launch();
+}
+
+template <class Mass>
+int launch_rotate(const double* Y, const double* AY, const double* C, const double* theta, const Mass mass,
+                  double mass_bytes, int p, int n, int Bp, double* X, double* AX, double* MX, double* R, void* stream) {
+  if (!Y || !AY || !C || !mass.m || !X || !AX || (R && !theta) || bad_block(p, n, Bp) || X == Y || AX == AY || X == AY ||
+      AX == Y)
+    return DIFFHE_E_BADARG;
+  if (!valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
+  int oc = kLdsEntries / p;
+  if (oc > p) oc = p;
+  const int passes = (p + oc - 1) / oc;
+  const dim3 g = node_grid(n, Bp, 1024);
+  const dim3 grid(g.x, g.y, (unsigned)passes);
+  const size_t lds = sizeof(double) * (size_t)p * oc * lanes_of(Bp);
+  account(8.0 * Bp * (double)n * p * (2.0 + 2.0 + (MX ? 1.0 : 0.0) + (R ? 1.0 : 0.0)) + mass_bytes);
+  hipStream_t st = (hipStream_t)stream;
+#define DIFFHE_ROTATE(PT)                                                                                            \
+  hipLaunchKernelGGL((rotate_kernel<PT, Mass>), grid, dim3(256), lds, st, Y, AY, C, theta, mass, p, n, Bp, oc, X, AX, MX, \
+                     R)
+  if (p <= 4)
+    DIFFHE_ROTATE(4);
+  else if (p <= 8)
+    DIFFHE_ROTATE(8);
+  else if (p <= 12)
+    DIFFHE_ROTATE(12);
+  else
+    DIFFHE_ROTATE(16);
+#undef DIFFHE_ROTATE
+  return check_launch();
+}
+
+template <class Mass>
+int launch_residual(const double* R, const double* theta, const Mass mass, double mass_bytes, int p, int n, int Bp,
+                    double* part, double* rho, void* stream) {
+  if (!R || !theta || !mass.m || !part || !rho || bad_block(p, n, Bp)) return DIFFHE_E_BADARG;
+  if (!valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
+  const int nblk = reduce_blocks(n, Bp);
+  const unsigned gy = (unsigned)((Bp + kWave - 1) / kWave);
+  account(8.0 * Bp * ((double)p * n + p * (2.0 * nblk + 1.0)) + mass_bytes);
+  hipLaunchKernelGGL(resid_kernel<Mass>, dim3((unsigned)nblk, gy, (unsigned)p), dim3(256), 0, (hipStream_t)stream, R, mass,
+                     p, n, Bp, part);
+  hipLaunchKernelGGL(resid_final_kernel, dim3(gy, (unsigned)p), dim3(64), 0, (hipStream_t)stream, (const double*)part,
+                     theta, nblk, p, Bp, rho);
+  return check_launch();
+}
+
+template <class Mass>
+int launch_fix_sign(double* X, const Mass mass, double mass_bytes, int k, int n, int Bp, double* part, double* sgn,
+                    void* stream) {
+  if (!X || !mass.m || !part || !sgn || bad_block(k, n, Bp)) return DIFFHE_E_BADARG;
+  if (!valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
+  const int nblk = reduce_blocks(n, Bp);
+  const unsigned gy = (unsigned)((Bp + kWave - 1) / kWave);
+  account(8.0 * Bp * (double)k * n * 3.0 + mass_bytes);
+  hipLaunchKernelGGL(sign_kernel<Mass>, dim3((unsigned)nblk, gy, (unsigned)k), dim3(256), 0, (hipStream_t)stream,
+                     (const double*)X, mass, k, n, Bp, part);
+  hipLaunchKernelGGL(sign_final_kernel, dim3(gy, (unsigned)k), dim3(64), 0, (hipStream_t)stream, (const double*)part, nblk,
+                     k, Bp, sgn);
+  const dim3 g = node_grid(n, Bp, 1024);
+  hipLaunchKernelGGL(flip_kernel, dim3(g.x, g.y, (unsigned)k), dim3(256), 0, (hipStream_t)stream, X, (const double*)sgn, n,
+                     Bp);
+  return check_launch();
+}
+
+// f(SampleMass<d>, bytes of one read of the mass) for the d of a diffhe_modal_* call; n counts rows, node * d + component
+template <class F>
+int with_sample_mass(const double* mass, i64 ms, i64 mb, int d, int n, int Bp, F&& f) {
+  if (d < 1 || d > 3 || n % d != 0 || ms < 0 || mb < 0) return DIFFHE_E_BADARG;
+  const double bytes = mb ? 8.0 * Bp * (double)(n / d) : 0.0;
+  if (d == 1) return f(SampleMass<1>{mass, ms, mb}, bytes);
+  if (d == 2) return f(SampleMass<2>{mass, ms, mb}, bytes);
+  return f(SampleMass<3>{mass, ms, mb}, bytes);
+}
+
 }  // namespace
 
 extern "C" int diffhe_eig_gram_blocks(int n, int Bp) {
@@ -397,17 +511,7 @@ extern "C" int diffhe_eig_gram_blocks(int n, int Bp) {
 
 extern "C" int diffhe_eig_gram(const double* Y, const double* AY, const double* mass, const unsigned char* is_bc, int p,
                                int n, int Bp, double* part, double* GA, double* GM, void* stream) {
-  if (!Y || !AY || !mass || !part || !GA || !GM || bad_block(p, n, Bp)) return DIFFHE_E_BADARG;
-  if (!valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
-  const int nblk = reduce_blocks(n, Bp);
-  const int nt = (p + kTile - 1) / kTile, nq = p * (p + 1) / 2;
-  const unsigned gy = (unsigned)((Bp + kWave - 1) / kWave);
-  account(8.0 * Bp * (2.0 * p * n + 2.0 * nq * (2.0 * nblk + 1.0)));
-  hipLaunchKernelGGL(gram_kernel, dim3((unsigned)nblk, gy, (unsigned)(nt * (nt + 1) / 2)), dim3(256), 0,
-                     (hipStream_t)stream, Y, AY, mass, is_bc, p, n, Bp, nt, part);
-  hipLaunchKernelGGL(sum_blocks_kernel, dim3(gy, (unsigned)(2 * nq)), dim3(64), 0, (hipStream_t)stream,
-                     (const double*)part, nblk, 2 * nq, Bp, GA, GM, nq);
-  return check_launch();
+  return launch_gram(Y, AY, NodalMass{mass}, 0.0, is_bc, p, n, Bp, part, GA, GM, stream);
 }
 
 extern "C" int diffhe_eig_ritz(const double* GA, const double* GM, int p, int Bp, int sweeps, double* work, double* C,
@@ -421,59 +525,48 @@ extern "C" int diffhe_eig_ritz(const double* GA, const double* GM, int p, int Bp
 extern "C" int diffhe_eig_rotate(const double* Y, const double* AY, const double* C, const double* theta,
                                  const double* mass, int p, int n, int Bp, double* X, double* AX, double* MX, double* R,
                                  void* stream) {
-  if (!Y || !AY || !C || !mass || !X || !AX || (R && !theta) || bad_block(p, n, Bp) || X == Y || AX == AY || X == AY ||
-      AX == Y)
-    return DIFFHE_E_BADARG;
-  if (!valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
-  int oc = kLdsEntries / p;
-  if (oc > p) oc = p;
-  const int passes = (p + oc - 1) / oc;
-  const dim3 g = node_grid(n, Bp, 1024);
-  const dim3 grid(g.x, g.y, (unsigned)passes);
-  const size_t lds = sizeof(double) * (size_t)p * oc * lanes_of(Bp);
-  account(8.0 * Bp * (double)n * p * (2.0 + 2.0 + (MX ? 1.0 : 0.0) + (R ? 1.0 : 0.0)));
-  hipStream_t st = (hipStream_t)stream;
-#define DIFFHE_ROTATE(PT) \
-  hipLaunchKernelGGL(rotate_kernel<PT>, grid, dim3(256), lds, st, Y, AY, C, theta, mass, p, n, Bp, oc, X, AX, MX, R)
-  if (p <= 4)
-    DIFFHE_ROTATE(4);
-  else if (p <= 8)
-    DIFFHE_ROTATE(8);
-  else if (p <= 12)
-    DIFFHE_ROTATE(12);
-  else
-    DIFFHE_ROTATE(16);
-#undef DIFFHE_ROTATE
-  return check_launch();
+  return launch_rotate(Y, AY, C, theta, NodalMass{mass}, 0.0, p, n, Bp, X, AX, MX, R, stream);
 }
 
 extern "C" int diffhe_eig_residual(const double* R, const double* theta, const double* mass, int p, int n, int Bp,
                                    double* part, double* rho, void* stream) {
-  if (!R || !theta || !mass || !part || !rho || bad_block(p, n, Bp)) return DIFFHE_E_BADARG;
-  if (!valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
-  const int nblk = reduce_blocks(n, Bp);
-  const unsigned gy = (unsigned)((Bp + kWave - 1) / kWave);
-  account(8.0 * Bp * ((double)p * n + p * (2.0 * nblk + 1.0)));
-  hipLaunchKernelGGL(resid_kernel, dim3((unsigned)nblk, gy, (unsigned)p), dim3(256), 0, (hipStream_t)stream, R, mass, p, n,
-                     Bp, part);
-  hipLaunchKernelGGL(resid_final_kernel, dim3(gy, (unsigned)p), dim3(64), 0, (hipStream_t)stream, (const double*)part,
-                     theta, nblk, p, Bp, rho);
-  return check_launch();
+  return launch_residual(R, theta, NodalMass{mass}, 0.0, p, n, Bp, part, rho, stream);
 }
 
 extern "C" int diffhe_eig_fix_sign(double* X, const double* mass, int k, int n, int Bp, double* part, double* sgn,
                                    void* stream) {
-  if (!X || !mass || !part || !sgn || bad_block(k, n, Bp)) return DIFFHE_E_BADARG;
-  if (!valid_batch_pad(Bp)) return DIFFHE_E_BATCHPAD;
-  const int nblk = reduce_blocks(n, Bp);
-  const unsigned gy = (unsigned)((Bp + kWave - 1) / kWave);
-  account(8.0 * Bp * (double)k * n * 3.0);
-  hipLaunchKernelGGL(sign_kernel, dim3((unsigned)nblk, gy, (unsigned)k), dim3(256), 0, (hipStream_t)stream,
-                     (const double*)X, mass, k, n, Bp, part);
-  hipLaunchKernelGGL(sign_final_kernel, dim3(gy, (unsigned)k), dim3(64), 0, (hipStream_t)stream, (const double*)part, nblk,
-                     k, Bp, sgn);
-  const dim3 g = node_grid(n, Bp, 1024);
-  hipLaunchKernelGGL(flip_kernel, dim3(g.x, g.y, (unsigned)k), dim3(256), 0, (hipStream_t)stream, X, (const double*)sgn, n,
-                     Bp);
-  return check_launch();
+  return launch_fix_sign(X, NodalMass{mass}, 0.0, k, n, Bp, part, sgn, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same four passes with a nodal mass per sample under d unknowns per node (include/diffhe_modal.h).
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int diffhe_modal_gram(const double* Y, const double* AY, const double* mass, long long ms, long long mb, int d,
+                                 const unsigned char* is_bc, int p, int n, int Bp, double* part, double* GA, double* GM,
+                                 void* stream) {
+  return with_sample_mass(mass, ms, mb, d, n, Bp, [&](auto acc, double bytes) {
+    return launch_gram(Y, AY, acc, bytes, is_bc, p, n, Bp, part, GA, GM, stream);
+  });
+}
+
+extern "C" int diffhe_modal_rotate(const double* Y, const double* AY, const double* C, const double* theta,
+                                   const double* mass, long long ms, long long mb, int d, int p, int n, int Bp, double* X,
+                                   double* AX, double* MX, double* R, void* stream) {
+  return with_sample_mass(mass, ms, mb, d, n, Bp, [&](auto acc, double bytes) {
+    return launch_rotate(Y, AY, C, theta, acc, bytes, p, n, Bp, X, AX, MX, R, stream);
+  });
+}
+
+extern "C" int diffhe_modal_residual(const double* R, const double* theta, const double* mass, long long ms, long long mb,
+                                     int d, int p, int n, int Bp, double* part, double* rho, void* stream) {
+  return with_sample_mass(mass, ms, mb, d, n, Bp, [&](auto acc, double bytes) {
+    return launch_residual(R, theta, acc, bytes, p, n, Bp, part, rho, stream);
+  });
+}
+
+extern "C" int diffhe_modal_fix_sign(double* X, const double* mass, long long ms, long long mb, int d, int k, int n,
+                                     int Bp, double* part, double* sgn, void* stream) {
+  return with_sample_mass(mass, ms, mb, d, n, Bp, [&](auto acc, double bytes) {
+    return launch_fix_sign(X, acc, bytes, k, n, Bp, part, sgn, stream);
+  });
 }

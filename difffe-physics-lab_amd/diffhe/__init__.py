@@ -18,9 +18,11 @@ load, also exported here (its kernels are declared in include/diffhe_elastic.h),
 gradients to u and E and `pnorm` (kernels declared in include/diffhe_stress.h), and its eigenstrain (initial strain:
 thermal expansion, swelling, pre-stress) -- `eigenstrain_load`, `eigenstrain=` on the solve and on the stress methods,
 with gradients to eps0 and E, and the torch helpers `thermal_strain` / `element_mean` that carry the temperature of a
-heat solve to it (kernels declared in include/diffhe_eigenstrain.h); `diffhe._hip`: the ctypes binding).
+heat solve to it (kernels declared in include/diffhe_eigenstrain.h); `diffhe.modal`: `ElasticEigenSolver`, the vibration
+modes K(E) phi = lambda M(rho) phi of elastic bodies per sample with d lambda / dE and d lambda / d rho, also exported
+here (kernels declared in include/diffhe_modal.h); `diffhe._hip`: the ctypes binding).
 """
-from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, loss as _loss, mesh as _mesh, neural as _neural, robin as _robin, shape as _shape,
+from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, shape as _shape,
                solver as _solver)
 
 FEMesh = _mesh.FEMesh
@@ -32,7 +34,8 @@ AnisotropicFESolver = _aniso.AnisotropicFESolver
 RobinFESolver = _robin.RobinFESolver
 EigenFESolver = _eigen.EigenFESolver
 ElasticFESolver = _elastic.ElasticFESolver
+ElasticEigenSolver = _modal.ElasticEigenSolver
 
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
-           "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver")
+           "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver", "ElasticEigenSolver")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

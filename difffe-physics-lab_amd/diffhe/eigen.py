@@ -16,7 +16,8 @@ a dense Ritz step per sample (Cholesky + cyclic Jacobi, one sample per lane), th
 residual norms rho = |A x - theta M x|_{M^-1} / theta of the M-normalised Ritz vectors -- computed from the explicit
 A Y, so they certify the result whatever the inner tolerance was.  The iteration stops when rho <= tol for the first k
 columns of every sample (one host read per outer iteration); what is left above `tol` at `max_iter` is counted in
-`last_info.not_converged` and warned about.
+`last_info.not_converged` and warned about.  The iteration itself is `_BlockRun`, which `diffhe.modal` runs on the dofs of
+an elastic body with a mass per sample; `_EigenRun` is the scalar problem on it.
 
 kappa layouts are the scalar ones of the base class, read as for a call whose f carries no batch: () one value,
 (m,) per element, (B,) or (B, 1) per sample, (B, m) per sample and element; `batch=B` forces the per-sample reading of
@@ -89,98 +90,43 @@ def _eigen_layout(kappa: torch.Tensor, m: int, batch: Optional[int]):
     return mode, B, (Bk is not None or batch is not None)
 
 
-class _EigenRun:
-    """One eigen call: the inner solver's path state (assembled operators, hierarchy) plus the block buffers.  After
-    `run()` it keeps what the Hellmann-Feynman backward reads -- the k returned columns and the call's facts."""
+class _BlockRun:
+    """The block inverse iteration with Rayleigh-Ritz of DESIGN section 7 "Eigenpairs" on vectors of `rows` unknowns, each
+    shaped `vec` -- (n,) for the scalar operator, (n, d) for a displacement.  A subclass supplies the problem: `_setup`
+    (assemble once, hierarchy once), `_apply` (y = A x), `_inner_solve`, the four mass-weighted passes (`_rayleigh_ritz`,
+    `_fix_sign`), `_bc_rows` and `_release`; and sets es, plan, L, B, Bp, batched, k, p, rows, vec before `run`.  After
+    `run()` X holds the k returned columns."""
 
-    def __init__(self, es: "EigenFESolver", kappa: torch.Tensor, batch: Optional[int]):
-        inner = es.inner
-        if inner._tensor_components():
-            raise NotImplementedError("diffhe: eigenpairs with a conductivity tensor are not implemented")
-        self.es, self.plan = es, inner._plan()
-        plan = self.plan
-        self.mode, self.B, self.batched = _eigen_layout(kappa, plan.m, batch)
-        self.Bp = padded_batch(self.B)
-        self.k, self.p = es.k, es.k + es.guard
-        if self.p > plan.n - plan.n_bc:
-            raise ValueError(f"block of {self.p} vectors on a mesh with {plan.n - plan.n_bc} free nodes")
-        self.kappa_shape, self.kappa_device = kappa.shape, kappa.device
-        self.L = _hip.lib()
-        self.mass = plan.lumped_mass()
-        self.state = None
-        self.X = None
-
-    # -- buffers and kernels ----------------------------------------------------------------------------------------
     def _new(self, *shape, dtype=torch.float64):
         return torch.empty(shape, dtype=dtype, device=self.plan.device)
 
     def _start_block(self, x0, node_layout: bool) -> torch.Tensor:
-        """(p, n, Bp): seeded random columns (one draw per column, shared by the samples), the leading ones replaced
+        """(p, rows, Bp): seeded random columns (one draw per column, shared by the samples), the leading ones replaced
         by `x0` where given; zero on the Dirichlet rows."""
-        plan, p, n, B, Bp = self.plan, self.p, self.plan.n, self.B, self.Bp
+        plan, p, n, B, Bp, vec = self.plan, self.p, self.rows, self.B, self.Bp, tuple(self.vec)
         gen = torch.Generator().manual_seed(int(self.es.seed))
         cols = torch.randn(p, n, generator=gen, dtype=torch.float64).to(plan.device)
         Y = cols[:, :, None].expand(p, n, Bp).contiguous()
         if x0 is not None:
             x = x0.detach().to(plan.device, torch.float64)
+            nv = len(vec)
             if node_layout:
-                ok = x.dim() == 3 and x.shape[1] == n and x.shape[2] == B
+                ok = x.dim() == 2 + nv and tuple(x.shape[1:-1]) == vec and x.shape[-1] == B
+                x = x.reshape(x.shape[0], n, B) if ok else x
             else:
-                if x.dim() == 2 and not self.batched:
+                if x.dim() == 1 + nv and not self.batched:
                     x = x[None]
-                ok = x.dim() == 3 and x.shape[0] == B and x.shape[2] == n
-                x = x.permute(1, 2, 0) if ok else x
+                ok = x.dim() == 2 + nv and x.shape[0] == B and tuple(x.shape[2:]) == vec
+                x = x.reshape(B, x.shape[1], n).permute(1, 2, 0) if ok else x
             if not ok or not (self.k <= x.shape[0] <= p):
-                want = f"(c, {n}, {B})" if node_layout else f"({B}, c, {n})"
+                dims = ", ".join(str(v) for v in vec)
+                want = f"(c, {dims}, {B})" if node_layout else f"({B}, c, {dims})"
                 raise ValueError(f"x0 must be a previous phi, {want} with {self.k} <= c <= {p}, got {tuple(x0.shape)}")
             Y[:x.shape[0], :, :B] = x
-        if plan.n_bc:
-            Y[:, plan.bc_index(), :] = 0.0
+        bc = self._bc_rows()
+        if bc is not None:
+            Y[:, bc, :] = 0.0
         return Y
-
-    def _setup(self, kappa: torch.Tensor, Y: torch.Tensor, keep: bool = False) -> None:
-        """Assemble once and build (or reuse) the hierarchy once: the inner solver's path object solves the LAST column,
-        A y = M y_{p-1} to `inner_tol` -- one step of inverse iteration on a guard column, not wasted -- and keeps the
-        operators every later solve and every application of A reads.  keep: leave the column as it is (a warm start
-        without guard columns: a solve to `inner_tol` would throw its accuracy away)."""
-        inner, plan, B, n = self.es.inner, self.plan, self.B, self.plan.n
-        f0 = torch.zeros((B, n), dtype=torch.float64, device=plan.device)
-        load0 = (self.mass[:, None] * Y[-1])[:, :B].t().contiguous()
-        call = _Call.of(inner, plan, kappa, f0, load0, False)
-        state = _begin_call(inner, plan, call, homogeneous=True)
-        info = SolveInfo()
-        state.forward(call, info)                # no warning per inner solve: `run` reports what the iteration missed
-        inner.last_info = info
-        if not keep:
-            Y[-1][:, :B] = state.x[:, :B]
-        self.state, self.lattice = state, isinstance(state, _LatticeSolve)
-        if self.lattice:
-            eng = state.eng
-            shift = state.shift[:1] if state.shift is not None else None
-            self._lev = eng.lattice_levels(state.vals[:1], shift=shift)
-            self._apart = self._new(self.L.diffhe_lattice_blocks(n, self.Bp) * self.Bp)
-        else:
-            self._apart = self._new(self.L.diffhe_grad_kappa_blocks(n, self.Bp) * self.Bp)
-            self._kscale = None if state.inv_kappa is None else (1.0 / state.inv_kappa)
-
-    def _apply(self, x: torch.Tensor, y: torch.Tensor) -> None:
-        """y = A x with the saved operator (identity on the Dirichlet rows, where x is 0)."""
-        state, plan, L, st = self.state, self.plan, self.L, _stream(self.plan.device)
-        if self.lattice:
-            L.diffhe_lattice_apply(self._lev, state.Bv, state.scale, x, y, self._apart, self.Bp, st)
-            return
-        L.diffhe_ell_apply(state.vals, plan.cols, x, y, self._apart, plan.n, plan.W, self.Bp, state.Bv, st)
-        if self._kscale is not None:             # factored general path: A_b = kappa_b K_1
-            y *= self._kscale
-
-    def _rayleigh_ritz(self, Y, AY) -> None:
-        """Gram -> Ritz -> rotate -> residual: X, AX, R = theta M X - A X, theta, rho from the block Y and A Y."""
-        L, plan, p, n, Bp, st = self.L, self.plan, self.p, self.plan.n, self.Bp, _stream(self.plan.device)
-        b = self.buf
-        L.diffhe_eig_gram(Y, AY, self.mass, plan.is_bc, p, n, Bp, b["part"], b["GA"], b["GM"], st)
-        L.diffhe_eig_ritz(b["GA"], b["GM"], p, Bp, JACOBI_SWEEPS, b["work"], b["C"], b["theta"], b["flag"], st)
-        L.diffhe_eig_rotate(Y, AY, b["C"], b["theta"], self.mass, p, n, Bp, b["X"], b["AX"], None, b["R"], st)
-        L.diffhe_eig_residual(b["R"], b["theta"], self.mass, p, n, Bp, b["part"], b["rho"], st)
 
     def _status(self) -> Tuple[int, int]:
         """The one host read of an outer iteration: ((sample, mode) pairs above tol, samples with a failed Gram matrix).
@@ -191,16 +137,13 @@ class _EigenRun:
         return int(both[0]), int(both[1])
 
     # -- the iteration --------------------------------------------------------------------------------------------------
-    def run(self, kappa: torch.Tensor, x0, node_layout: bool):
+    def run(self, coeffs, x0, node_layout: bool):
+        """coeffs: what `_setup` assembles from (kappa, or E and rho)."""
         es, plan, L = self.es, self.plan, self.L
-        p, k, n, B, Bp = self.p, self.k, plan.n, self.B, self.Bp
+        p, k, n, B, Bp = self.p, self.k, self.rows, self.B, self.Bp
         info = EigenInfo(inner_tol=float(es.inner_tol), block=p)
         Y = self._start_block(x0, node_layout)
-        self._setup(kappa, Y, keep=x0 is not None and self.p == self.k)
-        state = self.state
-        info.inner, info.path = es.inner.last_info, es.inner.last_info.path
-        info.inner_solves, info.inner_iterations = 1, int(info.inner.iterations)
-        info.inner_not_converged = int(info.inner.not_converged)
+        self._setup(coeffs, Y, info, keep=x0 is not None and self.p == self.k)
         nblk = L.diffhe_eig_gram_blocks(n, Bp)
         nq = p * (p + 1) // 2
         self.buf = dict(X=self._new(p, n, Bp), AX=self._new(p, n, Bp), R=self._new(p, n, Bp), GA=self._new(nq, Bp),
@@ -213,11 +156,10 @@ class _EigenRun:
             self._apply(Y[i], AY[i])
         self._rayleigh_ritz(Y, AY)
         above, failed = self._status()
-        scratch = SolveInfo()
         while above and info.outer_iterations < es.max_iter:
             info.outer_iterations += 1
             for i in range(p):
-                res = state._adjoint_solve(b["R"][i], scratch)
+                res = self._inner_solve(b["R"][i])
                 info.inner_solves += 1
                 info.inner_iterations += res.iterations
                 info.inner_not_converged += res.not_converged
@@ -226,7 +168,7 @@ class _EigenRun:
             self._rayleigh_ritz(Y, AY)
             above, failed = self._status()
         sgn = self._new(k, Bp)
-        L.diffhe_eig_fix_sign(b["X"], self.mass, k, n, Bp, b["part"], sgn, _stream(plan.device))
+        self._fix_sign(b["X"], sgn)
         info.not_converged, info.gram_failures = above, failed
         info.residual = b["rho"][:k, :B].t().cpu()
         es.last_info = info
@@ -240,19 +182,106 @@ class _EigenRun:
         lam = (b["theta"][:k, :B] - es.shift).t().contiguous()                 # (B, k)
         self.X = b["X"][:k]
         if node_layout:
-            phi = self.X if Bp == B else self.X[:, :, :B]
+            phi = (self.X if Bp == B else self.X[:, :, :B]).reshape(k, *self.vec, B)
         else:
             phi = self._new(B, k, n)
             for i in range(k):      # column i of every sample into phi[:, i, :]: one transposing pass per column
                 L.diffhe_to_sample_major(self.X[i], None, phi[:, i], k * n, n, B, Bp, _stream(plan.device))
+            phi = phi.reshape(B, k, *self.vec)
             if not self.batched:
                 phi = phi[0]
         if not self.batched:
             lam = lam[0]
-        # what backward needs: the k columns and the engine (element tables, zero Dirichlet data); nothing else stays
-        self.eng = state.eng
-        self.state = self.buf = self._lev = self._apart = None
+        self._release()
+        self.buf = None
         return lam, phi
+
+
+class _EigenRun(_BlockRun):
+    """One eigen call: the inner solver's path state (assembled operators, hierarchy) plus the block buffers.  After
+    `run()` it keeps what the Hellmann-Feynman backward reads -- the k returned columns and the call's facts."""
+
+    def __init__(self, es: "EigenFESolver", kappa: torch.Tensor, batch: Optional[int]):
+        inner = es.inner
+        if inner._tensor_components():
+            raise NotImplementedError("diffhe: eigenpairs with a conductivity tensor are not implemented")
+        self.es, self.plan = es, inner._plan()
+        plan = self.plan
+        self.mode, self.B, self.batched = _eigen_layout(kappa, plan.m, batch)
+        self.Bp = padded_batch(self.B)
+        self.k, self.p = es.k, es.k + es.guard
+        self.rows, self.vec = plan.n, (plan.n,)
+        if self.p > plan.n - plan.n_bc:
+            raise ValueError(f"block of {self.p} vectors on a mesh with {plan.n - plan.n_bc} free nodes")
+        self.kappa_shape, self.kappa_device = kappa.shape, kappa.device
+        self.L = _hip.lib()
+        self.mass = plan.lumped_mass()
+        self.state = None
+        self.X = None
+
+    # -- the problem: K(kappa) against the plan's lumped mass -------------------------------------------------------------
+    def _bc_rows(self):
+        return self.plan.bc_index() if self.plan.n_bc else None
+
+    def _setup(self, kappa: torch.Tensor, Y: torch.Tensor, info: EigenInfo, keep: bool = False) -> None:
+        """Assemble once and build (or reuse) the hierarchy once: the inner solver's path object solves the LAST column,
+        A y = M y_{p-1} to `inner_tol` -- one step of inverse iteration on a guard column, not wasted -- and keeps the
+        operators every later solve and every application of A reads.  keep: leave the column as it is (a warm start
+        without guard columns: a solve to `inner_tol` would throw its accuracy away)."""
+        inner, plan, B, n = self.es.inner, self.plan, self.B, self.plan.n
+        f0 = torch.zeros((B, n), dtype=torch.float64, device=plan.device)
+        load0 = (self.mass[:, None] * Y[-1])[:, :B].t().contiguous()
+        call = _Call.of(inner, plan, kappa, f0, load0, False)
+        state = _begin_call(inner, plan, call, homogeneous=True)
+        sinfo = SolveInfo()
+        state.forward(call, sinfo)               # no warning per inner solve: `run` reports what the iteration missed
+        inner.last_info = sinfo
+        if not keep:
+            Y[-1][:, :B] = state.x[:, :B]
+        self.state, self.lattice = state, isinstance(state, _LatticeSolve)
+        if self.lattice:
+            eng = state.eng
+            shift = state.shift[:1] if state.shift is not None else None
+            self._lev = eng.lattice_levels(state.vals[:1], shift=shift)
+            self._apart = self._new(self.L.diffhe_lattice_blocks(n, self.Bp) * self.Bp)
+        else:
+            self._apart = self._new(self.L.diffhe_grad_kappa_blocks(n, self.Bp) * self.Bp)
+            self._kscale = None if state.inv_kappa is None else (1.0 / state.inv_kappa)
+        info.inner, info.path = sinfo, sinfo.path
+        info.inner_solves, info.inner_iterations = 1, int(sinfo.iterations)
+        info.inner_not_converged = int(sinfo.not_converged)
+        self._scratch = SolveInfo()
+
+    def _apply(self, x: torch.Tensor, y: torch.Tensor) -> None:
+        """y = A x with the saved operator (identity on the Dirichlet rows, where x is 0)."""
+        state, plan, L, st = self.state, self.plan, self.L, _stream(self.plan.device)
+        if self.lattice:
+            L.diffhe_lattice_apply(self._lev, state.Bv, state.scale, x, y, self._apart, self.Bp, st)
+            return
+        L.diffhe_ell_apply(state.vals, plan.cols, x, y, self._apart, plan.n, plan.W, self.Bp, state.Bv, st)
+        if self._kscale is not None:             # factored general path: A_b = kappa_b K_1
+            y *= self._kscale
+
+    def _inner_solve(self, rhs: torch.Tensor):
+        return self.state._adjoint_solve(rhs, self._scratch)
+
+    def _rayleigh_ritz(self, Y, AY) -> None:
+        """Gram -> Ritz -> rotate -> residual: X, AX, R = theta M X - A X, theta, rho from the block Y and A Y."""
+        L, plan, p, n, Bp, st = self.L, self.plan, self.p, self.plan.n, self.Bp, _stream(self.plan.device)
+        b = self.buf
+        L.diffhe_eig_gram(Y, AY, self.mass, plan.is_bc, p, n, Bp, b["part"], b["GA"], b["GM"], st)
+        L.diffhe_eig_ritz(b["GA"], b["GM"], p, Bp, JACOBI_SWEEPS, b["work"], b["C"], b["theta"], b["flag"], st)
+        L.diffhe_eig_rotate(Y, AY, b["C"], b["theta"], self.mass, p, n, Bp, b["X"], b["AX"], None, b["R"], st)
+        L.diffhe_eig_residual(b["R"], b["theta"], self.mass, p, n, Bp, b["part"], b["rho"], st)
+
+    def _fix_sign(self, X, sgn) -> None:
+        self.L.diffhe_eig_fix_sign(X, self.mass, self.k, self.plan.n, self.Bp, self.buf["part"], sgn,
+                                   _stream(self.plan.device))
+
+    def _release(self) -> None:
+        # what backward needs: the k columns and the engine (element tables, zero Dirichlet data); nothing else stays
+        self.eng = self.state.eng
+        self.state = self._lev = self._apart = self._scratch = None
 
     def backward(self, glam: torch.Tensor) -> torch.Tensor:
         """dL/dkappa = sum_i lambda_bar_{b,i} phi_{b,i}^T k0_e phi_{b,i} in the shape of kappa, by the solve's gradient

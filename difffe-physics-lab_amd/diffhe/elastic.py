@@ -234,6 +234,16 @@ def _setup_of(plan, nu, plane, lam1, mu1, is_bc, g) -> _ElasticSetup:
         return cache[key]
 
 
+def _cycle_defaults(amg: dict, n_dofs: int, Bp: int) -> dict:
+    """`amg` with the cycle options the caller left open filled in (in place): the Jacobi scale of elastic operators and
+    a W-cycle from 12 M unknowns of the batch on.  Shared with `diffhe.modal`, whose inner solves run the same cycle."""
+    if amg.get("scale") is None:
+        amg["scale"] = 1.3
+    if amg.get("gamma") is None:
+        amg["gamma"] = 2 if n_dofs * Bp >= 12_000_000 else 1
+    return amg
+
+
 # ---------------------------------------------------------------------------------------------
 # One call
 # ---------------------------------------------------------------------------------------------
@@ -320,11 +330,7 @@ class _ElasticSolve:
         if solver.method != "ell-jacobi":
             levels, stats = setup.levels()
             if levels:
-                amg = self.amg
-                if amg.get("scale") is None:
-                    amg["scale"] = 1.3
-                if amg.get("gamma") is None:
-                    amg["gamma"] = 2 if dofs.n * Bp >= 12_000_000 else 1
+                amg = _cycle_defaults(self.amg, dofs.n, Bp)
                 self.hier = eng.amg_setup(vals, Bv, bool(amg.get("fp32", 0)), levels)
                 info.hierarchy, info.hierarchy_levels, info.operator_complexity = "unit", stats[0], stats[1]
         if self.hier is not None:
