@@ -12,9 +12,9 @@
 //   shape_elem_kernel: one group of LB lanes per element reduces its samples (lanes over samples, LB = min(Bp, 64), when
 //     the batch is innermost; LB = 1 -- one element per lane and a sample loop -- otherwise or for B = 1) to the d^2 + 1
 //     numbers T_e, q_e and writes the (d+1) d vertex contributions to work (m, (d+1) d);
-//   shape_gather_kernel: per node, the contributions of its incident (element, vertex) pairs in the fixed order of the
-//     incidence list (diffhe/plan.py: SolvePlan.shape_incidence).
-#include "common.h"
+//   shape_gather_kernel (shape_gather.h, shared with elastic_shape.hip): per node, the contributions of its incident
+//     (element, vertex) pairs in the fixed order of the incidence list (diffhe/plan.py: SolvePlan.shape_incidence).
+#include "shape_gather.h"
 
 namespace {
 
@@ -178,19 +178,6 @@ __global__ __launch_bounds__(256) void shape_elem_kernel(const double* __restric
   }
 }
 
-// grad[i, k] = sum over the incidence list of node i (codes e * (d+1) + p, element order) of work[code * d + k]
-__global__ __launch_bounds__(256) void shape_gather_kernel(const int* __restrict__ inc_ptr, const int* __restrict__ inc,
-                                                           const double* __restrict__ work, int n, int dim,
-                                                           double* __restrict__ grad) {
-  for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < (i64)n * dim; t += (i64)gridDim.x * blockDim.x) {
-    const i64 i = t / dim;
-    const int k = (int)(t - i * dim);
-    double s = 0.0;
-    for (int j = inc_ptr[i]; j < inc_ptr[i + 1]; ++j) s += work[(i64)inc[j] * dim + k];
-    grad[t] = s;
-  }
-}
-
 }  // namespace
 
 extern "C" int diffhe_p1_shape_grad(const double* coords, const int* elems, int dim, int n, int m, int B,
@@ -221,9 +208,6 @@ extern "C" int diffhe_p1_shape_grad(const double* coords, const int* elems, int 
   else
     hipLaunchKernelGGL(shape_elem_kernel<3>, grid, block, 0, st, coords, elems, n, m, B, LB, u, g, lam, sn, sb, kappa,
                        kse, ksb, f, fsn, fsb, c, work);
-  long long gb = ((long long)n * dim + 255) / 256;
-  if (gb > 8192) gb = 8192;
-  hipLaunchKernelGGL(shape_gather_kernel, dim3((unsigned)gb), block, 0, st, inc_ptr, inc, (const double*)work, n, dim,
-                     grad);
+  launch_shape_gather(inc_ptr, inc, work, n, dim, grad, st);
   return check_launch();
 }

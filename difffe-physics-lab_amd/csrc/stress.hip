@@ -15,130 +15,19 @@
 //
 // Every kernel takes a compile-time EIG: with it the element carries an eigenstrain (eigen_field.h) and the stress is
 // E (s(u) - s0) with an out-of-plane component of its own (include/diffhe_eigenstrain.h, whose three stress entries are at
-// the end of this unit); without it the instantiations are the ones of diffhe_stress.h, unchanged.
+// the end of this unit); without it the instantiations are the ones of diffhe_stress.h, unchanged.  The element and the
+// adjoint form live in stress_form.h, which elastic_shape.hip shares for the node-coordinate gradient of the stress.
 #include "common.h"
 #include "diffhe_eigenstrain.h"
 #include "diffhe_stress.h"
 #include "eigen_field.h"
 #include "element_grad.h"
+#include "stress_form.h"
 
 namespace {
 
 using namespace diffhe;
 typedef long long i64;
-
-// What an element with an eigenstrain carries on top: the field, and its components where the batch shares them (zb == 0).
-template <int DIM, bool EIG>
-struct EigenOf {};
-template <int DIM>
-struct EigenOf<DIM, true> {
-  EigenField<DIM> ef;
-};
-template <int DIM, bool EIG>
-struct EigenElem {};
-template <int DIM>
-struct EigenElem<DIM, true> {
-  double z[EigenField<DIM>::NZ];
-};
-
-// What both directions read of an element and a sample.
-template <int DIM, bool EIG = false>
-struct StressElement : EigenOf<DIM, EIG> {
-  static constexpr int NPE = DIM + 1, NC = DIM * (DIM + 1) / 2;
-  const int* __restrict__ elems;
-  const double* __restrict__ gtab;
-  double lam1, mu1, nu_z;
-  const double* __restrict__ u;
-  const double* __restrict__ E;
-  i64 ese, esb;
-  int m;
-
-  struct Elem : EigenElem<DIM, EIG> {
-    int e;
-    int node[NPE];
-    double G[NPE][DIM];
-  };
-
-  __device__ __forceinline__ void load(int e, Elem& el) const {
-    el.e = e;
-#pragma unroll
-    for (int p = 0; p < NPE; ++p) {
-      el.node[p] = elems[(i64)p * m + e];
-#pragma unroll
-      for (int t = 0; t < DIM; ++t) el.G[p][t] = gtab[(i64)(p * DIM + t) * m + e];
-    }
-    if constexpr (EIG) {
-      if (this->ef.zb == 0) this->ef.read(e, 0, el.z);
-    }
-  }
-
-  // the unit stress s (NC) of sample b from H[a][t] = sum_p u[(p, a)] g_p[t]; returns tr H
-  __device__ __forceinline__ double unit_stress(const Elem& el, int Bp, int b, double* s) const {
-    double H[DIM][DIM];
-#pragma unroll
-    for (int a = 0; a < DIM; ++a)
-#pragma unroll
-      for (int t = 0; t < DIM; ++t) H[a][t] = 0.0;
-#pragma unroll
-    for (int p = 0; p < NPE; ++p)
-#pragma unroll
-      for (int a = 0; a < DIM; ++a) {
-        const double up = u[((i64)el.node[p] * DIM + a) * Bp + b];
-#pragma unroll
-        for (int t = 0; t < DIM; ++t) H[a][t] = fma(up, el.G[p][t], H[a][t]);
-      }
-    double tr = 0.0;
-#pragma unroll
-    for (int a = 0; a < DIM; ++a) tr += H[a][a];
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-      const int a = voigt_row<DIM>(k), t = voigt_col<DIM>(k);
-      s[k] = k < DIM ? fma(2.0 * mu1, H[a][a], lam1 * tr) : mu1 * (H[a][t] + H[t][a]);
-    }
-    return tr;
-  }
-
-  // EIG: s <- s - s0 in plane, tr = tr H; returns the out-of-plane unit stress lam1 (tr - theta0) - 2 mu1 eps0_zz of
-  // plane strain (0 otherwise)
-  __device__ __forceinline__ double subtract_initial(const Elem& el, int b, double tr, double* s) const {
-    double szz = 0.0;
-    if constexpr (EIG) {
-      constexpr int NZ = EigenField<DIM>::NZ;
-      double z[NZ], s0[NC];
-      if (this->ef.zb) {
-        this->ef.read(el.e, b, z);
-      } else {
-#pragma unroll
-        for (int k = 0; k < NZ; ++k) z[k] = el.z[k];
-      }
-      const double th = this->ef.initial_stress(z, s0);
-#pragma unroll
-      for (int k = 0; k < NC; ++k) s[k] -= s0[k];
-      if (DIM == 2 && this->ef.pstrain) szz = fma(lam1, tr - th, -2.0 * mu1 * z[3]);
-    }
-    return szz;
-  }
-
-  __device__ __forceinline__ double modulus(int e, int b) const { return E[(i64)e * ese + (i64)b * esb]; }
-};
-
-// The three normal stresses of sigma (NC): in 2D the third is nu_z (sigma_xx + sigma_yy), with an eigenstrain sg_zz.
-template <int DIM, bool EIG>
-__device__ __forceinline__ void normal_stresses(const double* sg, double nu_z, double sg_zz, double* nn) {
-  nn[0] = sg[0];
-  nn[1] = sg[1];
-  nn[2] = DIM == 2 ? (EIG ? sg_zz : nu_z * (sg[0] + sg[1])) : sg[2];
-}
-
-template <int DIM>
-__device__ __forceinline__ double von_mises(const double* sg, const double* nn) {
-  constexpr int NC = DIM * (DIM + 1) / 2;
-  const double d0 = nn[0] - nn[1], d1 = nn[1] - nn[2], d2 = nn[2] - nn[0];
-  double sh = 0.0;
-#pragma unroll
-  for (int k = DIM; k < NC; ++k) sh = fma(sg[k], sg[k], sh);
-  return sqrt(fma(0.5, fma(d0, d0, fma(d1, d1, d2 * d2)), 3.0 * sh));
-}
 
 // ---------------------------------------------------------------------------------------
 // sigma at c*osc + e*ose + b and / or vm (m, Bp); a NULL output is neither computed nor stored.
@@ -170,104 +59,6 @@ __global__ __launch_bounds__(256) void stress_eval_kernel(const StressElement<DI
     }
   }
 }
-
-// ---------------------------------------------------------------------------------------
-// The element pass of the adjoint as a form of element_grad.h: out[0] = dE[e, b] = sum_k c_k s_k with the combined
-// cotangent c = sigma_bar + vm_bar d vm / d sigma, and, where `work` is given, T = E (2 mu1 sym(C) + lam1 tr(C) I) to
-// work (NC, m, Bp).  Samples b >= B: dE = 0, T = 0, no cotangent read.
-// ---------------------------------------------------------------------------------------
-template <bool EIG>
-struct EigenOut {};
-template <>
-struct EigenOut<true> {
-  double* __restrict__ deps;   // d / d eps0 at c*dzc + e*dze + b, or NULL
-  i64 dzc, dze;
-};
-
-template <int DIM, bool EIG = false>
-struct StressAdjointForm : EigenOut<EIG> {
-  static constexpr int NC = 1;
-  static constexpr int NV = DIM * (DIM + 1) / 2;
-  typedef typename StressElement<DIM, EIG>::Elem Elem;
-  StressElement<DIM, EIG> el_of;
-  const double* __restrict__ sigma_bar;
-  i64 osc, ose;
-  const double* __restrict__ vm_bar;
-  double* __restrict__ work;
-  int B;
-
-  __device__ __forceinline__ void load(int e, Elem& el) const { el_of.load(e, el); }
-
-  __device__ __forceinline__ void eval(const Elem& el, int Bp, int b, double* out) const {
-    const i64 mb = (i64)el_of.m * Bp, at = (i64)el.e * Bp + b;
-    if (b >= B) {
-      out[0] = 0.0;
-      if (work) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) work[k * mb + at] = 0.0;
-      }
-      if constexpr (EIG) {
-        if (this->deps)
-          for (int k = 0; k < el_of.ef.count(); ++k) this->deps[k * this->dzc + el.e * this->dze + b] = 0.0;
-      }
-      return;
-    }
-    double s[NV], c[NV];
-    const double tr_h = el_of.unit_stress(el, Bp, b, s);
-    const double szz = el_of.subtract_initial(el, b, tr_h, s);   // EIG only
-    double czz = 0.0;                                            // EIG only: the cotangent of sigma_zz
-    const double Ee = el_of.modulus(el.e, b);
-#pragma unroll
-    for (int k = 0; k < NV; ++k) c[k] = sigma_bar ? sigma_bar[k * osc + el.e * ose + b] : 0.0;
-    if (vm_bar) {
-      double sg[NV], nn[3];
-#pragma unroll
-      for (int k = 0; k < NV; ++k) sg[k] = Ee * s[k];
-      normal_stresses<DIM, EIG>(sg, el_of.nu_z, Ee * szz, nn);
-      const double vm = von_mises<DIM>(sg, nn);
-      if (vm > 0.0) {                                   // d vm / d sigma = 0 where vm == 0
-        const double w = vm_bar[at] / vm;
-        const double mean = ((nn[0] + nn[1]) + nn[2]) / 3.0;
-        double cn[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) cn[i] = 1.5 * (nn[i] - mean) * w;
-#pragma unroll
-        for (int i = 0; i < DIM; ++i) c[i] += cn[i];
-        if (DIM == 2 && !EIG) {                         // sigma_zz = nu_z (sigma_xx + sigma_yy)
-          c[0] = fma(el_of.nu_z, cn[2], c[0]);
-          c[1] = fma(el_of.nu_z, cn[2], c[1]);
-        }
-        if constexpr (EIG && DIM == 2) {                // sigma_zz on its own; identically 0 in plane stress
-          if (el_of.ef.pstrain) czz = cn[2];
-        }
-#pragma unroll
-        for (int k = DIM; k < NV; ++k) c[k] = fma(3.0 * sg[k], w, c[k]);
-      }
-    }
-    double de = 0.0;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) de = fma(c[k], s[k], de);
-    if (EIG) de = fma(czz, szz, de);
-    out[0] = de;
-    if constexpr (EIG) {
-      if (this->deps) {
-        double dz[EigenField<DIM>::NZ];
-        el_of.ef.transpose(-Ee, c, czz, dz);
-#pragma unroll
-        for (int k = 0; k < EigenField<DIM>::NZ; ++k)
-          if (k < el_of.ef.count()) this->deps[k * this->dzc + el.e * this->dze + b] = dz[k];
-      }
-    }
-    if (work) {
-      double tr = EIG ? czz : 0.0;                      // sigma_zz = E lam1 tr eps(u) + ... feeds the trace
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) tr += c[i];
-#pragma unroll
-      for (int k = 0; k < NV; ++k)
-        work[k * mb + at] = Ee * (k < DIM ? fma(2.0 * el_of.mu1, c[k], el_of.lam1 * tr) : el_of.mu1 * c[k]);
-    }
-  }
-};
 
 // ---------------------------------------------------------------------------------------
 // Node pass: u_bar[(i, a), b] = sum over the incidence list of node i (codes e * NPE + p, element order) of

@@ -20,9 +20,12 @@ thermal expansion, swelling, pre-stress) -- `eigenstrain_load`, `eigenstrain=` o
 with gradients to eps0 and E, and the torch helpers `thermal_strain` / `element_mean` that carry the temperature of a
 heat solve to it (kernels declared in include/diffhe_eigenstrain.h); `diffhe.modal`: `ElasticEigenSolver`, the vibration
 modes K(E) phi = lambda M(rho) phi of elastic bodies per sample with d lambda / dE and d lambda / d rho, also exported
-here (kernels declared in include/diffhe_modal.h); `diffhe._hip`: the ctypes binding).
+here (kernels declared in include/diffhe_modal.h); `diffhe.elastic_shape`: `ShapeElasticFESolver`, `ElasticFESolver`
+that also returns dL/dX for the node coordinates of the solve and of its `stress` / `von_mises`, from the same single
+adjoint solve -- shape design of elastic bodies -- also exported here (kernels declared in
+include/diffhe_elastic_shape.h); `diffhe._hip`: the ctypes binding).
 """
-from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, shape as _shape,
+from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_shape as _elastic_shape, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, shape as _shape,
                solver as _solver)
 
 FEMesh = _mesh.FEMesh
@@ -35,7 +38,9 @@ RobinFESolver = _robin.RobinFESolver
 EigenFESolver = _eigen.EigenFESolver
 ElasticFESolver = _elastic.ElasticFESolver
 ElasticEigenSolver = _modal.ElasticEigenSolver
+ShapeElasticFESolver = _elastic_shape.ShapeElasticFESolver
 
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
-           "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver", "ElasticEigenSolver")
+           "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver", "ElasticEigenSolver",
+           "ShapeElasticFESolver")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

@@ -74,8 +74,11 @@ above with gradients to u, E and eps0.  `thermal_strain(alpha, dT, dim, plane)` 
 carry the temperature of a heat solve to eps0.  The gradient of an eps0 shared over elements or samples is a torch `sum`
 of the kernel's per-element, per-sample array over the shared axes.
 
+Node gradients (mesh.nodes requiring grad): `diffhe.elastic_shape.ShapeElasticFESolver`, this class with dL/dX of the
+solve and of the stress methods; `ElasticFESolver` itself refuses moving nodes.
+
 Not implemented (NotImplementedError): 1D meshes, P2 meshes, backward with create_graph=True, a per-call `dirichlet=`,
-node gradients (mesh.nodes requiring grad), Robin / flux data (h=, u_inf=, flux=); `amg=dict(strength=...)`.
+Robin / flux data (h=, u_inf=, flux=); `amg=dict(strength=...)`.
 """
 from __future__ import annotations
 
@@ -271,6 +274,8 @@ class _ElasticSolve:
         self.plan = setup.plan
         self.eng = _Engine(setup.dofs, tol, solver.max_iter, solver.check_every, "gather", g=setup.dofs.g)
         self.node_eng = _Engine(self.plan, tol, solver.max_iter, solver.check_every, "gather")
+        # a call whose nodes need grad (diffhe.elastic_shape) also keeps E and f as the kernels read them, and lambda
+        self.shape, self.e_s, self.f_dofs, self.lam = False, None, None, None
 
     # -- layout -----------------------------------------------------------------------------------
     def _to_dofs(self, t: torch.Tensor, batched: bool, zero_fixed: bool = False) -> torch.Tensor:
@@ -318,9 +323,14 @@ class _ElasticSolve:
         Bp = self.Bp = padded_batch(B)
         kdev, kse, ksb, Bv = self.node_eng.kappa_device(E, call.mode, B, Bp, em=call.kappa_em)
         vals, lift = setup.assemble(kdev, kse, ksb, Bv)
+        if self.shape:
+            self.e_s = (kdev, kse, ksb)
         rhs = -lift if Bv == Bp else (-lift).expand(dofs.n, Bp).contiguous()
         if f is not None:
-            rhs += self._apply_load_map(self._to_dofs(f, call.f_batched))
+            f_dofs = self._to_dofs(f, call.f_batched)
+            rhs += self._apply_load_map(f_dofs)
+            if self.shape:
+                self.f_dofs = f_dofs
         if load is not None:
             rhs += self._to_dofs(load, call.load_batched)
         rhs[dofs.is_bc.bool()] = 0.0
@@ -357,6 +367,8 @@ class _ElasticSolve:
         else:
             res = eng.cg(self.vals, rhs, Bp, self.Bv)
         lam = res.x
+        if self.shape:
+            self.lam = lam
         info.adj_iterations, info.adj_max_relres = res.iterations, float(res.relres[:B].max())
         info.not_converged += res.not_converged
         grad_e = grad_f = grad_load = None
@@ -402,7 +414,8 @@ def _batch_of(solver, f: torch.Tensor, load: torch.Tensor, node_major: bool):
     return B, fb, lb
 
 
-def _elastic_forward(solver: "ElasticFESolver", E, f, load, node_major):
+def _elastic_forward(solver: "ElasticFESolver", E, f, load, node_major, shape: bool = False):
+    """(u, state) of one call.  shape: the state also keeps what the node-gradient kernel reads (diffhe.elastic_shape)."""
     plan = solver._plan()
     setup = _setup_of(plan, solver.nu, solver.plane, solver._lam1, solver._mu1, solver._is_bc, solver._g)
     B_rhs, fb, lb = _batch_of(solver, f, load, node_major)
@@ -414,6 +427,7 @@ def _elastic_forward(solver: "ElasticFESolver", E, f, load, node_major):
                                 tol_user=solver._tol_user, mg_user=set(), mg={}, amg=solver.amg)
     solver.tol = tol
     state = _ElasticSolve(solver, setup, call, tol, amg)
+    state.shape = shape
     u = _run_call(state, _Inputs(E, f if f.numel() else None, load if load.numel() else None, B, call.batched,
                                  node_major, call.out_device))
     return u, state
@@ -1093,9 +1107,7 @@ class ElasticFESolver(nn.Module):
                                       "integrate a traction into load=")
         if layout not in ("sample", "node"):
             raise ValueError(f"Unknown layout: {layout!r}")
-        if self.mesh.nodes.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError("diffhe: node gradients are not implemented for elasticity (mesh.nodes requires "
-                                      "grad)")
+        self._refuse_moving_nodes("solve", eigenstrain is not None)
         f64, load64 = self._checked(f, "f", layout), self._checked(load, "load", layout)
         if eigenstrain is not None:
             load64 = self._with_eigenstrain_load(eigenstrain, f64, load64, layout)
@@ -1112,8 +1124,20 @@ class ElasticFESolver(nn.Module):
         f_in, load_in = (empty if f64 is None else f64), (empty if load64 is None else load64)
         _kappa_layout(E, self.mesh.n_elements, _batch_of(self, f_in, load_in, layout == "node")[0], layout == "node")
         _SOLVERS[id(self)] = self
+        return self._solve_op(E, f_in, load_in, layout == "node")
+
+    def _moving_nodes(self) -> bool:
+        return self.mesh.nodes.requires_grad and torch.is_grad_enabled()
+
+    def _refuse_moving_nodes(self, what: str, eigenstrain: bool) -> None:
+        """Moving nodes are `ShapeElasticFESolver`'s (diffhe.elastic_shape), which overrides this."""
+        if self._moving_nodes():
+            raise NotImplementedError("diffhe: node gradients are not implemented for elasticity (mesh.nodes requires "
+                                      "grad)")
+
+    def _solve_op(self, E: torch.Tensor, f_in: torch.Tensor, load_in: torch.Tensor, node_major: bool) -> torch.Tensor:
         save = torch.is_grad_enabled() and (E.requires_grad or f_in.requires_grad or load_in.requires_grad)
-        u, _token = torch.ops.diffhe.elastic_solve(E, f_in, load_in, id(self), save, layout == "node")
+        u, _token = torch.ops.diffhe.elastic_solve(E, f_in, load_in, id(self), save, node_major)
         return u
 
     # -- eigenstrain ----------------------------------------------------------------------------------
@@ -1140,9 +1164,7 @@ class ElasticFESolver(nn.Module):
     def _eigenstrain_load(self, eps0, E, layout: str, B_hint: Optional[int]) -> torch.Tensor:
         if layout not in ("sample", "node"):
             raise ValueError(f"Unknown layout: {layout!r}")
-        if self.mesh.nodes.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError("diffhe: node gradients are not implemented for elasticity (mesh.nodes requires "
-                                      "grad)")
+        self._refuse_moving_nodes("eigenstrain_load", True)
         eps0, E = self._checked_eps0(eps0, layout), self._modulus(E)
         m, nc0, node = self.mesh.n_elements, eigen_components(self.mesh.dim, self.plane), layout == "node"
         B0 = _eigen_batch(eps0, E, m, nc0, node, B_hint)                     # the refusals, before the op
@@ -1188,9 +1210,7 @@ class ElasticFESolver(nn.Module):
             E = self._E
         elif not isinstance(E, torch.Tensor):
             E = torch.as_tensor(E, dtype=torch.float64)
-        if self.mesh.nodes.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError("diffhe: node gradients are not implemented for elasticity (mesh.nodes requires "
-                                      "grad)")
+        self._refuse_moving_nodes("stress", eigenstrain is not None)
         u, E = u.to(torch.float64), E.to(torch.float64)
         if eigenstrain is not None:
             eps0 = self._checked_eps0(eigenstrain, layout)
@@ -1202,7 +1222,10 @@ class ElasticFESolver(nn.Module):
             return torch.ops.diffhe.elastic_stress_eigen(u, E, eps0, id(self), node, want_sigma, want_vm)
         _kappa_layout(E, self.mesh.n_elements, _stress_batch(u, layout == "node"), layout == "node")
         _SOLVERS[id(self)] = self
-        return torch.ops.diffhe.elastic_stress(u, E, id(self), layout == "node", want_sigma, want_vm)
+        return self._stress_eval_op(u, E, layout == "node", want_sigma, want_vm)
+
+    def _stress_eval_op(self, u: torch.Tensor, E: torch.Tensor, node_major: bool, want_sigma: bool, want_vm: bool):
+        return torch.ops.diffhe.elastic_stress(u, E, id(self), node_major, want_sigma, want_vm)
 
     def stress(self, u: torch.Tensor, E=None, layout: str = "sample", eigenstrain=None) -> torch.Tensor:
         """Element stresses sigma = E (2 mu' eps + lambda' tr(eps) I) of the displacement u -- (n, d), (B, n, d), or
