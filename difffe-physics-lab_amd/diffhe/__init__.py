@@ -23,9 +23,12 @@ modes K(E) phi = lambda M(rho) phi of elastic bodies per sample with d lambda / 
 here (kernels declared in include/diffhe_modal.h); `diffhe.elastic_shape`: `ShapeElasticFESolver`, `ElasticFESolver`
 that also returns dL/dX for the node coordinates of the solve and of its `stress` / `von_mises`, from the same single
 adjoint solve -- shape design of elastic bodies -- also exported here (kernels declared in
-include/diffhe_elastic_shape.h); `diffhe._hip`: the ctypes binding).
+include/diffhe_elastic_shape.h); `diffhe.elastic_aniso`: `AnisotropicElasticFESolver`, `ElasticFESolver` with a stiffness
+tensor per element and sample in place of (E, nu) and its gradient dL/dC -- laminates, orthotropic and cubic materials,
+gradients to Poisson's ratio -- with the torch helpers that build and rotate such tensors, also exported here (kernels
+declared in include/diffhe_elastic_aniso.h); `diffhe._hip`: the ctypes binding).
 """
-from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_shape as _elastic_shape, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, shape as _shape,
+from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_shape as _elastic_shape, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, shape as _shape,
                solver as _solver)
 
 FEMesh = _mesh.FEMesh
@@ -39,8 +42,9 @@ EigenFESolver = _eigen.EigenFESolver
 ElasticFESolver = _elastic.ElasticFESolver
 ElasticEigenSolver = _modal.ElasticEigenSolver
 ShapeElasticFESolver = _elastic_shape.ShapeElasticFESolver
+AnisotropicElasticFESolver = _elastic_aniso.AnisotropicElasticFESolver
 
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
            "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver", "ElasticEigenSolver",
-           "ShapeElasticFESolver")
+           "ShapeElasticFESolver", "AnisotropicElasticFESolver")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

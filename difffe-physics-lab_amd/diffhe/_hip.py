@@ -1,5 +1,5 @@
 """ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h, include/diffhe_stress.h,
-include/diffhe_eigenstrain.h, include/diffhe_modal.h, include/diffhe_elastic_shape.h).
+include/diffhe_eigenstrain.h, include/diffhe_modal.h, include/diffhe_elastic_shape.h, include/diffhe_elastic_aniso.h).
 
 The library is built in-tree by `__graft_entry__.build()` /
 `make -C difffe-physics-lab_amd/csrc`.  There is NO fallback: if the library or a
@@ -210,6 +210,18 @@ ELASTIC_SHAPE_SIGNATURES = {
                                       _PI, _PD, _PD, _PV]),
 }
 
+# name -> (restype, argtypes) of every symbol of include/diffhe_elastic_aniso.h, the library's seventh header (elasticity
+# with a stiffness tensor per element, csrc/elastic_aniso.hip, and the row bound of lambda_max(D^-1 A) its solver takes for
+# the smoother of every level): bound by the same loop (tests/test_elastic_aniso.py holds this table against that header)
+ELASTIC_ANISO_SIGNATURES = {
+    "diffhe_elastc_assemble_rows": (_S, [_PD, _PD, _I, _PD, _L, _L, _L, _PI, _PI, _PI, _PB, _PD, _PD, _PD, _I, _I, _I,
+                                         _I, _PV]),
+    "diffhe_elastc_grad": (_S, [_PI, _PD, _PD, _I, _PD, _PD, _PD, _I, _I, _I, _PD, _L, _L, _PD, _PD, _PV]),
+    "diffhe_elastc_grad_shared": (_S, [_PI, _PD, _PD, _I, _PD, _PD, _PD, _I, _I, _I, _I, _PD, _L, _L, _PV]),
+    "diffhe_ell_jacobi_row_bound": (_S, [_PD, _PI, _I, _I, _I, _PD, _PD, _PV]),
+}
+ROW_BOUND_BLOCKS = 1024     # DIFFHE_ROW_BOUND_BLOCKS
+
 _lib = None
 
 
@@ -246,7 +258,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *ELASTIC_SIGNATURES.items(), *STRESS_SIGNATURES.items(),
                                   *EIGENSTRAIN_SIGNATURES.items(), *MODAL_SIGNATURES.items(),
-                                  *ELASTIC_SHAPE_SIGNATURES.items()):
+                                  *ELASTIC_SHAPE_SIGNATURES.items(), *ELASTIC_ANISO_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = (_I if res is _S else res), args
             if res is _S:
