@@ -937,7 +937,7 @@ TV* fmg_start(const Hier& H, const TV* b0, hipStream_t st, const TV** pending = 
       // have stored it, so x and the residual are bit for bit those of the two passes below
       Extra ex{};
       ex.a0 = coarse; ex.cW = H.lev[l + 1].W; ex.bc = L.bc; ex.p_out = x;
-      launch_strip<TV, M_RESID, false, F_PROLONG, TV, kStripCols, 1, MAT_SHARED>(
+      launch_strip<TV, M_RESID, false, F_PROLONG, TV, kStripCols, 5, MAT_SHARED>(
           L, H.Bv, H.scale, (const TV*)nullptr, bl[l], (TV*)H.rhs[l], 0.0, 0.0, nullptr, H.Bp, strip_geom(L, H.Bp), st, ex);
       have_resid = true;
     } else {

@@ -24,6 +24,9 @@
 namespace diffhe_lattice __attribute__((visibility("hidden"))) {
 namespace {
 
+template <bool STORED, typename TV> struct WindowType { typedef double type; };
+template <typename TV> struct WindowType<true, TV> { typedef TV type; };
+
 template <typename TV, typename TA, typename TM, int MODE, int FUSE, int ND, bool SHARED, bool XFROMB, int RW,
           bool TAIL, bool SHIFT = false>
 __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV* __restrict__ src,
@@ -94,19 +97,58 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
   TA* __restrict__ ppo = (is_pupd(FUSE)) ? (TA*)ex.p_out + i0 * Bp : nullptr;
   double* __restrict__ pxx = (FUSE == F_PUPD && ex.x) ? ex.x + i0 * Bp : nullptr;  // NULL: the iterate is not touched
 
+  // The prolongation + residual pass of the full-multigrid start (kProlongOnly) CARRIES the coarse rows under its window
+  // from one window row to the next (the rows arrive in order, rw0 first).  cea is coarse row `row >> 1`; an odd row
+  // 2k + 1 loads coarse row k + 1 into ceb, and the even row after it takes that over as its cea: every coarse row is
+  // loaded once per tile (plus the one the tile starts on), as stored (TA; widened at use, which is exact).  Coarse
+  // columns c0w/2 - 1 + j, clamped to the coarse row.  The M_JACOBI form keeps the per-row loads: carrying costs it a
+  // wave per SIMD (78 -> 89, 87 -> 108 VGPRs).
+  constexpr int NC = RW / 2 + 2;
+  // window values: fp64, except where they ARE stored values (kProlongOnly: the prolonged iterate as TV) -- held as such
+  // and widened at use, which is exact and leaves the registers to the carried rows
+  typedef typename WindowType<kProlongOnly, TV>::type WT;
+  TA cea[NC], ceb[NC];
+  int cjq[NC];
+  const int rw0 = r0 > 0 ? r0 - 1 : r0;      // first row the window loads
+  // ... and fetches the Dirichlet flags of a window row once: lane q < RW + 2 loads the flag of window column q (clamped
+  // as dq), a ballot turns them into a wave-uniform bit mask -- one byte load per row instead of one per window value
+  const int lane = (int)(lb & 63u);
+  int bcol = c0w - 1 + (lane < RW + 2 ? lane : RW + 1);
+  bcol = bcol < 0 ? 0 : (bcol > W - 1 ? W - 1 : bcol);
+  if (FUSE == F_PROLONG) {
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      int cj = (c0w >> 1) - 1 + j;
+      cjq[j] = cj < 0 ? 0 : (cj > ex.cW - 1 ? ex.cW - 1 : cj);
+      if (kProlongOnly) cea[j] = ceb[j] = (aux + ((i64)(rw0 >> 1) * ex.cW + cjq[j]) * Bp)[lb];
+    }
+  }
+
   // `row` is the grid row being loaded; xrow / d0row point at (row, c0w); roff = offset of that
   // row from the current one in vector elements
   auto load_window = [&](int row, i64 roff, const TV* __restrict__ xrow, const TD* __restrict__ d0row,
-                         double* dst, const double* __restrict__ shrow = nullptr) {
-    double ce[RW / 2 + 2], ce2[RW / 2 + 2];
-    if (FUSE == F_PROLONG) {  // coarse values around this strip: coarse columns c0w/2 - 1 + j
+                         WT* dst, const double* __restrict__ shrow = nullptr) __attribute__((always_inline)) {
+    double ce[NC], ce2[NC];
+    unsigned long long dir = 0;   // kProlongOnly, bit q: window column q is a Dirichlet node of this row
+    if (kProlongOnly) {
+      dir = __ballot(ex.bc[(i64)row * W + bcol] != 0);
+      const bool odd = row & 1;
+      if (odd) {
+#pragma unroll
+        for (int j = 0; j < NC; ++j) ceb[j] = (aux + ((i64)((row >> 1) + 1) * ex.cW + cjq[j]) * Bp)[lb];
+      }
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        cea[j] = odd ? cea[j] : ceb[j];   // even row: the row its predecessor loaded (rw0 even: the primed one)
+        ce[j] = (double)cea[j];
+        ce2[j] = odd ? (double)ceb[j] : 0.0;
+      }
+    } else if (FUSE == F_PROLONG) {  // coarse values around this strip
       const int cr = row >> 1;
 #pragma unroll
-      for (int j = 0; j < RW / 2 + 2; ++j) {
-        int cj = (c0w >> 1) - 1 + j;
-        cj = cj < 0 ? 0 : (cj > ex.cW - 1 ? ex.cW - 1 : cj);
-        ce[j] = (double)(aux + ((i64)cr * ex.cW + cj) * Bp)[lb];
-        ce2[j] = (row & 1) ? (double)(aux + ((i64)(cr + 1) * ex.cW + cj) * Bp)[lb] : 0.0;
+      for (int j = 0; j < NC; ++j) {
+        ce[j] = (double)(aux + ((i64)cr * ex.cW + cjq[j]) * Bp)[lb];
+        ce2[j] = (row & 1) ? (double)(aux + ((i64)(cr + 1) * ex.cW + cjq[j]) * Bp)[lb] : 0.0;
       }
     }
 #pragma unroll
@@ -133,15 +175,15 @@ __device__ __forceinline__ double strip_body(const Level& L, double sb, const TV
           corr = (row & 1) ? 0.5 * (ce[(q - 1) / 2 + 1] + ce2[(q - 1) / 2 + 1]) : ce[(q - 1) / 2 + 1];
         else
           corr = (row & 1) ? 0.5 * (ce[q / 2 + 1] + ce2[q / 2]) : 0.5 * (ce[q / 2] + ce[q / 2 + 1]);
-        if (ex.bc[(i64)row * W + c0w + dq[q]]) corr = 0.0;
+        if (kProlongOnly ? (bool)((dir >> q) & 1) : (bool)ex.bc[(i64)row * W + c0w + dq[q]]) corr = 0.0;
         if (kProlongOnly) v = (double)(TV)corr;   // the STORED value of the transfer kernels: the pass reads what they wrote
         else v += corr;
       }
-      dst[q] = okq[q] ? v : 0.0;
+      dst[q] = (WT)(okq[q] ? v : 0.0);
     }
   };
 
-  double xm[RW + 2], xc[RW + 2], xp[RW + 2];
+  WT xm[RW + 2], xc[RW + 2], xp[RW + 2];
   double n2p[RW], d3p[RW + 1];
 #pragma unroll
   for (int q = 0; q < RW + 2; ++q) xm[q] = 0.0;

@@ -15,7 +15,7 @@ INST(float, M_JACOBI, true, F_NONE, float, 4, 1, MAT_ANY);            // op_jaco
 INST(float, M_JACOBI, false, F_PROLONG, float, 4, 1, MAT_ANY);        // vcycle way up, fp32 cycle, unfused
 INST(float, M_RESID, false, F_NONE, float, 8, 1, MAT_ANY);            // op_residual, fp32 cycle (fmg_start)
 INST(float, M_RESID, false, F_RESTRICT, float, 5, 1, MAT_ANY);        // resid_restrict, fp32 cycle, one sample per lane
-INST(float, M_RESID, false, F_PROLONG, float, 8, 1, MAT_SHARED);      // fmg_start, fine level: prolongation + residual in one pass
+INST(float, M_RESID, false, F_PROLONG, float, 8, 5, MAT_SHARED);      // fmg_start, fine level: prolongation + residual in one pass
 #undef INST
 
 }  // namespace diffhe_lattice
