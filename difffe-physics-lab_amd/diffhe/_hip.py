@@ -1,5 +1,6 @@
 """ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h, include/diffhe_stress.h,
-include/diffhe_eigenstrain.h, include/diffhe_modal.h, include/diffhe_elastic_shape.h, include/diffhe_elastic_aniso.h).
+include/diffhe_eigenstrain.h, include/diffhe_modal.h, include/diffhe_elastic_shape.h, include/diffhe_elastic_aniso.h,
+include/diffhe_elastic_facets.h).
 
 The library is built in-tree by `__graft_entry__.build()` /
 `make -C difffe-physics-lab_amd/csrc`.  There is NO fallback: if the library or a
@@ -222,6 +223,18 @@ ELASTIC_ANISO_SIGNATURES = {
 }
 ROW_BOUND_BLOCKS = 1024     # DIFFHE_ROW_BOUND_BLOCKS
 
+# name -> (restype, argtypes) of every symbol of include/diffhe_elastic_facets.h, the library's eighth header (tractions,
+# pressure and elastic foundations on boundary facets of elastic bodies, csrc/elastic_facets.hip): bound by the same loop
+# (tests/test_elastic_facets.py holds this table against that header)
+_FACETS = [_PI, _I, _I, _PD, _PD]       # fac, d, nF, area, normal
+ELASTIC_FACET_SIGNATURES = {
+    "diffhe_elastf_facet_table": (_S, [_PD, _PI, _PI, _I, _I, _I, _PD, _PD, _PV]),
+    "diffhe_elastf_assemble": (_S, [*_FACETS, _PI, _PI, _PI, _PI, _I, _PB, _PD, _PD, _L, _L, _L, _PD, _L, _L, _PD, _L, _L,
+                                    _PD, _L, _L, _PD, _PD, _I, _I, _I, _I, _PV]),
+    "diffhe_elastf_grad": (_S, [*_FACETS, _PD, _PD, _PD, _I, _I, _PD, _L, _L, _L, _PD, _L, _L, _PD, _L, _L, _PD, _L, _L,
+                                _PV]),
+}
+
 _lib = None
 
 
@@ -258,7 +271,8 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *ELASTIC_SIGNATURES.items(), *STRESS_SIGNATURES.items(),
                                   *EIGENSTRAIN_SIGNATURES.items(), *MODAL_SIGNATURES.items(),
-                                  *ELASTIC_SHAPE_SIGNATURES.items(), *ELASTIC_ANISO_SIGNATURES.items()):
+                                  *ELASTIC_SHAPE_SIGNATURES.items(), *ELASTIC_ANISO_SIGNATURES.items(),
+                                  *ELASTIC_FACET_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = (_I if res is _S else res), args
             if res is _S:

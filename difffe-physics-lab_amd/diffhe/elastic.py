@@ -14,7 +14,8 @@ in E exactly as the scalar operator is linear in kappa, so the layouts, the expl
 Layouts.  E: (), (B,), (m,), (B, m), and (m, B) with layout="node" -- resolved by `solver._kappa_layout`, so the (B,) /
 (m,) rule is the scalar solver's; the gradient comes back in the shape of E, and a field shared by the batch gets its
 gradient summed over the batch inside the kernel, in a fixed order.  f (a nodal body-force density, None = zero) and
-load (a nodal force vector: point loads, tractions integrated by the caller) are (n, d) or (B, n, d), with layout="node"
+load (a nodal force vector: point loads; tractions, pressure and elastic foundations on boundary facets are
+`diffhe.elastic_facets.TractionElasticFESolver`'s, which integrates them) are (n, d) or (B, n, d), with layout="node"
 (n, d, B); u has the shape of the right-hand side.  F_a = M f_a + load_a per component a with the load map M of the
 scalar solvers (`plan.Mvals`).  dL/dload = lambda and dL/df = M lambda with the adjoint lambda, which vanishes on fixed
 dofs: dL/dload is zero there, and a fixed dof's f still reaches its free neighbours through M.
@@ -78,7 +79,8 @@ Node gradients (mesh.nodes requiring grad): `diffhe.elastic_shape.ShapeElasticFE
 solve and of the stress methods; `ElasticFESolver` itself refuses moving nodes.
 
 Not implemented (NotImplementedError): 1D meshes, P2 meshes, backward with create_graph=True, a per-call `dirichlet=`,
-Robin / flux data (h=, u_inf=, flux=); `amg=dict(strength=...)`.
+Robin / flux data (h=, u_inf=, flux=: surface tractions, pressure and elastic foundations are `traction=`, `pressure=`,
+`k_normal=`, `k_tangent=` of `diffhe.elastic_facets.TractionElasticFESolver`); `amg=dict(strength=...)`.
 """
 from __future__ import annotations
 
@@ -245,6 +247,25 @@ def _cycle_defaults(amg: dict, n_dofs: int, Bp: int) -> dict:
     if amg.get("gamma") is None:
         amg["gamma"] = 2 if n_dofs * Bp >= 12_000_000 else 1
     return amg
+
+
+def _measure_row_bounds(state, Bv: int, error: str) -> Tuple[float, ...]:
+    """The row bound (diffhe_ell_jacobi_row_bound) of every level of the hierarchy `state.hier` of one call, written over
+    the levels' recorded bounds (thousandths, rounded up: diffhe_amg_level.reserved).  ONE device synchronisation: the
+    copy of the n_levels doubles.  A bound that is not finite raises ValueError(error).  For the calls whose operator is
+    not a positive combination of the unit-E element matrices (diffhe.elastic_aniso, diffhe.elastic_facets)."""
+    arr, chain = state.hier
+    dev, st = state.plan.device, _stream(state.plan.device)
+    part = torch.empty(_hip.ROW_BOUND_BLOCKS, dtype=torch.float64, device=dev)
+    out = torch.empty(len(chain), dtype=torch.float64, device=dev)
+    for l, lv in enumerate(chain):
+        state.eng.L.diffhe_ell_jacobi_row_bound(lv["vals"], lv["cols"], lv["n"], lv["W"], Bv, part, out[l:], st)
+    bounds = tuple(out.cpu().tolist())
+    if not all(math.isfinite(b) for b in bounds):
+        raise ValueError(error)
+    for l, b in enumerate(bounds):
+        arr[l].reserved = int(math.ceil(1000.0 * b))
+    return bounds
 
 
 # ---------------------------------------------------------------------------------------------

@@ -46,16 +46,14 @@ grad); vibration modes (`modes`: `ElasticEigenSolver` takes (E, nu) only); a per
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
 
-from . import _hip
-from .elastic import (ElasticFESolver, _ElasticCall, _ElasticSolve, _Inputs, _batch_of, _cycle_defaults, _setup_of,
-                      lame_unit, parse_fixed)
+from .elastic import (ElasticFESolver, _ElasticCall, _ElasticSolve, _Inputs, _batch_of, _cycle_defaults,
+                      _measure_row_bounds, _setup_of, lame_unit, parse_fixed)
 from .plan import get_plan, padded_batch, _stream
 from .solver import (K_SAMPLE, K_SAMPLE_ELEM, K_SCALAR, SolveInfo, _SOLVERS, _call_options, _fake_grads,
                      _kappa_layout, _like_grads, _register_state, _resolve_device, _run_call, _state_of, _tensor_mode,
@@ -247,19 +245,8 @@ class _AnisoElasticSolve(_ElasticSolve):
     def _measure_bounds(self, Bv) -> Tuple[float, ...]:
         """The row bound of every level of this call's hierarchy, written over the levels' recorded bounds (thousandths,
         rounded up: diffhe_amg_level.reserved).  ONE device synchronisation: the copy of the n_levels doubles."""
-        arr, chain = self.hier
-        dev, st = self.plan.device, _stream(self.plan.device)
-        part = torch.empty(_hip.ROW_BOUND_BLOCKS, dtype=torch.float64, device=dev)
-        out = torch.empty(len(chain), dtype=torch.float64, device=dev)
-        for l, lv in enumerate(chain):
-            self.eng.L.diffhe_ell_jacobi_row_bound(lv["vals"], lv["cols"], lv["n"], lv["W"], Bv, part, out[l:], st)
-        bounds = tuple(out.cpu().tolist())
-        if not all(math.isfinite(b) for b in bounds):
-            raise ValueError("diffhe: stiffness tensor not positive definite (a diagonal entry of the assembled operator "
-                             "is not positive and finite)")
-        for l, b in enumerate(bounds):
-            arr[l].reserved = int(math.ceil(1000.0 * b))
-        return bounds
+        return _measure_row_bounds(self, Bv, "diffhe: stiffness tensor not positive definite (a diagonal entry of the "
+                                   "assembled operator is not positive and finite)")
 
     def forward(self, call_in, info: SolveInfo) -> torch.Tensor:
         C, f, load = call_in.E, call_in.f, call_in.load

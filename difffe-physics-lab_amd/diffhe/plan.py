@@ -779,6 +779,50 @@ class SolvePlan:
                               ent_code=dev((F * 16 + p * 4 + c)[order]), ent_slot=dev(slot[order]))
             return cache[key]
 
+    def elastic_facet_table(self, key, facets: np.ndarray, opposite: np.ndarray):
+        """The boundary band of tractions, pressure and foundations on the facets `facets` (n_F, d) int64 of an elastic
+        body (csrc/elastic_facets.hip), built once per (plan, facet set `key`): the fields of `robin_table` for d dofs per
+        node, plus `normal` (d, n_F), the outward unit normal -- away from `opposite` (n_F), the node of the owning element
+        opposite the facet -- computed on the device with `area`.  Fixed dofs come per dof from the solver, not per node
+        from the mesh: `rows` lists EVERY node on a facet and `ent_slot` is the node slot of the coupling (row, node c of
+        F) in `cols`, never -1; the kernels skip fixed rows and lift fixed columns themselves.  Returns None when a
+        coupling has no slot in this plan's pattern."""
+        cache = self.__dict__.setdefault("_elastic_facet_tables", {})
+        with self._build_lock:
+            if key in cache:
+                return cache[key]
+            self._ensure_ell()
+            nF, d = facets.shape
+            if nF < 1 or nF >= 2 ** 27:
+                raise ValueError(f"diffhe: {nF} facets (expected 1 .. 2**27 - 1)")
+            if d != self.dim or d not in (2, 3) or facets.min() < 0 or facets.max() >= self.n:
+                raise ValueError("diffhe: facets must be (n_F, dim) node ids of this 2D or 3D mesh")
+            if opposite.shape != (nF,) or opposite.min() < 0 or opposite.max() >= self.n:
+                raise ValueError("diffhe: one opposite node of this mesh per facet")
+            cols = self.cols.cpu().numpy()                                   # (W, n)
+            F = np.repeat(np.arange(nF, dtype=np.int64), d * d)
+            pc = np.tile(np.arange(d * d, dtype=np.int64), nF)
+            p, c = pc // d, pc % d
+            row, col = facets[F, p], facets[F, c]
+            hit = cols[:, row] == col[None, :]                               # (W, entries); the diagonal is slot 0
+            if not bool(hit.any(axis=0).all()):
+                cache[key] = None
+                return None
+            slot = hit.argmax(axis=0)
+            order = np.argsort(row, kind="stable")                           # by row, facet order inside
+            rows, counts = np.unique(row, return_counts=True)
+            row_ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+            np.cumsum(counts, out=row_ptr[1:])
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)  # noqa: E731
+            fac = dev(facets.T)
+            area = torch.empty(nF, dtype=torch.float64, device=self.device)
+            normal = torch.empty((d, nF), dtype=torch.float64, device=self.device)
+            _hip.lib().diffhe_elastf_facet_table(self.coords, fac, dev(opposite), d, self.n, nF, area, normal,
+                                                 _stream(self.device))
+            cache[key] = dict(d=d, n_f=nF, fac=fac, area=area, normal=normal, rows=dev(rows), n_rows=len(rows),
+                              row_ptr=dev(row_ptr), ent_code=dev((F * 16 + p * 4 + c)[order]), ent_slot=dev(slot[order]))
+            return cache[key]
+
     def ensure_ell(self):
         """ELL pattern, gather lists, element integrals and the ELL load matrix of the general path."""
         with self._build_lock:
