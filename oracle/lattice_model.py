@@ -25,6 +25,13 @@ its terms in reverse order.  fp32: the cycle's vectors, r32 = (float)(rs r), the
 copies are rounded to float32 where the fp32 cycle stores them (arithmetic stays in `dtype`).  arith32: the cycle's
 arithmetic is float32 as well (the fused passes and the two-samples-per-lane kernels compute in fp32, not only store in
 it).  r.z is accumulated, as the kernels do it, from the last sweep's result BEFORE it is rounded for storage.
+
+Pinned by truncated solves, besides the cold cycle: the diagonal shift of a factored operator (every level's own shift in
+the smoother's diagonal, the residuals, the Chebyshev level and the CG's operator; SHIFT_MUTATIONS) and the warm start
+(pcg(x_init=...): where rs enters, which residual feeds the start, where the pending correction and the guess are added;
+WARM_MUTATIONS).  The coarsest level's spectrum bound ignores the shift, as the device's does (gershgorin_lmax).
+Still held by converged solves only: the stopping rules (floor, energy estimate, the low half of the residual pair being
+dropped near the stop), the adjoint solve's warm start from the previous lambda, and the direct (single dense level) solve.
 """
 from __future__ import annotations
 
@@ -35,11 +42,18 @@ import numpy as np
 
 OMEGAS = (0.56, 1.39)                   # Chebyshev weights for the interval [0.5, 2] of D^-1 A (nu = 2)
 
+# defects of the diagonal shift of a factored operator, A_b = scale_b K_1 + diag(shift), and of the warm start
+SHIFT_MUTATIONS = ("shift_dropped_coarse", "shift_not_rediscretised", "shift_scaled", "shift_not_in_diag",
+                   "shift_dropped_residual", "shift_dropped_A0", "shift_row_off", "shift_col_off", "shift_tail")
+WARM_MUTATIONS = ("warm_guess_dropped", "warm_residual_of_b", "warm_rs_missing", "warm_pending_twice")
 # single defects a model can be given (tests: each must move a truncated iterate far beyond the comparison's tolerance)
 MUTATIONS = ("pre_weight_slot", "restrict_corner_quarter", "restrict_corners_swapped", "restrict_writes_dirichlet",
              "prolong_corrects_dirichlet", "halo_east_dropped", "halo_east_dropped_tail", "diag4_mirrored",
              "coarse_no_scale", "cheby_degree_off", "final_z_omitted", "rs_not_undone", "h16_no_rowsum",
-             "fmg_pending_dropped", "guess_from_zero", "post_order", "pre_order")
+             "fmg_pending_dropped", "guess_from_zero", "post_order", "pre_order") + SHIFT_MUTATIONS + WARM_MUTATIONS
+# not a defect but a measure: the coarsest level's solve returns 0 -- how far the iterates move then bounds what any defect
+# of that solve can do to them
+PROBES = ("coarse_zero",)
 # pairs that are equal in exact arithmetic: two sweeps are polynomials in D^-1 A applied to the same right-hand side,
 #   x'' = (I - w_b D^-1 A)(I - w_a D^-1 A) x + (w_a + w_b - w_a w_b D^-1 A) D^-1 rhs,
 # symmetric in (w_a, w_b) -- the order of the two post-sweeps, and of the two pre-sweeps, changes roundings only
@@ -63,9 +77,19 @@ def strip_use(lv, Bp, T, spl=1):
 
 
 def level_forms(levels, Bv, Bp, T, fp32, scale=None, fused=1, pre4=1, dense_mfma=1, split_start=0, fp32_step=1,
-                resid_pair=1, nu=2):
+                resid_pair=1, nu=2, fmg=0, warm=0):
     """Per level dict(pre, post, coarse, guess, coef32, tile); plus, under key None, the driver's forms.
-    levels: dicts with nx, ny, nd and the PRESENCE of vals32 / rd32 / o16 / shift / dense_inv (values are not read)."""
+    levels: dicts with nx, ny, nd and the PRESENCE of vals32 / rd32 / o16 / shift / dense_inv (values are not read).
+
+    A level with a shift (Bv == 1 only) has no shared fp32 copy (shared32_ok), hence no two-samples-per-lane kernels, no
+    fused passes, no initial-guess cycle and no fp32 step length: its strip levels run dia_strip_shift_kernel ("strip_*"),
+    the others the generic kernels with their shift_at terms, and -- there is no dense inverse of a shifted operator -- the
+    last level is the Chebyshev semi-iteration.
+    The start of a full-multigrid solve is two facts, which differ with a shift: the DRIVER (Solve::fused_start,
+    lattice_pcg.hip) converts and restricts b in one pass and hands fmg_start the level-1 right-hand side (`cvt_restrict`,
+    = have_b1) without looking at the shift; the CYCLE (prolong_resid_ok, lattice_cycle.hip) takes prolongation and residual
+    of the fine level as one strip pass (`prolong_resid`) only without one.  A warm start (`warm`, DIFFHE_PCG_WARM) forces
+    the split start on both: the start's right-hand side is then the residual pass's fp32 copy, not b's."""
     nl, wave = len(levels), T["wave"]
     out = {}
     halves = lambda l: l + 1 < nl and levels[l]["nx"] == 2 * levels[l + 1]["nx"] and levels[l]["ny"] == 2 * levels[l + 1]["ny"]  # noqa: E731
@@ -111,10 +135,14 @@ def level_forms(levels, Bv, Bp, T, fp32, scale=None, fused=1, pre4=1, dense_mfma
     shared32_0 = (Bv == 1 and L0.get("vals32") is not None and L0.get("rd32") is not None and L0.get("shift") is None
                   and Bp % wave == 0)
     cspl = 2 if Bp % (2 * wave) == 0 else 1
+    fusable = bool(not split_start and fp32 and Bv == 1 and nl > 1 and strip0 and halves(0))
     out[None] = dict(cg="fused_step" if strip0 else "unfused", rupd=rupd, rpair=bool(rupd and resid_pair),
                      step2=bool(fp32 and rupd and fp32_step and Bp % wave == 0 and strip_use(L0, Bp, T, cspl) and shared32_0),
-                     p32=bool(fp32 and strip0),
-                     fused_start=bool(not split_start and fp32 and Bv == 1 and nl > 1 and strip0 and halves(0)))
+                     p32=bool(fp32 and strip0), warm=bool(warm),
+                     # what the two facts of the start share, before the start itself, a guess or a shift are looked at
+                     fused_start=fusable,
+                     cvt_restrict=bool(fusable and fmg and not warm and Bp % wave == 0),
+                     prolong_resid=bool(fusable and fmg and not warm and L0.get("shift") is None))
     return out
 
 
@@ -125,7 +153,11 @@ def dense_level(levels, max_nodes=1200):
 
 def gershgorin_lmax(level):
     """H.coarse_lmax as cycle_coarse_bound sets it: 2, or on a 4-diagonal coarsest level the Gershgorin bound of
-    D^-1 A over all rows and stored samples, times 1 + 1e-9, where that lies in (2, 1e3)."""
+    D^-1 A over all rows and stored samples, times 1 + 1e-9, where that lies in (2, 1e3).
+    dia_gershgorin_kernel reads the stored diagonals alone: neither the per-sample scale nor a shift enters.  That is the
+    bound of D^-1 K_1; with a shift s >= 0 every row's sum_j |a_ij| / a_ii only shrinks, (d + o) / d >= (s_b d + s + s_b o)
+    / (s_b d + s), so it still bounds the shifted operator's spectrum (from further above), and the model takes the same
+    number."""
     if level["nd"] != 4:
         return 2.0
     v = np.asarray(level["vals"], dtype=np.float64)
@@ -146,8 +178,8 @@ class Result:
 
 class LatticeModel:
     def __init__(self, levels, forms, scale=None, omegas=OMEGAS, n_coarse=4, coarse_lmax=2.0, fp32=False, arith32=False,
-                 dtype=np.float64, reverse=False, columns=None, fmg=False, fmg_cycles=1, mutate=()):
-        unknown = set(mutate) - set(MUTATIONS)
+                 dtype=np.float64, reverse=False, columns=None, fmg=False, fmg_cycles=1, warm=False, mutate=()):
+        unknown = set(mutate) - set(MUTATIONS) - set(PROBES)
         assert not unknown, unknown
         assert not arith32 or fp32
         self.mutate, self.reverse = frozenset(mutate), bool(reverse)
@@ -155,10 +187,13 @@ class LatticeModel:
         self.ct = np.float32 if arith32 else dtype          # the type the cycle computes in
         self.columns = None if columns is None else np.asarray(columns, dtype=np.int64)
         self.omegas, self.nu, self.n_coarse, self.lmax = tuple(omegas), len(omegas), int(n_coarse), float(coarse_lmax)
-        self.fmg, self.fmg_cycles = bool(fmg) and len(levels) > 1, int(fmg_cycles)
+        self.fmg, self.fmg_cycles, self.warm = bool(fmg) and len(levels) > 1, int(fmg_cycles), bool(warm)
         self.forms, self.nl = forms, len(levels)
         self.shared = np.asarray(levels[0]["vals"]).ndim == 2
         self.scale = None if scale is None else self._cols(np.asarray(scale, dtype=np.float64)).astype(dtype)
+        self._shift0 = None if levels[0].get("shift") is None else np.asarray(levels[0]["shift"], dtype=np.float64).reshape(-1)
+        self._nxy0 = (int(levels[0]["nx"]), int(levels[0]["ny"]))
+        self.shift_index_delta = {}      # per index defect of the shift: max |shift read - shift| / diagonal, level 0
         self.lv = [self._level(l, lv) for l, lv in enumerate(levels)]
 
     # -- set-up ----------------------------------------------------------------------------------------------------
@@ -175,8 +210,7 @@ class LatticeModel:
         v = v[:, :, None] if v.ndim == 2 else self._cols(v)
         L = dict(nx=nx, ny=ny, nd=nd, W=W, n=n, bc=bc, free=(~bc)[:, None], unit=False)
         L["A64"] = v.astype(dt)                                   # the outer CG's operator (level 0) in fp64
-        sh = lv.get("shift")
-        L["shift"] = None if sh is None else np.asarray(sh, dtype=np.float64).reshape(n, 1)
+        L["shift"] = self._shift(l, lv, L)
         rsn = None if self.scale is None else np.where(L["free"], self.scale[None, :], dt(1.0))   # row_scale
         L["rsn"] = rsn
         c = v
@@ -228,10 +262,63 @@ class LatticeModel:
             L["dense"] = np.asarray(lv["dense_inv"]).astype(np.float64).astype(ct)
         return L
 
+    def _shift(self, l, lv, L):
+        """The level's diagonal shift (n, 1) or None, with whatever defect it was given."""
+        sh = lv.get("shift")
+        if sh is None:
+            return None
+        n, W, mut = L["n"], L["W"], self.mutate
+        sh = np.asarray(sh, dtype=np.float64).reshape(n).copy()
+        free, col = ~L["bc"], np.arange(n) % W
+        if l >= 1 and "shift_dropped_coarse" in mut:
+            sh[:] = 0.0
+        if l >= 1 and "shift_not_rediscretised" in mut:      # the fine level's nodal values at the coarse nodes
+            nx0, ny0 = self._nxy0
+            ry, rx = ny0 // L["ny"], nx0 // L["nx"]
+            rows, cols = np.divmod(np.arange(n), W)
+            sh = np.where(free, self._shift0[rows * ry * (nx0 + 1) + cols * rx], 0.0)
+        for name, off in (("shift_row_off", W), ("shift_col_off", 1)):
+            moved = np.zeros(n)
+            moved[off:] = sh[:n - off]                       # row R + 1 (column c + 1) reads the shift of row R (column c)
+            if off == 1:
+                moved[col == 0] = 0.0
+            moved = np.where(free, moved, 0.0)
+            # live: some free node reads another FREE node's different shift (not only the boundary's 0)
+            src_free = np.zeros(n, dtype=bool)
+            src_free[off:] = free[:n - off]
+            if off == 1:
+                src_free[col == 0] = False
+            if l == 0:       # what the defect does to the fine level's diagonal, relative: the size of its effect on x
+                d0 = np.asarray(lv["vals"], dtype=np.float64)[0].reshape(n, -1).min(axis=1)
+                smin = 1.0 if self.scale is None else float(np.min(self.scale))
+                live = free & src_free
+                self.shift_index_delta[name] = float(np.max(np.abs(moved - sh)[live] / (smin * d0 + sh)[live])) if live.any() else 0.0
+            if name in mut:
+                sh = moved
+        if "shift_tail" in mut and self.forms[l]["strip"]:   # the strips that take the clamped (TAIL) body: both edges
+            rw = 4 if self.fp32 else 8
+            sh = np.where((col < rw) | (col >= rw * -(-(W - rw) // rw)), 0.0, sh)
+        return sh.reshape(n, 1)
+
+    def _sh(self, L):
+        """diag(shift) as the operators add it: (n, 1), or (n, B) where a defect scales it per sample; None: no shift."""
+        if L["shift"] is None or "shift_scaled" not in self.mutate or L["rsn"] is None:
+            return L["shift"]
+        return L["rsn"].astype(np.float64) * L["shift"]
+
+    def shift_share(self):
+        """The largest part the shift has of a free row's diagonal on level 0 (0 without one)."""
+        L = self.lv[0]
+        if L["shift"] is None:
+            return 0.0
+        d = np.asarray(L["A64"][0], dtype=np.float64) * (1.0 if L["rsn"] is None else np.asarray(L["rsn"], dtype=np.float64))
+        return float(np.max(np.where(L["free"], L["shift"] / (d + L["shift"]), 0.0)))
+
     def applies(self, mutation):
         """Whether this model has what the mutation would break."""
         lv, nl = self.lv, self.nl
         dense = lv[-1].get("dense") is not None
+        shifted = self._shift0 is not None and bool(np.any(self._shift0))
         return {"pre_weight_slot": nl > 1, "restrict_corner_quarter": self._full(), "restrict_corners_swapped": self._full(),
                 "restrict_writes_dirichlet": nl > 1, "prolong_corrects_dirichlet": self._dirichlet_interpolates(),
                 "halo_east_dropped": True,
@@ -240,7 +327,16 @@ class LatticeModel:
                 "final_z_omitted": True, "rs_not_undone": self.fp32,
                 "h16_no_rowsum": any(L.get("h16") for L in lv),
                 "fmg_pending_dropped": self.fmg, "guess_from_zero": self.fmg and any(self.forms[l]["guess"] for l in range(nl)),
-                "post_order": nl > 1, "pre_order": nl > 1}[mutation]
+                "post_order": nl > 1, "pre_order": nl > 1,
+                "shift_dropped_coarse": shifted and nl > 1, "shift_not_rediscretised": shifted and nl > 1,
+                "shift_scaled": shifted and self.scale is not None and bool(np.any(self.scale != 1)),
+                "shift_not_in_diag": shifted, "shift_dropped_residual": shifted and nl > 1, "shift_dropped_A0": shifted,
+                "shift_row_off": shifted and self.shift_index_delta.get("shift_row_off", 0.0) > 0.0,
+                "shift_col_off": shifted and self.shift_index_delta.get("shift_col_off", 0.0) > 0.0,
+                "shift_tail": shifted and bool(self.forms[0]["strip"]),
+                "warm_guess_dropped": self.warm, "warm_residual_of_b": self.warm,
+                "warm_rs_missing": self.warm and self.fmg and self.fp32,
+                "warm_pending_twice": self.warm and self.fmg}[mutation]
 
     def _dirichlet_interpolates(self):
         """Some fine Dirichlet node interpolates from a free coarse node (never on a boundary that is Dirichlet as a
@@ -285,21 +381,21 @@ class LatticeModel:
                 acc[off:] += minus[k][:n - off] * x[:n - off]
         return acc
 
-    def _A(self, L, x):
+    def _A(self, L, x, drop_shift=False):
         """The cycle's operator of the level: row_scale K x + shift x."""
         y = self._K(L, x)
         if L["rsn"] is not None:
             y = L["rsn"].astype(y.dtype) * y
-        if L["shift"] is not None:
-            y = y + L["shift"].astype(y.dtype) * x
+        if L["shift"] is not None and not drop_shift:
+            y = y + self._sh(L).astype(y.dtype) * x
         return y
 
     def _dinv(self, L):
         d = L["c"][0]
         if L["rsn"] is not None:
             d = L["rsn"].astype(d.dtype) * d
-        if L["shift"] is not None:
-            d = d + L["shift"].astype(d.dtype)
+        if L["shift"] is not None and "shift_not_in_diag" not in self.mutate:
+            d = d + self._sh(L).astype(d.dtype)
         if L.get("rcp32"):
             return (np.float32(1.0) / d.astype(np.float32)).astype(self.ct)
         return self.ct(1.0) / d
@@ -374,6 +470,9 @@ class LatticeModel:
     def coarse_solve(self, l, rhs):
         """The dense inverse times 1 / s_b, or the Chebyshev semi-iteration of coarse_solve (lattice_cycle.hip)."""
         L = self.lv[l]
+        if "coarse_zero" in self.mutate:
+            self._wide = np.zeros_like(rhs)
+            return self._wide
         if L.get("dense") is not None:
             x = L["dense"] @ rhs
             if self.scale is not None and "coarse_no_scale" not in self.mutate:
@@ -381,13 +480,9 @@ class LatticeModel:
                 x = si.astype(x.dtype) * x
             self._wide = x
             return self._st(x)
-        lmin = 0.5 * (0.5 * (1.0 - math.cos(math.pi / L["nx"])) + 0.5 * (1.0 - math.cos(math.pi / L["ny"])))
-        lmax = self.lmax
-        deg = min(max(int(math.ceil(1.5 * math.sqrt(lmax / lmin))), self.n_coarse), 400)
+        deg, theta, delta, sigma = self._cheby(L)
         if "cheby_degree_off" in self.mutate:
             deg -= 1
-        theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
-        sigma = theta / delta
         rho = 1.0 / sigma
         dinv, ct = self._dinv(L), self.ct
         dn = ct(1.0 / theta) * rhs * dinv
@@ -402,6 +497,22 @@ class LatticeModel:
             x = self._st(self._wide)
             rho = rho_new
         return x
+
+    def _cheby(self, L):
+        """(degree, theta, delta, sigma) of the semi-iteration on level L, as coarse_solve chooses them."""
+        lmin = 0.5 * (0.5 * (1.0 - math.cos(math.pi / L["nx"])) + 0.5 * (1.0 - math.cos(math.pi / L["ny"])))
+        lmax = self.lmax
+        deg = min(max(int(math.ceil(1.5 * math.sqrt(lmax / lmin))), self.n_coarse), 400)
+        theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
+        return deg, theta, delta, theta / delta
+
+    def cheby_last_step_share(self):
+        """A bound of what the last step of the coarsest level's semi-iteration changes, as a part of that level's
+        solution: the error polynomials of degree k - 1 and k are at most 1 / T_(k-1)(sigma) and 1 / T_k(sigma) on the
+        interval the iteration is built for, so the two results differ by at most their sum."""
+        deg, _, _, sigma = self._cheby(self.lv[-1])
+        t = lambda k: math.cosh(k * math.acosh(sigma))   # noqa: E731
+        return 1.0 / t(deg - 1) + 1.0 / t(deg)
 
     def cycle(self, rhs, l0=0, guess=None):
         """z = V(rhs) on levels l0 .. last from a zero guess; guess given: the new ITERATE from the initial guess
@@ -427,7 +538,7 @@ class LatticeModel:
                 for ws in pre:
                     x = self._st(self._sweep(L, rhs_l[l], x, ws))
             cur[l] = x
-            r = self._st(rhs_l[l] - self._A(L, x))
+            r = self._st(rhs_l[l] - self._A(L, x, drop_shift="shift_dropped_residual" in self.mutate))
             rhs_l[l + 1] = self._st(self._restrict(l, r))
         for l in range(last - 1, l0 - 1, -1):
             L = self.lv[l]
@@ -481,8 +592,8 @@ class LatticeModel:
         y = self._K(L, x, L["A64"])
         if L["rsn"] is not None:
             y = L["rsn"] * y
-        if L["shift"] is not None:
-            y = y + L["shift"].astype(self.dtype) * x
+        if L["shift"] is not None and "shift_dropped_A0" not in self.mutate:
+            y = y + self._sh(L).astype(self.dtype) * x
         return y
 
     def _pAp32(self, p):
@@ -494,8 +605,9 @@ class LatticeModel:
         s = np.sum((p32 * kp).astype(np.float64), axis=0).astype(self.dtype)
         return s if self.scale is None else s * self.scale
 
-    def pcg(self, b, ks=(0, 1, 3)):
-        """The solve from a cold (zero or full-multigrid) start; -> Result with snap[k] for every k of ks."""
+    def pcg(self, b, ks=(0, 1, 3), x_init=None):
+        """The solve from a cold (zero or full-multigrid) start, or (x_init (n, B), a model built with warm=True) from the
+        caller's guess; -> Result with snap[k] for every k of ks."""
         dt = self.dtype
         b = np.asarray(b, dtype=np.float64)
         if self.columns is not None and b.shape[1] != len(self.columns):
@@ -515,7 +627,31 @@ class LatticeModel:
             z = self.cycle(rin)
             return z.astype(dt), np.sum(rin.astype(dt) * self._wide.astype(dt), axis=0)
 
-        if self.fmg:
+        assert (x_init is not None) == self.warm
+        mut = self.mutate
+        if self.warm:
+            # PCGRun::start() with DIFFHE_PCG_WARM: x holds the caller's guess g.  rs comes from b.b as in a cold solve; b
+            # itself is never converted (no pcg_cvt_kernel).  The residual pass leaves r = b - A g in fp64 and its copy
+            # (float)(rs r); with the full-multigrid start that copy (fp64 cycle: r itself) is the start's right-hand
+            # side, and pcg_setx_kernel (add = 1) writes x = (x0 + e0) / rs + g in fp64 -- the start's iterate, its pending
+            # correction e0 once, the scale undone on both, the guess added unscaled.  Then the residual of that x.
+            # Without the start the guess is the iterate and r its residual.
+            g = np.asarray(x_init, dtype=np.float64)
+            if self.columns is not None and g.shape[1] != len(self.columns):
+                g = g[:, self.columns]
+            g = g.astype(dt)
+            r = b.copy() if "warm_residual_of_b" in mut else b - self._A0(g)
+            if self.fmg:
+                x0, e0 = self.fmg_start(rin_of(r))
+                pend = 0 if "fmg_pending_dropped" in mut else 2 if "warm_pending_twice" in mut else 1
+                x = x0.astype(dt) + dt(pend) * e0.astype(dt)
+                x = x if "warm_rs_missing" in mut else x / rs
+                if "warm_guess_dropped" not in mut:
+                    x = x + g
+                r = b - self._A0(x)
+            else:
+                x = np.zeros_like(b) if "warm_guess_dropped" in mut else g
+        elif self.fmg:
             x0, e0 = self.fmg_start(rin_of(b))
             x = x0.astype(dt) if "fmg_pending_dropped" in self.mutate else x0.astype(dt) + e0.astype(dt)
             x = x / rs                                           # pcg_setx_kernel, in fp64
