@@ -14,7 +14,10 @@ gradients to the film coefficient, the ambient value and the flux, also exported
 the smallest eigenpairs of K phi = lambda M_L phi per sample with d lambda / d kappa, also exported here;
 `diffhe.elastic`: `ElasticFESolver`, linear elasticity on P1 triangles and tetrahedra -- the first vector-valued problem,
 d displacement components per node -- with gradients to a Young's modulus per element, the body force and the nodal
-load, also exported here (its kernels are declared in include/diffhe_elastic.h), and its `stress` / `von_mises` with
+load, also exported here (its kernels are declared in include/diffhe_elastic.h), and the ONE call pipeline of the elastic
+family (`_ElasticSolve.forward` / `adjoint` with hooks, the hierarchy choice, the call builder, the shared plumbing of
+the solve ops, the shared construction of the public solvers) that the other elastic modules build on;
+`diffhe.elastic_stress`, re-exported by `diffhe.elastic`: its `stress` / `von_mises` with
 gradients to u and E and `pnorm` (kernels declared in include/diffhe_stress.h), and its eigenstrain (initial strain:
 thermal expansion, swelling, pre-stress) -- `eigenstrain_load`, `eigenstrain=` on the solve and on the stress methods,
 with gradients to eps0 and E, and the torch helpers `thermal_strain` / `element_mean` that carry the temperature of a

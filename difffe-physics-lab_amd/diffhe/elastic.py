@@ -36,47 +36,18 @@ translations exactly.  It is built from the unit-E operator and cached per (plan
 carries `amg.jacobi_bound` of its unit operator for the cycle's Jacobi weights (elastic operators have positive
 off-diagonals).  The coarse space has no rotations ("Elasticity").
 
-Stress recovery (csrc/stress.hip, include/diffhe_stress.h): `solver.stress(u, E=None)`, `solver.von_mises(u, E=None)`,
-`solver.stress_and_von_mises(u, E=None)` and `pnorm(vm, p)`, differentiable in u and E.  Per element e and sample b, with
-the element-constant displacement gradient H[a][t] = sum_p u[(p, a)] g_p[t] and eps = (H + H^T) / 2:
-
-    unit stress   s = 2 mu' eps + lambda' tr(eps) I,   (lambda', mu') = lame_unit(nu, dim, plane)
-    stress        sigma = E_e s
-    Voigt order   diffhe.aniso's: nc = 3, (xx, yy, xy) in 2D; nc = 6, (xx, yy, zz, yz, xz, xy) in 3D.  A shear component
-                  is the tensor component itself, not doubled; its cotangent is the derivative with respect to that one
-                  number.
-    out of plane  plane stress: sigma_zz = 0; plane strain: sigma_zz = E lambda' tr(eps) = nu (sigma_xx + sigma_yy).
-                  `stress` returns the in-plane components only, `von_mises` includes sigma_zz.
-    von Mises     vm^2 = 1/2 [(s_xx - s_yy)^2 + (s_yy - s_zz)^2 + (s_zz - s_xx)^2] + 3 (s_xy^2 + s_yz^2 + s_xz^2) of sigma,
-                  absent components zero; d vm / d sigma = (3/2) dev(sigma) / vm, defined as 0 where vm == 0: no NaN or
-                  Inf leaves the kernels.
-
-u is the full displacement as `forward` returns it, prescribed values included: the evaluation is a pure function of
-(u, E, mesh, nu, plane) and reads no Dirichlet data.  An explicit E evaluates the stress with another modulus than the
-solve used (the relaxed stress rho^q E_0 D eps of stress-constrained SIMP); the batch rules are those of E above, and an
-unbatched u with a batched E is broadcast.  The gradients come from one element pass (dL/dE, and a symmetric tensor per
-element) and one node pass over the per-node incidence list (dL/du), in fixed orders: bitwise reproducible.
-
-Eigenstrain (csrc/eigenstrain.hip, the eigen instantiations of csrc/stress.hip, include/diffhe_eigenstrain.h): an initial
-strain eps0 per element and sample -- thermal expansion, swelling, shrinkage, pre-stress.  nc0 = 3 components (xx, yy, xy)
-in plane stress, 4 in plane strain, (xx, yy, xy, zz): the total eps_zz is 0 there, so an eps0_zz is constrained and loads
-the body in plane; 6 in 3D; shear components are tensor components.  Layouts: (nc0,), (B, nc0), (m, nc0), (B, m, nc0), and
-(nc0, m, B) with layout="node" -- `AnisotropicFESolver`'s -- with the batch rules of `_kappa_layout`.
-
-    unit initial stress   s0 = 2 mu' eps0 + lambda' theta0 I in plane, theta0 = tr eps0 over ALL stored normal components
-    load                  F0[(i, a)] = sum_{(e, p) at i} vol_e E_e sum_t s0_e[a][t] grad phi_p[t]: K(E) u = M f + load + F0
-    stress                sigma = E (s(u) - s0) in plane; sigma_zz = E [lambda' (tr eps(u) - theta0) - 2 mu' eps0_zz] in
-                          plane strain (NOT nu (sigma_xx + sigma_yy)), 0 in plane stress
-
-`solver.eigenstrain_load(eps0, E=None)` is F0, differentiable in eps0 and E; `solver(f, load, eigenstrain=eps0)` adds it
-to `load` in front of the unchanged solve, so that dL/dload = lambda flows back into dL/deps0 and the second E path, which
-autograd adds to the solve's; `stress` / `von_mises` / `stress_and_von_mises(..., eigenstrain=eps0)` evaluate the stress
-above with gradients to u, E and eps0.  `thermal_strain(alpha, dT, dim, plane)` and `element_mean(T, mesh)` (plain torch)
-carry the temperature of a heat solve to eps0.  The gradient of an eps0 shared over elements or samples is a torch `sum`
-of the kernel's per-element, per-sample array over the shared axes.
+Stress recovery and eigenstrain (`solver.stress`, `von_mises`, `stress_and_von_mises`, `eigenstrain_load`,
+`solver(f, load, eigenstrain=eps0)`, `pnorm`, `thermal_strain`, `element_mean`): `diffhe.elastic_stress` holds their ops,
+conventions and layouts; this module re-exports its public names.
 
 Node gradients (mesh.nodes requiring grad): `diffhe.elastic_shape.ShapeElasticFESolver`, this class with dL/dX of the
 solve and of the stress methods; `ElasticFESolver` itself refuses moving nodes.
+
+The call pipeline of the elastic family lives here once ("Elasticity"): `_ElasticSolve` with the only
+`forward` and `adjoint` and the hooks its subclasses override (diffhe.elastic_shape, elastic_aniso, elastic_facets);
+`_select_hierarchy`, the hierarchy choice of the solves and of diffhe.modal; `_solve_call`, the one call builder;
+`_solve_result`, `_solve_fake`, `_run_adjoint` and `_solve_autograd`, the plumbing of the four solve ops; and
+`_ElasticOptions`, `_check_mesh`, `_amg_options`, the construction and argument checking the public solvers share.
 
 Not implemented (NotImplementedError): 1D meshes, P2 meshes, backward with create_graph=True, a per-call `dirichlet=`,
 Robin / flux data (h=, u_inf=, flux=: surface tractions, pressure and elastic foundations are `traction=`, `pressure=`,
@@ -94,10 +65,15 @@ import torch
 import torch.nn as nn
 
 from . import _hip
+from .elastic_stress import (_EigenCall, _StressCall, _eigen_batch, _eigen_call, _stress_adjoint,  # noqa: F401
+                             _stress_backward, _stress_batch, _stress_call, _stress_eigen_backward,
+                             _stress_eigen_setup_context, _stress_forward, _stress_setup_context, _stress_shapes,
+                             eigen_components, eigenstrain_load_backward, eigenstrain_load_op, elastic_stress,
+                             elastic_stress_backward, elastic_stress_eigen, elastic_stress_eigen_backward, element_mean,
+                             pnorm, thermal_strain)    # the names this module held before they moved: they keep resolving
 from .plan import get_plan, padded_batch, valid_batch_pad, _stream
-from .solver import (K_ELEM, K_SAMPLE, K_SAMPLE_ELEM, K_SCALAR, SolveInfo, _Engine, _SOLVERS, _call_options, _kappa_grad,
-                     _kappa_layout, _kappa_mode, _like_grads, _fake_grads, _register_state, _resolve_device, _run_call,
-                     _state_of, _tensor_mode, _tie_state)
+from .solver import (SolveInfo, _Engine, _SOLVERS, _call_options, _kappa_grad, _kappa_layout, _like_grads, _fake_grads,
+                     _register_state, _resolve_device, _run_call, _state_of, _tie_state)
 
 __all__ = ("ElasticFESolver", "lame_unit", "parse_fixed", "dof_pattern", "pnorm", "thermal_strain", "element_mean",
            "eigen_components")
@@ -249,23 +225,44 @@ def _cycle_defaults(amg: dict, n_dofs: int, Bp: int) -> dict:
     return amg
 
 
-def _measure_row_bounds(state, Bv: int, error: str) -> Tuple[float, ...]:
-    """The row bound (diffhe_ell_jacobi_row_bound) of every level of the hierarchy `state.hier` of one call, written over
-    the levels' recorded bounds (thousandths, rounded up: diffhe_amg_level.reserved).  ONE device synchronisation: the
-    copy of the n_levels doubles.  A bound that is not finite raises ValueError(error).  For the calls whose operator is
-    not a positive combination of the unit-E element matrices (diffhe.elastic_aniso, diffhe.elastic_facets)."""
-    arr, chain = state.hier
-    dev, st = state.plan.device, _stream(state.plan.device)
+def _measure_row_bounds(eng: _Engine, hier, Bv: int, error: str) -> Tuple[float, ...]:
+    """The row bound (diffhe_ell_jacobi_row_bound) of every level of the hierarchy `hier` of one call, written over the
+    levels' recorded bounds (thousandths, rounded up: diffhe_amg_level.reserved).  ONE device synchronisation: the copy
+    of the n_levels doubles.  A bound that is not finite raises ValueError(error).  For the calls whose operator is not a
+    positive combination of the unit-E element matrices (diffhe.elastic_aniso, diffhe.elastic_facets)."""
+    arr, chain = hier
+    dev, st = eng.p.device, _stream(eng.p.device)
     part = torch.empty(_hip.ROW_BOUND_BLOCKS, dtype=torch.float64, device=dev)
     out = torch.empty(len(chain), dtype=torch.float64, device=dev)
     for l, lv in enumerate(chain):
-        state.eng.L.diffhe_ell_jacobi_row_bound(lv["vals"], lv["cols"], lv["n"], lv["W"], Bv, part, out[l:], st)
+        eng.L.diffhe_ell_jacobi_row_bound(lv["vals"], lv["cols"], lv["n"], lv["W"], Bv, part, out[l:], st)
     bounds = tuple(out.cpu().tolist())
     if not all(math.isfinite(b) for b in bounds):
         raise ValueError(error)
     for l, b in enumerate(bounds):
         arr[l].reserved = int(math.ceil(1000.0 * b))
     return bounds
+
+
+def _select_hierarchy(eng: _Engine, setup: _ElasticSetup, method: str, amg: dict, vals, Bv: int, Bp: int, info: SolveInfo,
+                      bounds_error: Optional[str] = None):
+    """The hierarchy choice of every elastic solve and of `diffhe.modal`'s inner solves: -> (hier or None, bounds).  With
+    method "ell-jacobi", or a mesh too small for a second level, None and `info.path` "ell-pcg"; otherwise the Galerkin
+    operators of `vals` on the cached unit-E levels (`amg` gets its cycle defaults in place), `info.path` "ell-amgpcg"
+    and the hierarchy fields of `info`.  bounds_error: the smoother's row bounds are measured on every level
+    (`_measure_row_bounds`, which raises ValueError with this text) and `info.hierarchy` reads "unit+row-bounds"."""
+    hier, bounds = None, ()
+    if method != "ell-jacobi":
+        levels, stats = setup.levels()
+        if levels:
+            _cycle_defaults(amg, setup.dofs.n, Bp)
+            hier = eng.amg_setup(vals, Bv, bool(amg.get("fp32", 0)), levels)
+            info.hierarchy, info.hierarchy_levels, info.operator_complexity = "unit", stats[0], stats[1]
+            if bounds_error is not None:
+                bounds = _measure_row_bounds(eng, hier, Bv, bounds_error)
+                info.hierarchy = "unit+row-bounds"
+    info.path = "ell-amgpcg" if hier is not None else "ell-pcg"
+    return hier, bounds
 
 
 # ---------------------------------------------------------------------------------------------
@@ -288,15 +285,20 @@ class _ElasticCall:
 
 class _ElasticSolve:
     """One call's solve: forward() keeps what adjoint() needs -- the assembled operator, the hierarchy, the iterate -- and
-    this object is the adjoint state the custom ops hold until the end of backward."""
+    this object is the adjoint state the custom ops hold until the end of backward.  The ONE `forward` and the ONE
+    `adjoint` of the elastic family; a solver path subclasses this and overrides the hooks `_operator`, `_body_force`,
+    `_after_rhs`, `_coeff_grad` and the class attributes below, nothing else."""
+    Info = SolveInfo                        # the class of `solver.last_info` after a call of this path
+    bounds_error: Optional[str] = None      # set: the smoother's row bounds are measured per call; the ValueError's text
+    bounds: Tuple[float, ...] = ()          # what was measured, the fine level first
+    keep_lambda = False                     # the adjoint lambda stays in `lam` for what the op computes after `adjoint`
+    lam = None
 
-    def __init__(self, solver: "ElasticFESolver", setup: _ElasticSetup, call: _ElasticCall, tol: float, amg: dict):
+    def __init__(self, solver, setup: _ElasticSetup, call: _ElasticCall, tol: float, amg: dict):
         self.solver, self.setup, self.call, self.amg = solver, setup, call, amg
         self.plan = setup.plan
         self.eng = _Engine(setup.dofs, tol, solver.max_iter, solver.check_every, "gather", g=setup.dofs.g)
         self.node_eng = _Engine(self.plan, tol, solver.max_iter, solver.check_every, "gather")
-        # a call whose nodes need grad (diffhe.elastic_shape) also keeps E and f as the kernels read them, and lambda
-        self.shape, self.e_s, self.f_dofs, self.lam = False, None, None, None
 
     # -- layout -----------------------------------------------------------------------------------
     def _to_dofs(self, t: torch.Tensor, batched: bool, zero_fixed: bool = False) -> torch.Tensor:
@@ -336,39 +338,55 @@ class _ElasticSolve:
         yc = torch.stack([self.node_eng.load_vector(xc[a], None, 1, Bp, free_rows=False) for a in range(d)])
         return yc.permute(1, 0, 2).reshape(plan.n * d, Bp).contiguous()
 
+    # -- hooks ------------------------------------------------------------------------------------
+    def _operator(self, E: torch.Tensor):
+        """-> (vals (d W, n d, Bv), lift (n d, Bv), Bv) of the call's coefficient: here the modulus as the kernels read it
+        and the block row-gather assembly of csrc/elastic.hip."""
+        kdev, kse, ksb, Bv = self.node_eng.kappa_device(E, self.call.mode, self.call.B, self.Bp, em=self.call.kappa_em)
+        return (*self.setup.assemble(kdev, kse, ksb, Bv), Bv)
+
+    def _body_force(self, f: torch.Tensor) -> torch.Tensor:
+        """f as the dof vector (n d, Bp) the load map reads."""
+        return self._to_dofs(f, self.call.f_batched)
+
+    def _after_rhs(self, vals: torch.Tensor, rhs: torch.Tensor, Bv: int) -> None:
+        """What a path adds to the stored operator and the finished right-hand side, in place: nothing here."""
+
+    def _coeff_grad(self, lam: torch.Tensor) -> torch.Tensor:
+        """dL/dE in the shape of E from the adjoint lambda and the saved iterate (`diffhe_elast_grad*`)."""
+        call, setup, plan, B, Bp = self.call, self.setup, self.plan, self.call.B, self.Bp
+        L, st = self.eng.L, _stream(plan.device)
+        gtab, vol = plan.gradient_table()
+        args = (plan.elems, gtab, vol, plan.dim, setup.lam1, setup.mu1, lam, self.x, setup.dofs.g, plan.n, plan.m)
+        sums, de = self.node_eng.element_grad(
+            call.mode, call.kappa_em, B, Bp, None,
+            lambda de_e, osc, ose, part, total: L.diffhe_elast_grad(*args, Bp, de_e, part, total, st),
+            lambda de, osc, ose: L.diffhe_elast_grad_shared(*args, B, Bp, de, st))
+        return _kappa_grad(call.mode, call.e_shape, sums, de)
+
     # -- forward ----------------------------------------------------------------------------------
     def forward(self, call_in, info: SolveInfo) -> torch.Tensor:
-        E, f, load = call_in.E, call_in.f, call_in.load
-        solver, setup, plan, call, eng = self.solver, self.setup, self.plan, self.call, self.eng
+        f, load = call_in.f, call_in.load
+        setup, call, eng = self.setup, self.call, self.eng
         dofs, B = setup.dofs, call.B
         Bp = self.Bp = padded_batch(B)
-        kdev, kse, ksb, Bv = self.node_eng.kappa_device(E, call.mode, B, Bp, em=call.kappa_em)
-        vals, lift = setup.assemble(kdev, kse, ksb, Bv)
-        if self.shape:
-            self.e_s = (kdev, kse, ksb)
+        vals, lift, Bv = self._operator(call_in.E)
         rhs = -lift if Bv == Bp else (-lift).expand(dofs.n, Bp).contiguous()
         if f is not None:
-            f_dofs = self._to_dofs(f, call.f_batched)
-            rhs += self._apply_load_map(f_dofs)
-            if self.shape:
-                self.f_dofs = f_dofs
+            rhs += self._apply_load_map(self._body_force(f))
         if load is not None:
             rhs += self._to_dofs(load, call.load_batched)
         rhs[dofs.is_bc.bool()] = 0.0
         if Bp > B:
             rhs[:, B:] = 0.0
-        self.hier = None
-        if solver.method != "ell-jacobi":
-            levels, stats = setup.levels()
-            if levels:
-                amg = _cycle_defaults(self.amg, dofs.n, Bp)
-                self.hier = eng.amg_setup(vals, Bv, bool(amg.get("fp32", 0)), levels)
-                info.hierarchy, info.hierarchy_levels, info.operator_complexity = "unit", stats[0], stats[1]
+        self._after_rhs(vals, rhs, Bv)
+        self.hier, self.bounds = _select_hierarchy(eng, setup, self.solver.method, self.amg, vals, Bv, Bp, info,
+                                                   self.bounds_error)
+        if self.bounds_error is not None:
+            info.jacobi_bounds = self.bounds
         if self.hier is not None:
-            info.path = "ell-amgpcg"
             x, its, bad, relres, *_ = eng.amg_pcg(self.hier, rhs, Bp, Bv, self.amg)
         else:
-            info.path = "ell-pcg"
             x, its, bad, relres, *_ = eng.cg(vals, rhs, Bp, Bv)
         info.iterations, info.not_converged = its, bad
         info.max_relres = float(relres[:B].max())
@@ -376,11 +394,10 @@ class _ElasticSolve:
         return self._from_dofs(x, dofs.g if (setup.has_data or not call.node_major) else None)
 
     # -- adjoint ----------------------------------------------------------------------------------
-    def adjoint(self, gbar: torch.Tensor, need_e: bool, need_f: bool, need_load: bool):
-        """lambda = A^-1 gbar on the free dofs with the forward's operator and hierarchy, then dL/dE in the shape of E,
-        dL/df = M lambda and dL/dload = lambda in the caller's layout."""
-        call, setup, plan, eng, B, Bp = self.call, self.setup, self.plan, self.eng, self.call.B, self.Bp
-        L, st = eng.L, _stream(plan.device)
+    def adjoint(self, gbar: torch.Tensor, need_coeff: bool, need_f: bool, need_load: bool):
+        """lambda = A^-1 gbar on the free dofs with the forward's operator, hierarchy and bounds, then the coefficient's
+        gradient in its own shape (`_coeff_grad`), dL/df = M lambda and dL/dload = lambda in the caller's layout."""
+        call, eng, B, Bp = self.call, self.eng, self.call.B, self.Bp
         info = self.solver.last_info
         rhs = self._to_dofs(gbar, True, zero_fixed=True)
         if self.hier is not None:
@@ -388,20 +405,13 @@ class _ElasticSolve:
         else:
             res = eng.cg(self.vals, rhs, Bp, self.Bv)
         lam = res.x
-        if self.shape:
+        if self.keep_lambda:
             self.lam = lam
         info.adj_iterations, info.adj_max_relres = res.iterations, float(res.relres[:B].max())
         info.not_converged += res.not_converged
-        grad_e = grad_f = grad_load = None
-        if need_e:
-            gtab, vol = plan.gradient_table()
-            args = (plan.elems, gtab, vol, plan.dim, setup.lam1, setup.mu1, lam, self.x, setup.dofs.g, plan.n, plan.m)
-            sums, de = self.node_eng.element_grad(
-                call.mode, call.kappa_em, B, Bp, None,
-                lambda de_e, osc, ose, part, total: L.diffhe_elast_grad(*args, Bp, de_e, part, total, st),
-                lambda de, osc, ose: L.diffhe_elast_grad_shared(*args, B, Bp, de, st))
-            grad_e = _kappa_grad(call.mode, call.e_shape, sums, de)
-            grad_e = grad_e.to(call.e_device)
+        grad_c = grad_f = grad_load = None
+        if need_coeff:
+            grad_c = self._coeff_grad(lam).to(call.e_device)
         if need_f:
             df = self._from_dofs(self._apply_load_map(lam))
             grad_f = (df if call.f_batched else df.sum(dim=0)).to(call.out_device)
@@ -409,7 +419,7 @@ class _ElasticSolve:
             dl = self._from_dofs(lam)
             dl = dl.clone() if call.node_major else dl
             grad_load = (dl if call.load_batched else dl.sum(dim=0)).to(call.out_device)
-        return grad_e, grad_f, grad_load
+        return grad_c, grad_f, grad_load
 
 
 @dataclass
@@ -435,52 +445,100 @@ def _batch_of(solver, f: torch.Tensor, load: torch.Tensor, node_major: bool):
     return B, fb, lb
 
 
-def _elastic_forward(solver: "ElasticFESolver", E, f, load, node_major, shape: bool = False):
-    """(u, state) of one call.  shape: the state also keeps what the node-gradient kernel reads (diffhe.elastic_shape)."""
+def _solve_call(solver, State, coeff, f, load, node_major: bool, layout=_kappa_layout, hierarchy=None, prepare=None):
+    """(u, state) of one call of any elastic solver: the ONE call builder.  State: the `_ElasticSolve` class of the path;
+    coeff: E or C; layout(coeff, m, B_rhs, node_major) -> (mode, B, element-major): `_kappa_layout` or the tensor's;
+    hierarchy: (nu, plane) of the unit operator whose cached hierarchy the call uses, None: the solver's own;
+    prepare(state): what a path sets on the state before the solve (diffhe.elastic_facets)."""
     plan = solver._plan()
-    setup = _setup_of(plan, solver.nu, solver.plane, solver._lam1, solver._mu1, solver._is_bc, solver._g)
+    nu, plane = hierarchy or (solver.nu, solver.plane)
+    setup = _setup_of(plan, nu, plane, *lame_unit(nu, plan.dim, plane), solver._is_bc, solver._g)
     B_rhs, fb, lb = _batch_of(solver, f, load, node_major)
-    mode, B, em = _kappa_layout(E, plan.m, B_rhs, node_major)
+    mode, B, em = layout(coeff, plan.m, B_rhs, node_major)
     src = f if f.numel() else load
-    call = _ElasticCall(B, mode, em, B_rhs is not None, node_major, src.device if src.numel() else E.device, E.shape,
-                        E.device, fb, lb)
+    call = _ElasticCall(B, mode, em, B_rhs is not None, node_major, src.device if src.numel() else coeff.device,
+                        coeff.shape, coeff.device, fb, lb)
     tol, _, amg = _call_options(chain=False, lattice=False, closed_boundary=False, n=setup.dofs.n, mode=mode,
                                 tol_user=solver._tol_user, mg_user=set(), mg={}, amg=solver.amg)
     solver.tol = tol
-    state = _ElasticSolve(solver, setup, call, tol, amg)
-    state.shape = shape
-    u = _run_call(state, _Inputs(E, f if f.numel() else None, load if load.numel() else None, B, call.batched,
+    state = State(solver, setup, call, tol, amg)
+    if prepare is not None:
+        prepare(state)
+    u = _run_call(state, _Inputs(coeff, f if f.numel() else None, load if load.numel() else None, B, call.batched,
                                  node_major, call.out_device))
     return u, state
 
 
-def _out_shape(solver, E, f, load, node_major):
+def _out_shape(solver, coeff, f, load, node_major, nc: int = 0):
+    """The shape of u; nc: the components of a tensor coefficient, 0 for E."""
     n, d, m = solver.mesh.n_nodes, solver.mesh.dim, solver.mesh.n_elements
     B_rhs, _, _ = _batch_of(solver, f, load, node_major)
     if node_major:
         return (n, d, B_rhs)
-    _, B, _ = _kappa_layout(E, m, B_rhs, False)
+    _, B, _ = _kappa_layout(coeff, m, B_rhs, False, nc)
     return (B, n, d) if (B_rhs is not None or B > 1) else (n, d)
 
 
 # ---------------------------------------------------------------------------------------------
-# torch.library custom ops diffhe::elastic_solve / diffhe::elastic_solve_backward; the solver and the state of the call
-# travel as integer handles through the registries of diffhe.solver.  f / load: empty tensor = absent.
+# What the four solve ops share (diffhe::elastic_solve here, elastic_solve_shape, elastic_aniso_solve, elastic_facet_solve
+# in their modules).  The solver and the state of the call travel as integer handles through the registries of
+# diffhe.solver; f / load: empty tensor = absent.  torch.library needs every op's explicit signature: the `def`s stay.
 # ---------------------------------------------------------------------------------------------
+def _solve_result(u: torch.Tensor, state: _ElasticSolve, save: bool):
+    """What a forward op returns: u (a copy where it is a view, or the saved iterate itself) and the state's token."""
+    return u.clone() if u._base is not None or u.data_ptr() == state.x.data_ptr() else u, _register_state(state, save)
+
+
+def _solve_fake(solver, coeff, f, load, node_major, nc: int = 0):
+    """(u, token) of a forward op's fake (meta) implementation."""
+    like = f if f.numel() else (load if load.numel() else coeff)
+    return (like.new_empty(_out_shape(solver, coeff, f, load, node_major, nc), dtype=torch.float64),
+            torch.empty((), dtype=torch.int64))
+
+
+def _run_adjoint(gbar: torch.Tensor, token: torch.Tensor, need_coeff: bool, need_f: bool, need_load: bool):
+    """(state, (dL/dcoeff, dL/df, dL/dload)) of the call named by `token`: the ONE adjoint solve, for the cotangent of u
+    as autograd hands it over (an unbatched call's gets its batch axis)."""
+    state = _state_of(token)
+    call = state.call
+    g = gbar.detach()
+    if not call.node_major and not call.batched and call.B == 1:
+        g = g.unsqueeze(0)
+    return state, state.adjoint(g, need_coeff, need_f, need_load)
+
+
+def _solve_autograd(op: str, n_diff: int, n_in: int, refusal: str):
+    """Register and return (setup_context, backward) of the solve op `op`, whose `n_in` inputs begin with `n_diff`
+    differentiable tensors and whose backward op diffhe::<op>_backward takes (gbar, token, *needs, *those tensors).
+    refusal: the text of the create_graph=True error."""
+    def setup_context(ctx, inputs, output):
+        _tie_state(ctx, output[1], *inputs[:n_diff])
+
+    def backward(ctx, grad_u, _grad_token):
+        if torch.is_grad_enabled():
+            raise NotImplementedError(refusal)
+        token, *tensors = ctx.saved_tensors[:n_diff + 1]
+        needs = tuple(bool(v) for v in ctx.needs_input_grad[:n_diff])
+        if not any(needs):
+            return (None,) * n_in
+        grads = getattr(torch.ops.diffhe, op + "_backward")(grad_u.contiguous(), token, *needs, *tensors)
+        return (*(g if need else None for g, need in zip(grads, needs)), *(None,) * (n_in - n_diff))
+
+    torch.library.register_autograd("diffhe::" + op, backward, setup_context=setup_context)
+    return setup_context, backward
+
+
 @torch.library.custom_op("diffhe::elastic_solve", mutates_args=())
 def elastic_solve(E: torch.Tensor, f: torch.Tensor, load: torch.Tensor, handle: int, save: bool,
                   node_major: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     """(u, token) of the `ElasticFESolver` registered under `handle`; `token` names the saved adjoint state (0 when
     `save` is false)."""
-    u, state = _elastic_forward(_SOLVERS[handle], E, f, load, node_major)
-    return u.clone() if u._base is not None or u.data_ptr() == state.x.data_ptr() else u, _register_state(state, save)
+    return _solve_result(*_solve_call(_SOLVERS[handle], _ElasticSolve, E, f, load, node_major), save)
 
 
 @elastic_solve.register_fake
 def _elastic_solve_fake(E, f, load, handle, save, node_major):
-    shape = _out_shape(_SOLVERS[handle], E, f, load, node_major)
-    like = f if f.numel() else (load if load.numel() else E)
-    return like.new_empty(shape, dtype=torch.float64), torch.empty((), dtype=torch.int64)
+    return _solve_fake(_SOLVERS[handle], E, f, load, node_major)
 
 
 @torch.library.custom_op("diffhe::elastic_solve_backward", mutates_args=())
@@ -488,12 +546,7 @@ def elastic_solve_backward(gbar: torch.Tensor, token: torch.Tensor, need_e: bool
                            e_like: torch.Tensor, f_like: torch.Tensor,
                            load_like: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(dL/dE, dL/df, dL/dload) of the forward call named by `token` from ONE adjoint solve; unused ones come back empty."""
-    state = _state_of(token)
-    call = state.call
-    g = gbar.detach()
-    if not call.node_major and not call.batched and call.B == 1:
-        g = g.unsqueeze(0)
-    grads = state.adjoint(g, need_e, need_f, need_load)
+    _, grads = _run_adjoint(gbar, token, need_e, need_f, need_load)
     return _like_grads(gbar, grads, (e_like, f_like, load_like))
 
 
@@ -502,603 +555,59 @@ def _elastic_solve_backward_fake(gbar, token, need_e, need_f, need_load, e_like,
     return _fake_grads(gbar, (need_e, need_f, need_load), (e_like, f_like, load_like))
 
 
-def _setup_context(ctx, inputs, output):
-    E, f, load = inputs[:3]
-    _tie_state(ctx, output[1], E, f, load)
-
-
-def _backward(ctx, grad_u, _grad_token):
-    if torch.is_grad_enabled():
-        raise NotImplementedError("diffhe: second-order derivatives of an elastic solve are not implemented (backward "
-                                  "with create_graph=True, diffhe.elastic)")
-    token, E, f, load = ctx.saved_tensors[:4]
-    needs = tuple(bool(v) for v in ctx.needs_input_grad[:3])
-    if not any(needs):
-        return (None,) * 6
-    ge, gf, gl = torch.ops.diffhe.elastic_solve_backward(grad_u.contiguous(), token, *needs, E, f, load)
-    return (ge if needs[0] else None, gf if needs[1] else None, gl if needs[2] else None, None, None, None)
-
-
-torch.library.register_autograd("diffhe::elastic_solve", _backward, setup_context=_setup_context)
+_setup_context, _backward = _solve_autograd(
+    "elastic_solve", 3, 6, "diffhe: second-order derivatives of an elastic solve are not implemented (backward with "
+    "create_graph=True, diffhe.elastic)")
 
 
 # ---------------------------------------------------------------------------------------------
-# Stress recovery: diffhe::elastic_stress / diffhe::elastic_stress_backward (csrc/stress.hip, include/diffhe_stress.h).
-# A pure function of (u, E) for the solver registered under `handle`: no adjoint state, backward recomputes from u and E.
+# The public solvers: what `ElasticFESolver`, `AnisotropicElasticFESolver` (not an `ElasticFESolver`), through the former
+# `TractionElasticFESolver` and `ShapeElasticFESolver`, and where it applies `ElasticEigenSolver` share of construction
+# and argument checking.  Where the classes word a message differently the wording is a parameter.
 # ---------------------------------------------------------------------------------------------
-@dataclass
-class _StressCall:
-    """One evaluation: the device views the kernels read and the facts both directions share."""
-    plan: object
-    eng: _Engine
-    B: int
-    Bp: int
-    mode: int
-    em: bool
-    batched: bool           # u came with a batch dimension
-    node_major: bool
-    head: tuple             # the leading arguments of the three entries, up to e_sb
-    nc: int
-
-    def rows_in(self, t: torch.Tensor, rows: int, batched: bool) -> torch.Tensor:
-        """(B, rows...) | (rows...) broadcast to the batch | node-major (rows..., B) -> (rows, Bp), padding samples zero."""
-        B, Bp, dev = self.B, self.Bp, self.plan.device
-        t = t.detach().to(dev, torch.float64)
-        if self.node_major:
-            src = t.reshape(rows, B)
-            if Bp == B and src.is_contiguous():
-                return src
-            out = torch.zeros((rows, Bp), dtype=torch.float64, device=dev)
-            out[:, :B] = src
-            return out
-        src = t.reshape(B, rows).contiguous() if batched else t.reshape(rows).contiguous()
-        return self.eng.to_node_major(src, B, Bp, rows)
-
-    def rows_out(self, x: torch.Tensor, rows: int) -> torch.Tensor:
-        """(rows, Bp) -> (B, rows), or node-major (rows, B): the kernel's array itself when B needs no padding."""
-        if self.node_major:
-            return x if self.Bp == self.B else x[:, :self.B].contiguous()
-        return self.eng.to_sample_major(x, self.B, self.Bp, rows)
-
-
-def _stress_batch(u: torch.Tensor, node_major: bool) -> Optional[int]:
-    return u.shape[2] if node_major else (u.shape[0] if u.dim() == 3 else None)
-
-
-def _stress_shapes(solver, u, E, node_major):
-    """-> (shape of sigma, shape of vm) for u and E as the op gets them."""
-    m, d = solver.mesh.n_elements, solver.mesh.dim
-    nc = d * (d + 1) // 2
-    B_u = _stress_batch(u, node_major)
-    _, B, _ = _kappa_layout(E, m, B_u, node_major)
-    if node_major:
-        return (m, nc, B), (m, B)
-    return ((B, m, nc), (B, m)) if (B_u is not None or B > 1) else ((m, nc), (m,))
-
-
-def _stress_call(solver: "ElasticFESolver", u, E, node_major) -> _StressCall:
-    plan = solver._plan()
-    d, n, m = plan.dim, plan.n, plan.m
-    B_u = _stress_batch(u, node_major)
-    mode, B, em = _kappa_layout(E, m, B_u, node_major)
-    Bp = padded_batch(B)
-    eng = _Engine(plan, 0.0, 0, 0, "gather")
-    call = _StressCall(plan, eng, B, Bp, mode, em, B_u is not None, node_major, (), d * (d + 1) // 2)
-    udev = call.rows_in(u, n * d, call.batched)
-    kdev, kse, ksb, _ = eng.kappa_device(E, mode, B, Bp, em=em)
-    gtab = plan.oriented_gradient_table()                        # the stress is linear in grad phi: its sign counts
-    nu_z = solver.nu if solver.plane == "strain" else 0.0       # sigma_zz = nu_z (sigma_xx + sigma_yy), 2D only
-    call.head = (plan.elems, gtab, d, solver._lam1, solver._mu1, nu_z, udev, kdev, kse, ksb)
-    return call
-
-
-def _stress_forward(solver, u, E, node_major, want_sigma, want_vm):
-    """(sigma, vm) in the caller's layout, None for the one not asked for: the kernel writes (m, nc, Bp) and (m, Bp)."""
-    call = _stress_call(solver, u, E, node_major)
-    plan, m, nc, B, Bp = call.plan, call.plan.m, call.nc, call.B, call.Bp
-    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=plan.device)  # noqa: E731
-    sigma, vm = (new(m * nc, Bp) if want_sigma else None), (new(m, Bp) if want_vm else None)
-    _hip.lib().diffhe_stress_eval(*call.head, plan.n, m, Bp, sigma, Bp, nc * Bp, vm, _stream(plan.device))
-    s_shape, v_shape = _stress_shapes(solver, u, E, node_major)
-    if sigma is not None:
-        sigma = call.rows_out(sigma, m * nc).reshape(s_shape).to(u.device)
-    if vm is not None:
-        vm = call.rows_out(vm, m).reshape(v_shape).to(u.device)
-    return sigma, vm
-
-
-def _stress_adjoint(solver, sigma_bar, vm_bar, u, E, node_major, need_u, need_e):
-    """(dL/du, dL/dE) in the shapes of u and E, None for the one not asked for.  One element pass feeds both where the
-    dE of the call is per sample; a field the batch shares takes its dE from the batch-summing entry."""
-    call = _stress_call(solver, u, E, node_major)
-    plan, eng, nc, B, Bp, mode = call.plan, call.eng, call.nc, call.B, call.Bp, call.mode
-    d, n, m = plan.dim, plan.n, plan.m
-    L, st = _hip.lib(), _stream(plan.device)
-    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=plan.device)  # noqa: E731
-    sb = call.rows_in(sigma_bar, m * nc, True) if sigma_bar is not None else None
-    vb = call.rows_in(vm_bar, m, True) if vm_bar is not None else None
-    head = (*call.head, sb, Bp, nc * Bp, vb)
-    ubar = new(n * d, Bp) if need_u else None
-
-    def adjoint(nodes, de_e, part, total):
-        lists = plan.shape_incidence() if nodes else (None, None)
-        L.diffhe_stress_adjoint(*head, *lists, n, m, B, Bp, new(nc, m, Bp) if nodes else None, ubar if nodes else None,
-                                de_e, part, total, st)
-
-    grad_u = grad_e = None
-    fused = need_u and need_e and mode != K_ELEM
-    if need_e:
-        sums, de = eng.element_grad(mode, call.em, B, Bp, None,
-                                    lambda de_e, osc, ose, part, total: adjoint(fused, de_e, part, total),
-                                    lambda de, osc, ose: L.diffhe_stress_adjoint_shared(*head, n, m, B, Bp, de, st))
-        grad_e = _kappa_grad(mode, E.shape, sums, de).to(E.device)
-    if need_u:
-        if not fused:
-            adjoint(True, None, None, None)
-        du = call.rows_out(ubar, n * d)
-        if node_major:
-            grad_u = du.reshape(n, d, B)
-        else:
-            du = du.reshape(B, n, d)
-            grad_u = du if call.batched else du.sum(dim=0)
-        grad_u = grad_u.to(u.device)
-    return grad_u, grad_e
-
-
-@torch.library.custom_op("diffhe::elastic_stress", mutates_args=())
-def elastic_stress(u: torch.Tensor, E: torch.Tensor, handle: int, node_major: bool, want_sigma: bool,
-                   want_vm: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(sigma, vm) of the displacement u and the modulus E for the `ElasticFESolver` registered under `handle`; the
-    output not asked for comes back empty."""
-    sigma, vm = _stress_forward(_SOLVERS[handle], u, E, node_major, want_sigma, want_vm)
-    return (u.new_empty(0) if sigma is None else sigma), (u.new_empty(0) if vm is None else vm)
-
-
-@elastic_stress.register_fake
-def _elastic_stress_fake(u, E, handle, node_major, want_sigma, want_vm):
-    s_shape, v_shape = _stress_shapes(_SOLVERS[handle], u, E, node_major)
-    return (u.new_empty(s_shape if want_sigma else 0, dtype=torch.float64),
-            u.new_empty(v_shape if want_vm else 0, dtype=torch.float64))
-
-
-@torch.library.custom_op("diffhe::elastic_stress_backward", mutates_args=())
-def elastic_stress_backward(sigma_bar: torch.Tensor, vm_bar: torch.Tensor, u: torch.Tensor, E: torch.Tensor, handle: int,
-                            node_major: bool, need_u: bool, need_e: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(dL/du, dL/dE) of `elastic_stress` for the cotangents of sigma and vm (empty = absent); unused ones come back
-    empty."""
-    grads = _stress_adjoint(_SOLVERS[handle], sigma_bar if sigma_bar.numel() else None,
-                            vm_bar if vm_bar.numel() else None, u, E, node_major, need_u, need_e)
-    return _like_grads(u, grads, (u, E))
-
-
-@elastic_stress_backward.register_fake
-def _elastic_stress_backward_fake(sigma_bar, vm_bar, u, E, handle, node_major, need_u, need_e):
-    return _fake_grads(u, (need_u, need_e), (u, E))
-
-
-def _stress_setup_context(ctx, inputs, output):
-    u, E, handle, node_major = inputs[:4]
-    ctx.handle, ctx.node_major = handle, bool(node_major)
-    ctx.set_materialize_grads(False)
-    ctx.save_for_backward(u, E)
-
-
-def _stress_backward(ctx, grad_sigma, grad_vm):
-    if torch.is_grad_enabled():
-        raise NotImplementedError("diffhe: second-order derivatives of an elastic stress evaluation are not implemented "
-                                  "(backward with create_graph=True, diffhe.elastic)")
-    u, E = ctx.saved_tensors
-    need_u, need_e = (bool(v) for v in ctx.needs_input_grad[:2])
-    absent = lambda g: g is None or g.numel() == 0  # noqa: E731
-    if not (need_u or need_e) or (absent(grad_sigma) and absent(grad_vm)):
-        return (None,) * 6
-    empty = u.new_empty(0)
-    du, de = torch.ops.diffhe.elastic_stress_backward(empty if absent(grad_sigma) else grad_sigma.contiguous(),
-                                                      empty if absent(grad_vm) else grad_vm.contiguous(), u, E,
-                                                      ctx.handle, ctx.node_major, need_u, need_e)
-    return (du if need_u else None, de if need_e else None, None, None, None, None)
-
-
-torch.library.register_autograd("diffhe::elastic_stress", _stress_backward, setup_context=_stress_setup_context)
-
-
-# ---------------------------------------------------------------------------------------------
-# Eigenstrain (csrc/eigenstrain.hip and the eigen instantiations of csrc/stress.hip, include/diffhe_eigenstrain.h):
-# diffhe::eigenstrain_load / eigenstrain_load_backward, the load F0(eps0, E), and diffhe::elastic_stress_eigen /
-# elastic_stress_eigen_backward, the stress E (s(u) - s0).  Pure functions of their tensors for the solver registered under
-# `handle`: backward recomputes from the saved inputs.
-# ---------------------------------------------------------------------------------------------
-def eigen_components(dim: int, plane: Optional[str]) -> int:
-    """nc0: 6 in 3D, 4 in plane strain (xx, yy, xy, zz), 3 in plane stress."""
-    return 6 if dim == 3 else (4 if plane == "strain" else 3)
-
-
-def _eigen_batch(eps0, E, m: int, nc0: int, node_major: bool, B_hint: Optional[int]) -> Optional[int]:
-    """The batch of one call: the hint (the batch of f, load or u), else that of whichever of eps0 and E shows one, the
-    shapes that read only one way first; None: nothing is batched.  The shapes that read both ways -- (m, nc0) and (m,)
-    with m equal to the batch -- are then classified WITH that batch, by the tie rule of `_kappa_layout`."""
-    if B_hint is not None:
-        return B_hint
-    if eps0.dim() == 3:
-        return eps0.shape[2] if (node_major and tuple(eps0.shape[:2]) == (nc0, m)) else eps0.shape[0]
-    if E.dim() == 2:
-        return E.shape[1] if (node_major and E.shape[0] == m) else E.shape[0]
-    _, B_z, _ = _tensor_mode(eps0, nc0, m, None, node_major)
-    return B_z if B_z is not None else _kappa_mode(E, m, None)[1]
-
-
-@dataclass
-class _EigenCall(_StressCall):
-    """`_StressCall` (mode, em: those of E) with the eigenstrain of the call."""
-    mode_z: int = 0
-    em_z: bool = False
-    nc0: int = 0
-    zhead: tuple = ()       # lam1, mu1, plane_strain, E and its strides, eps0 and its strides
-
-    def eps0_out(self):
-        """(array, stride per component, per element) of the kernels' d / d eps0: (m, nc0, Bp) where the caller's
-        (B, m, nc0) is one transposing pass away, else (nc0, m, Bp)."""
-        m, nc0, Bp = self.plan.m, self.nc0, self.Bp
-        if self.mode_z == K_SAMPLE_ELEM and not self.em_z:
-            return torch.empty((m, nc0, Bp), dtype=torch.float64, device=self.plan.device), Bp, nc0 * Bp
-        return torch.empty((nc0, m, Bp), dtype=torch.float64, device=self.plan.device), m * Bp, Bp
-
-    def eps0_grad(self, d: torch.Tensor, shape) -> torch.Tensor:
-        """That array in the shape of the caller's eps0.  A tensor shared over elements or samples is a torch `sum` of the
-        contiguous (nc0, m, Bp) array (padding samples hold zeros) over the shared axes: a reduction whose order torch
-        decides, like the batch sum of an unbatched u's gradient and autograd's sum over a broadcast load (DESIGN
-        section 7, "Eigenstrain")."""
-        m, nc0, B, Bp = self.plan.m, self.nc0, self.B, self.Bp
-        if self.mode_z == K_SAMPLE_ELEM:
-            if self.em_z:
-                return (d if Bp == B else d[..., :B].contiguous()).reshape(shape)
-            return self.eng.to_sample_major(d.view(m * nc0, Bp), B, Bp, m * nc0).reshape(shape)
-        if self.mode_z == K_ELEM:
-            return d.sum(dim=2).t().reshape(shape)
-        if self.mode_z == K_SAMPLE:
-            return d.sum(dim=1)[:, :B].t().reshape(shape)
-        return d.sum(dim=(1, 2)).reshape(shape)
-
-
-def _eigen_call(solver: "ElasticFESolver", eps0, E, node_major: bool, B_hint: Optional[int], collapse: bool,
-                u=None) -> _EigenCall:
-    """The device views and facts of one eigenstrain call.  collapse: with neither eps0 nor E batched the call is one
-    sample whatever the hint says (a load every sample shares)."""
-    plan = solver._plan()
-    d, n, m = plan.dim, plan.n, plan.m
-    nc0 = eigen_components(d, solver.plane)
-    B0 = _eigen_batch(eps0, E, m, nc0, node_major, B_hint)
-    mode_z, B, em_z = _kappa_layout(eps0, m, B0, node_major, nc0)
-    mode, B_e, em = _kappa_layout(E, m, B0, node_major)
-    if B_e != B:
-        raise ValueError(f"E batch {B_e} does not match eigenstrain batch {B}")
-    batched = B0 is not None
-    if collapse and mode_z in (K_SCALAR, K_ELEM) and mode in (K_SCALAR, K_ELEM):
-        B, batched = 1, False
-    Bp = padded_batch(B)
-    eng = _Engine(plan, 0.0, 0, 0, "gather")
-    call = _EigenCall(plan, eng, B, Bp, mode, em, batched, node_major, (), d * (d + 1) // 2, mode_z, em_z, nc0)
-    kdev, kse, ksb, _ = eng.kappa_device(E, mode, B, Bp, em=em)
-    zdev, zc, ze, zb, _ = eng.tensor_device(eps0, mode_z, B, Bp, nc0, em=em_z)
-    call.zhead = (solver._lam1, solver._mu1, int(solver.plane == "strain"), kdev, kse, ksb, zdev, zc, ze, zb)
-    if u is not None:
-        udev = call.rows_in(u, n * d, u.dim() == 3)
-        call.head = (plan.elems, plan.oriented_gradient_table(), d, *call.zhead[:3], udev, *call.zhead[3:])
-    return call
-
-
-def _load_shape(call: _EigenCall):
-    n, d = call.plan.n, call.plan.dim
-    return (n, d, call.B) if call.node_major else ((call.B, n, d) if call.batched else (n, d))
-
-
-def _hint(B_hint: int) -> Optional[int]:
-    return None if B_hint < 0 else B_hint
-
-
-@torch.library.custom_op("diffhe::eigenstrain_load", mutates_args=())
-def eigenstrain_load_op(eps0: torch.Tensor, E: torch.Tensor, handle: int, node_major: bool, B_hint: int) -> torch.Tensor:
-    """F0 of the eigenstrain eps0 and the modulus E for the `ElasticFESolver` registered under `handle`; B_hint: the
-    batch of the right-hand side the load joins, -1 for none."""
-    call = _eigen_call(_SOLVERS[handle], eps0, E, node_major, _hint(B_hint), True)
-    plan = call.plan
-    F0 = torch.empty((plan.n * plan.dim, call.Bp), dtype=torch.float64, device=plan.device)
-    _, vol = plan.gradient_table()
-    _hip.lib().diffhe_eigenstrain_load(*plan.shape_incidence(), plan.oriented_gradient_table(), vol, plan.dim, *call.zhead,
-                                       plan.n, plan.m, call.B, call.Bp, F0, _stream(plan.device))
-    return call.rows_out(F0, plan.n * plan.dim).reshape(_load_shape(call)).to(eps0.device)
-
-
-@eigenstrain_load_op.register_fake
-def _eigenstrain_load_fake(eps0, E, handle, node_major, B_hint):
-    solver = _SOLVERS[handle]
-    n, d, m = solver.mesh.n_nodes, solver.mesh.dim, solver.mesh.n_elements
-    nc0 = eigen_components(d, solver.plane)
-    B0 = _eigen_batch(eps0, E, m, nc0, node_major, _hint(B_hint))
-    mode_z, B, _ = _kappa_layout(eps0, m, B0, node_major, nc0)
-    mode, _, _ = _kappa_layout(E, m, B0, node_major)
-    if mode_z in (K_SCALAR, K_ELEM) and mode in (K_SCALAR, K_ELEM):
-        B, B0 = 1, None
-    return eps0.new_empty((n, d, B) if node_major else ((B, n, d) if B0 is not None else (n, d)), dtype=torch.float64)
-
-
-@torch.library.custom_op("diffhe::eigenstrain_load_backward", mutates_args=())
-def eigenstrain_load_backward(gbar: torch.Tensor, eps0: torch.Tensor, E: torch.Tensor, handle: int, node_major: bool,
-                              B_hint: int, need_z: bool, need_e: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(dL/deps0, dL/dE) of `eigenstrain_load` for the cotangent of F0; unused ones come back empty."""
-    call = _eigen_call(_SOLVERS[handle], eps0, E, node_major, _hint(B_hint), True)
-    plan, B, Bp = call.plan, call.B, call.Bp
-    L, st = _hip.lib(), _stream(plan.device)
-    _, vol = plan.gradient_table()
-    w = call.rows_in(gbar, plan.n * plan.dim, call.batched)
-    head = (plan.elems, plan.oriented_gradient_table(), vol, plan.dim, *call.zhead, w, plan.n, plan.m, B, Bp)
-    deps, osc, ose = call.eps0_out() if need_z else (None, 0, 0)
-    grad_z = grad_e = None
-    fused = need_z and need_e and call.mode != K_ELEM           # one element pass for both
-    if need_e:
-        sums, de = call.eng.element_grad(
-            call.mode, call.em, B, Bp, None,
-            lambda de_e, _osc, _ose, part, total: L.diffhe_eigenstrain_load_adjoint(
-                *head, deps if fused else None, osc, ose, de_e, part, total, st),
-            lambda de, _osc, _ose: L.diffhe_eigenstrain_load_adjoint_shared(*head, de, st))
-        grad_e = _kappa_grad(call.mode, E.shape, sums, de).to(E.device)
-    if need_z:
-        if not fused:
-            L.diffhe_eigenstrain_load_adjoint(*head, deps, osc, ose, None, None, None, st)
-        grad_z = call.eps0_grad(deps, eps0.shape).to(eps0.device)
-    return _like_grads(gbar, (grad_z, grad_e), (eps0, E))
-
-
-@eigenstrain_load_backward.register_fake
-def _eigenstrain_load_backward_fake(gbar, eps0, E, handle, node_major, B_hint, need_z, need_e):
-    return _fake_grads(gbar, (need_z, need_e), (eps0, E))
-
-
-def _load_setup_context(ctx, inputs, output):
-    eps0, E, ctx.handle, node_major, ctx.B_hint = inputs
-    ctx.node_major = bool(node_major)
-    ctx.solver = _SOLVERS[ctx.handle]       # the registry holds it weakly: the graph keeps it alive for backward
-    ctx.save_for_backward(eps0, E)
-
-
-def _load_backward(ctx, grad_F):
-    if torch.is_grad_enabled():
-        raise NotImplementedError("diffhe: second-order derivatives of an eigenstrain load are not implemented (backward "
-                                  "with create_graph=True, diffhe.elastic)")
-    eps0, E = ctx.saved_tensors
-    need_z, need_e = (bool(v) for v in ctx.needs_input_grad[:2])
-    if not (need_z or need_e):
-        return (None,) * 5
-    _SOLVERS[ctx.handle] = ctx.solver
-    dz, de = torch.ops.diffhe.eigenstrain_load_backward(grad_F.contiguous(), eps0, E, ctx.handle, ctx.node_major,
-                                                        ctx.B_hint, need_z, need_e)
-    return (dz if need_z else None, de if need_e else None, None, None, None)
-
-
-torch.library.register_autograd("diffhe::eigenstrain_load", _load_backward, setup_context=_load_setup_context)
-
-
-def _stress_shapes_eigen(solver, u, E, eps0, node_major):
-    m, d = solver.mesh.n_elements, solver.mesh.dim
-    nc, nc0 = d * (d + 1) // 2, eigen_components(d, solver.plane)
-    B0 = _eigen_batch(eps0, E, m, nc0, node_major, _stress_batch(u, node_major))
-    _, B, _ = _kappa_layout(eps0, m, B0, node_major, nc0)
-    if node_major:
-        return (m, nc, B), (m, B)
-    return ((B, m, nc), (B, m)) if B0 is not None else ((m, nc), (m,))
-
-
-@torch.library.custom_op("diffhe::elastic_stress_eigen", mutates_args=())
-def elastic_stress_eigen(u: torch.Tensor, E: torch.Tensor, eps0: torch.Tensor, handle: int, node_major: bool,
-                         want_sigma: bool, want_vm: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(sigma, vm) of `elastic_stress` with the eigenstrain eps0: sigma = E (s(u) - s0)."""
-    solver = _SOLVERS[handle]
-    call = _eigen_call(solver, eps0, E, node_major, _stress_batch(u, node_major), False, u=u)
-    plan, m, nc, Bp = call.plan, call.plan.m, call.nc, call.Bp
-    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=plan.device)  # noqa: E731
-    sigma, vm = (new(m * nc, Bp) if want_sigma else None), (new(m, Bp) if want_vm else None)
-    _hip.lib().diffhe_stress_eval_eigen(*call.head, plan.n, m, Bp, sigma, Bp, nc * Bp, vm, _stream(plan.device))
-    s_shape, v_shape = _stress_shapes_eigen(solver, u, E, eps0, node_major)
-    sigma = u.new_empty(0) if sigma is None else call.rows_out(sigma, m * nc).reshape(s_shape).to(u.device)
-    vm = u.new_empty(0) if vm is None else call.rows_out(vm, m).reshape(v_shape).to(u.device)
-    return sigma, vm
-
-
-@elastic_stress_eigen.register_fake
-def _elastic_stress_eigen_fake(u, E, eps0, handle, node_major, want_sigma, want_vm):
-    s_shape, v_shape = _stress_shapes_eigen(_SOLVERS[handle], u, E, eps0, node_major)
-    return (u.new_empty(s_shape if want_sigma else 0, dtype=torch.float64),
-            u.new_empty(v_shape if want_vm else 0, dtype=torch.float64))
-
-
-@torch.library.custom_op("diffhe::elastic_stress_eigen_backward", mutates_args=())
-def elastic_stress_eigen_backward(sigma_bar: torch.Tensor, vm_bar: torch.Tensor, u: torch.Tensor, E: torch.Tensor,
-                                  eps0: torch.Tensor, handle: int, node_major: bool, need_u: bool, need_e: bool,
-                                  need_z: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """(dL/du, dL/dE, dL/deps0) of `elastic_stress_eigen` for the cotangents of sigma and vm (empty = absent); unused
-    ones come back empty.  One element pass feeds all three where the dE of the call is per sample."""
-    call = _eigen_call(_SOLVERS[handle], eps0, E, node_major, _stress_batch(u, node_major), False, u=u)
-    plan, eng, nc, B, Bp, mode = call.plan, call.eng, call.nc, call.B, call.Bp, call.mode
-    d, n, m = plan.dim, plan.n, plan.m
-    L, st = _hip.lib(), _stream(plan.device)
-    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=plan.device)  # noqa: E731
-    sb = call.rows_in(sigma_bar, m * nc, True) if sigma_bar.numel() else None
-    vb = call.rows_in(vm_bar, m, True) if vm_bar.numel() else None
-    head = (*call.head, sb, Bp, nc * Bp, vb)
-    ubar = new(n * d, Bp) if need_u else None
-    deps, dzc, dze = call.eps0_out() if need_z else (None, 0, 0)
-
-    def adjoint(side, de_e, part, total):
-        """The element pass (and the node pass) with the side products u_bar and d / d eps0, or with dE alone."""
-        nodes = side and need_u
-        lists = plan.shape_incidence() if nodes else (None, None)
-        L.diffhe_stress_adjoint_eigen(*head, *lists, n, m, B, Bp, new(nc, m, Bp) if nodes else None,
-                                      ubar if nodes else None, de_e, part, total, deps if side else None, dzc, dze, st)
-
-    grad_u = grad_e = grad_z = None
-    side = need_u or need_z
-    fused = side and need_e and mode != K_ELEM
-    if need_e:
-        sums, de = eng.element_grad(mode, call.em, B, Bp, None,
-                                    lambda de_e, osc, ose, part, total: adjoint(fused, de_e, part, total),
-                                    lambda de, osc, ose: L.diffhe_stress_adjoint_eigen_shared(*head, n, m, B, Bp, de, st))
-        grad_e = _kappa_grad(mode, E.shape, sums, de).to(E.device)
-    if side and not fused:
-        adjoint(True, None, None, None)
-    if need_u:
-        du = call.rows_out(ubar, n * d)
-        if node_major:
-            grad_u = du.reshape(n, d, B)
-        else:
-            du = du.reshape(B, n, d)
-            grad_u = du if u.dim() == 3 else du.sum(dim=0)
-        grad_u = grad_u.to(u.device)
-    if need_z:
-        grad_z = call.eps0_grad(deps, eps0.shape).to(eps0.device)
-    return _like_grads(u, (grad_u, grad_e, grad_z), (u, E, eps0))
-
-
-@elastic_stress_eigen_backward.register_fake
-def _elastic_stress_eigen_backward_fake(sigma_bar, vm_bar, u, E, eps0, handle, node_major, need_u, need_e, need_z):
-    return _fake_grads(u, (need_u, need_e, need_z), (u, E, eps0))
-
-
-def _stress_eigen_setup_context(ctx, inputs, output):
-    u, E, eps0, handle, node_major = inputs[:5]
-    ctx.handle, ctx.node_major = handle, bool(node_major)
-    ctx.solver = _SOLVERS[handle]           # the registry holds it weakly: the graph keeps it alive for backward
-    ctx.set_materialize_grads(False)
-    ctx.save_for_backward(u, E, eps0)
-
-
-def _stress_eigen_backward(ctx, grad_sigma, grad_vm):
-    if torch.is_grad_enabled():
-        raise NotImplementedError("diffhe: second-order derivatives of an elastic stress evaluation are not implemented "
-                                  "(backward with create_graph=True, diffhe.elastic)")
-    u, E, eps0 = ctx.saved_tensors
-    needs = tuple(bool(v) for v in ctx.needs_input_grad[:3])
-    absent = lambda g: g is None or g.numel() == 0  # noqa: E731
-    if not any(needs) or (absent(grad_sigma) and absent(grad_vm)):
-        return (None,) * 7
-    empty = u.new_empty(0)
-    _SOLVERS[ctx.handle] = ctx.solver
-    grads = torch.ops.diffhe.elastic_stress_eigen_backward(empty if absent(grad_sigma) else grad_sigma.contiguous(),
-                                                           empty if absent(grad_vm) else grad_vm.contiguous(), u, E, eps0,
-                                                           ctx.handle, ctx.node_major, *needs)
-    return (*(g if need else None for g, need in zip(grads, needs)), None, None, None, None)
-
-
-torch.library.register_autograd("diffhe::elastic_stress_eigen", _stress_eigen_backward,
-                                setup_context=_stress_eigen_setup_context)
-
-
-def thermal_strain(alpha, dT: torch.Tensor, dim: int, plane: Optional[str] = None) -> torch.Tensor:
-    """The isotropic eigenstrain eps0 = alpha dT on the normal components, shears zero: (m, nc0) or (B, m, nc0) for dT (m,)
-    or (B, m), nc0 = 6 in 3D, 3 in plane stress (the 2D default), 4 in plane strain (zz included: the expansion out of
-    the plane is constrained).  alpha: a number or a tensor that broadcasts against dT, e.g. per element (m,).  Plain
-    differentiable torch."""
-    if dim not in (2, 3):
-        raise ValueError(f"thermal_strain: dim must be 2 or 3, got {dim!r}")
-    if dim == 3 and plane is not None:
-        raise ValueError("plane= applies to 2D only")
-    plane = None if dim == 3 else ("stress" if plane is None else plane)
-    if dim == 2 and plane not in ("stress", "strain"):
-        raise ValueError(f"Unknown plane: {plane!r} (\"stress\" or \"strain\")")
-    if dT.dim() not in (1, 2):
-        raise ValueError(f"thermal_strain: dT must be (m,) or (B, m), got {tuple(dT.shape)}")
-    v = torch.as_tensor(alpha, dtype=dT.dtype, device=dT.device) * dT
-    zero = torch.zeros_like(v)
-    parts = {6: (v, v, v, zero, zero, zero), 4: (v, v, zero, v), 3: (v, v, zero)}[eigen_components(dim, plane)]
-    return torch.stack(parts, dim=-1)
-
-
-def element_mean(T: torch.Tensor, mesh) -> torch.Tensor:
-    """The mean of a nodal field (n,) or (B, n) over the vertices of every element: (m,) or (B, m).  Plain differentiable
-    torch; with `thermal_strain` it carries the temperature of a heat solve to an eigenstrain."""
-    if T.dim() not in (1, 2) or T.shape[-1] != mesh.n_nodes:
-        raise ValueError(f"element_mean: T must be (n,) or (B, n) with n={mesh.n_nodes}, got {tuple(T.shape)}")
-    return T[..., mesh.elements.to(T.device).long()].mean(dim=-1)
-
-
-def pnorm(vm: torch.Tensor, p: float = 8.0, weights: Optional[torch.Tensor] = None, dim: int = -1) -> torch.Tensor:
-    """The weighted p-mean (sum_e w_e vm_e^p / sum_e w_e)^(1/p) over the element axis `dim` of a non-negative field: the
-    last axis of `von_mises(..., layout="sample")`, the first (dim=0) of layout="node".  It lies between max(vm) m^(-1/p)
-    and max(vm).  Plain differentiable torch, evaluated as vmax (sum w (vm / vmax)^p / sum w)^(1/p) with vmax detached, so
-    that a large p neither overflows nor underflows; an all-zero row gives 0 with zero gradient."""
-    p = float(p)
-    if not p >= 1.0:
-        raise ValueError(f"pnorm needs p >= 1, got {p!r}")
-    if weights is None:
-        w = torch.ones((), dtype=vm.dtype, device=vm.device)
-        wsum = float(vm.shape[dim])
-    else:
-        w = torch.as_tensor(weights, dtype=vm.dtype, device=vm.device)
-        if w.dim() == 1 and vm.dim() > 1:
-            shape = [1] * vm.dim()
-            shape[dim] = w.shape[0]
-            w = w.reshape(shape)
-        wsum = w.sum(dim=dim if w.dim() == vm.dim() else -1)
-    vmax = vm.detach().abs().amax(dim=dim, keepdim=True)
-    live = vmax > 0
-    r = vm / torch.where(live, vmax, torch.ones_like(vmax))
-    s = (w * r ** p).sum(dim=dim) / wsum
-    live, vmax = live.squeeze(dim) & (s > 0), vmax.squeeze(dim)
-    root = torch.where(live, s, torch.ones_like(s)) ** (1.0 / p)
-    return torch.where(live, vmax * root, torch.zeros_like(root))
-
-
-class ElasticFESolver(nn.Module):
-    """Displacement of a linear-elastic body per sample, differentiable with respect to the Young's modulus E per element,
-    the body force f and the nodal load (see the module docstring).
-
-    Parameters
-    ----------
-    mesh : FEMesh -- P1 triangles or P1 tetrahedra.
-    E : float or tensor or Parameter -- (), (B,), (m,), (B, m); (m, B) with layout="node".  May require grad.
-    nu : float, -1 < nu < 0.5.  plane : "stress" (default) or "strain", 2D meshes only.
-    fixed : None (clamp the nodes of mesh.dirichlet_nodes) or {(node, component): value}.
-    device, tol, max_iter, method ("auto" or "ell-jacobi"), amg : as on `DifferentiableFESolver`.
-    """
-
-    def __init__(self, mesh, E=1.0, nu: float = 0.3, *, plane: Optional[str] = None, fixed=None, device=None,
-                 tol: Optional[float] = None, max_iter: int = 20000, method: str = "auto", amg: Optional[dict] = None,
-                 check_every: int = 25):
-        super().__init__()
-        if mesh.dim == 1:
-            raise NotImplementedError("diffhe: elasticity needs a 2D or 3D mesh (a 1D bar is the scalar problem of "
-                                      "DifferentiableFESolver with kappa = E A)")
-        if mesh.dim not in (2, 3):
-            raise NotImplementedError("Only 2D and 3D supported")
-        if mesh.elements.shape[1] != mesh.dim + 1:
-            raise NotImplementedError("diffhe: elasticity is implemented for P1 elements only (this mesh has "
-                                      f"{mesh.elements.shape[1]} nodes per element)")
-        if mesh.dim == 3 and plane is not None:
-            raise ValueError("plane= applies to 2D meshes only (a 3D body needs no plane-stress / plane-strain choice)")
-        self.plane = None if mesh.dim == 3 else ("stress" if plane is None else plane)
-        self.nu = float(nu)
-        self._lam1, self._mu1 = lame_unit(self.nu, mesh.dim, self.plane)
+def _check_mesh(mesh, one_d: str, p1: str, dims: str = "Only 2D and 3D supported") -> None:
+    """The mesh refusals (NotImplementedError): 1D (`one_d`), a dimension other than 2 and 3 (`dims`), elements other
+    than P1 (`p1`, formatted with k = nodes per element)."""
+    if mesh.dim == 1:
+        raise NotImplementedError(one_d)
+    if mesh.dim not in (2, 3):
+        raise NotImplementedError(dims)
+    if mesh.elements.shape[1] != mesh.dim + 1:
+        raise NotImplementedError(p1.format(k=mesh.elements.shape[1]))
+
+
+def _amg_options(amg: Optional[dict], strength: str,
+                 smoothed: str = "diffhe: elasticity builds a smoothed-aggregation hierarchy (amg smoothed=0 is not "
+                                 "implemented)") -> dict:
+    """The options of the general path's aggregation-multigrid PCG, as on DifferentiableFESolver, with the caller's `amg`
+    over the defaults and the two refusals (NotImplementedError with the texts `strength` and `smoothed`)."""
+    out = dict(n_coarse=16, gamma=None, scale=None, fp32=0, max_iter=20000, smoothed=1)
+    out.update(amg or {})
+    if float(out.get("strength", 0) or 0) > 0.0:
+        raise NotImplementedError(strength)
+    if not out.get("smoothed", 1):
+        raise NotImplementedError(smoothed)
+    return out
+
+
+class _ElasticOptions(nn.Module):
+    """The private base of the elastic solvers: the solve options and Dirichlet data of the constructor, the plan, and
+    the step from a call's (f, load, layout) to the op's inputs.  """
+    _refusal_scope = "for elasticity"       # "node gradients are not implemented <scope>": the class names its coefficient
+    _ONE_D = ("diffhe: elasticity needs a 2D or 3D mesh (a 1D bar is the scalar problem of DifferentiableFESolver with "
+              "kappa = E A)")
+
+    def _init_options(self, mesh, fixed, device, tol, max_iter, method, amg, check_every, hierarchy_of: str) -> None:
+        """method, fixed= and the option attributes; hierarchy_of: the operator the strength refusal names."""
         if method not in ("auto", "ell", "ell-jacobi"):
             raise ValueError(f"Unknown method: {method!r}")
         self.mesh, self.method = mesh, method
-        self._E = torch.tensor(float(E), dtype=torch.float64) if isinstance(E, (int, float)) else E.to(dtype=torch.float64)
         self._is_bc, self._g = parse_fixed(mesh, fixed)
-        # the options of the general path's aggregation-multigrid PCG, as on DifferentiableFESolver
-        self.amg = dict(n_coarse=16, gamma=None, scale=None, fp32=0, max_iter=20000, smoothed=1)
-        self.amg.update(amg or {})
-        if float(self.amg.get("strength", 0) or 0) > 0.0:
-            raise NotImplementedError("diffhe: amg=dict(strength=...) is not implemented for elasticity (the hierarchy "
-                                      "is built from the unit-E operator)")
-        if not self.amg.get("smoothed", 1):
-            raise NotImplementedError("diffhe: elasticity builds a smoothed-aggregation hierarchy (amg smoothed=0 is not "
-                                      "implemented)")
+        self.amg = _amg_options(amg, "diffhe: amg=dict(strength=...) is not implemented for elasticity (the hierarchy is "
+                                     f"built from the {hierarchy_of})")
         self._device = device
         self._tol_user = tol
         self.tol, self.max_iter, self.check_every = tol, int(max_iter), int(check_every)
-        self.last_info = SolveInfo()
-
-    @property
-    def E(self) -> torch.Tensor:
-        return self._E
 
     def _plan(self):
         return get_plan(self.mesh, _resolve_device(self._device), prune=False)
@@ -1115,11 +624,23 @@ class ElasticFESolver(nn.Module):
             raise ValueError(f"{name} must be (n, d) or (B, n, d) with n={n}, d={d}, got {tuple(t.shape)}")
         return t.to(torch.float64)
 
-    def forward(self, f: Optional[torch.Tensor] = None, load: Optional[torch.Tensor] = None, layout: str = "sample",
-                dirichlet=None, h=None, u_inf=None, flux=None, eigenstrain=None) -> torch.Tensor:
-        """u for the body force f and the nodal load: (n, d), (B, n, d), or (n, d, B) with layout="node" -- the shape of
-        the right-hand side.  f None: zero.  eigenstrain: an initial strain eps0 (layouts: `eigenstrain_load`), whose
-        load F0(eps0, E) joins `load` in front of the unchanged solve; None takes exactly the path without it."""
+    def _moving_nodes(self) -> bool:
+        return self.mesh.nodes.requires_grad and torch.is_grad_enabled()
+
+    def _refuse_moving_nodes(self, what: str, eigenstrain: bool) -> None:
+        """Moving nodes are `ShapeElasticFESolver`'s (diffhe.elastic_shape), which overrides this."""
+        if self._moving_nodes():
+            raise NotImplementedError(f"diffhe: node gradients are not implemented {self._refusal_scope} (mesh.nodes "
+                                      "requires grad)")
+
+    def _rhs_inputs(self, coeff: torch.Tensor, f, load, layout: str, *, dirichlet=None, h=None, u_inf=None, flux=None,
+                    eigenstrain=None, eigenstrain_batch: bool = True, implied: Optional[int] = None, where=None):
+        """-> (f_in, load_in, node) as the solve ops take them (empty tensor = absent; `node`: layout == "node") from the
+        arguments of one `forward`: the refusals of scalar-solver data, the layout and shape checks, the eigenstrain's
+        load joined to `load`, and a zero f where neither is given.  eigenstrain_batch: with layout="node" an eigenstrain
+        alone may carry the batch (false: f or load must, and are checked before the load joins); implied: the batch
+        that other data of the call carry (facet data), which an unbatched right-hand side is expanded to; where: the
+        device of that zero f and of the default, None: the coefficient's."""
         if dirichlet is not None:
             raise NotImplementedError("diffhe: dirichlet= is not implemented for elasticity (the boundary-band kernels "
                                       "read scalar element tables); give prescribed displacements with fixed=")
@@ -1129,32 +650,72 @@ class ElasticFESolver(nn.Module):
         if layout not in ("sample", "node"):
             raise ValueError(f"Unknown layout: {layout!r}")
         self._refuse_moving_nodes("solve", eigenstrain is not None)
+        n, d, node = self.mesh.n_nodes, self.mesh.dim, layout == "node"
+        where = coeff.device if where is None else where
         f64, load64 = self._checked(f, "f", layout), self._checked(load, "load", layout)
-        if eigenstrain is not None:
+        if implied is not None and not node and not any(t is not None and t.dim() == 3 for t in (f64, load64)):
+            base = f64 if f64 is not None else torch.zeros((n, d), dtype=torch.float64, device=where)
+            f64 = base.reshape(1, n, d).expand(implied, n, d)
+        if eigenstrain is not None and eigenstrain_batch:
             load64 = self._with_eigenstrain_load(eigenstrain, f64, load64, layout)
-        if layout == "node":
+        if node:
             if f64 is None and load64 is None:
                 raise ValueError("layout='node' needs f or load to carry the batch: (n, d, B)")
             if f64 is not None and load64 is not None and f64.shape != load64.shape:
                 raise ValueError(f"layout='node': f (and load) must be (n, d, B) with one B, got {tuple(f64.shape)} and "
                                  f"{tuple(load64.shape)}")
-        E = self._E
-        empty = E.new_empty(0)
+        if eigenstrain is not None and not eigenstrain_batch:
+            load64 = self._with_eigenstrain_load(eigenstrain, f64, load64, layout)
+        empty = coeff.new_empty(0)
         if f64 is None and load64 is None:
-            f64 = torch.zeros((self.mesh.n_nodes, self.mesh.dim), dtype=torch.float64, device=E.device)
-        f_in, load_in = (empty if f64 is None else f64), (empty if load64 is None else load64)
-        _kappa_layout(E, self.mesh.n_elements, _batch_of(self, f_in, load_in, layout == "node")[0], layout == "node")
+            f64 = torch.zeros((n, d), dtype=torch.float64, device=where)
+        return (empty if f64 is None else f64), (empty if load64 is None else load64), node
+
+
+
+class ElasticFESolver(_ElasticOptions):
+    """Displacement of a linear-elastic body per sample, differentiable with respect to the Young's modulus E per element,
+    the body force f and the nodal load (see the module docstring).
+
+    Parameters
+    ----------
+    mesh : FEMesh -- P1 triangles or P1 tetrahedra.
+    E : float or tensor or Parameter -- (), (B,), (m,), (B, m); (m, B) with layout="node".  May require grad.
+    nu : float, -1 < nu < 0.5.  plane : "stress" (default) or "strain", 2D meshes only.
+    fixed : None (clamp the nodes of mesh.dirichlet_nodes) or {(node, component): value}.
+    device, tol, max_iter, method ("auto" or "ell-jacobi"), amg : as on `DifferentiableFESolver`.
+    """
+
+    def __init__(self, mesh, E=1.0, nu: float = 0.3, *, plane: Optional[str] = None, fixed=None, device=None,
+                 tol: Optional[float] = None, max_iter: int = 20000, method: str = "auto", amg: Optional[dict] = None,
+                 check_every: int = 25):
+        super().__init__()
+        _check_mesh(mesh, self._ONE_D, "diffhe: elasticity is implemented for P1 elements only (this mesh has {k} nodes "
+                                       "per element)")
+        if mesh.dim == 3 and plane is not None:
+            raise ValueError("plane= applies to 2D meshes only (a 3D body needs no plane-stress / plane-strain choice)")
+        self.plane = None if mesh.dim == 3 else ("stress" if plane is None else plane)
+        self.nu = float(nu)
+        self._lam1, self._mu1 = lame_unit(self.nu, mesh.dim, self.plane)
+        self._init_options(mesh, fixed, device, tol, max_iter, method, amg, check_every, "unit-E operator")
+        self._E = torch.tensor(float(E), dtype=torch.float64) if isinstance(E, (int, float)) else E.to(dtype=torch.float64)
+        self.last_info = SolveInfo()
+
+    @property
+    def E(self) -> torch.Tensor:
+        return self._E
+
+    def forward(self, f: Optional[torch.Tensor] = None, load: Optional[torch.Tensor] = None, layout: str = "sample",
+                dirichlet=None, h=None, u_inf=None, flux=None, eigenstrain=None) -> torch.Tensor:
+        """u for the body force f and the nodal load: (n, d), (B, n, d), or (n, d, B) with layout="node" -- the shape of
+        the right-hand side.  f None: zero.  eigenstrain: an initial strain eps0 (layouts: `eigenstrain_load`), whose
+        load F0(eps0, E) joins `load` in front of the unchanged solve; None takes exactly the path without it."""
+        E = self._E
+        f_in, load_in, node = self._rhs_inputs(E, f, load, layout, dirichlet=dirichlet, h=h, u_inf=u_inf, flux=flux,
+                                               eigenstrain=eigenstrain)
+        _kappa_layout(E, self.mesh.n_elements, _batch_of(self, f_in, load_in, node)[0], node)
         _SOLVERS[id(self)] = self
-        return self._solve_op(E, f_in, load_in, layout == "node")
-
-    def _moving_nodes(self) -> bool:
-        return self.mesh.nodes.requires_grad and torch.is_grad_enabled()
-
-    def _refuse_moving_nodes(self, what: str, eigenstrain: bool) -> None:
-        """Moving nodes are `ShapeElasticFESolver`'s (diffhe.elastic_shape), which overrides this."""
-        if self._moving_nodes():
-            raise NotImplementedError("diffhe: node gradients are not implemented for elasticity (mesh.nodes requires "
-                                      "grad)")
+        return self._solve_op(E, f_in, load_in, node)
 
     def _solve_op(self, E: torch.Tensor, f_in: torch.Tensor, load_in: torch.Tensor, node_major: bool) -> torch.Tensor:
         save = torch.is_grad_enabled() and (E.requires_grad or f_in.requires_grad or load_in.requires_grad)

@@ -50,14 +50,12 @@ from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
-import torch.nn as nn
 
-from .elastic import (ElasticFESolver, _ElasticCall, _ElasticSolve, _Inputs, _batch_of, _cycle_defaults,
-                      _measure_row_bounds, _setup_of, lame_unit, parse_fixed)
-from .plan import get_plan, padded_batch, _stream
-from .solver import (K_SAMPLE, K_SAMPLE_ELEM, K_SCALAR, SolveInfo, _SOLVERS, _call_options, _fake_grads,
-                     _kappa_layout, _like_grads, _register_state, _resolve_device, _run_call, _state_of, _tensor_mode,
-                     _tie_state)
+from .elastic import (_ElasticOptions, _ElasticSolve, _batch_of, _check_mesh, _run_adjoint, _solve_autograd, _solve_call,
+                      _solve_fake, _solve_result)
+from .plan import _stream
+from .solver import (K_SAMPLE, K_SAMPLE_ELEM, K_SCALAR, SolveInfo, _SOLVERS, _fake_grads, _kappa_layout, _like_grads,
+                     _tensor_mode)
 
 __all__ = ("AnisotropicElasticFESolver", "AnisoElasticInfo", "isotropic", "orthotropic_2d", "orthotropic_3d", "cubic",
            "rotated", "matrix", "components")
@@ -228,144 +226,61 @@ def _stiffness_device(eng, C: torch.Tensor, mode: int, B: int, Bp: int, nt: int,
 
 
 class _AnisoElasticSolve(_ElasticSolve):
-    """`_ElasticSolve` with the tensor assembly, the measured smoother bounds and dL/dC; the right-hand side, the layout
-    helpers and the solves are the base class's."""
+    """`_ElasticSolve` with the tensor assembly, the measured smoother bounds and dL/dC; `forward`, `adjoint`, the
+    right-hand side, the layout helpers and the solves are the base class's."""
+    Info = AnisoElasticInfo
+    bounds_error = ("diffhe: stiffness tensor not positive definite (a diagonal entry of the assembled operator is not "
+                    "positive and finite)")
 
-    def _assemble(self, cdev, csc, cse, csb, Bv):
-        """vals (d W, n d, Bv), lift (n d, Bv) of the block row-gather assembly (csrc/elastic_aniso.hip)."""
-        plan, dofs = self.plan, self.setup.dofs
+    def _operator(self, C):
+        """vals (d W, n d, Bv), lift (n d, Bv) of the block row-gather assembly (csrc/elastic_aniso.hip), and Bv."""
+        plan, dofs, call = self.plan, self.setup.dofs, self.call
+        cdev, csc, cse, csb, Bv = _stiffness_device(self.node_eng, C, call.mode, call.B, self.Bp, self.solver.nt,
+                                                    call.kappa_em)
         gtab, vol = plan.gradient_table()
         vals = torch.empty((dofs.W, dofs.n, Bv), dtype=torch.float64, device=plan.device)
         lift = torch.empty((dofs.n, Bv), dtype=torch.float64, device=plan.device)
         self.eng.L.diffhe_elastc_assemble_rows(gtab, vol, plan.dim, cdev, csc, cse, csb, plan.ent_ptr, plan.contrib,
                                                plan.cols, dofs.is_bc, dofs.g, vals, lift, plan.n, plan.m, plan.W, Bv,
                                                _stream(plan.device))
-        return vals, lift
+        return vals, lift, Bv
 
-    def _measure_bounds(self, Bv) -> Tuple[float, ...]:
-        """The row bound of every level of this call's hierarchy, written over the levels' recorded bounds (thousandths,
-        rounded up: diffhe_amg_level.reserved).  ONE device synchronisation: the copy of the n_levels doubles."""
-        return _measure_row_bounds(self, Bv, "diffhe: stiffness tensor not positive definite (a diagonal entry of the "
-                                   "assembled operator is not positive and finite)")
-
-    def forward(self, call_in, info: SolveInfo) -> torch.Tensor:
-        C, f, load = call_in.E, call_in.f, call_in.load
-        solver, setup, call, eng = self.solver, self.setup, self.call, self.eng
-        dofs, B = setup.dofs, call.B
-        Bp = self.Bp = padded_batch(B)
-        cdev, csc, cse, csb, Bv = _stiffness_device(self.node_eng, C, call.mode, B, Bp, solver.nt, call.kappa_em)
-        vals, lift = self._assemble(cdev, csc, cse, csb, Bv)
-        rhs = -lift if Bv == Bp else (-lift).expand(dofs.n, Bp).contiguous()
-        if f is not None:
-            rhs += self._apply_load_map(self._to_dofs(f, call.f_batched))
-        if load is not None:
-            rhs += self._to_dofs(load, call.load_batched)
-        rhs[dofs.is_bc.bool()] = 0.0
-        if Bp > B:
-            rhs[:, B:] = 0.0
-        self.hier, self.bounds = None, ()
-        if solver.method != "ell-jacobi":
-            levels, stats = setup.levels()
-            if levels:
-                amg = _cycle_defaults(self.amg, dofs.n, Bp)
-                self.hier = eng.amg_setup(vals, Bv, bool(amg.get("fp32", 0)), levels)
-                self.bounds = self._measure_bounds(Bv)
-                info.hierarchy, info.hierarchy_levels, info.operator_complexity = "unit+row-bounds", stats[0], stats[1]
-        if self.hier is not None:
-            info.path = "ell-amgpcg"
-            x, its, bad, relres, *_ = eng.amg_pcg(self.hier, rhs, Bp, Bv, self.amg)
-        else:
-            info.path = "ell-pcg"
-            x, its, bad, relres, *_ = eng.cg(vals, rhs, Bp, Bv)
-        info.iterations, info.not_converged = its, bad
-        info.max_relres = float(relres[:B].max())
-        self.vals, self.x, self.Bv = vals, x, Bv
-        return self._from_dofs(x, dofs.g if (setup.has_data or not call.node_major) else None)
-
-    def adjoint(self, gbar: torch.Tensor, need_c: bool, need_f: bool, need_load: bool):
-        """lambda = A^-1 gbar on the free dofs with the forward's operator, hierarchy and bounds, then dL/dC in the shape
-        of C, dL/df = M lambda and dL/dload = lambda in the caller's layout."""
-        call, setup, plan, eng, B, Bp = self.call, self.setup, self.plan, self.eng, self.call.B, self.Bp
-        L, st, nt = eng.L, _stream(plan.device), self.solver.nt
-        info = self.solver.last_info
-        rhs = self._to_dofs(gbar, True, zero_fixed=True)
-        if self.hier is not None:
-            res = eng.amg_pcg(self.hier, rhs, Bp, self.Bv, self.amg)
-        else:
-            res = eng.cg(self.vals, rhs, Bp, self.Bv)
-        lam = res.x
-        info.adj_iterations, info.adj_max_relres = res.iterations, float(res.relres[:B].max())
-        info.not_converged += res.not_converged
-        grad_c = grad_f = grad_load = None
-        if need_c:
-            gtab, vol = plan.gradient_table()
-            args = (plan.elems, gtab, vol, plan.dim, lam, self.x, setup.dofs.g, plan.n, plan.m)
-            sums, dc = self.node_eng.element_grad(
-                call.mode, call.kappa_em, B, Bp, nt,
-                lambda dc_e, osc, ose, part, total: L.diffhe_elastc_grad(*args, Bp, dc_e, osc, ose, part, total, st),
-                lambda dc, osc, ose: L.diffhe_elastc_grad_shared(*args, B, Bp, dc, osc, ose, st))
-            if call.mode == K_SCALAR:               # (nt, B) sums over the elements: the one tensor takes their total
-                dc = sums.sum(dim=1)
-            elif call.mode == K_SAMPLE:
-                dc = sums.t()
-            grad_c = dc.reshape(call.e_shape).to(call.e_device)
-        if need_f:
-            df = self._from_dofs(self._apply_load_map(lam))
-            grad_f = (df if call.f_batched else df.sum(dim=0)).to(call.out_device)
-        if need_load:
-            dl = self._from_dofs(lam)
-            dl = dl.clone() if call.node_major else dl
-            grad_load = (dl if call.load_batched else dl.sum(dim=0)).to(call.out_device)
-        return grad_c, grad_f, grad_load
-
-
-def _aniso_forward(solver: "AnisotropicElasticFESolver", C, f, load, node_major):
-    """(u, state) of one call."""
-    plan = solver._plan()
-    setup = _setup_of(plan, HIERARCHY_NU, solver._plane, *lame_unit(HIERARCHY_NU, plan.dim, solver._plane),
-                      solver._is_bc, solver._g)
-    B_rhs, fb, lb = _batch_of(solver, f, load, node_major)
-    mode, B, em = _stiffness_layout(C, solver.nt, plan.m, B_rhs, node_major)
-    src = f if f.numel() else load
-    call = _ElasticCall(B, mode, em, B_rhs is not None, node_major, src.device if src.numel() else C.device, C.shape,
-                        C.device, fb, lb)
-    tol, _, amg = _call_options(chain=False, lattice=False, closed_boundary=False, n=setup.dofs.n, mode=mode,
-                                tol_user=solver._tol_user, mg_user=set(), mg={}, amg=solver.amg)
-    solver.tol = tol
-    state = _AnisoElasticSolve(solver, setup, call, tol, amg)
-    u = _run_call(state, _Inputs(C, f if f.numel() else None, load if load.numel() else None, B, call.batched,
-                                 node_major, call.out_device))
-    solver.last_info = AnisoElasticInfo(**vars(solver.last_info), jacobi_bounds=state.bounds)
-    return u, state
-
-
-def _out_shape(solver, C, f, load, node_major):
-    n, d, m = solver.mesh.n_nodes, solver.mesh.dim, solver.mesh.n_elements
-    B_rhs, _, _ = _batch_of(solver, f, load, node_major)
-    if node_major:
-        return (n, d, B_rhs)
-    _, B, _ = _kappa_layout(C, m, B_rhs, False, solver.nt)
-    return (B, n, d) if (B_rhs is not None or B > 1) else (n, d)
+    def _coeff_grad(self, lam):
+        """dL/dC in the shape of C from the adjoint lambda and the saved iterate (`diffhe_elastc_grad*`)."""
+        call, plan, B, Bp = self.call, self.plan, self.call.B, self.Bp
+        L, st = self.eng.L, _stream(plan.device)
+        gtab, vol = plan.gradient_table()
+        args = (plan.elems, gtab, vol, plan.dim, lam, self.x, self.setup.dofs.g, plan.n, plan.m)
+        sums, dc = self.node_eng.element_grad(
+            call.mode, call.kappa_em, B, Bp, self.solver.nt,
+            lambda dc_e, osc, ose, part, total: L.diffhe_elastc_grad(*args, Bp, dc_e, osc, ose, part, total, st),
+            lambda dc, osc, ose: L.diffhe_elastc_grad_shared(*args, B, Bp, dc, osc, ose, st))
+        if call.mode == K_SCALAR:               # (nt, B) sums over the elements: the one tensor takes their total
+            dc = sums.sum(dim=1)
+        elif call.mode == K_SAMPLE:
+            dc = sums.t()
+        return dc.reshape(call.e_shape)
 
 
 # ---------------------------------------------------------------------------------------------
-# torch.library custom ops diffhe::elastic_aniso_solve / diffhe::elastic_aniso_solve_backward, in the manner of
-# diffhe::elastic_solve: the solver and the state of the call travel as integer handles.  f / load: empty tensor = absent.
+# torch.library custom ops diffhe::elastic_aniso_solve / diffhe::elastic_aniso_solve_backward, on the shared plumbing of
+# diffhe::elastic_solve (diffhe.elastic): the solver and the state of the call travel as integer handles.  f / load: empty
+# tensor = absent.
 # ---------------------------------------------------------------------------------------------
 @torch.library.custom_op("diffhe::elastic_aniso_solve", mutates_args=())
 def elastic_aniso_solve(C: torch.Tensor, f: torch.Tensor, load: torch.Tensor, handle: int, save: bool,
                         node_major: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     """(u, token) of the `AnisotropicElasticFESolver` registered under `handle`; `token` names the saved adjoint state
     (0 when `save` is false)."""
-    u, state = _aniso_forward(_SOLVERS[handle], C, f, load, node_major)
-    return u.clone() if u._base is not None or u.data_ptr() == state.x.data_ptr() else u, _register_state(state, save)
+    solver = _SOLVERS[handle]
+    return _solve_result(*_solve_call(solver, _AnisoElasticSolve, C, f, load, node_major,
+                                      lambda C_, m, B_rhs, node: _stiffness_layout(C_, solver.nt, m, B_rhs, node),
+                                      hierarchy=(HIERARCHY_NU, solver._plane)), save)
 
 
 @elastic_aniso_solve.register_fake
 def _elastic_aniso_solve_fake(C, f, load, handle, save, node_major):
-    shape = _out_shape(_SOLVERS[handle], C, f, load, node_major)
-    like = f if f.numel() else (load if load.numel() else C)
-    return like.new_empty(shape, dtype=torch.float64), torch.empty((), dtype=torch.int64)
+    return _solve_fake(_SOLVERS[handle], C, f, load, node_major, _SOLVERS[handle].nt)
 
 
 @torch.library.custom_op("diffhe::elastic_aniso_solve_backward", mutates_args=())
@@ -373,12 +288,7 @@ def elastic_aniso_solve_backward(gbar: torch.Tensor, token: torch.Tensor, need_c
                                  c_like: torch.Tensor, f_like: torch.Tensor,
                                  load_like: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(dL/dC, dL/df, dL/dload) of the forward call named by `token` from ONE adjoint solve; unused ones come back empty."""
-    state = _state_of(token)
-    call = state.call
-    g = gbar.detach()
-    if not call.node_major and not call.batched and call.B == 1:
-        g = g.unsqueeze(0)
-    grads = state.adjoint(g, need_c, need_f, need_load)
+    _, grads = _run_adjoint(gbar, token, need_c, need_f, need_load)
     return _like_grads(gbar, grads, (c_like, f_like, load_like))
 
 
@@ -387,30 +297,15 @@ def _elastic_aniso_solve_backward_fake(gbar, token, need_c, need_f, need_load, c
     return _fake_grads(gbar, (need_c, need_f, need_load), (c_like, f_like, load_like))
 
 
-def _setup_context(ctx, inputs, output):
-    C, f, load = inputs[:3]
-    _tie_state(ctx, output[1], C, f, load)
-
-
-def _backward(ctx, grad_u, _grad_token):
-    if torch.is_grad_enabled():
-        raise NotImplementedError("diffhe: second-order derivatives of an anisotropic elastic solve are not implemented "
-                                  "(backward with create_graph=True, diffhe.elastic_aniso)")
-    token, C, f, load = ctx.saved_tensors[:4]
-    needs = tuple(bool(v) for v in ctx.needs_input_grad[:3])
-    if not any(needs):
-        return (None,) * 6
-    gc, gf, gl = torch.ops.diffhe.elastic_aniso_solve_backward(grad_u.contiguous(), token, *needs, C, f, load)
-    return (gc if needs[0] else None, gf if needs[1] else None, gl if needs[2] else None, None, None, None)
-
-
-torch.library.register_autograd("diffhe::elastic_aniso_solve", _backward, setup_context=_setup_context)
+_setup_context, _backward = _solve_autograd(
+    "elastic_aniso_solve", 3, 6, "diffhe: second-order derivatives of an anisotropic elastic solve are not implemented "
+    "(backward with create_graph=True, diffhe.elastic_aniso)")
 
 
 # ---------------------------------------------------------------------------------------------
 # The public solver
 # ---------------------------------------------------------------------------------------------
-class AnisotropicElasticFESolver(nn.Module):
+class AnisotropicElasticFESolver(_ElasticOptions):
     """Displacement of a linear-elastic body with a stiffness tensor per element and sample, differentiable with respect
     to the tensor, the body force f and the nodal load (see the module docstring).
 
@@ -424,48 +319,26 @@ class AnisotropicElasticFESolver(nn.Module):
     device, tol, max_iter, method ("auto" or "ell-jacobi"), amg : as on `ElasticFESolver`.
     """
 
+    _refusal_scope = "with a stiffness tensor"
+
     def __init__(self, mesh, C, *, fixed=None, validate: bool = False, device=None, tol: Optional[float] = None,
                  max_iter: int = 20000, method: str = "auto", amg: Optional[dict] = None, check_every: int = 25):
         super().__init__()
-        if mesh.dim == 1:
-            raise NotImplementedError("diffhe: elasticity needs a 2D or 3D mesh (a 1D bar is the scalar problem of "
-                                      "DifferentiableFESolver with kappa = E A)")
-        if mesh.dim not in (2, 3):
-            raise NotImplementedError("Only 2D and 3D supported")
-        if mesh.elements.shape[1] != mesh.dim + 1:
-            raise NotImplementedError("diffhe: elasticity with a stiffness tensor is implemented for P1 elements only "
-                                      f"(this mesh has {mesh.elements.shape[1]} nodes per element)")
-        if method not in ("auto", "ell", "ell-jacobi"):
-            raise ValueError(f"Unknown method: {method!r}")
-        self.mesh, self.method, self.validate = mesh, method, bool(validate)
+        _check_mesh(mesh, self._ONE_D, "diffhe: elasticity with a stiffness tensor is implemented for P1 elements only "
+                                       "(this mesh has {k} nodes per element)")
+        self._init_options(mesh, fixed, device, tol, max_iter, method, amg, check_every, "isotropic unit operator")
+        self.validate = bool(validate)
         self.nv = 3 if mesh.dim == 2 else 6
         self.nt = self.nv * (self.nv + 1) // 2
         self._plane = "stress" if mesh.dim == 2 else None      # of the isotropic unit operator behind the hierarchy
         self._C = _t64(C).to(dtype=torch.float64)
         if self._C.dim() != 3:      # a per-sample field is checked against the batch of the right-hand side at the first solve
             _stiffness_layout(self._C, self.nt, mesh.n_elements, None)
-        self._is_bc, self._g = parse_fixed(mesh, fixed)
-        self.amg = dict(n_coarse=16, gamma=None, scale=None, fp32=0, max_iter=20000, smoothed=1)
-        self.amg.update(amg or {})
-        if float(self.amg.get("strength", 0) or 0) > 0.0:
-            raise NotImplementedError("diffhe: amg=dict(strength=...) is not implemented for elasticity (the hierarchy "
-                                      "is built from the isotropic unit operator)")
-        if not self.amg.get("smoothed", 1):
-            raise NotImplementedError("diffhe: elasticity builds a smoothed-aggregation hierarchy (amg smoothed=0 is not "
-                                      "implemented)")
-        self._device = device
-        self._tol_user = tol
-        self.tol, self.max_iter, self.check_every = tol, int(max_iter), int(check_every)
         self.last_info = AnisoElasticInfo()
 
     @property
     def C(self) -> torch.Tensor:
         return self._C
-
-    def _plan(self):
-        return get_plan(self.mesh, _resolve_device(self._device), prune=False)
-
-    _checked = ElasticFESolver._checked
 
     def _validate(self, mode: int, em: bool) -> None:
         Cm = matrix(self._C.detach().movedim(0, -1) if (mode == K_SAMPLE_ELEM and em) else self._C.detach())
@@ -477,33 +350,11 @@ class AnisotropicElasticFESolver(nn.Module):
                 dirichlet=None, h=None, u_inf=None, flux=None, eigenstrain=None) -> torch.Tensor:
         """u for the body force f and the nodal load: (n, d), (B, n, d), or (n, d, B) with layout="node" -- the shape of
         the right-hand side.  f None: zero."""
-        if dirichlet is not None:
-            raise NotImplementedError("diffhe: dirichlet= is not implemented for elasticity (the boundary-band kernels "
-                                      "read scalar element tables); give prescribed displacements with fixed=")
-        if h is not None or u_inf is not None or flux is not None:
-            raise NotImplementedError("diffhe: Robin / flux data (h=, u_inf=, flux=) are not implemented for elasticity; "
-                                      "integrate a traction into load=")
         if eigenstrain is not None:
             raise NotImplementedError("diffhe: eigenstrain= is not implemented with a stiffness tensor (the eigenstrain "
                                       "kernels read (E, nu)); add the load C eps0 to load=")
-        if layout not in ("sample", "node"):
-            raise ValueError(f"Unknown layout: {layout!r}")
-        if self.mesh.nodes.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError("diffhe: node gradients are not implemented with a stiffness tensor (mesh.nodes "
-                                      "requires grad)")
-        f64, load64 = self._checked(f, "f", layout), self._checked(load, "load", layout)
-        node = layout == "node"
-        if node:
-            if f64 is None and load64 is None:
-                raise ValueError("layout='node' needs f or load to carry the batch: (n, d, B)")
-            if f64 is not None and load64 is not None and f64.shape != load64.shape:
-                raise ValueError(f"layout='node': f (and load) must be (n, d, B) with one B, got {tuple(f64.shape)} and "
-                                 f"{tuple(load64.shape)}")
         C = self._C
-        empty = C.new_empty(0)
-        if f64 is None and load64 is None:
-            f64 = torch.zeros((self.mesh.n_nodes, self.mesh.dim), dtype=torch.float64, device=C.device)
-        f_in, load_in = (empty if f64 is None else f64), (empty if load64 is None else load64)
+        f_in, load_in, node = self._rhs_inputs(C, f, load, layout, dirichlet=dirichlet, h=h, u_inf=u_inf, flux=flux)
         mode, _, em = _stiffness_layout(C, self.nt, self.mesh.n_elements, _batch_of(self, f_in, load_in, node)[0], node)
         if self.validate:
             self._validate(mode, em)

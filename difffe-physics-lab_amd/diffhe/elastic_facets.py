@@ -63,12 +63,11 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .elastic import (ElasticFESolver, _ElasticCall, _ElasticSolve, _Inputs, _batch_of, _cycle_defaults,
-                      _measure_row_bounds, _out_shape, _setup_of)
-from .plan import padded_batch, _stream
+from .elastic import (ElasticFESolver, _ElasticSolve, _batch_of, _run_adjoint, _solve_autograd, _solve_call, _solve_fake,
+                      _solve_result)
+from .plan import _stream
 from .robin import BOTH, FACET, SAMPLE, SCALAR
-from .solver import (SolveInfo, _SOLVERS, _call_options, _fake_grads, _kappa_layout, _like_grads, _register_state,
-                     _run_call, _state_of, _tie_state)
+from .solver import SolveInfo, _SOLVERS, _fake_grads, _kappa_layout, _like_grads
 
 __all__ = ("TractionElasticFESolver", "ElasticFacetInfo", "opposite_nodes", "facet_geometry")
 
@@ -195,64 +194,34 @@ class ElasticFacetInfo(SolveInfo):
 # One call
 # ---------------------------------------------------------------------------------------------
 class _FacetElasticSolve(_ElasticSolve):
-    """`_ElasticSolve` with the facet terms added to the stored operator and the right-hand side, the measured smoother
-    bounds of a call with a foundation, and the facet gradients (csrc/elastic_facets.hip).  `tab`: the plan's facet
-    table; `data`: the call's (traction, pressure, k_normal, k_tangent) as `_Datum` or None -- boundary-sized, kept for
-    the adjoint."""
+    """`_ElasticSolve` with the facet terms added to the stored operator and the right-hand side -- one launch after the
+    right-hand side is formed --, the measured smoother bounds of a call with a foundation (`bounds_error` is set on such
+    a call), and the facet gradients from the adjoint lambda it keeps (csrc/elastic_facets.hip).  `tab`: the plan's
+    facet table; `data`: the call's (traction, pressure, k_normal, k_tangent) as `_Datum` or None -- boundary-sized, kept
+    for the adjoint."""
+    Info = ElasticFacetInfo
+    keep_lambda = True                  # `facet_grads` reads lambda after `adjoint`
     tab = None
     data = (None, None, None, None)
-    bounds: Tuple[float, ...] = ()
 
-    def _facet_terms(self, vals, rhs, Bv) -> None:
+    def _operator(self, E):
+        """The isotropic operator, one matrix per sample also where only a foundation stiffness is per sample."""
+        call, Bp = self.call, self.Bp
+        kdev, kse, ksb, Bv = self.node_eng.kappa_device(E, call.mode, call.B, Bp, em=call.kappa_em)
+        if Bv == 1 and Bp > 1 and any(z is not None and z.per_sample for z in self.data[2:]):
+            Bv = Bp                     # for the foundation's sake: the shared E has ksb = 0
+        return (*self.setup.assemble(kdev, kse, ksb, Bv), Bv)
+
+    def _after_rhs(self, vals, rhs, Bv) -> None:
         plan, dofs, tab = self.plan, self.setup.dofs, self.tab
         t, p, kn, kt = self.data
         scalar = lambda z: (None, 0, 0) if z is None else (z.dev, z.sf, z.sb)  # noqa: E731
         self.eng.L.diffhe_elastf_assemble(
             tab["fac"], tab["d"], tab["n_f"], tab["area"], tab["normal"], tab["rows"], tab["row_ptr"], tab["ent_code"],
             tab["ent_slot"], tab["n_rows"], dofs.is_bc, dofs.g, *((None, 0, 0, 0) if t is None else (t.dev, t.sf, t.sc, t.sb)),
-            *scalar(p), *scalar(kn), *scalar(kt), vals, rhs, plan.n, Bv, self.call.B, self.Bp, _stream(plan.device))
+            *scalar(p), *scalar(kn), *scalar(kt), vals if (kn is not None or kt is not None) else None, rhs, plan.n, Bv,
+            self.call.B, self.Bp, _stream(plan.device))
 
-    def forward(self, call_in, info: SolveInfo) -> torch.Tensor:
-        E, f, load = call_in.E, call_in.f, call_in.load
-        solver, setup, call, eng = self.solver, self.setup, self.call, self.eng
-        dofs, B = setup.dofs, call.B
-        Bp = self.Bp = padded_batch(B)
-        kn, kt = self.data[2:]
-        stiff = kn is not None or kt is not None
-        kdev, kse, ksb, Bv = self.node_eng.kappa_device(E, call.mode, B, Bp, em=call.kappa_em)
-        if Bv == 1 and Bp > 1 and any(z is not None and z.per_sample for z in (kn, kt)):
-            Bv = Bp                     # one matrix per sample for the foundation's sake: the shared E has ksb = 0
-        vals, lift = setup.assemble(kdev, kse, ksb, Bv)
-        rhs = -lift if Bv == Bp else (-lift).expand(dofs.n, Bp).contiguous()
-        if f is not None:
-            rhs += self._apply_load_map(self._to_dofs(f, call.f_batched))
-        if load is not None:
-            rhs += self._to_dofs(load, call.load_batched)
-        rhs[dofs.is_bc.bool()] = 0.0
-        if Bp > B:
-            rhs[:, B:] = 0.0
-        self._facet_terms(vals if stiff else None, rhs, Bv)
-        self.hier, self.bounds = None, ()
-        if solver.method != "ell-jacobi":
-            levels, stats = setup.levels()
-            if levels:
-                amg = _cycle_defaults(self.amg, dofs.n, Bp)
-                self.hier = eng.amg_setup(vals, Bv, bool(amg.get("fp32", 0)), levels)
-                info.hierarchy, info.hierarchy_levels, info.operator_complexity = "unit", stats[0], stats[1]
-                if stiff:
-                    self.bounds = _measure_row_bounds(self, Bv, "diffhe: a diagonal entry of the operator with its "
-                                                      "foundation is not positive and finite (a negative stiffness?)")
-                    info.hierarchy = "unit+row-bounds"
-        if self.hier is not None:
-            info.path = "ell-amgpcg"
-            x, its, bad, relres, *_ = eng.amg_pcg(self.hier, rhs, Bp, Bv, self.amg)
-        else:
-            info.path = "ell-pcg"
-            x, its, bad, relres, *_ = eng.cg(vals, rhs, Bp, Bv)
-        info.iterations, info.not_converged = its, bad
-        info.max_relres = float(relres[:B].max())
-        self.vals, self.x, self.Bv = vals, x, Bv
-        return self._from_dofs(x, dofs.g if (setup.has_data or not call.node_major) else None)
 
     def facet_grads(self, needs):
         """(dL/dtraction, dL/dpressure, dL/dk_normal, dL/dk_tangent), each in the shape of its input or None, from the
@@ -295,38 +264,33 @@ class _FacetElasticSolve(_ElasticSolve):
         return grads
 
 
+_BOUNDS_ERROR = ("diffhe: a diagonal entry of the operator with its foundation is not positive and finite (a negative "
+                 "stiffness?)")
+
+
 def _facet_forward(solver: "TractionElasticFESolver", E, f, load, data, node_major):
-    """(u, state) of one call with facet data (`data`: the four tensors, empty = absent)."""
-    plan = solver._plan()
-    setup = _setup_of(plan, solver.nu, solver.plane, solver._lam1, solver._mu1, solver._is_bc, solver._g)
-    tab = solver._table(plan)
-    B_rhs, fb, lb = _batch_of(solver, f, load, node_major)
-    mode, B, em = _kappa_layout(E, plan.m, B_rhs, node_major)
-    src = f if f.numel() else load
-    call = _ElasticCall(B, mode, em, B_rhs is not None, node_major, src.device if src.numel() else E.device, E.shape,
-                        E.device, fb, lb)
-    tol, _, amg = _call_options(chain=False, lattice=False, closed_boundary=False, n=setup.dofs.n, mode=mode,
-                                tol_user=solver._tol_user, mg_user=set(), mg={}, amg=solver.amg)
-    solver.tol = tol
-    state = _FacetElasticSolve(solver, setup, call, tol, amg)
-    state.shape = True                  # the adjoint keeps lambda: `facet_grads` reads it
-    state.tab = tab
-    state.data = tuple(None if t.numel() == 0 else
-                       _Datum.of(t, name, tab["n_f"], B, node_major, plan.device, plan.dim if name == "traction" else 0)
-                       for t, name in zip(data, NAMES))
-    if not setup.is_bc_host.any() and not any(z is not None and bool((z.dev > 0).any()) for z in state.data[2:]):
-        warnings.warn("diffhe: the system is singular (a body with no fixed dof and no foundation stiffness > 0: its "
-                      "rigid-body modes are free); the returned values are not a solution", RuntimeWarning)
-    u = _run_call(state, _Inputs(E, f if f.numel() else None, load if load.numel() else None, B, call.batched,
-                                 node_major, call.out_device))
-    solver.last_info = ElasticFacetInfo(**vars(solver.last_info), jacobi_bounds=state.bounds)
-    return u, state
+    """(u, state) of one call with facet data (`data`: the four tensors, empty = absent): the shared call builder, with
+    the facet table, the data as the kernels read them and the singular-system warning set up before the solve."""
+    def prepare(state):
+        plan, setup = state.plan, state.setup
+        state.tab = tab = solver._table(plan)
+        state.data = tuple(None if t.numel() == 0 else
+                           _Datum.of(t, name, tab["n_f"], state.call.B, node_major, plan.device,
+                                     plan.dim if name == "traction" else 0)
+                           for t, name in zip(data, NAMES))
+        if any(z is not None for z in state.data[2:]):
+            state.bounds_error = _BOUNDS_ERROR         # a foundation: the smoother's bounds are measured per call
+        if not setup.is_bc_host.any() and not any(z is not None and bool((z.dev > 0).any()) for z in state.data[2:]):
+            warnings.warn("diffhe: the system is singular (a body with no fixed dof and no foundation stiffness > 0: its "
+                          "rigid-body modes are free); the returned values are not a solution", RuntimeWarning)
+
+    return _solve_call(solver, _FacetElasticSolve, E, f, load, node_major, prepare=prepare)
 
 
 # ---------------------------------------------------------------------------------------------
 # torch.library custom ops diffhe::elastic_facet_solve / diffhe::elastic_facet_solve_backward, next to
-# diffhe::elastic_solve: the solver and the state of the call travel as integer handles through the registries of
-# diffhe.solver.  f / load and the four facet data: empty tensor = absent.
+# diffhe::elastic_solve and on its shared plumbing (diffhe.elastic): the solver and the state of the call travel as integer
+# handles through the registries of diffhe.solver.  f / load and the four facet data: empty tensor = absent.
 # ---------------------------------------------------------------------------------------------
 @torch.library.custom_op("diffhe::elastic_facet_solve", mutates_args=())
 def elastic_facet_solve(E: torch.Tensor, f: torch.Tensor, load: torch.Tensor, traction: torch.Tensor,
@@ -334,15 +298,13 @@ def elastic_facet_solve(E: torch.Tensor, f: torch.Tensor, load: torch.Tensor, tr
                         node_major: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     """(u, token) of the `TractionElasticFESolver` registered under `handle`; arguments as diffhe::elastic_solve, plus the
     facet data in one of the layouts of the module docstring."""
-    u, state = _facet_forward(_SOLVERS[handle], E, f, load, (traction, pressure, k_normal, k_tangent), node_major)
-    return u.clone() if u._base is not None or u.data_ptr() == state.x.data_ptr() else u, _register_state(state, save)
+    return _solve_result(*_facet_forward(_SOLVERS[handle], E, f, load, (traction, pressure, k_normal, k_tangent),
+                                         node_major), save)
 
 
 @elastic_facet_solve.register_fake
 def _elastic_facet_solve_fake(E, f, load, traction, pressure, k_normal, k_tangent, handle, save, node_major):
-    shape = _out_shape(_SOLVERS[handle], E, f, load, node_major)
-    like = f if f.numel() else (load if load.numel() else E)
-    return like.new_empty(shape, dtype=torch.float64), torch.empty((), dtype=torch.int64)
+    return _solve_fake(_SOLVERS[handle], E, f, load, node_major)
 
 
 _Grads7 = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]
@@ -355,12 +317,7 @@ def elastic_facet_solve_backward(gbar: torch.Tensor, token: torch.Tensor, need_e
                                  p_like: torch.Tensor, kn_like: torch.Tensor, kt_like: torch.Tensor) -> _Grads7:
     """The seven gradients of the forward call named by `token` from ONE adjoint solve, each with the device and dtype of
     its `*_like`; unused ones come back empty."""
-    state = _state_of(token)
-    call = state.call
-    g = gbar.detach()
-    if not call.node_major and not call.batched and call.B == 1:
-        g = g.unsqueeze(0)
-    grads = state.adjoint(g, need_e, need_f, need_load)
+    state, grads = _run_adjoint(gbar, token, need_e, need_f, need_load)
     facet_needs = (need_t, need_p, need_kn, need_kt)
     facet = state.facet_grads(facet_needs) if any(facet_needs) else [None] * 4
     return _like_grads(gbar, (*grads, *facet), (e_like, f_like, load_like, t_like, p_like, kn_like, kt_like))
@@ -373,23 +330,9 @@ def _elastic_facet_solve_backward_fake(gbar, token, need_e, need_f, need_load, n
                        (e_like, f_like, load_like, t_like, p_like, kn_like, kt_like))
 
 
-def _setup_context(ctx, inputs, output):
-    _tie_state(ctx, output[1], *inputs[:7])
-
-
-def _backward(ctx, grad_u, _grad_token):
-    if torch.is_grad_enabled():
-        raise NotImplementedError("diffhe: second-order derivatives of an elastic solve with facet data are not "
-                                  "implemented (backward with create_graph=True, diffhe.elastic_facets)")
-    token, *tensors = ctx.saved_tensors[:8]
-    needs = tuple(bool(v) for v in ctx.needs_input_grad[:7])
-    if not any(needs):
-        return (None,) * 10
-    grads = torch.ops.diffhe.elastic_facet_solve_backward(grad_u.contiguous(), token, *needs, *tensors)
-    return (*(g if need else None for g, need in zip(grads, needs)), None, None, None)
-
-
-torch.library.register_autograd("diffhe::elastic_facet_solve", _backward, setup_context=_setup_context)
+_setup_context, _backward = _solve_autograd(
+    "elastic_facet_solve", 7, 10, "diffhe: second-order derivatives of an elastic solve with facet data are not "
+    "implemented (backward with create_graph=True, diffhe.elastic_facets)")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -455,31 +398,18 @@ class TractionElasticFESolver(ElasticFESolver):
         if self.mesh.nodes.requires_grad:
             raise NotImplementedError("diffhe: facet data with moving nodes are not implemented (mesh.nodes requires "
                                       "grad: the normals and areas of a follower load would move with them)")
-        n, d, node = self.mesh.n_nodes, self.mesh.dim, layout == "node"
-        where = next(t.device for t in data if t is not None)      # of u when neither f nor load says it
+        d, node = self.mesh.dim, layout == "node"
         for t, name in zip(data, NAMES):
             if t is not None and (t.is_complex() or t.dim() > (3 if name == "traction" else 2)):
                 raise ValueError(f"{name} must be a real tensor of at most {3 if name == 'traction' else 2} dimensions, "
                                  f"got {tuple(t.shape)} {t.dtype}")
-        f64, load64 = self._checked(f, "f", layout), self._checked(load, "load", layout)
         implied = [b for b in (_implied_batch(t, node, d if name == "traction" else 0) for t, name in zip(data, NAMES))
                    if b is not None]
-        if node:
-            if f64 is None and load64 is None:
-                raise ValueError("layout='node' needs f or load to carry the batch: (n, d, B)")
-            if f64 is not None and load64 is not None and f64.shape != load64.shape:
-                raise ValueError(f"layout='node': f (and load) must be (n, d, B) with one B, got {tuple(f64.shape)} and "
-                                 f"{tuple(load64.shape)}")
-        elif implied and not any(t is not None and t.dim() == 3 for t in (f64, load64)):
-            base = f64 if f64 is not None else torch.zeros((n, d), dtype=torch.float64, device=where)
-            f64 = base.reshape(1, n, d).expand(implied[0], n, d)
-        if eigenstrain is not None:
-            load64 = self._with_eigenstrain_load(eigenstrain, f64, load64, layout)
         E = self._E
-        empty = E.new_empty(0)
-        if f64 is None and load64 is None:
-            f64 = torch.zeros((n, d), dtype=torch.float64, device=where)
-        f_in, load_in = (empty if f64 is None else f64), (empty if load64 is None else load64)
+        # the facet data's device is u's when neither f nor load says it; an eigenstrain alone carries no batch here
+        f_in, load_in, node = self._rhs_inputs(E, f, load, layout, eigenstrain=eigenstrain, eigenstrain_batch=False,
+                                               implied=implied[0] if implied else None,
+                                               where=next(t.device for t in data if t is not None))
         _, B, _ = _kappa_layout(E, self.mesh.n_elements, _batch_of(self, f_in, load_in, node)[0], node)
         for t, name in zip(data, NAMES):                       # the layout errors, before the op
             if t is not None:
@@ -488,6 +418,7 @@ class TractionElasticFESolver(ElasticFESolver):
             for t, name in zip(data[2:], NAMES[2:]):
                 if t is not None and not bool((torch.isfinite(t.detach()) & (t.detach() >= 0)).all()):
                     raise ValueError(f"diffhe: {name} must be finite and >= 0 everywhere (validate=True)")
+        empty = E.new_empty(0)
         d_in = [empty if t is None else t.to(torch.float64) for t in data]
         _SOLVERS[id(self)] = self
         save = torch.is_grad_enabled() and any(t.requires_grad for t in (E, f_in, load_in, *d_in))

@@ -34,11 +34,12 @@ from typing import Tuple
 import torch
 
 from . import _hip
-from .elastic import (ElasticFESolver, _elastic_forward, _out_shape, _stress_adjoint, _stress_call, _stress_forward,
-                      _stress_shapes)
+from .elastic import ElasticFESolver, _ElasticSolve, _run_adjoint, _solve_autograd, _solve_call, _solve_fake, _solve_result
+from .elastic_stress import (_stress_adjoint, _stress_autograd, _stress_call, _stress_fake, _stress_forward,
+                             _stress_outputs, _stress_shapes)
 from .plan import _stream
 from .shape import _check_nodes
-from .solver import _SOLVERS, _fake_grads, _like_grads, _register_state, _state_of, _tie_state
+from .solver import _SOLVERS, _fake_grads, _like_grads
 
 __all__ = ("ShapeElasticFESolver",)
 
@@ -70,6 +71,21 @@ def _stress_node_grad(solver, sigma_bar, vm_bar, u, E, node_major: bool) -> torc
     return grad
 
 
+class _ShapeElasticSolve(_ElasticSolve):
+    """`_ElasticSolve` that also keeps what the node-gradient kernel reads: E (`e_s`) and f (`f_dofs`) as the kernels read
+    them, and the adjoint lambda."""
+    keep_lambda = True
+    e_s = f_dofs = None
+
+    def _operator(self, E):
+        *self.e_s, Bv = self.node_eng.kappa_device(E, self.call.mode, self.call.B, self.Bp, em=self.call.kappa_em)
+        return (*self.setup.assemble(*self.e_s, Bv), Bv)
+
+    def _body_force(self, f):
+        self.f_dofs = super()._body_force(f)
+        return self.f_dofs
+
+
 # ---------------------------------------------------------------------------------------------
 # diffhe::elastic_solve_shape / diffhe::elastic_solve_shape_backward: `diffhe::elastic_solve` with the nodes as an input.
 # ---------------------------------------------------------------------------------------------
@@ -81,15 +97,12 @@ def elastic_solve_shape(E: torch.Tensor, f: torch.Tensor, load: torch.Tensor, no
     from.  The adjoint state is always kept."""
     solver = _SOLVERS[handle]
     _check_nodes(solver.mesh, nodes, nodes_version)
-    u, state = _elastic_forward(solver, E, f, load, node_major, shape=True)
-    return u.clone() if u._base is not None or u.data_ptr() == state.x.data_ptr() else u, _register_state(state, True)
+    return _solve_result(*_solve_call(solver, _ShapeElasticSolve, E, f, load, node_major), True)
 
 
 @elastic_solve_shape.register_fake
 def _elastic_solve_shape_fake(E, f, load, nodes, nodes_version, handle, node_major):
-    shape = _out_shape(_SOLVERS[handle], E, f, load, node_major)
-    like = f if f.numel() else (load if load.numel() else E)
-    return like.new_empty(shape, dtype=torch.float64), torch.empty((), dtype=torch.int64)
+    return _solve_fake(_SOLVERS[handle], E, f, load, node_major)
 
 
 _Grads4 = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]
@@ -101,12 +114,7 @@ def elastic_solve_shape_backward(gbar: torch.Tensor, token: torch.Tensor, need_e
                                  nodes_like: torch.Tensor) -> _Grads4:
     """(dL/dE, dL/df, dL/dload, dL/dX) of the forward call named by `token` from ONE adjoint solve; unused ones come back
     empty.  The first three are `_ElasticSolve.adjoint`'s, unchanged."""
-    state = _state_of(token)
-    call = state.call
-    g = gbar.detach()
-    if not call.node_major and not call.batched and call.B == 1:
-        g = g.unsqueeze(0)
-    grads = state.adjoint(g, need_e, need_f, need_load)
+    state, grads = _run_adjoint(gbar, token, need_e, need_f, need_load)
     gx = _solve_node_grad(state) if need_x else None
     state.lam = None
     return _like_grads(gbar, (*grads, gx), (e_like, f_like, load_like, nodes_like))
@@ -118,24 +126,9 @@ def _elastic_solve_shape_backward_fake(gbar, token, need_e, need_f, need_load, n
     return _fake_grads(gbar, (need_e, need_f, need_load, need_x), (e_like, f_like, load_like, nodes_like))
 
 
-def _solve_setup_context(ctx, inputs, output):
-    E, f, load, nodes = inputs[:4]
-    _tie_state(ctx, output[1], E, f, load, nodes)
-
-
-def _solve_backward(ctx, grad_u, _grad_token):
-    if torch.is_grad_enabled():
-        raise NotImplementedError("diffhe: second-order derivatives of an elastic solve are not implemented (backward with "
-                                  "create_graph=True while mesh.nodes requires grad, diffhe.elastic_shape)")
-    token, E, f, load, nodes = ctx.saved_tensors[:5]
-    needs = tuple(bool(v) for v in ctx.needs_input_grad[:4])
-    if not any(needs):
-        return (None,) * 7
-    grads = torch.ops.diffhe.elastic_solve_shape_backward(grad_u.contiguous(), token, *needs, E, f, load, nodes)
-    return (*(g if need else None for g, need in zip(grads, needs)), None, None, None)
-
-
-torch.library.register_autograd("diffhe::elastic_solve_shape", _solve_backward, setup_context=_solve_setup_context)
+_solve_setup_context, _solve_backward = _solve_autograd(
+    "elastic_solve_shape", 4, 7, "diffhe: second-order derivatives of an elastic solve are not implemented (backward with "
+    "create_graph=True while mesh.nodes requires grad, diffhe.elastic_shape)")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -148,15 +141,12 @@ def elastic_stress_shape(u: torch.Tensor, E: torch.Tensor, nodes: torch.Tensor, 
     at version `nodes_version`); the output not asked for comes back empty."""
     solver = _SOLVERS[handle]
     _check_nodes(solver.mesh, nodes, nodes_version)
-    sigma, vm = _stress_forward(solver, u, E, node_major, want_sigma, want_vm)
-    return (u.new_empty(0) if sigma is None else sigma), (u.new_empty(0) if vm is None else vm)
+    return _stress_outputs(u, *_stress_forward(solver, u, E, node_major, want_sigma, want_vm))
 
 
 @elastic_stress_shape.register_fake
 def _elastic_stress_shape_fake(u, E, nodes, nodes_version, handle, node_major, want_sigma, want_vm):
-    s_shape, v_shape = _stress_shapes(_SOLVERS[handle], u, E, node_major)
-    return (u.new_empty(s_shape if want_sigma else 0, dtype=torch.float64),
-            u.new_empty(v_shape if want_vm else 0, dtype=torch.float64))
+    return _stress_fake(u, _stress_shapes(_SOLVERS[handle], u, E, node_major), want_sigma, want_vm)
 
 
 @torch.library.custom_op("diffhe::elastic_stress_shape_backward", mutates_args=())
@@ -180,32 +170,9 @@ def _elastic_stress_shape_backward_fake(sigma_bar, vm_bar, u, E, nodes, handle, 
     return _fake_grads(u, (need_u, need_e, need_x), (u, E, nodes))
 
 
-def _stress_setup_context(ctx, inputs, output):
-    u, E, nodes, _version, handle, node_major = inputs[:6]
-    ctx.handle, ctx.node_major = handle, bool(node_major)
-    ctx.solver = _SOLVERS[handle]           # the registry holds it weakly: the graph keeps it alive for backward
-    ctx.set_materialize_grads(False)
-    ctx.save_for_backward(u, E, nodes)
-
-
-def _stress_backward(ctx, grad_sigma, grad_vm):
-    if torch.is_grad_enabled():
-        raise NotImplementedError("diffhe: second-order derivatives of an elastic stress evaluation are not implemented "
-                                  "(backward with create_graph=True while mesh.nodes requires grad, diffhe.elastic_shape)")
-    u, E, nodes = ctx.saved_tensors
-    needs = tuple(bool(v) for v in ctx.needs_input_grad[:3])
-    absent = lambda g: g is None or g.numel() == 0  # noqa: E731
-    if not any(needs) or (absent(grad_sigma) and absent(grad_vm)):
-        return (None,) * 8
-    empty = u.new_empty(0)
-    _SOLVERS[ctx.handle] = ctx.solver
-    grads = torch.ops.diffhe.elastic_stress_shape_backward(empty if absent(grad_sigma) else grad_sigma.contiguous(),
-                                                           empty if absent(grad_vm) else grad_vm.contiguous(), u, E, nodes,
-                                                           ctx.handle, ctx.node_major, *needs)
-    return (*(g if need else None for g, need in zip(grads, needs)), None, None, None, None, None)
-
-
-torch.library.register_autograd("diffhe::elastic_stress_shape", _stress_backward, setup_context=_stress_setup_context)
+_stress_setup_context, _stress_backward = _stress_autograd(
+    "elastic_stress_shape", 3, 8, "diffhe: second-order derivatives of an elastic stress evaluation are not implemented "
+    "(backward with create_graph=True while mesh.nodes requires grad, diffhe.elastic_shape)")
 
 
 class ShapeElasticFESolver(ElasticFESolver):

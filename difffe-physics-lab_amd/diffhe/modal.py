@@ -51,7 +51,7 @@ import torch.nn as nn
 
 from . import _hip
 from .eigen import JACOBI_SWEEPS, MAX_BLOCK, EigenInfo, _BlockRun
-from .elastic import _cycle_defaults, _setup_of, lame_unit, parse_fixed
+from .elastic import _amg_options, _check_mesh, _select_hierarchy, _setup_of, lame_unit, parse_fixed
 from .plan import get_plan, padded_batch, _stream
 from .solver import (K_ELEM, K_SAMPLE_ELEM, SolveInfo, _Engine, _SOLVERS, _fake_grads, _kappa_grad, _kappa_mode,
                      _like_grads, _register_state, _resolve_device, _state_of, _tie_state)
@@ -146,15 +146,8 @@ class _ModalRun(_BlockRun):
             add = (ms.shift * self.mass)[:, None, :].expand(plan.n, d, Bvr).reshape(dofs.n, Bvr)
             vals[0] += torch.where(setup.free[:, None], add, torch.zeros_like(add))     # slot 0: the diagonal
         self.vals, self.Bv = vals, Bv
-        sinfo = SolveInfo()
-        self.hier, self.amg = None, dict(ms.amg)
-        if ms.method != "ell-jacobi":
-            levels, stats = setup.levels()
-            if levels:
-                _cycle_defaults(self.amg, dofs.n, Bp)
-                self.hier = self.eng.amg_setup(vals, Bv, bool(self.amg.get("fp32", 0)), levels)
-                sinfo.hierarchy, sinfo.hierarchy_levels, sinfo.operator_complexity = "unit", stats[0], stats[1]
-        sinfo.path = "ell-amgpcg" if self.hier is not None else "ell-pcg"
+        sinfo, self.amg = SolveInfo(), dict(ms.amg)
+        self.hier, _ = _select_hierarchy(self.eng, setup, ms.method, self.amg, vals, Bv, Bp, sinfo)
         info.inner, info.path = sinfo, sinfo.path
         self._apart = self._new(L.diffhe_grad_kappa_blocks(dofs.n, Bp) * Bp)
 
@@ -317,14 +310,10 @@ class ElasticEigenSolver(nn.Module):
                                                                                        else ""))
         if options:
             raise TypeError(f"ElasticEigenSolver got unexpected options: {sorted(options)}")
-        if mesh.dim == 1:
-            raise NotImplementedError("diffhe: vibration modes need a 2D or 3D mesh (a 1D bar is a tridiagonal pencil: "
-                                      "dense-eigh territory)")
-        if mesh.dim not in (2, 3):
-            raise NotImplementedError("Only 2D and 3D meshes supported")
-        if mesh.elements.shape[1] != mesh.dim + 1:
-            raise NotImplementedError("diffhe: vibration modes are implemented for P1 elements only (the row-sum lumped "
-                                      f"mass of a mesh with {mesh.elements.shape[1]} nodes per element is not positive)")
+        _check_mesh(mesh, "diffhe: vibration modes need a 2D or 3D mesh (a 1D bar is a tridiagonal pencil: dense-eigh "
+                    "territory)",
+                    "diffhe: vibration modes are implemented for P1 elements only (the row-sum lumped mass of a mesh with "
+                    "{k} nodes per element is not positive)", dims="Only 2D and 3D meshes supported")
         if mesh.dim == 3 and plane is not None:
             raise ValueError("plane= applies to 2D meshes only (a 3D body needs no plane-stress / plane-strain choice)")
         self.plane = None if mesh.dim == 3 else ("stress" if plane is None else plane)
@@ -349,14 +338,10 @@ class ElasticEigenSolver(nn.Module):
         if not self._is_bc.any() and float(shift) == 0.0:
             raise ValueError("diffhe: a body with no fixed dof needs shift > 0 (K alone is singular there: rigid-body "
                              "modes)")
-        self.amg = dict(n_coarse=16, gamma=None, scale=None, fp32=0, max_iter=20000, smoothed=1)
-        self.amg.update(amg or {})
-        if float(self.amg.get("strength", 0) or 0) > 0.0:
-            raise NotImplementedError("diffhe: amg=dict(strength=...) is not implemented for vibration modes (the "
-                                      "hierarchy is built from the unit-E operator)")
-        if not self.amg.get("smoothed", 1):
-            raise NotImplementedError("diffhe: vibration modes use the smoothed-aggregation hierarchy of elasticity (amg "
-                                      "smoothed=0 is not implemented)")
+        self.amg = _amg_options(amg, "diffhe: amg=dict(strength=...) is not implemented for vibration modes (the hierarchy "
+                                     "is built from the unit-E operator)",
+                                "diffhe: vibration modes use the smoothed-aggregation hierarchy of elasticity (amg "
+                                "smoothed=0 is not implemented)")
         as64 = lambda v: (torch.tensor(float(v), dtype=torch.float64) if isinstance(v, (int, float))  # noqa: E731
                           else v.to(dtype=torch.float64))
         self.mesh, self.method, self.k, self.guard = mesh, method, k, guard

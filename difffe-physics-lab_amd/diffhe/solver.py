@@ -880,6 +880,7 @@ class _PathSolve:
     side or assembly temporary -- and this object is the adjoint state the custom ops hold until the end of backward.
     adjoint(g, need_k, need_f, need_load) -> (lambda in the path's layout, per-sample dL/dkappa sums, per-element
     dL/dkappa as `_kappa_grad` takes them, dL/df and dL/dload per sample in the caller's layout)."""
+    Info = SolveInfo        # the class of `solver.last_info` after a call on this path (`_run_call`)
 
     def __init__(self, solver, plan: SolvePlan, call: _Call, tol: float, mg: dict, amg: dict, homogeneous: bool = False):
         self.solver, self.plan, self.call, self.mg, self.amg = solver, plan, call.facts(), mg, amg
@@ -1244,7 +1245,7 @@ def _begin_call(solver, plan: SolvePlan, call: _Call, path: Optional[type] = Non
 def _run_call(state: _PathSolve, call: _Call) -> torch.Tensor:
     """The forward solve of a call that `_begin_call` set up: u as the caller gets it (a call without a batch loses the
     batch dimension; on f's device), the solver's `last_info`, the warning when a system missed the tolerance."""
-    solver, info = state.solver, SolveInfo()
+    solver, info = state.solver, state.Info()
     u = state.forward(call, info)
     solver.last_info = info
     if info.not_converged:
