@@ -31,9 +31,12 @@ tensor per element and sample in place of (E, nu) and its gradient dL/dC -- lami
 gradients to Poisson's ratio -- with the torch helpers that build and rotate such tensors, also exported here (kernels
 declared in include/diffhe_elastic_aniso.h); `diffhe.elastic_facets`: `TractionElasticFESolver`, `ElasticFESolver` with
 tractions, pressure and an elastic (Winkler) foundation on boundary facets, per facet and sample, and their gradients,
-also exported here (kernels declared in include/diffhe_elastic_facets.h); `diffhe._hip`: the ctypes binding).
+also exported here (kernels declared in include/diffhe_elastic_facets.h); `diffhe.filters`: `DensityFilter`, the
+mesh-independent density filter with a physical radius on the elements of any P1 mesh and its exact adjoint, also exported
+here, and the tanh projection `heaviside` -- the regularisation of a design in front of the solvers (kernels declared in
+include/diffhe_filter.h); `diffhe._hip`: the ctypes binding).
 """
-from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, shape as _shape,
+from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, filters as _filters, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, shape as _shape,
                solver as _solver)
 
 FEMesh = _mesh.FEMesh
@@ -49,8 +52,9 @@ ElasticEigenSolver = _modal.ElasticEigenSolver
 ShapeElasticFESolver = _elastic_shape.ShapeElasticFESolver
 AnisotropicElasticFESolver = _elastic_aniso.AnisotropicElasticFESolver
 TractionElasticFESolver = _elastic_facets.TractionElasticFESolver
+DensityFilter = _filters.DensityFilter
 
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
            "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver", "ElasticEigenSolver",
-           "ShapeElasticFESolver", "AnisotropicElasticFESolver", "TractionElasticFESolver")
+           "ShapeElasticFESolver", "AnisotropicElasticFESolver", "TractionElasticFESolver", "DensityFilter")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

@@ -1,6 +1,6 @@
 """ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h, include/diffhe_stress.h,
 include/diffhe_eigenstrain.h, include/diffhe_modal.h, include/diffhe_elastic_shape.h, include/diffhe_elastic_aniso.h,
-include/diffhe_elastic_facets.h).
+include/diffhe_elastic_facets.h, include/diffhe_filter.h).
 
 The library is built in-tree by `__graft_entry__.build()` /
 `make -C difffe-physics-lab_amd/csrc`.  There is NO fallback: if the library or a
@@ -235,6 +235,16 @@ ELASTIC_FACET_SIGNATURES = {
                                 _PV]),
 }
 
+# name -> (restype, argtypes) of every symbol of include/diffhe_filter.h, the library's ninth header (the density filter
+# on the elements of a P1 mesh and its adjoint, csrc/filter.hip): bound by the same loop (tests/test_density_filter.py
+# holds this table against that header)
+_CELLS = [_PI, _PI, _PI, _I, _I, _I, _D]       # cell_of, order, cell_start, ncx, ncy, ncz, R
+FILTER_SIGNATURES = {
+    "diffhe_filter_count": (_S, [_PD, _I, _I, *_CELLS, _PI, _PV]),
+    "diffhe_filter_fill": (_S, [_PD, _PD, _I, _I, *_CELLS, _I, _PL, _PI, _PD, _PD, _PV]),
+    "diffhe_filter_apply": (_S, [_PD, _PD, _I, _I, _PL, _PI, _PD, _D, _I, _I, _PD, _L, _L, _PD, _L, _L, _I, _PV]),
+}
+
 _lib = None
 
 
@@ -272,7 +282,7 @@ def lib():
         for name, (res, args) in (*SIGNATURES.items(), *ELASTIC_SIGNATURES.items(), *STRESS_SIGNATURES.items(),
                                   *EIGENSTRAIN_SIGNATURES.items(), *MODAL_SIGNATURES.items(),
                                   *ELASTIC_SHAPE_SIGNATURES.items(), *ELASTIC_ANISO_SIGNATURES.items(),
-                                  *ELASTIC_FACET_SIGNATURES.items()):
+                                  *ELASTIC_FACET_SIGNATURES.items(), *FILTER_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = (_I if res is _S else res), args
             if res is _S:
