@@ -34,9 +34,12 @@ tractions, pressure and an elastic (Winkler) foundation on boundary facets, per 
 also exported here (kernels declared in include/diffhe_elastic_facets.h); `diffhe.filters`: `DensityFilter`, the
 mesh-independent density filter with a physical radius on the elements of any P1 mesh and its exact adjoint, also exported
 here, and the tanh projection `heaviside` -- the regularisation of a design in front of the solvers (kernels declared in
-include/diffhe_filter.h); `diffhe._hip`: the ctypes binding).
+include/diffhe_filter.h); `diffhe.sampling`: `PointSampler`, nodal fields sampled at arbitrary points of any P1 mesh, their
+spatial gradient there and the exact transposes -- readings of sensors that do not sit on nodes, and the transfer of a
+field from one mesh to another -- also exported here (kernels declared in include/diffhe_sample.h); `diffhe._hip`: the
+ctypes binding).
 """
-from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, filters as _filters, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, shape as _shape,
+from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, filters as _filters, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, sampling as _sampling, shape as _shape,
                solver as _solver)
 
 FEMesh = _mesh.FEMesh
@@ -53,8 +56,10 @@ ShapeElasticFESolver = _elastic_shape.ShapeElasticFESolver
 AnisotropicElasticFESolver = _elastic_aniso.AnisotropicElasticFESolver
 TractionElasticFESolver = _elastic_facets.TractionElasticFESolver
 DensityFilter = _filters.DensityFilter
+PointSampler = _sampling.PointSampler
 
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
            "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver", "ElasticEigenSolver",
-           "ShapeElasticFESolver", "AnisotropicElasticFESolver", "TractionElasticFESolver", "DensityFilter")
+           "ShapeElasticFESolver", "AnisotropicElasticFESolver", "TractionElasticFESolver", "DensityFilter",
+           "PointSampler")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

@@ -59,6 +59,31 @@ def _element_sizes(P: torch.Tensor) -> torch.Tensor:
     return (a * torch.linalg.cross(b, P[:, 3] - P[:, 0])).sum(1).abs() / 6.0
 
 
+def cell_grid(cent_md: torch.Tensor, min_edge: float):
+    """The uniform grid that bins the m centroids cent_md (m, dim): edge = max(min_edge, extent / c) with c^dim <= m, so
+    the number of cells stays O(m) however small min_edge is; offsets from the minimum, indices clamped at the upper faces.
+    Returns (lo (dim,), edge, [ncx, ncy, ncz], cell_of (m) int32, order (m) int32: the ids sorted by cell and ascending
+    within a cell, cell_start (cells + 1) int32).  Shared with diffhe/sampling.py."""
+    m, dim = cent_md.shape
+    dev = cent_md.device
+    lo = cent_md.min(0).values
+    ext = (cent_md.max(0).values - lo).cpu()
+    c = max(1, int(math.floor(m ** (1.0 / dim) + 1e-9)))
+    edge = max(min_edge, float(ext.max()) / c)
+    nc = [int(min(math.floor(float(e) / edge), c)) + 1 for e in ext] + [1] * (3 - dim)
+    top = torch.tensor(nc[:dim], device=dev) - 1
+    idx = torch.minimum(torch.floor((cent_md - lo) / edge).to(torch.int64), top)
+    cell = idx[:, 0]
+    if dim > 1:
+        cell = cell + nc[0] * idx[:, 1]
+    if dim > 2:
+        cell = cell + nc[0] * nc[1] * idx[:, 2]
+    n_cells = nc[0] * nc[1] * nc[2]
+    cell_sorted, order = torch.sort(cell, stable=True)                 # within a cell: ascending element id
+    cell_start = torch.searchsorted(cell_sorted, torch.arange(n_cells + 1, device=dev)).to(torch.int32)
+    return lo, edge, nc, cell.to(torch.int32), order.to(torch.int32), cell_start
+
+
 def check_field(x, m: int, layout: str) -> torch.Tensor:
     """x as a tensor, after the refusals of a field on m elements: (m,) or (B, m), or (m, B) with layout="node"."""
     if layout not in ("sample", "node"):
@@ -122,24 +147,8 @@ class DensityFilter(nn.Module):
         self._cent = cent_md.t().contiguous()                              # (dim, m)
         self._size = _element_sizes(P).contiguous()
         self._vol = self._size if self.volume_weighted else None
-        # cells: edge = max(R, extent / c) with c^dim <= m, so their number stays O(m) however small R is; offsets from
-        # the minimum, indices clamped at the upper faces
-        lo = cent_md.min(0).values
-        ext = (cent_md.max(0).values - lo).cpu()
-        c = max(1, int(math.floor(m ** (1.0 / dim) + 1e-9)))
-        edge = max(R, float(ext.max()) / c)
-        nc = [int(min(math.floor(float(e) / edge), c)) + 1 for e in ext] + [1] * (3 - dim)
-        top = torch.tensor(nc[:dim], device=dev) - 1
-        idx = torch.minimum(torch.floor((cent_md - lo) / edge).to(torch.int64), top)
-        cell = idx[:, 0]
-        if dim > 1:
-            cell = cell + nc[0] * idx[:, 1]
-        if dim > 2:
-            cell = cell + nc[0] * nc[1] * idx[:, 2]
+        _, _, nc, cell_of, order, cell_start = cell_grid(cent_md, R)
         n_cells = nc[0] * nc[1] * nc[2]
-        cell_sorted, order = torch.sort(cell, stable=True)                 # within a cell: ascending element id
-        cell_start = torch.searchsorted(cell_sorted, torch.arange(n_cells + 1, device=dev)).to(torch.int32)
-        cell_of, order = cell.to(torch.int32), order.to(torch.int32)
         grid = (cell_of, order, cell_start, nc[0], nc[1], nc[2], R)
         st = _stream(dev)
         count = torch.empty(m, dtype=torch.int32, device=dev)

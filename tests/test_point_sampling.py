@@ -1,0 +1,626 @@
+"""Nodal fields sampled at arbitrary points of a P1 mesh, the spatial gradient there and the transposes (diffhe.sampling).
+
+The yardstick is written here, independent of the product (`_brute`): for every point and EVERY element the (dim + 1)
+linear system [1 .. 1; x_0 .. x_dim] lambda = [1; x] is solved by Cramer's rule in numpy longdouble; the element of a point
+is the one whose smallest barycentric coordinate is largest, ties to the lowest id, inside if that coordinate is >= -tol.
+From it the dense (P, n) matrix S of the weights and the dim matrices G_r of d phi_k / d x_r (central: lambda_k is affine in
+x, so G_r is lambda_k(x + e_r) - lambda_k(x) with the same solves) are formed; sampling is `S @ u`, its adjoint `S.T @ g`,
+and likewise for G_r.  The yardstick is itself pinned on the CPU: linear reproduction, unit rows at the nodes.
+
+Tolerances, with their reasons:
+  * element ids: exact, after asserting that the smallest barycentric coordinate of every random point in its element is
+    >= 1e-9 (the points are drawn inside elements with seeds that give a margin >= 1e-5), so that rounding cannot move a
+    point across a facet; no random point is left out.  Nodes, edge midpoints and boundary points lie on shared facets,
+    where either neighbour is a legitimate answer: there the VALUES are compared (a P1 field is continuous);
+  * weights: 1e-12 absolute, they are at most 1 in magnitude;
+  * kernels against the dense products: 1e-12 relative to the largest reference entry, the tolerance
+    tests/test_modal.py and tests/test_density_filter.py give kernels with short fp64 sums; the sums here have at most 4
+    terms per point and, per node, at most the number of incident points times dim;
+  * central differences of the end-to-end misfit: step 1e-5, tolerance 1e-7, the rule in the header of tests/test_robin.py.
+"""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import diffhe
+from diffhe import DifferentiableFESolver, FEMesh, _hip, sampling
+from diffhe.sampling import PointSampler
+from _util import rel_err
+from test_elasticity import _box, _rect
+from test_stress import BY_VALUE, _declarations
+
+T64 = torch.float64
+DEV = "cuda:0"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "diffhe_sample.h")
+LD = np.longdouble
+TOL = 1e-9
+
+MESHES = ("2d", "2d-neg", "3d", "1d", "1d-single", "graded")
+BATCHES = (1, 3, 64, 65, 130)
+N_RANDOM = 203                                  # not a multiple of 64
+
+
+@functools.lru_cache(maxsize=None)
+def _mesh(name):
+    if name == "2d":
+        return _rect(8, 6, 21, x_range=(0.0, 2.0))
+    if name == "2d-neg":
+        return _rect(8, 6, 21, x_range=(-1.0, 1.0))
+    if name == "3d":
+        return _box(3, 3, 3, 22)
+    if name == "graded":                        # x -> x^2: the cell edge is far larger than most elements
+        base = _mesh("2d")
+        X = base.nodes.clone()
+        X[:, 0] = X[:, 0] ** 2
+        return FEMesh(nodes=X, elements=base.elements, dirichlet_nodes={})
+    return FEMesh.line(20 if name == "1d" else 1)
+
+
+def _arrays(name):
+    mesh = _mesh(name)
+    return mesh.nodes.to(T64).numpy().reshape(mesh.n_nodes, -1), mesh.elements.numpy()
+
+
+# ------------------------------------------------------------------------------------------------
+# point sets
+# ------------------------------------------------------------------------------------------------
+def _facet_points(name, lam):
+    """One point on every boundary facet of the mesh, at the barycentric position lam (dim values) within the facet."""
+    X, _ = _arrays(name)
+    fac = _mesh(name).boundary_facets().numpy()
+    return np.einsum("k,fkd->fd", np.asarray(lam, dtype=np.float64), X[fac])
+
+
+def _outward(name):
+    """(mid, direction) of every boundary facet: its midpoint and the unit vector from the owning element's centroid to it."""
+    X, el = _arrays(name)
+    fac = _mesh(name).boundary_facets().numpy()
+    mid = X[fac].mean(axis=1)
+    owner = np.array([np.nonzero([np.isin(f, row).all() for row in el])[0][0] for f in fac])
+    d = mid - X[el[owner]].mean(axis=1)
+    return mid, d / np.linalg.norm(d, axis=1, keepdims=True)
+
+
+@functools.lru_cache(maxsize=None)
+def _points(name, kind):
+    """(P, dim) numpy fp64, read-only."""
+    X, el = _arrays(name)
+    dim = X.shape[1]
+    if kind in ("random", "one"):
+        rng = np.random.default_rng({"random": 100, "one": 7}[kind] + MESHES.index(name))
+        P = N_RANDOM if kind == "random" else 1
+        lam = rng.dirichlet(np.full(dim + 1, 2.0), size=P)          # inside, away from the facets
+        e = rng.integers(0, len(el), size=P)
+        out = np.einsum("pk,pkd->pd", lam, X[el[e]])
+    elif kind == "nodes":
+        out = X.copy()
+    elif kind == "midpoints":
+        edges = np.unique(np.sort(np.concatenate([el[:, [i, j]] for i in range(dim + 1) for j in range(i)]), axis=1), axis=0)
+        out = X[edges].mean(axis=1)
+    elif kind == "boundary":
+        lams = {1: [[1.0]], 2: [[0.5, 0.5], [0.3, 0.7]], 3: [[1 / 3, 1 / 3, 1 / 3], [0.2, 0.3, 0.5]]}[dim]
+        out = np.concatenate([_facet_points(name, lam) for lam in lams])
+    elif kind == "outside":                      # just outside by 1e-6, and far outside
+        mid, d = _outward(name)
+        pick = np.array([0, len(mid) // 3, 2 * len(mid) // 3]) % len(mid)
+        out = np.concatenate([mid[pick] + 1e-6 * d[pick], mid[pick[:2]] + 10.0 * d[pick[:2]], mid[pick[:1]] + 1e6 * d[pick[:1]]])
+    elif kind == "mixed":                        # inside and outside points, interleaved
+        a, b = _points(name, "random")[:37], _points(name, "outside")
+        out = np.concatenate([a[:5], b[:2], a[5:20], b[2:4], a[20:], b[4:]])
+    else:
+        raise KeyError(kind)
+    out = np.ascontiguousarray(out, dtype=np.float64)
+    out.setflags(write=False)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# dense restatement (independent of the product code)
+# ------------------------------------------------------------------------------------------------
+def _det(M):
+    """Determinant of stacked (..., k, k) longdouble matrices by Laplace expansion along the first row."""
+    k = M.shape[-1]
+    if k == 1:
+        return M[..., 0, 0]
+    if k == 2:
+        return M[..., 0, 0] * M[..., 1, 1] - M[..., 0, 1] * M[..., 1, 0]
+    cols = np.arange(k)
+    return sum((-1) ** j * M[..., 0, j] * _det(M[..., 1:, cols != j]) for j in range(k))
+
+
+def _barycentric(X, el, x):
+    """lambda (m, dim + 1) of the point x in every element: Cramer's rule on [1 .. 1; x_0 .. x_dim] lambda = [1; x]."""
+    m, npe = el.shape
+    A = np.empty((m, npe, npe), dtype=LD)
+    A[:, 0, :] = 1
+    A[:, 1:, :] = np.transpose(X[el].astype(LD), (0, 2, 1))
+    rhs = np.concatenate([[LD(1)], x.astype(LD)])
+    det = _det(A)
+    lam = np.empty((m, npe), dtype=LD)
+    for k in range(npe):
+        Ak = A.copy()
+        Ak[:, :, k] = rhs
+        lam[:, k] = _det(Ak) / det
+    return lam
+
+
+@functools.lru_cache(maxsize=None)
+def _brute(name, kind, tol=TOL):
+    """(element (P,), inside (P,), margin (P,), S (P, n), G (dim, P, n)) of the module docstring; read-only fp64."""
+    X, el = _arrays(name)
+    pts = _points(name, kind)
+    (n, dim), P = X.shape, len(pts)
+    element, margin = np.empty(P, dtype=np.int64), np.empty(P)
+    S, G = np.zeros((P, n)), np.zeros((dim, P, n))
+    for p, x in enumerate(pts):
+        lam = _barycentric(X, el, x)
+        worst = lam.min(axis=1)
+        e = int(np.argmax(worst))                 # the first maximum: ties to the lowest id
+        element[p], margin[p] = e, float(worst[e])
+        if worst[e] >= -LD(tol):
+            np.add.at(S[p], el[e], lam[e].astype(np.float64))
+            for r in range(dim):
+                step = np.zeros(dim)
+                step[r] = 1.0
+                np.add.at(G[r, p], el[e], (_barycentric(X, el[e:e + 1], x + step)[0] - lam[e]).astype(np.float64))
+    inside = margin >= -tol
+    element[~inside] = -1
+    out = (element, inside, margin, S, G)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def _rand(shape, seed):
+    return 2 * torch.rand(shape, generator=torch.Generator().manual_seed(seed), dtype=T64) - 1
+
+
+@functools.lru_cache(maxsize=None)
+def _sampler(name, kind, outside="raise"):
+    return PointSampler(_mesh(name), torch.from_numpy(_points(name, kind).copy()), outside=outside, tol=TOL, device=DEV)
+
+
+def _kinds(name):
+    dim = _mesh(name).dim
+    return ["nodes", "boundary"] + (["midpoints"] if dim == 2 else [])
+
+
+# ------------------------------------------------------------------------------------------------
+# CPU
+# ------------------------------------------------------------------------------------------------
+def test_tenth_signature_table_matches_the_tenth_header():
+    decls = _declarations(HEADER)
+    names = ["diffhe_sample_adjoint", "diffhe_sample_apply", "diffhe_sample_locate"]
+    assert sorted(decls) == sorted(_hip.SAMPLE_SIGNATURES) == names
+    others = (_hip.SIGNATURES, _hip.ELASTIC_SIGNATURES, _hip.STRESS_SIGNATURES, _hip.EIGENSTRAIN_SIGNATURES,
+              _hip.MODAL_SIGNATURES, _hip.ELASTIC_SHAPE_SIGNATURES, _hip.ELASTIC_ANISO_SIGNATURES,
+              _hip.ELASTIC_FACET_SIGNATURES, _hip.FILTER_SIGNATURES)
+    assert not any(set(decls) & set(t) for t in others)
+    assert [len(t) for t in others] == [64, 3, 3, 6, 7, 2, 4, 3, 3]
+    for name, (ret, params) in decls.items():
+        res, argtypes = _hip.SAMPLE_SIGNATURES[name]
+        assert len(argtypes) == len(params), name
+        for i, ((ctype, is_ptr), t) in enumerate(zip(params, argtypes)):
+            if not is_ptr:
+                assert t is BY_VALUE[ctype], (name, i, ctype, t)
+            else:
+                assert isinstance(t, type) and issubclass(t, _hip._Ptr) and t.elem == ctype, (name, i, ctype, t)
+        assert ret == "int" and res is _hip._S, name
+    csrc = os.path.join(ROOT, "difffe-physics-lab_amd", "csrc")
+    make = open(os.path.join(csrc, "Makefile")).read()
+    assert "sample.hip" in make.split("SRCS")[1].split("\n")[0] and "diffhe_sample.h" in make
+    assert "atomic" not in open(os.path.join(csrc, "sample.hip")).read().split("#include")[-1]
+    if os.path.exists(_hip.LIB_PATH):
+        L = _hip.lib()
+        for name in decls:
+            fn = getattr(L, name)
+            assert fn.restype is _hip._I and fn.errcheck is L.diffhe_to_node_major.errcheck, name
+        with pytest.raises(_hip.HipExtensionError, match="diffhe_sample_locate"):
+            L.diffhe_sample_locate(None, None, 2, 9, 8, None, None, 1, 1, 1, None, None, None, 4, 1e-9, None, None, None,
+                                   None, None)
+        with pytest.raises(_hip.HipExtensionError, match="diffhe_sample_apply"):
+            L.diffhe_sample_apply(None, 2, 9, None, None, 1, 4, None, 1, 0, 9, None, 1, 0, 0, 4, 1, 1, None)
+        with pytest.raises(_hip.HipExtensionError, match="diffhe_sample_adjoint"):
+            L.diffhe_sample_adjoint(None, None, None, 0, 2, 9, None, 1, 4, None, 1, 0, 0, 4, None, 1, 0, 9, 1, 1, None)
+
+
+def test_constructor_and_field_refusals_need_no_gpu():
+    assert diffhe.PointSampler is PointSampler and "PointSampler" in diffhe.__all__
+    mesh = _mesh("2d")
+    pts = torch.from_numpy(_points("2d", "random").copy())
+    with pytest.raises(NotImplementedError, match="P1"):
+        PointSampler(FEMesh.rectangle_p2(2, 2), pts)
+    moving = FEMesh(nodes=mesh.nodes.clone().requires_grad_(True), elements=mesh.elements, dirichlet_nodes={})
+    with pytest.raises(NotImplementedError, match="mesh.nodes requires grad"):
+        PointSampler(moving, pts)
+    with pytest.raises(NotImplementedError, match="points requires grad"):
+        PointSampler(mesh, pts.clone().requires_grad_(True))
+    for bad in (-1e-9, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="tol"):
+            PointSampler(mesh, pts, tol=bad)
+    with pytest.raises(ValueError, match="Unknown outside"):
+        PointSampler(mesh, pts, outside="clamp")
+    with pytest.raises(ValueError, match="device"):
+        PointSampler(mesh, pts, device="cpu")
+    for bad in (float("nan"), float("inf")):
+        broken = pts.clone()
+        broken[3, 1] = bad
+        with pytest.raises(ValueError, match="finite"):
+            PointSampler(mesh, broken)
+    for shape in ((5,), (5, 3), (5, 1), (0, 2), (2, 5, 2)):
+        with pytest.raises(ValueError, match="dim=2"):
+            PointSampler(mesh, torch.zeros(shape, dtype=T64))
+    with pytest.raises(ValueError, match="dim=1"):
+        PointSampler(FEMesh.line(4), torch.zeros(3, 2, dtype=T64))
+    n, dim = mesh.n_nodes, 2
+    # (shape, has_r, node layout, vector)
+    wrong = [((n + 1,), False, False, False), ((2, n + 1), False, False, False), ((n, 2), False, False, False),
+             ((2, 3, n), False, False, False), ((), False, False, False), ((0, n), False, False, False),
+             ((n,), False, True, False), ((2, n), False, True, False), ((n, 0), False, True, False),
+             ((n,), False, False, True), ((n, 3), False, False, True), ((n, 1), False, False, True),
+             ((2, n, 3), False, False, True), ((n, 2, 4), False, False, True), ((n, 3, 4), False, True, True),
+             ((n, 4), False, True, True), ((n, 3), True, False, False), ((2, n, 2, 3), True, False, True),
+             ((n, 2, 3, 4), True, True, True)]
+    for shape, has_r, node, vector in wrong:
+        with pytest.raises(ValueError, match=f"n={n}"):
+            sampling.field_axes(shape, n, dim, has_r, node, vector, f"n={n}")
+    assert sampling.field_axes((2, n), n, dim, False, False, False, f"n={n}") == ["b", "N"]
+    assert sampling.field_axes((n, 2, 2, 5), n, dim, True, True, True, f"n={n}") == ["N", "c", "r", "b"]
+    assert sampling.field_axes((3, n, 2, 2), n, dim, True, False, True, f"n={n}") == ["b", "N", "c", "r"]
+
+
+@pytest.mark.parametrize("name", MESHES)
+def test_yardstick_reproduces_affine_fields_and_has_unit_rows_at_nodes(name):
+    X, _ = _arrays(name)
+    dim = X.shape[1]
+    for kind in ["random", "one", *_kinds(name)]:
+        element, inside, margin, S, G = _brute(name, kind)
+        pts = _points(name, kind)
+        assert inside.all() and (element >= 0).all()
+        if kind in ("random", "one"):
+            assert margin.min() >= 1e-9, (kind, margin.min())        # the margin the element-id comparison rests on
+            assert len(pts) == (N_RANDOM if kind == "random" else 1) and N_RANDOM % 64 != 0
+        assert np.max(np.abs(S.sum(axis=1) - 1.0)) <= 1e-13
+        assert rel_err(S @ X, pts) <= 1e-13                          # linear reproduction
+        for r in range(dim):
+            assert np.max(np.abs(G[r].sum(axis=1))) <= 1e-13 * np.max(np.abs(G[r]))
+            want = np.zeros((len(pts), dim))
+            want[:, r] = 1.0
+            assert np.max(np.abs(G[r] @ X - want)) <= 1e-13 * max(1.0, np.max(np.abs(G[r])))
+    S = _brute(name, "nodes")[3]
+    assert np.max(np.abs(S - np.eye(len(X)))) <= 1e-13
+    element, inside, margin, S, G = _brute(name, "outside")
+    assert not inside.any() and (element == -1).all() and margin.max() < -20 * TOL and not S.any() and not G.any()
+
+
+# ------------------------------------------------------------------------------------------------
+# GPU
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", MESHES)
+def test_location_equals_the_brute_force_search(name):
+    mesh = _mesh(name)
+    m, n, dim = mesh.n_elements, mesh.n_nodes, mesh.dim
+    for kind in ("random", "one"):
+        element, inside, margin, S, _ = _brute(name, kind)
+        assert margin.min() >= 1e-9
+        s = _sampler(name, kind)
+        P = len(element)
+        assert s.element.dtype == torch.int32 and s.element.shape == (P,)
+        assert np.array_equal(s.element.cpu().numpy(), element)              # every random point
+        assert s.weights.dtype == T64 and s.weights.shape == (P, dim + 1)
+        want = np.take_along_axis(S, mesh.elements.numpy()[element], axis=1)
+        assert np.max(np.abs(s.weights.cpu().numpy() - want)) <= 1e-12
+        assert s.inside.dtype == torch.bool and bool(s.inside.all())
+        info = s.info
+        assert info["points"] == P and info["outside"] == 0 and 1 <= info["cells"] <= 8 * m
+        assert info["touched_nodes"] == int((np.abs(S).sum(axis=0) > 0).sum())
+        assert 1 <= info["candidates_max"] <= m and info["build_seconds"] > 0
+        assert info["table_bytes"] == 4 * P + 8 * P * (dim + 1) ** 2 + 8 * (n + 1) + 4 * P * (dim + 1)
+        print(f"{name} {kind}: cells {info['cells']}, candidates_max {info['candidates_max']} of {m} elements, "
+              f"smallest margin {margin.min():.2e}")
+    # on shared facets either neighbour is legitimate: compare values
+    u = _rand((3, n), 40)
+    for kind in _kinds(name):
+        S = _brute(name, kind)[3]
+        s = _sampler(name, kind)
+        assert s.info["outside"] == 0 and bool(s.inside.all())
+        assert rel_err(s(u.to(DEV)).cpu().numpy(), u.numpy() @ S.T) <= 1e-12, kind
+        g = _rand((3, len(S)), 41)
+        assert rel_err(s.adjoint(g.to(DEV)).cpu().numpy(), g.numpy() @ S) <= 1e-12, kind
+        w = s.weights.cpu().numpy()
+        assert np.max(np.abs(w.sum(axis=1) - 1.0)) <= 1e-12 and w.min() >= -TOL
+
+
+def _layouts(x):
+    """(name, tensor, layout, back) for a CPU field (B, N, ...): every layout the sampler reads in place; `back` brings a
+    result of that layout to (B, N', ...)."""
+    B, N = x.shape[:2]
+    xd = x.to(DEV)
+    to_node, from_node = (lambda t: t.movedim(0, -1).contiguous()), (lambda y: y.movedim(-1, 0))
+    out = [("sample", xd, "sample", lambda y: y), ("node", to_node(xd), "node", from_node)]
+    if B == 1:
+        out.append(("flat", xd[0], "sample", lambda y: y[None]))
+    big = torch.full((B, 2 * N, *x.shape[2:]), float("nan"), dtype=T64, device=DEV)
+    big[:, ::2] = xd
+    out.append(("strided", big[:, ::2], "sample", lambda y: y))
+    bign = torch.full((N, *x.shape[2:], 2 * B), float("nan"), dtype=T64, device=DEV)
+    bign[..., ::2] = to_node(xd)
+    out.append(("strided-node", bign[..., ::2], "node", from_node))
+    return out
+
+
+def _reference(S, G, x, op, vector):
+    """The dense product for a (B, N, ...) numpy field in the sample layout."""
+    x = x if vector else x[:, :, None, ...]
+    if op == "forward":
+        y = np.einsum("pn,bnc->bpc", S, x)
+    elif op == "gradient":
+        y = np.einsum("rpn,bnc->bpcr", G, x)
+    elif op == "adjoint":
+        y = np.einsum("pn,bpc->bnc", S, x)
+    else:
+        y = np.einsum("rpn,bpcr->bnc", G, x)
+    return y if vector else y[:, :, 0, ...]
+
+
+def _input_shape(op, B, n, P, dim, vector):
+    c = (dim,) if vector else ()
+    return {"forward": (B, n, *c), "gradient": (B, n, *c), "adjoint": (B, P, *c), "gradient_adjoint": (B, P, *c, dim)}[op]
+
+
+OPS = ("forward", "gradient", "adjoint", "gradient_adjoint")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", MESHES)
+def test_values_gradients_and_adjoints_match_the_dense_products(name):
+    mesh = _mesh(name)
+    n, dim = mesh.n_nodes, mesh.dim
+    _, _, _, S, G = _brute(name, "random")
+    s, P = _sampler(name, "random"), N_RANDOM
+    worst = 0.0
+    for B in BATCHES:
+        for vector in (False, True):
+            for i, op in enumerate(OPS):
+                x = _rand(_input_shape(op, B, n, P, dim, vector), 10 * B + i)
+                want = _reference(S, G, x.numpy(), op, vector)
+                for lname, xv, layout, back in _layouts(x):
+                    y = getattr(s, op)(xv, layout=layout, vector=vector)
+                    assert y.dtype == T64 and y.is_contiguous() and back(y).shape == want.shape, (op, lname, y.shape)
+                    err = rel_err(back(y).cpu().numpy(), want)
+                    worst = max(worst, err)
+                    assert err <= 1e-12, (op, vector, B, lname, err)
+            # <S u, g> = <u, S^T g>, and for the gradient
+            for fwd, adj in (("forward", "adjoint"), ("gradient", "gradient_adjoint")):
+                u = _rand(_input_shape(fwd, B, n, P, dim, vector), 5 + B)
+                g = _rand(_input_shape(adj, B, n, P, dim, vector), 6 + B)
+                y = getattr(s, fwd)(u.to(DEV), vector=vector).cpu()
+                z = getattr(s, adj)(g.to(DEV), vector=vector).cpu()
+                assert abs(float((y * g).sum() - (u * z).sum())) <= 1e-12 * float(u.norm() * g.norm()) * \
+                    (1.0 if fwd == "forward" else float(np.abs(G).max())), (fwd, B, vector)
+    # nodes that no point touches get exact zeros
+    z = s.adjoint(_rand((3, P), 3).to(DEV))
+    untouched = torch.from_numpy(np.abs(S).sum(axis=0) == 0)
+    assert float(z[:, untouched.to(DEV)].abs().max() if untouched.any() else 0.0) == 0.0
+    # other dtypes and devices are converted first; the result is fp64 on the input's device
+    y = s(_rand((n,), 4).to(torch.float32))
+    assert y.dtype == T64 and y.device.type == "cpu" and y.shape == (P,)
+    print(f"worst relative error {worst:.2e}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", MESHES)
+def test_affine_fields_and_their_gradients_are_reproduced(name):
+    mesh = _mesh(name)
+    X = mesh.nodes.to(T64).reshape(mesh.n_nodes, -1)
+    dim = mesh.dim
+    a = torch.tensor([[0.7, -1.3, 2.1], [-0.4, 0.9, 0.3]], dtype=T64)[:, :dim]       # two affine fields a . x + c
+    c = torch.tensor([0.25, -1.5], dtype=T64)
+    u = (X @ a.t() + c).t().contiguous()                                            # (2, n)
+    for kind in ["random", *_kinds(name)]:
+        s = _sampler(name, kind)
+        pts = torch.from_numpy(_points(name, kind).copy())
+        want = (pts @ a.t() + c).t()
+        scale = float(want.abs().max())
+        assert float((s(u.to(DEV)).cpu() - want).abs().max()) <= 1e-12 * scale, kind
+        grad = s.gradient(u.to(DEV)).cpu()                                          # (2, P, dim)
+        assert grad.shape == (2, len(pts), dim)
+        gscale = float(s.gradient_table.abs().max()) * float(u.abs().max())          # the size of the terms that cancel
+        assert float((grad - a[:, None, :]).abs().max()) <= 1e-12 * max(1.0, gscale), kind
+    # the coordinates themselves as a vector field: the points, and the identity as gradient
+    s = _sampler(name, "random")
+    pts = torch.from_numpy(_points(name, "random").copy())
+    assert float((s(X.to(DEV), vector=True).cpu() - pts).abs().max()) <= 1e-12 * float(pts.abs().max())
+    jac = s.gradient(X.to(DEV), vector=True).cpu()
+    assert float((jac - torch.eye(dim, dtype=T64)).abs().max()) <= 1e-12 * max(1.0, float(s.gradient_table.abs().max()) *
+                                                                              float(X.abs().max()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["2d", "3d", "1d", "graded"])
+def test_bitwise_properties(name):
+    mesh = _mesh(name)
+    n, dim, P = mesh.n_nodes, mesh.dim, N_RANDOM
+    s = _sampler(name, "random")
+    twin = PointSampler(mesh, torch.from_numpy(_points(name, "random").copy()), tol=TOL, device=DEV)
+    assert twin is not s and torch.equal(twin.element, s.element) and torch.equal(twin.weights, s.weights)
+    assert torch.equal(twin.gradient_table, s.gradient_table) and torch.equal(twin.row_ptr, s.row_ptr)
+    assert torch.equal(twin.entries, s.entries)
+    for vector in (False, True):
+        for i, op in enumerate(OPS):
+            x = _rand(_input_shape(op, 130, n, P, dim, vector), 70 + i).to(DEV)
+            run = getattr(s, op)
+            y = run(x, vector=vector)
+            assert torch.equal(y, run(x, vector=vector))                                        # two runs
+            for b in (0, 63, 64, 129):
+                assert torch.equal(y[b], run(x[b], vector=vector))                              # B = 1 against B = 130
+                assert torch.equal(y[b:b + 1], run(x[b:b + 1], vector=vector))
+            assert torch.equal(y[:3], run(x[:3], vector=vector))
+            assert torch.equal(y, run(x.movedim(0, -1).contiguous(), layout="node", vector=vector).movedim(-1, 0))
+            assert torch.equal(y, getattr(twin, op)(x, vector=vector))                          # two samplers
+    # a sampler with few points reads a (B, n) field in place through its strides: the same bits
+    few = PointSampler(mesh, torch.from_numpy(_points(name, "random")[:3].copy()), tol=TOL, device=DEV)
+    u = _rand((130, n), 77).to(DEV)
+    assert torch.equal(few(u), s(u)[:, :3]) and torch.equal(few.gradient(u), s.gradient(u)[:, :3])
+    # ... and its transposes visit the touched nodes alone, if these are few, after zeroing the result: the same bits
+    g, gg = _rand((130, 3), 78).to(DEV), _rand((130, 3, dim), 79).to(DEV)
+    sparse = (few.adjoint(g), few.gradient_adjoint(gg), few.adjoint(g[0]))
+    assert (few._rows is not None) == (few.info["touched_nodes"] <= n // sampling.SPARSE_ROWS) and s._rows is None
+    few._rows = None
+    assert all(torch.equal(a, b) for a, b in zip(sparse, (few.adjoint(g), few.gradient_adjoint(gg), few.adjoint(g[0]))))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["2d", "3d", "1d-single", "graded"])
+def test_outside_points(name):
+    mesh = _mesh(name)
+    n, dim = mesh.n_nodes, mesh.dim
+    pts = torch.from_numpy(_points(name, "mixed").copy())
+    element, inside, _, S, G = _brute(name, "mixed")
+    n_out, first = int((~inside).sum()), int(np.nonzero(~inside)[0][0])
+    assert n_out == 6 and first == 5
+    with pytest.raises(ValueError, match=f"{n_out} of {len(pts)} points lie outside .* first is point {first} "):
+        PointSampler(mesh, pts, tol=TOL, device=DEV)
+    s = _sampler(name, "mixed", "zero")
+    out = torch.from_numpy(~inside)
+    assert np.array_equal(s.element.cpu().numpy(), element) and bool((s.element.cpu()[out] == -1).all())
+    assert np.array_equal(s.inside.cpu().numpy(), inside) and s.info["outside"] == n_out
+    assert float(s.weights.cpu()[out].abs().max()) == 0.0 and float(s.gradient_table.cpu()[out].abs().max()) == 0.0
+    assert s.info["touched_nodes"] == int((np.abs(S).sum(axis=0) > 0).sum())
+    P = len(pts)
+    for B in (1, 3, 65):
+        for vector in (False, True):
+            for i, op in enumerate(OPS):
+                x = _rand(_input_shape(op, B, n, P, dim, vector), 50 + i)
+                want = _reference(S, G, x.numpy(), op, vector)
+                if "adjoint" in op:
+                    x[:, out] = float("nan")                 # what an outside point carries never leaks
+                for lname, xv, layout, back in _layouts(x):
+                    y = back(getattr(s, op)(xv, layout=layout, vector=vector)).cpu()
+                    assert rel_err(y.numpy(), want) <= 1e-12, (op, vector, B, lname)
+                    if "adjoint" not in op:
+                        assert float(y[:, out].abs().max()) == 0.0 and not torch.signbit(y[:, out]).any()
+    # every point outside
+    lone = PointSampler(mesh, torch.from_numpy(_points(name, "outside").copy()), outside="zero", tol=TOL, device=DEV)
+    assert lone.info["outside"] == 6 and lone.info["touched_nodes"] == 0
+    assert float(lone(_rand((3, n), 1).to(DEV)).abs().max()) == 0.0
+    assert float(lone.adjoint(torch.full((3, 6), float("nan"), dtype=T64, device=DEV)).abs().max()) == 0.0
+    # a tolerance that reaches the points just outside takes them in
+    wide = PointSampler(mesh, torch.from_numpy(_points(name, "outside")[:3].copy()), tol=1e-3, device=DEV)
+    assert wide.info["outside"] == 0 and float(wide.weights.min()) < 0.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["1d", "2d", "3d"])
+def test_autograd_first_and_second_order(name):
+    mesh = _mesh(name)
+    n, dim = mesh.n_nodes, mesh.dim
+    _, _, _, S, G = _brute(name, "random")
+    S, G = torch.from_numpy(S.copy()), torch.from_numpy(G.copy())
+    s = _sampler(name, "random")
+    u = _rand((2, n), 8).to(DEV).requires_grad_(True)
+    for fn in (s, s.gradient):
+        assert torch.autograd.gradcheck(fn, (u,))
+        assert torch.autograd.gradgradcheck(fn, (u,))
+    un = _rand((n, dim, 2), 9).to(DEV).requires_grad_(True)
+    assert torch.autograd.gradcheck(lambda t: s(t, layout="node", vector=True), (un,))
+    assert torch.autograd.gradcheck(lambda t: s.gradient(t, layout="node", vector=True), (un,))
+    g = _rand((2, N_RANDOM), 12).to(DEV).requires_grad_(True)
+    assert torch.autograd.gradcheck(s.adjoint, (g,))
+    gg = _rand((2, N_RANDOM, dim), 13).to(DEV).requires_grad_(True)
+    assert torch.autograd.gradcheck(s.gradient_adjoint, (gg,))
+    (grad,) = torch.autograd.grad((s(u) ** 2).sum(), u, create_graph=True)
+    want = 2 * u.detach().cpu() @ S.T @ S
+    assert rel_err(grad.detach().cpu().numpy(), want.numpy()) <= 1e-12
+    r = _rand((2, n), 11)
+    (second,) = torch.autograd.grad((grad * r.to(DEV)).sum(), u)
+    assert rel_err(second.cpu().numpy(), (2 * r @ S.T @ S).numpy()) <= 1e-12
+
+
+@pytest.mark.gpu
+def test_misfit_to_scattered_readings_differentiates_to_kappa_per_element():
+    base = _mesh("2d")
+    mesh = FEMesh(nodes=base.nodes, elements=base.elements,
+                  dirichlet_nodes=dict(FEMesh.rectangle(8, 6, x_range=(0.0, 2.0)).dirichlet_nodes))
+    m, n = mesh.n_elements, mesh.n_nodes
+    pts = torch.from_numpy(_points("2d", "random")[:30].copy())
+    s = PointSampler(mesh, pts, tol=TOL, device=DEV)
+    f = (1.0 + 0.5 * _rand((n,), 14)).to(DEV)
+    data = 0.05 * _rand((30,), 15).to(DEV)
+
+    def misfit(kappa):
+        u = DifferentiableFESolver(mesh, kappa, device=DEV, tol=1e-13)(f)
+        return 0.5 * ((s(u) - data) ** 2).sum()
+
+    kappa = (1.0 + 0.4 * _rand((m,), 16)).to(DEV).requires_grad_(True)
+    (grad,) = torch.autograd.grad(misfit(kappa), kappa)
+    step = 1e-5
+    for k in range(2):
+        d = torch.randn(m, generator=torch.Generator().manual_seed(30 + k), dtype=T64).to(DEV)
+        with torch.no_grad():
+            fd = float(misfit(kappa + step * d) - misfit(kappa - step * d)) / (2 * step)
+        an = float((grad * d).sum())
+        print(f"direction {k}: central difference {fd:.12e}, backward {an:.12e}, |grad|_max {float(grad.abs().max()):.3e}")
+        assert abs(fd - an) <= 1e-7 * max(abs(an), float(grad.abs().max())), (k, fd, an)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("coarse,fine", [(lambda: FEMesh.line(5), lambda: FEMesh.line(20)),
+                                          (lambda: FEMesh.rectangle(4, 3), lambda: FEMesh.rectangle(8, 9)),
+                                          (lambda: FEMesh.box(2, 2, 2), lambda: FEMesh.box(4, 6, 4))],
+                         ids=["1d", "2d", "3d"])
+def test_mesh_transfer_of_an_affine_field_is_exact(coarse, fine):
+    coarse, fine = coarse(), fine()
+    dim = coarse.dim
+    a = torch.tensor([0.7, -1.3, 2.1], dtype=T64)[:dim]
+    Xc, Xf = coarse.nodes.to(T64).reshape(coarse.n_nodes, -1), fine.nodes.to(T64).reshape(fine.n_nodes, -1)
+    s = PointSampler(coarse, Xf, device=DEV)
+    assert s.info["outside"] == 0 and s.info["points"] == fine.n_nodes
+    got = s((Xc @ a + 0.25).to(DEV)).cpu()
+    assert float((got - (Xf @ a + 0.25)).abs().max()) <= 1e-12 * float((Xf @ a + 0.25).abs().max())
+
+
+@pytest.mark.gpu
+def test_call_refusals_and_fake_tensors():
+    s, mesh = _sampler("2d", "random"), _mesh("2d")
+    n, P = mesh.n_nodes, N_RANDOM
+    with pytest.raises(ValueError, match=f"n={n}"):
+        s(torch.zeros(n + 1, dtype=T64))
+    with pytest.raises(ValueError, match=f"n={n}"):
+        s(torch.zeros(n, 3, dtype=T64), vector=True)
+    with pytest.raises(ValueError, match=f"n={n}"):
+        s.gradient(torch.zeros(2, n, dtype=T64), layout="node")
+    with pytest.raises(ValueError, match=f"n={n}"):
+        s.adjoint(torch.zeros(P + 1, dtype=T64))
+    with pytest.raises(ValueError, match=f"P={P}"):
+        s.gradient_adjoint(torch.zeros(2, P, dtype=T64))
+    with pytest.raises(ValueError, match="Unknown layout"):
+        s(torch.zeros(n, dtype=T64), layout="dof")
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    h = id(s)
+    with FakeTensorMode():
+        y = torch.ops.diffhe.point_sample(torch.empty(3, n, dtype=T64), h, False, False, False)
+        yg = torch.ops.diffhe.point_sample(torch.empty(n, 2, 3, dtype=T64), h, True, True, True)
+        z = torch.ops.diffhe.point_sample_adjoint(torch.empty(P, 3, dtype=T64), h, False, True, False)
+        zg = torch.ops.diffhe.point_sample_adjoint(torch.empty(3, P, 2, 2, dtype=T64), h, True, False, True)
+    assert y.shape == (3, P) and yg.shape == (P, 2, 2, 3) and z.shape == (n, 3) and zg.shape == (3, n, 2) and y.dtype == T64
+
+
+@pytest.mark.gpu
+def test_sensor_inversion_example_descends_and_transfers():
+    """examples/sensor_inversion.py in small: the misfit to the scattered readings falls under Adam (a descent method
+    with a small step), and the transfer to the fine mesh returns one value per fine node and experiment."""
+    import importlib.util
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    spec = importlib.util.spec_from_file_location("sensor_inversion", os.path.join(ROOT, "examples", "sensor_inversion.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    first, last, err, transfer = mod.run(n=8, sensors=30, experiments=4, steps=25, device=DEV, verbose=False)
+    print(f"misfit {first:.3e} -> {last:.3e}, h error {err:.3f}, transfer difference {transfer:.2e}")
+    assert last < first and np.isfinite(err) and np.isfinite(transfer)
