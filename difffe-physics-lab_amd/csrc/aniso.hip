@@ -21,11 +21,11 @@
 // this unit holds their form, AnisoForm<DIM>, next to the table and the assembly.
 #include "common.h"
 #include "element_grad.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
 // ---------------------------------------------------------------------------------------
 // Gradient table: the cofactor arithmetic and the degenerate-element rules of tri_integrals / tet_integrals (ell_assemble.hip).
@@ -226,12 +226,10 @@ extern "C" int diffhe_aniso_assemble_rows(const double* gtab, const double* vol,
   if (!diffhe::valid_batch_pad(Bv)) return DIFFHE_E_BATCHPAD;
   const int nc = dim == 2 ? 3 : 6;
   diffhe::account(8.0 * Bv * ((double)W * n + (lift ? n : 0) + (k_se ? (double)nc * m : 0)));  // values, lift, tensor field
-  if (dim == 2)
-    hipLaunchKernelGGL(aniso_assemble_rows_kernel<2>, diffhe::node_grid(n, Bv), dim3(256), 0, (hipStream_t)stream, gtab,
+  diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(aniso_assemble_rows_kernel<D()>, diffhe::node_grid(n, Bv), dim3(256), 0, (hipStream_t)stream, gtab,
                        vol, K, k_sc, k_se, k_sb, ent_ptr, contrib, cols, is_bc, g, vals, lift, n, m, W, Bv);
-  else
-    hipLaunchKernelGGL(aniso_assemble_rows_kernel<3>, diffhe::node_grid(n, Bv), dim3(256), 0, (hipStream_t)stream, gtab,
-                       vol, K, k_sc, k_se, k_sb, ent_ptr, contrib, cols, is_bc, g, vals, lift, n, m, W, Bv);
+  });
   return diffhe::check_launch();
 }
 
@@ -243,11 +241,10 @@ extern "C" int diffhe_aniso_grad(const int* elems, const double* gtab, const dou
   if ((dk_part == nullptr) != (dk_sum == nullptr)) return DIFFHE_E_BADARG;
   const int nc = dim == 2 ? 3 : 6;
   const double bytes = 8.0 * Bp * (2.0 * n + (dk_e ? (double)nc * m : 0));  // lambda and u once per node, dK per element
-  if (dim == 2)
-    return diffhe::launch_element_grad(AnisoForm<2>{elems, gtab, vol, lam, u, g, m}, m, Bp, dk_e, o_sc, o_se, dk_part,
+  return diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    return diffhe::launch_element_grad(AnisoForm<D()>{elems, gtab, vol, lam, u, g, m}, m, Bp, dk_e, o_sc, o_se, dk_part,
                                        dk_sum, bytes, stream);
-  return diffhe::launch_element_grad(AnisoForm<3>{elems, gtab, vol, lam, u, g, m}, m, Bp, dk_e, o_sc, o_se, dk_part,
-                                     dk_sum, bytes, stream);
+  });
 }
 
 extern "C" int diffhe_aniso_grad_shared(const int* elems, const double* gtab, const double* vol, int dim,
@@ -257,9 +254,8 @@ extern "C" int diffhe_aniso_grad_shared(const int* elems, const double* gtab, co
     return DIFFHE_E_BADARG;
   const int nc = dim == 2 ? 3 : 6;
   const double bytes = 8.0 * (Bp * 2.0 * n + (double)nc * m);
-  if (dim == 2)
-    return diffhe::launch_element_grad_shared(AnisoForm<2>{elems, gtab, vol, lam, u, g, m}, m, B, Bp, dk, o_sc, o_se,
+  return diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    return diffhe::launch_element_grad_shared(AnisoForm<D()>{elems, gtab, vol, lam, u, g, m}, m, B, Bp, dk, o_sc, o_se,
                                               bytes, stream);
-  return diffhe::launch_element_grad_shared(AnisoForm<3>{elems, gtab, vol, lam, u, g, m}, m, B, Bp, dk, o_sc, o_se, bytes,
-                                            stream);
+  });
 }

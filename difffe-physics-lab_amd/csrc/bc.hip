@@ -14,26 +14,13 @@
 // restricted to the band (diffhe/plan.py: SolvePlan.dirichlet_band) in a fixed order.  One wave per band row, lanes
 // over samples; no floating-point atomics, so every result is bitwise reproducible.
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
-// LB lanes per row: the batch rounded up to a power of two, at most a wave; rows per wave = 64 / LB.
-inline int lanes_for(int B) {
-  int LB = 1;
-  while (LB < B && LB < kWave) LB <<= 1;
-  return LB;
-}
-
-inline dim3 row_grid(i64 rows, int LB, int B, bool sample_chunks) {
-  const int rpb = 4 * (kWave / LB);
-  i64 gx = (rows + rpb - 1) / rpb;
-  if (gx > 8192) gx = 8192;
-  if (gx < 1) gx = 1;
-  return dim3((unsigned)gx, sample_chunks ? (unsigned)((B + kWave - 1) / kWave) : 1u, 1);
-}
+constexpr int kMaxBlocks = 8192;   // grid.x cap of every kernel here
 
 // sum_q [node q of e is (not) Dirichlet] k0_e[p, q] * v(q): the row p of an element matrix against nodal data
 template <bool DIRICHLET_COLS>
@@ -57,13 +44,11 @@ __global__ __launch_bounds__(256) void bc_lift_kernel(const int* __restrict__ el
                                                       const double* __restrict__ G, i64 gsj, i64 gsb,
                                                       const int* __restrict__ rows, const int* __restrict__ row_ptr,
                                                       const int* __restrict__ row_inc, int n_rows,
-                                                      double* __restrict__ rhs, i64 rsn, i64 rsb, int B, int LB) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rpw = kWave / LB;
-  const int b = blockIdx.y * kWave + lane % LB;
-  const i64 stride = (i64)gridDim.x * 4 * rpw;
+                                                      double* __restrict__ rhs, i64 rsn, i64 rsb, int B, int Bp) {
+  const NodeMap nm = node_map(Bp);
+  const int b = nm.b;
   if (b >= B) return;
-  for (i64 r = ((i64)blockIdx.x * 4 + wave) * rpw + lane / LB; r < n_rows; r += stride) {
+  for (i64 r = nm.node0; r < n_rows; r += nm.stride) {
     double acc = 0.0;
     for (int t = row_ptr[r]; t < row_ptr[r + 1]; ++t) {
       const int code = row_inc[t];
@@ -85,13 +70,11 @@ __global__ __launch_bounds__(256) void bc_grad_kernel(const int* __restrict__ el
                                                       const double* __restrict__ gbar, i64 gsn, i64 gsb,
                                                       double* __restrict__ out, i64 osj, i64 osb,
                                                       const double* __restrict__ G, i64 Gsj, i64 Gsb,
-                                                      double* __restrict__ dots, int B, int LB) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rpw = kWave / LB;
-  const int b = blockIdx.y * kWave + lane % LB;
-  const i64 stride = (i64)gridDim.x * 4 * rpw;
+                                                      double* __restrict__ dots, int B, int Bp) {
+  const NodeMap nm = node_map(Bp);
+  const int b = nm.b;
   if (b >= B) return;
-  for (i64 j = ((i64)blockIdx.x * 4 + wave) * rpw + lane / LB; j < n_d; j += stride) {
+  for (i64 j = nm.node0; j < n_d; j += nm.stride) {
     double acc = 0.0, unit = 0.0;
     for (int t = d_ptr[j]; t < d_ptr[j + 1]; ++t) {
       const int code = d_inc[t];
@@ -109,18 +92,16 @@ __global__ __launch_bounds__(256) void bc_grad_kernel(const int* __restrict__ el
 
 __global__ __launch_bounds__(256) void bc_scatter_kernel(const int* __restrict__ d_idx, int n_d,
                                                          const double* __restrict__ G, i64 gsj, i64 gsb,
-                                                         double* __restrict__ u, i64 usn, i64 usb, int B, int LB) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rpw = kWave / LB;
-  const int b = blockIdx.y * kWave + lane % LB;
-  const i64 stride = (i64)gridDim.x * 4 * rpw;
+                                                         double* __restrict__ u, i64 usn, i64 usb, int B, int Bp) {
+  const NodeMap nm = node_map(Bp);
+  const int b = nm.b;
   if (b >= B) return;
-  for (i64 j = ((i64)blockIdx.x * 4 + wave) * rpw + lane / LB; j < n_d; j += stride)
+  for (i64 j = nm.node0; j < n_d; j += nm.stride)
     u[(i64)d_idx[j] * usn + (i64)b * usb] = G[j * gsj + (i64)b * gsb];
 }
 
-// one group of LB lanes per band element; each lane loops over its samples b = sub, sub + LB, ...  SHARED: the group
-// reduces over the batch with a fixed-order butterfly (as shape_elem_kernel) and lane 0 writes
+// one group of LB lanes per band element (group_map of launch.h); each lane loops over its samples b = sub, sub + LB, ...
+// SHARED: the group reduces over the batch (group_sum) and lane 0 writes
 template <bool SHARED>
 __global__ __launch_bounds__(256) void bc_grad_kappa_kernel(const int* __restrict__ elems, int npe, int m,
                                                             const double* __restrict__ k0,
@@ -129,14 +110,11 @@ __global__ __launch_bounds__(256) void bc_grad_kappa_kernel(const int* __restric
                                                             const double* __restrict__ lam, i64 lsn, i64 lsb,
                                                             const double* __restrict__ G, i64 gsj, i64 gsb,
                                                             double* __restrict__ dk, i64 dse, i64 dsb, int B, int LB) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane % LB, epw = kWave / LB;
-  const i64 stride = (i64)gridDim.x * 4 * epw;
-  // every lane of a group runs the same trip count (same element): the shuffles never leave the group
-  for (i64 r = ((i64)blockIdx.x * 4 + wave) * epw + lane / LB; r < n_be; r += stride) {
+  const GroupMap gm = group_map(LB);
+  for (i64 r = gm.item0; r < n_be; r += gm.stride) {
     const i64 e = band_elems[r];
     double total = 0.0;
-    for (int b = sub; b < B; b += LB) {
+    for (int b = gm.sub; b < B; b += LB) {
       double s = 0.0;
       for (int p = 0; p < npe; ++p) {
         const int node = elems[(i64)p * m + e];
@@ -149,8 +127,8 @@ __global__ __launch_bounds__(256) void bc_grad_kappa_kernel(const int* __restric
         dk[e * dse + (i64)b * dsb] -= s;
     }
     if (SHARED) {
-      for (int off = 1; off < LB; off <<= 1) total += __shfl_xor(total, off);
-      if (sub == 0) dk[e * dse] -= total;
+      group_sum(LB, total);
+      if (gm.sub == 0) dk[e * dse] -= total;
     }
   }
 }
@@ -169,11 +147,10 @@ extern "C" int diffhe_bc_lift(const int* elems, int npe, int m, const double* k0
       gsb < 0 || rsn < 0 || rsb < 0 || (n_rows > 0 && (!rows || !row_ptr || !row_inc)))
     return DIFFHE_E_BADARG;
   if (n_rows == 0) return DIFFHE_OK;
-  const int LB = lanes_for(B);
+  const int Bp = batch_pad(B);
   account(8.0 * (2.0 * n_rows * B));
-  hipLaunchKernelGGL(bc_lift_kernel, row_grid(n_rows, LB, B, true), dim3(256), 0, (hipStream_t)stream, elems, npe, m,
-                     k0, kappa, (i64)kse, (i64)ksb, d_slot, G, (i64)gsj, (i64)gsb, rows, row_ptr, row_inc, n_rows, rhs,
-                     (i64)rsn, (i64)rsb, B, LB);
+  hipLaunchKernelGGL(bc_lift_kernel, node_grid(n_rows, Bp, kMaxBlocks), dim3(256), 0, (hipStream_t)stream, elems, npe, m,
+                     k0, kappa, kse, ksb, d_slot, G, gsj, gsb, rows, row_ptr, row_inc, n_rows, rhs, rsn, rsb, B, Bp);
   return check_launch();
 }
 
@@ -187,11 +164,11 @@ extern "C" int diffhe_bc_grad(const int* elems, int npe, int m, const double* k0
       (n_d > 0 && (!d_idx || !d_ptr || !d_inc)))
     return DIFFHE_E_BADARG;
   if (n_d == 0) return DIFFHE_OK;
-  const int LB = lanes_for(B);
+  const int Bp = batch_pad(B);
   account(8.0 * ((dots ? 3.0 : 2.0) * n_d * B));
-  hipLaunchKernelGGL(bc_grad_kernel, row_grid(n_d, LB, B, true), dim3(256), 0, (hipStream_t)stream, elems, npe, m, k0,
-                     kappa, (i64)kse, (i64)ksb, d_slot, d_idx, d_ptr, d_inc, n_d, lam, (i64)lsn, (i64)lsb, gbar,
-                     (i64)gsn, (i64)gsb, out, (i64)osj, (i64)osb, G, (i64)Gsj, (i64)Gsb, dots, B, LB);
+  hipLaunchKernelGGL(bc_grad_kernel, node_grid(n_d, Bp, kMaxBlocks), dim3(256), 0, (hipStream_t)stream, elems, npe, m, k0,
+                     kappa, kse, ksb, d_slot, d_idx, d_ptr, d_inc, n_d, lam, lsn, lsb, gbar, gsn, gsb, out, osj, osb, G,
+                     Gsj, Gsb, dots, B, Bp);
   return check_launch();
 }
 
@@ -200,10 +177,10 @@ extern "C" int diffhe_bc_scatter(const int* d_idx, int n_d, const double* G, lon
   if (!G || !u || B < 1 || n_d < 0 || gsj < 0 || gsb < 0 || usn < 0 || usb < 0 || (n_d > 0 && !d_idx))
     return DIFFHE_E_BADARG;
   if (n_d == 0) return DIFFHE_OK;
-  const int LB = lanes_for(B);
+  const int Bp = batch_pad(B);
   account(8.0 * (2.0 * n_d * B));
-  hipLaunchKernelGGL(bc_scatter_kernel, row_grid(n_d, LB, B, true), dim3(256), 0, (hipStream_t)stream, d_idx, n_d, G,
-                     (i64)gsj, (i64)gsb, u, (i64)usn, (i64)usb, B, LB);
+  hipLaunchKernelGGL(bc_scatter_kernel, node_grid(n_d, Bp, kMaxBlocks), dim3(256), 0, (hipStream_t)stream, d_idx, n_d, G,
+                     gsj, gsb, u, usn, usb, B, Bp);
   return check_launch();
 }
 
@@ -215,15 +192,12 @@ extern "C" int diffhe_bc_grad_kappa(const int* elems, int npe, int m, const doub
       gsj < 0 || gsb < 0 || dse < 0 || dsb < 0 || (n_be > 0 && !band_elems))
     return DIFFHE_E_BADARG;
   if (n_be == 0) return DIFFHE_OK;
-  const int LB = lanes_for(B);
+  const int LB = group_lanes(B);
   account(8.0 * ((double)n_be * npe * B * 2.0 + (shared ? (double)n_be : 2.0 * n_be * B)));
-  const dim3 grid = row_grid(n_be, LB, B, false);
-  hipStream_t st = (hipStream_t)stream;
-  if (shared)
-    hipLaunchKernelGGL(bc_grad_kappa_kernel<true>, grid, dim3(256), 0, st, elems, npe, m, k0, d_slot, band_elems, n_be,
-                       lam, (i64)lsn, (i64)lsb, G, (i64)gsj, (i64)gsb, dk, (i64)dse, (i64)dsb, B, LB);
-  else
-    hipLaunchKernelGGL(bc_grad_kappa_kernel<false>, grid, dim3(256), 0, st, elems, npe, m, k0, d_slot, band_elems,
-                       n_be, lam, (i64)lsn, (i64)lsb, G, (i64)gsj, (i64)gsb, dk, (i64)dse, (i64)dsb, B, LB);
+  dispatch_bool(shared != 0, [&](auto SHARED) {
+    hipLaunchKernelGGL(bc_grad_kappa_kernel<SHARED()>, dim3(group_grid(n_be, LB, kMaxBlocks)), dim3(256), 0,
+                       (hipStream_t)stream, elems, npe, m, k0, d_slot, band_elems, n_be, lam, lsn, lsb, G, gsj, gsb, dk,
+                       dse, dsb, B, LB);
+  });
   return check_launch();
 }

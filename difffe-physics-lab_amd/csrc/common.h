@@ -39,6 +39,13 @@ DIFFHE_HD inline double pair_update(float& hi, float& lo, double t) {
 
 constexpr int kWave = 64;
 
+// Bp must be a power of two <= 64 or a multiple of 64 (see diffhe_hip.h).
+inline bool valid_batch_pad(int Bp) {
+  if (Bp <= 0) return false;
+  if (Bp <= 64) return (Bp & (Bp - 1)) == 0;
+  return (Bp % 64) == 0;
+}
+
 // grid.x of node_grid below: blocks of 4 waves over the nodes, each wave holding kWave / min(Bp, kWave) nodes
 inline int node_blocks(int n, int Bp, int max_blocks_x = 2048) {
   const int LB = Bp < kWave ? Bp : kWave;
@@ -80,13 +87,6 @@ inline int check(hipError_t e) {
     return DIFFHE_E_LAUNCH;
   }
   return DIFFHE_OK;
-}
-
-// Bp must be a power of two <= 64 or a multiple of 64 (see diffhe_hip.h).
-inline bool valid_batch_pad(int Bp) {
-  if (Bp <= 0) return false;
-  if (Bp <= 64) return (Bp & (Bp - 1)) == 0;
-  return (Bp % 64) == 0;
 }
 
 // Node-major thread mapping shared by every (n, Bp) kernel.

@@ -13,13 +13,13 @@
 // (diffhe.modal, include/diffhe_modal.h).  D is a compile-time constant: no integer division runs in the row loops.
 #include "common.h"
 #include "diffhe_modal.h"
+#include "launch.h"
 
 #include <math.h>
 
 namespace {
 
 using namespace diffhe;
-using i64 = long long;
 
 constexpr int kMaxP = 16;       // largest block
 constexpr int kTile = 4;        // column tile of the Gram pass: 2 x 16 accumulators next to 12 loads per node
@@ -497,9 +497,7 @@ template <class F>
 int with_sample_mass(const double* mass, i64 ms, i64 mb, int d, int n, int Bp, F&& f) {
   if (d < 1 || d > 3 || n % d != 0 || ms < 0 || mb < 0) return DIFFHE_E_BADARG;
   const double bytes = mb ? 8.0 * Bp * (double)(n / d) : 0.0;
-  if (d == 1) return f(SampleMass<1>{mass, ms, mb}, bytes);
-  if (d == 2) return f(SampleMass<2>{mass, ms, mb}, bytes);
-  return f(SampleMass<3>{mass, ms, mb}, bytes);
+  return dispatch_dim<1, 3>(d, [&](auto D) { return f(SampleMass<D()>{mass, ms, mb}, bytes); });
 }
 
 }  // namespace

@@ -15,11 +15,11 @@
 #include "diffhe_eigenstrain.h"
 #include "eigen_field.h"
 #include "element_grad.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
 // ---------------------------------------------------------------------------------------
 // F0[(i, a), b] = sum over the incidence list of node i (codes e * NPE + p, element order) of
@@ -197,12 +197,10 @@ extern "C" int diffhe_eigenstrain_load(const int* inc_ptr, const int* inc, const
   diffhe::account(8.0 * Bp * (double)dim * n + eigen_bytes(components(dim, plane_strain), ze, zb, m, Bp) +
                   modulus_bytes(e_se, e_sb, m, Bp));
   const dim3 grid = diffhe::node_grid(n, Bp);
-  if (dim == 2)
-    hipLaunchKernelGGL(eigen_load_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, inc_ptr, inc, gtab, vol,
-                       field_of<2>(eps0, zc, ze, zb, lam1, mu1, plane_strain), E, e_se, e_sb, n, m, B, Bp, F0);
-  else
-    hipLaunchKernelGGL(eigen_load_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, inc_ptr, inc, gtab, vol,
-                       field_of<3>(eps0, zc, ze, zb, lam1, mu1, plane_strain), E, e_se, e_sb, n, m, B, Bp, F0);
+  diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(eigen_load_kernel<D()>, grid, dim3(256), 0, (hipStream_t)stream, inc_ptr, inc, gtab, vol,
+                       field_of<D()>(eps0, zc, ze, zb, lam1, mu1, plane_strain), E, e_se, e_sb, n, m, B, Bp, F0);
+  });
   return diffhe::check_launch();
 }
 
@@ -220,13 +218,11 @@ extern "C" int diffhe_eigenstrain_load_adjoint(const int* elems, const double* g
   // w once per dof, eps0, d eps0 (which reads E) and dE per element
   const double bytes = 8.0 * Bp * ((double)dim * n + (deps ? (double)nc0 * m : 0.0) + (de_e ? (double)m : 0.0)) +
                        eigen_bytes(nc0, ze, zb, m, Bp) + (deps ? modulus_bytes(e_se, e_sb, m, Bp) : 0.0);
-  if (dim == 2)
-    return diffhe::launch_element_grad(adjoint_form<2>(elems, gtab, vol, lam1, mu1, plane_strain, E, e_se, e_sb, eps0, zc,
-                                                       ze, zb, w, deps, osc, ose, m, B),
+  return diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    return diffhe::launch_element_grad(adjoint_form<D()>(elems, gtab, vol, lam1, mu1, plane_strain, E, e_se, e_sb, eps0,
+                                                         zc, ze, zb, w, deps, osc, ose, m, B),
                                        m, Bp, de_e, 0, Bp, de_part, de_sum, bytes, stream);
-  return diffhe::launch_element_grad(adjoint_form<3>(elems, gtab, vol, lam1, mu1, plane_strain, E, e_se, e_sb, eps0, zc,
-                                                     ze, zb, w, deps, osc, ose, m, B),
-                                     m, Bp, de_e, 0, Bp, de_part, de_sum, bytes, stream);
+  });
 }
 
 extern "C" int diffhe_eigenstrain_load_adjoint_shared(const int* elems, const double* gtab, const double* vol, int dim,
@@ -238,11 +234,9 @@ extern "C" int diffhe_eigenstrain_load_adjoint_shared(const int* elems, const do
     return DIFFHE_E_BADARG;
   // w once per dof, eps0, dE per element; E is not read: dE = vol s0 : sym(W)
   const double bytes = 8.0 * (Bp * (double)dim * n + (double)m) + eigen_bytes(components(dim, plane_strain), ze, zb, m, Bp);
-  if (dim == 2)
-    return diffhe::launch_element_grad_shared(adjoint_form<2>(elems, gtab, vol, lam1, mu1, plane_strain, E, e_se, e_sb,
-                                                              eps0, zc, ze, zb, w, nullptr, 0, 0, m, B),
+  return diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    return diffhe::launch_element_grad_shared(adjoint_form<D()>(elems, gtab, vol, lam1, mu1, plane_strain, E, e_se, e_sb,
+                                                                eps0, zc, ze, zb, w, nullptr, 0, 0, m, B),
                                               m, B, Bp, de, 0, 1, bytes, stream);
-  return diffhe::launch_element_grad_shared(adjoint_form<3>(elems, gtab, vol, lam1, mu1, plane_strain, E, e_se, e_sb, eps0,
-                                                            zc, ze, zb, w, nullptr, 0, 0, m, B),
-                                            m, B, Bp, de, 0, 1, bytes, stream);
+  });
 }

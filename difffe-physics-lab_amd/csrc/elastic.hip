@@ -19,11 +19,11 @@
 #include "common.h"
 #include "diffhe_elastic.h"
 #include "element_grad.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
 // ---------------------------------------------------------------------------------------
 // Block row-gather assembly: one lane owns node i of sample b, walks the node's W slots and builds the d x d block of
@@ -236,12 +236,10 @@ extern "C" int diffhe_elast_assemble_rows(const double* gtab, const double* vol,
   // values, lift, the field
   diffhe::account(8.0 * Bv * ((double)dim * dim * W * n + (lift ? (double)dim * n : 0) + (e_se ? (double)m : 0)));
   const dim3 grid = diffhe::node_grid(n, Bv);
-  if (dim == 2)
-    hipLaunchKernelGGL(elast_assemble_rows_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, gtab, vol, lam1, mu1, E,
+  diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(elast_assemble_rows_kernel<D()>, grid, dim3(256), 0, (hipStream_t)stream, gtab, vol, lam1, mu1, E,
                        e_se, e_sb, ent_ptr, contrib, cols, is_bc, g, vals, lift, n, m, W, Bv);
-  else
-    hipLaunchKernelGGL(elast_assemble_rows_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, gtab, vol, lam1, mu1, E,
-                       e_se, e_sb, ent_ptr, contrib, cols, is_bc, g, vals, lift, n, m, W, Bv);
+  });
   return diffhe::check_launch();
 }
 
@@ -255,12 +253,10 @@ extern "C" int diffhe_elast_grad(const int* elems, const double* gtab, const dou
   const dim3 grid = diffhe::node_grid(m, Bp);
   if ((int)grid.x != diffhe_grad_kappa_blocks(m, Bp)) return DIFFHE_E_BADARG;   // de_part is sized by that entry
   diffhe::account(8.0 * Bp * (2.0 * dim * n + (de_e ? (double)m : 0)));  // lambda and u once per dof, dE per element
-  if (dim == 2)
-    hipLaunchKernelGGL(elast_grad_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, elems, gtab, vol, lam1, mu1, lam, u,
-                       g, m, Bp, de_e, de_part);
-  else
-    hipLaunchKernelGGL(elast_grad_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, elems, gtab, vol, lam1, mu1, lam, u,
-                       g, m, Bp, de_e, de_part);
+  diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(elast_grad_kernel<D()>, grid, dim3(256), 0, (hipStream_t)stream, elems, gtab, vol, lam1, mu1, lam,
+                       u, g, m, Bp, de_e, de_part);
+  });
   if (de_part)
     hipLaunchKernelGGL(diffhe::element_sum_partials_kernel, dim3((Bp + 63) / 64), dim3(256), 0, (hipStream_t)stream,
                        (const double*)de_part, (int)grid.x, Bp, de_sum);
@@ -276,11 +272,9 @@ extern "C" int diffhe_elast_grad_shared(const int* elems, const double* gtab, co
   long long blocks = ((long long)m + 3) / 4;
   if (blocks > 16384) blocks = 16384;
   diffhe::account(8.0 * (Bp * 2.0 * dim * n + (double)m));
-  if (dim == 2)
-    hipLaunchKernelGGL(elast_grad_shared_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, elems,
+  diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(elast_grad_shared_kernel<D()>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, elems,
                        gtab, vol, lam1, mu1, lam, u, g, m, B, Bp, de);
-  else
-    hipLaunchKernelGGL(elast_grad_shared_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, elems,
-                       gtab, vol, lam1, mu1, lam, u, g, m, B, Bp, de);
+  });
   return diffhe::check_launch();
 }

@@ -23,11 +23,11 @@
 #include "common.h"
 #include "diffhe_elastic_aniso.h"
 #include "element_grad.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
 // Voigt index of the unordered pair (a, t): the diagonal first, then (0, 1) in 2D and (1, 2), (0, 2), (0, 1) in 3D
 template <int DIM>
@@ -266,12 +266,10 @@ extern "C" int diffhe_elastc_assemble_rows(const double* gtab, const double* vol
   // values, lift, the tensor field
   diffhe::account(8.0 * Bv * ((double)dim * dim * W * n + (lift ? (double)dim * n : 0) + (c_se ? (double)nt * m : 0)));
   const dim3 grid = diffhe::node_grid(n, Bv);
-  if (dim == 2)
-    hipLaunchKernelGGL(elastc_assemble_rows_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, gtab, vol, C, c_sc, c_se,
+  diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(elastc_assemble_rows_kernel<D()>, grid, dim3(256), 0, (hipStream_t)stream, gtab, vol, C, c_sc, c_se,
                        c_sb, ent_ptr, contrib, cols, is_bc, g, vals, lift, n, m, W, Bv);
-  else
-    hipLaunchKernelGGL(elastc_assemble_rows_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, gtab, vol, C, c_sc, c_se,
-                       c_sb, ent_ptr, contrib, cols, is_bc, g, vals, lift, n, m, W, Bv);
+  });
   return diffhe::check_launch();
 }
 
@@ -283,11 +281,10 @@ extern "C" int diffhe_elastc_grad(const int* elems, const double* gtab, const do
   if ((dc_part == nullptr) != (dc_sum == nullptr)) return DIFFHE_E_BADARG;
   const int nt = dim == 2 ? 6 : 21;
   const double bytes = 8.0 * Bp * (2.0 * dim * n + (dc_e ? (double)nt * m : 0));  // lambda and u once per dof, dC per element
-  if (dim == 2)
-    return diffhe::launch_element_grad(ElastcForm<2>{elems, gtab, vol, lam, u, g, m}, m, Bp, dc_e, o_sc, o_se, dc_part,
+  return diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    return diffhe::launch_element_grad(ElastcForm<D()>{elems, gtab, vol, lam, u, g, m}, m, Bp, dc_e, o_sc, o_se, dc_part,
                                        dc_sum, bytes, stream);
-  return diffhe::launch_element_grad(ElastcForm<3>{elems, gtab, vol, lam, u, g, m}, m, Bp, dc_e, o_sc, o_se, dc_part,
-                                     dc_sum, bytes, stream);
+  });
 }
 
 extern "C" int diffhe_elastc_grad_shared(const int* elems, const double* gtab, const double* vol, int dim,
@@ -297,11 +294,10 @@ extern "C" int diffhe_elastc_grad_shared(const int* elems, const double* gtab, c
     return DIFFHE_E_BADARG;
   const int nt = dim == 2 ? 6 : 21;
   const double bytes = 8.0 * (Bp * 2.0 * dim * n + (double)nt * m);
-  if (dim == 2)
-    return diffhe::launch_element_grad_shared(ElastcForm<2>{elems, gtab, vol, lam, u, g, m}, m, B, Bp, dc, o_sc, o_se,
+  return diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    return diffhe::launch_element_grad_shared(ElastcForm<D()>{elems, gtab, vol, lam, u, g, m}, m, B, Bp, dc, o_sc, o_se,
                                               bytes, stream);
-  return diffhe::launch_element_grad_shared(ElastcForm<3>{elems, gtab, vol, lam, u, g, m}, m, B, Bp, dc, o_sc, o_se,
-                                            bytes, stream);
+  });
 }
 
 extern "C" int diffhe_ell_jacobi_row_bound(const double* vals, const int* cols, int n, int W, int Bv, double* part,

@@ -23,11 +23,13 @@
 // per sample (0: shared): every layout of the Python API is one base pointer and its strides.
 #include "common.h"
 #include "diffhe_elastic_facets.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
+using Datum = Strided<const double>;   // a scalar facet datum as the kernels read it
+using Grad = Strided<double>;          // a scalar facet gradient: a zero sample stride is the sum over the batch
 
 template <int DIM>
 __global__ __launch_bounds__(256) void elastf_table_kernel(const double* __restrict__ coords, const int* __restrict__ fac,
@@ -73,13 +75,6 @@ __global__ __launch_bounds__(256) void elastf_table_kernel(const double* __restr
     for (int k = 0; k < DIM; ++k) normal[(i64)k * nF + F] = size > 0.0 ? sc * nv[k] : 0.0;
   }
 }
-
-// a scalar facet datum as the kernels read it
-struct Datum {
-  const double* v;
-  i64 sf, sb;
-  __device__ double at(i64 F, int b) const { return v[F * sf + (i64)b * sb]; }
-};
 
 // one group of LB lanes per band node; lane -> sample b < Bp
 template <int DIM>
@@ -161,27 +156,16 @@ __global__ __launch_bounds__(256) void elastf_assemble_kernel(
   }
 }
 
-// LB lanes per facet: the batch rounded up to a power of two, at most a wave (as csrc/robin.hip)
-inline int lanes_for(int B) {
-  int LB = 1;
-  while (LB < B && LB < kWave) LB <<= 1;
-  return LB;
-}
-
-// one group of LB lanes per facet, each lane loops over its samples b = sub, sub + LB, ...; an output with a zero
-// sample stride is the sum over the batch: fixed-order butterfly inside the group, lane 0 writes
+// one group of LB lanes per facet (group_map of launch.h), each lane loops over its samples b = sub, sub + LB, ...; an
+// output with a zero sample stride is the sum over the batch: group_sum, lane 0 writes
 template <int DIM>
 __global__ __launch_bounds__(256) void elastf_grad_kernel(
     const int* __restrict__ fac, int nF, const double* __restrict__ area, const double* __restrict__ normal,
     const double* __restrict__ lam, const double* __restrict__ x, const double* __restrict__ g, int B, int Bp,
-    double* __restrict__ dt, i64 dtf, i64 dtc, i64 dtb, double* __restrict__ dp, i64 dpf, i64 dpb,
-    double* __restrict__ dkn, i64 dnf, i64 dnb, double* __restrict__ dkt, i64 dkf, i64 dkb, int LB) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane % LB, fpw = kWave / LB;
-  const i64 stride = (i64)gridDim.x * 4 * fpw;
+    double* __restrict__ dt, i64 dtf, i64 dtc, i64 dtb, Grad dp, Grad dkn, Grad dkt, int LB) {
+  const GroupMap gm = group_map(LB);
   const double inv_dd = 1.0 / (double)(DIM * (DIM + 1)), inv_d = 1.0 / (double)DIM;
-  // every lane of a group runs the same trip count (same facet): the shuffles never leave the group
-  for (i64 F = ((i64)blockIdx.x * 4 + wave) * fpw + lane / LB; F < nF; F += stride) {
+  for (i64 F = gm.item0; F < nF; F += gm.stride) {
     i64 v[DIM];
     double gv[DIM][DIM], nv[DIM];
 #pragma unroll
@@ -195,7 +179,7 @@ __global__ __launch_bounds__(256) void elastf_grad_kernel(
     double tt[DIM], tp = 0.0, tn = 0.0, tk = 0.0;
 #pragma unroll
     for (int a = 0; a < DIM; ++a) tt[a] = 0.0;
-    for (int b = sub; b < B; b += LB) {
+    for (int b = gm.sub; b < B; b += LB) {
       double sl[DIM], su[DIM], lu = 0.0, sln = 0.0, sun = 0.0, lnun = 0.0;
 #pragma unroll
       for (int a = 0; a < DIM; ++a) sl[a] = su[a] = 0.0;
@@ -232,25 +216,19 @@ __global__ __launch_bounds__(256) void elastf_grad_kernel(
           if (dtb) dt[F * dtf + (i64)a * dtc + (i64)b * dtb] = s; else tt[a] += s;
         }
       }
-      if (dp) { if (dpb) dp[F * dpf + (i64)b * dpb] = vp; else tp += vp; }
-      if (dkn) { if (dnb) dkn[F * dnf + (i64)b * dnb] = vn; else tn += vn; }
-      if (dkt) { if (dkb) dkt[F * dkf + (i64)b * dkb] = vk; else tk += vk; }
+      if (dp.v) { if (dp.sb) dp.at(F, b) = vp; else tp += vp; }
+      if (dkn.v) { if (dkn.sb) dkn.at(F, b) = vn; else tn += vn; }
+      if (dkt.v) { if (dkt.sb) dkt.at(F, b) = vk; else tk += vk; }
     }
-    for (int off = 1; off < LB; off <<= 1) {
-#pragma unroll
-      for (int a = 0; a < DIM; ++a) tt[a] += __shfl_xor(tt[a], off);
-      tp += __shfl_xor(tp, off);
-      tn += __shfl_xor(tn, off);
-      tk += __shfl_xor(tk, off);
-    }
-    if (sub == 0) {
+    group_sum(LB, tt, tp, tn, tk);
+    if (gm.sub == 0) {
       if (dt && !dtb) {
 #pragma unroll
         for (int a = 0; a < DIM; ++a) dt[F * dtf + (i64)a * dtc] = tt[a];
       }
-      if (dp && !dpb) dp[F * dpf] = tp;
-      if (dkn && !dnb) dkn[F * dnf] = tn;
-      if (dkt && !dkb) dkt[F * dkf] = tk;
+      if (dp.v && !dp.sb) dp.at(F, 0) = tp;
+      if (dkn.v && !dkn.sb) dkn.at(F, 0) = tn;
+      if (dkt.v && !dkt.sb) dkt.at(F, 0) = tk;
     }
   }
 }
@@ -266,12 +244,10 @@ extern "C" int diffhe_elastf_facet_table(const double* coords, const int* fac, c
   if (bad_facets(fac, dim, nF, area, normal) || !coords || !opp || n < 1) return DIFFHE_E_BADARG;
   int gx = (nF + 255) / 256;
   if (gx > 1024) gx = 1024;
-  if (dim == 2)
-    hipLaunchKernelGGL(elastf_table_kernel<2>, dim3(gx), dim3(256), 0, (hipStream_t)stream, coords, fac, opp, n, nF, area,
-                       normal);
-  else
-    hipLaunchKernelGGL(elastf_table_kernel<3>, dim3(gx), dim3(256), 0, (hipStream_t)stream, coords, fac, opp, n, nF, area,
-                       normal);
+  dispatch_dim<2, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(elastf_table_kernel<D()>, dim3(gx), dim3(256), 0, (hipStream_t)stream, coords, fac, opp, n, nF,
+                       area, normal);
+  });
   return check_launch();
 }
 
@@ -292,16 +268,12 @@ extern "C" int diffhe_elastf_assemble(const int* fac, int d, int nF, const doubl
   if (n_rows == 0 || (!stiff && !t && !p)) return DIFFHE_OK;
   // per band node: its d rows of the right-hand side (read + write) and, with a foundation, d x d entries per facet node
   account(8.0 * n_rows * (2.0 * d * Bp + (stiff ? 2.0 * d * d * d * Bv : 0.0)));
-  const Datum pd{p, (i64)p_sf, (i64)p_sb}, nd{kn, kn ? (i64)kn_sf : 0, kn ? (i64)kn_sb : 0},
-      td{kt, kt ? (i64)kt_sf : 0, kt ? (i64)kt_sb : 0};
-  if (d == 2)
-    hipLaunchKernelGGL(elastf_assemble_kernel<2>, node_grid(n_rows, Bp), dim3(256), 0, (hipStream_t)stream, fac, nF, area,
-                       normal, rows, row_ptr, ent_code, ent_slot, n_rows, is_bc, g, t, (i64)t_sf, (i64)t_sc, (i64)t_sb, pd,
-                       nd, td, vals, rhs, n, Bv, B, Bp);
-  else
-    hipLaunchKernelGGL(elastf_assemble_kernel<3>, node_grid(n_rows, Bp), dim3(256), 0, (hipStream_t)stream, fac, nF, area,
-                       normal, rows, row_ptr, ent_code, ent_slot, n_rows, is_bc, g, t, (i64)t_sf, (i64)t_sc, (i64)t_sb, pd,
-                       nd, td, vals, rhs, n, Bv, B, Bp);
+  const Datum pd{p, p_sf, p_sb}, nd{kn, kn ? kn_sf : 0, kn ? kn_sb : 0}, td{kt, kt ? kt_sf : 0, kt ? kt_sb : 0};
+  dispatch_dim<2, 3>(d, [&](auto D) {
+    hipLaunchKernelGGL(elastf_assemble_kernel<D()>, node_grid(n_rows, Bp), dim3(256), 0, (hipStream_t)stream, fac, nF,
+                       area, normal, rows, row_ptr, ent_code, ent_slot, n_rows, is_bc, g, t, t_sf, t_sc, t_sb, pd, nd, td,
+                       vals, rhs, n, Bv, B, Bp);
+  });
   return check_launch();
 }
 
@@ -314,18 +286,12 @@ extern "C" int diffhe_elastf_grad(const int* fac, int d, int nF, const double* a
       dp_of < 0 || dp_ob < 0 || dkn_of < 0 || dkn_ob < 0 || dkt_of < 0 || dkt_ob < 0)
     return DIFFHE_E_BADARG;
   if (!dt && !dp && !dkn && !dkt) return DIFFHE_OK;
-  const int LB = lanes_for(B);
-  const int fpb = 4 * (kWave / LB);
-  i64 gx = ((i64)nF + fpb - 1) / fpb;
-  if (gx > 8192) gx = 8192;
+  const int LB = group_lanes(B);
   account(8.0 * nF * (2.0 * d * d * B + (double)(d + 3) * B));
-  if (d == 2)
-    hipLaunchKernelGGL(elastf_grad_kernel<2>, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, fac, nF, area, normal,
-                       lam, x, g, B, Bp, dt, (i64)dt_of, (i64)dt_oc, (i64)dt_ob, dp, (i64)dp_of, (i64)dp_ob, dkn,
-                       (i64)dkn_of, (i64)dkn_ob, dkt, (i64)dkt_of, (i64)dkt_ob, LB);
-  else
-    hipLaunchKernelGGL(elastf_grad_kernel<3>, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, fac, nF, area, normal,
-                       lam, x, g, B, Bp, dt, (i64)dt_of, (i64)dt_oc, (i64)dt_ob, dp, (i64)dp_of, (i64)dp_ob, dkn,
-                       (i64)dkn_of, (i64)dkn_ob, dkt, (i64)dkt_of, (i64)dkt_ob, LB);
+  dispatch_dim<2, 3>(d, [&](auto D) {
+    hipLaunchKernelGGL(elastf_grad_kernel<D()>, dim3(group_grid(nF, LB, 8192)), dim3(256), 0, (hipStream_t)stream, fac, nF,
+                       area, normal, lam, x, g, B, Bp, dt, dt_of, dt_oc, dt_ob, Grad{dp, dp_of, dp_ob},
+                       Grad{dkn, dkn_of, dkn_ob}, Grad{dkt, dkt_of, dkt_ob}, LB);
+  });
   return check_launch();
 }

@@ -25,11 +25,11 @@
 #include "diffhe_elastic_shape.h"
 #include "shape_gather.h"
 #include "stress_form.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
 // S(H) = 2 mu1 sym(H) + lam1 tr(H) I
 template <int D>
@@ -41,17 +41,6 @@ __device__ __forceinline__ void unit_stress_tensor(const double (*H)[D], double 
   for (int a = 0; a < D; ++a)
 #pragma unroll
     for (int t = 0; t < D; ++t) S[a][t] = a == t ? fma(2.0 * mu1, H[a][a], lam1 * tr) : mu1 * (H[a][t] + H[t][a]);
-}
-
-// fixed-order butterfly over the LB lanes of a group (LB = 1: nothing to do)
-template <int D>
-__device__ __forceinline__ void group_sum(double (*M)[D], int LB) {
-  for (int off = 1; off < LB; off <<= 1) {
-#pragma unroll
-    for (int k = 0; k < D; ++k)
-#pragma unroll
-      for (int t = 0; t < D; ++t) M[k][t] += __shfl_xor(M[k][t], off);
-  }
 }
 
 // out[p d + k] = scale * sum_t M[k][t] G[p][t], component ci = p d + k written by lane ci % LB of the group
@@ -80,12 +69,9 @@ __global__ __launch_bounds__(256) void elast_shape_elem_kernel(const int* __rest
                                                                const double* __restrict__ f, const double* __restrict__ E,
                                                                i64 ese, i64 esb, double* __restrict__ work) {
   constexpr int NPE = D + 1, NC = NPE * D;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane % LB;                       // sample lane inside this element's group
-  const int epw = kWave / LB;                      // elements per wave
-  const i64 stride = (i64)gridDim.x * 4 * epw;
-  // every lane of a group runs the same trip count (same e): the xor shuffles below never leave the group
-  for (i64 e = ((i64)blockIdx.x * 4 + wave) * epw + lane / LB; e < m; e += stride) {
+  const GroupMap gm = group_map(LB);               // a group of LB lanes per element
+  const int sub = gm.sub;
+  for (i64 e = gm.item0; e < m; e += gm.stride) {
     int v[NPE];
     double G[NPE][D], Hg[D][D];
 #pragma unroll
@@ -158,8 +144,7 @@ __global__ __launch_bounds__(256) void elast_shape_elem_kernel(const int* __rest
           M[k][t] = fma(Ee, s, M[k][t]);
         }
     }
-    group_sum<D>(M, LB);
-    for (int off = 1; off < LB; off <<= 1) q += __shfl_xor(q, off);
+    group_sum(LB, M, q);
 #pragma unroll
     for (int k = 0; k < D; ++k) M[k][k] += q;
     // a degenerate element has a zero row in the table and size 0: every contribution is +-0
@@ -171,11 +156,9 @@ template <int D>
 __global__ __launch_bounds__(256) void stress_shape_elem_kernel(const StressAdjointForm<D, false> form, int m, int B,
                                                                 int Bp, int LB, double* __restrict__ work) {
   constexpr int NPE = D + 1, NC = NPE * D, NV = D * (D + 1) / 2;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane % LB;
-  const int epw = kWave / LB;
-  const i64 stride = (i64)gridDim.x * 4 * epw;
-  for (i64 e = ((i64)blockIdx.x * 4 + wave) * epw + lane / LB; e < m; e += stride) {
+  const GroupMap gm = group_map(LB);
+  const int sub = gm.sub;
+  for (i64 e = gm.item0; e < m; e += gm.stride) {
     typename StressAdjointForm<D, false>::Elem el;
     form.load((int)e, el);
     double N[D][D];
@@ -201,24 +184,13 @@ __global__ __launch_bounds__(256) void stress_shape_elem_kernel(const StressAdjo
 #pragma unroll
           for (int a = 0; a < D; ++a) N[k][t] = fma(H[a][k], P[a][t], N[k][t]);
     }
-    group_sum<D>(N, LB);
+    group_sum(LB, N);
     write_vertices<D>(N, el.G, -1.0, LB, sub, work + e * NC);
   }
 }
 
-// LB = min(next power of two >= B, 64) and the grid of an element pass
-int group_lanes(int B) {
-  int LB = 1;
-  while (LB < B && LB < kWave) LB <<= 1;
-  return LB;
-}
-
-dim3 element_grid(int m, int LB) {
-  const int epb = 4 * (kWave / LB);                 // elements per 256-thread block and trip
-  long long blocks = ((long long)m + epb - 1) / epb;
-  if (blocks > 8192) blocks = 8192;
-  return dim3((unsigned)blocks);
-}
+// the grid of an element pass
+dim3 element_grid(int m, int LB) { return dim3(group_grid(m, LB, 8192)); }
 
 // what both entries refuse: pointers, dim, sizes, the batch, the E strides, the int32 codes e * npe + p
 bool bad_common(const int* elems, const double* gtab, int dim, const double* u, const double* E, i64 e_se, i64 e_sb, int n,
@@ -244,12 +216,10 @@ extern "C" int diffhe_elast_shape_grad(const int* elems, const double* gtab, con
   // algorithmic bytes: u and lambda (and f) once per dof and sample, E, the vertex contributions, the gradient
   account(8.0 * B * (double)dim * n * (f ? 3.0 : 2.0) + modulus_bytes(e_se, e_sb, m, B) + pass_bytes(dim, n, m));
   hipStream_t st = (hipStream_t)stream;
-  if (dim == 2)
-    hipLaunchKernelGGL(elast_shape_elem_kernel<2>, element_grid(m, LB), dim3(256), 0, st, elems, gtab, vol, m, B, Bp, LB,
+  dispatch_dim<2, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(elast_shape_elem_kernel<D()>, element_grid(m, LB), dim3(256), 0, st, elems, gtab, vol, m, B, Bp, LB,
                        lam1, mu1, u, g, lam, f, E, e_se, e_sb, work);
-  else
-    hipLaunchKernelGGL(elast_shape_elem_kernel<3>, element_grid(m, LB), dim3(256), 0, st, elems, gtab, vol, m, B, Bp, LB,
-                       lam1, mu1, u, g, lam, f, E, e_se, e_sb, work);
+  });
   launch_shape_gather(inc_ptr, inc, work, n, dim, grad, st);
   return check_launch();
 }
@@ -281,10 +251,9 @@ extern "C" int diffhe_stress_shape_grad(const int* elems, const double* gtab, in
   account(8.0 * B * ((double)dim * n + (sigma_bar ? (double)nc * m : 0.0) + (vm_bar ? (double)m : 0.0)) +
           modulus_bytes(e_se, e_sb, m, B) + pass_bytes(dim, n, m));
   hipStream_t st = (hipStream_t)stream;
-  if (dim == 2)
-    launch_stress_shape<2>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, sigma_bar, osc, ose, vm_bar, m, B, Bp, work, st);
-  else
-    launch_stress_shape<3>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, sigma_bar, osc, ose, vm_bar, m, B, Bp, work, st);
+  dispatch_dim<2, 3>(dim, [&](auto D) {
+    launch_stress_shape<D()>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, sigma_bar, osc, ose, vm_bar, m, B, Bp, work, st);
+  });
   launch_shape_gather(inc_ptr, inc, work, n, dim, grad, st);
   return check_launch();
 }

@@ -23,11 +23,12 @@
 
 #include "common.h"
 #include "diffhe_filter.h"
+#include "launch.h"
+#include "cell_grid.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
 template <int DIM>
 __device__ inline void load_centroid(const double* __restrict__ cent, int m, i64 e, double* c) {
@@ -57,10 +58,6 @@ __device__ inline double pair_weight(const double* __restrict__ cent, int m, con
   return R - distance<DIM>(ci, cj);
 }
 
-struct Grid {
-  int ncx, ncy, ncz;
-};
-
 // one thread per element, taken in cell order so that a wave scans the same cells
 template <int DIM>
 __global__ __launch_bounds__(256) void filter_count_kernel(const double* __restrict__ cent, int m,
@@ -71,24 +68,14 @@ __global__ __launch_bounds__(256) void filter_count_kernel(const double* __restr
     const int i = order[t];
     double ci[DIM];
     load_centroid<DIM>(cent, m, i, ci);
-    const int c = cell_of[i];
-    const int cx = c % g.ncx, cy = (c / g.ncx) % g.ncy, cz = c / (g.ncx * g.ncy);
-    const int x0 = cx > 0 ? cx - 1 : 0, x1 = cx + 1 < g.ncx ? cx + 1 : g.ncx - 1;
     int cnt = 0;
-    for (int dz = (DIM > 2 ? -1 : 0); dz <= (DIM > 2 ? 1 : 0); ++dz) {
-      const int z = cz + dz;
-      if (z < 0 || z >= g.ncz) continue;
-      for (int dy = (DIM > 1 ? -1 : 0); dy <= (DIM > 1 ? 1 : 0); ++dy) {
-        const int y = cy + dy;
-        if (y < 0 || y >= g.ncy) continue;
-        const i64 base = ((i64)z * g.ncy + y) * g.ncx;      // cells x0 .. x1 of this row are one range of `order`
-        for (int p = cell_start[base + x0]; p < cell_start[base + x1 + 1]; ++p) {
-          double cj[DIM];
-          load_centroid<DIM>(cent, m, order[p], cj);
-          cnt += distance<DIM>(ci, cj) < R ? 1 : 0;
-        }
+    for_each_neighbour_row<DIM>(g, cell_of[i], [&](i64 c0, i64 c1) {
+      for (int p = cell_start[c0]; p < cell_start[c1 + 1]; ++p) {
+        double cj[DIM];
+        load_centroid<DIM>(cent, m, order[p], cj);
+        cnt += distance<DIM>(ci, cj) < R ? 1 : 0;
       }
-    }
+    });
     count[i] = cnt;
   }
 }
@@ -106,25 +93,12 @@ __global__ __launch_bounds__(256) void filter_fill_kernel(const double* __restri
     const int i = order[t];
     double ci[DIM];
     load_centroid<DIM>(cent, m, i, ci);
-    const int c = cell_of[i];
-    const int cx = c % g.ncx, cy = (c / g.ncx) % g.ncy, cz = c / (g.ncx * g.ncy);
     int pos[NR], end[NR], head[NR], nr = 0;
-    for (int dz = (DIM > 2 ? -1 : 0); dz <= (DIM > 2 ? 1 : 0); ++dz) {
-      const int z = cz + dz;
-      if (z < 0 || z >= g.ncz) continue;
-      for (int dy = (DIM > 1 ? -1 : 0); dy <= (DIM > 1 ? 1 : 0); ++dy) {
-        const int y = cy + dy;
-        if (y < 0 || y >= g.ncy) continue;
-        for (int dx = -1; dx <= 1; ++dx) {
-          const int x = cx + dx;
-          if (x < 0 || x >= g.ncx) continue;
-          const i64 cc = ((i64)z * g.ncy + y) * g.ncx + x;
-          pos[nr] = cell_start[cc];
-          end[nr] = cell_start[cc + 1];
-          ++nr;
-        }
-      }
-    }
+    for_each_neighbour_cell<DIM>(g, cell_of[i], [&](i64 cc) {
+      pos[nr] = cell_start[cc];
+      end[nr] = cell_start[cc + 1];
+      ++nr;
+    });
     // head[r]: the next id of run r that lies inside the radius, INT_MAX once the run is exhausted
     auto advance = [&](int r) {
       int p = pos[r], h = INT_MAX;
@@ -238,10 +212,10 @@ __global__ __launch_bounds__(256) void filter_apply_kernel(
   }
 }
 
-bool bad_grid(const double* cent, int dim, int m, const int* cell_of, const int* order, const int* cell_start, int ncx,
-              int ncy, int ncz, double R) {
-  return !cent || !cell_of || !order || !cell_start || dim < 1 || dim > 3 || m < 1 || ncx < 1 || ncy < 1 || ncz < 1 ||
-         (dim < 2 && ncy != 1) || (dim < 3 && ncz != 1) || (i64)ncx * ncy * ncz >= INT_MAX || !(R > 0.0) || !(R < INFINITY);
+bool bad_search(const double* cent, int dim, int m, const int* cell_of, const int* order, const int* cell_start, int ncx,
+                int ncy, int ncz, double R) {
+  return !cent || !cell_of || !order || !cell_start || dim < 1 || dim > 3 || m < 1 || bad_grid(dim, ncx, ncy, ncz) ||
+         !(R > 0.0) || !(R < INFINITY);
 }
 
 inline unsigned element_blocks(int m) {
@@ -249,64 +223,29 @@ inline unsigned element_blocks(int m) {
   return (unsigned)(gx > 65536 ? 65536 : gx);
 }
 
-// the padded batch node_map takes: a power of two below a wave, whole waves above
-inline int padded_batch(int B) {
-  if (B >= kWave) return (B + kWave - 1) / kWave * kWave;
-  int Bp = 1;
-  while (Bp < B) Bp <<= 1;
-  return Bp;
-}
-
 }  // namespace
 
 extern "C" int diffhe_filter_count(const double* cent, int dim, int m, const int* cell_of, const int* order,
                                    const int* cell_start, int ncx, int ncy, int ncz, double R, int* count, void* stream) {
-  if (bad_grid(cent, dim, m, cell_of, order, cell_start, ncx, ncy, ncz, R) || !count) return DIFFHE_E_BADARG;
-  const Grid g{ncx, ncy, ncz};
-  const dim3 grid(element_blocks(m)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (dim == 1)
-    hipLaunchKernelGGL(filter_count_kernel<1>, grid, block, 0, st, cent, m, cell_of, order, cell_start, g, R, count);
-  else if (dim == 2)
-    hipLaunchKernelGGL(filter_count_kernel<2>, grid, block, 0, st, cent, m, cell_of, order, cell_start, g, R, count);
-  else
-    hipLaunchKernelGGL(filter_count_kernel<3>, grid, block, 0, st, cent, m, cell_of, order, cell_start, g, R, count);
+  if (bad_search(cent, dim, m, cell_of, order, cell_start, ncx, ncy, ncz, R) || !count) return DIFFHE_E_BADARG;
+  dispatch_dim<1, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(filter_count_kernel<D()>, dim3(element_blocks(m)), dim3(256), 0, (hipStream_t)stream, cent, m,
+                       cell_of, order, cell_start, Grid{ncx, ncy, ncz}, R, count);
+  });
   return check_launch();
 }
 
 extern "C" int diffhe_filter_fill(const double* cent, const double* vol, int dim, int m, const int* cell_of,
                                   const int* order, const int* cell_start, int ncx, int ncy, int ncz, double R, int weight,
                                   const long long* row_ptr, int* nbr, double* S, double* inv_S, void* stream) {
-  if (bad_grid(cent, dim, m, cell_of, order, cell_start, ncx, ncy, ncz, R) || !row_ptr || !nbr || !S || !inv_S ||
+  if (bad_search(cent, dim, m, cell_of, order, cell_start, ncx, ncy, ncz, R) || !row_ptr || !nbr || !S || !inv_S ||
       (weight != 0 && weight != 1))
     return DIFFHE_E_BADARG;
-  const Grid g{ncx, ncy, ncz};
-  const dim3 grid(element_blocks(m)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (dim == 1)
-    hipLaunchKernelGGL(filter_fill_kernel<1>, grid, block, 0, st, cent, vol, m, cell_of, order, cell_start, g, R, weight,
-                       row_ptr, nbr, S, inv_S);
-  else if (dim == 2)
-    hipLaunchKernelGGL(filter_fill_kernel<2>, grid, block, 0, st, cent, vol, m, cell_of, order, cell_start, g, R, weight,
-                       row_ptr, nbr, S, inv_S);
-  else
-    hipLaunchKernelGGL(filter_fill_kernel<3>, grid, block, 0, st, cent, vol, m, cell_of, order, cell_start, g, R, weight,
-                       row_ptr, nbr, S, inv_S);
+  dispatch_dim<1, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(filter_fill_kernel<D()>, dim3(element_blocks(m)), dim3(256), 0, (hipStream_t)stream, cent, vol, m,
+                       cell_of, order, cell_start, Grid{ncx, ncy, ncz}, R, weight, row_ptr, nbr, S, inv_S);
+  });
   return check_launch();
-}
-
-template <int DIM>
-static void launch_apply(const double* cent, int m, const long long* row_ptr, const int* nbr, const double* pre,
-                         const double* post, double R, int weight, const double* x, i64 xse, i64 xsb, double* y, i64 yse,
-                         i64 ysb, int B, hipStream_t st) {
-  const int Bp = padded_batch(B);
-  const dim3 grid = diffhe::node_grid(m, Bp, 65536);
-  if (Bp >= diffhe::kWave)
-    hipLaunchKernelGGL((filter_apply_kernel<DIM, true>), grid, dim3(256), 0, st, cent, m, row_ptr, nbr, pre, post, R,
-                       weight, x, xse, xsb, y, yse, ysb, B, Bp);
-  else
-    hipLaunchKernelGGL((filter_apply_kernel<DIM, false>), grid, dim3(256), 0, st, cent, m, row_ptr, nbr, pre, post, R,
-                       weight, x, xse, xsb, y, yse, ysb, B, Bp);
 }
 
 extern "C" int diffhe_filter_apply(const double* cent, const double* vol, int dim, int m, const long long* row_ptr,
@@ -315,17 +254,17 @@ extern "C" int diffhe_filter_apply(const double* cent, const double* vol, int di
                                    void* stream) {
   if (!cent || !row_ptr || !nbr || !inv_S || !x || !y || x == y || dim < 1 || dim > 3 || m < 1 || !(R > 0.0) ||
       !(R < INFINITY) || (weight != 0 && weight != 1) || (adjoint != 0 && adjoint != 1) || B < 1 || x_se < 0 || x_sb < 0 ||
-      y_se < 0 || y_sb < 0 || (B + diffhe::kWave - 1) / diffhe::kWave > 65535)
+      y_se < 0 || y_sb < 0 || (B + kWave - 1) / kWave > 65535)
     return DIFFHE_E_BADARG;
   const double* pre = adjoint ? inv_S : vol;
   const double* post = adjoint ? vol : inv_S;
-  diffhe::account(16.0 * m * B);
-  hipStream_t st = (hipStream_t)stream;
-  if (dim == 1)
-    launch_apply<1>(cent, m, row_ptr, nbr, pre, post, R, weight, x, x_se, x_sb, y, y_se, y_sb, B, st);
-  else if (dim == 2)
-    launch_apply<2>(cent, m, row_ptr, nbr, pre, post, R, weight, x, x_se, x_sb, y, y_se, y_sb, B, st);
-  else
-    launch_apply<3>(cent, m, row_ptr, nbr, pre, post, R, weight, x, x_se, x_sb, y, y_se, y_sb, B, st);
-  return diffhe::check_launch();
+  account(16.0 * m * B);
+  const int Bp = batch_pad(B);
+  dispatch_dim<1, 3>(dim, [&](auto D) {
+    dispatch_bool(Bp >= kWave, [&](auto WAVE) {
+      hipLaunchKernelGGL((filter_apply_kernel<D(), WAVE()>), node_grid(m, Bp, 65536), dim3(256), 0, (hipStream_t)stream,
+                         cent, m, row_ptr, nbr, pre, post, R, weight, x, x_se, x_sb, y, y_se, y_sb, B, Bp);
+    });
+  });
+  return check_launch();
 }

@@ -8,11 +8,11 @@
 #include "common.h"
 #include "diffhe_modal.h"
 #include "element_grad.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
 // ---------------------------------------------------------------------------------------
 // mass[i, b] = sum over the incidence list of node i (codes e * NPE + p, element order) of rho[e, b] vol_e / NPE.
@@ -100,12 +100,10 @@ extern "C" int diffhe_modal_mass(const int* inc_ptr, const int* inc, const doubl
   if (r_se < 0 || r_sb < 0) return DIFFHE_E_BADARG;   // Bv == 1: the one sample is b = 0, r_sb multiplies nothing
   if (!valid_batch_pad(Bv)) return DIFFHE_E_BATCHPAD;
   account(8.0 * Bv * ((double)n + (r_se ? (double)m : 0)));
-  if (dim == 2)
-    hipLaunchKernelGGL(modal_mass_kernel<3>, node_grid(n, Bv), dim3(256), 0, (hipStream_t)stream, inc_ptr, inc, vol, rho,
-                       r_se, r_sb, n, B, Bv, mass);
-  else
-    hipLaunchKernelGGL(modal_mass_kernel<4>, node_grid(n, Bv), dim3(256), 0, (hipStream_t)stream, inc_ptr, inc, vol, rho,
-                       r_se, r_sb, n, B, Bv, mass);
+  dispatch_dim<2, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(modal_mass_kernel<D() + 1>, node_grid(n, Bv), dim3(256), 0, (hipStream_t)stream, inc_ptr, inc, vol,
+                       rho, r_se, r_sb, n, B, Bv, mass);
+  });
   return check_launch();
 }
 
@@ -116,18 +114,17 @@ extern "C" int diffhe_modal_grad_rho(const int* elems, const double* vol, int di
   if (!dr_e && !dr_part) return DIFFHE_E_BADARG;
   if ((dr_part == nullptr) != (dr_sum == nullptr)) return DIFFHE_E_BADARG;
   const double bytes = 8.0 * Bp * ((double)k * dim * n + k + (dr_e ? (double)m : 0));
-  if (dim == 2)
-    return launch_element_grad(GradRhoForm<2>{elems, vol, X, w, k, n, m, B}, m, Bp, dr_e, 0, Bp, dr_part, dr_sum, bytes,
+  return dispatch_dim<2, 3>(dim, [&](auto D) {
+    return launch_element_grad(GradRhoForm<D()>{elems, vol, X, w, k, n, m, B}, m, Bp, dr_e, 0, Bp, dr_part, dr_sum, bytes,
                                stream);
-  return launch_element_grad(GradRhoForm<3>{elems, vol, X, w, k, n, m, B}, m, Bp, dr_e, 0, Bp, dr_part, dr_sum, bytes,
-                             stream);
+  });
 }
 
 extern "C" int diffhe_modal_grad_rho_shared(const int* elems, const double* vol, int dim, const double* X, const double* w,
                                             int k, int n, int m, int B, int Bp, double* dr, void* stream) {
   if (bad_grad(elems, vol, dim, X, w, k, n, m, B, Bp) || !dr) return DIFFHE_E_BADARG;
   const double bytes = 8.0 * (Bp * ((double)k * dim * n + k) + (double)m);
-  if (dim == 2)
-    return launch_element_grad_shared(GradRhoForm<2>{elems, vol, X, w, k, n, m, B}, m, B, Bp, dr, 0, 1, bytes, stream);
-  return launch_element_grad_shared(GradRhoForm<3>{elems, vol, X, w, k, n, m, B}, m, B, Bp, dr, 0, 1, bytes, stream);
+  return dispatch_dim<2, 3>(dim, [&](auto D) {
+    return launch_element_grad_shared(GradRhoForm<D()>{elems, vol, X, w, k, n, m, B}, m, B, Bp, dr, 0, 1, bytes, stream);
+  });
 }

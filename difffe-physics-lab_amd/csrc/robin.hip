@@ -20,11 +20,13 @@
 // facet and a stride per sample (0: shared), so every layout of the Python API -- (), (B,), (n_F,), (B, n_F), (n_F, B) --
 // is one base pointer and two strides.
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
+using Datum = Strided<const double>;   // h, uinf or q as the kernels read it
+using Grad = Strided<double>;          // dL/dh, dL/duinf or dL/dq: a zero sample stride is the sum over the batch
 
 constexpr int kSumChunk = 128;   // facets per block of the first summation stage
 
@@ -62,9 +64,8 @@ __global__ __launch_bounds__(256) void facet_table_kernel(const double* __restri
 __global__ __launch_bounds__(256) void robin_assemble_kernel(
     const int* __restrict__ fac, int d, int nF, const double* __restrict__ area, const int* __restrict__ rows,
     const int* __restrict__ row_ptr, const int* __restrict__ ent_code, const int* __restrict__ ent_slot, int n_rows,
-    const double* __restrict__ g, const double* __restrict__ h, i64 hsf, i64 hsb, const double* __restrict__ uinf,
-    i64 usf, i64 usb, const double* __restrict__ q, i64 qsf, i64 qsb, double* __restrict__ vals,
-    double* __restrict__ rhs, int n, int Bv, int B, int Bp) {
+    const double* __restrict__ g, Datum h, Datum uinf, Datum q, double* __restrict__ vals, double* __restrict__ rhs,
+    int n, int Bv, int B, int Bp) {
   const NodeMap nm = node_map(Bp);
   const int b = nm.b;
   if (b >= Bp) return;
@@ -78,15 +79,15 @@ __global__ __launch_bounds__(256) void robin_assemble_kernel(
       const i64 F = code >> 4;
       const int p = (code >> 2) & 3, c = code & 3;
       const double a = area[F];
-      const double hv = h ? ((real || hsb == 0) ? h[F * hsf + (i64)b * hsb] : 1.0) : 0.0;
+      const double hv = h.v ? ((real || h.sb == 0) ? h.at(F, b) : 1.0) : 0.0;
       const double mv = hv * (a * (p == c ? 2.0 : 1.0) * inv_dd);
       if (slot < 0)                                          // Dirichlet column: lifted with its value
         load -= mv * g[fac[(i64)c * nF + F]];
       else if (b < Bv)
         vals[((i64)slot * n + i) * Bv + b] += mv;
       if (p == c && real) {                                  // once per (facet, row): the facet load
-        const double uv = uinf ? uinf[F * usf + (i64)b * usb] : 0.0;
-        const double qv = q ? q[F * qsf + (i64)b * qsb] : 0.0;
+        const double uv = uinf.v ? uinf.at(F, b) : 0.0;
+        const double qv = q.v ? q.at(F, b) : 0.0;
         load += (hv * uv + qv) * (a * inv_d);
       }
     }
@@ -94,26 +95,15 @@ __global__ __launch_bounds__(256) void robin_assemble_kernel(
   }
 }
 
-// LB lanes per facet: the batch rounded up to a power of two, at most a wave (as csrc/bc.hip)
-inline int lanes_for(int B) {
-  int LB = 1;
-  while (LB < B && LB < kWave) LB <<= 1;
-  return LB;
-}
-
-// one group of LB lanes per facet, each lane loops over its samples b = sub, sub + LB, ...; an output with a zero
-// sample stride is the sum over the batch: fixed-order butterfly inside the group, lane 0 writes
+// one group of LB lanes per facet (group_map of launch.h), each lane loops over its samples b = sub, sub + LB, ...; an
+// output with a zero sample stride is the sum over the batch: group_sum, lane 0 writes
 __global__ __launch_bounds__(256) void robin_grad_kernel(
     const int* __restrict__ fac, int d, int nF, const double* __restrict__ area, const double* __restrict__ lam,
-    const double* __restrict__ u, const double* __restrict__ g, int B, int Bp, const double* __restrict__ h, i64 hsf,
-    i64 hsb, const double* __restrict__ uinf, i64 usf, i64 usb, double* __restrict__ dh, i64 dhf, i64 dhb,
-    double* __restrict__ du, i64 duf, i64 dub, double* __restrict__ dq, i64 dqf, i64 dqb, int LB) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane % LB, fpw = kWave / LB;
-  const i64 stride = (i64)gridDim.x * 4 * fpw;
+    const double* __restrict__ u, const double* __restrict__ g, int B, int Bp, Datum h, Datum uinf, Grad dh, Grad du,
+    Grad dq, int LB) {
+  const GroupMap gm = group_map(LB);
   const double inv_dd = 1.0 / (double)(d * (d + 1)), inv_d = 1.0 / (double)d;
-  // every lane of a group runs the same trip count (same facet): the shuffles never leave the group
-  for (i64 F = ((i64)blockIdx.x * 4 + wave) * fpw + lane / LB; F < nF; F += stride) {
+  for (i64 F = gm.item0; F < nF; F += gm.stride) {
     int v[3];
     double gv[3];
     for (int p = 0; p < d; ++p) {
@@ -122,7 +112,7 @@ __global__ __launch_bounds__(256) void robin_grad_kernel(
     }
     const double a = area[F];
     double th = 0.0, tu = 0.0, tq = 0.0;
-    for (int b = sub; b < B; b += LB) {
+    for (int b = gm.sub; b < B; b += LB) {
       double le[3], ue[3], sl = 0.0, su = 0.0, lu = 0.0;
       for (int p = 0; p < d; ++p) {
         const i64 o = (i64)v[p] * Bp + b;
@@ -134,22 +124,18 @@ __global__ __launch_bounds__(256) void robin_grad_kernel(
       }
       const double s = sl * (a * inv_d);
       const double lmu = (sl * su + lu) * (a * inv_dd);       // lambda^T M_F u, M_F = |F| (1 1^T + I) / (d (d + 1))
-      const double hv = h ? h[F * hsf + (i64)b * hsb] : 0.0;
-      const double uv = uinf ? uinf[F * usf + (i64)b * usb] : 0.0;
+      const double hv = h.v ? h.at(F, b) : 0.0;
+      const double uv = uinf.v ? uinf.at(F, b) : 0.0;
       const double vh = uv * s - lmu, vu = hv * s;
-      if (dh) { if (dhb) dh[F * dhf + (i64)b * dhb] = vh; else th += vh; }
-      if (du) { if (dub) du[F * duf + (i64)b * dub] = vu; else tu += vu; }
-      if (dq) { if (dqb) dq[F * dqf + (i64)b * dqb] = s; else tq += s; }
+      if (dh.v) { if (dh.sb) dh.at(F, b) = vh; else th += vh; }
+      if (du.v) { if (du.sb) du.at(F, b) = vu; else tu += vu; }
+      if (dq.v) { if (dq.sb) dq.at(F, b) = s; else tq += s; }
     }
-    for (int off = 1; off < LB; off <<= 1) {
-      th += __shfl_xor(th, off);
-      tu += __shfl_xor(tu, off);
-      tq += __shfl_xor(tq, off);
-    }
-    if (sub == 0) {
-      if (dh && !dhb) dh[F * dhf] = th;
-      if (du && !dub) du[F * duf] = tu;
-      if (dq && !dqb) dq[F * dqf] = tq;
+    group_sum(LB, th, tu, tq);
+    if (gm.sub == 0) {
+      if (dh.v && !dh.sb) dh.at(F, 0) = th;
+      if (du.v && !du.sb) du.at(F, 0) = tu;
+      if (dq.v && !dq.sb) dq.at(F, 0) = tq;
     }
   }
 }
@@ -194,8 +180,8 @@ extern "C" int diffhe_robin_assemble(const int* fac, int d, int nF, const double
   if (n_rows == 0) return DIFFHE_OK;
   account(8.0 * n_rows * ((double)d * Bv + 2.0 * Bp));
   hipLaunchKernelGGL(robin_assemble_kernel, node_grid(n_rows, Bp), dim3(256), 0, (hipStream_t)stream, fac, d, nF, area,
-                     rows, row_ptr, ent_code, ent_slot, n_rows, g, h, (i64)hsf, (i64)hsb, uinf, (i64)usf, (i64)usb, q,
-                     (i64)qsf, (i64)qsb, vals, rhs, n, Bv, B, Bp);
+                     rows, row_ptr, ent_code, ent_slot, n_rows, g, Datum{h, hsf, hsb}, Datum{uinf, usf, usb},
+                     Datum{q, qsf, qsb}, vals, rhs, n, Bv, B, Bp);
   return check_launch();
 }
 
@@ -208,14 +194,11 @@ extern "C" int diffhe_robin_grad(const int* fac, int d, int nF, const double* ar
       dhf < 0 || dhb < 0 || duf < 0 || dub < 0 || dqf < 0 || dqb < 0)
     return DIFFHE_E_BADARG;
   if (!dh && !du && !dq) return DIFFHE_OK;
-  const int LB = lanes_for(B);
-  const int fpb = 4 * (kWave / LB);
-  i64 gx = ((i64)nF + fpb - 1) / fpb;
-  if (gx > 8192) gx = 8192;
+  const int LB = group_lanes(B);
   account(8.0 * nF * (2.0 * d * B + 3.0 * B));
-  hipLaunchKernelGGL(robin_grad_kernel, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, fac, d, nF, area, lam, u,
-                     g, B, Bp, h, (i64)hsf, (i64)hsb, uinf, (i64)usf, (i64)usb, dh, (i64)dhf, (i64)dhb, du, (i64)duf,
-                     (i64)dub, dq, (i64)dqf, (i64)dqb, LB);
+  hipLaunchKernelGGL(robin_grad_kernel, dim3(group_grid(nF, LB, 8192)), dim3(256), 0, (hipStream_t)stream, fac, d, nF,
+                     area, lam, u, g, B, Bp, Datum{h, hsf, hsb}, Datum{uinf, usf, usb}, Grad{dh, dhf, dhb},
+                     Grad{du, duf, dub}, Grad{dq, dqf, dqb}, LB);
   return check_launch();
 }
 

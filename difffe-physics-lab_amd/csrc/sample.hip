@@ -21,11 +21,12 @@
 
 #include "common.h"
 #include "diffhe_sample.h"
+#include "launch.h"
+#include "cell_grid.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
 // G[r][k - 1] = det * d phi_k / d x_r for k = 1 .. DIM (the cofactors of the edge matrix) and det, from the edge vectors
 // E[k - 1][r] = x_k[r] - x_0[r]
@@ -99,10 +100,6 @@ __device__ inline double barycentric(const double* __restrict__ X, const int* __
   return mn;                                                   // a degenerate element gives NaN: never chosen below
 }
 
-struct Grid {
-  int ncx, ncy, ncz;
-};
-
 // one thread per point, taken in cell order so that a wave scans the same cells
 template <int DIM>
 __global__ __launch_bounds__(256) void sample_locate_kernel(const double* __restrict__ X, const int* __restrict__ el,
@@ -120,29 +117,20 @@ __global__ __launch_bounds__(256) void sample_locate_kernel(const double* __rest
     for (int a = 0; a < DIM; ++a) x[a] = pts[(i64)p * DIM + a];
     int c = pcell[p];
     c = c < 0 ? 0 : (c >= n_cells ? n_cells - 1 : c);          // the point's cell, clamped into the grid
-    const int cx = c % g.ncx, cy = (c / g.ncx) % g.ncy, cz = c / (g.ncx * g.ncy);
-    const int x0 = cx > 0 ? cx - 1 : 0, x1 = cx + 1 < g.ncx ? cx + 1 : g.ncx - 1;
     int best = -1, cnt = 0;
     double best_min = -INFINITY;
-    for (int dz = (DIM > 2 ? -1 : 0); dz <= (DIM > 2 ? 1 : 0); ++dz) {
-      const int z = cz + dz;
-      if (z < 0 || z >= g.ncz) continue;
-      for (int dy = (DIM > 1 ? -1 : 0); dy <= (DIM > 1 ? 1 : 0); ++dy) {
-        const int y = cy + dy;
-        if (y < 0 || y >= g.ncy) continue;
-        const i64 base = ((i64)z * g.ncy + y) * g.ncx;        // cells x0 .. x1 of this row are one range of `order`
-        for (int q = cell_start[base + x0]; q < cell_start[base + x1 + 1]; ++q) {
-          const int e = order[q];
-          double lam[DIM + 1];
-          const double mn = barycentric<DIM, false>(X, el, e, x, lam, nullptr);
-          ++cnt;
-          if (mn > best_min || (mn == best_min && e < best)) {
-            best = e;
-            best_min = mn;
-          }
+    for_each_neighbour_row<DIM>(g, c, [&](i64 c0, i64 c1) {
+      for (int q = cell_start[c0]; q < cell_start[c1 + 1]; ++q) {
+        const int e = order[q];
+        double lam[DIM + 1];
+        const double mn = barycentric<DIM, false>(X, el, e, x, lam, nullptr);
+        ++cnt;
+        if (mn > best_min || (mn == best_min && e < best)) {
+          best = e;
+          best_min = mn;
         }
       }
-    }
+    });
     const bool in = best >= 0 && best_min >= -tol;
     double best_lam[DIM + 1] = {}, best_grad[DIM][DIM + 1] = {};
     if (in) barycentric<DIM, true>(X, el, best, x, best_lam, best_grad);    // the same chain again: the same bits
@@ -235,14 +223,6 @@ inline unsigned point_blocks(int P) {
   return (unsigned)(gx > 65536 ? 65536 : gx);
 }
 
-// the padded batch node_map takes: a power of two below a wave, whole waves above
-inline int padded_batch(int B) {
-  if (B >= kWave) return (B + kWave - 1) / kWave * kWave;
-  int Bp = 1;
-  while (Bp < B) Bp <<= 1;
-  return Bp;
-}
-
 inline bool bad_batch(int dim, int R, int C, int B) {
   return dim < 1 || dim > 3 || (R != 1 && R != dim) || C < 1 || C > 3 || B < 1 || (B + kWave - 1) / kWave > 65535;
 }
@@ -252,31 +232,10 @@ inline bool overlap(const double* a, i64 a_last, const double* b, i64 b_last) {
   return a <= b + b_last && b <= a + a_last;
 }
 
-template <int DIM>
-void launch_apply(const int* el, const int* element, const double* W, int R, int P, const double* u, i64 usn, i64 usc,
-                  i64 usb, double* y, i64 ysp, i64 ysr, i64 ysc, i64 ysb, int C, int B, hipStream_t st) {
-  const int Bp = padded_batch(B);
-  const dim3 grid = node_grid(P, Bp, 65536);
-  if (Bp >= kWave)
-    hipLaunchKernelGGL((sample_apply_kernel<DIM, true>), grid, dim3(256), 0, st, el, element, W, R, P, u, usn, usc, usb, y,
-                       ysp, ysr, ysc, ysb, C, B, Bp);
-  else
-    hipLaunchKernelGGL((sample_apply_kernel<DIM, false>), grid, dim3(256), 0, st, el, element, W, R, P, u, usn, usc, usb,
-                       y, ysp, ysr, ysc, ysb, C, B, Bp);
-}
-
-template <int DIM>
-void launch_adjoint(const i64* row_ptr, const int* entries, const int* rows, int count, const double* W, int R,
-                    const double* g, i64 gsp, i64 gsr, i64 gsc, i64 gsb, double* out, i64 osn, i64 osc, i64 osb, int C, int B,
-                    hipStream_t st) {
-  const int Bp = padded_batch(B);
-  const dim3 grid = node_grid(count, Bp, 65536);
-  if (Bp >= kWave)
-    hipLaunchKernelGGL((sample_adjoint_kernel<DIM, true>), grid, dim3(256), 0, st, row_ptr, entries, rows, count, W, R, g,
-                       gsp, gsr, gsc, gsb, out, osn, osc, osb, C, B, Bp);
-  else
-    hipLaunchKernelGGL((sample_adjoint_kernel<DIM, false>), grid, dim3(256), 0, st, row_ptr, entries, rows, count, W, R, g,
-                       gsp, gsr, gsc, gsb, out, osn, osc, osb, C, B, Bp);
+// f(D, WAVE) for the dimension and for whether the padded batch Bp fills whole waves
+template <class F>
+void dispatch_apply(int dim, int Bp, F&& f) {
+  dispatch_dim<1, 3>(dim, [&](auto D) { dispatch_bool(Bp >= kWave, [&](auto WAVE) { f(D, WAVE); }); });
 }
 
 }  // namespace
@@ -286,25 +245,16 @@ extern "C" int diffhe_sample_locate(const double* X, const int* el, int dim, int
                                     const int* porder, int P, double tol, int* element, double* weights, double* gtab,
                                     int* tested, void* stream) {
   if (!X || !el || !order || !cell_start || !pts || !pcell || !porder || !element || !weights || !gtab || !tested ||
-      weights == gtab || element == tested || dim < 1 || dim > 3 || n < 2 || m < 1 || P < 1 || ncx < 1 || ncy < 1 ||
-      ncz < 1 || (dim < 2 && ncy != 1) || (dim < 3 && ncz != 1) || (i64)ncx * ncy * ncz >= INT_MAX || !(tol >= 0.0) ||
-      !(tol < INFINITY))
+      weights == gtab || element == tested || dim < 1 || dim > 3 || n < 2 || m < 1 || P < 1 ||
+      bad_grid(dim, ncx, ncy, ncz) || !(tol >= 0.0) || !(tol < INFINITY))
     return DIFFHE_E_BADARG;
-  const Grid g{ncx, ncy, ncz};
-  const dim3 grid(point_blocks(P)), block(256);
-  hipStream_t st = (hipStream_t)stream;
   // the points and the three tables of a point; the candidates are shared by the points of a cell
-  diffhe::account((8.0 * dim + 8.0 + 4.0 + 4.0 + 8.0 * (dim + 1) * (dim + 1)) * P);
-  if (dim == 1)
-    hipLaunchKernelGGL(sample_locate_kernel<1>, grid, block, 0, st, X, el, order, cell_start, g, pts, pcell, porder, P,
-                       tol, element, weights, gtab, tested);
-  else if (dim == 2)
-    hipLaunchKernelGGL(sample_locate_kernel<2>, grid, block, 0, st, X, el, order, cell_start, g, pts, pcell, porder, P,
-                       tol, element, weights, gtab, tested);
-  else
-    hipLaunchKernelGGL(sample_locate_kernel<3>, grid, block, 0, st, X, el, order, cell_start, g, pts, pcell, porder, P,
-                       tol, element, weights, gtab, tested);
-  return diffhe::check_launch();
+  account((8.0 * dim + 8.0 + 4.0 + 4.0 + 8.0 * (dim + 1) * (dim + 1)) * P);
+  dispatch_dim<1, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(sample_locate_kernel<D()>, dim3(point_blocks(P)), dim3(256), 0, (hipStream_t)stream, X, el, order,
+                       cell_start, Grid{ncx, ncy, ncz}, pts, pcell, porder, P, tol, element, weights, gtab, tested);
+  });
+  return check_launch();
 }
 
 extern "C" int diffhe_sample_apply(const int* el, int dim, int n, const int* element, const double* W, int R, int P,
@@ -317,15 +267,13 @@ extern "C" int diffhe_sample_apply(const int* el, int dim, int n, const int* ele
               (P - 1) * y_sp + (R - 1) * y_sr + (C - 1) * y_sc + (B - 1) * y_sb))
     return DIFFHE_E_BADARG;
   // per point, component and sample: dim + 1 values read, R written
-  diffhe::account(8.0 * P * C * B * (dim + 1 + R));
-  hipStream_t st = (hipStream_t)stream;
-  if (dim == 1)
-    launch_apply<1>(el, element, W, R, P, u, u_sn, u_sc, u_sb, y, y_sp, y_sr, y_sc, y_sb, C, B, st);
-  else if (dim == 2)
-    launch_apply<2>(el, element, W, R, P, u, u_sn, u_sc, u_sb, y, y_sp, y_sr, y_sc, y_sb, C, B, st);
-  else
-    launch_apply<3>(el, element, W, R, P, u, u_sn, u_sc, u_sb, y, y_sp, y_sr, y_sc, y_sb, C, B, st);
-  return diffhe::check_launch();
+  account(8.0 * P * C * B * (dim + 1 + R));
+  const int Bp = batch_pad(B);
+  dispatch_apply(dim, Bp, [&](auto D, auto WAVE) {
+    hipLaunchKernelGGL((sample_apply_kernel<D(), WAVE()>), node_grid(P, Bp, 65536), dim3(256), 0, (hipStream_t)stream, el,
+                       element, W, R, P, u, u_sn, u_sc, u_sb, y, y_sp, y_sr, y_sc, y_sb, C, B, Bp);
+  });
+  return check_launch();
 }
 
 extern "C" int diffhe_sample_adjoint(const long long* row_ptr, const int* entries, const int* rows, int n_rows, int dim,
@@ -339,13 +287,12 @@ extern "C" int diffhe_sample_adjoint(const long long* row_ptr, const int* entrie
     return DIFFHE_E_BADARG;
   const int count = rows ? n_rows : n;
   // the point data read once per vertex slot, every visited nodal entry written once
-  diffhe::account(8.0 * C * B * ((double)P * R * (dim + 1) + count));
-  hipStream_t st = (hipStream_t)stream;
-  if (dim == 1)
-    launch_adjoint<1>(row_ptr, entries, rows, count, W, R, g, g_sp, g_sr, g_sc, g_sb, out, o_sn, o_sc, o_sb, C, B, st);
-  else if (dim == 2)
-    launch_adjoint<2>(row_ptr, entries, rows, count, W, R, g, g_sp, g_sr, g_sc, g_sb, out, o_sn, o_sc, o_sb, C, B, st);
-  else
-    launch_adjoint<3>(row_ptr, entries, rows, count, W, R, g, g_sp, g_sr, g_sc, g_sb, out, o_sn, o_sc, o_sb, C, B, st);
-  return diffhe::check_launch();
+  account(8.0 * C * B * ((double)P * R * (dim + 1) + count));
+  const int Bp = batch_pad(B);
+  dispatch_apply(dim, Bp, [&](auto D, auto WAVE) {
+    hipLaunchKernelGGL((sample_adjoint_kernel<D(), WAVE()>), node_grid(count, Bp, 65536), dim3(256), 0,
+                       (hipStream_t)stream, row_ptr, entries, rows, count, W, R, g, g_sp, g_sr, g_sc, g_sb, out, o_sn, o_sc,
+                       o_sb, C, B, Bp);
+  });
+  return check_launch();
 }

@@ -15,11 +15,11 @@
 //   shape_gather_kernel (shape_gather.h, shared with elastic_shape.hip): per node, the contributions of its incident
 //     (element, vertex) pairs in the fixed order of the incidence list (diffhe/plan.py: SolvePlan.shape_incidence).
 #include "shape_gather.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
 // grad phi_p (G[p][k]) and the element size of a P1 simplex; false for a degenerate element, with the thresholds of the
 // assembly (ell_assemble.hip: tri_integrals area < 1e-15, tet_integrals |det| <= 1e-12 l^3; a zero-length segment in 1D).
@@ -86,12 +86,9 @@ __global__ __launch_bounds__(256) void shape_elem_kernel(const double* __restric
                                                          i64 ksb, const double* __restrict__ f, i64 fsn, i64 fsb,
                                                          double c, double* __restrict__ work) {
   constexpr int NPE = D + 1, NC = NPE * D;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane % LB;                       // sample lane inside this element's group
-  const int epw = kWave / LB;                      // elements per wave
-  const i64 stride = (i64)gridDim.x * 4 * epw;
-  // every lane of a group runs the same trip count (same e): the xor shuffles below never leave the group
-  for (i64 e = ((i64)blockIdx.x * 4 + wave) * epw + lane / LB; e < m; e += stride) {
+  const GroupMap gm = group_map(LB);               // a group of LB lanes per element
+  const int sub = gm.sub;
+  for (i64 e = gm.item0; e < m; e += gm.stride) {
     int v[NPE];
 #pragma unroll
     for (int p = 0; p < NPE; ++p) v[p] = elems[(i64)p * m + e];
@@ -155,14 +152,7 @@ __global__ __launch_bounds__(256) void shape_elem_kernel(const double* __restric
       }
       q += load - c * lu / (double)NPE;
     }
-    // fixed-order butterfly over the group's LB lanes (LB = 1: nothing to do)
-    for (int off = 1; off < LB; off <<= 1) {
-      q += __shfl_xor(q, off);
-#pragma unroll
-      for (int a = 0; a < D; ++a)
-#pragma unroll
-        for (int k = 0; k < D; ++k) T[a][k] += __shfl_xor(T[a][k], off);
-    }
+    group_sum(LB, q, T);
     double tr = 0.0;
 #pragma unroll
     for (int a = 0; a < D; ++a) tr += T[a][a];
@@ -189,25 +179,14 @@ extern "C" int diffhe_p1_shape_grad(const double* coords, const int* elems, int 
       m < 1 || B < 1 || sn < 0 || sb < 0 || kse < 0 || ksb < 0 || fsn < 0 || fsb < 0 || (long long)m * (dim + 1) >= (1LL << 31))
     return DIFFHE_E_BADARG;
   // lanes over samples when they are contiguous in memory, one element per lane otherwise
-  int LB = 1;
-  if (sb == 1)
-    while (LB < B && LB < kWave) LB <<= 1;
-  const int epb = 4 * (kWave / LB);                 // elements per 256-thread block and trip
-  long long blocks = ((long long)m + epb - 1) / epb;
-  if (blocks > 8192) blocks = 8192;
+  const int LB = sb == 1 ? group_lanes(B) : 1;
   // algorithmic bytes: u and lambda once, f once (batch-shared: one row), coords, the gradient
   account(8.0 * (2.0 * n * B + (f ? (fsb ? (double)n * B : (double)n) : 0.0) + 2.0 * dim * n));
-  const dim3 grid((unsigned)blocks), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dim == 1)
-    hipLaunchKernelGGL(shape_elem_kernel<1>, grid, block, 0, st, coords, elems, n, m, B, LB, u, g, lam, sn, sb, kappa,
-                       kse, ksb, f, fsn, fsb, c, work);
-  else if (dim == 2)
-    hipLaunchKernelGGL(shape_elem_kernel<2>, grid, block, 0, st, coords, elems, n, m, B, LB, u, g, lam, sn, sb, kappa,
-                       kse, ksb, f, fsn, fsb, c, work);
-  else
-    hipLaunchKernelGGL(shape_elem_kernel<3>, grid, block, 0, st, coords, elems, n, m, B, LB, u, g, lam, sn, sb, kappa,
-                       kse, ksb, f, fsn, fsb, c, work);
+  dispatch_dim<1, 3>(dim, [&](auto D) {
+    hipLaunchKernelGGL(shape_elem_kernel<D()>, dim3(group_grid(m, LB, 8192)), dim3(256), 0, st, coords, elems, n, m, B, LB,
+                       u, g, lam, sn, sb, kappa, kse, ksb, f, fsn, fsb, c, work);
+  });
   launch_shape_gather(inc_ptr, inc, work, n, dim, grad, st);
   return check_launch();
 }

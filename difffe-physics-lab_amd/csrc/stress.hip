@@ -23,11 +23,11 @@
 #include "eigen_field.h"
 #include "element_grad.h"
 #include "stress_form.h"
+#include "launch.h"
 
 namespace {
 
 using namespace diffhe;
-typedef long long i64;
 
 // ---------------------------------------------------------------------------------------
 // sigma at c*osc + e*ose + b and / or vm (m, Bp); a NULL output is neither computed nor stored.
@@ -165,10 +165,10 @@ int stress_eval(const int* elems, const double* gtab, int dim, double lam1, doub
   // u once per dof, E, the outputs (EIG: eps0)
   diffhe::account(8.0 * Bp * ((double)dim * n + (sigma ? (double)nc * m : 0.0) + (vm ? (double)m : 0.0)) +
                   modulus_bytes(e_se, e_sb, m, Bp) + eigen_array_bytes<EIG>(dim, z.plane_strain, z.ze, z.zb, m, Bp));
-  if (dim == 2)
-    return eval_of(element_of<2, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), Bp, sigma, osc, ose, vm,
+  return diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    return eval_of(element_of<D(), EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), Bp, sigma, osc, ose, vm,
                    stream);
-  return eval_of(element_of<3, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), Bp, sigma, osc, ose, vm, stream);
+  });
 }
 
 template <int DIM, bool EIG>
@@ -204,13 +204,11 @@ int stress_adjoint(const int* elems, const double* gtab, int dim, double lam1, d
                                    (nodes ? (double)nc * m : 0.0) + (de_e ? (double)m : 0.0)) +
                        modulus_bytes(e_se, e_sb, m, Bp) + eigen_array_bytes<EIG>(dim, z.plane_strain, z.ze, z.zb, m, Bp) +
                        (deps ? eigen_array_bytes<EIG>(dim, z.plane_strain, 1, 1, m, Bp) : 0.0);
-  if (dim == 2)
-    return adjoint_of(form_of(element_of<2, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), sigma_bar, osc, ose,
-                              vm_bar, work, B, deps, dzc, dze),
+  return diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
+    return adjoint_of(form_of(element_of<D(), EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), sigma_bar, osc,
+                              ose, vm_bar, work, B, deps, dzc, dze),
                       gtab, inc_ptr, inc, n, m, B, Bp, u_bar, de_e, de_part, de_sum, bytes, stream);
-  return adjoint_of(form_of(element_of<3, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), sigma_bar, osc, ose,
-                            vm_bar, work, B, deps, dzc, dze),
-                    gtab, inc_ptr, inc, n, m, B, Bp, u_bar, de_e, de_part, de_sum, bytes, stream);
+  });
 }
 
 template <bool EIG>
@@ -226,15 +224,12 @@ int stress_adjoint_shared(const int* elems, const double* gtab, int dim, double 
   const double bytes = 8.0 * (Bp * ((double)dim * n + (sigma_bar ? (double)nc * m : 0.0) + (vm_bar ? (double)m : 0.0)) +
                               (double)m) + modulus_bytes(e_se, e_sb, m, Bp) +
                        eigen_array_bytes<EIG>(dim, z.plane_strain, z.ze, z.zb, m, Bp);
-  if (dim == 2)
+  return diffhe::dispatch_dim<2, 3>(dim, [&](auto D) {
     return diffhe::launch_element_grad_shared(
-        form_of(element_of<2, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), sigma_bar, osc, ose, vm_bar,
+        form_of(element_of<D(), EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), sigma_bar, osc, ose, vm_bar,
                 nullptr, B, nullptr, 0, 0),
         m, B, Bp, de, 0, 1, bytes, stream);
-  return diffhe::launch_element_grad_shared(
-      form_of(element_of<3, EIG>(elems, gtab, lam1, mu1, nu_z, u, E, e_se, e_sb, m, z), sigma_bar, osc, ose, vm_bar, nullptr,
-              B, nullptr, 0, 0),
-      m, B, Bp, de, 0, 1, bytes, stream);
+  });
 }
 
 }  // namespace

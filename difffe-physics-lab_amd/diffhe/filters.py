@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
+from .cellgrid import cell_grid
 from .plan import _stream
 
 # refuse a table of more neighbour ids than this before it is allocated (and one that the free device memory cannot hold)
@@ -57,31 +58,6 @@ def _element_sizes(P: torch.Tensor) -> torch.Tensor:
     if dim == 2:
         return 0.5 * (a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]).abs()
     return (a * torch.linalg.cross(b, P[:, 3] - P[:, 0])).sum(1).abs() / 6.0
-
-
-def cell_grid(cent_md: torch.Tensor, min_edge: float):
-    """The uniform grid that bins the m centroids cent_md (m, dim): edge = max(min_edge, extent / c) with c^dim <= m, so
-    the number of cells stays O(m) however small min_edge is; offsets from the minimum, indices clamped at the upper faces.
-    Returns (lo (dim,), edge, [ncx, ncy, ncz], cell_of (m) int32, order (m) int32: the ids sorted by cell and ascending
-    within a cell, cell_start (cells + 1) int32).  Shared with diffhe/sampling.py."""
-    m, dim = cent_md.shape
-    dev = cent_md.device
-    lo = cent_md.min(0).values
-    ext = (cent_md.max(0).values - lo).cpu()
-    c = max(1, int(math.floor(m ** (1.0 / dim) + 1e-9)))
-    edge = max(min_edge, float(ext.max()) / c)
-    nc = [int(min(math.floor(float(e) / edge), c)) + 1 for e in ext] + [1] * (3 - dim)
-    top = torch.tensor(nc[:dim], device=dev) - 1
-    idx = torch.minimum(torch.floor((cent_md - lo) / edge).to(torch.int64), top)
-    cell = idx[:, 0]
-    if dim > 1:
-        cell = cell + nc[0] * idx[:, 1]
-    if dim > 2:
-        cell = cell + nc[0] * nc[1] * idx[:, 2]
-    n_cells = nc[0] * nc[1] * nc[2]
-    cell_sorted, order = torch.sort(cell, stable=True)                 # within a cell: ascending element id
-    cell_start = torch.searchsorted(cell_sorted, torch.arange(n_cells + 1, device=dev)).to(torch.int32)
-    return lo, edge, nc, cell.to(torch.int32), order.to(torch.int32), cell_start
 
 
 def check_field(x, m: int, layout: str) -> torch.Tensor:

@@ -3,7 +3,7 @@ tetrahedra, structured or not -- with the piecewise-constant spatial gradient at
 both.  Ours: the reference compares fields at mesh nodes only (kernels declared in include/diffhe_sample.h).
 
 `PointSampler(mesh, points)` locates every point once, on the device.  The elements are binned by centroid into a uniform
-grid whose edge is at least the longest element edge of the mesh (`filters.cell_grid`, the grid of the density filter), so
+grid whose edge is at least the longest element edge of the mesh (`cellgrid.cell_grid`, the grid of the density filter), so
 the element that contains a point has its centroid within one cell edge of it and the 3^dim cells around the point's cell
 hold every candidate.  Among the candidates the kernel takes the element whose smallest barycentric coordinate is largest,
 ties to the lowest element id; the point is inside if that coordinate is >= -tol.  The rule is a function of the mesh, the
@@ -32,7 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
-from .filters import cell_grid
+from .cellgrid import cell_grid, cell_index
 from .plan import _stream
 
 # the transposes visit the touched nodes alone once these are at most n / SPARSE_ROWS ("Point sampling")
@@ -133,15 +133,7 @@ class PointSampler(nn.Module):
         V = X[el.to(torch.int64)]                                           # (m, dim + 1, dim)
         longest = max(float((V[:, i] - V[:, j]).norm(dim=1).max()) for i in range(dim + 1) for j in range(i))
         lo, edge, nc, _, order, cell_start = cell_grid(V.sum(1) / float(dim + 1), longest)
-        # the cell of a point: the formula of the elements' cells, clamped into the grid on both sides
-        top = torch.tensor(nc[:dim], device=dev) - 1
-        idx = torch.floor((pts - lo) / edge).clamp_(-1.0, float(max(nc))).to(torch.int64)
-        idx = torch.minimum(idx.clamp_(min=0), top)
-        pcell = idx[:, 0]
-        if dim > 1:
-            pcell = pcell + nc[0] * idx[:, 1]
-        if dim > 2:
-            pcell = pcell + nc[0] * nc[1] * idx[:, 2]
+        pcell = cell_index(pts, lo, edge, nc, clamp_low=True)               # a point outside: the nearest cell
         porder = torch.sort(pcell, stable=True)[1].to(torch.int32)
         pcell = pcell.to(torch.int32)
         self._X, self._el, self.points = X, el, pts

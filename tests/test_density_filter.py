@@ -110,6 +110,9 @@ def test_ninth_signature_table_matches_the_ninth_header():
     make = open(os.path.join(csrc, "Makefile")).read()
     assert "filter.hip" in make.split("SRCS")[1].split("\n")[0] and "diffhe_filter.h" in make
     assert "atomic" not in open(os.path.join(csrc, "filter.hip")).read().split("#include")[-1]
+    for shared in ("launch.h", "cell_grid.h"):  # the plumbing the unit takes from shared headers
+        assert f'#include "{shared}"' in open(os.path.join(csrc, "filter.hip")).read()
+        assert "atomic" not in open(os.path.join(csrc, shared)).read().split("#include")[-1]
     if os.path.exists(_hip.LIB_PATH):
         L = _hip.lib()
         for name in decls:

@@ -322,6 +322,9 @@ def test_seventh_signature_table_matches_the_seventh_header():
     make = open(os.path.join(csrc, "Makefile")).read()
     assert "elastic_aniso.hip" in make.split("SRCS")[1].split("\n")[0] and "diffhe_elastic_aniso.h" in make
     assert "atomic" not in open(os.path.join(csrc, "elastic_aniso.hip")).read().split("#include")[-1]
+    for shared in ("launch.h",):  # the plumbing the unit takes from shared headers
+        assert f'#include "{shared}"' in open(os.path.join(csrc, "elastic_aniso.hip")).read()
+        assert "atomic" not in open(os.path.join(csrc, shared)).read().split("#include")[-1]
     if os.path.exists(_hip.LIB_PATH):
         L = _hip.lib()
         for name in decls:

@@ -247,6 +247,8 @@ def test_the_unit_is_built_and_uses_no_atomics():
     src = open(os.path.join(csrc, "elastic_shape.hip")).read()
     code = src.split('#include "stress_form.h"')[1]
     assert "diffhe_elast_shape_grad" in code and "diffhe_stress_shape_grad" in code and "atomic" not in code
+    assert '#include "launch.h"' in code                   # the lane groups and their reduction live there
+    assert "atomic" not in open(os.path.join(csrc, "launch.h")).read().split("#include")[-1]
     import diffhe
     assert "ShapeElasticFESolver" in diffhe.__all__
     assert diffhe.ShapeElasticFESolver is diffhe.elastic_shape.ShapeElasticFESolver

@@ -145,7 +145,11 @@ def test_shape_kernel_source_is_built():
     make = open(os.path.join(ROOT, "difffe-physics-lab_amd", "csrc", "Makefile")).read()
     assert "shape.hip" in make
     src = open(os.path.join(ROOT, "difffe-physics-lab_amd", "csrc", "shape.hip")).read()
-    assert "diffhe_p1_shape_grad" in src and "atomic" not in src.split("#include")[1]
+    code = src.split("#include")[-1]                       # everything after the last include: the whole unit
+    assert "shape_elem_kernel" in code and "diffhe_p1_shape_grad" in code and "atomic" not in code
+    assert '#include "launch.h"' in src                    # the lane groups and their reduction live there
+    launch = open(os.path.join(ROOT, "difffe-physics-lab_amd", "csrc", "launch.h")).read()
+    assert "atomic" not in launch.split("#include")[-1]
 
 
 @pytest.mark.parametrize("name", ["line", "rect", "box"])
