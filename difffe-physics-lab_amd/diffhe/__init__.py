@@ -36,10 +36,13 @@ mesh-independent density filter with a physical radius on the elements of any P1
 here, and the tanh projection `heaviside` -- the regularisation of a design in front of the solvers (kernels declared in
 include/diffhe_filter.h); `diffhe.sampling`: `PointSampler`, nodal fields sampled at arbitrary points of any P1 mesh, their
 spatial gradient there and the exact transposes -- readings of sensors that do not sit on nodes, and the transfer of a
-field from one mesh to another -- also exported here (kernels declared in include/diffhe_sample.h); `diffhe._hip`: the
-ctypes binding).
+field from one mesh to another -- also exported here (kernels declared in include/diffhe_sample.h); `diffhe.hyperelastic`:
+`HyperelasticFESolver`, the large-displacement counterpart of `ElasticFESolver` -- compressible Neo-Hookean material at
+finite strain in plane strain and 3D, Newton's method with load steps and a per-sample line search, dL/dE, dL/df and
+dL/dload from one adjoint solve with the final tangent -- also exported here (kernels declared in
+include/diffhe_hyperelastic.h); `diffhe._hip`: the ctypes binding).
 """
-from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, filters as _filters, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, sampling as _sampling, shape as _shape,
+from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, filters as _filters, hyperelastic as _hyperelastic, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, sampling as _sampling, shape as _shape,
                solver as _solver)
 
 FEMesh = _mesh.FEMesh
@@ -57,9 +60,10 @@ AnisotropicElasticFESolver = _elastic_aniso.AnisotropicElasticFESolver
 TractionElasticFESolver = _elastic_facets.TractionElasticFESolver
 DensityFilter = _filters.DensityFilter
 PointSampler = _sampling.PointSampler
+HyperelasticFESolver = _hyperelastic.HyperelasticFESolver
 
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
            "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver", "ElasticEigenSolver",
            "ShapeElasticFESolver", "AnisotropicElasticFESolver", "TractionElasticFESolver", "DensityFilter",
-           "PointSampler")
+           "PointSampler", "HyperelasticFESolver")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

@@ -1,6 +1,6 @@
 """ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h, include/diffhe_stress.h,
 include/diffhe_eigenstrain.h, include/diffhe_modal.h, include/diffhe_elastic_shape.h, include/diffhe_elastic_aniso.h,
-include/diffhe_elastic_facets.h, include/diffhe_filter.h, include/diffhe_sample.h).
+include/diffhe_elastic_facets.h, include/diffhe_filter.h, include/diffhe_sample.h, include/diffhe_hyperelastic.h).
 
 The library is built in-tree by `__graft_entry__.build()` /
 `make -C difffe-physics-lab_amd/csrc`.  There is NO fallback: if the library or a
@@ -256,6 +256,18 @@ SAMPLE_SIGNATURES = {
                                    _PV]),
 }
 
+# name -> (restype, argtypes) of every symbol of include/diffhe_hyperelastic.h, the library's eleventh header (finite-strain
+# Neo-Hookean elasticity: tangent, internal force, energy and dL/dE, csrc/hyperelastic.hip): bound by the same loop
+# (tests/test_hyperelastic.py holds this table against that header)
+_HYPER_HEAD = [_PI, _PD, _PD, _I, _D, _D]       # elems, gtab, vol, dim, lam1, mu1
+HYPERELASTIC_SIGNATURES = {
+    "diffhe_hyper_assemble_rows": (_S, [*_HYPER_HEAD, _PD, _L, _L, _PD, _PI, _PI, _PI, _PB, _PD, _I, _I, _I, _I, _PV]),
+    "diffhe_hyper_residual": (_S, [_PI, _PI, *_HYPER_HEAD, _PD, _L, _L, _PD, _I, _I, _I, _PD, _PV]),
+    "diffhe_hyper_energy": (_S, [*_HYPER_HEAD, _PD, _L, _L, _PD, _I, _I, _I, _PD, _PD, _PD, _PD, _PV]),
+    "diffhe_hyper_grad": (_S, [*_HYPER_HEAD, _PD, _PD, _I, _I, _I, _PD, _PD, _PD, _PV]),
+    "diffhe_hyper_grad_shared": (_S, [*_HYPER_HEAD, _PD, _PD, _I, _I, _I, _I, _PD, _PV]),
+}
+
 _lib = None
 
 
@@ -294,7 +306,7 @@ def lib():
                                   *EIGENSTRAIN_SIGNATURES.items(), *MODAL_SIGNATURES.items(),
                                   *ELASTIC_SHAPE_SIGNATURES.items(), *ELASTIC_ANISO_SIGNATURES.items(),
                                   *ELASTIC_FACET_SIGNATURES.items(), *FILTER_SIGNATURES.items(),
-                                  *SAMPLE_SIGNATURES.items()):
+                                  *SAMPLE_SIGNATURES.items(), *HYPERELASTIC_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = (_I if res is _S else res), args
             if res is _S:
