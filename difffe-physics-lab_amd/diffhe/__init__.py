@@ -40,7 +40,9 @@ field from one mesh to another -- also exported here (kernels declared in includ
 `HyperelasticFESolver`, the large-displacement counterpart of `ElasticFESolver` -- compressible Neo-Hookean material at
 finite strain in plane strain and 3D, Newton's method with load steps and a per-sample line search, dL/dE, dL/df and
 dL/dload from one adjoint solve with the final tangent -- also exported here (kernels declared in
-include/diffhe_hyperelastic.h); `diffhe._hip`: the ctypes binding).
+include/diffhe_hyperelastic.h), with `diffhe.hyper_stress`: the Cauchy stress, its von Mises stress and the strain-energy
+density of such a solve, differentiable in u and E (`cauchy_stress`, `cauchy_von_mises`, `energy_density` on the solver;
+kernels declared in include/diffhe_hyper_stress.h); `diffhe._hip`: the ctypes binding).
 """
 from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, filters as _filters, hyperelastic as _hyperelastic, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, sampling as _sampling, shape as _shape,
                solver as _solver)

@@ -49,9 +49,16 @@ final tangent, and the relative residual and the step length of every iteration 
 and are counted in `newton_not_converged`; the other samples are unaffected and nothing is raised.  A tangent whose
 diagonal is not positive and finite raises ValueError ("tangent not positive definite: reduce the load or raise steps").
 
+Stress recovery.  `cauchy_stress(u, E=None)`, `cauchy_von_mises`, `cauchy_stress_and_von_mises` and `energy_density`
+give the Cauchy (true) stress sigma = E (1/J) [mu1 (F F^T - I) + lam1 ln J I] per element and sample, its von Mises stress
+(with sigma_zz = E lam1 ln J / J of plane strain) and the energy density E W1(F) per reference volume, differentiable in
+u and E (`diffhe.hyper_stress`; csrc/hyper_stress.hip, include/diffhe_hyper_stress.h).  After a solve,
+`pnorm(solver.cauchy_von_mises(solver(f, load)))` is differentiable in E with one adjoint solve.
+
 Not implemented (NotImplementedError): 1D and P2 meshes; plane="stress" (it needs a local solve for F33); backward with
-create_graph=True; moving nodes; `eigenstrain=`, `dirichlet=`, Robin / flux data; `stress`, `von_mises`,
-`stress_and_von_mises` and `modes`; `amg=dict(strength=...)`.
+create_graph=True; moving nodes; `eigenstrain=`, `dirichlet=`, Robin / flux data; the small-strain `stress`, `von_mises`
+and `stress_and_von_mises` (the `cauchy_*` methods are the finite-strain ones), the Piola-Kirchhoff stresses PK1 and PK2,
+and `modes`; `amg=dict(strength=...)`.
 """
 from __future__ import annotations
 
@@ -62,9 +69,10 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _hip
+from . import _hip, hyper_stress as _hyper_stress  # noqa: F401  (registers diffhe::hyper_stress)
 from .elastic import (_ElasticOptions, _ElasticSolve, _batch_of, _check_mesh, _measure_row_bounds, _run_adjoint,
                       _select_hierarchy, _solve_autograd, _solve_call, _solve_fake, _solve_result, lame_unit)
+from .elastic_stress import _stress_batch
 from .plan import padded_batch, _stream
 from .solver import SolveInfo, _Engine, _SOLVERS, _fake_grads, _kappa_grad, _kappa_layout, _like_grads
 
@@ -390,11 +398,57 @@ class HyperelasticFESolver(_ElasticOptions):
         u, _token = torch.ops.diffhe.hyperelastic_solve(E, f_in, load_in, x0_in, id(self), save, node)
         return u
 
+    # -- stress recovery: the Cauchy stress (diffhe.hyper_stress) ---------------------------------------
+    def _cauchy_op(self, u, E, layout: str, want_sigma: bool, want_vm: bool, want_w: bool):
+        n, d = self.mesh.n_nodes, self.mesh.dim
+        if layout not in ("sample", "node"):
+            raise ValueError(f"Unknown layout: {layout!r}")
+        u = u if isinstance(u, torch.Tensor) else torch.as_tensor(u)
+        if layout == "node":
+            if u.dim() != 3 or tuple(u.shape[:2]) != (n, d):
+                raise ValueError(f"layout='node': u must be (n, d, B) with n={n}, d={d}, got {tuple(u.shape)}")
+        elif u.dim() not in (2, 3) or tuple(u.shape[-2:]) != (n, d):
+            raise ValueError(f"u must be (n, d) or (B, n, d) with n={n}, d={d}, got {tuple(u.shape)}")
+        if E is None:
+            E = self._E
+        elif not isinstance(E, torch.Tensor):
+            E = torch.as_tensor(E, dtype=torch.float64)
+        self._refuse_moving_nodes("stress", False)
+        u, E, node = u.to(torch.float64), E.to(torch.float64), layout == "node"
+        _kappa_layout(E, self.mesh.n_elements, _stress_batch(u, node), node)       # the refusals, before the op
+        _SOLVERS[id(self)] = self
+        return torch.ops.diffhe.hyper_stress(u, E, id(self), node, want_sigma, want_vm, want_w)
+
+    def cauchy_stress(self, u: torch.Tensor, E=None, layout: str = "sample") -> torch.Tensor:
+        """Cauchy (true) stresses sigma = E (1/J) [mu1 (F F^T - I) + lam1 ln J I] of the displacement u -- (n, d),
+        (B, n, d), or (n, d, B) with layout="node", what `forward` returns -- in Voigt components (xx, yy, xy | xx, yy, zz,
+        yz, xz, xy; shear components are tensor components): (m, nc), (B, m, nc), or (m, nc, B) with layout="node".  E:
+        None for the solver's, or another modulus in any layout E takes (the relaxed stress of stress-constrained design);
+        an unbatched u is broadcast to the batch of E.  u and E may require grad.  An element with det F <= 0 gets NaN."""
+        return self._cauchy_op(u, E, layout, True, False, False)[0]
+
+    def cauchy_von_mises(self, u: torch.Tensor, E=None, layout: str = "sample") -> torch.Tensor:
+        """The von Mises stress of the Cauchy stress per element, (m,), (B, m), or (m, B) with layout="node"; in 2D it
+        includes the out-of-plane sigma_zz = E lam1 ln J / J of plane strain.  No stress array is formed.  Its derivative
+        is defined as 0 where the stress vanishes.  Arguments as `cauchy_stress`."""
+        return self._cauchy_op(u, E, layout, False, True, False)[1]
+
+    def cauchy_stress_and_von_mises(self, u: torch.Tensor, E=None,
+                                    layout: str = "sample") -> Tuple[torch.Tensor, torch.Tensor]:
+        """(`cauchy_stress`, `cauchy_von_mises`) from one pass over the elements, and one backward pass for both."""
+        return self._cauchy_op(u, E, layout, True, True, False)[:2]
+
+    def energy_density(self, u: torch.Tensor, E=None, layout: str = "sample") -> torch.Tensor:
+        """The strain energy per reference volume w = E W1(F) per element, in the shape of `cauchy_von_mises`: the sum of
+        vol_e w_e is the energy the Newton iteration minimises.  Arguments as `cauchy_stress`."""
+        return self._cauchy_op(u, E, layout, False, False, True)[2]
+
     # -- what exists for small strains only -------------------------------------------------------------
     def _no_stress(self, *args, **kwargs):
-        raise NotImplementedError("diffhe: stress recovery is not implemented for finite-strain elasticity (stress, "
-                                  "von_mises and stress_and_von_mises evaluate the small-strain stress: "
-                                  "diffhe.elastic.ElasticFESolver)")
+        raise NotImplementedError("diffhe: stress recovery is not implemented for finite-strain elasticity by these "
+                                  "methods (stress, von_mises and stress_and_von_mises evaluate the small-strain stress: "
+                                  "diffhe.elastic.ElasticFESolver); the Cauchy stress of the deformed body is "
+                                  "cauchy_stress, cauchy_von_mises and cauchy_stress_and_von_mises")
 
     stress = von_mises = stress_and_von_mises = _no_stress
 
