@@ -29,7 +29,11 @@ adjoint solve -- shape design of elastic bodies -- also exported here (kernels d
 include/diffhe_elastic_shape.h); `diffhe.elastic_aniso`: `AnisotropicElasticFESolver`, `ElasticFESolver` with a stiffness
 tensor per element and sample in place of (E, nu) and its gradient dL/dC -- laminates, orthotropic and cubic materials,
 gradients to Poisson's ratio -- with the torch helpers that build and rotate such tensors, also exported here (kernels
-declared in include/diffhe_elastic_aniso.h); `diffhe.elastic_facets`: `TractionElasticFESolver`, `ElasticFESolver` with
+declared in include/diffhe_elastic_aniso.h), with `diffhe.elastic_aniso_stress`: the stress sigma = C eps(u) of such a solve
+and the fused quadratic failure index phi = q . sigma + sigma . Q sigma (Tsai-Wu, Tsai-Hill, von Mises as a quadratic form),
+differentiable in u, C and the criterion (`tensor_stress`, `failure_index` on the solver; the criterion helpers `tsai_wu`,
+`tsai_hill`, `quadratic`, `split`, `von_mises_criterion`, `rotated_criterion`, also exported here; kernels declared in
+include/diffhe_elastic_aniso_stress.h); `diffhe.elastic_facets`: `TractionElasticFESolver`, `ElasticFESolver` with
 tractions, pressure and an elastic (Winkler) foundation on boundary facets, per facet and sample, and their gradients,
 also exported here (kernels declared in include/diffhe_elastic_facets.h); `diffhe.filters`: `DensityFilter`, the
 mesh-independent density filter with a physical radius on the elements of any P1 mesh and its exact adjoint, also exported
@@ -44,7 +48,7 @@ include/diffhe_hyperelastic.h), with `diffhe.hyper_stress`: the Cauchy stress, i
 density of such a solve, differentiable in u and E (`cauchy_stress`, `cauchy_von_mises`, `energy_density` on the solver;
 kernels declared in include/diffhe_hyper_stress.h); `diffhe._hip`: the ctypes binding).
 """
-from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, filters as _filters, hyperelastic as _hyperelastic, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, sampling as _sampling, shape as _shape,
+from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_aniso_stress as _elastic_aniso_stress, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, filters as _filters, hyperelastic as _hyperelastic, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, sampling as _sampling, shape as _shape,
                solver as _solver)
 
 FEMesh = _mesh.FEMesh
@@ -63,9 +67,14 @@ TractionElasticFESolver = _elastic_facets.TractionElasticFESolver
 DensityFilter = _filters.DensityFilter
 PointSampler = _sampling.PointSampler
 HyperelasticFESolver = _hyperelastic.HyperelasticFESolver
+tsai_wu, tsai_hill = _elastic_aniso_stress.tsai_wu, _elastic_aniso_stress.tsai_hill
+quadratic, split = _elastic_aniso_stress.quadratic, _elastic_aniso_stress.split
+von_mises_criterion = _elastic_aniso_stress.von_mises_criterion
+rotated_criterion = _elastic_aniso_stress.rotated_criterion
 
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
            "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver", "ElasticEigenSolver",
            "ShapeElasticFESolver", "AnisotropicElasticFESolver", "TractionElasticFESolver", "DensityFilter",
-           "PointSampler", "HyperelasticFESolver")
+           "PointSampler", "HyperelasticFESolver", "tsai_wu", "tsai_hill", "quadratic", "split", "von_mises_criterion",
+           "rotated_criterion")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

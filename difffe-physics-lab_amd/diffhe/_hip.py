@@ -1,7 +1,7 @@
 """ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h, include/diffhe_stress.h,
 include/diffhe_eigenstrain.h, include/diffhe_modal.h, include/diffhe_elastic_shape.h, include/diffhe_elastic_aniso.h,
 include/diffhe_elastic_facets.h, include/diffhe_filter.h, include/diffhe_sample.h, include/diffhe_hyperelastic.h,
-include/diffhe_hyper_stress.h).
+include/diffhe_hyper_stress.h, include/diffhe_elastic_aniso_stress.h).
 
 The library is built in-tree by `__graft_entry__.build()` /
 `make -C difffe-physics-lab_amd/csrc`.  There is NO fallback: if the library or a
@@ -281,6 +281,20 @@ HYPER_STRESS_SIGNATURES = {
     "diffhe_hyper_stress_adjoint_shared": (_S, [*_CAUCHY_HEAD, *_CAUCHY_BARS, _I, _I, _I, _I, _PD, _PV]),
 }
 
+# name -> (restype, argtypes) of every symbol of include/diffhe_elastic_aniso_stress.h, the library's thirteenth header
+# (stress and quadratic failure index of anisotropic elastic solves with their adjoint, csrc/elastic_aniso_stress.hip): bound
+# by the same loop (tests/test_elastic_aniso_stress.py holds this table against that header)
+_ASTRESS_HEAD = [_PI, _PD, _I, _PD, _PD, _L, _L, _L, _PD, _L, _L, _L]   # elems, gtab, dim, u, C and the criterion with 3 strides each
+_ASTRESS_BARS = [_PD, _L, _L, _PD]                                       # sigma_bar, osc, ose, phi_bar
+_ASTRESS_GRAD = [_PD, _L, _L, _PD, _PD]                                  # per element and sample with 2 strides, partials, sums
+ELASTIC_ANISO_STRESS_SIGNATURES = {
+    "diffhe_elastc_stress_eval": (_S, [*_ASTRESS_HEAD, _I, _I, _I, _PD, _L, _L, _PD, _PV]),
+    "diffhe_elastc_stress_adjoint": (_S, [*_ASTRESS_HEAD, *_ASTRESS_BARS, _PI, _PI, _I, _I, _I, _I, _PD, _PD,
+                                          *_ASTRESS_GRAD, *_ASTRESS_GRAD, _PV]),
+    "diffhe_elastc_stress_adjoint_shared": (_S, [*_ASTRESS_HEAD, *_ASTRESS_BARS, _I, _I, _I, _I, _PD, _L, _L, _PD, _L, _L,
+                                                 _PV]),
+}
+
 _lib = None
 
 
@@ -320,7 +334,7 @@ def lib():
                                   *ELASTIC_SHAPE_SIGNATURES.items(), *ELASTIC_ANISO_SIGNATURES.items(),
                                   *ELASTIC_FACET_SIGNATURES.items(), *FILTER_SIGNATURES.items(),
                                   *SAMPLE_SIGNATURES.items(), *HYPERELASTIC_SIGNATURES.items(),
-                                  *HYPER_STRESS_SIGNATURES.items()):
+                                  *HYPER_STRESS_SIGNATURES.items(), *ELASTIC_ANISO_STRESS_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = (_I if res is _S else res), args
             if res is _S:

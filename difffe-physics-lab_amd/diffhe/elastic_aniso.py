@@ -39,9 +39,13 @@ synchronisation per call) and overwrites the levels' bounds with them.  `last_in
 ("stiffness tensor not positive definite").  The adjoint reuses the forward's hierarchy.  `validate=True` checks C itself
 with `torch.linalg.cholesky_ex` (one more synchronisation; ValueError).
 
+Stress recovery: `tensor_stress`, `failure_index` and `tensor_stress_and_failure_index` (`diffhe.elastic_aniso_stress`)
+give sigma = C eps(u) and a quadratic failure index per element and sample, differentiable in u, C and the criterion.
+
 Not implemented (NotImplementedError): 1D and P2 meshes; backward with create_graph=True; `eigenstrain=`; `stress`,
-`von_mises`, `stress_and_von_mises` (stress recovery for a tensor is the follow-up); moving nodes (mesh.nodes requiring
-grad); vibration modes (`modes`: `ElasticEigenSolver` takes (E, nu) only); a per-call `dirichlet=`, Robin / flux data;
+`von_mises`, `stress_and_von_mises` (they read (E, nu); the stress of a tensor is `tensor_stress` / `failure_index`);
+strength ratios and non-smooth (maximum-stress, Puck) criteria; moving nodes (mesh.nodes requiring grad, also for the
+stress); vibration modes (`modes`: `ElasticEigenSolver` takes (E, nu) only); a per-call `dirichlet=`, Robin / flux data;
 `amg=dict(strength=...)`.
 """
 from __future__ import annotations
@@ -363,10 +367,38 @@ class AnisotropicElasticFESolver(_ElasticOptions):
         u, _token = torch.ops.diffhe.elastic_aniso_solve(C, f_in, load_in, id(self), save, node)
         return u
 
+    # -- stress recovery: sigma = C eps(u) and the failure index (diffhe.elastic_aniso_stress) ---------------
+    def tensor_stress(self, u: torch.Tensor, C=None, layout: str = "sample") -> torch.Tensor:
+        """Stresses sigma = C eps(u) of the displacement u -- (n, d), (B, n, d), or (n, d, B) with layout="node", what
+        `forward` returns; strided views are read as they are -- in Voigt components (xx, yy, xy | xx, yy, zz, yz, xz, xy;
+        shear components are tensor components): (m, nc), (B, m, nc), or (m, nc, B) with layout="node", the shapes of
+        `ElasticFESolver.stress`.  C: None for the solver's, or another tensor in any layout C takes (the relaxed stress
+        of stress-constrained design); an unbatched u is broadcast to the batch of C.  u and C may require grad."""
+        from . import elastic_aniso_stress
+        return elastic_aniso_stress._evaluate(self, u, None, C, layout, True, False)[0]
+
+    def failure_index(self, u: torch.Tensor, criterion, C=None, layout: str = "sample") -> torch.Tensor:
+        """The failure index phi = q . sigma + sigma . Q sigma per element, (m,), (B, m), or (m, B) with layout="node"; no
+        stress array is formed.  criterion: ONE tensor of nk = nv + nt components (9 in 2D, 27 in 3D), q first, then the
+        upper triangle of Q -- `diffhe.tsai_wu`, `tsai_hill`, `von_mises_criterion`, `quadratic` -- as (nk,), (B, nk),
+        (m, nk), (B, m, nk), or (nk, m, B) with layout="node"; it may require grad, and its gradient comes back in its
+        shape.  Other arguments as `tensor_stress`."""
+        from . import elastic_aniso_stress
+        return elastic_aniso_stress._evaluate(self, u, criterion, C, layout, False, True)[1]
+
+    def tensor_stress_and_failure_index(self, u: torch.Tensor, criterion, C=None,
+                                        layout: str = "sample") -> Tuple[torch.Tensor, torch.Tensor]:
+        """(`tensor_stress`, `failure_index`) from one pass over the elements, and one backward for both."""
+        from . import elastic_aniso_stress
+        return elastic_aniso_stress._evaluate(self, u, criterion, C, layout, True, True)
+
     # -- what exists for (E, nu) only -----------------------------------------------------------------
     def _no_stress(self, *args, **kwargs):
-        raise NotImplementedError("diffhe: stress recovery is not implemented with a stiffness tensor (stress, von_mises "
-                                  "and stress_and_von_mises read (E, nu): diffhe.elastic.ElasticFESolver)")
+        raise NotImplementedError("diffhe: stress recovery is not implemented with a stiffness tensor by these methods "
+                                  "(stress, von_mises and stress_and_von_mises read (E, nu): "
+                                  "diffhe.elastic.ElasticFESolver; a reduced plane stiffness does not determine sigma_zz); "
+                                  "the stress of a tensor is tensor_stress, failure_index and "
+                                  "tensor_stress_and_failure_index, with diffhe.von_mises_criterion for (vm / sigma_y)^2")
 
     stress = von_mises = stress_and_von_mises = _no_stress
 
