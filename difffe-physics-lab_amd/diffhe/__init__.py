@@ -46,9 +46,13 @@ finite strain in plane strain and 3D, Newton's method with load steps and a per-
 dL/dload from one adjoint solve with the final tangent -- also exported here (kernels declared in
 include/diffhe_hyperelastic.h), with `diffhe.hyper_stress`: the Cauchy stress, its von Mises stress and the strain-energy
 density of such a solve, differentiable in u and E (`cauchy_stress`, `cauchy_von_mises`, `energy_density` on the solver;
-kernels declared in include/diffhe_hyper_stress.h); `diffhe._hip`: the ctypes binding).
+kernels declared in include/diffhe_hyper_stress.h); `diffhe.buckling`: `LinearBucklingSolver`, the critical load factors
+(K(E) + lambda K_G(sigma0)) phi = 0 of elastic bodies per sample and their modes -- the fourth classical structural design
+problem next to compliance, stress and eigenfrequencies -- with d lambda / dE and d lambda / d sigma0, the prestress taken
+from a solve of its own or given, and `aggregate`, the smooth lower bound of the smallest factor, also exported here
+(kernels declared in include/diffhe_buckling.h); `diffhe._hip`: the ctypes binding).
 """
-from . import (aniso as _aniso, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_aniso_stress as _elastic_aniso_stress, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, filters as _filters, hyperelastic as _hyperelastic, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, sampling as _sampling, shape as _shape,
+from . import (aniso as _aniso, buckling as _buckling, eigen as _eigen, elastic as _elastic, elastic_aniso as _elastic_aniso, elastic_aniso_stress as _elastic_aniso_stress, elastic_facets as _elastic_facets, elastic_shape as _elastic_shape, filters as _filters, hyperelastic as _hyperelastic, loss as _loss, mesh as _mesh, modal as _modal, neural as _neural, robin as _robin, sampling as _sampling, shape as _shape,
                solver as _solver)
 
 FEMesh = _mesh.FEMesh
@@ -67,6 +71,7 @@ TractionElasticFESolver = _elastic_facets.TractionElasticFESolver
 DensityFilter = _filters.DensityFilter
 PointSampler = _sampling.PointSampler
 HyperelasticFESolver = _hyperelastic.HyperelasticFESolver
+LinearBucklingSolver = _buckling.LinearBucklingSolver
 tsai_wu, tsai_hill = _elastic_aniso_stress.tsai_wu, _elastic_aniso_stress.tsai_hill
 quadratic, split = _elastic_aniso_stress.quadratic, _elastic_aniso_stress.split
 von_mises_criterion = _elastic_aniso_stress.von_mises_criterion
@@ -75,6 +80,6 @@ rotated_criterion = _elastic_aniso_stress.rotated_criterion
 __all__ = ("FEMesh", "DifferentiableFESolver", "PhysicsLoss", "NeuralPDE", "ShapeDifferentiableFESolver",
            "AnisotropicFESolver", "RobinFESolver", "EigenFESolver", "ElasticFESolver", "ElasticEigenSolver",
            "ShapeElasticFESolver", "AnisotropicElasticFESolver", "TractionElasticFESolver", "DensityFilter",
-           "PointSampler", "HyperelasticFESolver", "tsai_wu", "tsai_hill", "quadratic", "split", "von_mises_criterion",
+           "PointSampler", "HyperelasticFESolver", "LinearBucklingSolver", "tsai_wu", "tsai_hill", "quadratic", "split", "von_mises_criterion",
            "rotated_criterion")
 __version__ = "0.1.0"          # tracks the reference release this surface mirrors

@@ -1,7 +1,7 @@
 """ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h, include/diffhe_stress.h,
 include/diffhe_eigenstrain.h, include/diffhe_modal.h, include/diffhe_elastic_shape.h, include/diffhe_elastic_aniso.h,
 include/diffhe_elastic_facets.h, include/diffhe_filter.h, include/diffhe_sample.h, include/diffhe_hyperelastic.h,
-include/diffhe_hyper_stress.h, include/diffhe_elastic_aniso_stress.h).
+include/diffhe_hyper_stress.h, include/diffhe_elastic_aniso_stress.h, include/diffhe_buckling.h).
 
 The library is built in-tree by `__graft_entry__.build()` /
 `make -C difffe-physics-lab_amd/csrc`.  There is NO fallback: if the library or a
@@ -295,6 +295,20 @@ ELASTIC_ANISO_STRESS_SIGNATURES = {
                                                  _PV]),
 }
 
+# name -> (restype, argtypes) of every symbol of include/diffhe_buckling.h, the library's fourteenth header (linear buckling
+# of elastic bodies: the geometric stiffness applied from the node pattern, the block passes of a pencil whose right-hand
+# matrix is a block, and the cotangent of the prestress, csrc/buckling.hip): bound by the same loop
+# (tests/test_buckling.py holds this table against that header)
+_MODES = [_PI, _PD, _PD, _I, _PD, _PD, _I, _I, _I, _I, _I]      # elems, gtab, vol, dim, X, w, k, n, m, B, Bp
+BUCKLING_SIGNATURES = {
+    "diffhe_buckling_apply": (_S, [_PD, _PI, _PB, _PD, _PD, _D, _I, _I, _I, _I, _I, _PV]),
+    "diffhe_buckling_step": (_S, [_PD, _PD, _PD, _PD, _I, _I, _PD, _PD, _PD, _PV]),
+    "diffhe_buckling_gram": (_S, [_PD, _PD, _PD, _PB, _I, _I, _I, _PD, _PD, _PD, _PV]),
+    "diffhe_buckling_rotate": (_S, [_PD, _PD, _PD, _PD, _PD, _I, _I, _I, _PD, _PD, _PD, _PD, _PV]),
+    "diffhe_buckling_grad_sigma": (_S, [*_MODES, _PD, _L, _L, _PD, _PD, _PV]),
+    "diffhe_buckling_grad_sigma_shared": (_S, [*_MODES, _PD, _L, _L, _PV]),
+}
+
 _lib = None
 
 
@@ -334,7 +348,8 @@ def lib():
                                   *ELASTIC_SHAPE_SIGNATURES.items(), *ELASTIC_ANISO_SIGNATURES.items(),
                                   *ELASTIC_FACET_SIGNATURES.items(), *FILTER_SIGNATURES.items(),
                                   *SAMPLE_SIGNATURES.items(), *HYPERELASTIC_SIGNATURES.items(),
-                                  *HYPER_STRESS_SIGNATURES.items(), *ELASTIC_ANISO_STRESS_SIGNATURES.items()):
+                                  *HYPER_STRESS_SIGNATURES.items(), *ELASTIC_ANISO_STRESS_SIGNATURES.items(),
+                                  *BUCKLING_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = (_I if res is _S else res), args
             if res is _S:

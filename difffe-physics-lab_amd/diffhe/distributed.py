@@ -139,6 +139,9 @@ class ShardedBatchSolve:
     """
 
     def __init__(self, local_solve: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], group=None, collective=None):
+        refusal = getattr(getattr(local_solve, "__self__", local_solve), "_no_distributed", None)
+        if refusal:         # a solver whose call is not u = solve(kappa, f) over a batch that can be cut (diffhe.buckling)
+            raise NotImplementedError(refusal)
         self.local_solve = local_solve
         self.group = group
         self.collective = collective if collective is not None else _default_collective(group)

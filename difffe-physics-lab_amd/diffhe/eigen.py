@@ -95,7 +95,13 @@ class _BlockRun:
     shaped `vec` -- (n,) for the scalar operator, (n, d) for a displacement.  A subclass supplies the problem: `_setup`
     (assemble once, hierarchy once), `_apply` (y = A x), `_inner_solve`, the four mass-weighted passes (`_rayleigh_ritz`,
     `_fix_sign`), `_bc_rows` and `_release`; and sets es, plan, L, B, Bp, batched, k, p, rows, vec before `run`.  After
-    `run()` X holds the k returned columns."""
+    `run()` X holds the k returned columns.
+
+    The right-hand matrix of the pencil is the subclass's business: the two mass-weighted problems read a diagonal mass in
+    their passes; a pencil whose right-hand matrix is an operator (`diffhe.buckling`) carries it as a block next to A Y and
+    overrides the three column hooks `_apply_column`, `_next_column` and `_eigenvalues`, whose defaults are the inverse
+    iteration of the mass-weighted problems."""
+    Info = EigenInfo        # the class of `last_info` after a run
 
     def _new(self, *shape, dtype=torch.float64):
         return torch.empty(shape, dtype=dtype, device=self.plan.device)
@@ -136,12 +142,26 @@ class _BlockRun:
         both = torch.stack([above, b["flag"][:B].sum().to(above.dtype)]).cpu()
         return int(both[0]), int(both[1])
 
+    # -- the column hooks -----------------------------------------------------------------------------------------------
+    def _apply_column(self, i: int, Y, AY) -> None:
+        """Column i of the operator blocks from column i of Y."""
+        self._apply(Y[i], AY[i])
+
+    def _next_column(self, i: int, res, Y, AY) -> None:
+        """Column i of the next block from the inner solve `res` of column i of R, and its operator blocks."""
+        torch.add(self.buf["X"][i], res.x, out=Y[i])
+        self._apply_column(i, Y, AY)
+
+    def _eigenvalues(self) -> torch.Tensor:
+        """(B, k) returned eigenvalues from the Ritz values of the last block."""
+        return (self.buf["theta"][:self.k, :self.B] - self.es.shift).t().contiguous()
+
     # -- the iteration --------------------------------------------------------------------------------------------------
     def run(self, coeffs, x0, node_layout: bool):
         """coeffs: what `_setup` assembles from (kappa, or E and rho)."""
         es, plan, L = self.es, self.plan, self.L
         p, k, n, B, Bp = self.p, self.k, self.rows, self.B, self.Bp
-        info = EigenInfo(inner_tol=float(es.inner_tol), block=p)
+        info = self.Info(inner_tol=float(es.inner_tol), block=p)
         Y = self._start_block(x0, node_layout)
         self._setup(coeffs, Y, info, keep=x0 is not None and self.p == self.k)
         nblk = L.diffhe_eig_gram_blocks(n, Bp)
@@ -153,7 +173,7 @@ class _BlockRun:
         b = self.buf
         AY = self._new(p, n, Bp)
         for i in range(p):
-            self._apply(Y[i], AY[i])
+            self._apply_column(i, Y, AY)
         self._rayleigh_ritz(Y, AY)
         above, failed = self._status()
         while above and info.outer_iterations < es.max_iter:
@@ -163,8 +183,7 @@ class _BlockRun:
                 info.inner_solves += 1
                 info.inner_iterations += res.iterations
                 info.inner_not_converged += res.not_converged
-                torch.add(b["X"][i], res.x, out=Y[i])
-                self._apply(Y[i], AY[i])
+                self._next_column(i, res, Y, AY)
             self._rayleigh_ritz(Y, AY)
             above, failed = self._status()
         sgn = self._new(k, Bp)
@@ -179,7 +198,7 @@ class _BlockRun:
             warnings.warn(f"diffhe: {above} of {B * k} eigenpairs did not reach tol={es.tol:g} in {es.max_iter} outer "
                           f"iterations (max relative residual {float(info.residual.max()):.2e}, path {info.path})",
                           RuntimeWarning)
-        lam = (b["theta"][:k, :B] - es.shift).t().contiguous()                 # (B, k)
+        lam = self._eigenvalues()                                              # (B, k)
         self.X = b["X"][:k]
         if node_layout:
             phi = (self.X if Bp == B else self.X[:, :, :B]).reshape(k, *self.vec, B)
