@@ -1,7 +1,7 @@
 """ctypes binding of libdiffhe_hip.so (include/diffhe_hip.h, include/diffhe_elastic.h, include/diffhe_stress.h,
 include/diffhe_eigenstrain.h, include/diffhe_modal.h, include/diffhe_elastic_shape.h, include/diffhe_elastic_aniso.h,
 include/diffhe_elastic_facets.h, include/diffhe_filter.h, include/diffhe_sample.h, include/diffhe_hyperelastic.h,
-include/diffhe_hyper_stress.h, include/diffhe_elastic_aniso_stress.h, include/diffhe_buckling.h).
+include/diffhe_hyper_stress.h, include/diffhe_elastic_aniso_stress.h, include/diffhe_buckling.h, include/diffhe_lobpcg.h).
 
 The library is built in-tree by `__graft_entry__.build()` /
 `make -C difffe-physics-lab_amd/csrc`.  There is NO fallback: if the library or a
@@ -309,6 +309,16 @@ BUCKLING_SIGNATURES = {
     "diffhe_buckling_grad_sigma_shared": (_S, [*_MODES, _PD, _L, _L, _PV]),
 }
 
+# name -> (restype, argtypes) of every symbol of include/diffhe_lobpcg.h, the library's fifteenth header (the block passes of
+# the LOBPCG outer iteration on the basis [X | W | P]: Gram matrices, the Ritz step with its fallback, the rotation,
+# csrc/lobpcg.hip): bound by the same loop (tests/test_lobpcg.py holds this table against that header)
+LOBPCG_SIGNATURES = {
+    "diffhe_lobpcg_gram_blocks": (_I, [_I, _I]),
+    "diffhe_lobpcg_gram": (_S, [_PD, _PD, _PD, _PB, _I, _I, _I, _PD, _PD, _PD, _PV]),
+    "diffhe_lobpcg_ritz": (_S, [_PD, _PD, _I, _I, _I, _I, _PD, _PD, _PI, _PI, _PV]),
+    "diffhe_lobpcg_rotate": (_S, [_PD, _PD, _PD, _PD, _PD, _I, _I, _I, _I, _PD, _PD, _PD, _PD, _PV]),
+}
+
 _lib = None
 
 
@@ -349,7 +359,7 @@ def lib():
                                   *ELASTIC_FACET_SIGNATURES.items(), *FILTER_SIGNATURES.items(),
                                   *SAMPLE_SIGNATURES.items(), *HYPERELASTIC_SIGNATURES.items(),
                                   *HYPER_STRESS_SIGNATURES.items(), *ELASTIC_ANISO_STRESS_SIGNATURES.items(),
-                                  *BUCKLING_SIGNATURES.items()):
+                                  *BUCKLING_SIGNATURES.items(), *LOBPCG_SIGNATURES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = (_I if res is _S else res), args
             if res is _S:

@@ -73,7 +73,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
-from .eigen import JACOBI_SWEEPS, MAX_BLOCK, EigenInfo, _BlockRun
+from .eigen import JACOBI_SWEEPS, MAX_BLOCK, EigenInfo, _BlockRun, _check_iteration
 from .elastic import ElasticFESolver, _check_mesh, _select_hierarchy, _setup_of
 from .modal import _field_layout
 from .plan import padded_batch, _stream
@@ -188,7 +188,10 @@ class _BucklingRun(_BlockRun):
                                      plan.cols, None, None, self.G, None, plan.n, plan.m, plan.W, Bg, st)
         p, n = self.p, self.rows
         self._apart = self._new(L.diffhe_grad_kappa_blocks(n, Bp) * Bp)
-        self.NY, self.NX = self._new(p, n, Bp), self._new(p, n, Bp)
+        if bs.iteration == "subspace":
+            self.NY, self.NX = self._new(p, n, Bp), self._new(p, n, Bp)
+        else:                   # LOBPCG carries K_G S and K S as blocks of the basis
+            self.NY = self.NX = None
         self.mu, self.coef, self.dots = self._new(p, Bp), self._new(p, Bp), self._new(p, Bp)
         self.shift = torch.zeros(Bp, dtype=torch.float64, device=plan.device)
         self.neg_seen = torch.zeros(Bp, dtype=torch.int64, device=plan.device)
@@ -234,6 +237,52 @@ class _BucklingRun(_BlockRun):
         torch.add(self.mu, self.shift[None, :], out=self.coef)
         torch.maximum(self.neg_seen, (b["theta"] > 0.0).sum(dim=0), out=self.neg_seen)
 
+    # -- what LOBPCG asks of the problem: the pencil (K_G, K), theta = -mu, no shift --------------------------------------------
+    def _free_mask(self):
+        return self.setup.dofs.is_bc
+
+    def _lobpcg_apply(self, blk, j: int) -> None:
+        """K_G s_j = (G (x) I_d) s_j into A S and K s_j into B S."""
+        plan, dofs, L, st = self.plan, self.setup.dofs, self.L, _stream(self.plan.device)
+        L.diffhe_buckling_apply(self.G, plan.cols, dofs.is_bc, blk["S"][j], blk["AS"][j], 1.0, plan.n, plan.W, self.d,
+                                self.Bp, self.Bg, st)
+        L.diffhe_ell_apply(self.vals, dofs.cols, blk["S"][j], blk["BS"][j], self._apart, dofs.n, dofs.W, self.Bp, self.Bv, st)
+
+    def _lobpcg_column(self, i: int, res, blk) -> None:
+        """w_i into the W slot with w_i^T r_i left in `dots` (the step entry with a zero coefficient: one pass for both),
+        then its operator columns."""
+        b, j = self.buf, self.p + i
+        self._outer += i == 0
+        self.L.diffhe_buckling_step(b["X"][i], res.x, b["R"][i], self.coef[i], self.rows, self.Bp, blk["S"][j],
+                                    self._apart, self.dots[i], _stream(self.plan.device))
+        self._lobpcg_apply(blk, j)
+
+    def _lobpcg_pre(self) -> None:
+        """rho of the block the inner solves just read, from their dots (the measure is known one iteration late).  A
+        column without a positive mu has nothing to measure (rho 0: it counts as done, as under "subspace"); for mu > 0 a dot
+        that is not positive cannot come from a solve with K and measures nothing: rho = inf."""
+        b = self.buf
+        if self._outer:
+            pos = self.mu > 0.0
+            inf = torch.full_like(self.mu, float("inf"))
+            measured = torch.where(self.dots > 0.0, self.dots.clamp_min(0.0).sqrt() / torch.where(pos, self.mu,
+                                                                                              torch.ones_like(self.mu)), inf)
+            torch.where(pos, measured, torch.zeros_like(self.mu), out=b["rho"])
+        else:
+            b["rho"].fill_(float("inf"))            # not measured yet
+            self.coef.zero_()                       # stays 0: the step entry then copies w_i
+        self._had_mu = self.mu > 0.0 if self._outer else None
+
+    def _lobpcg_post(self) -> None:
+        """mu of the new block.  A column that had no positive mu when its residual would have been measured but has one
+        now -- Ritz on [X | W] can turn up k positive values in one step from a start block that had none -- has NOT been
+        measured: its rho is inf until the next iteration measures it, so the run cannot stop on it."""
+        b = self.buf
+        torch.neg(b["theta"], out=self.mu)          # theta = -mu ascending: mu descending, the positive ones first
+        if self._had_mu is not None:
+            b["rho"].masked_fill_((self.mu > 0.0) & ~self._had_mu, float("inf"))
+        torch.maximum(self.neg_seen, (b["theta"] > 0.0).sum(dim=0), out=self.neg_seen)
+
     def _status(self) -> Tuple[int, int]:
         """The one host read of an outer iteration.  A wanted column without a positive Ritz value counts as done (its
         rho is 0), but keeps the iteration running for its first `MIN_OUTER_MISSING` rounds."""
@@ -274,7 +323,7 @@ class _BucklingRun(_BlockRun):
                           "with zero modes", RuntimeWarning)
         self.g0, self.lam1, self.mu1 = self.setup.dofs.g, self.setup.lam1, self.setup.mu1
         self.vals = self.hier = self.G = self.NY = self.NX = self._apart = self.eng = self.setup = None
-        self.coef = self.dots = self.neg_seen = self.info = None
+        self.coef = self.dots = self.neg_seen = self.info = self._had_mu = None
 
     def backward(self, glam: torch.Tensor, need_e: bool, need_s: bool):
         """(dL/dE, dL/dsigma0) in the shapes of E and sigma0 from the cotangent of lam.  dE: the strain-form gradient
@@ -393,13 +442,18 @@ class LinearBucklingSolver(nn.Module):
     inner_tol : relative residual of the inner solves d_i = K^-1 r_i; the stopping measure is as accurate as they are.
     seed : of the CPU generator the start block is drawn from.
     method ("auto" or "ell-jacobi"), amg, device : as on `ElasticFESolver`, also for the prestress solve (`solver.inner`).
+    iteration : "subspace" (default), the shifted block iteration of the module docstring, or "lobpcg": Rayleigh-Ritz on
+        span{X, K^-1 R, P} of the pencil (K_G, K), theta = -mu, which picks the wanted end of the spectrum by itself -- no
+        shift (`last_info.shifts` is 0) and fewer outer iterations ("LOBPCG"); the stopping measure, the
+        sign rule, the +inf handling and the gradients are the same.
     """
     _no_distributed = "diffhe: the diffhe.distributed helpers are not implemented for LinearBucklingSolver"
 
     def __init__(self, mesh, E=1.0, k: int = 4, *, nu: float = 0.3, plane: Optional[str] = None, fixed=None,
                  guard: int = 4, tol: float = 1e-8, max_iter: int = 200, inner_tol: float = 1e-3, seed: int = 0,
-                 method: str = "auto", amg: Optional[dict] = None, device=None):
+                 method: str = "auto", amg: Optional[dict] = None, device=None, iteration: str = "subspace"):
         super().__init__()
+        self.iteration = _check_iteration(iteration)
         _check_mesh(mesh, "diffhe: linear buckling needs a 2D or 3D mesh (a 1D bar carries no bending: Euler buckling of a "
                     "rod is not in the P1 bar model)",
                     "diffhe: linear buckling is implemented for P1 elements only (K_G = G (x) I_d is read from the node "

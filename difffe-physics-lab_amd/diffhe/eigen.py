@@ -19,6 +19,11 @@ columns of every sample (one host read per outer iteration); what is left above 
 `last_info.not_converged` and warned about.  The iteration itself is `_BlockRun`, which `diffhe.modal` runs on the dofs of
 an elastic body with a mass per sample; `_EigenRun` is the scalar problem on it.
 
+`iteration="lobpcg"` swaps the outer iteration for LOBPCG on the same inner solves and stopping measure: Rayleigh-Ritz on the
+basis [X | W | P] -- W the p inner solves of the residuals, P the previous step -- carried as one (3p, rows, Bp) buffer next
+to A S and M S, by the three passes of csrc/lobpcg.hip ("LOBPCG"); `last_info.iteration` and
+`last_info.basis_drops` report it.  The default, "subspace", is the iteration described above, unchanged.
+
 kappa layouts are the scalar ones of the base class, read as for a call whose f carries no batch: () one value,
 (m,) per element, (B,) or (B, 1) per sample, (B, m) per sample and element; `batch=B` forces the per-sample reading of
 a (B,) kappa when B == m.  Returns `lam` (B, k) ascending -- (k,) when neither kappa nor `batch=` carries a batch -- and
@@ -58,6 +63,15 @@ __all__ = ("EigenFESolver", "EigenInfo")
 
 MAX_BLOCK = 16          # kMaxP of csrc/eigen.hip
 JACOBI_SWEEPS = 30      # cap of the cyclic Jacobi sweeps (quadratic convergence: 6-9 are taken at p = 16)
+ITERATIONS = ("subspace", "lobpcg")
+LOBPCG_REFRESH = 8      # outer iterations between two fresh applications of the operators to X ("LOBPCG")
+LOBPCG_RETRIES = 2      # of those refreshes, the first so many also let a sample that gave up P try [X | W | P] again
+
+
+def _check_iteration(iteration) -> str:
+    if iteration not in ITERATIONS:
+        raise ValueError(f"Unknown iteration: {iteration!r} (expected 'subspace' or 'lobpcg')")
+    return iteration
 
 
 @dataclass
@@ -73,6 +87,8 @@ class EigenInfo:
     residual: Optional[torch.Tensor] = None     # (B, k) final rho per (sample, mode), on the CPU
     not_converged: int = 0              # (sample, mode) pairs above `tol` when the iteration ended
     gram_failures: int = 0              # samples whose Gram matrix was not positive definite in the last Ritz step
+    iteration: str = "subspace"         # the outer iteration that ran: "subspace" or "lobpcg"
+    basis_drops: int = 0                # "lobpcg": (outer iteration, sample) pairs whose Ritz step fell back to a smaller basis
     inner: SolveInfo = field(default_factory=SolveInfo)     # the inner solver's record of the set-up solve
 
 
@@ -159,11 +175,20 @@ class _BlockRun:
     # -- the iteration --------------------------------------------------------------------------------------------------
     def run(self, coeffs, x0, node_layout: bool):
         """coeffs: what `_setup` assembles from (kappa, or E and rho)."""
-        es, plan, L = self.es, self.plan, self.L
-        p, k, n, B, Bp = self.p, self.k, self.rows, self.B, self.Bp
-        info = self.Info(inner_tol=float(es.inner_tol), block=p)
+        es = self.es
+        info = self.Info(inner_tol=float(es.inner_tol), block=self.p, iteration=es.iteration)
         Y = self._start_block(x0, node_layout)
         self._setup(coeffs, Y, info, keep=x0 is not None and self.p == self.k)
+        if es.iteration == "lobpcg":
+            above, failed = self._iterate_lobpcg(info, Y)
+        else:
+            above, failed = self._iterate_subspace(info, Y)
+        return self._finish(info, above, failed, node_layout)
+
+    def _iterate_subspace(self, info, Y) -> Tuple[int, int]:
+        """Block inverse iteration: Rayleigh-Ritz on Y = X + D alone.  -> the last `_status()`."""
+        es, L = self.es, self.L
+        p, n, Bp = self.p, self.rows, self.Bp
         nblk = L.diffhe_eig_gram_blocks(n, Bp)
         nq = p * (p + 1) // 2
         self.buf = dict(X=self._new(p, n, Bp), AX=self._new(p, n, Bp), R=self._new(p, n, Bp), GA=self._new(nq, Bp),
@@ -186,6 +211,90 @@ class _BlockRun:
                 self._next_column(i, res, Y, AY)
             self._rayleigh_ritz(Y, AY)
             above, failed = self._status()
+        return above, failed
+
+    # -- LOBPCG: Ritz on span{X, W, P} ("LOBPCG") -----------------------------------------------------------
+    # A subclass supplies `_lobpcg_apply` (columns j of A S and B S from column j of S) and the free-row mask; the defaults
+    # below are those of the mass-weighted pencils, (A, M) with M diagonal: `_times_mass` and `_residual_norms`.
+    refresh = LOBPCG_REFRESH
+
+    def _lobpcg_apply(self, blk, j: int) -> None:
+        self._apply(blk["S"][j], blk["AS"][j])
+        self._times_mass(blk["S"][j], blk["BS"][j])
+
+    def _lobpcg_column(self, i: int, res, blk) -> None:
+        """w_i = the inner solve of column i of R into the W slot, with its operator columns."""
+        j = self.p + i
+        blk["S"][j].copy_(res.x)
+        self._lobpcg_apply(blk, j)
+
+    def _lobpcg_pre(self) -> None:
+        """Before the Ritz step of an outer iteration (what measures the block that is about to be replaced)."""
+
+    def _lobpcg_post(self) -> None:
+        """After the rotation: the stopping measure of the new block from R and theta."""
+        self._residual_norms()
+
+    def _lobpcg_ritz(self, cur, nxt, q: int) -> None:
+        """Gram -> Ritz -> rotate on the leading q columns of `cur` into `nxt`: X', P', R' = A X' - theta B X', theta."""
+        L, p, n, Bp, B, st = self.L, self.p, self.rows, self.Bp, self.B, _stream(self.plan.device)
+        b = self.buf
+        self._lobpcg_pre()
+        L.diffhe_lobpcg_gram(cur["S"], cur["AS"], cur["BS"], self._free_mask(), q, n, Bp, b["part"], b["GA"], b["GM"], st)
+        L.diffhe_lobpcg_ritz(b["GA"], b["GM"], q, p, Bp, JACOBI_SWEEPS, b["C"], b["theta"], b["used"], b["flag"], st)
+        L.diffhe_lobpcg_rotate(cur["S"], cur["AS"], cur["BS"], b["C"], b["theta"], q, p, n, Bp, nxt["S"], nxt["AS"],
+                               nxt["BS"], b["R"], st)
+        b["drops"] += ((b["used"][:B] < q) & (b["flag"][:B] == 0)).sum()
+        b["used"].masked_fill_(b["used"] == q, 0)      # what stays marks the samples that fell back: they keep to [X | W]
+        b["X"] = nxt["S"][:p]
+        self._lobpcg_post()
+
+    def _iterate_lobpcg(self, info, Y) -> Tuple[int, int]:
+        """The basis [X | W | P] as one (3p, rows, Bp) buffer next to A S and B S, in a ping-pong pair.  -> the last
+        `_status()`."""
+        es, L = self.es, self.L
+        p, n, Bp = self.p, self.rows, self.Bp
+        q3 = 3 * p
+        nq = q3 * (q3 + 1) // 2
+        part = max(L.diffhe_lobpcg_gram_blocks(n, Bp) * 2 * nq, L.diffhe_eig_gram_blocks(n, Bp) * 2 * p) * Bp
+        self.buf = b = dict(R=self._new(p, n, Bp), GA=self._new(nq, Bp), GM=self._new(nq, Bp), part=self._new(part),
+                            C=self._new(q3, p, Bp), theta=self._new(p, Bp), rho=self._new(p, Bp),
+                            flag=self._new(Bp, dtype=torch.int32),
+                            used=torch.zeros(Bp, dtype=torch.int32, device=self.plan.device),
+                            drops=torch.zeros((), dtype=torch.int64, device=self.plan.device))
+        cur, nxt = (dict(S=self._new(q3, n, Bp), AS=self._new(q3, n, Bp), BS=self._new(q3, n, Bp)) for _ in range(2))
+        cur["S"][:p] = Y
+        for j in range(p):
+            self._lobpcg_apply(cur, j)
+        self._lobpcg_ritz(cur, nxt, p)          # Ritz on the start block alone
+        cur, nxt = nxt, cur
+        above, failed = self._status()
+        q = 2 * p                               # no P yet: the first iteration (cold or warm) runs on [X | W]
+        while above and info.outer_iterations < es.max_iter:
+            info.outer_iterations += 1
+            for i in range(p):
+                res = self._inner_solve(b["R"][i])
+                info.inner_solves += 1
+                info.inner_iterations += res.iterations
+                info.inner_not_converged += res.not_converged
+                self._lobpcg_column(i, res, cur)
+            if info.outer_iterations % self.refresh == 0:       # drift control: A X and B X afresh, not rotated
+                for j in range(p):
+                    self._lobpcg_apply(cur, j)
+                if info.outer_iterations <= LOBPCG_RETRIES * self.refresh:
+                    b["used"].zero_()                           # ... and a sample that gave up P may try it again
+            self._lobpcg_ritz(cur, nxt, q)
+            cur, nxt = nxt, cur
+            q = q3
+            above, failed = self._status()
+        info.basis_drops = int(b["drops"])
+        b["X"] = b["X"].clone()                 # the p columns alone outlive the run, not the basis they sit in
+        return above, failed
+
+    def _finish(self, info, above: int, failed: int, node_layout: bool):
+        """Sign rule, `last_info`, the warnings and the returned layout, from the buffers either iteration leaves."""
+        es, plan, L, b = self.es, self.plan, self.L, self.buf
+        k, n, B, Bp = self.k, self.rows, self.B, self.Bp
         sgn = self._new(k, Bp)
         self._fix_sign(b["X"], sgn)
         info.not_converged, info.gram_failures = above, failed
@@ -297,6 +406,18 @@ class _EigenRun(_BlockRun):
         self.L.diffhe_eig_fix_sign(X, self.mass, self.k, self.plan.n, self.Bp, self.buf["part"], sgn,
                                    _stream(self.plan.device))
 
+    # -- what LOBPCG asks of the problem ------------------------------------------------------------------------------------
+    def _free_mask(self):
+        return self.plan.is_bc
+
+    def _times_mass(self, x: torch.Tensor, y: torch.Tensor) -> None:
+        torch.mul(x, self.mass[:, None], out=y)
+
+    def _residual_norms(self) -> None:
+        b = self.buf
+        self.L.diffhe_eig_residual(b["R"], b["theta"], self.mass, self.p, self.plan.n, self.Bp, b["part"], b["rho"],
+                                   _stream(self.plan.device))
+
     def _release(self) -> None:
         # what backward needs: the k columns and the engine (element tables, zero Dirichlet data); nothing else stays
         self.eng = self.state.eng
@@ -402,13 +523,17 @@ class EigenFESolver(nn.Module):
     seed : of the CPU generator the start block is drawn from.
     inner_tol : relative residual of the inner correction solves (their right-hand side is the current eigen-residual, so
         the absolute accuracy asked of them tightens as the iteration converges).
+    iteration : "subspace" (default), the block inverse iteration with Rayleigh-Ritz on the p new columns alone, or
+        "lobpcg", Rayleigh-Ritz on span{X, W, P} with W the same inner solves and P the previous step: fewer outer
+        iterations for the same inner solves each ("LOBPCG"); every other option keeps its meaning.
     solver_options : passed to the inner `DifferentiableFESolver` (2D) / `DifferentiableFESolver3D` (3D): device, method,
         mg, amg, operator, assembly, ...
     """
 
     def __init__(self, mesh, kappa=1.0, k: int = 4, *, guard: int = 4, tol: float = 1e-8, max_iter: int = 200,
-                 shift: float = 0.0, seed: int = 0, inner_tol: float = 1e-2, **solver_options):
+                 shift: float = 0.0, seed: int = 0, inner_tol: float = 1e-2, iteration: str = "subspace", **solver_options):
         super().__init__()
+        self.iteration = _check_iteration(iteration)
         if mesh.dim == 1:
             raise NotImplementedError("diffhe: eigenpairs on 1D meshes are not implemented (a tridiagonal pencil is "
                                       "dense-eigh territory)")

@@ -50,7 +50,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
-from .eigen import JACOBI_SWEEPS, MAX_BLOCK, EigenInfo, _BlockRun
+from .eigen import JACOBI_SWEEPS, MAX_BLOCK, EigenInfo, _BlockRun, _check_iteration
 from .elastic import _amg_options, _check_mesh, _select_hierarchy, _setup_of, lame_unit, parse_fixed
 from .plan import get_plan, padded_batch, _stream
 from .solver import (K_ELEM, K_SAMPLE_ELEM, SolveInfo, _Engine, _SOLVERS, _fake_grads, _kappa_grad, _kappa_mode,
@@ -171,6 +171,19 @@ class _ModalRun(_BlockRun):
 
     def _fix_sign(self, X, sgn) -> None:
         self.L.diffhe_modal_fix_sign(X, *self.mass_args, self.k, self.rows, self.Bp, self.buf["part"], sgn,
+                                     _stream(self.plan.device))
+
+    # -- what LOBPCG asks of the problem ------------------------------------------------------------------------------------
+    def _free_mask(self):
+        return self.setup.dofs.is_bc
+
+    def _times_mass(self, x: torch.Tensor, y: torch.Tensor) -> None:
+        n, d, Bp = self.plan.n, self.d, self.Bp
+        torch.mul(x.view(n, d, Bp), self.mass[:, None, :], out=y.view(n, d, Bp))
+
+    def _residual_norms(self) -> None:
+        b = self.buf
+        self.L.diffhe_modal_residual(b["R"], b["theta"], *self.mass_args, self.p, self.rows, self.Bp, b["part"], b["rho"],
                                      _stream(self.plan.device))
 
     def _release(self) -> None:
@@ -297,13 +310,16 @@ class ElasticEigenSolver(nn.Module):
     shift : sigma >= 0, the inner solves run on K + sigma M(rho); required > 0 for a body with no fixed dof.  The returned
         lambda exclude it.
     seed : of the CPU generator the start block is drawn from.  inner_tol : relative residual of the inner solves.
+    iteration : "subspace" (default) or "lobpcg", as on `EigenFESolver`.
     device, method ("auto" or "ell-jacobi"), amg : as on `ElasticFESolver`.
     """
 
     def __init__(self, mesh, E=1.0, rho=1.0, k: int = 4, *, nu: float = 0.3, plane: Optional[str] = None, fixed=None,
                  guard: int = 4, tol: float = 1e-8, max_iter: int = 200, shift: float = 0.0, seed: int = 0,
-                 inner_tol: float = 1e-2, device=None, method: str = "auto", amg: Optional[dict] = None, **options):
+                 inner_tol: float = 1e-2, device=None, method: str = "auto", amg: Optional[dict] = None,
+                 iteration: str = "subspace", **options):
         super().__init__()
+        self.iteration = _check_iteration(iteration)
         for name in ("reaction", "warm_start"):
             if name in options:
                 raise ValueError(f"{name}= is not an option of ElasticEigenSolver" + (" (use shift=)" if name == "reaction"

@@ -21,7 +21,8 @@ of void material (Neves, Rodrigues and Guedes 1995; Bendsoe and Sigmund 2003, se
 usual one: the stress that enters K_G is evaluated with the modulus rho^3 WITHOUT the floor E_min --
 `solver.inner.stress(u, E=rho^3)` handed to `forward(prestress=...)` -- so that void carries no prestress.
 
-    python examples/buckling_optimisation.py [NY] [steps]       the mesh is 8 NY x NY quads
+    python examples/buckling_optimisation.py [NY] [steps] [--lobpcg]     the mesh is 8 NY x NY quads; --lobpcg runs the
+                                                                         solver with iteration="lobpcg" (default: "subspace")
 """
 import os
 import sys
@@ -57,7 +58,7 @@ def at_volume(filt, z, vol, iters=50):
 
 
 def optimise(ny=4, steps=20, volumes=(0.5, 0.6, 0.7), k=3, e_min=1e-3, nu=0.3, lr=0.05, cap=1.2, penalty=10.0,
-             device="cuda", verbose=True):
+             device="cuda", verbose=True, iteration="subspace"):
     mesh, fixed, right = column(ny)
     B, m = len(volumes), mesh.n_elements
     filt = DensityFilter(mesh, 1.5 / ny, device=device)
@@ -71,7 +72,7 @@ def optimise(ny=4, steps=20, volumes=(0.5, 0.6, 0.7), k=3, e_min=1e-3, nu=0.3, l
     for it in range(steps + 1):                                # the last pass only evaluates
         rho = at_volume(filt, z, vol)
         solver = LinearBucklingSolver(mesh, e_min + (1.0 - e_min) * rho ** 3, k, nu=nu, plane="stress", fixed=fixed,
-                                      device=device)
+                                      device=device, iteration=iteration)
         u = solver.inner(load=load)                            # (B, n, 2): one load for every design
         sigma = solver.inner.stress(u, E=rho ** 3)             # no prestress in void: see the module docstring
         lam, phi = solver(prestress=sigma, x0=phi)             # (B, k), (B, k, n, 2): warm start from the last design
@@ -99,9 +100,10 @@ def optimise(ny=4, steps=20, volumes=(0.5, 0.6, 0.7), k=3, e_min=1e-3, nu=0.3, l
 
 
 if __name__ == "__main__":
-    ny = int(sys.argv[1]) if len(sys.argv) > 1 else 4
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-    rho, hist, dt = optimise(ny, steps)
+    args = [a for a in sys.argv[1:] if a != "--lobpcg"]
+    ny = int(args[0]) if len(args) > 0 else 4
+    steps = int(args[1]) if len(args) > 1 else 20
+    rho, hist, dt = optimise(ny, steps, iteration="lobpcg" if "--lobpcg" in sys.argv else "subspace")
     first, last = hist[0], hist[-1]
     print(f"{8 * ny}x{ny} quads, {len(first[0])} designs at once, {steps} Adam steps in {dt:.1f} s; lambda_1 "
           + ", ".join(f"{float(a):.6f} -> {float(b):.6f}" for a, b in zip(first[0], last[0]))
