@@ -81,9 +81,9 @@ __global__ __launch_bounds__(256) void robin_assemble_kernel(
       const double a = area[F];
       const double hv = h.v ? ((real || h.sb == 0) ? h.at(F, b) : 1.0) : 0.0;
       const double mv = hv * (a * (p == c ? 2.0 : 1.0) * inv_dd);
-      if (slot < 0)                                          // Dirichlet column: lifted with its value
-        load -= mv * g[fac[(i64)c * nF + F]];
-      else if (b < Bv)
+      if (slot < 0) {                                        // Dirichlet column: lifted with its value (padding: rhs stays 0)
+        if (real) load -= mv * g[fac[(i64)c * nF + F]];
+      } else if (b < Bv)
         vals[((i64)slot * n + i) * Bv + b] += mv;
       if (p == c && real) {                                  // once per (facet, row): the facet load
         const double uv = uinf.v ? uinf.at(F, b) : 0.0;

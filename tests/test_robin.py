@@ -325,6 +325,33 @@ def test_solution_and_every_gradient_against_the_dense_restatement(name):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("data_layout", ["both", "mixed"])
+def test_a_batch_above_one_wave_against_the_dense_restatement(data_layout):
+    """B = 70: two sample chunks in the assembly, a second trip of the lane loop in the gradient kernel (lanes 0 .. 5)."""
+    mesh, reaction, _ = case_mesh("jittered2d")
+    B = 70
+    fac = mesh.boundary_facets()
+    inputs = make_inputs(mesh, len(fac), B, "sample_elem", data_layout, seed=170)
+    w = inputs[-1]
+    ref_in = [t.clone().requires_grad_(True) for t in inputs[:-1]]
+    u_ref = dense_batch(mesh, fac, reaction, B, *ref_in)
+    g_ref = torch.autograd.grad(loss(u_ref, w), ref_in)
+    kappa, f, load, h, ui, q = _leaves(*inputs[:-1])
+    solver = _gpu_solver(mesh, kappa, reaction)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        u = solver(f, h=h, u_inf=ui, flux=q, load=load)
+    loss(u, w.to("cuda:0")).backward()
+    errs = {"u": rel_err(u.detach().cpu().numpy(), u_ref.detach().numpy())}
+    for nm, t, gr in zip(("dkappa", "df", "dload", "dh", "du_inf", "dq"), (kappa, f, load, h, ui, q), g_ref):
+        assert t.grad is not None and t.grad.shape == gr.shape, (data_layout, nm)
+        errs[nm] = rel_err(t.grad.cpu().numpy(), gr.numpy())
+    print(f"jittered2d B={B} data={data_layout}: " + " ".join(f"{k}={v:.1e}" for k, v in errs.items()))
+    for k, v in errs.items():
+        assert v < (RTOL_U if k == "u" else RTOL_GRAD), (data_layout, k, v)
+
+
+@pytest.mark.gpu
 def test_facet_subset_and_unbatched_call():
     mesh, reaction, _ = case_mesh("jittered2d")
     every = mesh.boundary_facets()
